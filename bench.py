@@ -20,8 +20,13 @@ reports how many ranks RCCL itself counts ("rccl_ranks", ncclCommCount through d
                    step ends with the RCCL all-gather of the result slices (ds_allgather).
 At N = 1, `--predict-ranks 8` also times the per-rank shard shape of an 8-GPU strong-scaling
 job and prints the implied speed-up T(full) / T(shard) ("shard_prediction"; profiles/rNN_shard_prediction.jsonl).
-At N = 1 the default line also carries "workloads": the other BASELINE configs (welch_h1_1024, fir_bank, csm,
-deconv), each timed the same way over a shorter region with a bounded CPU leg (`--no-workloads` skips them).
+With default arguments exactly --steps steps are timed.  At N = 1, `--workloads` adds "workloads" to the headline line:
+the other BASELINE configs (welch_h1_1024, fir_bank, csm, deconv), each timed the same way over --workload-steps steps
+with a bounded CPU leg; `--steady-steps S` times a second region of S steps behind the K ones ("steady_state").
+`--dump-outputs DIR` writes what the last timed step of --workload computed on rank 0 as DIR/<name>.npy (float32 /
+float64, complex results as <name>_real / <name>_imag, a fixed sample of results beyond a few MB; 64 MB at most;
+the Welch estimates without the DC bin when detrended, where they are 0 / 0): the inputs are seeded, so two builds can
+be compared output for output.
 
 Prints ONE JSON line on rank 0.
 """
@@ -71,14 +76,16 @@ def parse_args():
     ap.add_argument("--cpu-channels", type=int, default=64,
                     help="output channels of the bounded CPU-baseline sample")
     ap.add_argument("--detrend", type=int, default=1)
-    ap.add_argument("--no-workloads", action="store_true",
-                    help="default workload at N = 1: do not time the other BASELINE configs into \"workloads\"")
+    ap.add_argument("--workloads", action="store_true",
+                    help="default workload at N = 1: also time the other BASELINE configs into \"workloads\"")
     ap.add_argument("--preheat-ms", type=float, default=40.0,
                     help="untimed steps run for this long before the warm-up (clock ramp of an idle chip; 0 = none)")
-    ap.add_argument("--steady-steps", type=int, default=2000,
-                    help="steps of the second timed region behind the K steps of the command line -> \"steady_state\" (0 = none)")
+    ap.add_argument("--steady-steps", type=int, default=0,
+                    help="steps of a second timed region behind the K steps of the command line -> \"steady_state\" (0 = none)")
     ap.add_argument("--workload-steps", type=int, default=200,
                     help="timed steps of each entry of \"workloads\" (40 until round 4: 5 ms of timed region sits inside the clock ramp of an idle chip -- the 1024-sample Welch step read 0.130 ms there and 0.103 ms over 60 000 steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the results of --workload's last step as DIR/<name>.npy")
     return ap.parse_args()
 
 
@@ -241,7 +248,14 @@ def gather_result(ctx, rccl: bool, shard, d_local, d_all, bytes_per_rank: int):
 # Every workload maker builds the step of ONE rank: `shard` = None (the whole job, also each
 # rank's independent batch under weak scaling) or (rank, world) for that rank's part of the one
 # job under strong scaling.  Returns (step, units, algorithmic bytes or flops, bound, info,
-# cpu_baselines, bcast_ms, dominant kernel names); units / bytes are those of the WHOLE job.
+# cpu_baselines, bcast_ms, dominant kernel names, outputs); units / bytes are those of the WHOLE job;
+# outputs() -> {name: float32 / float64 array}, this rank's results of the last step (--dump-outputs).
+
+
+def _re_im(name: str, z: np.ndarray) -> dict:
+    return {name + "_real": np.ascontiguousarray(z.real), name + "_imag": np.ascontiguousarray(z.imag)}
+
+
 def welch_h1(args, ctx, dist, shard, rccl, W=4096):
     from dsptoolbox_amd import backend
     from dsptoolbox_amd._lib import DeviceBuffer
@@ -283,12 +297,23 @@ def welch_h1(args, ctx, dist, shard, rccl, W=4096):
                  + (", detrend" if args.detrend else ""),
         channels=n_cy, samples_per_channel=n, nfft=W, overlap_percent=50, frames=n_frames)
 
-    def verify():
+    def result():
         raw = d_res.to_array((B * n_loc * 12,), np.uint8)
         tf = raw[:B * n_loc * 8].view(np.complex64).reshape(B, n_loc)
         coh = raw[B * n_loc * 8:].view(np.float32).reshape(B, n_loc)
+        return tf, coh
+
+    def verify():
+        tf, coh = result()
         assert np.all(np.isfinite(tf[1:]))
         return tf, coh
+
+    def outputs():
+        # (bins, output channels): tf complex64, coherence float32.  With detrend the kernels set bin 0 of every frame to
+        # its exact value after mean removal, 0, so both spectra vanish there and the estimate is 0 / 0: bins 1 .. W/2 only
+        tf, coh = result()
+        lo = 1 if args.detrend else 0
+        return dict(_re_im("tf", tf[lo:]), coherence=coh[lo:])
 
     def cpu_reference_loop():
         from oracle import dsp_oracle as orc
@@ -323,7 +348,7 @@ def welch_h1(args, ctx, dist, shard, rccl, W=4096):
                            f"scipy.fft workers=-1), all {n_cy} channels, {reps} passes of {dt:.1f} s")
 
     return step, samples_per_step, alg_bytes, "hbm", info, (cpu_reference_loop, cpu_batched), bcast_ms, \
-        ("welch4096_main", "welch1024_main", "welch_yacc")
+        ("welch4096_main", "welch1024_main", "welch_yacc"), outputs
 
 
 def fir_bank(args, ctx, dist, shard, rccl):
@@ -372,7 +397,20 @@ def fir_bank(args, ctx, dist, shard, rccl):
                            f"({dt * len(bands) / max(1, b - a):.1f} s), scaled to all {K}; parity on each of them",
                     parity_rel_max_vs_gpu=err)
 
-    return step, n_ch * n, alg_bytes, "hbm", info, (cpu_baseline,), bcast_ms, ("fir",)
+    def outputs():
+        # the result is 4 GiB (bands, channels, samples): per band and channel, the first L samples (the filters'
+        # onset) and L samples from a seeded position; y_window_starts holds where each window begins
+        L = 8192
+        starts = np.zeros((k_loc, n_ch, 2), dtype=np.int64)
+        starts[..., 1] = np.random.default_rng(17).integers(L, n - L, size=(k_loc, n_ch))
+        win = np.empty((k_loc, n_ch, 2, L), dtype=np.float32)
+        for k in range(k_loc):
+            for c in range(n_ch):
+                for j in range(2):
+                    ctx.download(d_y.ptr + 4 * ((k * n_ch + c) * n + int(starts[k, c, j])), win[k, c, j])
+        return dict(y_windows=win, y_window_starts=starts.astype(np.float64))
+
+    return step, n_ch * n, alg_bytes, "hbm", info, (cpu_baseline,), bcast_ms, ("fir",), outputs
 
 
 def csm(args, ctx, dist, shard, rccl):
@@ -434,7 +472,10 @@ def csm(args, ctx, dist, shard, rccl):
                            f"mics, {reps} passes of {dt:.1f} s; the reference's 2080-pair loop takes ~100 s",
                     parity_rel_max_vs_gpu=orc.rel_max(got[lo - a:], ref[lo:b]))
 
-    return step, n_ch * n, alg, "hbm", info, (cpu_baseline,), None, ("stft", "csm_gemm")
+    def outputs():  # (bins, mics, mics) complex64
+        return _re_im("csm", d_c.to_array((b - a, n_ch, n_ch), np.complex64))
+
+    return step, n_ch * n, alg, "hbm", info, (cpu_baseline,), None, ("stft", "csm_gemm"), outputs
 
 
 def deconv(args, ctx, dist, shard, rccl):
@@ -504,7 +545,12 @@ def deconv(args, ctx, dist, shard, rccl):
                            f"in {dt:.2f} s; parity on every one of them",
                     parity_rel_max_vs_gpu=err)
 
-    return step, items_all * n_ch * n, alg_bytes, "hbm", info, (cpu_baseline,), bcast_ms, ("deconv",)
+    def outputs():
+        # the result is 64 MiB (items, channels, samples): the impulse responses of 256 items at seeded positions
+        pick = np.sort(np.random.default_rng(19).choice(items, size=min(items, 256), replace=False))
+        return dict(ir=d_o.to_array((items, n_ch, n), np.float32)[pick], ir_items=pick.astype(np.float64))
+
+    return step, items_all * n_ch * n, alg_bytes, "hbm", info, (cpu_baseline,), bcast_ms, ("deconv",), outputs
 
 
 def pmc_summary(workload: str, kernel_hints):
@@ -640,7 +686,7 @@ def measure(args, ctx, dist, workload: str, steps: int, warmup: int, strong: boo
     maker = dict(welch_h1=welch_h1, welch_h1_1024=lambda a, c, d, sh, r: welch_h1(a, c, d, sh, r, W=1024),
                  fir_bank=fir_bank, csm=csm, deconv=deconv)[workload]
     made = maker(args, ctx, dist, shard, rccl)
-    step, units, alg, bound, info, cpu_legs, bcast_ms, dominant = made
+    step, units, alg, bound, info, cpu_legs, bcast_ms, dominant, _ = made
     info["parallelism"] = (f"strong: one job sharded x{dist.world}" if strong
                            else f"weak: independent batch x{dist.world}")
     # Warm-up; its last step is bracketed kernel by kernel (HIP events on the library's stream) to
@@ -668,8 +714,8 @@ def measure(args, ctx, dist, workload: str, steps: int, warmup: int, strong: boo
         dom = max(prof_all, key=lambda k: prof_all[k][0])
     wall, ev_ms, prof = timed_steps(ctx, dist, step, steps, events, dom)
     wall = dist.max_over_ranks(wall)
-    # a second, longer region right behind the one the command line asks for: K = 20 steps are
-    # 2.5 ms and 5 event brackets; this one is --steady-steps steps and a quarter as many brackets
+    # on request, a second, longer region right behind the one the command line asks for: K = 20
+    # steps are 2.5 ms and 5 event brackets; this one is --steady-steps steps and a quarter as many brackets
     steady = None
     if args.steady_steps > 0 and getattr(args, "steady_now", True):
         s_wall, s_ev, s_prof = timed_steps(ctx, dist, step, args.steady_steps, events, dom)
@@ -820,9 +866,22 @@ def measure(args, ctx, dist, workload: str, steps: int, warmup: int, strong: boo
 
 WELCH_CEILING_MS = 0.0645  # VALU-only build of welch4096::k_y3, profiles/r04_welch_ceiling.txt
 
+DUMP_MAX_BYTES = 64 * 10**6
+
+
+def dump_outputs(dirname: str, outputs: dict):
+    """--dump-outputs: every array of `outputs` as DIR/<name>.npy."""
+    total = sum(a.nbytes for a in outputs.values())
+    assert total <= DUMP_MAX_BYTES, f"outputs of {total} bytes: more than --dump-outputs writes"
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in outputs.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(dirname, name + ".npy"), a)
+    print(f"[bench] --dump-outputs: {len(outputs)} arrays, {total} bytes in {dirname}", file=sys.stderr, flush=True)
+
 
 def workload_entry(args, ctx, dist, name: str):
-    """One entry of the default line's "workloads": the same measurement over a shorter timed region, the
+    """One entry of the headline line's "workloads" (--workloads): the same measurement over a shorter timed region, the
     fraction by SURVEY 8(d)'s own definition for that config, and a BOUNDED CPU leg with its parity."""
     import gc
     args.cpu_bounded = True
@@ -893,8 +952,11 @@ def short_estimate_entry():
 def main():
     args = parse_args()
     args.cpu_bounded = False
-    if args.gpus < 1:
-        print("[bench] --gpus must be >= 1", file=sys.stderr)
+    if args.gpus < 1 or args.steps < 1:
+        print("[bench] --gpus and --steps must be >= 1", file=sys.stderr)
+        sys.exit(2)
+    if args.dump_outputs and args.scaling == "strong" and args.gpus > 1:
+        print("[bench] --dump-outputs: rank 0 holds only its shard under --scaling strong", file=sys.stderr)
         sys.exit(2)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ and "RANK" not in os.environ:
         sys.exit(launch_ranks(args.gpus))  # nothing has touched the GPU in this process
@@ -910,6 +972,8 @@ def main():
     if dist.rank != 0:
         dist.finish()
         return
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, made[8]())
     if "roofline" not in out:
         print(json.dumps(out), flush=True)
         dist.finish()
@@ -949,7 +1013,7 @@ def main():
         out["cpu_baseline"]["host_cpus"] = os.cpu_count()
         if len(cpu_legs) > 1:
             out["cpu_baseline_batched"] = cpu_legs[1]()
-    if args.workload == "welch_h1" and dist.world == 1 and not args.no_workloads and not args.no_cpu_baseline:
+    if args.workload == "welch_h1" and dist.world == 1 and args.workloads and not args.no_cpu_baseline:
         # the other BASELINE configs, driver-timed inside the default line
         import gc
         del made, cpu_legs

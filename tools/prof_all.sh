@@ -23,9 +23,9 @@ for W in $WORKLOADS; do
   rocprofv3 --pmc SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_INST_LEVEL_LDS SQ_INSTS_SALU SQ_ACTIVE_INST_VMEM SQ_ACTIVE_INST_SCA SQ_WAIT_INST_LDS --output-format csv -d $OUT/pmc5 -- $CMD > $OUT/pmc5.log 2>&1
   rocprofv3 --pmc SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INST_LEVEL_VMEM SQ_LDS_CMD_FIFO_FULL SQ_LDS_DATA_FIFO_FULL SQ_WAVES SQ_IFETCH SQ_INSTS_SMEM --output-format csv -d $OUT/pmc6 -- $CMD > $OUT/pmc6.log 2>&1
   python3 tools/prof_summary.py $OUT > profiles/${TAG}_${W}_rocprofv3_summary.txt 2>&1
-  # kernel trace: the bench command itself -- the headline workload as the driver runs it (the default line WITH its
-  # "workloads" entries), the others as their own command
-  if [ "$W" = "welch_h1" ]; then TRACE="python3 bench.py"; else TRACE="python3 bench.py --workload $W"; fi
+  # kernel trace: the bench command itself -- the headline workload with its "workloads" entries, the others as their
+  # own command; both with the 2000-step steady-state region the committed summaries carry
+  if [ "$W" = "welch_h1" ]; then TRACE="python3 bench.py --workloads --steady-steps 2000"; else TRACE="python3 bench.py --workload $W --steady-steps 2000"; fi
   rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- $TRACE > $OUT/trace.log 2>&1
   python3 tools/prof_summary.py $OUT > $OUT/summary.txt 2>&1
   grep "^{\"metric" $OUT/trace.log > $OUT/bench_line.txt
