@@ -721,6 +721,56 @@ def _das_map(csm, h):
     return out.astype(np.float64)
 
 
+BF_METHODS = {"mvdr": 0, "functional": 1, "orthogonal": 2}  # ds_bf_eig_map's method codes
+
+
+def _bf_inputs(csm, h):
+    cs = np.ascontiguousarray(csm, dtype=np.complex128)
+    hs = np.ascontiguousarray(h, dtype=np.complex128)
+    assert cs.ndim == 3 and hs.ndim == 3 and cs.shape[1] == cs.shape[2], "csm must be (bins, C, C)"
+    assert hs.shape[0] == cs.shape[0] and hs.shape[1] == cs.shape[1], \
+        "steering vector must be (bins, C, grid points)"
+    return cs, hs
+
+
+def hermitian_eigh(a):
+    """numpy.linalg.eigh of a stack of Hermitian matrices on the device (ds_bf_eigh; the lower triangle is read):
+    a (F, C, C) -> w (F, C) ascending float64, v (F, C, C) complex128 with v[f][:, k] the eigenvector of w[f][k]."""
+    a = np.ascontiguousarray(a, dtype=np.complex128)
+    assert a.ndim == 3 and a.shape[1] == a.shape[2], "a must be (matrices, C, C)"
+    n_mat, n_ch = a.shape[0], a.shape[1]
+    w = np.empty((n_mat, n_ch), dtype=np.float64)
+    v = np.empty_like(a)
+    ctx = get_context()
+    ctx.check(ctx.lib.ds_bf_eigh(ctx.handle, _ptr(a), n_mat, n_ch, _ptr(w), _ptr(v)), "ds_bf_eigh")
+    return w, v
+
+
+def beamformer_eig_map(csm, h, method: str, gamma: float = 10.0, n_eig: int = 0) -> np.ndarray:
+    """MVDR, Functional or Orthogonal map per grid point and bin from one eigendecomposition of every bin's CSM
+    (ds_bf_eig_map, float64): csm (F, C, C) the selected bins, h (F, C, G) -> (G, F) float64."""
+    cs, hs = _bf_inputs(csm, h)
+    n_bins, n_ch, n_grid = hs.shape
+    out = np.empty((n_grid, n_bins), dtype=np.float64)
+    ctx = get_context()
+    ctx.check(ctx.lib.ds_bf_eig_map(ctx.handle, _ptr(cs), _ptr(hs), n_bins, n_ch, n_grid, BF_METHODS[method],
+                                    float(gamma), int(n_eig), _ptr(out)), "ds_bf_eig_map")
+    return out
+
+
+def beamformer_cleansc_map(csm, h, maximum_iterations: int, safety_factor: float,
+                           remove_csm_diagonal: bool) -> np.ndarray:
+    """CLEAN-SC clean map per grid point and bin (ds_bf_cleansc, float64): csm (F, C, C) the selected bins,
+    h (F, C, G) -> (G, F) float64."""
+    cs, hs = _bf_inputs(csm, h)
+    n_bins, n_ch, n_grid = hs.shape
+    out = np.empty((n_grid, n_bins), dtype=np.float64)
+    ctx = get_context()
+    ctx.check(ctx.lib.ds_bf_cleansc(ctx.handle, _ptr(cs), _ptr(hs), n_bins, n_ch, n_grid, int(maximum_iterations),
+                                    float(safety_factor), int(bool(remove_csm_diagonal)), _ptr(out)), "ds_bf_cleansc")
+    return out
+
+
 def _istft(stft, nfft: int, W: int, step: int, window, scale: float, frame_offset: int,
            n_frames_total: int):
     """Frame-wise irfft (length nfft, cropped to W) * scale * window, overlap-added at

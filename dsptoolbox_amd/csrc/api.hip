@@ -39,6 +39,7 @@
 #include "kernels_stft_any.hpp"
 #include "kernels_fir_stream.hpp"
 #include "kernels_freqz.hpp"
+#include "kernels_beamform.hpp"
 
 using namespace dsk;
 
@@ -2288,6 +2289,108 @@ extern "C" int ds_das_map(ds_ctx* c, const ds_c32* csm, const ds_c32* h, int n_b
     CHK(ds_upload(c, dh, h, nh * 8));
     CHK(ds_das_map_dev(c, (const ds_c32*)dc, (const ds_c32*)dh, n_bins, n_ch, n_grid, dm));
     return ds_download(c, map, dm, nm * 4);
+}
+
+// ---- MVDR / Functional / Orthogonal / CLEAN-SC beamformer maps (kernels_beamform.hpp) -----------
+static int bf_shape_ok(ds_ctx* c, const char* who, int n_bins, int n_ch, int n_grid) {
+    if (n_bins <= 0 || n_ch <= 0 || n_grid <= 0) return fail(c, DS_ERR_ARG, std::string(who) + ": bad shape");
+    if (n_ch > bf::MAX_CH)
+        return fail(c, DS_ERR_UNSUP, std::string(who) + ": more than 64 microphones is not built (one bin's C x C "
+                                     "complex128 matrix is held in LDS; C <= 64)");
+    if (n_bins > 65535) return fail(c, DS_ERR_UNSUP, std::string(who) + ": more than 65535 bins per call is not built yet");
+    return DS_OK;
+}
+
+extern "C" int ds_bf_eigh_dev(ds_ctx* c, const double* a, int n_bins, int n_ch, double* w, double* v) {
+    if (!c || !a || !w || !v) return fail(c, DS_ERR_ARG, "ds_bf_eigh: null argument");
+    CHK(bf_shape_ok(c, "ds_bf_eigh", n_bins, n_ch, 1));
+    bf::EighArgs ea{(const double2*)a, n_ch, w, (double2*)v};
+    return launch(c, "bf_eigh", bf::k_bf_eigh, dim3(n_bins), bf::THREADS, 0, ea);
+}
+
+extern "C" int ds_bf_eigh(ds_ctx* c, const double* a, int n_bins, int n_ch, double* w, double* v) {
+    if (!c || !a || !w || !v) return fail(c, DS_ERR_ARG, "ds_bf_eigh: null argument");
+    CHK(bf_shape_ok(c, "ds_bf_eigh", n_bins, n_ch, 1));
+    const size_t nm = (size_t)n_bins * n_ch * n_ch, nw = (size_t)n_bins * n_ch;
+    CHK(reserve(c, &c->io, &c->io_bytes, 2 * Carver::pad(nm * 16) + Carver::pad(nw * 8)));
+    Carver cv(c->io);
+    double2* da = cv.take<double2>(nm);
+    double2* dv = cv.take<double2>(nm);
+    double* dw = cv.take<double>(nw);
+    CHK(ds_upload(c, da, a, nm * 16));
+    CHK(ds_bf_eigh_dev(c, (const double*)da, n_bins, n_ch, dw, (double*)dv));
+    CHK(ds_download(c, w, dw, nw * 8));
+    return ds_download(c, v, dv, nm * 16);
+}
+
+extern "C" int ds_bf_eig_map_dev(ds_ctx* c, const double* csm, const double* h, int n_bins, int n_ch, int n_grid,
+                                 int method, double gamma, int n_eig, double* map) {
+    if (!c || !csm || !h || !map) return fail(c, DS_ERR_ARG, "ds_bf_eig_map: null argument");
+    CHK(bf_shape_ok(c, "ds_bf_eig_map", n_bins, n_ch, n_grid));
+    if (method != bf::MVDR && method != bf::FUNCTIONAL && method != bf::ORTHOGONAL)
+        return fail(c, DS_ERR_ARG, "ds_bf_eig_map: method must be 0 (MVDR), 1 (Functional) or 2 (Orthogonal)");
+    if (method == bf::ORTHOGONAL && (n_eig <= 0 || n_eig > n_ch))
+        return fail(c, DS_ERR_ARG, "ds_bf_eig_map: n_eig must be in [1, n_ch]");
+    if (method != bf::ORTHOGONAL) n_eig = 0;
+    const size_t nm = (size_t)n_bins * n_ch * n_ch, nw = (size_t)n_bins * n_ch, np = (size_t)n_bins * n_eig * n_grid;
+    CHK(reserve(c, &c->ws, &c->ws_bytes, Carver::pad(nm * 16) + Carver::pad(nw * 8) + Carver::pad(np * 8) + 256));
+    Carver cv(c->ws);
+    double2* dv = cv.take<double2>(nm);
+    double* dw = cv.take<double>(nw);
+    double* dp = np ? cv.take<double>(np) : nullptr;
+    CHK(ds_bf_eigh_dev(c, csm, n_bins, n_ch, dw, (double*)dv));
+    bf::ProjArgs pa{dw, dv, (const double2*)h, n_ch, n_grid, n_bins, method, n_eig, gamma, map, dp};
+    CHK(launch(c, "bf_project", bf::k_bf_project, dim3((n_grid + bf::THREADS - 1) / bf::THREADS, n_bins),
+               bf::THREADS, 0, pa));
+    if (method == bf::ORTHOGONAL) CHK(launch(c, "bf_orth_pick", bf::k_bf_orth_pick, dim3(n_bins), bf::THREADS, 0, pa));
+    return DS_OK;
+}
+
+extern "C" int ds_bf_eig_map(ds_ctx* c, const double* csm, const double* h, int n_bins, int n_ch, int n_grid,
+                             int method, double gamma, int n_eig, double* map) {
+    if (!c || !csm || !h || !map) return fail(c, DS_ERR_ARG, "ds_bf_eig_map: null argument");
+    CHK(bf_shape_ok(c, "ds_bf_eig_map", n_bins, n_ch, n_grid));
+    const size_t nc = (size_t)n_bins * n_ch * n_ch, nh = (size_t)n_bins * n_ch * n_grid, nm = (size_t)n_grid * n_bins;
+    CHK(reserve(c, &c->io, &c->io_bytes, Carver::pad(nc * 16) + Carver::pad(nh * 16) + Carver::pad(nm * 8)));
+    Carver cv(c->io);
+    double2* dc = cv.take<double2>(nc);
+    double2* dh = cv.take<double2>(nh);
+    double* dm = cv.take<double>(nm);
+    CHK(ds_upload(c, dc, csm, nc * 16));
+    CHK(ds_upload(c, dh, h, nh * 16));
+    CHK(ds_bf_eig_map_dev(c, (const double*)dc, (const double*)dh, n_bins, n_ch, n_grid, method, gamma, n_eig, dm));
+    return ds_download(c, map, dm, nm * 8);
+}
+
+extern "C" int ds_bf_cleansc_dev(ds_ctx* c, const double* csm, const double* h, int n_bins, int n_ch, int n_grid,
+                                 int max_iter, double safety, int remove_diagonal, double* map) {
+    if (!c || !csm || !h || !map) return fail(c, DS_ERR_ARG, "ds_bf_cleansc: null argument");
+    CHK(bf_shape_ok(c, "ds_bf_cleansc", n_bins, n_ch, n_grid));
+    if (max_iter <= 0) return fail(c, DS_ERR_ARG, "ds_bf_cleansc: max_iter must be positive");
+    if (!(safety > 0.0 && safety <= 1.0)) return fail(c, DS_ERR_ARG, "ds_bf_cleansc: safety factor must be in (0, 1]");
+    CHK(reserve(c, &c->ws, &c->ws_bytes, Carver::pad((size_t)n_bins * n_grid * 8)));
+    Carver cv(c->ws);
+    double* dr = cv.take<double>((size_t)n_bins * n_grid);
+    bf::CleanArgs ca{(const double2*)csm, (const double2*)h, n_ch, n_grid, n_bins, max_iter, remove_diagonal ? 1 : 0,
+                     safety, dr, map};
+    return launch(c, "bf_cleansc", bf::k_bf_cleansc, dim3(n_bins), bf::THREADS, 0, ca);
+}
+
+extern "C" int ds_bf_cleansc(ds_ctx* c, const double* csm, const double* h, int n_bins, int n_ch, int n_grid,
+                             int max_iter, double safety, int remove_diagonal, double* map) {
+    if (!c || !csm || !h || !map) return fail(c, DS_ERR_ARG, "ds_bf_cleansc: null argument");
+    CHK(bf_shape_ok(c, "ds_bf_cleansc", n_bins, n_ch, n_grid));
+    const size_t nc = (size_t)n_bins * n_ch * n_ch, nh = (size_t)n_bins * n_ch * n_grid, nm = (size_t)n_grid * n_bins;
+    CHK(reserve(c, &c->io, &c->io_bytes, Carver::pad(nc * 16) + Carver::pad(nh * 16) + Carver::pad(nm * 8)));
+    Carver cv(c->io);
+    double2* dc = cv.take<double2>(nc);
+    double2* dh = cv.take<double2>(nh);
+    double* dm = cv.take<double>(nm);
+    CHK(ds_upload(c, dc, csm, nc * 16));
+    CHK(ds_upload(c, dh, h, nh * 16));
+    CHK(ds_bf_cleansc_dev(c, (const double*)dc, (const double*)dh, n_bins, n_ch, n_grid, max_iter, safety,
+                          remove_diagonal, dm));
+    return ds_download(c, map, dm, nm * 8);
 }
 
 // ---- four-step FFT for 2^15 .. 2^24 points (kernels_bigfft.hpp) -------------------

@@ -243,6 +243,32 @@ int ds_das_map(ds_ctx* ctx, const ds_c32* csm, const ds_c32* h, int n_bins, int 
 int ds_csm_das_prepare_dev(ds_ctx* ctx, const ds_c32* csm_dev, int n_bins, int n_ch, double scale,
                            int zero_diagonal, ds_c32* out_dev);
 
+/* ---- MVDR, Functional, Orthogonal and CLEAN-SC beamformer maps on the CSM, float64 throughout:
+ * replace the per-bin / per-grid-point loops of BeamformerMVDR (beamforming/beamforming.py:1276-1304),
+ * BeamformerFunctional (:1177-1210), BeamformerOrthogonal (:1079-1114) and BeamformerCleanSC (:959-997
+ * with _clean_sc_deconvolve, beamforming/_beamforming.py:194-297).  csm [f][i][j] complex128 (the
+ * selected bins, n_ch x n_ch each), h [f][c][g] complex128 (the steering vectors), map [g][f] float64
+ * (before the Simpson integration over f).  n_ch <= 64: one bin's matrix is held in LDS; larger
+ * arrays return DS_ERR_UNSUP.
+ * ds_bf_eigh: Hermitian eigendecomposition of every bin's matrix (its lower triangle, as numpy's eigh):
+ * w [f][k] ascending, v [f][i][k] (column k = eigenvector of w[f][k]).  Complex Jacobi.
+ * ds_bf_eig_map: method 0 MVDR map = 1 / sum_k |v_k^H h|^2 / w_k (gamma, n_eig ignored);
+ * method 1 Functional map = (q / n)^gamma n with q = sum_k |v_k^H h|^2 sign(w_k)|w_k|^(1/gamma),
+ * n = h^H h; method 2 Orthogonal: for e = 0 .. n_eig - 1 (largest eigenvalue first) the grid point i
+ * that maximises |v^H h|^2 gets map[i] = |v^H h_i|^2 w (later picks overwrite), every other point 0.
+ * ds_bf_cleansc: the CLEAN-SC clean map, at most max_iter iterations of loop gain safety in (0, 1],
+ * remove_diagonal != 0 zeroes the CSM's and every source's diagonal.                              */
+int ds_bf_eigh_dev(ds_ctx* ctx, const double* a_dev, int n_bins, int n_ch, double* w_dev, double* v_dev);
+int ds_bf_eigh(ds_ctx* ctx, const double* a, int n_bins, int n_ch, double* w, double* v);
+int ds_bf_eig_map_dev(ds_ctx* ctx, const double* csm_dev, const double* h_dev, int n_bins, int n_ch,
+                      int n_grid, int method, double gamma, int n_eig, double* map_dev);
+int ds_bf_eig_map(ds_ctx* ctx, const double* csm, const double* h, int n_bins, int n_ch, int n_grid,
+                  int method, double gamma, int n_eig, double* map);
+int ds_bf_cleansc_dev(ds_ctx* ctx, const double* csm_dev, const double* h_dev, int n_bins, int n_ch,
+                      int n_grid, int max_iter, double safety, int remove_diagonal, double* map_dev);
+int ds_bf_cleansc(ds_ctx* ctx, const double* csm, const double* h, int n_bins, int n_ch, int n_grid,
+                  int max_iter, double safety, int remove_diagonal, double* map);
+
 /* ---- inverse STFT: replaces transforms.istft, transforms/transforms.py:444-586
  * (np.fft.irfft of every frame + _reconstruct_framed_signal,
  * standard/_framed_signal_representation.py:70-137: windowed overlap-add divided by
