@@ -24,6 +24,7 @@ NO_SCRATCH = [
     "stft1k11k_stft_wave", "stft4k6k_stft", "stft4k7k_istft", "stft4k10k_stft_dif", "welch1k3k_y", "welch1k3k_x", "welch8k3k_y", "welch8k3k_x", "welch16k3k_y", "welch16k3k_x", "welchl4k_yc", "welchl4k_xc", "stftl10k_stft_cls",
     "fir16k5k_firILb1E", "fir4k5k_firILi1E", "fir4k5k_firILi2E", "fir4k6k_fir3ILi0E", "deconv8k10k_deconv_p", "k_csm_gemm64",
     "k_bf_eigh", "k_bf_project", "k_bf_cleansc",
+    "k_iir_group", "k_iir_carry", "k_iir_apply",
 ]
 
 

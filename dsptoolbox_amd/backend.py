@@ -1203,3 +1203,152 @@ def _filtfilt_fir(b, x):
     y, _ = _lfilter_fir(b, [1.0], ext, zi * ext[:1])
     y, _ = _lfilter_fir(b, [1.0], y[::-1], zi * y[-1:])
     return y[::-1][edge:-edge]
+
+
+# ---- IIR filtering: cascades of second-order sections (ds_iir_sos, csrc/kernels_iir.hpp) ----------------------------
+IIR_MAX_SECTIONS = 32  # one cascade on the device (DS_ERR_UNSUP above)
+_IDENTITY_SECTION = np.array([1.0, 0.0, 0.0, 1.0, 0.0, 0.0])
+
+
+def _sos_stack(sos_list) -> np.ndarray:
+    """K filters' (n_k, 6) sections -> [K][max n_k][6] float64; shorter cascades are padded with the identity section,
+    which passes its input through exactly and keeps a zero state."""
+    n_max = max(np.atleast_2d(s).shape[0] for s in sos_list)
+    out = np.tile(_IDENTITY_SECTION, (len(sos_list), n_max, 1))
+    for k, s in enumerate(sos_list):
+        s = np.atleast_2d(np.asarray(s, dtype=np.float64))
+        out[k, :s.shape[0]] = s
+    return out
+
+
+def iir_sos_filter(x, sos_list, mode: int, zi=None):
+    """sosfilt of x (N, C) float64 through K cascades of second-order sections (the recursion in float64 on the
+    device).  Parallel -> (K, N, C); Sequential / Summed -> (N, C).  zi (K, n_max, 2, C) (sosfilt's per-filter
+    layout, identity-padded sections included) gives the initial state; then (y, zf) is returned, zf in the same
+    layout.  A Sequential bank longer than one device cascade runs as consecutive cascades."""
+    xa = np.ascontiguousarray(np.asarray(x, dtype=np.float64))
+    if xa.ndim == 1:
+        xa = xa[:, None]
+    if mode == DS_FB_SEQUENTIAL:
+        sections = np.concatenate([np.atleast_2d(np.asarray(s, dtype=np.float64)) for s in sos_list])
+        if zi is None and len(sections) > IIR_MAX_SECTIONS:
+            y = xa
+            for i0 in range(0, len(sections), IIR_MAX_SECTIONS):
+                y = iir_sos_filter(y, [sections[i0:i0 + IIR_MAX_SECTIONS]], DS_FB_PARALLEL)[0]
+            return y
+        sos_list = [sections] if zi is None else sos_list
+    sos = _sos_stack(sos_list)
+    k, n_sec = sos.shape[0], sos.shape[1]
+    n, n_ch = xa.shape
+    y = np.empty(((k if mode == DS_FB_PARALLEL else 1), n, n_ch), dtype=np.float64)
+    zf = None
+    if zi is not None:
+        zi = np.ascontiguousarray(zi, dtype=np.float64)
+        assert zi.shape == (k, n_sec, 2, n_ch), "zi must be (filters, sections, 2, channels)"
+        zf = np.empty_like(zi)
+    ctx = get_context()
+    ctx.check(ctx.lib.ds_iir_sos(ctx.handle, _ptr(xa), n_ch, n, _ptr(sos), k, n_sec,
+                                 None if zi is None else _ptr(zi), int(mode), _ptr(y),
+                                 None if zf is None else _ptr(zf)), "ds_iir_sos")
+    y = y if mode == DS_FB_PARALLEL else y[0]
+    return y if zi is None else (y, zf)
+
+
+def iir_sos_filter_device(x_dev: DevicePlanar, sos_list, mode: int):
+    """iir_sos_filter over device-resident samples (ds_iir_sos_dev, no state): Parallel -> a list of K DevicePlanar
+    (slices of ONE output buffer), Sequential / Summed -> one DevicePlanar.  Nothing comes down."""
+    if mode == DS_FB_SEQUENTIAL:
+        sections = np.concatenate([np.atleast_2d(np.asarray(s, dtype=np.float64)) for s in sos_list])
+        if len(sections) > IIR_MAX_SECTIONS:
+            y = x_dev
+            for i0 in range(0, len(sections), IIR_MAX_SECTIONS):
+                y = iir_sos_filter_device(y, [sections[i0:i0 + IIR_MAX_SECTIONS]], DS_FB_PARALLEL)[0]
+            return y
+        sos_list = [sections]
+    sos = _sos_stack(sos_list)
+    k, n_sec = sos.shape[0], sos.shape[1]
+    ctx = x_dev.ctx
+    n, n_ch = x_dev.n_samples, x_dev.n_ch
+    n_out = k if mode == DS_FB_PARALLEL else 1
+    d_y = DeviceBuffer(ctx, n_out * n_ch * n * 4)
+    try:
+        ctx.check(ctx.lib.ds_iir_sos_dev(ctx.handle, C.c_void_p(x_dev.ptr), n_ch, x_dev.ld, n, _ptr(sos), k, n_sec, None,
+                                         int(mode), C.c_void_p(d_y.ptr), n, None), "ds_iir_sos_dev")
+    except BaseException:
+        d_y.free()
+        raise
+    outs = [DevicePlanar(d_y, n_ch, n, n, 4 * i * n_ch * n) for i in range(n_out)]
+    return outs if mode == DS_FB_PARALLEL else outs[0]
+
+
+def _ba_section(b, a) -> np.ndarray:
+    """A ba filter of order <= 2 as one second-order section (lfilter normalises by a[0] as the section does)."""
+    b = np.asarray(b, dtype=np.float64)
+    a = np.asarray(a, dtype=np.float64)
+    if max(len(b), len(a)) > 3:
+        raise NotImplementedError("IIR ba filters of order > 2 are not run on the device (one second-order section "
+                                  "at most); use FilterCoefficientsType.Sos or Zpk for higher orders")
+    sec = np.zeros(6)
+    sec[:len(b)] = b
+    sec[3:3 + len(a)] = a
+    return sec[None, :]
+
+
+def _sosfilt(sos, x, zi=None):
+    """scipy.signal.sosfilt(sos, x, axis=0[, zi]) for x (N, C) real on the device; zi (K, 2, C)."""
+    if zi is None:
+        return iir_sos_filter(x, [sos], DS_FB_PARALLEL)[0]
+    y, zf = iir_sos_filter(x, [sos], DS_FB_PARALLEL, zi=np.asarray(zi)[None])
+    return y[0], zf[0]
+
+
+def _lfilter_iir(b, a, x, zi=None):
+    """scipy.signal.lfilter(b, a, x, axis=0[, zi]) of an IIR filter of order <= 2 on the device; zi (order, C)."""
+    sec = _ba_section(b, a)
+    if zi is None:
+        return _sosfilt(sec, x)
+    zi = np.asarray(zi, dtype=np.float64)
+    order = zi.shape[0]
+    z2 = np.zeros((1, 2, zi.shape[1]))
+    z2[0, :order] = zi
+    y, zf = _sosfilt(sec, x, z2)
+    return y, zf[0, :order]
+
+
+def _odd_extension(x, padlen: int):
+    if padlen == 0:
+        return x
+    left = 2 * x[:1] - x[padlen:0:-1]
+    right = 2 * x[-1:] - x[-2:-(padlen + 2):-1]
+    return np.concatenate([left, x, right])
+
+
+def _filtfilt_sections(sos, x, padlen: int):
+    """Forward-backward filtering as scipy's sosfiltfilt / filtfilt (padtype 'odd'): the odd extension by padlen
+    samples, the steady-state initial state scaled by the first sample of each pass, two device calls -- the second
+    over the reversed signal."""
+    x = np.asarray(x, dtype=np.float64)
+    if x.ndim == 1:
+        x = x[:, None]
+    if x.shape[0] <= padlen:
+        raise ValueError(f"The length of the input vector x must be greater than padlen, which is {padlen}.")
+    from scipy.signal import sosfilt_zi
+    zi = sosfilt_zi(sos)[:, :, None]  # (K, 2, 1)
+    ext = _odd_extension(x, padlen)
+    y, _ = _sosfilt(sos, ext, zi * ext[0][None, None, :])
+    yr = np.ascontiguousarray(y[::-1])
+    y, _ = _sosfilt(sos, yr, zi * yr[0][None, None, :])
+    y = y[::-1]
+    return np.ascontiguousarray(y[padlen:y.shape[0] - padlen] if padlen > 0 else y)
+
+
+def _sosfiltfilt(sos, x):
+    """scipy.signal.sosfiltfilt(sos, x, axis=0) on the device."""
+    sos = np.atleast_2d(np.asarray(sos, dtype=np.float64))
+    n_first = min(int((sos[:, 2] == 0).sum()), int((sos[:, 5] == 0).sum()))
+    return _filtfilt_sections(sos, x, 3 * (2 * len(sos) + 1 - n_first))
+
+
+def _filtfilt_iir(b, a, x):
+    """scipy.signal.filtfilt(b, a, x, axis=0) of an IIR filter of order <= 2 on the device."""
+    return _filtfilt_sections(_ba_section(b, a), x, 3 * max(len(a), len(b)))

@@ -1,11 +1,11 @@
-"""Filter: FIR part of dsptoolbox/classes/filter.py (fir_filter :189-235,
-from_ba :237-260, ba setter :485-529, is_fir :460-470, filter_signal :648-743,
-get_ir :818-860, get_transfer_function :862-900).
-FIR filtering runs on the device as FFT block convolution
-(dsptoolbox_amd.backend.fir_filter_bank), including filter state (zi, initialize_zi
-:331-353) and zero-phase filtering (two device convolutions).  IIR / SOS / zpk
-filters are recursive and outside the FFT-batchable hot path; they raise
-NotImplementedError."""
+"""Filter (API mirror of dsptoolbox/classes/filter.py: constructor :51-89, iir_filter :91-141, biquad :143-187,
+fir_filter :189-235, from_ba / from_sos / from_zpk :237-300, initialize_zi :331-353, ba / sos / zpk setters
+:485-600, filter_signal :648-743, get_ir :818-860, get_transfer_function :862-900, get_coefficients :927-966).
+FIR filtering runs on the device as FFT block convolution (dsptoolbox_amd.backend.fir_filter_bank), IIR
+filtering -- sos, zpk (converted to sos) and ba filters of order <= 2 -- as a time-parallel float64 recursion
+(backend.iir_sos_filter), both with filter state (zi) and zero-phase filtering.  Design and conversion stay
+scipy on the host.  A recursive filter with a pole on or outside the unit circle raises NotImplementedError
+when it is built: the device's carry over time holds only for stable filters."""
 
 from copy import deepcopy
 from warnings import warn
@@ -14,8 +14,66 @@ import numpy as np
 import scipy.signal as sig
 
 from .. import backend
-from ..standard.enums import FilterCoefficientsType, FilterPassType, Window
+from ..standard.enums import BiquadEqType, FilterCoefficientsType, FilterPassType, IirDesignMethod, Window
 from .signal import Signal
+
+
+def _check_stable(poles, what: str):
+    poles = np.atleast_1d(poles)
+    if poles.size and np.max(np.abs(poles)) >= 1.0:
+        raise NotImplementedError(
+            f"{what} has a pole of magnitude {np.max(np.abs(poles)):.6g} >= 1: only stable recursive filters are run "
+            "on the device (the time-parallel carry of the recursion needs every pole inside the unit circle)")
+
+
+def _biquad_coefficients(eq_type: BiquadEqType, fs_hz: int, frequency_hz: float, gain_db: float, q: float):
+    """b, a of one biquad after the Audio EQ Cookbook (R. Bristow-Johnson; W3C note of 2021-06-08) with w0 = 2 pi f /
+    fs and alpha = sin(w0) / 2Q.  Peaking and the shelves take A = 10^(gain / 40); every other type is scaled in
+    its numerator by the linear gain 10^(gain / 20).  The first-order types use K = cot(w0 / 2) (bilinear
+    transform of the analog prototype); Inverter is the gain alone, b = [g, 0, 0], a = [1, 0, 0]."""
+    shelf_or_peak = eq_type in (BiquadEqType.Peaking, BiquadEqType.Lowshelf, BiquadEqType.Highshelf)
+    A = 10 ** (gain_db / 40) if shelf_or_peak else 10 ** (gain_db / 20)
+    w0 = 2.0 * np.pi * frequency_hz / fs_hz
+    sw, cw = np.sin(w0), np.cos(w0)
+    alpha = sw / (2.0 * q)
+    # the common denominator of the second-order cookbook filters
+    den = [1 + alpha, -2 * cw, 1 - alpha]
+    match eq_type:
+        case BiquadEqType.Lowpass:
+            num = [(1 - cw) / 2, 1 - cw, (1 - cw) / 2]
+        case BiquadEqType.Highpass:
+            num = [(1 + cw) / 2, -(1 + cw), (1 + cw) / 2]
+        case BiquadEqType.BandpassSkirt:  # constant skirt gain, peak gain Q
+            num = [sw / 2, 0.0, -sw / 2]
+        case BiquadEqType.BandpassPeak:  # constant 0 dB peak gain
+            num = [alpha, 0.0, -alpha]
+        case BiquadEqType.Notch:
+            num = [1.0, -2 * cw, 1.0]
+        case BiquadEqType.Allpass:
+            num = [1 - alpha, -2 * cw, 1 + alpha]
+        case BiquadEqType.Peaking:
+            num = [1 + alpha * A, -2 * cw, 1 - alpha * A]
+            den = [1 + alpha / A, -2 * cw, 1 - alpha / A]
+            A = 1.0  # (the gain is in the pole / zero placement)
+        case BiquadEqType.Lowshelf | BiquadEqType.Highshelf:
+            s = 1.0 if eq_type == BiquadEqType.Lowshelf else -1.0  # the high shelf is the low shelf at -cos(w0)
+            r = 2 * np.sqrt(A) * alpha
+            num = [A * ((A + 1) - s * (A - 1) * cw + r), s * 2 * A * ((A - 1) - s * (A + 1) * cw),
+                   A * ((A + 1) - s * (A - 1) * cw - r)]
+            den = [(A + 1) + s * (A - 1) * cw + r, -s * 2 * ((A - 1) + s * (A + 1) * cw),
+                   (A + 1) + s * (A - 1) * cw - r]
+            A = 1.0
+        case BiquadEqType.LowpassFirstOrder | BiquadEqType.HighpassFirstOrder | BiquadEqType.AllpassFirstOrder:
+            k = 1.0 / np.tan(w0 / 2.0)
+            num = {BiquadEqType.LowpassFirstOrder: [1.0, 1.0, 0.0],
+                   BiquadEqType.HighpassFirstOrder: [k, -k, 0.0],
+                   BiquadEqType.AllpassFirstOrder: [1.0 - k, 1.0 + k, 0.0]}[eq_type]
+            den = [1.0 + k, 1.0 - k, 0.0]
+        case BiquadEqType.Inverter:
+            num, den = [1.0, 0.0, 0.0], [1.0, 0.0, 0.0]
+        case _:
+            raise Exception("eq_type not supported")
+    return np.asarray(num, dtype=np.float64) * A, np.asarray(den, dtype=np.float64)
 
 
 class Filter:
@@ -26,12 +84,37 @@ class Filter:
                 ^ (FilterCoefficientsType.Sos in filter_coefficients)
                 ^ (FilterCoefficientsType.Zpk in filter_coefficients)), (
             "Only (and at least) one type of filter coefficients should be passed to create a filter")
-        if FilterCoefficientsType.Ba not in filter_coefficients:
-            raise NotImplementedError(
-                "only ba (FIR) coefficients are supported on the GPU path; SOS / zpk filters are "
-                "recursive and outside the FFT-batchable hot path")
-        b, a = filter_coefficients[FilterCoefficientsType.Ba]
-        self.ba = [np.atleast_1d(b), np.atleast_1d(a)]
+        if FilterCoefficientsType.Zpk in filter_coefficients:
+            self.zpk = filter_coefficients[FilterCoefficientsType.Zpk]
+            _check_stable(self.zpk[1], "the zpk filter")
+            self.sos = sig.zpk2sos(*self.zpk, analog=False)
+        elif FilterCoefficientsType.Sos in filter_coefficients:
+            self.sos = filter_coefficients[FilterCoefficientsType.Sos]
+            _check_stable(np.concatenate([np.roots(sec[3:]) for sec in self.sos]), "the sos filter")
+        else:
+            b, a = filter_coefficients[FilterCoefficientsType.Ba]
+            self.ba = [np.atleast_1d(b), np.atleast_1d(a)]
+            if self.is_iir:
+                _check_stable(np.roots(self.ba[1]), "the ba filter")
+
+    @staticmethod
+    def iir_filter(order: int, frequency_hz, type_of_pass: FilterPassType, sampling_rate_hz: int,
+                   filter_design_method: IirDesignMethod = IirDesignMethod.Butterworth,
+                   passband_ripple_db: float | None = None,
+                   stopband_attenuation_db: float | None = None) -> "Filter":
+        """IIR design with scipy.signal.iirfilter, kept as zpk (and sos)."""
+        zpk = sig.iirfilter(N=order, Wn=frequency_hz, btype=type_of_pass.to_str(), analog=False,
+                            fs=sampling_rate_hz, ftype=filter_design_method.to_scipy_str(),
+                            rp=passband_ripple_db, rs=stopband_attenuation_db, output="zpk")
+        return Filter({FilterCoefficientsType.Zpk: zpk}, sampling_rate_hz)
+
+    @staticmethod
+    def biquad(eq_type: BiquadEqType, frequency_hz: float, gain_db: float, q: float,
+               sampling_rate_hz: int) -> "Filter":
+        """Biquad after the Audio EQ Cookbook, as a ba filter."""
+        return Filter({FilterCoefficientsType.Ba: _biquad_coefficients(
+            eq_type=eq_type, frequency_hz=frequency_hz, gain_db=gain_db, q=q, fs_hz=sampling_rate_hz)},
+            sampling_rate_hz)
 
     @staticmethod
     def fir_filter(order: int, frequency_hz, type_of_pass: FilterPassType, sampling_rate_hz: int,
@@ -45,6 +128,14 @@ class Filter:
     @staticmethod
     def from_ba(b, a, sampling_rate_hz: int) -> "Filter":
         return Filter({FilterCoefficientsType.Ba: [b, a]}, sampling_rate_hz)
+
+    @staticmethod
+    def from_sos(sos, sampling_rate_hz: int) -> "Filter":
+        return Filter({FilterCoefficientsType.Sos: sos}, sampling_rate_hz)
+
+    @staticmethod
+    def from_zpk(z, p, k, sampling_rate_hz: int) -> "Filter":
+        return Filter({FilterCoefficientsType.Zpk: [z, p, k]}, sampling_rate_hz)
 
     @property
     def sampling_rate_hz(self) -> int:
@@ -65,11 +156,36 @@ class Filter:
         self.__warning_if_complex = new_warning
 
     @property
+    def sos(self):
+        return self.__sos
+
+    @sos.setter
+    def sos(self, sos):
+        assert isinstance(sos, np.ndarray)
+        assert sos.ndim == 2
+        assert sos.shape[1] == 6
+        self.__sos = sos
+
+    @property
     def has_sos(self) -> bool:
-        return False
+        return hasattr(self, "sos")
+
+    @property
+    def zpk(self) -> list:
+        return self.__zpk
+
+    @zpk.setter
+    def zpk(self, new_zpk):
+        self.__zpk = list(new_zpk)
+
+    @property
+    def has_zpk(self) -> bool:
+        return hasattr(self, "zpk")
 
     @property
     def is_iir(self) -> bool:
+        if self.has_sos:
+            return True
         a = self.ba[1]
         return not (len(a) == 1 and a[0] == 1.0)
 
@@ -79,6 +195,11 @@ class Filter:
 
     @property
     def order(self) -> int:
+        if self.has_zpk:
+            return max(len(self.zpk[0]), len(self.zpk[1]))
+        if self.has_sos:
+            n_first_order = np.sum((self.sos[:, 2] == 0.0) & (self.sos[:, 5] == 0.0))
+            return self.sos.shape[0] * 2 - n_first_order
         return max(len(self.ba[0]), len(self.ba[1])) - 1
 
     def __len__(self):
@@ -107,18 +228,45 @@ class Filter:
             self.__ba = ba
 
     def get_coefficients(self, coefficients_mode: FilterCoefficientsType):
-        """Copy of the filter coefficients (classes/filter.py:927-966).  Only the ba form exists on
-        this path (filters are stored as ba; SOS / zpk conversions are IIR design work)."""
+        """Copy of the filter coefficients in the requested form (classes/filter.py:927-966): ba [b, a], sos
+        (sections, 6), zpk (z, p, k).  Conversions are scipy's."""
+        if coefficients_mode == FilterCoefficientsType.Sos:
+            if self.has_sos:
+                return self.sos.copy()
+            if self.order > 500:
+                warn("Order is above 500. Computing SOS might take a long time")
+            return sig.tf2sos(self.ba[0], self.ba[1])
         if coefficients_mode == FilterCoefficientsType.Ba:
-            return [self.ba[0].copy(), self.ba[1].copy()]
-        if coefficients_mode in (FilterCoefficientsType.Sos, FilterCoefficientsType.Zpk):
-            raise NotImplementedError("only FilterCoefficientsType.Ba is kept on the GPU FIR path")
+            if self.has_sos:
+                return sig.sos2tf(self.sos)
+            return deepcopy(self.ba)
+        if coefficients_mode == FilterCoefficientsType.Zpk:
+            if self.has_zpk:
+                return tuple(deepcopy(self.zpk))
+            if self.has_sos:
+                return sig.sos2zpk(self.sos)
+            if self.order > 500:
+                warn("Order is above 500. Computing zpk might take a long time")
+            return sig.tf2zpk(self.ba[0], self.ba[1])
         raise ValueError(f"{coefficients_mode} is not valid. Use sos, ba or zpk")
 
     @property
     def metadata(self) -> dict:
-        return dict(sampling_rate_hz=self.sampling_rate_hz, order=self.order,
-                    filter_type="fir" if self.is_fir else "iir")
+        return dict(order=self.order, sampling_rate_hz=self.sampling_rate_hz,
+                    filter_type="iir" if self.is_iir else "fir", has_sos=self.has_sos, has_zpk=self.has_zpk)
+
+    def _device_sections(self) -> np.ndarray:
+        """The filter as second-order sections for the device recursion: its own sos, or a ba filter of order <= 2
+        as one section.  Complex coefficients and higher-order ba filters raise NotImplementedError."""
+        if self.has_sos:
+            if np.iscomplexobj(self.sos):
+                raise NotImplementedError("IIR filters with complex coefficients are not run on the device "
+                                          "(the recursion is real float64)")
+            return np.asarray(self.sos, dtype=np.float64)
+        if np.iscomplexobj(self.ba[0]) or np.iscomplexobj(self.ba[1]):
+            raise NotImplementedError("IIR filters with complex coefficients are not run on the device "
+                                      "(the recursion is real float64)")
+        return backend._ba_section(self.ba[0], self.ba[1])
 
     def filter_signal(self, signal: Signal, channels=None, activate_zi: bool = False,
                       zero_phase: bool = False) -> Signal:
@@ -134,8 +282,8 @@ class Filter:
             assert all(channels < signal.number_of_channels), (
                 f"Selected channels ({channels}) are not valid for the signal with "
                 f"{signal.number_of_channels} channels")
-        if not self.is_fir:
-            raise NotImplementedError("IIR filtering is outside the FFT-batchable GPU hot path")
+        if self.is_iir:
+            sections = self._device_sections()  # (raises before any state is touched)
         # zi: always created for all channels, the selected ones are updated (filter.py:693-707)
         if activate_zi:
             if not hasattr(self, "zi"):
@@ -144,11 +292,11 @@ class Filter:
                 warn("zi values of the filter have not been correctly intialized for the number "
                      "of channels. They have now been corrected")
                 self.initialize_zi(signal.number_of_channels)
-            zi = np.asarray(self.zi).T  # (T-1, C), filter_helpers.py:344-345
-        else:
-            zi = None
         if self.order > len(signal):
             warn("Filter is longer than signal, results might be meaningless!")
+        if self.is_iir:
+            return self._filter_signal_iir(signal, channels, activate_zi, zero_phase, sections)
+        zi = np.asarray(self.zi).T if activate_zi else None  # (T-1, C), filter_helpers.py:344-345
         if (signal.on_device and zi is None and not zero_phase and len(channels) == signal.number_of_channels
                 and np.array_equal(channels, np.arange(signal.number_of_channels)) and not np.iscomplexobj(self.ba[0])):
             # device-resident samples, every channel, plain causal filtering: read and written in HBM
@@ -176,13 +324,46 @@ class Filter:
             self.zi = zi
         return signal.copy_with_new_time_data(new_time_data)
 
+    def _filter_signal_iir(self, signal: Signal, channels, activate_zi: bool, zero_phase: bool,
+                           sections: np.ndarray) -> Signal:
+        """The IIR branch of filter_signal: sosfilt / lfilter (filter_helpers.py:207-280, :288-382) on the device."""
+        every_channel = np.array_equal(channels, np.arange(signal.number_of_channels))
+        if signal.on_device and not activate_zi and not zero_phase and every_channel:
+            # device-resident samples, every channel, no state: read and written in HBM
+            y = backend.iir_sos_filter_device(signal.device_samples, [sections], backend.DS_FB_PARALLEL)[0]
+            return signal._device_result(y)
+        x = signal.time_data[:, channels]
+        new_time_data = signal.time_data.copy()
+        if self.has_sos:
+            if activate_zi:
+                # zi unpacking: per-channel (K, 2) states -> (K, 2, C) (filter_helpers.py:246-248)
+                zi = np.moveaxis(np.asarray(self.zi, dtype=np.float64), 0, -1)
+                y, zi[:, :, channels] = backend._sosfilt(sections, x, zi[:, :, channels])
+            elif zero_phase:
+                y = backend._sosfiltfilt(sections, x)
+            else:
+                y = backend._sosfilt(sections, x)
+        else:
+            if activate_zi:
+                zi = np.asarray(self.zi, dtype=np.float64).T  # (order, C), filter_helpers.py:343-345
+                y, zi[:, channels] = backend._lfilter_iir(self.ba[0], self.ba[1], x, zi[:, channels])
+            elif zero_phase:
+                y = backend._filtfilt_iir(self.ba[0], self.ba[1], x)
+            else:
+                y = backend._lfilter_iir(self.ba[0], self.ba[1], x)
+        new_time_data[:, channels] = y
+        if activate_zi:
+            # the reference keeps the unpacked state array, not a per-channel list (filter_helpers.py:274-280 and
+            # :377-382 return `zi`): (K, 2, C) for sos, (order, C) for ba -- the next call re-initialises unless
+            # its first dimension equals the channel count, exactly as there
+            self.zi = zi
+        return signal.copy_with_new_time_data(new_time_data)
+
     def get_ir(self, length_samples: int, zero_phase: bool = False):
         """Impulse response of the filter with the given length (classes/filter.py:818-860): the padded /
-        trimmed taps themselves, or -- zero phase -- a unit impulse through the device's two-pass filtering."""
+        trimmed taps of an FIR filter, or a unit impulse through the device's filtering."""
         from .impulse_response import ImpulseResponse
-        if not self.is_fir:
-            raise NotImplementedError("IIR filtering is outside the FFT-batchable GPU hot path")
-        if not zero_phase:
+        if self.is_fir and not zero_phase:
             b = self.ba[0].copy()
             if length_samples < len(b):
                 warn(f"{length_samples} is not enough for filter with length {len(b)}. IR will have the latter length.")
@@ -192,23 +373,30 @@ class Filter:
         d = np.zeros(length_samples)
         d[0] = 1.0
         ir = ImpulseResponse(None, d, self.sampling_rate_hz, constrain_amplitude=False)
-        return self.filter_signal(ir, zero_phase=True)
+        return self.filter_signal(ir, zero_phase=zero_phase)
 
     def get_transfer_function(self, frequency_vector_hz) -> np.ndarray:
-        """Complex transfer function at the given frequencies (classes/filter.py:862-900; the reference calls
-        scipy.signal.freqz, here the same sum in float64 on the device)."""
+        """Complex transfer function at the given frequencies (classes/filter.py:862-900): FIR filters as the same
+        sum in float64 on the device, IIR filters with scipy.signal.sosfreqz / freqz on the host as the reference."""
         frequency_vector_hz = np.asarray(frequency_vector_hz)
         assert frequency_vector_hz.ndim == 1, "Frequency vector can only have one dimension"
         assert frequency_vector_hz.max() <= self.sampling_rate_hz / 2, \
             "Queried frequency vector has values larger than nyquist"
-        if not self.is_fir:
-            raise NotImplementedError("IIR filters are outside the FFT-batchable GPU hot path")
+        if self.has_sos:
+            return sig.sosfreqz(self.sos, frequency_vector_hz, fs=self.sampling_rate_hz)[1]
+        if self.is_iir:
+            return sig.freqz(self.ba[0], self.ba[1], frequency_vector_hz, fs=self.sampling_rate_hz)[1]
         return backend.fir_transfer_function([self.ba[0]], frequency_vector_hz, self.sampling_rate_hz)[:, 0]
 
     def initialize_zi(self, number_of_channels: int = 1):
-        """Steady-state initial filter state for every channel (scipy.signal.lfilter_zi)."""
+        """Steady-state initial filter state for every channel (scipy.signal.sosfilt_zi / lfilter_zi)."""
         assert number_of_channels > 0, "Zi's have to be initialized for at least one channel"
-        self.zi = [backend._lfilter_zi_fir(self.ba[0]) for _ in range(number_of_channels)]
+        if self.has_sos:
+            self.zi = [sig.sosfilt_zi(self.sos) for _ in range(number_of_channels)]
+        elif self.is_iir:
+            self.zi = [sig.lfilter_zi(self.ba[0], self.ba[1]) for _ in range(number_of_channels)]
+        else:
+            self.zi = [backend._lfilter_zi_fir(self.ba[0]) for _ in range(number_of_channels)]
         return self
 
     def copy(self) -> "Filter":

@@ -1,8 +1,10 @@
 """FilterBank (API mirror of dsptoolbox/classes/filterbank.py: ctor :33-66,
 filter_signal :415-477 and the loop of filter_helpers.py:385-451, swap_filters :365-393,
 filter_multiband_signal :479-532, get_ir :534-613, get_transfer_function :615-655).
-A bank of equal-length FIR filters is applied in ONE device call: every input
-block is transformed once and all band filters are applied on chip."""
+The FIR filters of a bank are applied in ONE device call (every input block is
+transformed once and all band filters are applied on chip), its IIR filters in
+another (one float64 recursion per filter and channel, every filter of a channel
+from one read of the samples); a bank that mixes both composes the two calls."""
 
 from copy import deepcopy
 from warnings import warn
@@ -114,12 +116,9 @@ class FilterBank:
                 self.initialize_zi(signal.number_of_channels)
         if mode not in (FilterBankMode.Parallel, FilterBankMode.Sequential, FilterBankMode.Summed):
             raise ValueError("Invalid filter bank apply mode")
-        for f in self.filters:
-            if not f.is_fir:
-                raise NotImplementedError("IIR filters are outside the FFT-batchable GPU hot path")
         if activate_zi or zero_phase:
             # per-filter state / two-pass filtering: the reference's own loop
-            # (filter_helpers.py:385-451), one device convolution (or two) per filter
+            # (filter_helpers.py:385-451), one device call (or two) per filter
             if mode == FilterBankMode.Parallel:
                 bands = [f.filter_signal(signal, activate_zi=activate_zi, zero_phase=zero_phase)
                          for f in self.filters]
@@ -134,26 +133,56 @@ class FilterBank:
                 acc[:, :, n] = f.filter_signal(signal, activate_zi=activate_zi,
                                                zero_phase=zero_phase).time_data
             return signal.copy_with_new_time_data(np.sum(acc, axis=-1))
-        taps = [f.ba[0] for f in self.filters]
-        n_taps = max(len(t) for t in taps)
-        # zero-extending a FIR filter at the end does not change its output
-        taps = [np.concatenate([t, np.zeros(n_taps - len(t))]) for t in taps]
         ds_mode = {FilterBankMode.Parallel: backend.DS_FB_PARALLEL,
                    FilterBankMode.Sequential: backend.DS_FB_SEQUENTIAL,
                    FilterBankMode.Summed: backend.DS_FB_SUMMED}[mode]
-        if signal.on_device and not any(np.iscomplexobj(t) for t in taps):
-            # device-resident samples: the whole bank in one call, its output stays in HBM -- a Parallel bank's
-            # MultiBandSignal holds K device-resident bands (slices of ONE buffer), downloaded when asked for
-            y = backend.fir_filter_bank_device(signal.device_samples, taps, ds_mode)
-            if mode == FilterBankMode.Parallel:
-                return MultiBandSignal([signal._device_result(b) for b in y], same_sampling_rate=self.same_sampling_rate)
-            return signal._device_result(y)
-        y = backend.fir_filter_bank(signal.time_data, taps, ds_mode)
-        if mode == FilterBankMode.Parallel:
-            bands = [signal.copy_with_new_time_data(np.ascontiguousarray(y[k]))
-                     for k in range(len(taps))]
-            return MultiBandSignal(bands, same_sampling_rate=self.same_sampling_rate)
-        return signal.copy_with_new_time_data(y)
+        fir = [n for n, f in enumerate(self.filters) if f.is_fir]
+        iir = [n for n, f in enumerate(self.filters) if not f.is_fir]
+        sections = [self.filters[n]._device_sections() for n in iir]
+        taps = [f.ba[0] for f in self.filters if f.is_fir]
+        if taps:
+            n_taps = max(len(t) for t in taps)
+            # zero-extending a FIR filter at the end does not change its output
+            taps = [np.concatenate([t, np.zeros(n_taps - len(t))]) for t in taps]
+        on_device = signal.on_device and not any(np.iscomplexobj(t) for t in taps)
+        if on_device and not (fir and iir and mode == FilterBankMode.Summed):
+            # device-resident samples: the whole bank in one call per filter kind, the output stays in HBM -- a
+            # Parallel bank's MultiBandSignal holds device-resident bands (slices of one buffer per kind),
+            # downloaded when asked for
+            x = signal.device_samples
+            if mode == FilterBankMode.Sequential:
+                # causal linear filters commute: the FIR cascade first, then the IIR one
+                y = backend.fir_filter_bank_device(x, taps, ds_mode) if fir else x
+                y = backend.iir_sos_filter_device(y, sections, ds_mode) if iir else y
+                return signal._device_result(y)
+            bands = [None] * len(self.filters)
+            if fir:
+                y = backend.fir_filter_bank_device(x, taps, ds_mode)
+                if mode == FilterBankMode.Summed:
+                    return signal._device_result(y)
+                for n, b in zip(fir, y):
+                    bands[n] = b
+            if iir:
+                y = backend.iir_sos_filter_device(x, sections, ds_mode)
+                if mode == FilterBankMode.Summed:
+                    return signal._device_result(y)
+                for n, b in zip(iir, y):
+                    bands[n] = b
+            return MultiBandSignal([signal._device_result(b) for b in bands], same_sampling_rate=self.same_sampling_rate)
+        x = signal.time_data
+        if mode == FilterBankMode.Sequential:
+            y = backend.fir_filter_bank(x, taps, ds_mode) if fir else x
+            y = backend.iir_sos_filter(y, sections, ds_mode) if iir else y
+            return signal.copy_with_new_time_data(y)
+        y_fir = backend.fir_filter_bank(x, taps, ds_mode) if fir else None
+        y_iir = backend.iir_sos_filter(x, sections, ds_mode) if iir else None
+        if mode == FilterBankMode.Summed:
+            return signal.copy_with_new_time_data(sum(y for y in (y_fir, y_iir) if y is not None))
+        bands = [None] * len(self.filters)
+        for idx, y in ((fir, y_fir), (iir, y_iir)):
+            for i, n in enumerate(idx):
+                bands[n] = signal.copy_with_new_time_data(np.ascontiguousarray(y[i]))
+        return MultiBandSignal(bands, same_sampling_rate=self.same_sampling_rate)
 
     def filter_multiband_signal(self, mbsignal: MultiBandSignal, activate_zi: bool = False,
                                 zero_phase: bool = False) -> MultiBandSignal:
@@ -199,7 +228,8 @@ class FilterBank:
 
     def get_transfer_function(self, frequency_vector_hz, mode: FilterBankMode) -> np.ndarray:
         """Complex transfer function of the bank (filterbank.py:615-655): Parallel -> (frequency, filter);
-        Sequential -> the product; Summed -> ONE PLUS the sum (the reference starts its sum from ones)."""
+        Sequential -> the product; Summed -> ONE PLUS the sum (the reference starts its sum from ones).
+        The FIR filters in one device call, the IIR filters with scipy on the host (Filter.get_transfer_function)."""
         frequency_vector_hz = np.asarray(frequency_vector_hz)
         assert frequency_vector_hz.ndim == 1, "Frequency vector can only have one dimension"
         if mode not in (FilterBankMode.Parallel, FilterBankMode.Sequential, FilterBankMode.Summed):
@@ -207,10 +237,17 @@ class FilterBank:
         for f in self.filters:
             assert frequency_vector_hz.max() <= f.sampling_rate_hz / 2, \
                 "Queried frequency vector has values larger than nyquist"
-            if not f.is_fir:
-                raise NotImplementedError("IIR filters are outside the FFT-batchable GPU hot path")
-        if self.same_sampling_rate:  # every filter in one device call
+        if self.same_sampling_rate and all(f.is_fir for f in self.filters):  # every filter in one device call
             h = backend.fir_transfer_function([f.ba[0] for f in self.filters], frequency_vector_hz, self.sampling_rate_hz)
+        elif self.same_sampling_rate:
+            fir = [n for n, f in enumerate(self.filters) if f.is_fir]
+            h = np.empty((len(frequency_vector_hz), len(self.filters)), dtype=np.complex128)
+            if fir:
+                h[:, fir] = backend.fir_transfer_function([self.filters[n].ba[0] for n in fir], frequency_vector_hz,
+                                                          self.sampling_rate_hz)
+            for n, f in enumerate(self.filters):
+                if not f.is_fir:
+                    h[:, n] = f.get_transfer_function(frequency_vector_hz)
         else:
             h = np.stack([f.get_transfer_function(frequency_vector_hz) for f in self.filters], axis=1)
         if mode == FilterBankMode.Parallel:

@@ -40,6 +40,7 @@
 #include "kernels_fir_stream.hpp"
 #include "kernels_freqz.hpp"
 #include "kernels_beamform.hpp"
+#include "kernels_iir.hpp"
 
 using namespace dsk;
 
@@ -3622,6 +3623,154 @@ extern "C" int ds_fir_freqz(ds_ctx* c, const double* taps, int n_filt, int n_tap
     CHK(launch(c, "fir_freqz", freqz::k_freqz, dim3((n_freq + 255) / 256, n_filt), 256, 0, a));
     HIPCHK(c, hipMemcpyAsync(out, dout, bo, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    return DS_OK;
+}
+
+// ---- IIR filtering: cascades of second-order sections (kernels_iir.hpp) --------------------------------
+// Host side of the carry: the normalised sections, the zero-input state transition A of each cascade and its
+// powers Phi = A^L and Phi^B, in float64.
+static void mat_mul(const std::vector<double>& a, const std::vector<double>& b, int d, std::vector<double>& out) {
+    std::vector<double> r((size_t)d * d, 0.0);
+    for (int i = 0; i < d; ++i)
+        for (int k = 0; k < d; ++k) {
+            const double v = a[(size_t)i * d + k];
+            if (v == 0.0) continue;
+            for (int j = 0; j < d; ++j) r[(size_t)i * d + j] += v * b[(size_t)k * d + j];
+        }
+    out.swap(r);
+}
+
+static void mat_pow2(std::vector<double>& m, int d, int log2_exp) {  // m <- m^(2^log2_exp)
+    for (int i = 0; i < log2_exp; ++i) mat_mul(m, m, d, m);
+}
+
+// sos [n_filt][n_sec][6] -> coef [n_filt][n_sec][5] (b0 b1 b2 a1 a2 / a0), phi = A^L, phig = A^(L B), each [n_filt][D][D]
+static bool iir_tables(const double* sos, int n_filt, int n_sec, std::vector<double>& coef, std::vector<double>& phi,
+                       std::vector<double>& phig) {
+    const int d = 2 * n_sec;
+    coef.assign((size_t)n_filt * n_sec * 5, 0.0);
+    phi.assign((size_t)n_filt * d * d, 0.0);
+    phig.assign((size_t)n_filt * d * d, 0.0);
+    for (int f = 0; f < n_filt; ++f) {
+        double* cf = coef.data() + (size_t)f * n_sec * 5;
+        for (int k = 0; k < n_sec; ++k) {
+            const double* s = sos + ((size_t)f * n_sec + k) * 6;
+            for (int i = 0; i < 6; ++i)
+                if (!std::isfinite(s[i])) return false;
+            if (s[3] == 0.0) return false;
+            const double a0 = s[3];
+            cf[5 * k] = s[0] / a0;
+            cf[5 * k + 1] = s[1] / a0;
+            cf[5 * k + 2] = s[2] / a0;
+            cf[5 * k + 3] = s[4] / a0;
+            cf[5 * k + 4] = s[5] / a0;
+        }
+        // column j of A: one zero-input step of the cascade from the unit state e_j
+        std::vector<double> a((size_t)d * d, 0.0);
+        for (int j = 0; j < d; ++j) {
+            double in = 0.0;
+            for (int k = 0; k < n_sec; ++k) {
+                const double z1 = (j == 2 * k) ? 1.0 : 0.0, z2 = (j == 2 * k + 1) ? 1.0 : 0.0;
+                const double y = cf[5 * k] * in + z1;
+                a[(size_t)(2 * k) * d + j] = cf[5 * k + 1] * in - cf[5 * k + 3] * y + z2;
+                a[(size_t)(2 * k + 1) * d + j] = cf[5 * k + 2] * in - cf[5 * k + 4] * y;
+                in = y;
+            }
+        }
+        static_assert(iir::L == 32 && iir::B == 64, "the squarings below assume L = 2^5, B = 2^6");
+        mat_pow2(a, d, 5);
+        std::copy(a.begin(), a.end(), phi.begin() + (size_t)f * d * d);
+        mat_pow2(a, d, 6);
+        std::copy(a.begin(), a.end(), phig.begin() + (size_t)f * d * d);
+    }
+    return true;
+}
+
+// the three passes over device buffers of either sample type; y element (f, c, n) at y[f syf + c syc + n syn]
+template <typename T>
+static int iir_run(ds_ctx* c, const char* who, const T* x, int64_t sxc, int64_t sxn, int64_t n, int n_ch,
+                   const double* sos, int n_filt, int n_sec, const double* zi, int mode, T* y, int64_t syf,
+                   int64_t syc, int64_t syn, double* zf) {
+    if (mode != DS_FB_PARALLEL && mode != DS_FB_SUMMED && mode != DS_FB_SEQUENTIAL)
+        return fail(c, DS_ERR_ARG, std::string(who) + ": invalid filter bank apply mode");
+    if (mode == DS_FB_SEQUENTIAL) {  // one cascade of all sections: sos and zi keep their memory layout
+        n_sec *= n_filt;
+        n_filt = 1;
+    }
+    if (n_sec > iir::MAX_SEC)
+        return fail(c, DS_ERR_UNSUP, std::string(who) + ": more than 32 second-order sections in one cascade is not "
+                                     "built (the carry's state vector is one value per lane of a wave)");
+    if ((int64_t)n_filt * n_ch > 65535)
+        return fail(c, DS_ERR_UNSUP, std::string(who) + ": more than 65535 (filter, channel) streams is not built yet");
+    const int64_t n_groups = (n + iir::G - 1) / iir::G;
+    if (n_groups > INT32_MAX) return fail(c, DS_ERR_UNSUP, std::string(who) + ": signal too long");
+    std::vector<double> coef, phi, phig;
+    if (!iir_tables(sos, n_filt, n_sec, coef, phi, phig))
+        return fail(c, DS_ERR_ARG, std::string(who) + ": sections must be finite with a0 != 0");
+    const int d = 2 * n_sec;
+    const size_t n_streams = (size_t)n_filt * n_ch;
+    CHK(reserve(c, &c->ws, &c->ws_bytes, Carver::pad(coef.size() * 8) + 2 * Carver::pad(phi.size() * 8) +
+                                             Carver::pad(n_streams * n_groups * d * 8)));
+    Carver cv(c->ws);
+    double* dcoef = cv.take<double>(coef.size());
+    double* dphi = cv.take<double>(phi.size());
+    double* dphig = cv.take<double>(phig.size());
+    double* gst = cv.take<double>(n_streams * n_groups * d);
+    CHK(ds_upload(c, dcoef, coef.data(), coef.size() * 8));
+    CHK(ds_upload(c, dphi, phi.data(), phi.size() * 8));
+    CHK(ds_upload(c, dphig, phig.data(), phig.size() * 8));
+    iir::Args<T> a{x, sxc, sxn, y, mode == DS_FB_PARALLEL ? syf : 0, syc, syn, n, n_ch, n_filt, n_sec,
+                   mode == DS_FB_SUMMED ? 1 : 0, n_groups, dcoef, dphi, dphig, gst, zi, zf};
+    if (n_groups > 1)
+        CHK(launch(c, "iir_group", iir::k_iir_group<T>, dim3((unsigned)(n_groups - 1), (unsigned)n_streams), iir::B,
+                   iir::lds_bytes(n_sec, false), a));
+    iir::CarryArgs ca{dphig, gst, zi, n_groups, n_ch, n_sec};
+    CHK(launch(c, "iir_carry", iir::k_iir_carry, dim3((unsigned)n_streams), iir::B, sizeof(double) * d * d, ca));
+    return launch(c, "iir_apply", iir::k_iir_apply<T>, dim3((unsigned)n_groups, (unsigned)n_ch), iir::B,
+                  iir::lds_bytes(n_sec, true), a);
+}
+
+static int iir_shape_ok(ds_ctx* c, const char* who, int n_ch, int64_t n_samples, const double* sos, int n_filt,
+                        int n_sec) {
+    if (!sos) return fail(c, DS_ERR_ARG, std::string(who) + ": null argument");
+    if (n_ch <= 0 || n_samples <= 0 || n_filt <= 0 || n_sec <= 0)
+        return fail(c, DS_ERR_ARG, std::string(who) + ": bad shape");
+    return DS_OK;
+}
+
+extern "C" int ds_iir_sos_dev(ds_ctx* c, const float* x, int n_ch, int64_t ldx, int64_t n_samples, const double* sos,
+                              int n_filt, int n_sec, const double* zi, int mode, float* y, int64_t ld_y, double* zf) {
+    if (!c || !x || !y) return fail(c, DS_ERR_ARG, "ds_iir_sos_dev: null argument");
+    CHK(iir_shape_ok(c, "ds_iir_sos_dev", n_ch, n_samples, sos, n_filt, n_sec));
+    if (ldx < n_samples || ld_y < n_samples) return fail(c, DS_ERR_ARG, "ds_iir_sos_dev: bad shape");
+    HIPCHK(c, hipSetDevice(c->device));
+    return iir_run<float>(c, "ds_iir_sos_dev", x, ldx, 1, n_samples, n_ch, sos, n_filt, n_sec, zi, mode, y,
+                          (int64_t)n_ch * ld_y, ld_y, 1, zf);
+}
+
+// host pointers in the reference's layouts: x (n_samples, n_ch), y (n_filt or 1, n_samples, n_ch), float64; the
+// samples cross the link as they are and the kernels read them with the channel stride
+extern "C" int ds_iir_sos(ds_ctx* c, const double* x, int n_ch, int64_t n_samples, const double* sos, int n_filt,
+                          int n_sec, const double* zi, int mode, double* y, double* zf) {
+    if (!c || !x || !y) return fail(c, DS_ERR_ARG, "ds_iir_sos: null argument");
+    CHK(iir_shape_ok(c, "ds_iir_sos", n_ch, n_samples, sos, n_filt, n_sec));
+    if (mode != DS_FB_PARALLEL && mode != DS_FB_SUMMED && mode != DS_FB_SEQUENTIAL)
+        return fail(c, DS_ERR_ARG, "ds_iir_sos: invalid filter bank apply mode");
+    HIPCHK(c, hipSetDevice(c->device));
+    const int n_out = mode == DS_FB_PARALLEL ? n_filt : 1;
+    const size_t nx = (size_t)n_ch * n_samples, ny = nx * n_out, nz = (size_t)n_filt * n_sec * 2 * n_ch;
+    CHK(stage_reserve(c, Carver::pad(nx * 8) + Carver::pad(ny * 8) + 2 * Carver::pad(nz * 8)));
+    Carver cv(c->io);
+    double* dx = cv.take<double>(nx);
+    double* dy = cv.take<double>(ny);
+    double* dzi = cv.take<double>(nz);
+    double* dzf = cv.take<double>(nz);
+    CHK(ds_upload(c, dx, x, nx * 8));
+    if (zi) CHK(ds_upload(c, dzi, zi, nz * 8));
+    CHK(iir_run<double>(c, "ds_iir_sos", dx, 1, n_ch, n_samples, n_ch, sos, n_filt, n_sec, zi ? dzi : nullptr, mode,
+                        dy, (int64_t)nx, 1, n_ch, zf ? dzf : nullptr));
+    CHK(ds_download(c, y, dy, ny * 8));
+    if (zf) CHK(ds_download(c, zf, dzf, nz * 8));
     return DS_OK;
 }
 

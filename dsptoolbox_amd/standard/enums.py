@@ -2,8 +2,8 @@
 
 Only the members and methods the hot path touches are provided:
 SpectrumMethod (:7-18), SpectrumScaling (:21-229), FilterCoefficientsType
-(:232-243), FilterBankMode (:279-292), FilterPassType (:295-305), Window
-(:341-437), SpectrumType.
+(:232-243), BiquadEqType (:246-276), FilterBankMode (:279-292), FilterPassType
+(:295-305), IirDesignMethod (:308-338), Window (:341-437), SpectrumType.
 """
 
 from enum import Enum, auto
@@ -105,6 +105,25 @@ class FilterCoefficientsType(Enum):
     Ba = auto()
 
 
+class BiquadEqType(Enum):
+    """Biquad types of the Audio EQ Cookbook (Filter.biquad), plus first-order low / high / all passes and a
+    pure gain (Inverter)."""
+
+    Lowpass = auto()
+    Highpass = auto()
+    Peaking = auto()
+    Lowshelf = auto()
+    Highshelf = auto()
+    BandpassSkirt = auto()
+    BandpassPeak = auto()
+    LowpassFirstOrder = auto()
+    HighpassFirstOrder = auto()
+    AllpassFirstOrder = auto()
+    Allpass = auto()
+    Notch = auto()
+    Inverter = auto()
+
+
 class FilterBankMode(Enum):
     """Parallel -> MultiBandSignal of band outputs; Sequential -> cascade;
     Summed -> sum of the band outputs."""
@@ -125,6 +144,21 @@ class FilterPassType(Enum):
 
     def to_str(self):
         return str(self)
+
+
+class IirDesignMethod(Enum):
+    """IIR design methods of scipy.signal.iirfilter (Filter.iir_filter)."""
+
+    Bessel = auto()
+    Butterworth = auto()
+    Chebyshev1 = auto()
+    Chebyshev2 = auto()
+    Elliptic = auto()
+
+    def to_scipy_str(self) -> str:
+        return {IirDesignMethod.Bessel: "bessel", IirDesignMethod.Butterworth: "butter",
+                IirDesignMethod.Chebyshev1: "cheby1", IirDesignMethod.Chebyshev2: "cheby2",
+                IirDesignMethod.Elliptic: "ellip"}[self]
 
 
 class Window(Enum):

@@ -1,0 +1,46 @@
+"""tools: the fractional-octave band arithmetic of the reference's tools.fractional_octave_frequencies
+(dsptoolbox/tools.py:186-255), after the band definitions of IEC 61260-1:2014 / ANSI S1.11-2004."""
+
+import numpy as np
+
+# base-ten octave ratio and reference frequency of IEC 61260-1 (5.2, 5.4)
+_G = 10 ** (3 / 10)
+_F_REF = 1000.0
+# the standard's nominal mid-band frequencies (IEC 61260-1, Annex E): octave and one-third-octave bands
+_NOMINAL = {
+    1: [31.5, 63, 125, 250, 500, 1e3, 2e3, 4e3, 8e3, 16e3],
+    3: [25, 31.5, 40, 50, 63, 80, 100, 125, 160, 200, 250, 315, 400, 500, 630, 800, 1000, 1250, 1600, 2000, 2500,
+        3150, 4000, 5000, 6300, 8000, 10000, 12500, 16000, 20000],
+}
+
+
+def fractional_octave_frequencies(num_fractions=1, frequency_range=(20, 20e3), return_cutoff=False):
+    """Nominal and exact mid-band frequencies of 1/num_fractions-octave bands within frequency_range, and -- with
+    return_cutoff -- the band edges (lower, upper) = exact * G^(-+1 / (2 num_fractions)).
+
+    For octaves and thirds the bands are the standard's: band x has the exact mid-band frequency
+    1000 G^(x / b), x the index whose nominal frequency is that of the table, and only bands whose nominal
+    frequency lies inside the range are kept.  Other fractions have no nominal frequencies (an empty array)
+    and exact frequencies 1000 * 2^(x / b) for x from -round(b log2(1000 / f_low)) to round(b log2(f_high / 1000)).
+
+    Returns (nominal, exact) or (nominal, exact, (lower, upper))."""
+    f_lims = np.asarray(frequency_range)
+    if f_lims.size != 2:
+        raise ValueError("You need to specify a lower and upper limit frequency.")
+    if f_lims[0] > f_lims[1]:
+        raise ValueError("The second frequency needs to be higher than the first.")
+    b = num_fractions
+    if b in _NOMINAL:
+        nominal = np.asarray(_NOMINAL[b], dtype=float)
+        # odd b: mid-band frequencies at integer band indices relative to 1 kHz
+        exact = _F_REF * _G ** (np.around(b * np.log(nominal / _F_REF) / np.log(_G)) / b)
+        keep = (nominal >= f_lims[0]) & (nominal <= f_lims[1])
+        nominal, exact = nominal[keep], exact[keep]
+    else:
+        nominal = np.array([])
+        x_hi = np.around(b * np.log2(f_lims[1] / _F_REF))
+        x_lo = np.around(b * np.log2(_F_REF / f_lims[0]))
+        exact = _F_REF * 2 ** (np.arange(-x_lo, x_hi + 1) / b)
+    if not return_cutoff:
+        return nominal, exact
+    return nominal, exact, (exact * _G ** (-1 / 2 / b), exact * _G ** (1 / 2 / b))

@@ -358,6 +358,29 @@ int ds_fir_ola_dev(ds_ctx* ctx, const float* x_dev, int n_ch, int64_t ldx,
 int ds_fir_ola(ds_ctx* ctx, const float* x, int n_ch, int64_t n_samples,
                const float* taps, int n_filt, int n_taps, int mode, float* y);
 
+/* ---- IIR filtering: cascades of second-order sections, float64 recursion: replaces scipy.signal.sosfilt /
+ * lfilter in _filter_on_signal (classes/filter_helpers.py:207-280), the IIR branch of _filter_on_signal_ba
+ * (:288-382) and the filter loop of _filterbank_on_signal (:385-451) for IIR filters.
+ * sos [n_filt][n_sec][6] float64, host pointer: each row b0 b1 b2 a0 a1 a2 (a0 != 0; the rows are divided by it),
+ * each filter a cascade of n_sec sections in transposed direct form II -- what sosfilt computes.  Filters with
+ * fewer sections are padded by the caller with the identity section 1 0 0 1 0 0.
+ * zi / zf [n_filt][n_sec][2][n_ch] float64 (sosfilt's (n_sec, 2, channels) state per filter): the initial state
+ * (NULL: zero) and the final state after the last sample (NULL: not wanted).
+ * mode DS_FB_PARALLEL: every filter on every channel, y[k] per filter; DS_FB_SUMMED: the sum over the filters;
+ * DS_FB_SEQUENTIAL: one cascade of all n_filt * n_sec sections (sos, zi and zf read as [1][n_filt * n_sec]...).
+ * One cascade holds at most 32 sections (DS_ERR_UNSUP above); n_filt * n_ch <= 65535.  The filters must be
+ * stable (every pole inside the unit circle): the time-parallel carry is exact only for them.
+ * ds_iir_sos: host pointers in the reference's layouts, x (n_samples, n_ch) float64, y (n_filt or 1, n_samples,
+ * n_ch) float64.
+ * ds_iir_sos_dev: device-resident planar float32 samples, x_dev[c*ldx + n]; DS_FB_PARALLEL:
+ * y_dev[(k*n_ch + c)*ld_y + n], otherwise y_dev[c*ld_y + n]; zi_dev / zf_dev device pointers (or NULL);
+ * sos stays a host pointer.  The recursion itself is float64 on both entries.                              */
+int ds_iir_sos(ds_ctx* ctx, const double* x, int n_ch, int64_t n_samples, const double* sos, int n_filt,
+               int n_sec, const double* zi, int mode, double* y, double* zf);
+int ds_iir_sos_dev(ds_ctx* ctx, const float* x_dev, int n_ch, int64_t ldx, int64_t n_samples, const double* sos,
+                   int n_filt, int n_sec, const double* zi_dev, int mode, float* y_dev, int64_t ld_y,
+                   double* zf_dev);
+
 /* ---- block-streaming FIR classes with device-resident state ------------------------------
  * One process_block of the reference's real-time classes (classes/fir_filter_realtime.py:75-335),
  * executed literally on buffers that stay on the device between calls; per call only the block
