@@ -391,18 +391,30 @@ static int reserve(ds_ctx* c, void** buf, size_t* cap, size_t bytes) {
     return DS_OK;
 }
 
-struct Carver {  // 256-byte aligned sub-allocations out of one buffer
-    char* base;
+struct Carver {  // 256-byte aligned sub-allocations out of one buffer; without a base it only adds up their sizes
+    char* base = nullptr;
     size_t off = 0;
+    Carver() = default;
     explicit Carver(void* b) : base((char*)b) {}
     template <typename T>
     T* take(size_t count) {
-        T* p = (T*)(base + off);
+        T* p = base ? (T*)(base + off) : nullptr;
         off += (count * sizeof(T) + 255) & ~size_t(255);
         return p;
     }
-    static size_t pad(size_t bytes) { return (bytes + 255) & ~size_t(255); }
 };
+
+// The one place a buffer's pieces are written down: lay(Carver&) runs once to size *buf (grown by reserve), then
+// again to place its pointers in it.  So lay takes pieces and stores the pointers; it launches, copies or fails nothing.
+template <class F>
+static int carve(ds_ctx* c, void** buf, size_t* cap, F&& lay) {
+    Carver probe;
+    lay(probe);
+    CHK(reserve(c, buf, cap, probe.off));
+    Carver cv(*buf);
+    lay(cv);
+    return DS_OK;
+}
 
 static int prof_event(ds_ctx* c, hipEvent_t* ev) {
     if (!c->prof_pool.empty()) {
@@ -503,8 +515,12 @@ static int check_fft_len(ds_ctx* c, int n, const char* what) {
 }
 
 static int upload_table_fwd(ds_ctx* c, float2** slot, const std::vector<float2>& h);
-static size_t stft_big_ws(int n_ch, int n_frames, int64_t nfft);
-static int stft_big(ds_ctx* c, Carver& cv, const float* x, int n_ch, int64_t ld, int64_t n_samples,
+struct BigScratch {  // stft_big's scratch: two groups of four-step transforms and the frame means
+    float2 *P, *Q;
+    float* means;
+};
+static BigScratch take_big_scratch(Carver& cv, int n_ch, int n_frames, int64_t nfft);
+static int stft_big(ds_ctx* c, const BigScratch& s, const float* x, int n_ch, int64_t ld, int64_t n_samples,
                     int W, int hop, int64_t nfft, int64_t pad_front, int n_frames, const float* window,
                     int detrend, float scale, float edge_scale, int power, int layout, float2* out);
 static int welch_big(ds_ctx* c, int kind, const float* x, int n_cx, int64_t ldx, const float* y,
@@ -532,11 +548,12 @@ static int stft_any(ds_ctx* c, const float* x, int64_t n_samples, int n_ch, int6
     int64_t group = std::max<int64_t>(2, ((int64_t)256 << 20) / (conv * 16));
     group = std::min<int64_t>(total_rows, group & ~(int64_t)1);
     if (group < 1) group = 1;
-    CHK(reserve(c, &c->aux, &c->aux_bytes,
-                Carver::pad(sizeof(float) * (size_t)group * keep) + Carver::pad(sizeof(float2) * (size_t)group * B)));
-    Carver cv(c->aux);
-    float* rows = cv.take<float>((size_t)group * keep);
-    float2* tmp = cv.take<float2>((size_t)group * B);
+    float* rows;
+    float2* tmp;
+    CHK(carve(c, &c->aux, &c->aux_bytes, [&](Carver& cv) {
+        rows = cv.take<float>((size_t)group * keep);
+        tmp = cv.take<float2>((size_t)group * B);
+    }));
     for (int64_t r0 = 0; r0 < total_rows; r0 += group) {
         const int nr = (int)std::min<int64_t>(group, total_rows - r0);
         stftany::PrepArgs pa{x, n_samples, ld, pad_front, n_ch, W, hop, detrend, window, keep, (int)r0, rows};
@@ -579,9 +596,8 @@ extern "C" int ds_stft_r2c_dev(ds_ctx* c, const float* x, int64_t n_samples, int
         }
         const int n_pc = (n_ch + 1) / 2, n_groups = (n_ch + 15) / 16;
         const int per = std::min(65535, stftl::frames_per_group(n_ch, nfft, n_frames));
-        CHK(reserve(c, &c->ws, &c->ws_bytes, Carver::pad(sizeof(float2) * (size_t)n_pc * per * nfft)));
-        Carver cv(c->ws);
-        float2* b = cv.take<float2>((size_t)n_pc * per * nfft);
+        float2* b;
+        CHK(carve(c, &c->ws, &c->ws_bytes, [&](Carver& cv) { b = cv.take<float2>((size_t)n_pc * per * nfft); }));
         for (int f0 = 0; f0 < n_frames; f0 += per) {
             const int nf = std::min(per, n_frames - f0);
             // chunks of (frame, kind) units: two rounds of one workgroup (8 channels) per CU, as for 8192 / 16384 points
@@ -604,9 +620,9 @@ extern "C" int ds_stft_r2c_dev(ds_ctx* c, const float* x, int64_t n_samples, int
         return DS_OK;
     }
     if (nfft > kMaxFft && is_pow2(nfft)) {  // four-step transform per frame pair
-        CHK(reserve(c, &c->ws, &c->ws_bytes, stft_big_ws(n_ch, n_frames, nfft)));
-        Carver cv(c->ws);
-        return stft_big(c, cv, x, n_ch, ld, n_samples, W, hop, nfft, pad_front, n_frames, window, detrend,
+        BigScratch s;
+        CHK(carve(c, &c->ws, &c->ws_bytes, [&](Carver& cv) { s = take_big_scratch(cv, n_ch, n_frames, nfft); }));
+        return stft_big(c, s, x, n_ch, ld, n_samples, W, hop, nfft, pad_front, n_frames, window, detrend,
                         scale, edge_scale, power, 1, (float2*)out);
     }
     CHK(check_fft_len(c, nfft, "ds_stft_r2c nfft"));
@@ -775,13 +791,13 @@ static int istft_any_frames(ds_ctx* c, const float2* stft, int n_bins, int n_fra
     const int64_t m_len = blue_len(nfft);
     int group = (int)std::max<int64_t>(1, ((int64_t)64 << 20) / std::max<int64_t>(1, m_len * n_ch));
     group = std::min(group, n_frames);
-    CHK(reserve(c, &c->aux, &c->aux_bytes,
-                Carver::pad(sizeof(float2) * (size_t)n_ch * group * nb) + Carver::pad(sizeof(float) * (size_t)n_ch * group) +
-                    Carver::pad(sizeof(float) * (size_t)n_ch * group * W) + 4096));
-    Carver cv(c->aux);
-    float2* r = cv.take<float2>((size_t)n_ch * group * nb);
-    float* ones = cv.take<float>((size_t)n_ch * group);
-    float* part = cv.take<float>((size_t)n_ch * group * W);
+    float2* r;
+    float *ones, *part;
+    CHK(carve(c, &c->aux, &c->aux_bytes, [&](Carver& cv) {
+        r = cv.take<float2>((size_t)n_ch * group * nb);
+        ones = cv.take<float>((size_t)n_ch * group);
+        part = cv.take<float>((size_t)n_ch * group * W);
+    }));
     for (int f0 = 0; f0 < n_frames; f0 += group) {
         const int nf = std::min(group, n_frames - f0);
         const int64_t total = (int64_t)n_ch * nf * nb;
@@ -834,11 +850,12 @@ extern "C" int ds_istft_dev(ds_ctx* c, const ds_c32* stft, int n_bins, int n_fra
         const bool fused = W == nfft && 2 * step == nfft && R <= 16 &&
                            (int64_t)n_pc * n_frames * nfft * 8 < ((int64_t)1 << 32) - 16;
         const int per = fused ? n_frames : istftl::frames_per_group(n_ch, nfft, n_frames);
-        const size_t cq_bytes = Carver::pad(sizeof(float2) * (size_t)n_pc * per * nfft);
-        CHK(reserve(c, &c->ws, &c->ws_bytes, cq_bytes + (fused ? 0 : Carver::pad(sizeof(float) * (size_t)n_ch * n_frames * W))));
-        Carver cv(c->ws);
-        float2* cq = cv.take<float2>((size_t)n_pc * per * nfft);
-        float* frames = fused ? nullptr : cv.take<float>((size_t)n_ch * n_frames * W);
+        float2* cq;
+        float* frames;
+        CHK(carve(c, &c->ws, &c->ws_bytes, [&](Carver& cv) {
+            cq = cv.take<float2>((size_t)n_pc * per * nfft);
+            frames = fused ? nullptr : cv.take<float>((size_t)n_ch * n_frames * W);
+        }));
         istftl::Args a{(const float2*)stft, n_bins, n_frames, n_ch, W, step, 1, n_groups, R, lgR, 0, n_frames, window,
                        c->w4_tables, *slot, scale, cq, frames, frame_offset, n_frames_total, total_length, ld_out, out};
         for (int f0 = 0; f0 < n_frames; f0 += per) {
@@ -1046,14 +1063,16 @@ extern "C" int ds_band_power(ds_ctx* c, const ds_c32* stft, int n_bins, int64_t 
         return fail(c, DS_ERR_ARG, "ds_band_power: null argument");
     if (n_bins <= 0 || n_fc <= 0 || n_bands <= 0) return fail(c, DS_ERR_ARG, "ds_band_power: bad shape");
     const size_t ns = (size_t)n_bins * n_fc, nw = (size_t)n_bands * n_bins, no = (size_t)n_bands * n_fc;
-    CHK(reserve(c, &c->io, &c->io_bytes,
-                Carver::pad(ns * 8) + Carver::pad(nw * 4) + 2 * Carver::pad((size_t)n_bands * 4) + Carver::pad(no * 4) + 4096));
-    Carver cv(c->io);
-    float2* dx = cv.take<float2>(ns);
-    float* dw = cv.take<float>(nw);
-    int* d0 = cv.take<int>(n_bands);
-    int* d1 = cv.take<int>(n_bands);
-    float* dout = cv.take<float>(no);
+    float2* dx;
+    float *dw, *dout;
+    int *d0, *d1;
+    CHK(carve(c, &c->io, &c->io_bytes, [&](Carver& cv) {
+        dx = cv.take<float2>(ns);
+        dw = cv.take<float>(nw);
+        d0 = cv.take<int>(n_bands);
+        d1 = cv.take<int>(n_bands);
+        dout = cv.take<float>(no);
+    }));
     CHK(ds_upload(c, dx, stft, ns * 8));
     CHK(ds_upload(c, dw, weights, nw * 4));
     CHK(ds_upload(c, d0, band_start, (size_t)n_bands * 4));
@@ -1124,19 +1143,16 @@ static int welch_common(ds_ctx* c, int kind, const float* x, int n_cx, int64_t l
         const int bpb = median_bins_per_block(3, n_frames, &lds);
         if (!bpb)
             return fail(c, DS_ERR_UNSUP, "welch: median averaging over more than 12 799 frames is not built yet");
-        size_t mb = Carver::pad(sizeof(float2) * (size_t)n_cx * n_frames * nb) +
-                    Carver::pad(sizeof(float2) * (size_t)nyc * n_frames * nb) +
-                    Carver::pad(sizeof(float) * (size_t)pl.n_chunks * std::max(n_cx, nyc) * nb) +
-                    Carver::pad(sizeof(float) * (size_t)n_cx * nb) + Carver::pad(sizeof(float2) * (size_t)std::max(1, nyc) * nb) +
-                    Carver::pad(sizeof(float) * (size_t)std::max(1, nyc) * nb);
-        CHK(reserve(c, &c->ws, &c->ws_bytes, mb));
-        Carver cv(c->ws);
-        float2* xsp = cv.take<float2>((size_t)n_cx * n_frames * nb);
-        float2* ysp = nyc ? cv.take<float2>((size_t)nyc * n_frames * nb) : nullptr;
-        float* scratch = cv.take<float>((size_t)pl.n_chunks * std::max(n_cx, nyc) * nb);
-        float* mxx = cv.take<float>((size_t)n_cx * nb);
-        float2* mxy = cv.take<float2>((size_t)std::max(1, nyc) * nb);
-        float* myy = cv.take<float>((size_t)std::max(1, nyc) * nb);
+        float2 *xsp, *ysp, *mxy;
+        float *scratch, *mxx, *myy;
+        CHK(carve(c, &c->ws, &c->ws_bytes, [&](Carver& cv) {
+            xsp = cv.take<float2>((size_t)n_cx * n_frames * nb);
+            ysp = nyc ? cv.take<float2>((size_t)nyc * n_frames * nb) : nullptr;
+            scratch = cv.take<float>((size_t)pl.n_chunks * std::max(n_cx, nyc) * nb);
+            mxx = cv.take<float>((size_t)n_cx * nb);
+            mxy = cv.take<float2>((size_t)std::max(1, nyc) * nb);
+            myy = cv.take<float>((size_t)std::max(1, nyc) * nb);
+        }));
         {
             XspecArgs ax{x, n_samples, ldx, n_cx, W, hop, n_frames, detrend, pl.fpc, window, tw, xsp, scratch};
             DISPATCH_N(W, CHK(launch(c, "welch_xspec", k_xspec<NN>, dim3(pl.n_chunks, n_cx), Cfg<NN>::NT, Cfg<NN>::LDS_BYTES, ax)));
@@ -1156,23 +1172,16 @@ static int welch_common(ds_ctx* c, int kind, const float* x, int n_cx, int64_t l
         return DS_OK;
     }
     const bool need_xs = kind != 1;
-    size_t bytes = Carver::pad(sizeof(float) * (size_t)pl.n_chunks * n_cx * nb);
-    if (need_xs) {
-        bytes += Carver::pad(sizeof(float2) * (size_t)n_cx * n_frames * nb);
-        bytes += Carver::pad(sizeof(float2) * (size_t)pl.n_chunks * n_cy * nb);
-        bytes += Carver::pad(sizeof(float) * (size_t)pl.n_chunks * n_cy * nb);
-    }
-    CHK(reserve(c, &c->ws, &c->ws_bytes, bytes));
-    Carver cv(c->ws);
-    float* pxx = cv.take<float>((size_t)pl.n_chunks * n_cx * nb);
-    float2* xs = nullptr;
-    float2* pxy = nullptr;
-    float* pyy = nullptr;
-    if (need_xs) {
-        xs = cv.take<float2>((size_t)n_cx * n_frames * nb);
-        pxy = cv.take<float2>((size_t)pl.n_chunks * n_cy * nb);
-        pyy = cv.take<float>((size_t)pl.n_chunks * n_cy * nb);
-    }
+    float *pxx, *pyy = nullptr;
+    float2 *xs = nullptr, *pxy = nullptr;
+    CHK(carve(c, &c->ws, &c->ws_bytes, [&](Carver& cv) {
+        pxx = cv.take<float>((size_t)pl.n_chunks * n_cx * nb);
+        if (need_xs) {
+            xs = cv.take<float2>((size_t)n_cx * n_frames * nb);
+            pxy = cv.take<float2>((size_t)pl.n_chunks * n_cy * nb);
+            pyy = cv.take<float>((size_t)pl.n_chunks * n_cy * nb);
+        }
+    }));
     {
         XspecArgs a{x, n_samples, ldx, n_cx, W, hop, n_frames, detrend, pl.fpc, window, tw, xs, pxx};
         dim3 grid(pl.n_chunks, n_cx);
@@ -1224,15 +1233,15 @@ static int welch4096_run(ds_ctx* c, const float* x, int n_cx, int64_t ldx, const
     const bool half = hop == 2048;
     const bool three = half && !c->cfg.w4_two_per_cu && w4::fits3(n_samples, nf);
     w4::Plan pl = three ? w4::plan3(nf, n_cy, c->cfg.welch_chunks) : w4::plan(nf, n_cy, c->cfg.welch_chunks);
-    CHK(reserve(c, &c->ws, &c->ws_bytes, pl.bytes + (size_t)(n_cx - 1) * (Carver::pad(sizeof(float2) * (size_t)pl.n_pairs * w4::N) +
-                                                                  Carver::pad(sizeof(float) * (size_t)pl.n_pairs * w4::NB) +
-                                                                  Carver::pad(sizeof(float) * (size_t)pl.n_chunks * w4::NB)) + 4096));
-    Carver cv(c->ws);
-    float2* xs = cv.take<float2>((size_t)n_cx * pl.n_pairs * w4::N);
-    float* px = cv.take<float>((size_t)n_cx * pl.n_pairs * w4::NB);
-    float* psx = cv.take<float>((size_t)pl.n_chunks * n_cx * w4::NB);
-    float2* pxy = cv.take<float2>((size_t)pl.n_chunks * n_cy * w4::NB);
-    float* pyy = cv.take<float>((size_t)pl.n_chunks * n_cy * w4::NB);
+    float2 *xs, *pxy;
+    float *px, *psx, *pyy;
+    CHK(carve(c, &c->ws, &c->ws_bytes, [&](Carver& cv) {
+        xs = cv.take<float2>((size_t)n_cx * pl.n_pairs * w4::N);
+        px = cv.take<float>((size_t)n_cx * pl.n_pairs * w4::NB);
+        psx = cv.take<float>((size_t)pl.n_chunks * n_cx * w4::NB);
+        pxy = cv.take<float2>((size_t)pl.n_chunks * n_cy * w4::NB);
+        pyy = cv.take<float>((size_t)pl.n_chunks * n_cy * w4::NB);
+    }));
     w4::Args ax{x, n_samples, ldx, 1, hop, nf, pl.n_pairs, detrend, pl.n_chunks, pl.ppc, window,
                 c->w4_tables, xs, px, pxy, pyy, psx};
     ax.n_cx = n_cx;
@@ -1285,13 +1294,15 @@ static int welch2048h_run(ds_ctx* c, const float* x, int n_cx, int64_t ldx, cons
     const int nf = frames_to_visit(n_samples, wh::HOP, n_frames);
     const int n_out = auto_only ? n_cx : n_cy;
     wh::Plan pl = wh::plan(nf, n_out, auto_only ? 0 : n_cx, c->cfg.welch_chunks);
-    CHK(reserve(c, &c->ws, &c->ws_bytes, pl.bytes + 4096));
-    Carver cv(c->ws);
-    float2* xs = auto_only ? nullptr : cv.take<float2>((size_t)n_cx * pl.n_passes * wh::PASS);
-    float* px = auto_only ? nullptr : cv.take<float>((size_t)n_cx * pl.n_passes * wh::NBW);
-    float* psx = auto_only ? nullptr : cv.take<float>((size_t)pl.n_chunks * n_cx * wh::NBW);
-    float2* pxy = auto_only ? nullptr : cv.take<float2>((size_t)pl.n_chunks * n_cy * wh::NBW);
-    float* pyy = cv.take<float>((size_t)pl.n_chunks * n_out * wh::NBW);
+    float2 *xs, *pxy;
+    float *px, *psx, *pyy;
+    CHK(carve(c, &c->ws, &c->ws_bytes, [&](Carver& cv) {
+        xs = auto_only ? nullptr : cv.take<float2>((size_t)n_cx * pl.n_passes * wh::PASS);
+        px = auto_only ? nullptr : cv.take<float>((size_t)n_cx * pl.n_passes * wh::NBW);
+        psx = auto_only ? nullptr : cv.take<float>((size_t)pl.n_chunks * n_cx * wh::NBW);
+        pxy = auto_only ? nullptr : cv.take<float2>((size_t)pl.n_chunks * n_cy * wh::NBW);
+        pyy = cv.take<float>((size_t)pl.n_chunks * n_out * wh::NBW);
+    }));
     // (Args::n_pairs counts passes of four frames here)
     w4::Args ax{x, n_samples, ldx, 1, wh::HOP, nf, pl.n_passes, detrend, pl.n_chunks, 0, window, c->w4_tables, xs, px, pxy, pyy, psx};
     ax.n_cx = n_cx;
@@ -1341,13 +1352,15 @@ static int welch8192_run(ds_ctx* c, const float* x, int n_cx, int64_t ldx, const
     const int nf = frames_to_visit(n_samples, hop, n_frames);
     if (n_cx != 1 && n_cx != n_cy) return fail(c, DS_ERR_ARG, "ds_welch_tf: one input channel, or one per output channel");
     w8::Plan pl = w8::plan(nf, n_cy, n_cx);
-    CHK(reserve(c, &c->ws, &c->ws_bytes, pl.bytes));
-    Carver cv(c->ws);
-    float2* xs = cv.take<float2>((size_t)n_cx * pl.n_pairs * w8::N);
-    float* px = cv.take<float>((size_t)n_cx * pl.n_pairs * w8::NB);
-    float* psx = cv.take<float>((size_t)pl.n_chunks * n_cx * w8::NB);
-    float2* pxy = cv.take<float2>((size_t)pl.n_chunks * n_cy * w8::NB);
-    float* pyy = cv.take<float>((size_t)pl.n_chunks * n_cy * w8::NB);
+    float2 *xs, *pxy;
+    float *px, *psx, *pyy;
+    CHK(carve(c, &c->ws, &c->ws_bytes, [&](Carver& cv) {
+        xs = cv.take<float2>((size_t)n_cx * pl.n_pairs * w8::N);
+        px = cv.take<float>((size_t)n_cx * pl.n_pairs * w8::NB);
+        psx = cv.take<float>((size_t)pl.n_chunks * n_cx * w8::NB);
+        pxy = cv.take<float2>((size_t)pl.n_chunks * n_cy * w8::NB);
+        pyy = cv.take<float>((size_t)pl.n_chunks * n_cy * w8::NB);
+    }));
     const bool half = hop == 4096;
     w8::Args ax{x, n_samples, ldx, n_cx, hop, nf, pl.n_pairs, detrend, pl.n_chunks, window,
                 c->w4_tables, c->deconv8k_tables, (float4*)xs, px, pxy, pyy, psx, n_cx};
@@ -1392,9 +1405,8 @@ static int welch8192_psd_run(ds_ctx* c, const float* x, int n_cx, int64_t ldx, i
     }
     const int nf = frames_to_visit(n_samples, hop, n_frames);
     w8::Plan pl = w8::plan(nf, n_cx);
-    CHK(reserve(c, &c->ws, &c->ws_bytes, Carver::pad(sizeof(float) * (size_t)pl.n_chunks * n_cx * w8::NB)));
-    Carver cv(c->ws);
-    float* pyy = cv.take<float>((size_t)pl.n_chunks * n_cx * w8::NB);
+    float* pyy;
+    CHK(carve(c, &c->ws, &c->ws_bytes, [&](Carver& cv) { pyy = cv.take<float>((size_t)pl.n_chunks * n_cx * w8::NB); }));
     w8::Args a{x, n_samples, ldx, n_cx, hop, nf, pl.n_pairs, detrend, pl.n_chunks, window,
                c->w4_tables, c->deconv8k_tables, nullptr, nullptr, nullptr, pyy, nullptr};
     auto ky = hop == 4096 ? w8::k_y<true, true, true> : w8::k_y<false, true, true>;
@@ -1436,15 +1448,17 @@ static int welch16384_run(ds_ctx* c, const float* x, int n_cx, int64_t ldx, cons
     CHK(welch16k_tables(c));
     const int nf = frames_to_visit(n_samples, hop, n_frames);
     w16::Plan pl = w16::plan(nf, n_cy, n_cx);
-    CHK(reserve(c, &c->ws, &c->ws_bytes, pl.bytes));
-    Carver cv(c->ws);
-    float2* xs = cv.take<float2>((size_t)n_cx * pl.n_pairs * w16::N);
-    float* pxu = cv.take<float>((size_t)n_cx * pl.n_pairs * w16::N);
-    float* psx = cv.take<float>((size_t)pl.n_chunks * n_cx * w16::NB);
-    float2* pxy = cv.take<float2>((size_t)pl.n_chunks * n_cy * w16::NB);
-    float* pyy = cv.take<float>((size_t)pl.n_chunks * n_cy * w16::NB);
-    float2* tu = cv.take<float2>((size_t)pl.n_chunks * n_cy * w16::N);
-    float* pu = cv.take<float>((size_t)pl.n_chunks * n_cy * w16::N);
+    float2 *xs, *pxy, *tu;
+    float *pxu, *psx, *pyy, *pu;
+    CHK(carve(c, &c->ws, &c->ws_bytes, [&](Carver& cv) {
+        xs = cv.take<float2>((size_t)n_cx * pl.n_pairs * w16::N);
+        pxu = cv.take<float>((size_t)n_cx * pl.n_pairs * w16::N);
+        psx = cv.take<float>((size_t)pl.n_chunks * n_cx * w16::NB);
+        pxy = cv.take<float2>((size_t)pl.n_chunks * n_cy * w16::NB);
+        pyy = cv.take<float>((size_t)pl.n_chunks * n_cy * w16::NB);
+        tu = cv.take<float2>((size_t)pl.n_chunks * n_cy * w16::N);
+        pu = cv.take<float>((size_t)pl.n_chunks * n_cy * w16::N);
+    }));
     w16::Args ax{x, n_samples, ldx, n_cx, hop, nf, pl.n_pairs, detrend, pl.n_chunks, window,
                  c->w4_tables, c->fir16k_tables, (float4*)xs, pxu, pxy, pyy, psx, n_cx, tu, pu};
     CHK(launch(c, "welch16384_x", w16::k_x, dim3(pl.n_pairs, n_cx, 4), w16::NTB, w16::LDS_BYTES, ax));
@@ -1506,23 +1520,19 @@ static int welch_long_run(ds_ctx* c, const float* x, int n_cx, int64_t ldx, cons
     const int n_out = auto_only ? n_cx : n_cy;  // channels that are accumulated
     wl::Plan pl = wl::plan(nf, n_out, R);
     const size_t seq = (size_t)pl.n_pairs * W;  // complex values per channel
-    CHK(reserve(c, &c->ws, &c->ws_bytes,
-                Carver::pad(sizeof(float2) * seq * n_cx) + (auto_only ? 0 : Carver::pad(sizeof(float2) * seq * n_cy)) +
-                    (auto_only ? 0 : Carver::pad(sizeof(float2) * seq * n_cx) + Carver::pad(sizeof(float) * seq * n_cx) +
-                                         Carver::pad(sizeof(float) * (size_t)pl.n_chunks * n_cx * nb) +
-                                         Carver::pad(sizeof(float2) * (size_t)pl.n_chunks * n_cy * nb) +
-                                         Carver::pad(sizeof(float2) * (size_t)pl.n_chunks * n_cy * W)) +
-                    Carver::pad(sizeof(float) * (size_t)pl.n_chunks * n_out * nb) + Carver::pad(sizeof(float) * (size_t)pl.n_chunks * n_out * W)));
-    Carver cv(c->ws);
-    float2* bx = cv.take<float2>(seq * n_cx);
-    float2* by = auto_only ? nullptr : cv.take<float2>(seq * n_cy);
-    float2* xs = auto_only ? nullptr : cv.take<float2>(seq * n_cx);
-    float* pxu = auto_only ? nullptr : cv.take<float>(seq * n_cx);
-    float* psx = auto_only ? nullptr : cv.take<float>((size_t)pl.n_chunks * n_cx * nb);
-    float2* pxy = auto_only ? nullptr : cv.take<float2>((size_t)pl.n_chunks * n_cy * nb);
-    float2* tu = auto_only ? nullptr : cv.take<float2>((size_t)pl.n_chunks * n_cy * W);
-    float* pyy = cv.take<float>((size_t)pl.n_chunks * n_out * nb);
-    float* pu = cv.take<float>((size_t)pl.n_chunks * n_out * W);
+    float2 *bx, *by, *xs, *pxy, *tu;
+    float *pxu, *psx, *pyy, *pu;
+    CHK(carve(c, &c->ws, &c->ws_bytes, [&](Carver& cv) {
+        bx = cv.take<float2>(seq * n_cx);
+        by = auto_only ? nullptr : cv.take<float2>(seq * n_cy);
+        xs = auto_only ? nullptr : cv.take<float2>(seq * n_cx);
+        pxu = auto_only ? nullptr : cv.take<float>(seq * n_cx);
+        psx = auto_only ? nullptr : cv.take<float>((size_t)pl.n_chunks * n_cx * nb);
+        pxy = auto_only ? nullptr : cv.take<float2>((size_t)pl.n_chunks * n_cy * nb);
+        tu = auto_only ? nullptr : cv.take<float2>((size_t)pl.n_chunks * n_cy * W);
+        pyy = cv.take<float>((size_t)pl.n_chunks * n_out * nb);
+        pu = cv.take<float>((size_t)pl.n_chunks * n_out * W);
+    }));
     wl::Args ax{x, n_samples, ldx, n_cx, hop, nf, pl.n_pairs, detrend, pl.n_chunks, R, lgR, window, c->w4_tables, *slot,
                 bx, (float4*)xs, pxu, pxy, pyy, psx, n_cx, tu, pu};
     auto dif = [&](const wl::Args& a, int n_ch) {
@@ -1572,11 +1582,11 @@ static int welch16384_psd_run(ds_ctx* c, const float* x, int n_cx, int64_t ldx, 
     CHK(welch16k_tables(c));
     const int nf = frames_to_visit(n_samples, hop, n_frames);
     w16::Plan pl = w16::plan(nf, n_cx);
-    CHK(reserve(c, &c->ws, &c->ws_bytes, Carver::pad(sizeof(float) * (size_t)pl.n_chunks * n_cx * w16::NB) +
-                                             Carver::pad(sizeof(float) * (size_t)pl.n_chunks * n_cx * w16::N)));
-    Carver cv(c->ws);
-    float* pyy = cv.take<float>((size_t)pl.n_chunks * n_cx * w16::NB);
-    float* pu = cv.take<float>((size_t)pl.n_chunks * n_cx * w16::N);
+    float *pyy, *pu;
+    CHK(carve(c, &c->ws, &c->ws_bytes, [&](Carver& cv) {
+        pyy = cv.take<float>((size_t)pl.n_chunks * n_cx * w16::NB);
+        pu = cv.take<float>((size_t)pl.n_chunks * n_cx * w16::N);
+    }));
     w16::Args a{x, n_samples, ldx, n_cx, hop, nf, pl.n_pairs, detrend, pl.n_chunks, window,
                 c->w4_tables, c->fir16k_tables, nullptr, nullptr, nullptr, pyy, nullptr, 1, nullptr, pu};
     CHK(launch(c, "welch16384_main", w16::k_y<true>, dim3(pl.n_chunks * n_cx, 1, 4), w16::NTB, w16::LDS_BYTES, a));
@@ -1605,9 +1615,8 @@ static int welch4096_psd_run(ds_ctx* c, const float* x, int n_cx, int64_t ldx, i
     const int nf = frames_to_visit(n_samples, hop, n_frames);
     const bool three = hop == 2048 && !c->cfg.w4_two_per_cu && w4::fits3(n_samples, nf);
     w4::Plan pl = three ? w4::plan3(nf, n_cx, c->cfg.welch_chunks) : w4::plan(nf, n_cx, c->cfg.welch_chunks);
-    CHK(reserve(c, &c->ws, &c->ws_bytes, Carver::pad(sizeof(float) * (size_t)pl.n_chunks * n_cx * w4::NB)));
-    Carver cv(c->ws);
-    float* pyy = cv.take<float>((size_t)pl.n_chunks * n_cx * w4::NB);
+    float* pyy;
+    CHK(carve(c, &c->ws, &c->ws_bytes, [&](Carver& cv) { pyy = cv.take<float>((size_t)pl.n_chunks * n_cx * w4::NB); }));
     w4::Args a{x, n_samples, ldx, n_cx, hop, nf, pl.n_pairs, detrend, pl.n_chunks, pl.ppc, window,
                c->w4_tables, nullptr, nullptr, nullptr, pyy, nullptr};
     if (three) {
@@ -1659,19 +1668,21 @@ static int welch_wave_run(ds_ctx* c, const float* x, int n_cx, int64_t ldx, cons
     const int nf = frames_to_visit(n_samples, hop, n_frames);
     if (n_cx != 1 && n_cx != n_cy) return fail(c, DS_ERR_ARG, "ds_welch_tf: one input channel, or one per output channel");
     w1::Plan pl = w1::plan<NN>(nf, n_cy, n_cx, c->cfg.welch1k_chunks);
-    CHK(reserve(c, &c->ws, &c->ws_bytes, pl.bytes + Carver::pad(sizeof(float) * NN)));
-    Carver cv(c->ws);
+    float *wz, *px, *psx, *pyy;
+    float2 *xs, *pxy;
+    CHK(carve(c, &c->ws, &c->ws_bytes, [&](Carver& cv) {
+        wz = decim > 1 ? cv.take<float>(NN) : nullptr;
+        xs = cv.take<float2>((size_t)n_cx * pl.n_pairs * NN);
+        px = cv.take<float>((size_t)n_cx * pl.n_pairs * W::NB);
+        psx = cv.take<float>((size_t)pl.n_chunks * n_cx * W::NB);
+        pxy = cv.take<float2>((size_t)pl.n_chunks * n_cy * W::NB);
+        pyy = cv.take<float>((size_t)pl.n_chunks * n_cy * W::NB);
+    }));
     if (decim > 1) {  // the window, zero-padded to the transform length
-        float* wz = cv.take<float>(NN);
         HIPCHK(c, hipMemsetAsync(wz, 0, sizeof(float) * NN, c->stream));
         HIPCHK(c, hipMemcpyAsync(wz, window, sizeof(float) * (NN / decim), hipMemcpyDeviceToDevice, c->stream));
         window = wz;
     }
-    float2* xs = cv.take<float2>((size_t)n_cx * pl.n_pairs * NN);
-    float* px = cv.take<float>((size_t)n_cx * pl.n_pairs * W::NB);
-    float* psx = cv.take<float>((size_t)pl.n_chunks * n_cx * W::NB);
-    float2* pxy = cv.take<float2>((size_t)pl.n_chunks * n_cy * W::NB);
-    float* pyy = cv.take<float>((size_t)pl.n_chunks * n_cy * W::NB);
     const bool half = hop == NN / 2;
     w1::Args ax{x, n_samples, ldx, n_cx, hop, nf, pl.n_pairs, detrend, pl.n_chunks, pl.ppc, window,
                 tab, (float4*)xs, px, pxy, pyy, psx, n_cx};
@@ -1708,16 +1719,16 @@ static int welch_wave_psd_run(ds_ctx* c, const float* x, int n_cx, int64_t ldx, 
     CHK(wave_tables<NN>(c, &tab));
     const int nf = frames_to_visit(n_samples, hop, n_frames);
     w1::Plan pl = w1::plan<NN>(nf, n_cx, 1, c->cfg.welch1k_chunks);
-    CHK(reserve(c, &c->ws, &c->ws_bytes,
-                Carver::pad(sizeof(float) * (size_t)pl.n_chunks * n_cx * W::NB) + Carver::pad(sizeof(float) * NN)));
-    Carver cv(c->ws);
+    float *wz, *pyy;
+    CHK(carve(c, &c->ws, &c->ws_bytes, [&](Carver& cv) {
+        wz = decim > 1 ? cv.take<float>(NN) : nullptr;
+        pyy = cv.take<float>((size_t)pl.n_chunks * n_cx * W::NB);
+    }));
     if (decim > 1) {  // the window, zero-padded to the transform length (see welch_wave_run)
-        float* wz = cv.take<float>(NN);
         HIPCHK(c, hipMemsetAsync(wz, 0, sizeof(float) * NN, c->stream));
         HIPCHK(c, hipMemcpyAsync(wz, window, sizeof(float) * (NN / decim), hipMemcpyDeviceToDevice, c->stream));
         window = wz;
     }
-    float* pyy = cv.take<float>((size_t)pl.n_chunks * n_cx * W::NB);
     w1::Args a{x, n_samples, ldx, n_cx, hop, nf, pl.n_pairs, detrend, pl.n_chunks, pl.ppc, window,
                tab, nullptr, nullptr, nullptr, pyy, nullptr, 1};
     auto ky = hop == NN / 2 ? w1::k_y<NN, true, true> : w1::k_y<NN, false, true>;
@@ -1784,7 +1795,7 @@ static int x64_launch_frames(ds_ctx* c, const double* dsig, int n_ch, int64_t n_
     if (W <= 16384) {
         // four channels or more: read a planar copy (one 8-byte value per 32-byte sector otherwise)
         if (n_ch >= 4 && (n_samples + 31) / 32 <= 0x7fffffff) {
-            CHK(reserve(c, &c->ws, &c->ws_bytes, Carver::pad(sizeof(double) * (size_t)n_ch * n_samples)));
+            CHK(reserve(c, &c->ws, &c->ws_bytes, sizeof(double) * (size_t)n_ch * n_samples));
             double* planar = (double*)c->ws;
             hipLaunchKernelGGL(w64::k_planar, dim3((unsigned)((n_samples + 31) / 32), (unsigned)((n_ch + 31) / 32)), dim3(256), 0,
                                c->stream, dsig, n_samples, n_ch, planar);
@@ -1803,11 +1814,12 @@ static int x64_launch_frames(ds_ctx* c, const double* dsig, int n_ch, int64_t n_
     while ((1 << lg_rc) < rc) ++lg_rc;
     if ((int64_t)n_frames * rc > 0x7fffffff || n_ch > 65535 || n_frames > 65535)
         return fail(c, DS_ERR_UNSUP, "float64 Welch route: too many frames / channels for the long-window kernels");
-    CHK(reserve(c, &c->ws, &c->ws_bytes, Carver::pad(sizeof(double2) * (size_t)n_ch * n_frames * (W / 2)) +
-                                             Carver::pad(sizeof(double) * (size_t)n_ch * n_samples)));
-    Carver cvl(c->ws);
-    double2* zc = cvl.take<double2>((size_t)n_ch * n_frames * (W / 2));
-    double* planar = cvl.take<double>((size_t)n_ch * n_samples);
+    double2* zc;
+    double* planar;
+    CHK(carve(c, &c->ws, &c->ws_bytes, [&](Carver& cv) {
+        zc = cv.take<double2>((size_t)n_ch * n_frames * (W / 2));
+        planar = cv.take<double>((size_t)n_ch * n_samples);
+    }));
     if ((n_samples + 31) / 32 > 0x7fffffff) return fail(c, DS_ERR_UNSUP, "float64 Welch route: signal too long for the long-window kernels");
     hipLaunchKernelGGL(w64::k_planar, dim3((unsigned)((n_samples + 31) / 32), (unsigned)((n_ch + 31) / 32)), dim3(256), 0, c->stream,
                        dsig, n_samples, n_ch, planar);
@@ -1816,6 +1828,19 @@ static int x64_launch_frames(ds_ctx* c, const double* dsig, int n_ch, int64_t n_
     CHK(launch(c, "welch_f64_frames@long", w64::k_frames_cls, dim3((unsigned)(n_frames * rc), n_ch), 256,
                (size_t)w64::LONG_M * 16 + 256 * 8, la));
     return launch(c, "welch_f64_split", w64::k_split, dim3((W / 2 + 1 + 255) / 256, n_frames, n_ch), 256, 0, la);
+}
+
+// the float64 window and twiddle tables of the x64 entries: carved by take_x64_tables, filled by x64_tables
+struct X64Tables {
+    double* dw;
+    double2* tw;
+};
+static X64Tables take_x64_tables(Carver& cv, int W) { return {cv.take<double>(W), cv.take<double2>(W / 2)}; }
+static int x64_tables(ds_ctx* c, const X64Tables& t, const double* window, int W) {
+    HIPCHK(c, hipMemcpyAsync(t.dw, window, (size_t)W * 8, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(w64::k_twiddles, dim3((W / 2 + 255) / 256), dim3(256), 0, c->stream, t.tw, W / 2);
+    HIPCHK(c, hipGetLastError());
+    return DS_OK;
 }
 
 // float64 end to end (kernels_welch_f64.hpp): host arrays in the reference's own layout
@@ -1840,25 +1865,23 @@ extern "C" int ds_welch_tf_x64(ds_ctx* c, const double* x, int n_cx, const doubl
     HIPCHK(c, hipSetDevice(c->device));
     const size_t bx = (size_t)n_samples * n_cx * 8, by = (size_t)n_samples * n_cy * 8;
     const size_t bout = (size_t)nb * n_cy;
-    CHK(reserve(c, &c->io, &c->io_bytes,
-                Carver::pad(bx) + Carver::pad(by) + Carver::pad((size_t)W * 8) + Carver::pad((size_t)W * 8) +
-                    Carver::pad((spec_x + spec_y) * 16) + Carver::pad(bout * 16) + Carver::pad(bout * 8)));
-    Carver cv(c->io);
-    double* dx = cv.take<double>((size_t)n_samples * n_cx);
-    double* dy = cv.take<double>((size_t)n_samples * n_cy);
-    double* dw = cv.take<double>(W);
-    double2* tw = cv.take<double2>(W / 2);
-    double2* xs = cv.take<double2>(spec_x);
-    double2* ys = cv.take<double2>(spec_y);
-    double2* dtf = cv.take<double2>(bout);
-    double* dcoh = cv.take<double>(bout);
+    double *dx, *dy, *dcoh;
+    double2 *xs, *ys, *dtf;
+    X64Tables t;
+    CHK(carve(c, &c->io, &c->io_bytes, [&](Carver& cv) {
+        dx = cv.take<double>((size_t)n_samples * n_cx);
+        dy = cv.take<double>((size_t)n_samples * n_cy);
+        t = take_x64_tables(cv, W);
+        xs = cv.take<double2>(spec_x);
+        ys = cv.take<double2>(spec_y);
+        dtf = cv.take<double2>(bout);
+        dcoh = cv.take<double>(bout);
+    }));
     HIPCHK(c, hipMemcpyAsync(dx, x, bx, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(dy, y, by, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(dw, window, (size_t)W * 8, hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(w64::k_twiddles, dim3((W / 2 + 255) / 256), dim3(256), 0, c->stream, tw, W / 2);
-    HIPCHK(c, hipGetLastError());
-    CHK(x64_launch_frames(c, dx, n_cx, n_samples, W, hop, n_frames, detrend, dw, tw, xs));
-    CHK(x64_launch_frames(c, dy, n_cy, n_samples, W, hop, n_frames, detrend, dw, tw, ys));
+    CHK(x64_tables(c, t, window, W));
+    CHK(x64_launch_frames(c, dx, n_cx, n_samples, W, hop, n_frames, detrend, t.dw, t.tw, xs));
+    CHK(x64_launch_frames(c, dy, n_cy, n_samples, W, hop, n_frames, detrend, t.dw, t.tw, ys));
     if (average == DS_AVG_MEDIAN) {
         const int nbias = (n_frames & 1) ? n_frames : n_frames - 1;
         w64::TfArgs ta{xs, ys, n_cx, n_cy, n_frames, mode,
@@ -1876,20 +1899,8 @@ extern "C" int ds_welch_tf_x64(ds_ctx* c, const double* x, int n_cx, const doubl
     return DS_OK;
 }
 
-// float64 frame spectra of a host (samples, channels) float64 array: upload, window / twiddle tables, k_frames.
-// The caller has reserved c->io and carves `dsig` (n_samples * n_ch doubles) and `spec` out of it.
-struct X64Tables {
-    double* dw = nullptr;
-    double2* tw = nullptr;
-};
-static int x64_tables(ds_ctx* c, Carver& cv, const double* window, int W, X64Tables* t) {
-    t->dw = cv.take<double>(W);
-    t->tw = cv.take<double2>(W / 2);
-    HIPCHK(c, hipMemcpyAsync(t->dw, window, (size_t)W * 8, hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(w64::k_twiddles, dim3((W / 2 + 255) / 256), dim3(256), 0, c->stream, t->tw, W / 2);
-    HIPCHK(c, hipGetLastError());
-    return DS_OK;
-}
+// float64 frame spectra of a host (samples, channels) float64 array: upload, k_frames on the window / twiddle tables
+// (take_x64_tables() carves them, x64_tables() fills them)
 static int x64_frames(ds_ctx* c, const X64Tables& t, const double* sig, double* dsig, int n_ch, int64_t n_samples, int W,
                       int hop, int n_frames, int detrend, double2* spec) {
     HIPCHK(c, hipMemcpyAsync(dsig, sig, (size_t)n_samples * n_ch * 8, hipMemcpyHostToDevice, c->stream));
@@ -1918,22 +1929,23 @@ extern "C" int ds_welch_spec_x64(ds_ctx* c, const double* x, const double* y, in
     if (spec * n_in * sizeof(double2) > ((size_t)2 << 30))
         return fail(c, DS_ERR_UNSUP, "ds_welch_spec_x64: problem too large for the float64 route (use ds_welch_psd / ds_welch_csd)");
     HIPCHK(c, hipSetDevice(c->device));
-    const size_t bsig = (size_t)n_samples * n_ch * 8, bout = (size_t)nb * n_ch;
-    CHK(reserve(c, &c->io, &c->io_bytes, n_in * (Carver::pad(bsig) + Carver::pad(spec * 16)) + 2 * Carver::pad((size_t)W * 8) +
-                                             Carver::pad(bout * 16)));
-    Carver cv(c->io);
+    const size_t bout = (size_t)nb * n_ch;
     X64Tables t;
-    CHK(x64_tables(c, cv, window, W, &t));
-    double* dx = cv.take<double>((size_t)n_samples * n_ch);
-    double2* xs = cv.take<double2>(spec);
+    double *dx, *dy = nullptr;
+    double2 *xs, *ys = nullptr, *dout;
+    CHK(carve(c, &c->io, &c->io_bytes, [&](Carver& cv) {
+        t = take_x64_tables(cv, W);
+        dx = cv.take<double>((size_t)n_samples * n_ch);
+        xs = cv.take<double2>(spec);
+        if (y) {
+            dy = cv.take<double>((size_t)n_samples * n_ch);
+            ys = cv.take<double2>(spec);
+        }
+        dout = cv.take<double2>(bout);
+    }));
+    CHK(x64_tables(c, t, window, W));
     CHK(x64_frames(c, t, x, dx, n_ch, n_samples, W, hop, n_frames, detrend, xs));
-    double2* ys = nullptr;
-    if (y) {
-        double* dy = cv.take<double>((size_t)n_samples * n_ch);
-        ys = cv.take<double2>(spec);
-        CHK(x64_frames(c, t, y, dy, n_ch, n_samples, W, hop, n_frames, detrend, ys));
-    }
-    double2* dout = cv.take<double2>(bout);
+    if (y) CHK(x64_frames(c, t, y, dy, n_ch, n_samples, W, hop, n_frames, detrend, ys));
     if (average == DS_AVG_MEDIAN) {
         const int nbias = (n_frames & 1) ? n_frames : n_frames - 1;
         w64::SpecArgs sa{xs, ys, n_ch, n_frames, FinishPar{norm_scale * (double)std::max(1, nbias), factor, halve_edges, amp_sqrt, nb}, dout};
@@ -1961,15 +1973,17 @@ extern "C" int ds_csm_x64(ds_ctx* c, const double* x, int n_ch, int64_t n_sample
     if (spec * sizeof(double2) > ((size_t)2 << 30))
         return fail(c, DS_ERR_UNSUP, "ds_csm_x64: problem too large for the float64 route (use ds_csm)");
     HIPCHK(c, hipSetDevice(c->device));
-    CHK(reserve(c, &c->io, &c->io_bytes, Carver::pad((size_t)n_samples * n_ch * 8) + Carver::pad(spec * 16) +
-                                             2 * Carver::pad((size_t)W * 8) + Carver::pad(bout * 16)));
-    Carver cv(c->io);
     X64Tables t;
-    CHK(x64_tables(c, cv, window, W, &t));
-    double* dx = cv.take<double>((size_t)n_samples * n_ch);
-    double2* xs = cv.take<double2>(spec);
+    double* dx;
+    double2 *xs, *dcsm;
+    CHK(carve(c, &c->io, &c->io_bytes, [&](Carver& cv) {
+        t = take_x64_tables(cv, W);
+        dx = cv.take<double>((size_t)n_samples * n_ch);
+        xs = cv.take<double2>(spec);
+        dcsm = cv.take<double2>(bout);
+    }));
+    CHK(x64_tables(c, t, window, W));
     CHK(x64_frames(c, t, x, dx, n_ch, n_samples, W, hop, n_frames, detrend, xs));
-    double2* dcsm = cv.take<double2>(bout);
     if (average == DS_AVG_MEDIAN) {
         const int nbias = (n_frames & 1) ? n_frames : n_frames - 1;  // as ds_welch_spec_x64
         w64::CsmArgs ca{xs, n_ch, n_frames, FinishPar{norm_scale * (double)std::max(1, nbias), factor, halve_edges, amp_sqrt, nb}, dcsm};
@@ -2070,10 +2084,11 @@ static int csm_chunked(ds_ctx* c, const float* x, int n_ch, int64_t ld, int64_t 
                        int K, float2* csm) {
     const int nb = W / 2 + 1;
     const size_t part_elems = (size_t)nb * n_ch * n_ch;
-    CHK(reserve(c, &c->ws, &c->ws_bytes, Carver::pad(sizeof(float2) * (size_t)nb * n_frames * n_ch) + Carver::pad(sizeof(float2) * part_elems)));
-    Carver cv(c->ws);
-    float2* X = cv.take<float2>((size_t)nb * n_frames * n_ch);
-    float2* part = cv.take<float2>(part_elems);
+    float2 *X, *part;
+    CHK(carve(c, &c->ws, &c->ws_bytes, [&](Carver& cv) {
+        X = cv.take<float2>((size_t)nb * n_frames * n_ch);
+        part = cv.take<float2>(part_elems);
+    }));
     if (c->ev_chunk[0] == nullptr)
         for (auto& e : c->ev_chunk) HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
     hipStream_t main_stream = c->stream;
@@ -2125,18 +2140,20 @@ static int csm_dev(ds_ctx* c, const float* x, int n_ch, int64_t ld, int64_t n_sa
         const int bpb = median_bins_per_block(2, n_frames, &lds);
         if (!bpb)
             return fail(c, DS_ERR_UNSUP, "ds_csm: median averaging over more than 19 199 frames is not built yet");
-        size_t bytes = Carver::pad(sizeof(float2) * (size_t)n_ch * n_frames * nb);
         WelchPlan pl = plan_welch(n_frames, n_ch);
-        bytes += big ? stft_big_ws(n_ch, n_frames, W) : Carver::pad(sizeof(float) * (size_t)pl.n_chunks * n_ch * nb);
-        CHK(reserve(c, &c->ws, &c->ws_bytes, bytes));
-        Carver cv(c->ws);
-        float2* xsp = cv.take<float2>((size_t)n_ch * n_frames * nb);
+        float2* xsp;
+        BigScratch s;
+        float* scratch;
+        CHK(carve(c, &c->ws, &c->ws_bytes, [&](Carver& cv) {
+            xsp = cv.take<float2>((size_t)n_ch * n_frames * nb);
+            if (big) s = take_big_scratch(cv, n_ch, n_frames, W);
+            else scratch = cv.take<float>((size_t)pl.n_chunks * n_ch * nb);
+        }));
         if (big) {
-            CHK(stft_big(c, cv, x, n_ch, ld, n_samples, W, hop, W, 0, n_frames, window, detrend, 1.0f, 1.0f, 0, 0, xsp));
+            CHK(stft_big(c, s, x, n_ch, ld, n_samples, W, hop, W, 0, n_frames, window, detrend, 1.0f, 1.0f, 0, 0, xsp));
         } else {
             const float2* tw;
             CHK(get_twiddles(c, W, &tw));
-            float* scratch = cv.take<float>((size_t)pl.n_chunks * n_ch * nb);
             XspecArgs ax{x, n_samples, ld, n_ch, W, hop, n_frames, detrend, pl.fpc, window, tw, xsp, scratch};
             DISPATCH_N(W, CHK(launch(c, "welch_xspec", k_xspec<NN>, dim3(pl.n_chunks, n_ch), Cfg<NN>::NT, Cfg<NN>::LDS_BYTES, ax)));
         }
@@ -2160,13 +2177,14 @@ static int csm_dev(ds_ctx* c, const float* x, int n_ch, int64_t ld, int64_t n_sa
                                halve_edges, K, (float2*)csm);
     }
     // the STFT buffer X[b][f][c] (+ the four-step scratch for long windows) in the workspace
-    size_t bytes = Carver::pad(sizeof(float2) * (size_t)nb * n_frames * n_ch);
-    if (big) bytes += stft_big_ws(n_ch, n_frames, W);
-    CHK(reserve(c, &c->ws, &c->ws_bytes, bytes));
-    Carver cv(c->ws);
-    float2* X = cv.take<float2>((size_t)nb * n_frames * n_ch);
+    float2* X;
+    BigScratch s;
+    CHK(carve(c, &c->ws, &c->ws_bytes, [&](Carver& cv) {
+        X = cv.take<float2>((size_t)nb * n_frames * n_ch);
+        if (big) s = take_big_scratch(cv, n_ch, n_frames, W);
+    }));
     if (big)
-        CHK(stft_big(c, cv, x, n_ch, ld, n_samples, W, hop, W, 0, n_frames, window, detrend, 1.0f, 1.0f, 0, 1, X));
+        CHK(stft_big(c, s, x, n_ch, ld, n_samples, W, hop, W, 0, n_frames, window, detrend, 1.0f, 1.0f, 0, 1, X));
     else
         CHK(ds_stft_r2c_dev(c, x, n_samples, n_ch, ld, W, hop, W, 0, n_frames, window, detrend, 1.0f, 1.0f,
                             0, (ds_c32*)X));
@@ -2237,10 +2255,8 @@ extern "C" int ds_csm_spec(ds_ctx* c, const ds_c32* X, int n_bins, int n_frames,
     if (!c || !X || !csm) return fail(c, DS_ERR_ARG, "ds_csm_spec: null argument");
     if (n_bins <= 0 || n_frames <= 0 || n_ch <= 0) return fail(c, DS_ERR_ARG, "ds_csm_spec: bad shape");
     size_t nx = (size_t)n_bins * n_frames * n_ch, no = (size_t)n_bins * n_ch * n_ch;
-    CHK(reserve(c, &c->io, &c->io_bytes, Carver::pad(nx * 8) + Carver::pad(no * 8) + 4096));
-    Carver cv(c->io);
-    float2* dx = cv.take<float2>(nx);
-    float2* dc = cv.take<float2>(no);
+    float2 *dx, *dc;
+    CHK(carve(c, &c->io, &c->io_bytes, [&](Carver& cv) { dx = cv.take<float2>(nx); dc = cv.take<float2>(no); }));
     CHK(ds_upload(c, dx, X, nx * 8));
     CHK(ds_csm_spec_dev(c, (const ds_c32*)dx, n_bins, n_frames, n_ch, amp_sqrt, norm_scale, factor,
                         halve_edges, (ds_c32*)dc));
@@ -2281,11 +2297,13 @@ extern "C" int ds_das_map(ds_ctx* c, const ds_c32* csm, const ds_c32* h, int n_b
     if (!c || !csm || !h || !map) return fail(c, DS_ERR_ARG, "ds_das_map: null argument");
     if (n_bins <= 0 || n_ch <= 0 || n_grid <= 0) return fail(c, DS_ERR_ARG, "ds_das_map: bad shape");
     size_t nc = (size_t)n_bins * n_ch * n_ch, nh = (size_t)n_bins * n_ch * n_grid, nm = (size_t)n_grid * n_bins;
-    CHK(reserve(c, &c->io, &c->io_bytes, Carver::pad(nc * 8) + Carver::pad(nh * 8) + Carver::pad(nm * 4) + 4096));
-    Carver cv(c->io);
-    float2* dc = cv.take<float2>(nc);
-    float2* dh = cv.take<float2>(nh);
-    float* dm = cv.take<float>(nm);
+    float2 *dc, *dh;
+    float* dm;
+    CHK(carve(c, &c->io, &c->io_bytes, [&](Carver& cv) {
+        dc = cv.take<float2>(nc);
+        dh = cv.take<float2>(nh);
+        dm = cv.take<float>(nm);
+    }));
     CHK(ds_upload(c, dc, csm, nc * 8));
     CHK(ds_upload(c, dh, h, nh * 8));
     CHK(ds_das_map_dev(c, (const ds_c32*)dc, (const ds_c32*)dh, n_bins, n_ch, n_grid, dm));
@@ -2313,11 +2331,13 @@ extern "C" int ds_bf_eigh(ds_ctx* c, const double* a, int n_bins, int n_ch, doub
     if (!c || !a || !w || !v) return fail(c, DS_ERR_ARG, "ds_bf_eigh: null argument");
     CHK(bf_shape_ok(c, "ds_bf_eigh", n_bins, n_ch, 1));
     const size_t nm = (size_t)n_bins * n_ch * n_ch, nw = (size_t)n_bins * n_ch;
-    CHK(reserve(c, &c->io, &c->io_bytes, 2 * Carver::pad(nm * 16) + Carver::pad(nw * 8)));
-    Carver cv(c->io);
-    double2* da = cv.take<double2>(nm);
-    double2* dv = cv.take<double2>(nm);
-    double* dw = cv.take<double>(nw);
+    double2 *da, *dv;
+    double* dw;
+    CHK(carve(c, &c->io, &c->io_bytes, [&](Carver& cv) {
+        da = cv.take<double2>(nm);
+        dv = cv.take<double2>(nm);
+        dw = cv.take<double>(nw);
+    }));
     CHK(ds_upload(c, da, a, nm * 16));
     CHK(ds_bf_eigh_dev(c, (const double*)da, n_bins, n_ch, dw, (double*)dv));
     CHK(ds_download(c, w, dw, nw * 8));
@@ -2334,11 +2354,13 @@ extern "C" int ds_bf_eig_map_dev(ds_ctx* c, const double* csm, const double* h, 
         return fail(c, DS_ERR_ARG, "ds_bf_eig_map: n_eig must be in [1, n_ch]");
     if (method != bf::ORTHOGONAL) n_eig = 0;
     const size_t nm = (size_t)n_bins * n_ch * n_ch, nw = (size_t)n_bins * n_ch, np = (size_t)n_bins * n_eig * n_grid;
-    CHK(reserve(c, &c->ws, &c->ws_bytes, Carver::pad(nm * 16) + Carver::pad(nw * 8) + Carver::pad(np * 8) + 256));
-    Carver cv(c->ws);
-    double2* dv = cv.take<double2>(nm);
-    double* dw = cv.take<double>(nw);
-    double* dp = np ? cv.take<double>(np) : nullptr;
+    double2* dv;
+    double *dw, *dp;
+    CHK(carve(c, &c->ws, &c->ws_bytes, [&](Carver& cv) {
+        dv = cv.take<double2>(nm);
+        dw = cv.take<double>(nw);
+        dp = np ? cv.take<double>(np) : nullptr;
+    }));
     CHK(ds_bf_eigh_dev(c, csm, n_bins, n_ch, dw, (double*)dv));
     bf::ProjArgs pa{dw, dv, (const double2*)h, n_ch, n_grid, n_bins, method, n_eig, gamma, map, dp};
     CHK(launch(c, "bf_project", bf::k_bf_project, dim3((n_grid + bf::THREADS - 1) / bf::THREADS, n_bins),
@@ -2352,11 +2374,13 @@ extern "C" int ds_bf_eig_map(ds_ctx* c, const double* csm, const double* h, int 
     if (!c || !csm || !h || !map) return fail(c, DS_ERR_ARG, "ds_bf_eig_map: null argument");
     CHK(bf_shape_ok(c, "ds_bf_eig_map", n_bins, n_ch, n_grid));
     const size_t nc = (size_t)n_bins * n_ch * n_ch, nh = (size_t)n_bins * n_ch * n_grid, nm = (size_t)n_grid * n_bins;
-    CHK(reserve(c, &c->io, &c->io_bytes, Carver::pad(nc * 16) + Carver::pad(nh * 16) + Carver::pad(nm * 8)));
-    Carver cv(c->io);
-    double2* dc = cv.take<double2>(nc);
-    double2* dh = cv.take<double2>(nh);
-    double* dm = cv.take<double>(nm);
+    double2 *dc, *dh;
+    double* dm;
+    CHK(carve(c, &c->io, &c->io_bytes, [&](Carver& cv) {
+        dc = cv.take<double2>(nc);
+        dh = cv.take<double2>(nh);
+        dm = cv.take<double>(nm);
+    }));
     CHK(ds_upload(c, dc, csm, nc * 16));
     CHK(ds_upload(c, dh, h, nh * 16));
     CHK(ds_bf_eig_map_dev(c, (const double*)dc, (const double*)dh, n_bins, n_ch, n_grid, method, gamma, n_eig, dm));
@@ -2369,9 +2393,8 @@ extern "C" int ds_bf_cleansc_dev(ds_ctx* c, const double* csm, const double* h, 
     CHK(bf_shape_ok(c, "ds_bf_cleansc", n_bins, n_ch, n_grid));
     if (max_iter <= 0) return fail(c, DS_ERR_ARG, "ds_bf_cleansc: max_iter must be positive");
     if (!(safety > 0.0 && safety <= 1.0)) return fail(c, DS_ERR_ARG, "ds_bf_cleansc: safety factor must be in (0, 1]");
-    CHK(reserve(c, &c->ws, &c->ws_bytes, Carver::pad((size_t)n_bins * n_grid * 8)));
-    Carver cv(c->ws);
-    double* dr = cv.take<double>((size_t)n_bins * n_grid);
+    double* dr;
+    CHK(carve(c, &c->ws, &c->ws_bytes, [&](Carver& cv) { dr = cv.take<double>((size_t)n_bins * n_grid); }));
     bf::CleanArgs ca{(const double2*)csm, (const double2*)h, n_ch, n_grid, n_bins, max_iter, remove_diagonal ? 1 : 0,
                      safety, dr, map};
     return launch(c, "bf_cleansc", bf::k_bf_cleansc, dim3(n_bins), bf::THREADS, 0, ca);
@@ -2382,11 +2405,13 @@ extern "C" int ds_bf_cleansc(ds_ctx* c, const double* csm, const double* h, int 
     if (!c || !csm || !h || !map) return fail(c, DS_ERR_ARG, "ds_bf_cleansc: null argument");
     CHK(bf_shape_ok(c, "ds_bf_cleansc", n_bins, n_ch, n_grid));
     const size_t nc = (size_t)n_bins * n_ch * n_ch, nh = (size_t)n_bins * n_ch * n_grid, nm = (size_t)n_grid * n_bins;
-    CHK(reserve(c, &c->io, &c->io_bytes, Carver::pad(nc * 16) + Carver::pad(nh * 16) + Carver::pad(nm * 8)));
-    Carver cv(c->io);
-    double2* dc = cv.take<double2>(nc);
-    double2* dh = cv.take<double2>(nh);
-    double* dm = cv.take<double>(nm);
+    double2 *dc, *dh;
+    double* dm;
+    CHK(carve(c, &c->io, &c->io_bytes, [&](Carver& cv) {
+        dc = cv.take<double2>(nc);
+        dh = cv.take<double2>(nh);
+        dm = cv.take<double>(nm);
+    }));
     CHK(ds_upload(c, dc, csm, nc * 16));
     CHK(ds_upload(c, dh, h, nh * 16));
     CHK(ds_bf_cleansc_dev(c, (const double*)dc, (const double*)dh, n_bins, n_ch, n_grid, max_iter, safety,
@@ -2439,10 +2464,11 @@ static int check_big_len(ds_ctx* c, int64_t n, const char* what) {
 static int rfft_big(ds_ctx* c, const float* x, int n_ch, int64_t ld, int64_t n_samples, int64_t N,
                     float scale, float2* spec) {
     const int npair = (n_ch + 1) / 2;
-    CHK(reserve(c, &c->ws, &c->ws_bytes, 2 * Carver::pad(sizeof(float2) * (size_t)npair * N)));
-    Carver cv(c->ws);
-    float2* P = cv.take<float2>((size_t)npair * N);
-    float2* Q = cv.take<float2>((size_t)npair * N);
+    float2 *P, *Q;
+    CHK(carve(c, &c->ws, &c->ws_bytes, [&](Carver& cv) {
+        P = cv.take<float2>((size_t)npair * N);
+        Q = cv.take<float2>((size_t)npair * N);
+    }));
     CHK(big_cols(c, nullptr, x, n_ch, ld, n_samples, P, N, npair));
     CHK(big_rows(c, P, Q, N, npair));
     dsbig::UnpackArgs u{Q, N, n_ch, scale, spec, n_ch, 1};
@@ -2454,10 +2480,11 @@ static int deconv_big(ds_ctx* c, const float* y, int n_items, int n_ch, int64_t 
                       int64_t N, const float2* r, int r_per_channel, int64_t n_out, int64_t ld_out,
                       float* ir) {
     const int npair = (n_ch + 1) / 2, batch = n_items * npair;
-    CHK(reserve(c, &c->ws, &c->ws_bytes, 2 * Carver::pad(sizeof(float2) * (size_t)batch * N)));
-    Carver cv(c->ws);
-    float2* P = cv.take<float2>((size_t)batch * N);
-    float2* Q = cv.take<float2>((size_t)batch * N);
+    float2 *P, *Q;
+    CHK(carve(c, &c->ws, &c->ws_bytes, [&](Carver& cv) {
+        P = cv.take<float2>((size_t)batch * N);
+        Q = cv.take<float2>((size_t)batch * N);
+    }));
     CHK(big_cols(c, nullptr, y, n_ch, ld, n_samples, P, N, batch));
     CHK(big_rows(c, P, Q, N, batch));
     dsbig::MulArgs m{Q, N, n_ch, r_per_channel, r};
@@ -2475,13 +2502,17 @@ static int deconv_big(ds_ctx* c, const float* y, int n_items, int n_ch, int64_t 
 static int64_t stft_big_group(int64_t nfft, int64_t batch) {
     return std::max<int64_t>(1, std::min<int64_t>({batch, ((int64_t)1 << 25) / nfft, (int64_t)32768}));
 }
-static size_t stft_big_ws(int n_ch, int n_frames, int64_t nfft) {
-    const int64_t batch = (int64_t)n_ch * ((n_frames + 1) / 2);
-    const int64_t g = stft_big_group(nfft, batch);
-    return 2 * Carver::pad(sizeof(float2) * (size_t)g * nfft) + Carver::pad(sizeof(float) * (size_t)n_ch * n_frames);
+static BigScratch take_big_scratch(Carver& cv, int n_ch, int n_frames, int64_t nfft) {
+    const int64_t grp = stft_big_group(nfft, (int64_t)n_ch * ((n_frames + 1) / 2));
+    BigScratch s;
+    s.P = cv.take<float2>((size_t)grp * nfft);
+    s.Q = cv.take<float2>((size_t)grp * nfft);
+    s.means = cv.take<float>((size_t)n_ch * n_frames);
+    return s;
 }
 // layout 0: out[(c*F + f)*nb + k] (unscaled spectra for the Welch sums), 1: out[(k*F + f)*C + c]
-static int stft_big(ds_ctx* c, Carver& cv, const float* x, int n_ch, int64_t ld, int64_t n_samples,
+// s: take_big_scratch() for at least n_ch channels and n_frames frames
+static int stft_big(ds_ctx* c, const BigScratch& s, const float* x, int n_ch, int64_t ld, int64_t n_samples,
                     int W, int hop, int64_t nfft, int64_t pad_front, int n_frames, const float* window,
                     int detrend, float scale, float edge_scale, int power, int layout, float2* out) {
     CHK(check_big_len(c, nfft, "framed transform length"));
@@ -2489,9 +2520,8 @@ static int stft_big(ds_ctx* c, Carver& cv, const float* x, int n_ch, int64_t ld,
     const int n2 = (int)(nfft / N1);
     const int64_t batch = (int64_t)n_ch * ((n_frames + 1) / 2);
     const int64_t grp = stft_big_group(nfft, batch);
-    float2* P = cv.take<float2>((size_t)grp * nfft);
-    float2* Q = cv.take<float2>((size_t)grp * nfft);
-    float* means = cv.take<float>((size_t)n_ch * n_frames);
+    float2 *P = s.P, *Q = s.Q;
+    float* means = s.means;
     if (detrend) {
         dsbig::FrameMeansArgs m{x, n_samples, ld, pad_front, n_ch, W, hop, n_frames, window, means};
         CHK(launch(c, "bigfft_means", dsbig::k_frame_means, dim3(n_frames, n_ch), 256, 0, m));
@@ -2525,24 +2555,21 @@ static int welch_big(ds_ctx* c, int kind, const float* x, int n_cx, int64_t ldx,
     const int med_bpb = median_bins_per_block(3, n_frames, &med_lds);
     if (average == DS_AVG_MEDIAN && !med_bpb)
         return fail(c, DS_ERR_UNSUP, "welch: median averaging over more than 12 799 frames is not built yet");
-    size_t bytes = stft_big_ws(nmax, n_frames, W) + Carver::pad(sizeof(float2) * (size_t)n_cx * n_frames * nb) +
-                   Carver::pad(sizeof(float2) * (size_t)std::max(1, nyc) * n_frames * nb) +
-                   Carver::pad(sizeof(float) * (size_t)n_cx * nb) +
-                   Carver::pad(sizeof(float2) * (size_t)std::max(1, nyc) * nb) +
-                   Carver::pad(sizeof(float) * (size_t)std::max(1, nyc) * nb);
-    CHK(reserve(c, &c->ws, &c->ws_bytes, bytes));
-    Carver cv(c->ws);
-    float2* xsp = cv.take<float2>((size_t)n_cx * n_frames * nb);
-    float2* ysp = cv.take<float2>((size_t)std::max(1, nyc) * n_frames * nb);
-    float* pxx = cv.take<float>((size_t)n_cx * nb);
-    float2* pxy = cv.take<float2>((size_t)std::max(1, nyc) * nb);
-    float* pyy = cv.take<float>((size_t)std::max(1, nyc) * nb);
-    Carver scratch = cv;  // the FFT scratch is reused by both signals
-    CHK(stft_big(c, scratch, x, n_cx, ldx, n_samples, W, hop, W, 0, n_frames, window, detrend, 1.0f, 1.0f, 0,
+    float2 *xsp, *ysp, *pxy;
+    float *pxx, *pyy;
+    BigScratch s;  // the FFT scratch is reused by both signals
+    CHK(carve(c, &c->ws, &c->ws_bytes, [&](Carver& cv) {
+        xsp = cv.take<float2>((size_t)n_cx * n_frames * nb);
+        ysp = cv.take<float2>((size_t)std::max(1, nyc) * n_frames * nb);
+        pxx = cv.take<float>((size_t)n_cx * nb);
+        pxy = cv.take<float2>((size_t)std::max(1, nyc) * nb);
+        pyy = cv.take<float>((size_t)std::max(1, nyc) * nb);
+        s = take_big_scratch(cv, nmax, n_frames, W);
+    }));
+    CHK(stft_big(c, s, x, n_cx, ldx, n_samples, W, hop, W, 0, n_frames, window, detrend, 1.0f, 1.0f, 0,
                  0, xsp));
     if (nyc) {
-        scratch = cv;
-        CHK(stft_big(c, scratch, y, nyc, ldy, n_samples, W, hop, W, 0, n_frames, window, detrend, 1.0f, 1.0f,
+        CHK(stft_big(c, s, y, nyc, ldy, n_samples, W, hop, W, 0, n_frames, window, detrend, 1.0f, 1.0f,
                      0, 0, ysp));
     }
     double count = (double)n_frames;
@@ -2642,12 +2669,12 @@ static int rfft_blue(ds_ctx* c, const float* x, int n_ch, int64_t ld, int64_t n_
                      float scale, float2* spec) {
     const int npair = (n_ch + 1) / 2;
     const int64_t M = blue_len(L);
-    CHK(reserve(c, &c->ws, &c->ws_bytes, 2 * Carver::pad(sizeof(float2) * (size_t)npair * M) +
-                                             Carver::pad(sizeof(float2) * (size_t)npair * L)));
-    Carver cv(c->ws);
-    float2* P = cv.take<float2>((size_t)npair * M);
-    float2* Q = cv.take<float2>((size_t)npair * M);
-    float2* X = cv.take<float2>((size_t)npair * L);
+    float2 *P, *Q, *X;
+    CHK(carve(c, &c->ws, &c->ws_bytes, [&](Carver& cv) {
+        P = cv.take<float2>((size_t)npair * M);
+        Q = cv.take<float2>((size_t)npair * M);
+        X = cv.take<float2>((size_t)npair * L);
+    }));
     CHK(blue_dft(c, x, n_ch, ld, n_samples, nullptr, npair, L, M, P, Q, X));
     hipLaunchKernelGGL(dsblue::k_unpack, dim3(512, npair), dim3(256), 0, c->stream, (const float2*)X, L, n_ch,
                        scale, spec);
@@ -2660,13 +2687,13 @@ static int deconv_blue(ds_ctx* c, const float* y, int n_items, int n_ch, int64_t
                        float* ir) {
     const int npair = (n_ch + 1) / 2, batch = n_items * npair;
     const int64_t M = blue_len(L);
-    CHK(reserve(c, &c->ws, &c->ws_bytes, 2 * Carver::pad(sizeof(float2) * (size_t)batch * M) +
-                                             2 * Carver::pad(sizeof(float2) * (size_t)batch * L)));
-    Carver cv(c->ws);
-    float2* P = cv.take<float2>((size_t)batch * M);
-    float2* Q = cv.take<float2>((size_t)batch * M);
-    float2* X = cv.take<float2>((size_t)batch * L);
-    float2* Y = cv.take<float2>((size_t)batch * L);
+    float2 *P, *Q, *X, *Y;
+    CHK(carve(c, &c->ws, &c->ws_bytes, [&](Carver& cv) {
+        P = cv.take<float2>((size_t)batch * M);
+        Q = cv.take<float2>((size_t)batch * M);
+        X = cv.take<float2>((size_t)batch * L);
+        Y = cv.take<float2>((size_t)batch * L);
+    }));
     CHK(blue_dft(c, y, n_ch, ld, n_samples, nullptr, batch, L, M, P, Q, X));
     hipLaunchKernelGGL(dsblue::k_mul_r, dim3(512, batch), dim3(256), 0, c->stream, X, L, n_ch, r_per_channel, r);
     HIPCHK(c, hipGetLastError());
@@ -2814,14 +2841,13 @@ static int fir_long(ds_ctx* c, const float* x, int n_ch, int64_t ldx, int64_t n_
     const int npair = (n_ch + 1) / 2;
     const int G = (int)std::max<int64_t>(1, std::min<int64_t>(n_filt, ((int64_t)1 << 25) / (npair * L)));
     const size_t scratch = (size_t)G * npair * L;
-    CHK(reserve(c, &c->ws, &c->ws_bytes,
-                Carver::pad(sizeof(float2) * (size_t)n_filt * nb) + Carver::pad(sizeof(float2) * (size_t)npair * L) +
-                    2 * Carver::pad(sizeof(float2) * scratch)));
-    Carver cv(c->ws);
-    float2* R = cv.take<float2>((size_t)n_filt * nb);
-    float2* Qs = cv.take<float2>((size_t)npair * L);
-    float2* P = cv.take<float2>(scratch);
-    float2* S = cv.take<float2>(scratch);
+    float2 *R, *Qs, *P, *S;
+    CHK(carve(c, &c->ws, &c->ws_bytes, [&](Carver& cv) {
+        R = cv.take<float2>((size_t)n_filt * nb);
+        Qs = cv.take<float2>((size_t)npair * L);
+        P = cv.take<float2>(scratch);
+        S = cv.take<float2>(scratch);
+    }));
     constexpr int N1 = 1024;
     const int n2 = (int)(L / N1);
     const float2* tw;
@@ -2870,9 +2896,8 @@ static int fir4k_run(ds_ctx* c, const float* x, int n_ch, int64_t ldx, int64_t n
         HIPCHK(c, hipStreamSynchronize(c->stream));
     }
     const int P = f4::partitions(n_taps);
-    CHK(reserve(c, &c->ws, &c->ws_bytes, Carver::pad(sizeof(float4) * (size_t)n_filt * P * 8 * 256)));
-    Carver cv(c->ws);
-    float4* hp = cv.take<float4>((size_t)n_filt * P * 8 * 256);
+    float4* hp;
+    CHK(carve(c, &c->ws, &c->ws_bytes, [&](Carver& cv) { hp = cv.take<float4>((size_t)n_filt * P * 8 * 256); }));
     f4::TapArgs ta{taps, n_filt, n_taps, P, c->w4_tables, hp};
     CHK(launch(c, "fir_taps", f4::k_taps, dim3((unsigned)(n_filt * P)), f4::NT, f4::LDS_BYTES, ta));
     const int pairs = (n_ch + 1) / 2;
@@ -2915,9 +2940,11 @@ static int fir_once(ds_ctx* c, const float* x, int n_ch, int64_t ldx, int64_t n_
     CHK(get_twiddles(c, N, &tw));
     const bool no16k = c->cfg.fir_generic;
     const bool use16k = N == fir16k::NBIG && !no16k;
-    CHK(reserve(c, &c->ws, &c->ws_bytes, (use16k ? 2 : 1) * Carver::pad(sizeof(float2) * (size_t)n_filt * N)));
-    Carver cvw(c->ws);
-    float2* hs = cvw.take<float2>((size_t)n_filt * N);
+    float2 *hs, *hperm;  // tap spectra (16384-point blocks: and their permuted copy)
+    CHK(carve(c, &c->ws, &c->ws_bytes, [&](Carver& cv) {
+        hs = cv.take<float2>((size_t)n_filt * N);
+        hperm = use16k ? cv.take<float2>((size_t)n_filt * N) : nullptr;
+    }));
     {
         FirTapsArgs a{taps, n_filt, n_taps, tw, hs};
         DISPATCH_N(N, CHK(launch(c, "fir_taps", k_fir_taps<NN>, dim3((n_filt + 1) / 2), Cfg<NN>::NT, Cfg<NN>::LDS_BYTES, a)));
@@ -2940,7 +2967,6 @@ static int fir_once(ds_ctx* c, const float* x, int n_ch, int64_t ldx, int64_t n_
             HIPCHK(c, hipMemcpyAsync(c->fir16k_tables, h.data(), sizeof(float2) * h.size(), hipMemcpyHostToDevice, c->stream));
             HIPCHK(c, hipStreamSynchronize(c->stream));
         }
-        float2* hperm = cvw.take<float2>((size_t)n_filt * N);
         fir16k::PermArgs pa{hs, n_filt, hperm};
         CHK(launch(c, "fir_taps", fir16k::k_permute, dim3((unsigned)(((int64_t)n_filt * N + 255) / 256)), 256, 0, pa));
         fir16k::Args a{x, n_samples, ldx, ld_y, n_ch, n_filt, n_taps, c->w4_tables, c->fir16k_tables, hperm, y, 0};
@@ -3044,12 +3070,13 @@ extern "C" int ds_fir_ola_dev(ds_ctx* c, const float* x, int n_ch, int64_t ldx, 
         // filter once -- no fp32 round trip of the intermediate signals through HBM.
         const int64_t n_comb = (int64_t)n_filt * (n_taps - 1) + 1;
         if (n_filt > 1 && n_comb - 1 <= kMaxBigFft / 2 && (double)n_comb * n_taps <= 1.0e10) {
-            CHK(reserve(c, &c->aux, &c->aux_bytes,
-                        2 * Carver::pad(sizeof(double) * (size_t)n_comb) + Carver::pad(sizeof(float) * (size_t)n_comb)));
-            Carver cv(c->aux);
-            double* pa = cv.take<double>((size_t)n_comb);
-            double* pb = cv.take<double>((size_t)n_comb);
-            float* bf = cv.take<float>((size_t)n_comb);
+            double *pa, *pb;
+            float* bf;
+            CHK(carve(c, &c->aux, &c->aux_bytes, [&](Carver& cv) {
+                pa = cv.take<double>((size_t)n_comb);
+                pb = cv.take<double>((size_t)n_comb);
+                bf = cv.take<float>((size_t)n_comb);
+            }));
             hipLaunchKernelGGL(k_taps_to_f64, dim3((n_taps + 255) / 256), dim3(256), 0, c->stream, taps, n_taps, pa);
             int len = n_taps;
             for (int k = 1; k < n_filt; ++k) {
@@ -3094,49 +3121,8 @@ extern "C" int ds_debug_welch_timing(unsigned long long out[16]) {
 #endif
 
 // ---- host-pointer entry points -------------------------------------------------
-struct Stage {  // device staging out of ctx->io
-    ds_ctx* c;
-    Carver cv;
-    explicit Stage(ds_ctx* ctx) : c(ctx), cv(ctx->io) {}
-};
-static int stage_reserve(ds_ctx* c, size_t bytes) { return reserve(c, &c->io, &c->io_bytes, bytes + 4096); }
-
-extern "C" int ds_stft_r2c(ds_ctx* c, const float* x, int64_t n_samples, int n_ch, int W, int hop,
-                           int nfft, int64_t pad_front, int n_frames, const float* window, int detrend,
-                           float scale, float edge_scale, int power, ds_c32* out) {
-    if (!c || !x || !window || !out) return fail(c, DS_ERR_ARG, "ds_stft_r2c: null argument");
-    if (n_ch <= 0 || n_samples <= 0 || W <= 0 || n_frames <= 0 || nfft <= 0) return fail(c, DS_ERR_ARG, "ds_stft_r2c: bad shape");
-    size_t nx = (size_t)n_ch * n_samples, no = (size_t)(nfft / 2 + 1) * n_frames * n_ch;
-    CHK(stage_reserve(c, Carver::pad(nx * 4) + Carver::pad((size_t)W * 4) + Carver::pad(no * 8)));
-    Carver cv(c->io);
-    float* dx = cv.take<float>(nx);
-    float* dw = cv.take<float>(W);
-    float2* dout = cv.take<float2>(no);
-    CHK(ds_upload(c, dx, x, nx * 4));
-    CHK(ds_upload(c, dw, window, (size_t)W * 4));
-    CHK(ds_stft_r2c_dev(c, dx, n_samples, n_ch, n_samples, W, hop, nfft, pad_front, n_frames, dw, detrend,
-                        scale, edge_scale, power, (ds_c32*)dout));
-    return ds_download(c, out, dout, no * 8);
-}
-
-extern "C" int ds_istft(ds_ctx* c, const ds_c32* stft, int n_bins, int n_frames, int n_ch, int nfft, int W,
-                        int step, int frame_offset, int n_frames_total, const float* window, float scale,
-                        int64_t total_length, float* out) {
-    if (!c || !stft || !window || !out) return fail(c, DS_ERR_ARG, "ds_istft: null argument");
-    if (n_bins <= 0 || n_frames <= 0 || n_ch <= 0 || W <= 0 || total_length <= 0)
-        return fail(c, DS_ERR_ARG, "ds_istft: bad shape");
-    size_t ns = (size_t)n_bins * n_frames * n_ch, no = (size_t)n_ch * total_length;
-    CHK(stage_reserve(c, Carver::pad(ns * 8) + Carver::pad((size_t)W * 4) + Carver::pad(no * 4)));
-    Carver cv(c->io);
-    float2* ds = cv.take<float2>(ns);
-    float* dw = cv.take<float>(W);
-    float* dout = cv.take<float>(no);
-    CHK(ds_upload(c, ds, stft, ns * 8));
-    CHK(ds_upload(c, dw, window, (size_t)W * 4));
-    CHK(ds_istft_dev(c, (const ds_c32*)ds, n_bins, n_frames, n_ch, nfft, W, step, frame_offset, n_frames_total,
-                     dw, scale, total_length, dout, total_length));
-    return ds_download(c, out, dout, no * 4);
-}
+// Each stages its arrays in ctx->io around the _dev entry.  The *_f64 entries take the reference's own float64 layouts
+// and cross the boundary through the pinned pipelines below; the others copy planar fp32 arrays as they are.
 
 // Fused boundary upload: (samples, channels) float64 C-order host array -> planar float32 device
 // rows.  Chunks of samples are cast + transposed by host threads straight into one of two pinned
@@ -3176,7 +3162,10 @@ struct HipTransport {
         return ok(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->stream)) && mark(b);
     }
 };
-static int pin_ready(ds_ctx* c, bool drain) {
+// One run of a host_marshal.hpp pipeline, pipe(transport, pinned chunks), on the context's two pinned chunks
+// (allocated on first use; drain: wait for their pending copies first).  `what` names the pipeline in errors.
+template <class F>
+static int pinned(ds_ctx* c, bool drain, const char* what, F&& pipe) {
     for (int i = 0; i < 2; ++i) {
         if (!c->pin[i]) {
             HIPCHK(c, hipHostMalloc(&c->pin[i], kPinBytes, hipHostMallocDefault));
@@ -3187,76 +3176,145 @@ static int pin_ready(ds_ctx* c, bool drain) {
             c->pin_busy[i] = false;
         }
     }
-    return DS_OK;
-}
-static int pipe_result(ds_ctx* c, bool ok, const HipTransport& tr, const char* what) {
-    if (ok) return DS_OK;
+    HipTransport tr{c};
+    float* const pin[2] = {(float*)c->pin[0], (float*)c->pin[1]};
+    if (pipe(tr, pin)) return DS_OK;
     if (tr.err != hipSuccess) return fail(c, DS_ERR_HIP, std::string(what) + ": " + hipGetErrorString(tr.err));
     return fail(c, DS_ERR_UNSUP, std::string(what) + ": too many channels for the staging chunk");
 }
-static int upload_planar_f64(ds_ctx* c, const double* src, int64_t n_samples, int n_ch, float* dst_dev,
-                             int64_t ld) {
-    CHK(pin_ready(c, false));
-    HipTransport tr{c};
-    float* pin[2] = {(float*)c->pin[0], (float*)c->pin[1]};
-    return pipe_result(c, dshost::upload_planar(tr, pin, kPinBytes, src, n_samples, n_ch, dst_dev, ld), tr, "upload_planar_f64");
-}
 static int upload_narrow_f64(ds_ctx* c, const double* src, int64_t n, float* dst_dev) {
-    CHK(pin_ready(c, false));
-    HipTransport tr{c};
-    float* pin[2] = {(float*)c->pin[0], (float*)c->pin[1]};
-    return pipe_result(c, dshost::upload_narrow(tr, pin, kPinBytes, src, n, dst_dev), tr, "upload_narrow_f64");
+    return pinned(c, false, "upload_narrow_f64", [&](HipTransport& tr, float* const* pin) {
+        return dshost::upload_narrow(tr, pin, kPinBytes, src, n, dst_dev);
+    });
 }
 static int download_widen(ds_ctx* c, const float* src_dev, int64_t n, double* dst) {
-    CHK(pin_ready(c, true));
-    HipTransport tr{c};
-    float* pin[2] = {(float*)c->pin[0], (float*)c->pin[1]};
-    return pipe_result(c, dshost::download_widen(tr, pin, kPinBytes, src_dev, n, dst), tr, "download_widen");
+    return pinned(c, true, "download_widen", [&](HipTransport& tr, float* const* pin) {
+        return dshost::download_widen(tr, pin, kPinBytes, src_dev, n, dst);
+    });
 }
 static int download_interleave(ds_ctx* c, const float* src_dev, int64_t n_samples, int n_ch, int64_t ld,
                                double* dst) {
-    CHK(pin_ready(c, true));
-    HipTransport tr{c};
-    float* pin[2] = {(float*)c->pin[0], (float*)c->pin[1]};
-    return pipe_result(c, dshost::download_interleave(tr, pin, kPinBytes, src_dev, n_samples, n_ch, ld, dst), tr,
-                       "download_interleave");
+    return pinned(c, true, "download_interleave", [&](HipTransport& tr, float* const* pin) {
+        return dshost::download_interleave(tr, pin, kPinBytes, src_dev, n_samples, n_ch, ld, dst);
+    });
+}
+// a signal into planar float32 rows dst[n_ch][n_samples]: x has that layout already; x64 is the reference's
+// (n_samples, n_ch) float64 C-order array
+static int upload_signal(ds_ctx* c, const float* x, const double* x64, int64_t n_samples, int n_ch, float* dst) {
+    if (!x64) return ds_upload(c, dst, x, sizeof(float) * (size_t)n_ch * n_samples);
+    return pinned(c, false, "upload_planar_f64", [&](HipTransport& tr, float* const* pin) {
+        return dshost::upload_planar(tr, pin, kPinBytes, x64, n_samples, n_ch, dst, n_samples);
+    });
 }
 
+// The bodies below serve both entries of a pair: x / x64 as upload_signal, outputs as ds_c32 / float or, with the
+// *64 pointer, as the reference's complex128 / float64 layouts.  `who` is the entry's name in its error messages.
+
+// out: the (bins, frames, channels) spectrogram
+static int stft_host(ds_ctx* c, const char* who, const float* x, const double* x64, int64_t n_samples, int n_ch, int W,
+                     int hop, int nfft, int64_t pad_front, int n_frames, const float* window, int detrend, float scale,
+                     float edge_scale, int power, ds_c32* out, double* out64) {
+    if (!c || (!x && !x64) || !window || (!out && !out64)) return fail(c, DS_ERR_ARG, std::string(who) + ": null argument");
+    if (n_ch <= 0 || n_samples <= 0 || W <= 0 || n_frames <= 0 || nfft <= 0)
+        return fail(c, DS_ERR_ARG, std::string(who) + ": bad shape");
+    const size_t no = (size_t)(nfft / 2 + 1) * n_frames * n_ch;
+    float *dx, *dw;
+    float2* dout;
+    CHK(carve(c, &c->io, &c->io_bytes, [&](Carver& cv) {
+        dx = cv.take<float>((size_t)n_ch * n_samples);
+        dw = cv.take<float>(W);
+        dout = cv.take<float2>(no);
+    }));
+    CHK(upload_signal(c, x, x64, n_samples, n_ch, dx));
+    CHK(ds_upload(c, dw, window, (size_t)W * 4));
+    CHK(ds_stft_r2c_dev(c, dx, n_samples, n_ch, n_samples, W, hop, nfft, pad_front, n_frames, dw, detrend,
+                        scale, edge_scale, power, (ds_c32*)dout));
+    if (out64) return download_widen(c, (const float*)dout, (int64_t)no * 2, out64);
+    return ds_download(c, out, dout, no * 8);
+}
+extern "C" int ds_stft_r2c(ds_ctx* c, const float* x, int64_t n_samples, int n_ch, int W, int hop,
+                           int nfft, int64_t pad_front, int n_frames, const float* window, int detrend,
+                           float scale, float edge_scale, int power, ds_c32* out) {
+    return stft_host(c, "ds_stft_r2c", x, nullptr, n_samples, n_ch, W, hop, nfft, pad_front, n_frames, window, detrend,
+                     scale, edge_scale, power, out, nullptr);
+}
 // ds_stft_r2c with the reference's layouts on both sides: x (n_samples, n_ch) float64 C-order in,
 // (bins, frames, channels) complex128 out.
 extern "C" int ds_stft_r2c_f64(ds_ctx* c, const double* x, int64_t n_samples, int n_ch, int W, int hop,
                                int nfft, int64_t pad_front, int n_frames, const float* window, int detrend,
                                float scale, float edge_scale, int power, double* out_c128) {
-    if (!c || !x || !window || !out_c128) return fail(c, DS_ERR_ARG, "ds_stft_r2c_f64: null argument");
-    if (n_ch <= 0 || n_samples <= 0 || W <= 0 || n_frames <= 0 || nfft <= 0)
-        return fail(c, DS_ERR_ARG, "ds_stft_r2c_f64: bad shape");
-    size_t nx = (size_t)n_ch * n_samples, no = (size_t)(nfft / 2 + 1) * n_frames * n_ch;
-    CHK(stage_reserve(c, Carver::pad(nx * 4) + Carver::pad((size_t)W * 4) + Carver::pad(no * 8)));
-    Carver cv(c->io);
-    float* dx = cv.take<float>(nx);
-    float* dw = cv.take<float>(W);
-    float2* dout = cv.take<float2>(no);
-    CHK(upload_planar_f64(c, x, n_samples, n_ch, dx, n_samples));
-    CHK(ds_upload(c, dw, window, (size_t)W * 4));
-    CHK(ds_stft_r2c_dev(c, dx, n_samples, n_ch, n_samples, W, hop, nfft, pad_front, n_frames, dw, detrend,
-                        scale, edge_scale, power, (ds_c32*)dout));
-    return download_widen(c, (const float*)dout, (int64_t)no * 2, out_c128);
+    return stft_host(c, "ds_stft_r2c_f64", nullptr, x, n_samples, n_ch, W, hop, nfft, pad_front, n_frames, window,
+                     detrend, scale, edge_scale, power, nullptr, out_c128);
 }
 
+// stft / stft64: the (bins, frames, channels) spectrogram as ds_c32 / complex128; out: (n_ch, total_length) float32
+// rows, out64: the reference's (total_length, n_ch) float64 array
+static int istft_host(ds_ctx* c, const char* who, const ds_c32* stft, const double* stft64, int n_bins, int n_frames,
+                      int n_ch, int nfft, int W, int step, int frame_offset, int n_frames_total, const float* window,
+                      float scale, int64_t total_length, float* out, double* out64) {
+    if (!c || (!stft && !stft64) || !window || (!out && !out64))
+        return fail(c, DS_ERR_ARG, std::string(who) + ": null argument");
+    if (n_bins <= 0 || n_frames <= 0 || n_ch <= 0 || W <= 0 || total_length <= 0)
+        return fail(c, DS_ERR_ARG, std::string(who) + ": bad shape");
+    const size_t ns = (size_t)n_bins * n_frames * n_ch, no = (size_t)n_ch * total_length;
+    float2* ds;
+    float *dw, *dout;
+    CHK(carve(c, &c->io, &c->io_bytes, [&](Carver& cv) {
+        ds = cv.take<float2>(ns);
+        dw = cv.take<float>(W);
+        dout = cv.take<float>(no);
+    }));
+    if (stft64)
+        CHK(upload_narrow_f64(c, stft64, (int64_t)ns * 2, (float*)ds));
+    else
+        CHK(ds_upload(c, ds, stft, ns * 8));
+    CHK(ds_upload(c, dw, window, (size_t)W * 4));
+    CHK(ds_istft_dev(c, (const ds_c32*)ds, n_bins, n_frames, n_ch, nfft, W, step, frame_offset, n_frames_total,
+                     dw, scale, total_length, dout, total_length));
+    if (out64) return download_interleave(c, dout, total_length, n_ch, total_length, out64);
+    return ds_download(c, out, dout, no * 4);
+}
+extern "C" int ds_istft(ds_ctx* c, const ds_c32* stft, int n_bins, int n_frames, int n_ch, int nfft, int W,
+                        int step, int frame_offset, int n_frames_total, const float* window, float scale,
+                        int64_t total_length, float* out) {
+    return istft_host(c, "ds_istft", stft, nullptr, n_bins, n_frames, n_ch, nfft, W, step, frame_offset, n_frames_total,
+                      window, scale, total_length, out, nullptr);
+}
+// ds_istft with the reference's layouts on both sides: the spectrogram (bins, frames, channels) complex128 in,
+// the signal (total_length, n_ch) float64 out (transforms.istft, transforms/transforms.py:444-586).
+extern "C" int ds_istft_f64(ds_ctx* c, const double* stft_c128, int n_bins, int n_frames, int n_ch, int nfft, int W,
+                            int step, int frame_offset, int n_frames_total, const float* window, float scale,
+                            int64_t total_length, double* out) {
+    return istft_host(c, "ds_istft_f64", nullptr, stft_c128, n_bins, n_frames, n_ch, nfft, W, step, frame_offset,
+                      n_frames_total, window, scale, total_length, nullptr, out);
+}
+
+// spec: (bins, channels)
+static int rfft_host(ds_ctx* c, const char* who, const float* x, const double* x64, int n_ch, int64_t n_samples,
+                     int n_fft, float scale, ds_c32* spec, double* spec64) {
+    if (!c || (!x && !x64) || (!spec && !spec64)) return fail(c, DS_ERR_ARG, std::string(who) + ": null argument");
+    if (n_ch <= 0 || n_samples <= 0 || n_fft < (x64 ? 2 : 1)) return fail(c, DS_ERR_ARG, std::string(who) + ": bad shape");
+    const size_t no = (size_t)(n_fft / 2 + 1) * n_ch;
+    float* dx;
+    float2* ds;
+    CHK(carve(c, &c->io, &c->io_bytes, [&](Carver& cv) {
+        dx = cv.take<float>((size_t)n_ch * n_samples);
+        ds = cv.take<float2>(no);
+    }));
+    CHK(upload_signal(c, x, x64, n_samples, n_ch, dx));
+    CHK(ds_rfft_dev(c, dx, n_ch, n_samples, n_samples, n_fft, scale, (ds_c32*)ds));
+    if (spec64) return download_widen(c, (const float*)ds, (int64_t)no * 2, spec64);
+    return ds_download(c, spec, ds, no * 8);
+}
+extern "C" int ds_rfft(ds_ctx* c, const float* x, int n_ch, int64_t n_samples, int n_fft, float scale,
+                       ds_c32* spec) {
+    return rfft_host(c, "ds_rfft", x, nullptr, n_ch, n_samples, n_fft, scale, spec, nullptr);
+}
 // ds_rfft with the reference's layouts on both sides: x (n_samples, n_ch) float64 C-order in, (bins, channels)
 // complex128 out (Signal.get_spectrum with SpectrumMethod.FFT, classes/signal.py:899-911).
 extern "C" int ds_rfft_f64(ds_ctx* c, const double* x, int n_ch, int64_t n_samples, int n_fft, float scale,
                            double* spec_c128) {
-    if (!c || !x || !spec_c128) return fail(c, DS_ERR_ARG, "ds_rfft_f64: null argument");
-    if (n_ch <= 0 || n_samples <= 0 || n_fft < 2) return fail(c, DS_ERR_ARG, "ds_rfft_f64: bad shape");
-    const size_t nx = (size_t)n_ch * n_samples, no = (size_t)(n_fft / 2 + 1) * n_ch;
-    CHK(stage_reserve(c, Carver::pad(nx * 4) + Carver::pad(no * 8)));
-    Carver cv(c->io);
-    float* dx = cv.take<float>(nx);
-    float2* ds = cv.take<float2>(no);
-    CHK(upload_planar_f64(c, x, n_samples, n_ch, dx, n_samples));
-    CHK(ds_rfft_dev(c, dx, n_ch, n_samples, n_samples, n_fft, scale, (ds_c32*)ds));
-    return download_widen(c, (const float*)ds, (int64_t)no * 2, spec_c128);
+    return rfft_host(c, "ds_rfft_f64", nullptr, x, n_ch, n_samples, n_fft, scale, nullptr, spec_c128);
 }
 
 // ds_deconv for ONE item in the reference's layouts: y (n_samples, n_ch) float64 in, the impulse responses
@@ -3265,110 +3323,94 @@ extern "C" int ds_deconv_f64(ds_ctx* c, const double* y, int n_ch, int64_t n_sam
                              int r_per_channel, int64_t n_out, double* ir) {
     if (!c || !y || !r || !ir) return fail(c, DS_ERR_ARG, "ds_deconv_f64: null argument");
     if (n_ch <= 0 || n_samples <= 0 || n_fft < 2 || n_out <= 0 || n_out > n_fft) return fail(c, DS_ERR_ARG, "ds_deconv_f64: bad shape");
-    const size_t ny = (size_t)n_ch * n_samples, nr = (size_t)(r_per_channel ? n_ch : 1) * (n_fft / 2 + 1), no = (size_t)n_ch * n_out;
-    CHK(stage_reserve(c, Carver::pad(ny * 4) + Carver::pad(nr * 8) + Carver::pad(no * 4)));
-    Carver cv(c->io);
-    float* dy = cv.take<float>(ny);
-    float2* dr = cv.take<float2>(nr);
-    float* dout = cv.take<float>(no);
-    CHK(upload_planar_f64(c, y, n_samples, n_ch, dy, n_samples));
+    const size_t nr = (size_t)(r_per_channel ? n_ch : 1) * (n_fft / 2 + 1);
+    float *dy, *dout;
+    float2* dr;
+    CHK(carve(c, &c->io, &c->io_bytes, [&](Carver& cv) {
+        dy = cv.take<float>((size_t)n_ch * n_samples);
+        dr = cv.take<float2>(nr);
+        dout = cv.take<float>((size_t)n_ch * n_out);
+    }));
+    CHK(upload_signal(c, nullptr, y, n_samples, n_ch, dy));
     CHK(ds_upload(c, dr, r, nr * 8));
     CHK(ds_deconv_dev(c, dy, 1, n_ch, n_samples, n_samples, n_fft, (const ds_c32*)dr, r_per_channel, n_out, n_out, dout));
     return download_interleave(c, dout, n_out, n_ch, n_out, ir);
 }
 
-// ds_istft with the reference's layouts on both sides: the spectrogram (bins, frames, channels) complex128 in,
-// the signal (total_length, n_ch) float64 out (transforms.istft, transforms/transforms.py:444-586).
-extern "C" int ds_istft_f64(ds_ctx* c, const double* stft_c128, int n_bins, int n_frames, int n_ch, int nfft, int W,
-                            int step, int frame_offset, int n_frames_total, const float* window, float scale,
-                            int64_t total_length, double* out) {
-    if (!c || !stft_c128 || !window || !out) return fail(c, DS_ERR_ARG, "ds_istft_f64: null argument");
-    if (n_bins <= 0 || n_frames <= 0 || n_ch <= 0 || W <= 0 || total_length <= 0) return fail(c, DS_ERR_ARG, "ds_istft_f64: bad shape");
-    const size_t ns = (size_t)n_bins * n_frames * n_ch, no = (size_t)n_ch * total_length;
-    CHK(stage_reserve(c, Carver::pad(ns * 8) + Carver::pad((size_t)W * 4) + Carver::pad(no * 4)));
-    Carver cv(c->io);
-    float2* dsp = cv.take<float2>(ns);
-    float* dw = cv.take<float>(W);
-    float* dout = cv.take<float>(no);
-    CHK(upload_narrow_f64(c, stft_c128, (int64_t)ns * 2, (float*)dsp));
-    CHK(ds_upload(c, dw, window, (size_t)W * 4));
-    CHK(ds_istft_dev(c, (const ds_c32*)dsp, n_bins, n_frames, n_ch, nfft, W, step, frame_offset, n_frames_total, dw, scale,
-                     total_length, dout, total_length));
-    return download_interleave(c, dout, total_length, n_ch, total_length, out);
+// y: (bands or 1, n_ch, n_samples) float32, or y64: (bands or 1, n_samples, n_ch) float64
+static int fir_ola_host(ds_ctx* c, const char* who, const float* x, const double* x64, int n_ch, int64_t n_samples,
+                        const float* taps, int n_filt, int n_taps, int mode, float* y, double* y64) {
+    if (!c || (!x && !x64) || !taps || (!y && !y64)) return fail(c, DS_ERR_ARG, std::string(who) + ": null argument");
+    if (n_ch <= 0 || n_samples <= 0 || n_filt <= 0 || n_taps <= 0) return fail(c, DS_ERR_ARG, std::string(who) + ": bad shape");
+    const int n_out = mode == DS_FB_PARALLEL ? n_filt : 1;
+    const size_t nt = (size_t)n_filt * n_taps, no = (size_t)n_out * n_ch * n_samples;
+    float *dx, *dt, *dy;
+    CHK(carve(c, &c->io, &c->io_bytes, [&](Carver& cv) {
+        dx = cv.take<float>((size_t)n_ch * n_samples);
+        dt = cv.take<float>(nt);
+        dy = cv.take<float>(no);
+    }));
+    CHK(upload_signal(c, x, x64, n_samples, n_ch, dx));
+    CHK(ds_upload(c, dt, taps, nt * 4));
+    CHK(ds_fir_ola_dev(c, dx, n_ch, n_samples, n_samples, dt, n_filt, n_taps, mode, dy, n_samples));
+    if (!y64) return ds_download(c, y, dy, no * 4);
+    for (int k = 0; k < n_out; ++k)
+        CHK(download_interleave(c, dy + (size_t)k * n_ch * n_samples, n_samples, n_ch, n_samples,
+                                y64 + (size_t)k * n_samples * n_ch));
+    return DS_OK;
 }
-
+extern "C" int ds_fir_ola(ds_ctx* c, const float* x, int n_ch, int64_t n_samples, const float* taps,
+                          int n_filt, int n_taps, int mode, float* y) {
+    return fir_ola_host(c, "ds_fir_ola", x, nullptr, n_ch, n_samples, taps, n_filt, n_taps, mode, y, nullptr);
+}
 // ds_fir_ola with the reference's layouts on both sides: x (n_samples, n_ch) float64 in,
 // y (bands or 1, n_samples, n_ch) float64 out.
 extern "C" int ds_fir_ola_f64(ds_ctx* c, const double* x, int n_ch, int64_t n_samples, const float* taps,
                               int n_filt, int n_taps, int mode, double* y) {
-    if (!c || !x || !taps || !y) return fail(c, DS_ERR_ARG, "ds_fir_ola_f64: null argument");
-    if (n_ch <= 0 || n_samples <= 0 || n_filt <= 0 || n_taps <= 0) return fail(c, DS_ERR_ARG, "ds_fir_ola_f64: bad shape");
-    const int n_out = mode == DS_FB_PARALLEL ? n_filt : 1;
-    size_t nx = (size_t)n_ch * n_samples, nt = (size_t)n_filt * n_taps, no = (size_t)n_out * n_ch * n_samples;
-    CHK(stage_reserve(c, Carver::pad(nx * 4) + Carver::pad(nt * 4) + Carver::pad(no * 4)));
-    Carver cv(c->io);
-    float* dx = cv.take<float>(nx);
-    float* dt = cv.take<float>(nt);
-    float* dy = cv.take<float>(no);
-    CHK(upload_planar_f64(c, x, n_samples, n_ch, dx, n_samples));
-    CHK(ds_upload(c, dt, taps, nt * 4));
-    CHK(ds_fir_ola_dev(c, dx, n_ch, n_samples, n_samples, dt, n_filt, n_taps, mode, dy, n_samples));
-    for (int k = 0; k < n_out; ++k)
-        CHK(download_interleave(c, dy + (size_t)k * n_ch * n_samples, n_samples, n_ch, n_samples,
-                                y + (size_t)k * n_samples * n_ch));
-    return DS_OK;
+    return fir_ola_host(c, "ds_fir_ola_f64", nullptr, x, n_ch, n_samples, taps, n_filt, n_taps, mode, nullptr, y);
 }
 
+static int welch_tf_host(ds_ctx* c, const char* who, const float* x, const float* y, const double* x64,
+                         const double* y64, int n_cx, int n_cy, int64_t n_samples, int W, int hop, int n_frames,
+                         const float* window, int detrend, int average, int mode, int amp_sqrt, double norm_scale,
+                         double factor, int halve_edges, ds_c32* tf, float* coh) {
+    if (!c || (!x && !x64) || (!y && !y64) || !window || !tf || !coh)
+        return fail(c, DS_ERR_ARG, std::string(who) + ": null argument");
+    if (n_cx <= 0 || n_cy <= 0 || n_samples <= 0 || W <= 0) return fail(c, DS_ERR_ARG, std::string(who) + ": bad shape");
+    const size_t no = (size_t)(W / 2 + 1) * n_cy;
+    float *dx, *dy, *dw, *dcoh;
+    float2* dtf;
+    CHK(carve(c, &c->io, &c->io_bytes, [&](Carver& cv) {
+        dx = cv.take<float>((size_t)n_cx * n_samples);
+        dy = cv.take<float>((size_t)n_cy * n_samples);
+        dw = cv.take<float>(W);
+        dtf = cv.take<float2>(no);
+        dcoh = cv.take<float>(no);
+    }));
+    CHK(upload_signal(c, x, x64, n_samples, n_cx, dx));
+    CHK(upload_signal(c, y, y64, n_samples, n_cy, dy));
+    CHK(ds_upload(c, dw, window, (size_t)W * 4));
+    CHK(ds_welch_tf_dev(c, dx, n_cx, n_samples, dy, n_cy, n_samples, n_samples, W, hop, n_frames, dw,
+                        detrend, average, mode, amp_sqrt, norm_scale, factor, halve_edges, (ds_c32*)dtf,
+                        dcoh));
+    CHK(ds_download(c, tf, dtf, no * 8));
+    return ds_download(c, coh, dcoh, no * 4);
+}
 // ds_welch_tf with the reference's own array layout at the boundary: x (n_samples, n_cx) and
 // y (n_samples, n_cy) float64 C-order (classes/signal.py:222-301), outputs as ds_welch_tf.
 extern "C" int ds_welch_tf_f64(ds_ctx* c, const double* x, int n_cx, const double* y, int n_cy,
                                int64_t n_samples, int W, int hop, int n_frames, const float* window,
                                int detrend, int average, int mode, int amp_sqrt, double norm_scale,
                                double factor, int halve_edges, ds_c32* tf, float* coh) {
-    if (!c || !x || !y || !window || !tf || !coh) return fail(c, DS_ERR_ARG, "ds_welch_tf_f64: null argument");
-    if (n_cx <= 0 || n_cy <= 0 || n_samples <= 0 || W <= 0) return fail(c, DS_ERR_ARG, "ds_welch_tf_f64: bad shape");
-    size_t nx = (size_t)n_cx * n_samples, ny = (size_t)n_cy * n_samples, no = (size_t)(W / 2 + 1) * n_cy;
-    CHK(stage_reserve(c, Carver::pad(nx * 4) + Carver::pad(ny * 4) + Carver::pad((size_t)W * 4) +
-                             Carver::pad(no * 8) + Carver::pad(no * 4)));
-    Carver cv(c->io);
-    float* dx = cv.take<float>(nx);
-    float* dy = cv.take<float>(ny);
-    float* dw = cv.take<float>(W);
-    float2* dtf = cv.take<float2>(no);
-    float* dcoh = cv.take<float>(no);
-    CHK(upload_planar_f64(c, x, n_samples, n_cx, dx, n_samples));
-    CHK(upload_planar_f64(c, y, n_samples, n_cy, dy, n_samples));
-    CHK(ds_upload(c, dw, window, (size_t)W * 4));
-    CHK(ds_welch_tf_dev(c, dx, n_cx, n_samples, dy, n_cy, n_samples, n_samples, W, hop, n_frames, dw,
-                        detrend, average, mode, amp_sqrt, norm_scale, factor, halve_edges, (ds_c32*)dtf,
-                        dcoh));
-    CHK(ds_download(c, tf, dtf, no * 8));
-    return ds_download(c, coh, dcoh, no * 4);
+    return welch_tf_host(c, "ds_welch_tf_f64", nullptr, nullptr, x, y, n_cx, n_cy, n_samples, W, hop, n_frames, window,
+                         detrend, average, mode, amp_sqrt, norm_scale, factor, halve_edges, tf, coh);
 }
-
 extern "C" int ds_welch_tf(ds_ctx* c, const float* x, int n_cx, const float* y, int n_cy,
                            int64_t n_samples, int W, int hop, int n_frames, const float* window,
                            int detrend, int average, int mode, int amp_sqrt, double norm_scale,
                            double factor, int halve_edges, ds_c32* tf, float* coh) {
-    if (!c || !x || !y || !window || !tf || !coh) return fail(c, DS_ERR_ARG, "ds_welch_tf: null argument");
-    if (n_cx <= 0 || n_cy <= 0 || n_samples <= 0 || W <= 0) return fail(c, DS_ERR_ARG, "ds_welch_tf: bad shape");
-    size_t nx = (size_t)n_cx * n_samples, ny = (size_t)n_cy * n_samples, no = (size_t)(W / 2 + 1) * n_cy;
-    CHK(stage_reserve(c, Carver::pad(nx * 4) + Carver::pad(ny * 4) + Carver::pad((size_t)W * 4) +
-                             Carver::pad(no * 8) + Carver::pad(no * 4)));
-    Carver cv(c->io);
-    float* dx = cv.take<float>(nx);
-    float* dy = cv.take<float>(ny);
-    float* dw = cv.take<float>(W);
-    float2* dtf = cv.take<float2>(no);
-    float* dcoh = cv.take<float>(no);
-    CHK(ds_upload(c, dx, x, nx * 4));
-    CHK(ds_upload(c, dy, y, ny * 4));
-    CHK(ds_upload(c, dw, window, (size_t)W * 4));
-    CHK(ds_welch_tf_dev(c, dx, n_cx, n_samples, dy, n_cy, n_samples, n_samples, W, hop, n_frames, dw,
-                        detrend, average, mode, amp_sqrt, norm_scale, factor, halve_edges, (ds_c32*)dtf,
-                        dcoh));
-    CHK(ds_download(c, tf, dtf, no * 8));
-    return ds_download(c, coh, dcoh, no * 4);
+    return welch_tf_host(c, "ds_welch_tf", x, y, nullptr, nullptr, n_cx, n_cy, n_samples, W, hop, n_frames, window,
+                         detrend, average, mode, amp_sqrt, norm_scale, factor, halve_edges, tf, coh);
 }
 
 static int welch_psd_host(ds_ctx* c, const float* x, const double* x64, int n_cx, int64_t n_samples, int W,
@@ -3376,16 +3418,14 @@ static int welch_psd_host(ds_ctx* c, const float* x, const double* x64, int n_cx
                           double norm_scale, double factor, int halve_edges, float* psd) {
     if (!c || (!x && !x64) || !window || !psd) return fail(c, DS_ERR_ARG, "ds_welch_psd: null argument");
     if (n_cx <= 0 || n_samples <= 0 || W <= 0) return fail(c, DS_ERR_ARG, "ds_welch_psd: bad shape");
-    size_t nx = (size_t)n_cx * n_samples, no = (size_t)(W / 2 + 1) * n_cx;
-    CHK(stage_reserve(c, Carver::pad(nx * 4) + Carver::pad((size_t)W * 4) + Carver::pad(no * 4)));
-    Carver cv(c->io);
-    float* dx = cv.take<float>(nx);
-    float* dw = cv.take<float>(W);
-    float* dp = cv.take<float>(no);
-    if (x64)
-        CHK(upload_planar_f64(c, x64, n_samples, n_cx, dx, n_samples));
-    else
-        CHK(ds_upload(c, dx, x, nx * 4));
+    const size_t no = (size_t)(W / 2 + 1) * n_cx;
+    float *dx, *dw, *dp;
+    CHK(carve(c, &c->io, &c->io_bytes, [&](Carver& cv) {
+        dx = cv.take<float>((size_t)n_cx * n_samples);
+        dw = cv.take<float>(W);
+        dp = cv.take<float>(no);
+    }));
+    CHK(upload_signal(c, x, x64, n_samples, n_cx, dx));
     CHK(ds_upload(c, dw, window, (size_t)W * 4));
     CHK(ds_welch_psd_dev(c, dx, n_cx, n_samples, n_samples, W, hop, n_frames, dw, detrend, average,
                          amp_sqrt, norm_scale, factor, halve_edges, dp));
@@ -3410,20 +3450,17 @@ static int welch_csd_host(ds_ctx* c, const float* x, const float* y, const doubl
                           int amp_sqrt, double norm_scale, double factor, int halve_edges, ds_c32* csd) {
     if (!c || (!x && !x64) || (!y && !y64) || !window || !csd) return fail(c, DS_ERR_ARG, "ds_welch_csd: null argument");
     if (n_ch <= 0 || n_samples <= 0 || W <= 0) return fail(c, DS_ERR_ARG, "ds_welch_csd: bad shape");
-    size_t nx = (size_t)n_ch * n_samples, no = (size_t)(W / 2 + 1) * n_ch;
-    CHK(stage_reserve(c, 2 * Carver::pad(nx * 4) + Carver::pad((size_t)W * 4) + Carver::pad(no * 8)));
-    Carver cv(c->io);
-    float* dx = cv.take<float>(nx);
-    float* dy = cv.take<float>(nx);
-    float* dw = cv.take<float>(W);
-    float2* dc = cv.take<float2>(no);
-    if (x64) {
-        CHK(upload_planar_f64(c, x64, n_samples, n_ch, dx, n_samples));
-        CHK(upload_planar_f64(c, y64, n_samples, n_ch, dy, n_samples));
-    } else {
-        CHK(ds_upload(c, dx, x, nx * 4));
-        CHK(ds_upload(c, dy, y, nx * 4));
-    }
+    const size_t nx = (size_t)n_ch * n_samples, no = (size_t)(W / 2 + 1) * n_ch;
+    float *dx, *dy, *dw;
+    float2* dc;
+    CHK(carve(c, &c->io, &c->io_bytes, [&](Carver& cv) {
+        dx = cv.take<float>(nx);
+        dy = cv.take<float>(nx);
+        dw = cv.take<float>(W);
+        dc = cv.take<float2>(no);
+    }));
+    CHK(upload_signal(c, x, x64, n_samples, n_ch, dx));
+    CHK(upload_signal(c, y, y64, n_samples, n_ch, dy));
     CHK(ds_upload(c, dw, window, (size_t)W * 4));
     CHK(welch_csd_dev(c, dx, dy, n_ch, n_samples, n_samples, W, hop, n_frames, dw, detrend, average,
                       amp_sqrt, norm_scale, factor, halve_edges, (ds_c32*)dc));
@@ -3450,16 +3487,15 @@ static int csm_host(ds_ctx* c, const float* x, const double* x64, int n_ch, int6
                     double norm_scale, double factor, int halve_edges, ds_c32* csm) {
     if (!c || (!x && !x64) || !window || !csm) return fail(c, DS_ERR_ARG, "ds_csm: null argument");
     if (n_ch <= 0 || n_samples <= 0 || W <= 0) return fail(c, DS_ERR_ARG, "ds_csm: bad shape");
-    size_t nx = (size_t)n_ch * n_samples, no = (size_t)(W / 2 + 1) * n_ch * n_ch;
-    CHK(stage_reserve(c, Carver::pad(nx * 4) + Carver::pad((size_t)W * 4) + Carver::pad(no * 8)));
-    Carver cv(c->io);
-    float* dx = cv.take<float>(nx);
-    float* dw = cv.take<float>(W);
-    float2* dc = cv.take<float2>(no);
-    if (x64)
-        CHK(upload_planar_f64(c, x64, n_samples, n_ch, dx, n_samples));
-    else
-        CHK(ds_upload(c, dx, x, nx * 4));
+    const size_t no = (size_t)(W / 2 + 1) * n_ch * n_ch;
+    float *dx, *dw;
+    float2* dc;
+    CHK(carve(c, &c->io, &c->io_bytes, [&](Carver& cv) {
+        dx = cv.take<float>((size_t)n_ch * n_samples);
+        dw = cv.take<float>(W);
+        dc = cv.take<float2>(no);
+    }));
+    CHK(upload_signal(c, x, x64, n_samples, n_ch, dx));
     CHK(ds_upload(c, dw, window, (size_t)W * 4));
     CHK(ds_csm_dev(c, dx, n_ch, n_samples, n_samples, W, hop, n_frames, dw, detrend, average, amp_sqrt,
                    norm_scale, factor, halve_edges, (ds_c32*)dc));
@@ -3478,53 +3514,24 @@ extern "C" int ds_csm_f64(ds_ctx* c, const double* x, int n_ch, int64_t n_sample
                     norm_scale, factor, halve_edges, csm);
 }
 
-extern "C" int ds_rfft(ds_ctx* c, const float* x, int n_ch, int64_t n_samples, int n_fft, float scale,
-                       ds_c32* spec) {
-    if (!c || !x || !spec) return fail(c, DS_ERR_ARG, "ds_rfft: null argument");
-    if (n_ch <= 0 || n_samples <= 0 || n_fft <= 0) return fail(c, DS_ERR_ARG, "ds_rfft: bad shape");
-    size_t nx = (size_t)n_ch * n_samples, no = (size_t)(n_fft / 2 + 1) * n_ch;
-    CHK(stage_reserve(c, Carver::pad(nx * 4) + Carver::pad(no * 8)));
-    Carver cv(c->io);
-    float* dx = cv.take<float>(nx);
-    float2* ds = cv.take<float2>(no);
-    CHK(ds_upload(c, dx, x, nx * 4));
-    CHK(ds_rfft_dev(c, dx, n_ch, n_samples, n_samples, n_fft, scale, (ds_c32*)ds));
-    return ds_download(c, spec, ds, no * 8);
-}
-
 extern "C" int ds_deconv(ds_ctx* c, const float* y, int n_items, int n_ch, int64_t n_samples, int n_fft,
                          const ds_c32* r, int r_per_channel, int64_t n_out, float* ir) {
     if (!c || !y || !r || !ir) return fail(c, DS_ERR_ARG, "ds_deconv: null argument");
     if (n_items <= 0 || n_ch <= 0 || n_samples <= 0 || n_fft <= 0 || n_out <= 0) return fail(c, DS_ERR_ARG, "ds_deconv: bad shape");
     size_t ny = (size_t)n_items * n_ch * n_samples, nr = (size_t)(r_per_channel ? n_ch : 1) * (n_fft / 2 + 1),
            no = (size_t)n_items * n_ch * n_out;
-    CHK(stage_reserve(c, Carver::pad(ny * 4) + Carver::pad(nr * 8) + Carver::pad(no * 4)));
-    Carver cv(c->io);
-    float* dy = cv.take<float>(ny);
-    float2* dr = cv.take<float2>(nr);
-    float* dir = cv.take<float>(no);
+    float *dy, *dir;
+    float2* dr;
+    CHK(carve(c, &c->io, &c->io_bytes, [&](Carver& cv) {
+        dy = cv.take<float>(ny);
+        dr = cv.take<float2>(nr);
+        dir = cv.take<float>(no);
+    }));
     CHK(ds_upload(c, dy, y, ny * 4));
     CHK(ds_upload(c, dr, r, nr * 8));
     CHK(ds_deconv_dev(c, dy, n_items, n_ch, n_samples, n_samples, n_fft, (const ds_c32*)dr, r_per_channel,
                       n_out, n_out, dir));
     return ds_download(c, ir, dir, no * 4);
-}
-
-extern "C" int ds_fir_ola(ds_ctx* c, const float* x, int n_ch, int64_t n_samples, const float* taps,
-                          int n_filt, int n_taps, int mode, float* y) {
-    if (!c || !x || !taps || !y) return fail(c, DS_ERR_ARG, "ds_fir_ola: null argument");
-    if (n_ch <= 0 || n_samples <= 0 || n_filt <= 0 || n_taps <= 0) return fail(c, DS_ERR_ARG, "ds_fir_ola: bad shape");
-    size_t nx = (size_t)n_ch * n_samples, nt = (size_t)n_filt * n_taps,
-           no = (size_t)(mode == DS_FB_PARALLEL ? n_filt : 1) * n_ch * n_samples;
-    CHK(stage_reserve(c, Carver::pad(nx * 4) + Carver::pad(nt * 4) + Carver::pad(no * 4)));
-    Carver cv(c->io);
-    float* dx = cv.take<float>(nx);
-    float* dt = cv.take<float>(nt);
-    float* dy = cv.take<float>(no);
-    CHK(ds_upload(c, dx, x, nx * 4));
-    CHK(ds_upload(c, dt, taps, nt * 4));
-    CHK(ds_fir_ola_dev(c, dx, n_ch, n_samples, n_samples, dt, n_filt, n_taps, mode, dy, n_samples));
-    return ds_download(c, y, dy, no * 4);
 }
 
 // ---- block-streaming FIR classes, state on the device (kernels_fir_stream.hpp) ----------
@@ -3547,14 +3554,14 @@ extern "C" int ds_fir_part_step_dev(ds_ctx* c, float* inbuf, const float* block,
         (n_fir_ch != 1 && n_fir_ch != n_ch))
         return fail(c, DS_ERR_ARG, "ds_fir_part_step: bad shape");
     const int n_fft = 2 * bs, B = bs + 1;
-    CHK(reserve(c, &c->aux, &c->aux_bytes,
-                2 * Carver::pad(sizeof(float2) * (size_t)B * n_call) + Carver::pad(sizeof(float) * (size_t)n_call * n_fft) +
-                    Carver::pad(sizeof(float) * (size_t)n_call)));
-    Carver cv(c->aux);
-    float2* X = cv.take<float2>((size_t)B * n_call);
-    float2* Y = cv.take<float2>((size_t)B * n_call);
-    float* full = cv.take<float>((size_t)n_call * n_fft);
-    float* ones = cv.take<float>(n_call);
+    float2 *X, *Y;
+    float *full, *ones;
+    CHK(carve(c, &c->aux, &c->aux_bytes, [&](Carver& cv) {
+        X = cv.take<float2>((size_t)B * n_call);
+        Y = cv.take<float2>((size_t)B * n_call);
+        full = cv.take<float>((size_t)n_call * n_fft);
+        ones = cv.take<float>(n_call);
+    }));
     CHK(stream_ones(c, ones, n_call));
     const int64_t nb = (int64_t)n_call * bs;
     hipLaunchKernelGGL(firstream::k_shift_in, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, c->stream, inbuf, block,
@@ -3579,15 +3586,15 @@ extern "C" int ds_fir_ols_step_dev(ds_ctx* c, float* row, const float* block, in
     const int B = (int)(L / 2 + 1);
     const int64_t n_inv = 2 * (int64_t)(B - 1);  // L for even L, L - 1 for odd L: irfft without a length
     if (bs > n_inv) return fail(c, DS_ERR_ARG, "ds_fir_ols_step: block longer than the inverse transform");
-    CHK(reserve(c, &c->aux, &c->aux_bytes,
-                2 * Carver::pad(sizeof(float2) * (size_t)B) + 2 * Carver::pad(sizeof(float) * (size_t)L) +
-                    Carver::pad(sizeof(float))));
-    Carver cv(c->aux);
-    float2* X = cv.take<float2>(B);
-    float2* Y = cv.take<float2>(B);
-    float* full = cv.take<float>((size_t)L);
-    float* roll = cv.take<float>((size_t)L);
-    float* one = cv.take<float>(1);
+    float2 *X, *Y;
+    float *full, *roll, *one;
+    CHK(carve(c, &c->aux, &c->aux_bytes, [&](Carver& cv) {
+        X = cv.take<float2>(B);
+        Y = cv.take<float2>(B);
+        full = cv.take<float>((size_t)L);
+        roll = cv.take<float>((size_t)L);
+        one = cv.take<float>(1);
+    }));
     CHK(stream_ones(c, one, 1));
     hipLaunchKernelGGL(firstream::k_ols_put, dim3((bs + 255) / 256), dim3(256), 0, c->stream, row, block, L, bs);
     HIPCHK(c, hipGetLastError());
@@ -3612,11 +3619,13 @@ extern "C" int ds_fir_freqz(ds_ctx* c, const double* taps, int n_filt, int n_tap
     if (n_filt <= 0 || n_taps <= 0 || n_freq <= 0 || !(fs_hz > 0.0)) return fail(c, DS_ERR_ARG, "ds_fir_freqz: bad shape");
     HIPCHK(c, hipSetDevice(c->device));
     const size_t bt = (size_t)n_filt * n_taps * 16, bf = (size_t)n_freq * 8, bo = (size_t)n_filt * n_freq * 16;
-    CHK(reserve(c, &c->io, &c->io_bytes, Carver::pad(bt) + Carver::pad(bf) + Carver::pad(bo)));
-    Carver cv(c->io);
-    double2* dt = cv.take<double2>((size_t)n_filt * n_taps);
-    double* df = cv.take<double>(n_freq);
-    double2* dout = cv.take<double2>((size_t)n_filt * n_freq);
+    double2 *dt, *dout;
+    double* df;
+    CHK(carve(c, &c->io, &c->io_bytes, [&](Carver& cv) {
+        dt = cv.take<double2>((size_t)n_filt * n_taps);
+        df = cv.take<double>(n_freq);
+        dout = cv.take<double2>((size_t)n_filt * n_freq);
+    }));
     HIPCHK(c, hipMemcpyAsync(dt, taps, bt, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(df, freqs_hz, bf, hipMemcpyHostToDevice, c->stream));
     freqz::Args a{dt, n_filt, n_taps, df, n_freq, fs_hz, dout};
@@ -3709,13 +3718,13 @@ static int iir_run(ds_ctx* c, const char* who, const T* x, int64_t sxc, int64_t 
         return fail(c, DS_ERR_ARG, std::string(who) + ": sections must be finite with a0 != 0");
     const int d = 2 * n_sec;
     const size_t n_streams = (size_t)n_filt * n_ch;
-    CHK(reserve(c, &c->ws, &c->ws_bytes, Carver::pad(coef.size() * 8) + 2 * Carver::pad(phi.size() * 8) +
-                                             Carver::pad(n_streams * n_groups * d * 8)));
-    Carver cv(c->ws);
-    double* dcoef = cv.take<double>(coef.size());
-    double* dphi = cv.take<double>(phi.size());
-    double* dphig = cv.take<double>(phig.size());
-    double* gst = cv.take<double>(n_streams * n_groups * d);
+    double *dcoef, *dphi, *dphig, *gst;
+    CHK(carve(c, &c->ws, &c->ws_bytes, [&](Carver& cv) {
+        dcoef = cv.take<double>(coef.size());
+        dphi = cv.take<double>(phi.size());
+        dphig = cv.take<double>(phig.size());
+        gst = cv.take<double>(n_streams * n_groups * d);
+    }));
     CHK(ds_upload(c, dcoef, coef.data(), coef.size() * 8));
     CHK(ds_upload(c, dphi, phi.data(), phi.size() * 8));
     CHK(ds_upload(c, dphig, phig.data(), phig.size() * 8));
@@ -3759,12 +3768,13 @@ extern "C" int ds_iir_sos(ds_ctx* c, const double* x, int n_ch, int64_t n_sample
     HIPCHK(c, hipSetDevice(c->device));
     const int n_out = mode == DS_FB_PARALLEL ? n_filt : 1;
     const size_t nx = (size_t)n_ch * n_samples, ny = nx * n_out, nz = (size_t)n_filt * n_sec * 2 * n_ch;
-    CHK(stage_reserve(c, Carver::pad(nx * 8) + Carver::pad(ny * 8) + 2 * Carver::pad(nz * 8)));
-    Carver cv(c->io);
-    double* dx = cv.take<double>(nx);
-    double* dy = cv.take<double>(ny);
-    double* dzi = cv.take<double>(nz);
-    double* dzf = cv.take<double>(nz);
+    double *dx, *dy, *dzi, *dzf;
+    CHK(carve(c, &c->io, &c->io_bytes, [&](Carver& cv) {
+        dx = cv.take<double>(nx);
+        dy = cv.take<double>(ny);
+        dzi = cv.take<double>(nz);
+        dzf = cv.take<double>(nz);
+    }));
     CHK(ds_upload(c, dx, x, nx * 8));
     if (zi) CHK(ds_upload(c, dzi, zi, nz * 8));
     CHK(iir_run<double>(c, "ds_iir_sos", dx, 1, n_ch, n_samples, n_ch, sos, n_filt, n_sec, zi ? dzi : nullptr, mode,

@@ -356,7 +356,6 @@ __global__ __launch_bounds__(NTB, 3) void k_y(Args p) {
 // ---- host side -------------------------------------------------------------------
 struct Plan {
     int n_pairs, n_chunks, ppc;
-    size_t bytes;
 };
 template <int NN>
 inline Plan plan(int n_frames, int n_cy, int n_cx = 1, int want_chunks = 0) {  // want_chunks: ds_config::welch1k_chunks
@@ -375,10 +374,6 @@ inline Plan plan(int n_frames, int n_cy, int n_cx = 1, int want_chunks = 0) {  /
     if (want >= 8) want &= ~7;  // whole chunks per XCD: the input spectra a chunk re-reads stay in one L2
     pl.n_chunks = want;         // chunk q = pairs [q n_pairs / n_chunks, (q+1) n_pairs / n_chunks)
     pl.ppc = (pl.n_pairs + want - 1) / want;
-    auto pad = [](size_t b) { return (b + 255) & ~size_t(255); };
-    pl.bytes = pad(sizeof(float2) * (size_t)n_cx * pl.n_pairs * NN) + pad(sizeof(float) * (size_t)n_cx * pl.n_pairs * W::NB) +
-               pad(sizeof(float) * (size_t)pl.n_chunks * n_cx * W::NB) + pad(sizeof(float2) * (size_t)pl.n_chunks * n_cy * W::NB) +
-               pad(sizeof(float) * (size_t)pl.n_chunks * n_cy * W::NB);
     return pl;
 }
 

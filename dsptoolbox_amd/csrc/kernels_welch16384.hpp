@@ -265,7 +265,6 @@ __global__ __launch_bounds__(256) void k_fold(Args p) {
 // ---- host side ------------------------------------------------------------------------
 struct Plan {
     int n_pairs, n_chunks;
-    size_t bytes;
 };
 inline Plan plan(int n_frames, int n_cy, int n_cx = 1) {
     Plan pl;
@@ -279,11 +278,6 @@ inline Plan plan(int n_frames, int n_cy, int n_cx = 1) {
     want = std::max(1, std::min(want, pl.n_pairs));
     if (want >= 8) want &= ~7;
     pl.n_chunks = want;
-    auto pad = [](size_t b) { return (b + 255) & ~size_t(255); };
-    pl.bytes = pad(sizeof(float2) * (size_t)n_cx * pl.n_pairs * N) + pad(sizeof(float) * (size_t)n_cx * pl.n_pairs * N) +
-               pad(sizeof(float) * (size_t)pl.n_chunks * n_cx * NB) + pad(sizeof(float2) * (size_t)pl.n_chunks * n_cy * NB) +
-               pad(sizeof(float) * (size_t)pl.n_chunks * n_cy * NB) + pad(sizeof(float2) * (size_t)pl.n_chunks * n_cy * N) +
-               pad(sizeof(float) * (size_t)pl.n_chunks * n_cy * N);
     return pl;
 }
 

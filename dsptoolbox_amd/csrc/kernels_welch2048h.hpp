@@ -379,16 +379,11 @@ __global__ __launch_bounds__(NT, 3) void k_y2h(Args p) {
 // ---- host side ------------------------------------------------------------------------------------------------------
 struct Plan {
     int n_passes, n_chunks;
-    size_t bytes;
 };
 inline Plan plan(int n_frames, int n_cy, int n_cx, int want_chunks = 0) {
     Plan pl;
     pl.n_passes = (n_frames + 3) / 4;
     pl.n_chunks = w4::chunks_for3(pl.n_passes, n_cy, want_chunks);
-    auto pad = [](size_t b) { return (b + 255) & ~size_t(255); };
-    pl.bytes = pad(sizeof(float2) * (size_t)n_cx * pl.n_passes * PASS) + pad(sizeof(float) * (size_t)n_cx * pl.n_passes * NBW) +
-               pad(sizeof(float) * (size_t)pl.n_chunks * n_cx * NBW) + pad(sizeof(float2) * (size_t)pl.n_chunks * n_cy * NBW) +
-               pad(sizeof(float) * (size_t)pl.n_chunks * n_cy * NBW);
     return pl;
 }
 // the raw-buffer loads carry byte offsets in 32 bits

@@ -565,17 +565,12 @@ inline int chunks_for(int n_pairs, int n_ch, int want = 0) {
 
 struct Plan {
     int n_pairs, n_chunks, ppc;
-    size_t bytes;
 };
 inline Plan plan(int n_frames, int n_cy, int want_chunks = 0) {
     Plan pl;
     pl.n_pairs = (n_frames + 1) / 2;
     pl.n_chunks = chunks_for(pl.n_pairs, n_cy, want_chunks);  // chunk q = pairs [q n_pairs / n_chunks, (q+1) n_pairs / n_chunks)
     pl.ppc = (pl.n_pairs + pl.n_chunks - 1) / pl.n_chunks;
-    auto pad = [](size_t b) { return (b + 255) & ~size_t(255); };
-    pl.bytes = pad(sizeof(float2) * (size_t)pl.n_pairs * N) + pad(sizeof(float) * (size_t)pl.n_pairs * NB) +
-               pad(sizeof(float) * (size_t)pl.n_chunks * NB) + pad(sizeof(float2) * (size_t)pl.n_chunks * n_cy * NB) +
-               pad(sizeof(float) * (size_t)pl.n_chunks * n_cy * NB);
     return pl;
 }
 

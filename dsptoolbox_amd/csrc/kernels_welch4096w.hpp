@@ -698,10 +698,6 @@ inline Plan plan3(int n_frames, int n_cy, int want_chunks = 0) {
     pl.n_pairs = (n_frames + 1) / 2;
     pl.n_chunks = chunks_for3(pl.n_pairs, n_cy, want_chunks);
     pl.ppc = (pl.n_pairs + pl.n_chunks - 1) / pl.n_chunks;
-    auto pad = [](size_t b) { return (b + 255) & ~size_t(255); };
-    pl.bytes = pad(sizeof(float2) * (size_t)pl.n_pairs * N) + pad(sizeof(float) * (size_t)pl.n_pairs * NB) +
-               pad(sizeof(float) * (size_t)pl.n_chunks * NB) + pad(sizeof(float2) * (size_t)pl.n_chunks * n_cy * NB) +
-               pad(sizeof(float) * (size_t)pl.n_chunks * n_cy * NB);
     return pl;
 }
 // Where the n_pairs % n_chunks longer chunks go.  k_y3 hands XCD x the units [x U, (x + 1) U) of
