@@ -78,6 +78,15 @@ __device__ inline double block_sum(double v, double* red) {
     for (int k = 0; k < THREADS / 64; ++k) s += red[k];
     return s;
 }
+__device__ inline double block_max(double v, double* red) {
+    v = wave_max(v);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    double m = red[0];
+    for (int k = 1; k < THREADS / 64; ++k) m = fmax(m, red[k]);
+    return m;
+}
 
 // ---- eigendecomposition ------------------------------------------------------------------
 struct EighArgs {
@@ -104,13 +113,25 @@ __global__ __launch_bounds__(THREADS) void k_bf_eigh(EighArgs p) {
     __shared__ int rank[MAX_CH];
     const int n = p.n, t = threadIdx.x, b = blockIdx.x;
     const double2* a = p.a + (size_t)b * n * n;
+    double amax = 0.0;
     for (int e = t; e < n * n; e += THREADS) {
         const int i = e / n, j = e - i * n;
         double2 x = i >= j ? a[e] : conjd(a[j * n + i]);  // the lower triangle, as eigh (UPLO='L')
         if (i == j) x.y = 0.0;
+        amax = fmax(amax, fmax(fabs(x.x), fabs(x.y)));
         A[i * LD + j] = x;
         V[i * LD + j] = make_double2(i == j ? 1.0 : 0.0, 0.0);
     }
+    // scale by 2^-ex so that the largest |entry| is in [0.5, 1): exact, and the sums of squares below neither
+    // overflow nor go subnormal (as LAPACK scales before eigh); the eigenvalues are scaled back on output
+    int ex = 0;
+    amax = block_max(amax, red);
+    if (amax > 0.0 && amax <= DBL_MAX) frexp(amax, &ex);
+    if (ex != 0)
+        for (int e = t; e < n * n; e += THREADS) {
+            double2& x = A[(e / n) * LD + e % n];
+            x = make_double2(ldexp(x.x, -ex), ldexp(x.y, -ex));
+        }
     __syncthreads();
     double fro2 = 0.0;
     for (int e = t; e < n * n; e += THREADS) fro2 += abs2(A[(e / n) * LD + e % n]);
@@ -199,7 +220,7 @@ __global__ __launch_bounds__(THREADS) void k_bf_eigh(EighArgs p) {
             r += (lj < lt) || (lj == lt && j < t);
         }
         rank[t] = r;
-        p.w[(size_t)b * n + r] = lt;
+        p.w[(size_t)b * n + r] = ldexp(lt, ex);
     }
     __syncthreads();
     double2* vo = p.v + (size_t)b * n * n;
