@@ -25,6 +25,7 @@ NO_SCRATCH = [
     "fir16k5k_firILb1E", "fir4k5k_firILi1E", "fir4k5k_firILi2E", "fir4k6k_fir3ILi0E", "deconv8k10k_deconv_p", "k_csm_gemm64",
     "k_bf_eigh", "k_bf_project", "k_bf_cleansc",
     "k_iir_group", "k_iir_carry", "k_iir_apply",
+    "k_delay_sum",
 ]
 
 

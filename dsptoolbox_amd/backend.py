@@ -1352,3 +1352,109 @@ def _sosfiltfilt(sos, x):
 def _filtfilt_iir(b, a, x):
     """scipy.signal.filtfilt(b, a, x, axis=0) of an IIR filter of order <= 2 on the device."""
     return _filtfilt_sections(_ba_section(b, a), x, 3 * max(len(a), len(b)))
+
+
+# ---- fractional delays and their weighted sums (ds_delay_sum, csrc/kernels_delay.hpp) ------------------------------
+DELAY_MAX_ORDER = 255  # the kernel's limit (DS_ERR_UNSUP above)
+
+
+def _kaiser_window_beta(side_lobe_suppression_db: float) -> float:
+    """standard/_standard_backend.py:259-287 (pyfar's Eq. 7.75 of Oppenheim & Schafer)."""
+    a = np.abs(side_lobe_suppression_db)
+    if a > 50:
+        return 0.1102 * (a - 8.7)
+    if a >= 21:
+        return 0.5842 * (a - 21) ** 0.4 + 0.07886 * (a - 21)
+    return 0.0
+
+
+def _delay_split(delay_samples, order: int):
+    """(integer_delay, fraction) of _fractional_delay_filter (standard/_standard_backend.py:430-492) for one delay in
+    samples or an array of them: int() truncation, the fraction as delay - int(delay), and M_opt with np.round's
+    half-to-even (a fraction of exactly 0.5 does not shift).  The same float64 operations as the reference, so an
+    integer part never flips against it."""
+    d = np.asarray(delay_samples, dtype=np.float64)
+    d_int = np.trunc(d)
+    frac = d - d_int
+    if order % 2:
+        m_opt = np.trunc(frac) - (order - 1) / 2
+    else:
+        m_opt = np.round(frac) - order / 2
+    integer_delay = np.trunc(d_int + m_opt).astype(np.int64)
+    if np.ndim(delay_samples) == 0:
+        return int(integer_delay), float(frac)
+    return integer_delay, frac
+
+
+def _delay_terms(n_rows: int, n_terms: int, src, shift, frac, weight):
+    src = np.ascontiguousarray(np.broadcast_to(np.asarray(src, dtype=np.int32), (n_rows, n_terms)))
+    shift = np.ascontiguousarray(np.broadcast_to(np.asarray(shift, dtype=np.int64), (n_rows, n_terms)))
+    frac = np.ascontiguousarray(np.broadcast_to(np.asarray(frac, dtype=np.float64), (n_rows, n_terms)))
+    weight = np.ascontiguousarray(np.broadcast_to(np.asarray(weight, dtype=np.float64), (n_rows, n_terms)))
+    return src, shift, frac, weight
+
+
+def delay_sum(x, src_len, src, shift, frac, weight, order: int, side_lobe_suppression_db: float, out_len: int,
+              want_samples: bool = True, want_peaks: bool = False):
+    """y[g, t] = sum_j weight[g,j] (h(frac[g,j]) * x_{src[g,j]})[t - shift[g,j]] for 0 <= t < out_len on the device
+    (ds_delay_sum, float64).  x (N, sources) float64, source c read over its first src_len[c] samples; src is a
+    (rows, terms) array, shift, frac and weight broadcast to it; frac < 0 marks a pass-through (a delay of exactly 0).  Returns
+    (y (out_len, rows) float64 or None, peaks (rows,) float64 or None): peaks[g] = max_t |y[g, t]|."""
+    xa = np.ascontiguousarray(np.asarray(x, dtype=np.float64))
+    if xa.ndim == 1:
+        xa = xa[:, None]
+    n_x, n_src = xa.shape
+    n_rows, n_terms = np.shape(src)
+    src, shift, frac, weight = _delay_terms(n_rows, n_terms, src, shift, frac, weight)
+    lens = np.ascontiguousarray(np.broadcast_to(np.asarray(src_len, dtype=np.int64), (n_src,)))
+    y = np.empty((int(out_len), n_rows), dtype=np.float64) if want_samples else None
+    pk = np.zeros(n_rows, dtype=np.float64) if want_peaks else None
+    ctx = get_context()
+    ctx.check(ctx.lib.ds_delay_sum(ctx.handle, _ptr(xa), n_src, n_x, _ptr(lens), n_rows, n_terms, _ptr(src),
+                                   _ptr(shift), _ptr(frac), _ptr(weight), int(order),
+                                   float(_kaiser_window_beta(side_lobe_suppression_db)), int(out_len),
+                                   None if y is None else _ptr(y), None if pk is None else _ptr(pk)), "ds_delay_sum")
+    return y, pk
+
+
+def delay_sum_device(x_dev: DevicePlanar, src_len, src, shift, frac, weight, order: int,
+                     side_lobe_suppression_db: float, out_len: int) -> DevicePlanar:
+    """delay_sum over device-resident planar float32 sources (ds_delay_sum_dev, float64 arithmetic) -> a DevicePlanar
+    of the rows (rows, out_len).  Nothing comes down."""
+    n_rows, n_terms = np.shape(src)
+    src, shift, frac, weight = _delay_terms(n_rows, n_terms, src, shift, frac, weight)
+    lens = np.ascontiguousarray(np.broadcast_to(np.asarray(src_len, dtype=np.int64), (x_dev.n_ch,)))
+    ctx = x_dev.ctx
+    out_len = int(out_len)
+    d_y = DeviceBuffer(ctx, n_rows * out_len * 4)
+    try:
+        ctx.check(ctx.lib.ds_delay_sum_dev(ctx.handle, C.c_void_p(x_dev.ptr), x_dev.n_ch, x_dev.ld, _ptr(lens), n_rows,
+                                           n_terms, _ptr(src), _ptr(shift), _ptr(frac), _ptr(weight), int(order),
+                                           float(_kaiser_window_beta(side_lobe_suppression_db)), out_len,
+                                           C.c_void_p(d_y.ptr), out_len, None), "ds_delay_sum_dev")
+    except BaseException:
+        d_y.free()
+        raise
+    return DevicePlanar(d_y, n_rows, out_len, out_len)
+
+
+def stack_device(planars, lengths) -> DevicePlanar:
+    """One-channel device signals -> one DevicePlanar (sources, max length): row j holds the first lengths[j] samples
+    of planars[j], zeros after them.  Each row is a pass-through of ds_delay_sum_dev (a unit tap: exact)."""
+    ctx = planars[0].ctx
+    n_max = int(max(lengths))
+    buf = DeviceBuffer(ctx, len(planars) * n_max * 4)
+    one = np.zeros((1, 1), dtype=np.int32)
+    zero = np.zeros((1, 1), dtype=np.int64)
+    through = np.full((1, 1), -1.0)
+    w = np.ones((1, 1))
+    try:
+        for j, (p, n) in enumerate(zip(planars, lengths)):
+            lens = np.array([int(n)], dtype=np.int64)
+            ctx.check(ctx.lib.ds_delay_sum_dev(ctx.handle, C.c_void_p(p.ptr), 1, p.ld, _ptr(lens), 1, 1, _ptr(one),
+                                               _ptr(zero), _ptr(through), _ptr(w), 1, 0.0, n_max,
+                                               C.c_void_p(buf.ptr + 4 * j * n_max), n_max, None), "ds_delay_sum_dev")
+    except BaseException:
+        buf.free()
+        raise
+    return DevicePlanar(buf, len(planars), n_max, n_max)

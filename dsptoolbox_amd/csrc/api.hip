@@ -41,6 +41,7 @@
 #include "kernels_freqz.hpp"
 #include "kernels_beamform.hpp"
 #include "kernels_iir.hpp"
+#include "kernels_delay.hpp"
 
 using namespace dsk;
 
@@ -3781,6 +3782,100 @@ extern "C" int ds_iir_sos(ds_ctx* c, const double* x, int n_ch, int64_t n_sample
                         dy, (int64_t)nx, 1, n_ch, zf ? dzf : nullptr));
     CHK(ds_download(c, y, dy, ny * 8));
     if (zf) CHK(ds_download(c, zf, dzf, nz * 8));
+    return DS_OK;
+}
+
+// ---- weighted sums of fractionally delayed channels (kernels_delay.hpp) -----------------------------------------
+// the taps of every term, then the sum; x element (c, n) at x[c sxc + n sxn], y element (g, t) at y[g syg + t syt]
+template <typename T>
+static int delay_run(ds_ctx* c, const char* who, const T* x, int64_t sxc, int64_t sxn, int n_src,
+                     const int64_t* src_len, int n_rows, int n_terms, const int* src, const int64_t* shift,
+                     const double* frac, const double* weight, int order, double beta, int64_t out_len, T* y,
+                     int64_t syg, int64_t syt, double* peak) {
+    const int ntp = (order + 1 + dly::R - 1) / dly::R * dly::R;
+    const size_t n_t = (size_t)n_rows * n_terms;
+    if ((n_rows + dly::WAVES - 1) / dly::WAVES > 65535)
+        return fail(c, DS_ERR_UNSUP, std::string(who) + ": more than 262140 output rows in one call is not built");
+    if ((out_len + dly::TT - 1) / dly::TT > INT32_MAX || (n_t * ntp + 255) / 256 > (size_t)INT32_MAX)
+        return fail(c, DS_ERR_UNSUP, std::string(who) + ": output too long or too many terms");
+    for (size_t e = 0; e < n_t; ++e)
+        if (src[e] < 0 || src[e] >= n_src || !std::isfinite(weight[e]) || !(frac[e] < 1.0))
+            return fail(c, DS_ERR_ARG, std::string(who) + ": a term's source, weight or fraction is out of range");
+    int64_t *dlen, *dshift;
+    int* dsrc;
+    double *dfrac, *dw, *dtaps;
+    unsigned long long* dpk;
+    CHK(carve(c, &c->ws, &c->ws_bytes, [&](Carver& cv) {
+        dlen = cv.take<int64_t>(n_src);
+        dsrc = cv.take<int>(n_t);
+        dshift = cv.take<int64_t>(n_t);
+        dfrac = cv.take<double>(n_t);
+        dw = cv.take<double>(n_t);
+        dtaps = cv.take<double>(n_t * ntp);
+        dpk = cv.take<unsigned long long>(peak ? n_rows : 0);
+    }));
+    CHK(ds_upload(c, dlen, src_len, (size_t)n_src * 8));
+    CHK(ds_upload(c, dsrc, src, n_t * 4));
+    CHK(ds_upload(c, dshift, shift, n_t * 8));
+    CHK(ds_upload(c, dfrac, frac, n_t * 8));
+    CHK(ds_upload(c, dw, weight, n_t * 8));
+    if (peak) HIPCHK(c, hipMemsetAsync(dpk, 0, (size_t)n_rows * 8, c->stream));
+    dly::TapArgs ta{dfrac, (int)n_t, order, ntp, beta, dtaps};
+    const int64_t n_tap_threads = (int64_t)n_t * ntp;
+    CHK(launch(c, "delay_taps", dly::k_delay_taps, dim3((unsigned)((n_tap_threads + 255) / 256)), 256, 0, ta));
+    dly::Args<T> a{x, sxc, sxn, dlen, y, syg, syt, out_len, n_rows, n_terms, ntp, dsrc, dshift, dw, dtaps,
+                   peak ? dpk : nullptr};
+    CHK(launch(c, "delay_sum", dly::k_delay_sum<T>,
+               dim3((unsigned)((out_len + dly::TT - 1) / dly::TT), (unsigned)((n_rows + dly::WAVES - 1) / dly::WAVES)),
+               dly::THREADS, 0, a));
+    if (peak) CHK(ds_download(c, peak, dpk, (size_t)n_rows * 8));  // the bits of non-negative doubles
+    return DS_OK;
+}
+
+static int delay_shape_ok(ds_ctx* c, const char* who, int n_src, const int64_t* src_len, int64_t n_avail, int n_rows,
+                          int n_terms, const int* src, const int64_t* shift, const double* frac,
+                          const double* weight, int order, double beta, int64_t out_len) {
+    if (!src_len || !src || !shift || !frac || !weight) return fail(c, DS_ERR_ARG, std::string(who) + ": null argument");
+    if (n_src <= 0 || n_rows <= 0 || n_terms <= 0 || out_len <= 0 || !std::isfinite(beta) || beta < 0)
+        return fail(c, DS_ERR_ARG, std::string(who) + ": bad shape");
+    for (int s = 0; s < n_src; ++s)
+        if (src_len[s] < 0 || src_len[s] > n_avail) return fail(c, DS_ERR_ARG, std::string(who) + ": bad source length");
+    if (order < 1 || order > dly::MAX_ORDER)
+        return fail(c, DS_ERR_UNSUP, std::string(who) + ": filter orders 1 to 255 are built");
+    return DS_OK;
+}
+
+extern "C" int ds_delay_sum_dev(ds_ctx* c, const float* x, int n_src, int64_t ldx, const int64_t* src_len,
+                                int n_rows, int n_terms, const int* src, const int64_t* shift, const double* frac,
+                                const double* weight, int order, double beta, int64_t out_len, float* y,
+                                int64_t ld_y, double* peak) {
+    if (!c || !x || (!y && !peak)) return fail(c, DS_ERR_ARG, "ds_delay_sum_dev: null argument");
+    CHK(delay_shape_ok(c, "ds_delay_sum_dev", n_src, src_len, ldx, n_rows, n_terms, src, shift, frac, weight, order,
+                       beta, out_len));
+    if (y && ld_y < out_len) return fail(c, DS_ERR_ARG, "ds_delay_sum_dev: bad shape");
+    HIPCHK(c, hipSetDevice(c->device));
+    return delay_run<float>(c, "ds_delay_sum_dev", x, ldx, 1, n_src, src_len, n_rows, n_terms, src, shift, frac,
+                            weight, order, beta, out_len, y, ld_y, 1, peak);
+}
+
+// host pointers in the reference's layouts: x (n_x, n_src), y (out_len, n_rows), float64
+extern "C" int ds_delay_sum(ds_ctx* c, const double* x, int n_src, int64_t n_x, const int64_t* src_len, int n_rows,
+                            int n_terms, const int* src, const int64_t* shift, const double* frac,
+                            const double* weight, int order, double beta, int64_t out_len, double* y, double* peak) {
+    if (!c || !x || (!y && !peak)) return fail(c, DS_ERR_ARG, "ds_delay_sum: null argument");
+    CHK(delay_shape_ok(c, "ds_delay_sum", n_src, src_len, n_x, n_rows, n_terms, src, shift, frac, weight, order, beta,
+                       out_len));
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t nx = (size_t)n_src * n_x, ny = y ? (size_t)n_rows * out_len : 0;
+    double *dx, *dy;
+    CHK(carve(c, &c->io, &c->io_bytes, [&](Carver& cv) {
+        dx = cv.take<double>(nx);
+        dy = cv.take<double>(ny);
+    }));
+    CHK(ds_upload(c, dx, x, nx * 8));
+    CHK(delay_run<double>(c, "ds_delay_sum", dx, 1, n_src, n_src, src_len, n_rows, n_terms, src, shift, frac, weight,
+                          order, beta, out_len, y ? dy : nullptr, 1, n_rows, peak));
+    if (y) CHK(ds_download(c, y, dy, ny * 8));
     return DS_OK;
 }
 

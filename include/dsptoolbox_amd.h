@@ -381,6 +381,27 @@ int ds_iir_sos_dev(ds_ctx* ctx, const float* x_dev, int n_ch, int64_t ldx, int64
                    int n_filt, int n_sec, const double* zi_dev, int mode, float* y_dev, int64_t ld_y,
                    double* zf_dev);
 
+/* ---- fractional delays and their weighted sums, float64 arithmetic: replaces the reference's fractional_delay
+ * (standard/latency_delay.py:159-285, filter from standard/_standard_backend.py:259-321, :430-492) and the loops of
+ * MonopoleSource.get_signals_on_array, mix_sources_on_array and BeamformerDASTime (beamforming/beamforming.py:
+ * 1317-1512).  Computes, for 0 <= g < n_rows and 0 <= t < out_len,
+ *     y[g, t] = sum_{j < n_terms} w[g,j] sum_{k <= order} h(frac[g,j])[k] x_{src[g,j]}[t - shift[g,j] - k]
+ * with x_c[n] = 0 outside [0, src_len[c]).  h(f) is the reference's Kaiser-windowed sinc for the fractional delay f
+ * (0 <= f < 1, side lobe parameter beta = _kaiser_window_beta(...)); a term with frac < 0 is a pass-through, the
+ * single unit tap of a delay of exactly 0.  shift may be negative.  The per-term arrays src (int), shift (int64),
+ * frac and weight (float64) are host pointers laid out [n_rows][n_terms]; src_len is a host array [n_src].
+ * peak (host, [n_rows], or NULL) receives each row's max |y| as computed, before any rounding of the output type;
+ * y may be NULL when only the peaks are wanted.  Orders 1 to 255 and at most 262140 rows: DS_ERR_UNSUP beyond.
+ * ds_delay_sum: x (n_x, n_src) float64 host (the reference's (samples, channels)), src_len[c] <= n_x;
+ * y (out_len, n_rows) float64 host.
+ * ds_delay_sum_dev: x_dev planar float32 x_dev[c*ldx + n], src_len[c] <= ldx; y_dev[g*ld_y + t] float32.          */
+int ds_delay_sum(ds_ctx* ctx, const double* x, int n_src, int64_t n_x, const int64_t* src_len, int n_rows,
+                 int n_terms, const int* src, const int64_t* shift, const double* frac, const double* weight,
+                 int order, double beta, int64_t out_len, double* y, double* peak);
+int ds_delay_sum_dev(ds_ctx* ctx, const float* x_dev, int n_src, int64_t ldx, const int64_t* src_len, int n_rows,
+                     int n_terms, const int* src, const int64_t* shift, const double* frac, const double* weight,
+                     int order, double beta, int64_t out_len, float* y_dev, int64_t ld_y, double* peak);
+
 /* ---- block-streaming FIR classes with device-resident state ------------------------------
  * One process_block of the reference's real-time classes (classes/fir_filter_realtime.py:75-335),
  * executed literally on buffers that stay on the device between calls; per call only the block
