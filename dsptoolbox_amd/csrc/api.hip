@@ -462,7 +462,9 @@ static int launch(ds_ctx* c, const char* name, K kernel, dim3 grid, int threads,
 // every Welch route ends here: chunk partials -> spectra / transfer functions (kernels_finish.hpp).  Partial slabs of
 // 4 GiB or more leave the kernel's 32-bit raw-buffer descriptors (size_guards.hpp); DSPTOOLBOX_AMD_FINISH_WIDE=1
 // sends every call down that 64-bit-load path (the GPU test of it: such slabs themselves do not fit a test).
-static int launch_finish(ds_ctx* c, dim3 grid, WelchFinArgs f) {
+// One thread per output value, 64 per workgroup.
+static int launch_finish(ds_ctx* c, WelchFinArgs f) {
+    const dim3 grid((unsigned)(((int64_t)f.fin.nb * (f.kind == 1 ? f.n_cx : f.n_cy) + 63) / 64));
     f.force_wide = c->cfg.finish_wide ? 1 : 0;
     const bool wide = f.force_wide || welch_finish_wide_slab((int64_t)f.n_cx * (f.in_nb > 0 ? f.in_nb : f.fin.nb),
                                                              (int64_t)f.n_cy * (f.in_nb > 0 ? f.in_nb : f.fin.nb));
@@ -515,7 +517,17 @@ static int check_fft_len(ds_ctx* c, int n, const char* what) {
     return DS_OK;
 }
 
-static int upload_table_fwd(ds_ctx* c, float2** slot, const std::vector<float2>& h);
+// a context's constant table: filled on the host (fill(std::vector<float2>&)) and uploaded on first use
+template <class Fill>
+static int ensure_table(ds_ctx* c, float2** slot, Fill fill) {
+    if (*slot) return DS_OK;
+    std::vector<float2> h;
+    fill(h);
+    HIPCHK(c, hipMalloc((void**)slot, sizeof(float2) * h.size()));
+    HIPCHK(c, hipMemcpyAsync(*slot, h.data(), sizeof(float2) * h.size(), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return DS_OK;
+}
 struct BigScratch {  // stft_big's scratch: two groups of four-step transforms and the frame means
     float2 *P, *Q;
     float* means;
@@ -584,17 +596,9 @@ extern "C" int ds_stft_r2c_dev(ds_ctx* c, const float* x, int64_t n_samples, int
     if (const int R = stftl::classes_of(nfft); R && W <= nfft && (W == nfft || !detrend) && !c->cfg.stft_generic && (n_ch + 1) / 2 <= 65535) {
         int lgR = 0;
         while ((1 << lgR) < R) ++lgR;
-        if (!c->w4_tables) {
-            std::vector<float2> h;
-            welch4096::host_tables(h);
-            CHK(upload_table_fwd(c, &c->w4_tables, h));
-        }
+        CHK(ensure_table(c, &c->w4_tables, welch4096::host_tables));
         float2** slot = &c->wl_tables[lgR - 1];
-        if (!*slot) {
-            std::vector<float2> h;
-            welchl::host_tables(R, h);
-            CHK(upload_table_fwd(c, slot, h));
-        }
+        CHK(ensure_table(c, slot, [R](std::vector<float2>& h) { welchl::host_tables(R, h); }));
         const int n_pc = (n_ch + 1) / 2, n_groups = (n_ch + 15) / 16;
         const int per = std::min(65535, stftl::frames_per_group(n_ch, nfft, n_frames));
         float2* b;
@@ -641,14 +645,12 @@ extern "C" int ds_stft_r2c_dev(ds_ctx* c, const float* x, int64_t n_samples, int
         nfft = nfft_k;
         const int slot = nfft == 1024 ? 0 : (nfft == 512 ? 1 : (nfft == 256 ? 2 : 3));
         float2** tab = slot == 0 ? &c->stft1k_tables : &c->stft_wave_tables[slot - 1];
-        if (!*tab) {
-            std::vector<float2> h;
+        CHK(ensure_table(c, tab, [nfft](std::vector<float2>& h) {
             if (nfft == 2048) stft1k::host_tables<2048>(h);
             else if (nfft == 1024) stft1k::host_tables<1024>(h);
             else if (nfft == 512) stft1k::host_tables<512>(h);
             else stft1k::host_tables<256>(h);
-            CHK(upload_table_fwd(c, tab, h));
-        }
+        }));
         // channels per workgroup: 16 teams = 128-byte runs of the output X[bin][frame][channel] (whole
         // cache lines; at 1024 points that is one 1024-thread workgroup of 140 KB per CU instead of two
         // of 8 channels with 64-byte runs: transform of the 64-microphone shape 105 -> 97 us);
@@ -685,11 +687,7 @@ extern "C" int ds_stft_r2c_dev(ds_ctx* c, const float* x, int64_t n_samples, int
     // 4096-point transforms: the register-resident transform of the Welch path, four teams of two neighbouring
     // channels per workgroup and frame (kernels_stft4096.hpp)
     if (nfft == 4096 && W <= nfft && (W == nfft || !detrend) && !stft_generic && stft4k::fits(n_samples, pad_front)) {
-        if (!c->w4_tables) {
-            std::vector<float2> h;
-            welch4096::host_tables(h);
-            CHK(upload_table_fwd(c, &c->w4_tables, h));
-        }
+        CHK(ensure_table(c, &c->w4_tables, welch4096::host_tables));
         const int n_groups = (n_ch + 15) / 16;
         // chunks of frames: as many as put one workgroup (8 channels) on each of the 256 CUs
         int n_chunks = std::max(1, std::min(n_frames, 128 / std::max(1, std::min(128, n_groups))));
@@ -704,17 +702,9 @@ extern "C" int ds_stft_r2c_dev(ds_ctx* c, const float* x, int64_t n_samples, int
     // 4096-point kernel's structure per residue (kernels_stft4096.hpp, k_stft_dif)
     if ((nfft == 8192 || nfft == 16384) && W <= nfft && (W == nfft || !detrend) && !stft_generic &&
         stft4k::fits_long(n_samples, pad_front, nfft)) {
-        if (!c->w4_tables) {
-            std::vector<float2> h;
-            welch4096::host_tables(h);
-            CHK(upload_table_fwd(c, &c->w4_tables, h));
-        }
+        CHK(ensure_table(c, &c->w4_tables, welch4096::host_tables));
         float2** twn = &c->stft_dif_tw[nfft == 8192 ? 0 : 1];
-        if (!*twn) {
-            std::vector<float2> h;
-            stft4k::host_twiddles(nfft, h);
-            CHK(upload_table_fwd(c, twn, h));
-        }
+        CHK(ensure_table(c, twn, [nfft](std::vector<float2>& h) { stft4k::host_twiddles(nfft, h); }));
         const int n_groups = (n_ch + 15) / 16;
         // chunks of (frame, phase) units: two rounds of one workgroup (8 channels) per CU (64 x 512 000 samples, 8192
         // points: 0.182 ms against 0.198 with one round)
@@ -835,17 +825,9 @@ extern "C" int ds_istft_dev(ds_ctx* c, const ds_c32* stft, int n_bins, int n_fra
                                                  (int64_t)n_bins * n_frames * n_ch * 8 < ((int64_t)1 << 32) - 16) {
         int lgR = 0;
         while ((1 << lgR) < R) ++lgR;
-        if (!c->w4_tables) {
-            std::vector<float2> h;
-            welch4096::host_tables(h);
-            CHK(upload_table_fwd(c, &c->w4_tables, h));
-        }
+        CHK(ensure_table(c, &c->w4_tables, welch4096::host_tables));
         float2** slot = &c->wl_tables[lgR - 1];
-        if (!*slot) {
-            std::vector<float2> h;
-            welchl::host_tables(R, h);
-            CHK(upload_table_fwd(c, slot, h));
-        }
+        CHK(ensure_table(c, slot, [R](std::vector<float2>& h) { welchl::host_tables(R, h); }));
         const int n_pc = (n_ch + 1) / 2, n_groups = (n_ch + 15) / 16;
         // (fused: the class sequences of ALL frames at once, addressed through a raw-buffer descriptor: below 4 GB)
         const bool fused = W == nfft && 2 * step == nfft && R <= 16 &&
@@ -921,14 +903,12 @@ extern "C" int ds_istft_dev(ds_ctx* c, const ds_c32* stft, int n_bins, int n_fra
         // (2048 points: 45 registers over the 128 of a 1024-thread workgroup: four teams = 512 threads there)
         const int slot = nfft == 1024 ? 0 : (nfft == 512 ? 1 : (nfft == 256 ? 2 : 3));
         float2** tab = slot == 0 ? &c->stft1k_tables : &c->stft_wave_tables[slot - 1];
-        if (!*tab) {
-            std::vector<float2> h;
+        CHK(ensure_table(c, tab, [nfft](std::vector<float2>& h) {
             if (nfft == 2048) stft1k::host_tables<2048>(h);
             else if (nfft == 1024) stft1k::host_tables<1024>(h);
             else if (nfft == 512) stft1k::host_tables<512>(h);
             else stft1k::host_tables<256>(h);
-            CHK(upload_table_fwd(c, tab, h));
-        }
+        }));
         const int lanes = nfft / 16;
         int ct = std::min(nfft == 2048 ? 4 : 16, n_ch);
         while (ct & (ct - 1)) ct &= ct - 1;
@@ -954,11 +934,7 @@ extern "C" int ds_istft_dev(ds_ctx* c, const ds_c32* stft, int n_bins, int n_fra
     // ... and on the 4096-point register transform, two neighbouring channels per team (kernels_stft4096.hpp, k_istft)
     if (W == nfft && nfft == 4096 && 2 * step == nfft && n_ch > 1 && !no_fuse && !no_wave &&
         total_length < ((int64_t)1 << 31) && (int64_t)n_bins * n_frames * n_ch * 8 < ((int64_t)1 << 32) - 16) {
-        if (!c->w4_tables) {
-            std::vector<float2> h;
-            welch4096::host_tables(h);
-            CHK(upload_table_fwd(c, &c->w4_tables, h));
-        }
+        CHK(ensure_table(c, &c->w4_tables, welch4096::host_tables));
         const int n_groups = (n_ch + 15) / 16;
         // chunks of frames (+ 1 frame each for the carry): two rounds of one workgroup (8 channels) per CU
         int n_chunks = std::max(1, std::min((n_frames + 3) / 4, 256 / std::max(1, std::min(256, n_groups))));
@@ -1117,16 +1093,6 @@ static int welch_common(ds_ctx* c, int kind, const float* x, int n_cx, int64_t l
                         const float* window, int detrend, int average, int mode, int amp_sqrt,
                         double norm_scale, double factor, int halve_edges, float2* out_c,
                         float* out_r) {
-    if (!c || !x || !window) return fail(c, DS_ERR_ARG, "welch: null argument");
-    if (average != DS_AVG_MEAN && average != DS_AVG_MEDIAN)
-        return fail(c, DS_ERR_ARG, "welch: average must be mean (0) or median (1)");
-    if (kind != 1 && !y) return fail(c, DS_ERR_ARG, "welch: null output-signal pointer");
-    if (n_cx <= 0 || n_samples <= 0 || hop <= 0 || hop > W || n_frames <= 0 || ldx < n_samples)
-        return fail(c, DS_ERR_ARG, "welch: bad shape");
-    if (kind != 1 && (n_cy <= 0 || ldy < n_samples || !(n_cx == 1 || n_cx == n_cy)))
-        return fail(c, DS_ERR_ARG, "welch: input must have 1 channel or as many as the output");
-    if (kind == 0 && (mode < DS_TF_H1 || mode > DS_TF_H3))
-        return fail(c, DS_ERR_ARG, "welch: unsupported transfer function type");
     if (W > kMaxFft && is_pow2(W))
         return welch_big(c, kind, x, n_cx, ldx, y, n_cy, ldy, n_samples, W, hop, n_frames, window, detrend,
                          average, mode, amp_sqrt, norm_scale, factor, halve_edges, out_c, out_r);
@@ -1168,9 +1134,7 @@ static int welch_common(ds_ctx* c, int kind, const float* x, int n_cx, int64_t l
         WelchFinArgs f{mxx, mxy, myy, 1, 1, n_cx, n_cy, kind, mode,
                        FinishPar{norm_scale * (double)std::max(1, nbias), factor, halve_edges, amp_sqrt, nb},
                        out_c, out_r};
-        int64_t total = (int64_t)nb * (kind == 1 ? n_cx : n_cy);
-        CHK(launch_finish(c, dim3((unsigned)((total + 63) / 64)), f));
-        return DS_OK;
+        return launch_finish(c, f);
     }
     const bool need_xs = kind != 1;
     float *pxx, *pyy = nullptr;
@@ -1196,9 +1160,7 @@ static int welch_common(ds_ctx* c, int kind, const float* x, int n_cx, int64_t l
     WelchFinArgs f{pxx, pxy, pyy, pl.n_chunks, pl.n_chunks, n_cx, n_cy, kind, mode,
                    FinishPar{norm_scale / (double)n_frames, factor, halve_edges, amp_sqrt, nb},
                    out_c, out_r};
-    int64_t total = (int64_t)nb * (kind == 1 ? n_cx : n_cy);
-    CHK(launch_finish(c, dim3((unsigned)((total + 63) / 64)), f));
-    return DS_OK;
+    return launch_finish(c, f);
 }
 
 // Frames the kernels have to visit: a frame that starts at or past the end of the signal is all
@@ -1210,88 +1172,82 @@ static int frames_to_visit(int64_t n_samples, int hop, int n_frames) {
     return (int)std::min<int64_t>(n_frames, 2 * pairs);
 }
 
-// nfft 4096, one input channel: register-resident radix-16 FFT path (kernels_welch4096.hpp)
-static int welch4096_run(ds_ctx* c, const float* x, int n_cx, int64_t ldx, const float* y, int n_cy, int64_t ldy,
-                         int64_t n_samples, int hop, int n_frames, const float* window, int detrend,
-                         int mode, int amp_sqrt, double norm_scale, double factor, int halve_edges,
-                         float2* tf, float* coh, int kind = 0) {  // kind 2: tf = cross spectra, no coh
+// Every Welch runner below takes welch_common's arguments, already checked by welch_check, and handles the three kinds:
+// 0: transfer function + coherence (out_c, out_r), 1: auto spectra of x (out_r; y null), 2: cross spectra (out_c).
+
+// nfft 4096: register-resident radix-16 FFT path (kernels_welch4096.hpp); three workgroups per CU at 50 % overlap
+// (kernels_welch4096w.hpp), two otherwise
+static int welch4096_run(ds_ctx* c, int kind, const float* x, int n_cx, int64_t ldx, const float* y, int n_cy,
+                         int64_t ldy, int64_t n_samples, int W, int hop, int n_frames, const float* window, int detrend,
+                         int average, int mode, int amp_sqrt, double norm_scale, double factor, int halve_edges,
+                         float2* out_c, float* out_r) {
     namespace w4 = welch4096;
-    if (!x || !y || !window) return fail(c, DS_ERR_ARG, "ds_welch_tf: null argument");
-    if (n_cx != 1 && n_cx != n_cy) return fail(c, DS_ERR_ARG, "ds_welch_tf: one input channel, or one per output channel");
-    if (n_cy <= 0 || n_samples <= 0 || hop <= 0 || hop > 4096 || n_frames <= 0 || ldx < n_samples ||
-        ldy < n_samples)
-        return fail(c, DS_ERR_ARG, "ds_welch_tf: bad shape");
-    if (mode < DS_TF_H1 || mode > DS_TF_H3) return fail(c, DS_ERR_ARG, "welch: unsupported transfer function type");
-    if (!c->w4_tables) {
-        std::vector<float2> h;
-        w4::host_tables(h);
-        HIPCHK(c, hipMalloc((void**)&c->w4_tables, sizeof(float2) * h.size()));
-        HIPCHK(c, hipMemcpyAsync(c->w4_tables, h.data(), sizeof(float2) * h.size(), hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-    }
+    CHK(ensure_table(c, &c->w4_tables, w4::host_tables));
+    const bool auto_only = kind == 1;
+    const int n_out = auto_only ? n_cx : n_cy;  // channels that are accumulated
     const int nf = frames_to_visit(n_samples, hop, n_frames);
-    // 50 % overlap: three workgroups per CU (kernels_welch4096w.hpp); any other hop: two
     const bool half = hop == 2048;
     const bool three = half && !c->cfg.w4_two_per_cu && w4::fits3(n_samples, nf);
-    w4::Plan pl = three ? w4::plan3(nf, n_cy, c->cfg.welch_chunks) : w4::plan(nf, n_cy, c->cfg.welch_chunks);
-    float2 *xs, *pxy;
-    float *px, *psx, *pyy;
+    w4::Plan pl = three ? w4::plan3(nf, n_out, c->cfg.welch_chunks) : w4::plan(nf, n_out, c->cfg.welch_chunks);
+    float2 *xs = nullptr, *pxy = nullptr;
+    float *px = nullptr, *psx = nullptr, *pyy;
     CHK(carve(c, &c->ws, &c->ws_bytes, [&](Carver& cv) {
-        xs = cv.take<float2>((size_t)n_cx * pl.n_pairs * w4::N);
-        px = cv.take<float>((size_t)n_cx * pl.n_pairs * w4::NB);
-        psx = cv.take<float>((size_t)pl.n_chunks * n_cx * w4::NB);
-        pxy = cv.take<float2>((size_t)pl.n_chunks * n_cy * w4::NB);
-        pyy = cv.take<float>((size_t)pl.n_chunks * n_cy * w4::NB);
+        if (!auto_only) {
+            xs = cv.take<float2>((size_t)n_cx * pl.n_pairs * w4::N);
+            px = cv.take<float>((size_t)n_cx * pl.n_pairs * w4::NB);
+            psx = cv.take<float>((size_t)pl.n_chunks * n_cx * w4::NB);
+            pxy = cv.take<float2>((size_t)pl.n_chunks * n_cy * w4::NB);
+        }
+        pyy = cv.take<float>((size_t)pl.n_chunks * n_out * w4::NB);
     }));
-    w4::Args ax{x, n_samples, ldx, 1, hop, nf, pl.n_pairs, detrend, pl.n_chunks, pl.ppc, window,
+    w4::Args ax{x, n_samples, ldx, auto_only ? n_cx : 1, hop, nf, pl.n_pairs, detrend, pl.n_chunks, pl.ppc, window,
                 c->w4_tables, xs, px, pxy, pyy, psx};
-    ax.n_cx = n_cx;
-    w4::Args ay = ax;
-    ay.sig = y;
-    ay.ld = ldy;
-    ay.n_ch = n_cy;
-    if (three) w4::place_remainder(ay, n_cy);
-    if (three) {
-        CHK(launch(c, "welch4096_x", w4::k_x3, dim3(pl.n_pairs * n_cx), w4::NT, w4::LDS3_BYTES, ax));
-        if (n_cx > 1) CHK(launch(c, "welch4096_pxsum", w4::k_px_sum, dim3(pl.n_chunks, n_cx), 256, 0, ay));
-        CHK(launch(c, "welch4096_main@3", w4::k_y3<false>, dim3(pl.n_chunks * n_cy), w4::NT, w4::LDS3_BYTES, ay));
+    if (auto_only) {
+        if (three) {
+            w4::place_remainder(ax, n_cx);
+            CHK(launch(c, "welch4096_main@3", w4::k_y3<true>, dim3(pl.n_chunks * n_cx), w4::NT, w4::LDS3_BYTES, ax));
+        } else {
+            auto ky = half ? w4::k_y<true, true> : w4::k_y<false, true>;
+            CHK(launch(c, "welch4096_main@2", ky, dim3(pl.n_chunks * n_cx), w4::NT, w4::LDS_BYTES_2, ax));
+        }
     } else {
-        auto kx = half ? w4::k_x<true> : w4::k_x<false>;
-        auto ky = half ? w4::k_y<true> : w4::k_y<false>;
-        CHK(launch(c, "welch4096_x", kx, dim3(pl.n_pairs, n_cx), w4::NT, w4::LDS_BYTES, ax));
-        if (n_cx > 1) CHK(launch(c, "welch4096_pxsum", w4::k_px_sum, dim3(pl.n_chunks, n_cx), 256, 0, ay));
-        CHK(launch(c, "welch4096_main@2", ky, dim3(pl.n_chunks * n_cy), w4::NT, w4::LDS_BYTES_2, ay));
+        ax.n_cx = n_cx;
+        w4::Args ay = ax;
+        ay.sig = y;
+        ay.ld = ldy;
+        ay.n_ch = n_cy;
+        if (three) {
+            w4::place_remainder(ay, n_cy);
+            CHK(launch(c, "welch4096_x", w4::k_x3, dim3(pl.n_pairs * n_cx), w4::NT, w4::LDS3_BYTES, ax));
+            if (n_cx > 1) CHK(launch(c, "welch4096_pxsum", w4::k_px_sum, dim3(pl.n_chunks, n_cx), 256, 0, ay));
+            CHK(launch(c, "welch4096_main@3", w4::k_y3<false>, dim3(pl.n_chunks * n_cy), w4::NT, w4::LDS3_BYTES, ay));
+        } else {
+            auto kx = half ? w4::k_x<true> : w4::k_x<false>;
+            auto ky = half ? w4::k_y<true> : w4::k_y<false>;
+            CHK(launch(c, "welch4096_x", kx, dim3(pl.n_pairs, n_cx), w4::NT, w4::LDS_BYTES, ax));
+            if (n_cx > 1) CHK(launch(c, "welch4096_pxsum", w4::k_px_sum, dim3(pl.n_chunks, n_cx), 256, 0, ay));
+            CHK(launch(c, "welch4096_main@2", ky, dim3(pl.n_chunks * n_cy), w4::NT, w4::LDS_BYTES_2, ay));
+        }
     }
-    WelchFinArgs f{psx, pxy, pyy, pl.n_chunks, pl.n_chunks, n_cx, n_cy, kind, mode,
-                   FinishPar{norm_scale / (double)n_frames, factor, halve_edges, amp_sqrt, w4::NB},
-                   tf, coh};
-    int64_t total = (int64_t)w4::NB * n_cy;
-    CHK(launch_finish(c, dim3((unsigned)((total + 63) / 64)), f));
-    return DS_OK;
+    WelchFinArgs f{auto_only ? pyy : psx, pxy, auto_only ? nullptr : pyy, pl.n_chunks, pl.n_chunks, n_cx, n_cy, kind, mode,
+                   FinishPar{norm_scale / (double)n_frames, factor, halve_edges, amp_sqrt, w4::NB}, out_c, out_r};
+    return launch_finish(c, f);
 }
 
 // window 2048 at 50 % overlap: two 2048-point pair transforms per pass of the 4096-point register machine
-// (kernels_welch2048h.hpp).  y == nullptr: auto spectra of x only (psd in `coh`).
+// (kernels_welch2048h.hpp)
 static bool welch2048h_applies(const ds_ctx* c, int W, int hop, int average, int64_t n_samples, int n_frames) {
     return c && W == 2048 && hop == 1024 && average == DS_AVG_MEAN && !c->cfg.welch_generic && !c->cfg.w2048_wave &&
            welch2048h::fits(n_samples, n_frames);
 }
-static int welch2048h_run(ds_ctx* c, const float* x, int n_cx, int64_t ldx, const float* y, int n_cy, int64_t ldy,
-                          int64_t n_samples, int n_frames, const float* window, int detrend, int mode, int amp_sqrt,
-                          double norm_scale, double factor, int halve_edges, float2* tf, float* coh, int kind = 0) {
+static int welch2048h_run(ds_ctx* c, int kind, const float* x, int n_cx, int64_t ldx, const float* y, int n_cy,
+                          int64_t ldy, int64_t n_samples, int W, int hop, int n_frames, const float* window, int detrend,
+                          int average, int mode, int amp_sqrt, double norm_scale, double factor, int halve_edges,
+                          float2* out_c, float* out_r) {
     namespace wh = welch2048h;
     namespace w4 = welch4096;
     const bool auto_only = kind == 1;
-    if (!x || !window || (!auto_only && !y)) return fail(c, DS_ERR_ARG, "ds_welch: null argument");
-    if (!auto_only && n_cx != 1 && n_cx != n_cy) return fail(c, DS_ERR_ARG, "ds_welch_tf: one input channel, or one per output channel");
-    if (n_cx <= 0 || n_samples <= 0 || n_frames <= 0 || ldx < n_samples || (!auto_only && (n_cy <= 0 || ldy < n_samples)))
-        return fail(c, DS_ERR_ARG, "ds_welch: bad shape");
-    if (kind == 0 && (mode < DS_TF_H1 || mode > DS_TF_H3)) return fail(c, DS_ERR_ARG, "welch: unsupported transfer function type");
-    if (!c->w4_tables) {
-        std::vector<float2> h;
-        w4::host_tables(h);
-        CHK(upload_table_fwd(c, &c->w4_tables, h));
-    }
+    CHK(ensure_table(c, &c->w4_tables, w4::host_tables));
     const int nf = frames_to_visit(n_samples, wh::HOP, n_frames);
     const int n_out = auto_only ? n_cx : n_cy;
     wh::Plan pl = wh::plan(nf, n_out, auto_only ? 0 : n_cx, c->cfg.welch_chunks);
@@ -1312,8 +1268,8 @@ static int welch2048h_run(ds_ctx* c, const float* x, int n_cx, int64_t ldx, cons
         w4::place_remainder(ax, n_cx);
         CHK(launch(c, "welch2048_main@4k", wh::k_y2h<true>, dim3(pl.n_chunks * n_cx), w4::NT, wh::LDS_BYTES, ax));
         WelchFinArgs f{pyy, nullptr, nullptr, pl.n_chunks, pl.n_chunks, n_cx, 0, 1, 0,
-                       FinishPar{norm_scale / (double)n_frames, factor, halve_edges, amp_sqrt, wh::NBW}, nullptr, coh};
-        return launch_finish(c, dim3((unsigned)(((int64_t)wh::NBW * n_cx + 63) / 64)), f);
+                       FinishPar{norm_scale / (double)n_frames, factor, halve_edges, amp_sqrt, wh::NBW}, nullptr, out_r};
+        return launch_finish(c, f);
     }
     w4::Args ay = ax;
     ay.sig = y;
@@ -1324,162 +1280,105 @@ static int welch2048h_run(ds_ctx* c, const float* x, int n_cx, int64_t ldx, cons
     if (n_cx > 1) CHK(launch(c, "welch2048_pxsum", wh::k_px_sum, dim3(pl.n_chunks, n_cx), 256, 0, ay));
     CHK(launch(c, "welch2048_main@4k", wh::k_y2h<false>, dim3(pl.n_chunks * n_cy), w4::NT, wh::LDS_BYTES, ay));
     WelchFinArgs f{psx, pxy, pyy, pl.n_chunks, pl.n_chunks, n_cx, n_cy, kind, mode,
-                   FinishPar{norm_scale / (double)n_frames, factor, halve_edges, amp_sqrt, wh::NBW}, tf, coh};
-    return launch_finish(c, dim3((unsigned)(((int64_t)wh::NBW * n_cy + 63) / 64)), f);
+                   FinishPar{norm_scale / (double)n_frames, factor, halve_edges, amp_sqrt, wh::NBW}, out_c, out_r};
+    return launch_finish(c, f);
 }
 
-// window 8192, one input channel: two 4096-point register transforms per frame pair
-// (kernels_welch8192.hpp)
-static int welch8192_run(ds_ctx* c, const float* x, int n_cx, int64_t ldx, const float* y, int n_cy, int64_t ldy,
-                         int64_t n_samples, int hop, int n_frames, const float* window, int detrend,
-                         int mode, int amp_sqrt, double norm_scale, double factor, int halve_edges,
-                         float2* tf, float* coh, int kind = 0) {  // kind 2: tf = cross spectra, no coh
+// window 8192: two 4096-point register transforms per frame pair (kernels_welch8192.hpp)
+static int welch8192_run(ds_ctx* c, int kind, const float* x, int n_cx, int64_t ldx, const float* y, int n_cy,
+                         int64_t ldy, int64_t n_samples, int W, int hop, int n_frames, const float* window, int detrend,
+                         int average, int mode, int amp_sqrt, double norm_scale, double factor, int halve_edges,
+                         float2* out_c, float* out_r) {
     namespace w8 = welch8k;
-    if (!x || !y || !window) return fail(c, DS_ERR_ARG, "ds_welch_tf: null argument");
-    if (n_cy <= 0 || n_samples <= 0 || hop <= 0 || hop > 8192 || n_frames <= 0 || ldx < n_samples ||
-        ldy < n_samples)
-        return fail(c, DS_ERR_ARG, "ds_welch_tf: bad shape");
-    if (mode < DS_TF_H1 || mode > DS_TF_H3) return fail(c, DS_ERR_ARG, "welch: unsupported transfer function type");
-    if (!c->w4_tables) {
-        std::vector<float2> h;
-        welch4096::host_tables(h);
-        CHK(upload_table_fwd(c, &c->w4_tables, h));
-    }
-    if (!c->deconv8k_tables) {
-        std::vector<float2> h;
-        deconv8k::host_tables(h);
-        CHK(upload_table_fwd(c, &c->deconv8k_tables, h));
-    }
+    CHK(ensure_table(c, &c->w4_tables, welch4096::host_tables));
+    CHK(ensure_table(c, &c->deconv8k_tables, deconv8k::host_tables));
+    const bool auto_only = kind == 1;
+    const int n_out = auto_only ? n_cx : n_cy;
     const int nf = frames_to_visit(n_samples, hop, n_frames);
-    if (n_cx != 1 && n_cx != n_cy) return fail(c, DS_ERR_ARG, "ds_welch_tf: one input channel, or one per output channel");
-    w8::Plan pl = w8::plan(nf, n_cy, n_cx);
-    float2 *xs, *pxy;
-    float *px, *psx, *pyy;
+    w8::Plan pl = w8::plan(nf, n_out, auto_only ? 1 : n_cx);
+    float2 *xs = nullptr, *pxy = nullptr;
+    float *px = nullptr, *psx = nullptr, *pyy;
     CHK(carve(c, &c->ws, &c->ws_bytes, [&](Carver& cv) {
-        xs = cv.take<float2>((size_t)n_cx * pl.n_pairs * w8::N);
-        px = cv.take<float>((size_t)n_cx * pl.n_pairs * w8::NB);
-        psx = cv.take<float>((size_t)pl.n_chunks * n_cx * w8::NB);
-        pxy = cv.take<float2>((size_t)pl.n_chunks * n_cy * w8::NB);
-        pyy = cv.take<float>((size_t)pl.n_chunks * n_cy * w8::NB);
+        if (!auto_only) {
+            xs = cv.take<float2>((size_t)n_cx * pl.n_pairs * w8::N);
+            px = cv.take<float>((size_t)n_cx * pl.n_pairs * w8::NB);
+            psx = cv.take<float>((size_t)pl.n_chunks * n_cx * w8::NB);
+            pxy = cv.take<float2>((size_t)pl.n_chunks * n_cy * w8::NB);
+        }
+        pyy = cv.take<float>((size_t)pl.n_chunks * n_out * w8::NB);
     }));
     const bool half = hop == 4096;
     w8::Args ax{x, n_samples, ldx, n_cx, hop, nf, pl.n_pairs, detrend, pl.n_chunks, window,
-                c->w4_tables, c->deconv8k_tables, (float4*)xs, px, pxy, pyy, psx, n_cx};
-    auto kx = half ? w8::k_x<true> : w8::k_x<false>;
-    CHK(launch(c, "welch8192_x", kx, dim3(pl.n_pairs, n_cx), w8::NTB, w8::LDS_BYTES, ax));
-    if (n_cx > 1) CHK(launch(c, "welch8192_pxsum", w8::k_px_sum, dim3(pl.n_chunks, n_cx), 256, 0, ax));
-    w8::Args ay = ax;
-    ay.sig = y;
-    ay.ld = ldy;
-    ay.n_ch = n_cy;
+                c->w4_tables, c->deconv8k_tables, (float4*)xs, px, pxy, pyy, psx, auto_only ? 0 : n_cx};
     // window in LDS + one exchange buffer per group (0.226 ms; the global-window / two-buffer
     // variant measured 0.280 ms and spilled: removed)
-    {
-        auto kyw = half ? w8::k_y<true, true> : w8::k_y<false, true>;
-        CHK(launch(c, "welch8192_main", kyw, dim3(pl.n_chunks * n_cy), w8::NTB, w8::LDS_BYTES_WINLDS, ay));
+    if (auto_only) {
+        auto ky = half ? w8::k_y<true, true, true> : w8::k_y<false, true, true>;
+        CHK(launch(c, "welch8192_main", ky, dim3(pl.n_chunks * n_cx), w8::NTB, w8::LDS_BYTES_WINLDS, ax));
+    } else {
+        auto kx = half ? w8::k_x<true> : w8::k_x<false>;
+        CHK(launch(c, "welch8192_x", kx, dim3(pl.n_pairs, n_cx), w8::NTB, w8::LDS_BYTES, ax));
+        if (n_cx > 1) CHK(launch(c, "welch8192_pxsum", w8::k_px_sum, dim3(pl.n_chunks, n_cx), 256, 0, ax));
+        w8::Args ay = ax;
+        ay.sig = y;
+        ay.ld = ldy;
+        ay.n_ch = n_cy;
+        auto ky = half ? w8::k_y<true, true> : w8::k_y<false, true>;
+        CHK(launch(c, "welch8192_main", ky, dim3(pl.n_chunks * n_cy), w8::NTB, w8::LDS_BYTES_WINLDS, ay));
     }
-    WelchFinArgs f{psx, pxy, pyy, pl.n_chunks, pl.n_chunks, n_cx, n_cy, kind, mode,
-                   FinishPar{norm_scale / (double)n_frames, factor, halve_edges, amp_sqrt, w8::NB},
-                   tf, coh};
-    int64_t total = (int64_t)w8::NB * n_cy;
-    CHK(launch_finish(c, dim3((unsigned)((total + 63) / 64)), f));
-    return DS_OK;
-}
-
-// auto spectra of every channel with an 8192-sample window (AUTO variant of welch8k::k_y)
-static int welch8192_psd_run(ds_ctx* c, const float* x, int n_cx, int64_t ldx, int64_t n_samples, int hop,
-                             int n_frames, const float* window, int detrend, int amp_sqrt, double norm_scale,
-                             double factor, int halve_edges, float* psd) {
-    namespace w8 = welch8k;
-    if (!x || !window) return fail(c, DS_ERR_ARG, "ds_welch_psd: null argument");
-    if (n_cx <= 0 || n_samples <= 0 || hop <= 0 || hop > 8192 || n_frames <= 0 || ldx < n_samples)
-        return fail(c, DS_ERR_ARG, "ds_welch_psd: bad shape");
-    if (!c->w4_tables) {
-        std::vector<float2> h;
-        welch4096::host_tables(h);
-        CHK(upload_table_fwd(c, &c->w4_tables, h));
-    }
-    if (!c->deconv8k_tables) {
-        std::vector<float2> h;
-        deconv8k::host_tables(h);
-        CHK(upload_table_fwd(c, &c->deconv8k_tables, h));
-    }
-    const int nf = frames_to_visit(n_samples, hop, n_frames);
-    w8::Plan pl = w8::plan(nf, n_cx);
-    float* pyy;
-    CHK(carve(c, &c->ws, &c->ws_bytes, [&](Carver& cv) { pyy = cv.take<float>((size_t)pl.n_chunks * n_cx * w8::NB); }));
-    w8::Args a{x, n_samples, ldx, n_cx, hop, nf, pl.n_pairs, detrend, pl.n_chunks, window,
-               c->w4_tables, c->deconv8k_tables, nullptr, nullptr, nullptr, pyy, nullptr};
-    auto ky = hop == 4096 ? w8::k_y<true, true, true> : w8::k_y<false, true, true>;
-    CHK(launch(c, "welch8192_main", ky, dim3(pl.n_chunks * n_cx), w8::NTB, w8::LDS_BYTES_WINLDS, a));
-    WelchFinArgs f{pyy, nullptr, nullptr, pl.n_chunks, pl.n_chunks, n_cx, 0, 1, 0,
-                   FinishPar{norm_scale / (double)n_frames, factor, halve_edges, amp_sqrt, w8::NB},
-                   nullptr, psd};
-    int64_t total = (int64_t)w8::NB * n_cx;
-    CHK(launch_finish(c, dim3((unsigned)((total + 63) / 64)), f));
-    return DS_OK;
+    WelchFinArgs f{auto_only ? pyy : psx, pxy, auto_only ? nullptr : pyy, pl.n_chunks, pl.n_chunks, n_cx, n_cy, kind, mode,
+                   FinishPar{norm_scale / (double)n_frames, factor, halve_edges, amp_sqrt, w8::NB}, out_c, out_r};
+    return launch_finish(c, f);
 }
 
 // window 16384: four 4096-point register transforms per frame pair, two per slot of 256 threads
 // (kernels_welch16384.hpp)
-static int welch16k_tables(ds_ctx* c) {
-    if (!c->w4_tables) {
-        std::vector<float2> h;
-        welch4096::host_tables(h);
-        CHK(upload_table_fwd(c, &c->w4_tables, h));
-    }
-    if (!c->fir16k_tables) {
-        std::vector<float2> h;
-        fir16k::host_tables(h);
-        CHK(upload_table_fwd(c, &c->fir16k_tables, h));
-    }
-    return DS_OK;
-}
-static int welch16384_run(ds_ctx* c, const float* x, int n_cx, int64_t ldx, const float* y, int n_cy, int64_t ldy,
-                          int64_t n_samples, int hop, int n_frames, const float* window, int detrend,
-                          int mode, int amp_sqrt, double norm_scale, double factor, int halve_edges,
-                          float2* tf, float* coh, int kind = 0) {  // kind 2: tf = cross spectra, no coh
+static int welch16384_run(ds_ctx* c, int kind, const float* x, int n_cx, int64_t ldx, const float* y, int n_cy,
+                          int64_t ldy, int64_t n_samples, int W, int hop, int n_frames, const float* window, int detrend,
+                          int average, int mode, int amp_sqrt, double norm_scale, double factor, int halve_edges,
+                          float2* out_c, float* out_r) {
     namespace w16 = welch16k;
-    if (!x || !y || !window) return fail(c, DS_ERR_ARG, "ds_welch_tf: null argument");
-    if (n_cx != 1 && n_cx != n_cy) return fail(c, DS_ERR_ARG, "ds_welch_tf: one input channel, or one per output channel");
-    if (n_cy <= 0 || n_samples <= 0 || hop <= 0 || hop > 16384 || n_frames <= 0 || ldx < n_samples ||
-        ldy < n_samples)
-        return fail(c, DS_ERR_ARG, "ds_welch_tf: bad shape");
-    if (mode < DS_TF_H1 || mode > DS_TF_H3) return fail(c, DS_ERR_ARG, "welch: unsupported transfer function type");
-    CHK(welch16k_tables(c));
+    CHK(ensure_table(c, &c->w4_tables, welch4096::host_tables));
+    CHK(ensure_table(c, &c->fir16k_tables, fir16k::host_tables));
+    const bool auto_only = kind == 1;
+    const int n_out = auto_only ? n_cx : n_cy;
     const int nf = frames_to_visit(n_samples, hop, n_frames);
-    w16::Plan pl = w16::plan(nf, n_cy, n_cx);
-    float2 *xs, *pxy, *tu;
-    float *pxu, *psx, *pyy, *pu;
+    w16::Plan pl = w16::plan(nf, n_out, auto_only ? 1 : n_cx);
+    float2 *xs = nullptr, *pxy = nullptr, *tu = nullptr;
+    float *pxu = nullptr, *psx = nullptr, *pyy, *pu;
     CHK(carve(c, &c->ws, &c->ws_bytes, [&](Carver& cv) {
-        xs = cv.take<float2>((size_t)n_cx * pl.n_pairs * w16::N);
-        pxu = cv.take<float>((size_t)n_cx * pl.n_pairs * w16::N);
-        psx = cv.take<float>((size_t)pl.n_chunks * n_cx * w16::NB);
-        pxy = cv.take<float2>((size_t)pl.n_chunks * n_cy * w16::NB);
-        pyy = cv.take<float>((size_t)pl.n_chunks * n_cy * w16::NB);
-        tu = cv.take<float2>((size_t)pl.n_chunks * n_cy * w16::N);
-        pu = cv.take<float>((size_t)pl.n_chunks * n_cy * w16::N);
+        if (!auto_only) {
+            xs = cv.take<float2>((size_t)n_cx * pl.n_pairs * w16::N);
+            pxu = cv.take<float>((size_t)n_cx * pl.n_pairs * w16::N);
+            psx = cv.take<float>((size_t)pl.n_chunks * n_cx * w16::NB);
+            pxy = cv.take<float2>((size_t)pl.n_chunks * n_cy * w16::NB);
+        }
+        pyy = cv.take<float>((size_t)pl.n_chunks * n_out * w16::NB);
+        if (!auto_only) tu = cv.take<float2>((size_t)pl.n_chunks * n_cy * w16::N);
+        pu = cv.take<float>((size_t)pl.n_chunks * n_out * w16::N);
     }));
     w16::Args ax{x, n_samples, ldx, n_cx, hop, nf, pl.n_pairs, detrend, pl.n_chunks, window,
-                 c->w4_tables, c->fir16k_tables, (float4*)xs, pxu, pxy, pyy, psx, n_cx, tu, pu};
-    CHK(launch(c, "welch16384_x", w16::k_x, dim3(pl.n_pairs, n_cx, 4), w16::NTB, w16::LDS_BYTES, ax));
-    CHK(launch(c, "welch16384_pxsum", w16::k_px_sum, dim3((w16::NB + 255) / 256, pl.n_chunks, n_cx), 256, 0, ax));
-    w16::Args ay = ax;
-    ay.sig = y;
-    ay.ld = ldy;
-    ay.n_ch = n_cy;
-    CHK(launch(c, "welch16384_main", w16::k_y<false>, dim3(pl.n_chunks * n_cy, 1, 4), w16::NTB, w16::LDS_BYTES, ay));
-    CHK(launch(c, "welch16384_fold", w16::k_fold<false>, dim3((w16::NB + 255) / 256, pl.n_chunks * n_cy), 256, 0, ay));
-    WelchFinArgs f{psx, pxy, pyy, pl.n_chunks, pl.n_chunks, n_cx, n_cy, kind, mode,
-                   FinishPar{norm_scale / (double)n_frames, factor, halve_edges, amp_sqrt, w16::NB},
-                   tf, coh};
-    int64_t total = (int64_t)w16::NB * n_cy;
-    CHK(launch_finish(c, dim3((unsigned)((total + 63) / 64)), f));
-    return DS_OK;
+                 c->w4_tables, c->fir16k_tables, (float4*)xs, pxu, pxy, pyy, psx, auto_only ? 1 : n_cx, tu, pu};
+    if (auto_only) {
+        CHK(launch(c, "welch16384_main", w16::k_y<true>, dim3(pl.n_chunks * n_cx, 1, 4), w16::NTB, w16::LDS_BYTES, ax));
+        CHK(launch(c, "welch16384_fold", w16::k_fold<true>, dim3((w16::NB + 255) / 256, pl.n_chunks * n_cx), 256, 0, ax));
+    } else {
+        CHK(launch(c, "welch16384_x", w16::k_x, dim3(pl.n_pairs, n_cx, 4), w16::NTB, w16::LDS_BYTES, ax));
+        CHK(launch(c, "welch16384_pxsum", w16::k_px_sum, dim3((w16::NB + 255) / 256, pl.n_chunks, n_cx), 256, 0, ax));
+        w16::Args ay = ax;
+        ay.sig = y;
+        ay.ld = ldy;
+        ay.n_ch = n_cy;
+        CHK(launch(c, "welch16384_main", w16::k_y<false>, dim3(pl.n_chunks * n_cy, 1, 4), w16::NTB, w16::LDS_BYTES, ay));
+        CHK(launch(c, "welch16384_fold", w16::k_fold<false>, dim3((w16::NB + 255) / 256, pl.n_chunks * n_cy), 256, 0, ay));
+    }
+    WelchFinArgs f{auto_only ? pyy : psx, pxy, auto_only ? nullptr : pyy, pl.n_chunks, pl.n_chunks, n_cx, n_cy, kind, mode,
+                   FinishPar{norm_scale / (double)n_frames, factor, halve_edges, amp_sqrt, w16::NB}, out_c, out_r};
+    return launch_finish(c, f);
 }
+
 // Windows of 2^15 ... 2^18 samples: decimation in frequency into R = W / 4096 class sequences (k_dif), the headline
 // kernel's loop on them (k_xc / k_yc), fold across the classes, finish (kernels_welch_long.hpp).
-// y == nullptr: auto spectra of x only (ds_welch_psd), the result in `coh`.
 static bool welch_long_applies(const ds_ctx* c, int W, int n_ch_total, int64_t n_samples, int n_frames, int hop, int average) {
     if (!c || c->cfg.welch_generic || average != DS_AVG_MEAN || !welchl::classes_of(W) || W < c->cfg.welch_long_min) return false;
     if (hop <= 0 || hop > W || !welchl::buf_fits(n_samples, n_frames, hop, W)) return false;
@@ -1492,31 +1391,18 @@ static bool welch_long_applies(const ds_ctx* c, int W, int n_ch_total, int64_t n
     if (pairs > 65535 || n_ch_total > 65535 || chunks_max * n_ch_total > 65535) return false;
     return (int64_t)n_ch_total * pairs * W * 8 <= ((int64_t)16 << 30);
 }
-static int welch_long_run(ds_ctx* c, const float* x, int n_cx, int64_t ldx, const float* y, int n_cy, int64_t ldy,
-                          int64_t n_samples, int W, int hop, int n_frames, const float* window, int detrend, int mode,
-                          int amp_sqrt, double norm_scale, double factor, int halve_edges, float2* tf, float* coh,
-                          int kind = 0) {  // kind 0: tf + coherence, 1: auto spectra of x (y null), 2: cross spectra in tf
+static int welch_long_run(ds_ctx* c, int kind, const float* x, int n_cx, int64_t ldx, const float* y, int n_cy,
+                          int64_t ldy, int64_t n_samples, int W, int hop, int n_frames, const float* window, int detrend,
+                          int average, int mode, int amp_sqrt, double norm_scale, double factor, int halve_edges,
+                          float2* out_c, float* out_r) {
     namespace wl = welchl;
     const bool auto_only = kind == 1;
-    if (!x || !window || (!auto_only && !y)) return fail(c, DS_ERR_ARG, "ds_welch: null argument");
-    if (!auto_only && n_cx != 1 && n_cx != n_cy) return fail(c, DS_ERR_ARG, "ds_welch_tf: one input channel, or one per output channel");
-    if (n_cx <= 0 || n_samples <= 0 || n_frames <= 0 || ldx < n_samples || (!auto_only && (n_cy <= 0 || ldy < n_samples)))
-        return fail(c, DS_ERR_ARG, "ds_welch: bad shape");
-    if (!auto_only && kind == 0 && (mode < DS_TF_H1 || mode > DS_TF_H3)) return fail(c, DS_ERR_ARG, "welch: unsupported transfer function type");
     const int R = wl::classes_of(W);
     int lgR = 0;
     while ((1 << lgR) < R) ++lgR;
-    if (!c->w4_tables) {
-        std::vector<float2> h;
-        welch4096::host_tables(h);
-        CHK(upload_table_fwd(c, &c->w4_tables, h));
-    }
+    CHK(ensure_table(c, &c->w4_tables, welch4096::host_tables));
     float2** slot = &c->wl_tables[lgR - 1];
-    if (!*slot) {
-        std::vector<float2> h;
-        wl::host_tables(R, h);
-        CHK(upload_table_fwd(c, slot, h));
-    }
+    CHK(ensure_table(c, slot, [R](std::vector<float2>& h) { wl::host_tables(R, h); }));
     const int nf = frames_to_visit(n_samples, hop, n_frames), nb = W / 2 + 1;
     const int n_out = auto_only ? n_cx : n_cy;  // channels that are accumulated
     wl::Plan pl = wl::plan(nf, n_out, R);
@@ -1552,8 +1438,8 @@ static int welch_long_run(ds_ctx* c, const float* x, int n_cx, int64_t ldx, cons
         CHK(launch(c, "welch_long_main", wl::k_yc<true>, dim3((unsigned)(pl.n_chunks * n_cx * R)), wl::NT, wl::LDS_BYTES, ax));
         CHK(launch(c, "welch_long_fold", wl::k_fold<true>, fold_grid, 256, 0, ax));
         WelchFinArgs f{pyy, nullptr, nullptr, pl.n_chunks, pl.n_chunks, n_cx, 0, 1, 0,
-                       FinishPar{norm_scale / (double)n_frames, factor, halve_edges, amp_sqrt, nb}, nullptr, coh};
-        return launch_finish(c, dim3((unsigned)(((int64_t)nb * n_cx + 63) / 64)), f);
+                       FinishPar{norm_scale / (double)n_frames, factor, halve_edges, amp_sqrt, nb}, nullptr, out_r};
+        return launch_finish(c, f);
     }
     CHK(launch(c, "welch_long_x", wl::k_xc, dim3((unsigned)(pl.n_pairs * R * n_cx)), wl::NT, wl::LDS_BYTES, ax));
     CHK(launch(c, "welch_long_pxsum", wl::k_px_sum, dim3((nb + 255) / 256, pl.n_chunks, n_cx), 256, 0, ax));
@@ -1569,115 +1455,48 @@ static int welch_long_run(ds_ctx* c, const float* x, int n_cx, int64_t ldx, cons
         CHK(launch(c, "welch_long_main", wl::k_yc<false>, dim3((unsigned)(pl.n_chunks * n_cy * R)), wl::NT, wl::LDS_BYTES, ay));
     CHK(launch(c, "welch_long_fold", wl::k_fold<false>, fold_grid, 256, 0, ay));
     WelchFinArgs f{psx, pxy, pyy, pl.n_chunks, pl.n_chunks, n_cx, n_cy, kind, mode,
-                   FinishPar{norm_scale / (double)n_frames, factor, halve_edges, amp_sqrt, nb}, tf, coh};
-    return launch_finish(c, dim3((unsigned)(((int64_t)nb * n_cy + 63) / 64)), f);
-}
-
-static int welch16384_psd_run(ds_ctx* c, const float* x, int n_cx, int64_t ldx, int64_t n_samples, int hop,
-                              int n_frames, const float* window, int detrend, int amp_sqrt, double norm_scale,
-                              double factor, int halve_edges, float* psd) {
-    namespace w16 = welch16k;
-    if (!x || !window) return fail(c, DS_ERR_ARG, "ds_welch_psd: null argument");
-    if (n_cx <= 0 || n_samples <= 0 || hop <= 0 || hop > 16384 || n_frames <= 0 || ldx < n_samples)
-        return fail(c, DS_ERR_ARG, "ds_welch_psd: bad shape");
-    CHK(welch16k_tables(c));
-    const int nf = frames_to_visit(n_samples, hop, n_frames);
-    w16::Plan pl = w16::plan(nf, n_cx);
-    float *pyy, *pu;
-    CHK(carve(c, &c->ws, &c->ws_bytes, [&](Carver& cv) {
-        pyy = cv.take<float>((size_t)pl.n_chunks * n_cx * w16::NB);
-        pu = cv.take<float>((size_t)pl.n_chunks * n_cx * w16::N);
-    }));
-    w16::Args a{x, n_samples, ldx, n_cx, hop, nf, pl.n_pairs, detrend, pl.n_chunks, window,
-                c->w4_tables, c->fir16k_tables, nullptr, nullptr, nullptr, pyy, nullptr, 1, nullptr, pu};
-    CHK(launch(c, "welch16384_main", w16::k_y<true>, dim3(pl.n_chunks * n_cx, 1, 4), w16::NTB, w16::LDS_BYTES, a));
-    CHK(launch(c, "welch16384_fold", w16::k_fold<true>, dim3((w16::NB + 255) / 256, pl.n_chunks * n_cx), 256, 0, a));
-    WelchFinArgs f{pyy, nullptr, nullptr, pl.n_chunks, pl.n_chunks, n_cx, 0, 1, 0,
-                   FinishPar{norm_scale / (double)n_frames, factor, halve_edges, amp_sqrt, w16::NB},
-                   nullptr, psd};
-    int64_t total = (int64_t)w16::NB * n_cx;
-    CHK(launch_finish(c, dim3((unsigned)((total + 63) / 64)), f));
-    return DS_OK;
-}
-
-// auto spectra of every channel with a 4096-sample window on the headline kernel (AUTO variant)
-static int welch4096_psd_run(ds_ctx* c, const float* x, int n_cx, int64_t ldx, int64_t n_samples, int hop,
-                             int n_frames, const float* window, int detrend, int amp_sqrt, double norm_scale,
-                             double factor, int halve_edges, float* psd) {
-    namespace w4 = welch4096;
-    if (!x || !window) return fail(c, DS_ERR_ARG, "ds_welch_psd: null argument");
-    if (n_cx <= 0 || n_samples <= 0 || hop <= 0 || hop > 4096 || n_frames <= 0 || ldx < n_samples)
-        return fail(c, DS_ERR_ARG, "ds_welch_psd: bad shape");
-    if (!c->w4_tables) {
-        std::vector<float2> h;
-        w4::host_tables(h);
-        CHK(upload_table_fwd(c, &c->w4_tables, h));
-    }
-    const int nf = frames_to_visit(n_samples, hop, n_frames);
-    const bool three = hop == 2048 && !c->cfg.w4_two_per_cu && w4::fits3(n_samples, nf);
-    w4::Plan pl = three ? w4::plan3(nf, n_cx, c->cfg.welch_chunks) : w4::plan(nf, n_cx, c->cfg.welch_chunks);
-    float* pyy;
-    CHK(carve(c, &c->ws, &c->ws_bytes, [&](Carver& cv) { pyy = cv.take<float>((size_t)pl.n_chunks * n_cx * w4::NB); }));
-    w4::Args a{x, n_samples, ldx, n_cx, hop, nf, pl.n_pairs, detrend, pl.n_chunks, pl.ppc, window,
-               c->w4_tables, nullptr, nullptr, nullptr, pyy, nullptr};
-    if (three) {
-        w4::place_remainder(a, n_cx);
-        CHK(launch(c, "welch4096_main@3", w4::k_y3<true>, dim3(pl.n_chunks * n_cx), w4::NT, w4::LDS3_BYTES, a));
-    } else {
-        auto ky = hop == 2048 ? w4::k_y<true, true> : w4::k_y<false, true>;
-        CHK(launch(c, "welch4096_main@2", ky, dim3(pl.n_chunks * n_cx), w4::NT, w4::LDS_BYTES_2, a));
-    }
-    WelchFinArgs f{pyy, nullptr, nullptr, pl.n_chunks, pl.n_chunks, n_cx, 0, 1, 0,
-                   FinishPar{norm_scale / (double)n_frames, factor, halve_edges, amp_sqrt, w4::NB},
-                   nullptr, psd};
-    int64_t total = (int64_t)w4::NB * n_cx;
-    CHK(launch_finish(c, dim3((unsigned)((total + 63) / 64)), f));
-    return DS_OK;
+                   FinishPar{norm_scale / (double)n_frames, factor, halve_edges, amp_sqrt, nb}, out_c, out_r};
+    return launch_finish(c, f);
 }
 
 // twiddle tables of the wave-level transforms (stft1k::host_tables<N>), cached per context
 template <int NN>
 static int wave_tables(ds_ctx* c, const float2** out) {
     float2** tab = NN == 1024 ? &c->stft1k_tables : &c->stft_wave_tables[NN == 512 ? 0 : (NN == 256 ? 1 : 2)];
-    if (!*tab) {
-        std::vector<float2> h;
-        stft1k::host_tables<NN>(h);
-        CHK(upload_table_fwd(c, tab, h));
-    }
+    CHK(ensure_table(c, tab, stft1k::host_tables<NN>));
     *out = *tab;
     return DS_OK;
 }
 
-// windows of 256 / 512 / 1024 samples (1024 = the reference's default), one input channel:
-// wave-level register transforms (kernels_welch1024.hpp)
+// windows of 256 / 512 / 1024 / 2048 samples (1024 = the reference's default): wave-level register transforms
+// (kernels_welch1024.hpp).  W < NN (windows of 128 / 64 / 32 samples on the 256-point kernels): the frames are
+// transformed zero-padded to NN points and every (NN / W)-th bin is kept (removing a frame's mean still only clears
+// bin 0 of the kept bins)
 template <int NN>
-static int welch_wave_run(ds_ctx* c, const float* x, int n_cx, int64_t ldx, const float* y, int n_cy, int64_t ldy,
-                          int64_t n_samples, int hop, int n_frames, const float* window, int detrend,
-                          int mode, int amp_sqrt, double norm_scale, double factor, int halve_edges,
-                          float2* tf, float* coh, int kind = 0, int decim = 1) {  // kind 2: tf = cross spectra, no coh
-    // decim = D > 1: windows of NN / D samples (`window` holds that many values): the frames are transformed zero-padded
-    // to NN points and every D-th bin is kept (removing a frame's mean still only clears bin 0 of the kept bins)
+static int welch_wave_run(ds_ctx* c, int kind, const float* x, int n_cx, int64_t ldx, const float* y, int n_cy,
+                          int64_t ldy, int64_t n_samples, int W, int hop, int n_frames, const float* window, int detrend,
+                          int average, int mode, int amp_sqrt, double norm_scale, double factor, int halve_edges,
+                          float2* out_c, float* out_r) {
     namespace w1 = welch1k;
-    using W = w1::WG<NN>;
-    if (!x || !y || !window) return fail(c, DS_ERR_ARG, "ds_welch_tf: null argument");
-    if (n_cy <= 0 || n_samples <= 0 || hop <= 0 || hop > NN || n_frames <= 0 || ldx < n_samples ||
-        ldy < n_samples)
-        return fail(c, DS_ERR_ARG, "ds_welch_tf: bad shape");
-    if (mode < DS_TF_H1 || mode > DS_TF_H3) return fail(c, DS_ERR_ARG, "welch: unsupported transfer function type");
+    using G = w1::WG<NN>;
     const float2* tab;
     CHK(wave_tables<NN>(c, &tab));
+    const bool auto_only = kind == 1;
+    const int n_out = auto_only ? n_cx : n_cy;
+    const int decim = NN / W;
     const int nf = frames_to_visit(n_samples, hop, n_frames);
-    if (n_cx != 1 && n_cx != n_cy) return fail(c, DS_ERR_ARG, "ds_welch_tf: one input channel, or one per output channel");
-    w1::Plan pl = w1::plan<NN>(nf, n_cy, n_cx, c->cfg.welch1k_chunks);
-    float *wz, *px, *psx, *pyy;
-    float2 *xs, *pxy;
+    w1::Plan pl = w1::plan<NN>(nf, n_out, auto_only ? 1 : n_cx, c->cfg.welch1k_chunks);
+    float *wz, *px = nullptr, *psx = nullptr, *pyy;
+    float2 *xs = nullptr, *pxy = nullptr;
     CHK(carve(c, &c->ws, &c->ws_bytes, [&](Carver& cv) {
         wz = decim > 1 ? cv.take<float>(NN) : nullptr;
-        xs = cv.take<float2>((size_t)n_cx * pl.n_pairs * NN);
-        px = cv.take<float>((size_t)n_cx * pl.n_pairs * W::NB);
-        psx = cv.take<float>((size_t)pl.n_chunks * n_cx * W::NB);
-        pxy = cv.take<float2>((size_t)pl.n_chunks * n_cy * W::NB);
-        pyy = cv.take<float>((size_t)pl.n_chunks * n_cy * W::NB);
+        if (!auto_only) {
+            xs = cv.take<float2>((size_t)n_cx * pl.n_pairs * NN);
+            px = cv.take<float>((size_t)n_cx * pl.n_pairs * G::NB);
+            psx = cv.take<float>((size_t)pl.n_chunks * n_cx * G::NB);
+            pxy = cv.take<float2>((size_t)pl.n_chunks * n_cy * G::NB);
+        }
+        pyy = cv.take<float>((size_t)pl.n_chunks * n_out * G::NB);
     }));
     if (decim > 1) {  // the window, zero-padded to the transform length
         HIPCHK(c, hipMemsetAsync(wz, 0, sizeof(float) * NN, c->stream));
@@ -1686,62 +1505,84 @@ static int welch_wave_run(ds_ctx* c, const float* x, int n_cx, int64_t ldx, cons
     }
     const bool half = hop == NN / 2;
     w1::Args ax{x, n_samples, ldx, n_cx, hop, nf, pl.n_pairs, detrend, pl.n_chunks, pl.ppc, window,
-                tab, (float4*)xs, px, pxy, pyy, psx, n_cx};
-    auto kx = half ? w1::k_x<NN, true> : w1::k_x<NN, false>;
-    auto ky = half ? w1::k_y<NN, true> : w1::k_y<NN, false>;
-    CHK(launch(c, "welch1024_x", kx, dim3((pl.n_pairs + W::TPB - 1) / W::TPB, n_cx), w1::NTB, W::LDS_BYTES, ax));
-    if (n_cx > 1) CHK(launch(c, "welch1024_pxsum", w1::k_px_sum<NN>, dim3(pl.n_chunks, n_cx), 256, 0, ax));
-    w1::Args ay = ax;
-    ay.sig = y;
-    ay.ld = ldy;
-    ay.n_ch = n_cy;
-    const int n_grp = (n_cy + W::TPB - 1) / W::TPB;
-    CHK(launch(c, "welch1024_main", ky, dim3(pl.n_chunks * n_grp), w1::NTB, W::LDS_BYTES, ay));
-    const int nb_out = NN / decim / 2 + 1;
-    WelchFinArgs f{psx, pxy, pyy, pl.n_chunks, pl.n_chunks, n_cx, n_cy, kind, mode,
-                   FinishPar{norm_scale / (double)n_frames, factor, halve_edges, amp_sqrt, nb_out},
-                   tf, coh, W::NB, decim};
-    int64_t total = (int64_t)nb_out * n_cy;
-    CHK(launch_finish(c, dim3((unsigned)((total + 63) / 64)), f));
+                tab, (float4*)xs, px, pxy, pyy, psx, auto_only ? 1 : n_cx};
+    const int n_grp = (n_out + G::TPB - 1) / G::TPB;
+    if (auto_only) {
+        auto ky = half ? w1::k_y<NN, true, true> : w1::k_y<NN, false, true>;
+        CHK(launch(c, "welch1024_main", ky, dim3(pl.n_chunks * n_grp), w1::NTB, G::LDS_BYTES, ax));
+    } else {
+        auto kx = half ? w1::k_x<NN, true> : w1::k_x<NN, false>;
+        auto ky = half ? w1::k_y<NN, true> : w1::k_y<NN, false>;
+        CHK(launch(c, "welch1024_x", kx, dim3((pl.n_pairs + G::TPB - 1) / G::TPB, n_cx), w1::NTB, G::LDS_BYTES, ax));
+        if (n_cx > 1) CHK(launch(c, "welch1024_pxsum", w1::k_px_sum<NN>, dim3(pl.n_chunks, n_cx), 256, 0, ax));
+        w1::Args ay = ax;
+        ay.sig = y;
+        ay.ld = ldy;
+        ay.n_ch = n_cy;
+        CHK(launch(c, "welch1024_main", ky, dim3(pl.n_chunks * n_grp), w1::NTB, G::LDS_BYTES, ay));
+    }
+    WelchFinArgs f{auto_only ? pyy : psx, pxy, auto_only ? nullptr : pyy, pl.n_chunks, pl.n_chunks, n_cx, n_cy, kind, mode,
+                   FinishPar{norm_scale / (double)n_frames, factor, halve_edges, amp_sqrt, NN / decim / 2 + 1},
+                   out_c, out_r, G::NB, decim};
+    return launch_finish(c, f);
+}
+
+// What welch_common checks of its arguments, once per call: `who` is the entry point named in the message.
+static int welch_check(ds_ctx* c, const char* who, int kind, const float* x, int n_cx, int64_t ldx, const float* y,
+                       int n_cy, int64_t ldy, int64_t n_samples, int W, int hop, int n_frames, const float* window,
+                       int average, int mode) {
+    const std::string w(who);
+    if (!c || !x || !window) return fail(c, DS_ERR_ARG, w + ": null argument");
+    if (average != DS_AVG_MEAN && average != DS_AVG_MEDIAN)
+        return fail(c, DS_ERR_ARG, w + ": average must be mean (0) or median (1)");
+    if (kind != 1 && !y) return fail(c, DS_ERR_ARG, w + ": null output-signal pointer");
+    if (n_cx <= 0 || n_samples <= 0 || hop <= 0 || hop > W || n_frames <= 0 || ldx < n_samples)
+        return fail(c, DS_ERR_ARG, w + ": bad shape");
+    if (kind != 1 && (n_cy <= 0 || ldy < n_samples || !(n_cx == 1 || n_cx == n_cy)))
+        return fail(c, DS_ERR_ARG, w + ": input must have 1 channel or as many as the output");
+    if (kind == 0 && (mode < DS_TF_H1 || mode > DS_TF_H3))
+        return fail(c, DS_ERR_ARG, w + ": unsupported transfer function type");
     return DS_OK;
 }
 
-// auto spectra of every channel (Signal.get_spectrum's default parameters: window 1024)
-template <int NN>
-static int welch_wave_psd_run(ds_ctx* c, const float* x, int n_cx, int64_t ldx, int64_t n_samples, int hop,
-                              int n_frames, const float* window, int detrend, int amp_sqrt, double norm_scale,
-                              double factor, int halve_edges, float* psd, int decim = 1) {
-    namespace w1 = welch1k;
-    using W = w1::WG<NN>;
-    if (!x || !window) return fail(c, DS_ERR_ARG, "ds_welch_psd: null argument");
-    if (n_cx <= 0 || n_samples <= 0 || hop <= 0 || hop > NN || n_frames <= 0 || ldx < n_samples)
-        return fail(c, DS_ERR_ARG, "ds_welch_psd: bad shape");
-    const float2* tab;
-    CHK(wave_tables<NN>(c, &tab));
-    const int nf = frames_to_visit(n_samples, hop, n_frames);
-    w1::Plan pl = w1::plan<NN>(nf, n_cx, 1, c->cfg.welch1k_chunks);
-    float *wz, *pyy;
-    CHK(carve(c, &c->ws, &c->ws_bytes, [&](Carver& cv) {
-        wz = decim > 1 ? cv.take<float>(NN) : nullptr;
-        pyy = cv.take<float>((size_t)pl.n_chunks * n_cx * W::NB);
-    }));
-    if (decim > 1) {  // the window, zero-padded to the transform length (see welch_wave_run)
-        HIPCHK(c, hipMemsetAsync(wz, 0, sizeof(float) * NN, c->stream));
-        HIPCHK(c, hipMemcpyAsync(wz, window, sizeof(float) * (NN / decim), hipMemcpyDeviceToDevice, c->stream));
-        window = wz;
+using WelchRunner = int (*)(ds_ctx*, int, const float*, int, int64_t, const float*, int, int64_t, int64_t, int, int, int,
+                            const float*, int, int, int, int, double, double, int, float2*, float*);
+
+// The kernel family of a checked call: the register kernels of its window where they apply, welch_common otherwise.
+static WelchRunner welch_route(const ds_ctx* c, int kind, int W, int hop, int average, int n_cx, int64_t ldx, int n_cy,
+                               int64_t ldy, int64_t n_samples, int n_frames) {
+    if (average != DS_AVG_MEAN) return welch_common;
+    const bool generic = c->cfg.welch_generic;
+    // (DSPTOOLBOX_AMD_WELCH_GENERIC keeps transfer functions with 4096-sample windows on the register kernels)
+    if (W == 4096 && !c->cfg.no_welch4096 && (kind == 0 || !generic)) return welch4096_run;
+    if (welch_long_applies(c, W, kind == 1 ? n_cx : n_cx + n_cy, n_samples, n_frames, hop, average)) return welch_long_run;
+    if (generic) return welch_common;
+    if (W == 16384 && welch16k::buf_fits(n_samples, n_frames, hop)) return welch16384_run;
+    if (W == 8192 && welch8k::buf_fits(n_samples, n_frames, hop)) return welch8192_run;
+    if (welch2048h_applies(c, W, hop, average, n_samples, n_frames)) return welch2048h_run;
+    // the wave kernels: the accumulated channels (y; auto spectra: x) must fit their buffer descriptors
+    if (W > 2048 || W < 32 || !welch1k::buf_fits(n_samples, kind == 1 ? n_cx : n_cy, kind == 1 ? ldx : ldy))
+        return welch_common;
+    switch (W) {
+        case 2048: return welch_wave_run<2048>;
+        case 1024: return welch_wave_run<1024>;
+        case 512: return welch_wave_run<512>;
+        case 256: case 128: case 64: case 32: return welch_wave_run<256>;
+        default: return welch_common;
     }
-    w1::Args a{x, n_samples, ldx, n_cx, hop, nf, pl.n_pairs, detrend, pl.n_chunks, pl.ppc, window,
-               tab, nullptr, nullptr, nullptr, pyy, nullptr, 1};
-    auto ky = hop == NN / 2 ? w1::k_y<NN, true, true> : w1::k_y<NN, false, true>;
-    const int n_grp = (n_cx + W::TPB - 1) / W::TPB;
-    CHK(launch(c, "welch1024_main", ky, dim3(pl.n_chunks * n_grp), w1::NTB, W::LDS_BYTES, a));
-    const int nb_out = NN / decim / 2 + 1;
-    WelchFinArgs f{pyy, nullptr, nullptr, pl.n_chunks, pl.n_chunks, n_cx, 0, 1, 0,
-                   FinishPar{norm_scale / (double)n_frames, factor, halve_edges, amp_sqrt, nb_out},
-                   nullptr, psd, W::NB, decim};
-    int64_t total = (int64_t)nb_out * n_cx;
-    CHK(launch_finish(c, dim3((unsigned)((total + 63) / 64)), f));
-    return DS_OK;
+}
+
+// The three device entry points: check, choose the route, run it.
+static int welch_dev(ds_ctx* c, const char* who, int kind, const float* x, int n_cx, int64_t ldx, const float* y,
+                     int n_cy, int64_t ldy, int64_t n_samples, int W, int hop, int n_frames, const float* window,
+                     int detrend, int average, int mode, int amp_sqrt, double norm_scale, double factor,
+                     int halve_edges, float2* out_c, float* out_r) {
+    CHK(welch_check(c, who, kind, x, n_cx, ldx, y, n_cy, ldy, n_samples, W, hop, n_frames, window, average, mode));
+    const WelchRunner run = welch_route(c, kind, W, hop, average, n_cx, ldx, n_cy, ldy, n_samples, n_frames);
+    // (cross spectra: the finish reads no mode; the register kernels have always been handed H1, welch_common 0)
+    if (kind == 2 && run != welch_common) mode = DS_TF_H1;
+    return run(c, kind, x, n_cx, ldx, y, n_cy, ldy, n_samples, W, hop, n_frames, window, detrend, average, mode, amp_sqrt,
+               norm_scale, factor, halve_edges, out_c, out_r);
 }
 
 extern "C" int ds_welch_tf_dev(ds_ctx* c, const float* x, int n_cx, int64_t ldx, const float* y,
@@ -1750,40 +1591,26 @@ extern "C" int ds_welch_tf_dev(ds_ctx* c, const float* x, int n_cx, int64_t ldx,
                                double norm_scale, double factor, int halve_edges, ds_c32* tf,
                                float* coh) {
     if (!tf || !coh) return fail(c, DS_ERR_ARG, "ds_welch_tf: null output");
-    // one input channel, or one per output channel (three-per-CU kernels at 50 % overlap, two-per-CU otherwise)
-    if (c && W == 4096 && average == DS_AVG_MEAN && !c->cfg.no_welch4096 && (n_cx == 1 || n_cx == n_cy))
-        return welch4096_run(c, x, n_cx, ldx, y, n_cy, ldy, n_samples, hop, n_frames, window, detrend, mode,
-                             amp_sqrt, norm_scale, factor, halve_edges, (float2*)tf, coh);
-    const bool no1k = c && c->cfg.welch_generic;
-    if ((n_cx == 1 || n_cx == n_cy) && welch_long_applies(c, W, n_cx + n_cy, n_samples, n_frames, hop, average))
-        return welch_long_run(c, x, n_cx, ldx, y, n_cy, ldy, n_samples, W, hop, n_frames, window, detrend, mode, amp_sqrt,
-                              norm_scale, factor, halve_edges, (float2*)tf, coh);
-    if (c && W == 16384 && (n_cx == 1 || n_cx == n_cy) && average == DS_AVG_MEAN && !no1k &&
-        welch16k::buf_fits(n_samples, n_frames, hop))
-        return welch16384_run(c, x, n_cx, ldx, y, n_cy, ldy, n_samples, hop, n_frames, window, detrend, mode,
-                              amp_sqrt, norm_scale, factor, halve_edges, (float2*)tf, coh);
-    if (c && W == 8192 && (n_cx == 1 || n_cx == n_cy) && average == DS_AVG_MEAN && !no1k &&
-        welch8k::buf_fits(n_samples, n_frames, hop))
-        return welch8192_run(c, x, n_cx, ldx, y, n_cy, ldy, n_samples, hop, n_frames, window, detrend, mode,
-                             amp_sqrt, norm_scale, factor, halve_edges, (float2*)tf, coh);
-    if ((n_cx == 1 || n_cx == n_cy) && welch2048h_applies(c, W, hop, average, n_samples, n_frames))
-        return welch2048h_run(c, x, n_cx, ldx, y, n_cy, ldy, n_samples, n_frames, window, detrend, mode, amp_sqrt, norm_scale,
-                              factor, halve_edges, (float2*)tf, coh);
-    // 256 ... 2048-sample windows (1024: the reference's default): one input channel or one per output channel
-    if (c && (W == 2048 || W == 1024 || W == 512 || W == 256) && (n_cx == 1 || n_cx == n_cy) && average == DS_AVG_MEAN &&
-        !no1k && welch1k::buf_fits(n_samples, n_cy, ldy)) {
-        auto run = W == 2048 ? welch_wave_run<2048>
-                             : (W == 1024 ? welch_wave_run<1024> : (W == 512 ? welch_wave_run<512> : welch_wave_run<256>));
-        return run(c, x, n_cx, ldx, y, n_cy, ldy, n_samples, hop, n_frames, window, detrend, mode, amp_sqrt,
-                   norm_scale, factor, halve_edges, (float2*)tf, coh, 0, 1);
-    }
-    // 128 / 64 / 32-sample windows: every 2nd / 4th / 8th bin of the 256-point kernels on zero-padded frames
-    if (c && (W == 128 || W == 64 || W == 32) && (n_cx == 1 || n_cx == n_cy) && average == DS_AVG_MEAN && !no1k &&
-        welch1k::buf_fits(n_samples, n_cy, ldy))
-        return welch_wave_run<256>(c, x, n_cx, ldx, y, n_cy, ldy, n_samples, hop, n_frames, window, detrend, mode, amp_sqrt,
-                                   norm_scale, factor, halve_edges, (float2*)tf, coh, 0, 256 / W);
-    return welch_common(c, 0, x, n_cx, ldx, y, n_cy, ldy, n_samples, W, hop, n_frames, window, detrend,
-                        average, mode, amp_sqrt, norm_scale, factor, halve_edges, (float2*)tf, coh);
+    return welch_dev(c, "ds_welch_tf", 0, x, n_cx, ldx, y, n_cy, ldy, n_samples, W, hop, n_frames, window, detrend, average,
+                     mode, amp_sqrt, norm_scale, factor, halve_edges, (float2*)tf, coh);
+}
+extern "C" int ds_welch_psd_dev(ds_ctx* c, const float* x, int n_cx, int64_t ldx, int64_t n_samples,
+                                int W, int hop, int n_frames, const float* window, int detrend,
+                                int average, int amp_sqrt, double norm_scale, double factor,
+                                int halve_edges, float* psd) {
+    if (!psd) return fail(c, DS_ERR_ARG, "ds_welch_psd: null output");
+    return welch_dev(c, "ds_welch_psd", 1, x, n_cx, ldx, nullptr, 0, 0, n_samples, W, hop, n_frames, window, detrend,
+                     average, 0, amp_sqrt, norm_scale, factor, halve_edges, nullptr, psd);
+}
+// csd_i = mean_f conj(X_i) Y_i is the cross sum a transfer function with one input channel per
+// output channel accumulates: the same kernels with the finish of kind 2
+static int welch_csd_dev(ds_ctx* c, const float* x, const float* y, int n_ch, int64_t ld,
+                         int64_t n_samples, int W, int hop, int n_frames, const float* window,
+                         int detrend, int average, int amp_sqrt, double norm_scale, double factor,
+                         int halve_edges, ds_c32* csd) {
+    if (!csd) return fail(c, DS_ERR_ARG, "ds_welch_csd: null output");
+    return welch_dev(c, "ds_welch_csd", 2, x, n_ch, ld, y, n_ch, ld, n_samples, W, hop, n_frames, window, detrend, average,
+                     0, amp_sqrt, norm_scale, factor, halve_edges, (float2*)csd, nullptr);
 }
 // float64 frame spectra of a device-resident (samples, channels) float64 array: W <= 16384 one workgroup per
 // (frame, channel); 2^15 ... 2^18 one per (frame, class, channel) + the split (class spectra in the workspace)
@@ -2000,79 +1827,6 @@ extern "C" int ds_csm_x64(ds_ctx* c, const double* x, int n_ch, int64_t n_sample
     HIPCHK(c, hipMemcpyAsync(csm, dcsm, bout * 16, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return DS_OK;
-}
-
-extern "C" int ds_welch_psd_dev(ds_ctx* c, const float* x, int n_cx, int64_t ldx, int64_t n_samples,
-                                int W, int hop, int n_frames, const float* window, int detrend,
-                                int average, int amp_sqrt, double norm_scale, double factor,
-                                int halve_edges, float* psd) {
-    if (!psd) return fail(c, DS_ERR_ARG, "ds_welch_psd: null output");
-    const bool no1k = c && c->cfg.welch_generic;
-    if (welch_long_applies(c, W, n_cx, n_samples, n_frames, hop, average))
-        return welch_long_run(c, x, n_cx, ldx, nullptr, 0, 0, n_samples, W, hop, n_frames, window, detrend, 0, amp_sqrt,
-                              norm_scale, factor, halve_edges, nullptr, psd, 1);
-    if (c && W == 16384 && average == DS_AVG_MEAN && !no1k && welch16k::buf_fits(n_samples, n_frames, hop))
-        return welch16384_psd_run(c, x, n_cx, ldx, n_samples, hop, n_frames, window, detrend, amp_sqrt,
-                                  norm_scale, factor, halve_edges, psd);
-    if (c && W == 8192 && average == DS_AVG_MEAN && !no1k && welch8k::buf_fits(n_samples, n_frames, hop))
-        return welch8192_psd_run(c, x, n_cx, ldx, n_samples, hop, n_frames, window, detrend, amp_sqrt,
-                                 norm_scale, factor, halve_edges, psd);
-    if (c && W == 4096 && average == DS_AVG_MEAN && !c->cfg.no_welch4096 && !no1k)
-        return welch4096_psd_run(c, x, n_cx, ldx, n_samples, hop, n_frames, window, detrend, amp_sqrt,
-                                 norm_scale, factor, halve_edges, psd);
-    if (welch2048h_applies(c, W, hop, average, n_samples, n_frames))
-        return welch2048h_run(c, x, n_cx, ldx, nullptr, 0, 0, n_samples, n_frames, window, detrend, 0, amp_sqrt, norm_scale,
-                              factor, halve_edges, nullptr, psd, 1);
-    if (c && (W == 2048 || W == 1024 || W == 512 || W == 256) && average == DS_AVG_MEAN && !no1k &&
-        welch1k::buf_fits(n_samples, n_cx, ldx)) {
-        auto run = W == 2048 ? welch_wave_psd_run<2048>
-                             : (W == 1024 ? welch_wave_psd_run<1024>
-                                          : (W == 512 ? welch_wave_psd_run<512> : welch_wave_psd_run<256>));
-        return run(c, x, n_cx, ldx, n_samples, hop, n_frames, window, detrend, amp_sqrt, norm_scale, factor,
-                   halve_edges, psd, 1);
-    }
-    if (c && (W == 128 || W == 64 || W == 32) && average == DS_AVG_MEAN && !no1k && welch1k::buf_fits(n_samples, n_cx, ldx))
-        return welch_wave_psd_run<256>(c, x, n_cx, ldx, n_samples, hop, n_frames, window, detrend, amp_sqrt, norm_scale,
-                                       factor, halve_edges, psd, 256 / W);
-    return welch_common(c, 1, x, n_cx, ldx, nullptr, 0, 0, n_samples, W, hop, n_frames, window, detrend,
-                        average, 0, amp_sqrt, norm_scale, factor, halve_edges, nullptr, psd);
-}
-static int welch_csd_dev(ds_ctx* c, const float* x, const float* y, int n_ch, int64_t ld,
-                         int64_t n_samples, int W, int hop, int n_frames, const float* window,
-                         int detrend, int average, int amp_sqrt, double norm_scale, double factor,
-                         int halve_edges, ds_c32* csd) {
-    // csd_i = mean_f conj(X_i) Y_i is the cross sum a transfer function with one input channel per
-    // output channel accumulates: the register kernels with the finish of kind 2
-    const bool generic = c && c->cfg.welch_generic;
-    if (c && x && y && window && csd && average == DS_AVG_MEAN && !generic && n_ch > 0 && n_samples > 0 &&
-        n_frames > 0 && hop > 0 && hop <= W && ld >= n_samples) {
-        if (W == 4096 && !c->cfg.no_welch4096)
-            return welch4096_run(c, x, n_ch, ld, y, n_ch, ld, n_samples, hop, n_frames, window, detrend, DS_TF_H1,
-                                 amp_sqrt, norm_scale, factor, halve_edges, (float2*)csd, nullptr, 2);
-        if (welch_long_applies(c, W, 2 * n_ch, n_samples, n_frames, hop, average))
-            return welch_long_run(c, x, n_ch, ld, y, n_ch, ld, n_samples, W, hop, n_frames, window, detrend, DS_TF_H1, amp_sqrt,
-                                  norm_scale, factor, halve_edges, (float2*)csd, nullptr, 2);
-        if (W == 16384 && welch16k::buf_fits(n_samples, n_frames, hop))
-            return welch16384_run(c, x, n_ch, ld, y, n_ch, ld, n_samples, hop, n_frames, window, detrend, DS_TF_H1,
-                                  amp_sqrt, norm_scale, factor, halve_edges, (float2*)csd, nullptr, 2);
-        if (W == 8192 && welch8k::buf_fits(n_samples, n_frames, hop))
-            return welch8192_run(c, x, n_ch, ld, y, n_ch, ld, n_samples, hop, n_frames, window, detrend, DS_TF_H1,
-                                 amp_sqrt, norm_scale, factor, halve_edges, (float2*)csd, nullptr, 2);
-        if (welch2048h_applies(c, W, hop, average, n_samples, n_frames))
-            return welch2048h_run(c, x, n_ch, ld, y, n_ch, ld, n_samples, n_frames, window, detrend, DS_TF_H1, amp_sqrt,
-                                  norm_scale, factor, halve_edges, (float2*)csd, nullptr, 2);
-        if ((W == 2048 || W == 1024 || W == 512 || W == 256) && welch1k::buf_fits(n_samples, n_ch, ld)) {
-            auto run = W == 2048 ? welch_wave_run<2048>
-                                 : (W == 1024 ? welch_wave_run<1024> : (W == 512 ? welch_wave_run<512> : welch_wave_run<256>));
-            return run(c, x, n_ch, ld, y, n_ch, ld, n_samples, hop, n_frames, window, detrend, DS_TF_H1, amp_sqrt,
-                       norm_scale, factor, halve_edges, (float2*)csd, nullptr, 2, 1);
-        }
-        if ((W == 128 || W == 64 || W == 32) && welch1k::buf_fits(n_samples, n_ch, ld))
-            return welch_wave_run<256>(c, x, n_ch, ld, y, n_ch, ld, n_samples, hop, n_frames, window, detrend, DS_TF_H1,
-                                       amp_sqrt, norm_scale, factor, halve_edges, (float2*)csd, nullptr, 2, 256 / W);
-    }
-    return welch_common(c, 2, x, n_ch, ld, y, n_ch, ld, n_samples, W, hop, n_frames, window, detrend,
-                        average, 0, amp_sqrt, norm_scale, factor, halve_edges, (float2*)csd, nullptr);
 }
 
 // ---- CSM -------------------------------------------------------------------
@@ -2586,9 +2340,7 @@ static int welch_big(ds_ctx* c, int kind, const float* x, int n_cx, int64_t ldx,
     }
     WelchFinArgs f{pxx, pxy, pyy, 1, 1, n_cx, n_cy, kind, mode,
                    FinishPar{norm_scale / count, factor, halve_edges, amp_sqrt, nb}, out_c, out_r};
-    int64_t total = (int64_t)nb * (kind == 1 ? n_cx : n_cy);
-    CHK(launch_finish(c, dim3((unsigned)((total + 63) / 64)), f));
-    return DS_OK;
+    return launch_finish(c, f);
 }
 
 // ---- arbitrary lengths: Bluestein on top of the four-step FFT ------------------------
@@ -2760,16 +2512,8 @@ extern "C" int ds_deconv_dev(ds_ctx* c, const float* y, int n_items, int n_ch, i
     if (n_fft == deconv8k::N && !r_per_channel && !no8k) {
         // 8192 points, one inverse spectrum for all channels: two register-resident 4096-point
         // transforms per channel pair, the packed spectrum multiplied directly (kernels_deconv8k.hpp)
-        if (!c->w4_tables) {
-            std::vector<float2> h;
-            welch4096::host_tables(h);
-            CHK(upload_table_fwd(c, &c->w4_tables, h));
-        }
-        if (!c->deconv8k_tables) {
-            std::vector<float2> h;
-            deconv8k::host_tables(h);
-            CHK(upload_table_fwd(c, &c->deconv8k_tables, h));
-        }
+        CHK(ensure_table(c, &c->w4_tables, welch4096::host_tables));
+        CHK(ensure_table(c, &c->deconv8k_tables, deconv8k::host_tables));
         deconv8k::Args a8{y, n_samples, ld, n_out, ld_out, n_ch, c->w4_tables, c->deconv8k_tables,
                           (const float2*)r, ir};
         // one 256-thread group per channel pair, its two sub-spectra one after the other: three independent
@@ -2809,14 +2553,6 @@ extern "C" int ds_deconv_dev(ds_ctx* c, const float* y, int n_items, int n_ch, i
 }
 
 // ---- FIR ---------------------------------------------------------------------
-static int upload_table_fwd(ds_ctx* c, float2** slot, const std::vector<float2>& h) {
-    if (*slot) return DS_OK;
-    HIPCHK(c, hipMalloc((void**)slot, sizeof(float2) * h.size()));
-    HIPCHK(c, hipMemcpyAsync(*slot, h.data(), sizeof(float2) * h.size(), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return DS_OK;
-}
-
 static int fir_block_len(int n_taps, int v = 0) {  // v: forced block length (DSPTOOLBOX_AMD_FIR_BLOCK), 0 = none
     int n = 1024;
     while (n < 4 * n_taps && n < kMaxFft) n <<= 1;
@@ -2889,13 +2625,7 @@ static int fir_long(ds_ctx* c, const float* x, int n_ch, int64_t ldx, int64_t n_
 static int fir4k_run(ds_ctx* c, const float* x, int n_ch, int64_t ldx, int64_t n_samples, const float* taps,
                      int n_filt, int n_taps, float* y, int64_t ld_y) {
     namespace f4 = fir4k;
-    if (!c->w4_tables) {
-        std::vector<float2> h;
-        welch4096::host_tables(h);
-        HIPCHK(c, hipMalloc((void**)&c->w4_tables, sizeof(float2) * h.size()));
-        HIPCHK(c, hipMemcpyAsync(c->w4_tables, h.data(), sizeof(float2) * h.size(), hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-    }
+    CHK(ensure_table(c, &c->w4_tables, welch4096::host_tables));
     const int P = f4::partitions(n_taps);
     float4* hp;
     CHK(carve(c, &c->ws, &c->ws_bytes, [&](Carver& cv) { hp = cv.take<float4>((size_t)n_filt * P * 8 * 256); }));
@@ -2954,20 +2684,8 @@ static int fir_once(ds_ctx* c, const float* x, int n_ch, int64_t ldx, int64_t n_
     const int64_t n_blocks = (n_samples + L - 1) / L;
     if (use16k) {
         // 16384-point blocks: four 4096-point register transforms per block (kernels_fir16k.hpp)
-        if (!c->w4_tables) {
-            std::vector<float2> h;
-            welch4096::host_tables(h);
-            HIPCHK(c, hipMalloc((void**)&c->w4_tables, sizeof(float2) * h.size()));
-            HIPCHK(c, hipMemcpyAsync(c->w4_tables, h.data(), sizeof(float2) * h.size(), hipMemcpyHostToDevice, c->stream));
-            HIPCHK(c, hipStreamSynchronize(c->stream));
-        }
-        if (!c->fir16k_tables) {
-            std::vector<float2> h;
-            fir16k::host_tables(h);
-            HIPCHK(c, hipMalloc((void**)&c->fir16k_tables, sizeof(float2) * h.size()));
-            HIPCHK(c, hipMemcpyAsync(c->fir16k_tables, h.data(), sizeof(float2) * h.size(), hipMemcpyHostToDevice, c->stream));
-            HIPCHK(c, hipStreamSynchronize(c->stream));
-        }
+        CHK(ensure_table(c, &c->w4_tables, welch4096::host_tables));
+        CHK(ensure_table(c, &c->fir16k_tables, fir16k::host_tables));
         fir16k::PermArgs pa{hs, n_filt, hperm};
         CHK(launch(c, "fir_taps", fir16k::k_permute, dim3((unsigned)(((int64_t)n_filt * N + 255) / 256)), 256, 0, pa));
         fir16k::Args a{x, n_samples, ldx, ld_y, n_ch, n_filt, n_taps, c->w4_tables, c->fir16k_tables, hperm, y, 0};

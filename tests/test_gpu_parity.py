@@ -2595,6 +2595,113 @@ SWITCH_ROUTES = [
 ]
 
 
+# ---- which Welch kernel family each window runs on, per entry point (tests/golden/welch_routes.json) -----------------
+# Keys "<switch>|<kind>|<W>|<hop divisor>|<average>|<input channels>"; the launch names were recorded through the same
+# helper on the library before the Welch dispatch became one route choice (csrc/api.hip, welch_route).
+WELCH_ROUTE_SWITCHES = {"default": {}, "WELCH_GENERIC": {"DSPTOOLBOX_AMD_WELCH_GENERIC": "1"},
+                        "NO_WELCH4096": {"DSPTOOLBOX_AMD_NO_WELCH4096": "1"}}
+WELCH_ROUTE_WINDOWS = [32, 64, 128, 256, 1024, 2048, 4096, 8192, 16384, 32768, 2**20]
+# the transfer function, auto and cross spectra: host float32, host float64 and (tf, psd) device-resident entries
+WELCH_ROUTE_ENTRIES = {"tf": ("tf", "tf_f64", "tf_dev"), "psd": ("psd", "psd_f64", "psd_dev"), "csd": ("csd", "csd_f64")}
+
+
+def _welch_route_case(entry, W, hop_div, average, one_in, n_ch=3):
+    """One small estimate through one C-ABI entry point -> (output arrays, launch names).  `one_in`: one input channel
+    (transfer function) / one channel (spectra); otherwise n_ch of them."""
+    import ctypes as C
+    from dsptoolbox_amd._lib import DeviceBuffer, DevicePlanar, get_context
+    ctx = get_context()
+    p = lambda a: a.ctypes.data_as(C.c_void_p)
+    hop, n = W // hop_div, 2 * W + 3000
+    n_frames = -(-n // hop)
+    rng = np.random.default_rng(W + hop_div)
+    y = rng.standard_normal((n, n_ch))
+    x = (y[:, :1] if one_in else y) * 0.5 + 0.1 * rng.standard_normal((n, 1 if one_in else n_ch))
+    x = np.ascontiguousarray(x)
+    xp, yp = np.ascontiguousarray(x.T, dtype=np.float32), np.ascontiguousarray(y.T, dtype=np.float32)
+    w = (0.5 - 0.5 * np.cos(2 * np.pi * np.arange(W) / W)).astype(np.float32)
+    B, avg, kind = W // 2 + 1, backend.DS_AVG[average], entry.split("_")[0]
+    tail = (1, avg) + ((backend.DS_TF["H2"],) if kind == "tf" else ()) + (0, 1.0 / W, 2.0, 1)
+    n_out = n_ch if kind == "tf" else x.shape[1]
+    ctx.routes()
+    if entry.endswith("_dev"):
+        dx, dy = DevicePlanar.from_planar(ctx, xp), DevicePlanar.from_planar(ctx, yp)
+        dw, do = DeviceBuffer.from_array(ctx, w), DeviceBuffer(ctx, B * n_out * 12)
+        if kind == "tf":
+            ctx.check(ctx.lib.ds_welch_tf_dev(ctx.handle, C.c_void_p(dx.ptr), dx.n_ch, dx.ld, C.c_void_p(dy.ptr), dy.n_ch,
+                                              dy.ld, n, W, hop, n_frames, C.c_void_p(dw.ptr), *tail, C.c_void_p(do.ptr),
+                                              C.c_void_p(do.ptr + B * n_out * 8)), entry)
+            raw = do.to_array((B * n_out * 12,), np.uint8)
+            out = (raw[:B * n_out * 8].view(np.complex64), raw[B * n_out * 8:].view(np.float32))
+        else:
+            ctx.check(ctx.lib.ds_welch_psd_dev(ctx.handle, C.c_void_p(dx.ptr), dx.n_ch, dx.ld, n, W, hop, n_frames,
+                                               C.c_void_p(dw.ptr), *tail, C.c_void_p(do.ptr)), entry)
+            out = (do.to_array((B * n_out,), np.float32),)
+        for b in (dx.owner, dy.owner, dw, do):
+            b.free()
+        return out, ctx.routes()
+    f64 = entry.endswith("_f64")
+    xa, ya = (x, y) if f64 else (xp, yp)
+    if kind == "tf":
+        tf, coh = np.empty((B, n_out), np.complex64), np.empty((B, n_out), np.float32)
+        fn = ctx.lib.ds_welch_tf_f64 if f64 else ctx.lib.ds_welch_tf
+        ctx.check(fn(ctx.handle, p(xa), x.shape[1], p(ya), n_ch, n, W, hop, n_frames, p(w), *tail, p(tf), p(coh)), entry)
+        out = (tf, coh)
+    elif kind == "psd":
+        psd = np.empty((B, n_out), np.float32)
+        fn = ctx.lib.ds_welch_psd_f64 if f64 else ctx.lib.ds_welch_psd
+        ctx.check(fn(ctx.handle, p(xa), n_out, n, W, hop, n_frames, p(w), *tail, p(psd)), entry)
+        out = (psd,)
+    else:
+        ya = np.ascontiguousarray(ya[:, :n_out] if f64 else ya[:n_out])
+        csd = np.empty((B, n_out), np.complex64)
+        fn = ctx.lib.ds_welch_csd_f64 if f64 else ctx.lib.ds_welch_csd
+        ctx.check(fn(ctx.handle, p(xa), p(ya), n_out, n, W, hop, n_frames, p(w), *tail, p(csd)), entry)
+        out = (csd,)
+    return out, ctx.routes()
+
+
+def _welch_route_matrix(kinds=("tf", "psd", "csd"), windows=WELCH_ROUTE_WINDOWS, on_case=None):
+    """{key: sorted launch names} of every case of the matrix under the current context's switches."""
+    seen = {}
+    for kind in kinds:
+        for W in windows:
+            for hop_div in (2, 4):
+                for average in ("mean", "median"):
+                    for one_in in (True, False):
+                        for entry in WELCH_ROUTE_ENTRIES[kind]:
+                            out, routes = _welch_route_case(entry, W, hop_div, average, one_in)
+                            key = f"{entry}|{W}|{hop_div}|{average}|{1 if one_in else 3}"
+                            seen[key] = sorted(routes)
+                            if on_case:
+                                on_case(key, out)
+    return seen
+
+
+@pytest.mark.parametrize("W", WELCH_ROUTE_WINDOWS)
+@pytest.mark.parametrize("kind", list(WELCH_ROUTE_ENTRIES))
+@pytest.mark.parametrize("switch", list(WELCH_ROUTE_SWITCHES))
+def test_welch_routes_per_window(switch, kind, W, monkeypatch):
+    """Each (window, overlap, averaging, channel layout) of every Welch entry point launches the kernels it launched
+    when the table was recorded: a change of route is a change of the rounding of every spectrum that takes it."""
+    import json
+    from dsptoolbox_amd import _lib
+    with open(os.path.join(ROOT, "tests", "golden", "welch_routes.json")) as fh:
+        table = json.load(fh)
+    for k, v in WELCH_ROUTE_SWITCHES[switch].items():
+        monkeypatch.setenv(k, v)
+    _lib.reset_context()
+    try:
+        seen = _welch_route_matrix((kind,), (W,))
+    finally:
+        for k in WELCH_ROUTE_SWITCHES[switch]:
+            monkeypatch.delenv(k, raising=False)
+        _lib.reset_context()
+    # (every entry point of a kind runs the same kernels: the table has one row per kind)
+    want = {k: table[f"{switch}|{kind}|{k.split('|', 1)[1]}"].split() for k in seen}
+    assert seen == want
+
+
 @pytest.mark.parametrize("route", SWITCH_ROUTES, ids=lambda r: ",".join(f"{k.replace('DSPTOOLBOX_AMD_', '')}={v}"
                                                                         for k, v in r[0].items()) or "default")
 def test_kernel_selecting_switches(route, monkeypatch):
