@@ -471,22 +471,35 @@ static int launch_finish(ds_ctx* c, WelchFinArgs f) {
     return launch(c, wide ? "welch_finish@wide" : "welch_finish", k_welch_finish, grid, 256, 0, f);
 }
 
-#define DISPATCH_N(n, CALL)                                                        \
+// The statements after OTHER with constexpr NN = n for the FFT lengths of the LDS-resident kernels; OTHER for any other n
+#define DISPATCH_N_OR(n, OTHER, ...)                                               \
     switch (n) {                                                                   \
-        case 8: { constexpr int NN = 8; CALL; } break;                             \
-        case 16: { constexpr int NN = 16; CALL; } break;                           \
-        case 32: { constexpr int NN = 32; CALL; } break;                           \
-        case 64: { constexpr int NN = 64; CALL; } break;                           \
-        case 128: { constexpr int NN = 128; CALL; } break;                         \
-        case 256: { constexpr int NN = 256; CALL; } break;                         \
-        case 512: { constexpr int NN = 512; CALL; } break;                         \
-        case 1024: { constexpr int NN = 1024; CALL; } break;                       \
-        case 2048: { constexpr int NN = 2048; CALL; } break;                       \
-        case 4096: { constexpr int NN = 4096; CALL; } break;                       \
-        case 8192: { constexpr int NN = 8192; CALL; } break;                       \
-        case 16384: { constexpr int NN = 16384; CALL; } break;                     \
-        default: return fail(c, DS_ERR_UNSUP, "FFT length must be a power of two in [8, 16384]"); \
+        case 8: { constexpr int NN = 8; __VA_ARGS__; } break;                      \
+        case 16: { constexpr int NN = 16; __VA_ARGS__; } break;                    \
+        case 32: { constexpr int NN = 32; __VA_ARGS__; } break;                    \
+        case 64: { constexpr int NN = 64; __VA_ARGS__; } break;                    \
+        case 128: { constexpr int NN = 128; __VA_ARGS__; } break;                  \
+        case 256: { constexpr int NN = 256; __VA_ARGS__; } break;                  \
+        case 512: { constexpr int NN = 512; __VA_ARGS__; } break;                  \
+        case 1024: { constexpr int NN = 1024; __VA_ARGS__; } break;                \
+        case 2048: { constexpr int NN = 2048; __VA_ARGS__; } break;                \
+        case 4096: { constexpr int NN = 4096; __VA_ARGS__; } break;                \
+        case 8192: { constexpr int NN = 8192; __VA_ARGS__; } break;                \
+        case 16384: { constexpr int NN = 16384; __VA_ARGS__; } break;              \
+        default: OTHER;                                                            \
     }
+#define DISPATCH_N(n, ...) \
+    DISPATCH_N_OR(n, return fail(c, DS_ERR_UNSUP, "FFT length must be a power of two in [8, 16384]"), __VA_ARGS__)
+
+// The same for the few values of a runner's class count or flag: f(std::integral_constant<int, V>{}) for the V of Vs
+// that v equals (every caller's v is one of them) / f(std::true_type{}) or f(std::false_type{})
+template <int... Vs, class F>
+static int dispatch(int v, F&& f) {
+    int rc = DS_ERR_UNSUP;
+    (void)((v == Vs && ((rc = f(std::integral_constant<int, Vs>{})), true)) || ...);
+    return rc;
+}
+template <class F> static int dispatch_flag(bool b, F&& f) { return b ? f(std::true_type{}) : f(std::false_type{}); }
 
 // per-length twiddle blob (fft_lds.hpp: one [k][t] table per pass, forward + reversed sequence)
 static int get_twiddles(ds_ctx* c, int n, const float2** out) {
@@ -528,6 +541,24 @@ static int ensure_table(ds_ctx* c, float2** slot, Fill fill) {
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return DS_OK;
 }
+// twiddle tables of the wave-level transforms (stft1k::host_tables<N>), cached per context
+template <int NN>
+static int wave_tables(ds_ctx* c, const float2** out) {
+    float2** tab = NN == 1024 ? &c->stft1k_tables : &c->stft_wave_tables[NN == 512 ? 0 : (NN == 256 ? 1 : 2)];
+    CHK(ensure_table(c, tab, stft1k::host_tables<NN>));
+    *out = *tab;
+    return DS_OK;
+}
+// tables of the long-window transforms (R = length / 4096 classes, *lgR = log2 R): the 4096-point kernel's, then the
+// radix-R stage's (*twl)
+static int long_tables(ds_ctx* c, int R, int* lgR, const float2** twl) {
+    for (*lgR = 0; (1 << *lgR) < R;) ++*lgR;
+    CHK(ensure_table(c, &c->w4_tables, welch4096::host_tables));
+    float2** slot = &c->wl_tables[*lgR - 1];
+    CHK(ensure_table(c, slot, [R](std::vector<float2>& h) { welchl::host_tables(R, h); }));
+    *twl = *slot;
+    return DS_OK;
+}
 struct BigScratch {  // stft_big's scratch: two groups of four-step transforms and the frame means
     float2 *P, *Q;
     float* means;
@@ -544,13 +575,25 @@ static int welch_big(ds_ctx* c, int kind, const float* x, int n_cx, int64_t ldx,
 extern "C" int ds_rfft_dev(ds_ctx* c, const float* x, int n_ch, int64_t ld, int64_t n_samples,
                            int n_fft, float scale, ds_c32* spec);
 
+// ---- STFT ------------------------------------------------------------------
+// One call of ds_stft_r2c_dev, as every STFT runner takes it (checked by stft_check; `who`: the entry point called)
+struct StftCall {
+    const char* who;
+    const float* x; int64_t n_samples; int n_ch; int64_t ld; int W, hop, nfft; int64_t pad_front; int n_frames;
+    const float* window; int detrend; float scale, edge_scale; int power; float2* out;
+};
+static int stft_check(ds_ctx* c, const StftCall& s) {
+    const std::string w(s.who);
+    if (!c || !s.x || !s.out || !s.window) return fail(c, DS_ERR_ARG, w + ": null argument");
+    if (s.n_ch <= 0 || s.n_samples <= 0 || s.W <= 0 || s.hop <= 0 || s.n_frames <= 0 || s.ld < s.n_samples)
+        return fail(c, DS_ERR_ARG, w + ": bad shape");
+    if (s.nfft < 2) return fail(c, DS_ERR_ARG, w + ": fft length must be >= 2");
+    return DS_OK;
+}
 // any fft length (kernels_stft_any.hpp): rows = windowed frames -> ds_rfft_dev -> scaling pass
-static int stft_any(ds_ctx* c, const float* x, int64_t n_samples, int n_ch, int64_t ld, int W, int hop,
-                    int nfft, int64_t pad_front, int n_frames, const float* window, int detrend, float scale,
-                    float edge_scale, int power, float2* out) {
-    if (nfft < 2) return fail(c, DS_ERR_ARG, "ds_stft_r2c: fft length must be >= 2");
-    const int keep = std::min(W, nfft), B = nfft / 2 + 1;
-    const int64_t total_rows = (int64_t)n_frames * n_ch;
+static int stft_any_run(ds_ctx* c, const StftCall& s) {
+    const int nfft = s.nfft, keep = std::min(s.W, nfft), B = nfft / 2 + 1;
+    const int64_t total_rows = (int64_t)s.n_frames * s.n_ch;
     // rows per group: the transform's scratch grows with the (padded) length; keep a group's
     // rows + spectra near 256 MB (Bluestein lengths count with their convolution length)
     int64_t conv = nfft;
@@ -569,186 +612,242 @@ static int stft_any(ds_ctx* c, const float* x, int64_t n_samples, int n_ch, int6
     }));
     for (int64_t r0 = 0; r0 < total_rows; r0 += group) {
         const int nr = (int)std::min<int64_t>(group, total_rows - r0);
-        stftany::PrepArgs pa{x, n_samples, ld, pad_front, n_ch, W, hop, detrend, window, keep, (int)r0, rows};
+        stftany::PrepArgs pa{s.x, s.n_samples, s.ld, s.pad_front, s.n_ch, s.W, s.hop, s.detrend, s.window, keep, (int)r0, rows};
         CHK(launch(c, "stft_any_prepare", stftany::k_prepare, dim3(nr), 256, 0, pa));
         CHK(ds_rfft_dev(c, rows, nr, keep, keep, nfft, 1.0f, (ds_c32*)tmp));
-        stftany::PostArgs po{tmp, out, B, nr, (int)r0, (int)total_rows, scale, edge_scale, (nfft % 2) == 0, power};
+        stftany::PostArgs po{tmp, s.out, B, nr, (int)r0, (int)total_rows, s.scale, s.edge_scale, (nfft % 2) == 0, s.power};
         const int64_t tot = (int64_t)B * nr;
         CHK(launch(c, "stft_any_post", stftany::k_post, dim3((unsigned)((tot + 255) / 256)), 256, 0, po));
     }
     return DS_OK;
 }
-
-// ---- STFT ------------------------------------------------------------------
-extern "C" int ds_stft_r2c_dev(ds_ctx* c, const float* x, int64_t n_samples, int n_ch, int64_t ld,
-                               int W, int hop, int nfft, int64_t pad_front, int n_frames,
-                               const float* window, int detrend, float scale, float edge_scale,
-                               int power, ds_c32* out) {
-    if (!c || !x || !out || !window) return fail(c, DS_ERR_ARG, "ds_stft_r2c: null argument");
-    if (n_ch <= 0 || n_samples <= 0 || W <= 0 || hop <= 0 || n_frames <= 0 || ld < n_samples)
-        return fail(c, DS_ERR_ARG, "ds_stft_r2c: bad shape");
-    if (!is_pow2(nfft) || nfft < kMinFft)  // numpy's rfft(n=...) takes any n: crop or pad
-        return stft_any(c, x, n_samples, n_ch, ld, W, hop, nfft, pad_front, n_frames, window, detrend, scale,
-                        edge_scale, power, (float2*)out);
-    // 2^15 ... 2^18 points: one decimation-in-frequency pass, then the 4096-point register transform per class
-    // (kernels_stft_long.hpp)
-    // (k_sdif: frames of a group on grid.y, channel pairs on grid.z)
-    if (const int R = stftl::classes_of(nfft); R && W <= nfft && (W == nfft || !detrend) && !c->cfg.stft_generic && (n_ch + 1) / 2 <= 65535) {
-        int lgR = 0;
-        while ((1 << lgR) < R) ++lgR;
-        CHK(ensure_table(c, &c->w4_tables, welch4096::host_tables));
-        float2** slot = &c->wl_tables[lgR - 1];
-        CHK(ensure_table(c, slot, [R](std::vector<float2>& h) { welchl::host_tables(R, h); }));
-        const int n_pc = (n_ch + 1) / 2, n_groups = (n_ch + 15) / 16;
-        const int per = std::min(65535, stftl::frames_per_group(n_ch, nfft, n_frames));
-        float2* b;
-        CHK(carve(c, &c->ws, &c->ws_bytes, [&](Carver& cv) { b = cv.take<float2>((size_t)n_pc * per * nfft); }));
-        for (int f0 = 0; f0 < n_frames; f0 += per) {
-            const int nf = std::min(per, n_frames - f0);
-            // chunks of (frame, kind) units: two rounds of one workgroup (8 channels) per CU, as for 8192 / 16384 points
-            const int n_units = nf * (R - 1);
-            int n_chunks = std::max(1, std::min(n_units, 256 / std::max(1, std::min(256, n_groups))));
-            if (c->cfg.stft4k_chunks > 0) n_chunks = std::min(n_units, c->cfg.stft4k_chunks);
-            stftl::Args a{x, n_samples, ld, pad_front, n_ch, W, hop, n_frames, detrend, n_chunks, n_groups, R, lgR, f0, nf,
-                          window, c->w4_tables, *slot, scale, edge_scale, b, (float2*)out};
-            const dim3 gd(16, (unsigned)nf, (unsigned)n_pc);
-            switch (R) {
-                case 8: CHK(launch(c, "stft_long_dif", stftl::k_sdif<8>, gd, 256, 0, a)); break;
-                case 16: CHK(launch(c, "stft_long_dif", stftl::k_sdif<16>, gd, 256, 0, a)); break;
-                case 32: CHK(launch(c, "stft_long_dif", stftl::k_sdif<32>, gd, 256, 0, a)); break;
-                default: CHK(launch(c, "stft_long_dif", stftl::k_sdif<64>, gd, 256, 0, a)); break;
-            }
-            const dim3 grid((unsigned)stft4k::grid_size(n_groups, n_chunks));
-            CHK(power ? launch(c, "stft@long", stftl::k_stft_cls<true>, grid, stftl::NT, stftl::LDS_BYTES, a)
-                      : launch(c, "stft@long", stftl::k_stft_cls<false>, grid, stftl::NT, stftl::LDS_BYTES, a));
-        }
-        return DS_OK;
-    }
-    if (nfft > kMaxFft && is_pow2(nfft)) {  // four-step transform per frame pair
-        BigScratch s;
-        CHK(carve(c, &c->ws, &c->ws_bytes, [&](Carver& cv) { s = take_big_scratch(cv, n_ch, n_frames, nfft); }));
-        return stft_big(c, s, x, n_ch, ld, n_samples, W, hop, nfft, pad_front, n_frames, window, detrend,
-                        scale, edge_scale, power, 1, (float2*)out);
-    }
-    CHK(check_fft_len(c, nfft, "ds_stft_r2c nfft"));
-    // 256-, 512- and 1024-point transforms (1024 = the reference's default frame): wave-level
-    // register transforms, one frame pair per team of nfft/16 lanes (kernels_stft1024.hpp)
-    const bool stft_generic = c->cfg.stft_generic;
-    // frames of 128 / 64 / 32 samples: their transform is every 2nd / 4th / 8th bin of the 256-point transform of the
-    // zero-padded frame (the wave kernel with decim; removing the frame mean still only clears bin 0 of the kept bins)
-    const int decim = (nfft == 128 || nfft == 64 || nfft == 32) ? 256 / nfft : 1;
-    const int nfft_k = decim > 1 ? 256 : nfft;  // the transform that runs
-    if ((nfft_k == 2048 || nfft_k == 1024 || nfft_k == 512 || nfft_k == 256) && (W == nfft || (W < nfft && !detrend)) &&
-        !stft_generic && stft1k::stft_wave_fits(n_samples, n_ch, ld, pad_front, nfft_k)) {
-        const int nfft_api = nfft;
-        (void)nfft_api;
-        nfft = nfft_k;
-        const int slot = nfft == 1024 ? 0 : (nfft == 512 ? 1 : (nfft == 256 ? 2 : 3));
-        float2** tab = slot == 0 ? &c->stft1k_tables : &c->stft_wave_tables[slot - 1];
-        CHK(ensure_table(c, tab, [nfft](std::vector<float2>& h) {
-            if (nfft == 2048) stft1k::host_tables<2048>(h);
-            else if (nfft == 1024) stft1k::host_tables<1024>(h);
-            else if (nfft == 512) stft1k::host_tables<512>(h);
-            else stft1k::host_tables<256>(h);
+// 2^15 ... 2^18 points: one decimation-in-frequency pass, then the 4096-point register transform per class
+// (kernels_stft_long.hpp; k_sdif: frames of a group on grid.y, channel pairs on grid.z)
+static int stft_long_run(ds_ctx* c, const StftCall& s) {
+    const int R = stftl::classes_of(s.nfft);
+    int lgR;
+    const float2* twl;
+    CHK(long_tables(c, R, &lgR, &twl));
+    const int n_pc = (s.n_ch + 1) / 2, n_groups = (s.n_ch + 15) / 16;
+    const int per = std::min(65535, stftl::frames_per_group(s.n_ch, s.nfft, s.n_frames));
+    float2* b;
+    CHK(carve(c, &c->ws, &c->ws_bytes, [&](Carver& cv) { b = cv.take<float2>((size_t)n_pc * per * s.nfft); }));
+    for (int f0 = 0; f0 < s.n_frames; f0 += per) {
+        const int nf = std::min(per, s.n_frames - f0);
+        // chunks of (frame, kind) units: two rounds of one workgroup (8 channels) per CU, as for 8192 / 16384 points
+        const int n_units = nf * (R - 1);
+        int n_chunks = std::max(1, std::min(n_units, 256 / std::max(1, std::min(256, n_groups))));
+        if (c->cfg.stft4k_chunks > 0) n_chunks = std::min(n_units, c->cfg.stft4k_chunks);
+        stftl::Args a{s.x, s.n_samples, s.ld, s.pad_front, s.n_ch, s.W, s.hop, s.n_frames, s.detrend, n_chunks, n_groups, R,
+                      lgR, f0, nf, s.window, c->w4_tables, twl, s.scale, s.edge_scale, b, s.out};
+        const dim3 gd(16, (unsigned)nf, (unsigned)n_pc), grid((unsigned)stft4k::grid_size(n_groups, n_chunks));
+        CHK((dispatch<8, 16, 32, 64>(R, [&](auto r) { return launch(c, "stft_long_dif", stftl::k_sdif<r.value>, gd, 256, 0, a); })));
+        CHK(dispatch_flag(s.power, [&](auto p) {
+            return launch(c, "stft@long", stftl::k_stft_cls<p.value>, grid, stftl::NT, stftl::LDS_BYTES, a);
         }));
+    }
+    return DS_OK;
+}
+// powers of two beyond the register kernels: four-step transform per frame pair (kernels_bigfft.hpp)
+static int stft_big_run(ds_ctx* c, const StftCall& s) {
+    BigScratch b;
+    CHK(carve(c, &c->ws, &c->ws_bytes, [&](Carver& cv) { b = take_big_scratch(cv, s.n_ch, s.n_frames, s.nfft); }));
+    return stft_big(c, b, s.x, s.n_ch, s.ld, s.n_samples, s.W, s.hop, s.nfft, s.pad_front, s.n_frames, s.window, s.detrend,
+                    s.scale, s.edge_scale, s.power, 1, s.out);
+}
+// 256-, 512-, 1024- and 2048-point transforms (1024 = the reference's default frame): wave-level register transforms,
+// one frame pair per team of NN / 16 lanes (kernels_stft1024.hpp).  Frames of 128 / 64 / 32 samples (NN = 256): their
+// transform is every 2nd / 4th / 8th bin of the 256-point transform of the zero-padded frame (decim; removing the frame
+// mean still only clears bin 0 of the kept bins)
+static int stft_wave_run(ds_ctx* c, const StftCall& s) {
+    return dispatch<256, 512, 1024, 2048>(s.nfft < 256 ? 256 : s.nfft, [&](auto n) {
+        constexpr int NN = n.value;
+        const float2* tab;
+        CHK(wave_tables<NN>(c, &tab));
         // channels per workgroup: 16 teams = 128-byte runs of the output X[bin][frame][channel] (whole
         // cache lines; at 1024 points that is one 1024-thread workgroup of 140 KB per CU instead of two
         // of 8 channels with 64-byte runs: transform of the 64-microphone shape 105 -> 97 us);
         // 2048 points: 8 x 17 KB images, one 1024-thread workgroup per CU (4 channels = 32-byte runs,
         // two per CU: 0.20 ms against 0.16)
-        const int lanes = nfft / 16;
-        int ct = std::min(nfft >= 2048 ? 8 : 16, n_ch);
-        if (const int v = c->cfg.stft_ct; v >= 1 && v <= 16 && v * lanes <= 1024) ct = std::min(v, n_ch);
+        const int lanes = NN / 16;
+        int ct = std::min(NN >= 2048 ? 8 : 16, s.n_ch);
+        if (const int v = c->cfg.stft_ct; v >= 1 && v <= 16 && v * lanes <= 1024) ct = std::min(v, s.n_ch);
         while (ct & (ct - 1)) ct &= ct - 1;
-        const size_t lds = nfft == 2048 ? stft1k::lds_bytes<2048>(ct) : nfft == 1024 ? stft1k::lds_bytes<1024>(ct)
-                                        : (nfft == 512 ? stft1k::lds_bytes<512>(ct) : stft1k::lds_bytes<256>(ct));
+        const size_t lds = stft1k::lds_bytes<NN>(ct);
         const int threads = lanes * ct;
         // frame pairs per workgroup: as few as keep the whole grid resident at once, at most 16
         const int per_cu = std::max(1, std::min<int>({(int)((160 * 1024) / lds), 2048 / std::max(64, threads), 8}));
-        const int n_fp = (n_frames + 1) / 2, n_ct = (n_ch + ct - 1) / ct;
+        const int n_fp = (s.n_frames + 1) / 2, n_ct = (s.n_ch + ct - 1) / ct;
         const int64_t resident = 256 * (int64_t)per_cu;
         int fpw = std::max(1, std::min(16, (int)(((int64_t)n_fp * n_ct + resident - 1) / resident)));
         if (c->cfg.stft_fpw > 0) fpw = c->cfg.stft_fpw;
-        StftArgs a{x, n_samples, ld, pad_front, n_ch, W, hop, n_frames, detrend, power, ct, fpw, window,
-                   *tab, scale, edge_scale, (float2*)out, decim};
-        dim3 grid((unsigned)((n_fp + fpw - 1) / fpw), (unsigned)n_ct);
-        if (nfft == 2048)
-            return power ? launch(c, "stft@wave", stft1k::k_stft_wave<2048, true>, grid, threads, lds, a)
-                         : launch(c, "stft@wave", stft1k::k_stft_wave<2048, false>, grid, threads, lds, a);
-        if (nfft == 1024)
-            return power ? launch(c, "stft@wave", stft1k::k_stft_wave<1024, true>, grid, threads, lds, a)
-                         : launch(c, "stft@wave", stft1k::k_stft_wave<1024, false>, grid, threads, lds, a);
-        if (nfft == 512)
-            return power ? launch(c, "stft@wave", stft1k::k_stft_wave<512, true>, grid, threads, lds, a)
-                         : launch(c, "stft@wave", stft1k::k_stft_wave<512, false>, grid, threads, lds, a);
-        return power ? launch(c, "stft@wave", stft1k::k_stft_wave<256, true>, grid, threads, lds, a)
-                     : launch(c, "stft@wave", stft1k::k_stft_wave<256, false>, grid, threads, lds, a);
-    }
-    // 4096-point transforms: the register-resident transform of the Welch path, four teams of two neighbouring
-    // channels per workgroup and frame (kernels_stft4096.hpp)
-    if (nfft == 4096 && W <= nfft && (W == nfft || !detrend) && !stft_generic && stft4k::fits(n_samples, pad_front)) {
-        CHK(ensure_table(c, &c->w4_tables, welch4096::host_tables));
-        const int n_groups = (n_ch + 15) / 16;
-        // chunks of frames: as many as put one workgroup (8 channels) on each of the 256 CUs
-        int n_chunks = std::max(1, std::min(n_frames, 128 / std::max(1, std::min(128, n_groups))));
-        if (c->cfg.stft4k_chunks > 0) n_chunks = std::min(n_frames, c->cfg.stft4k_chunks);
-        stft4k::Args a{x, n_samples, ld, pad_front, n_ch, W, hop, n_frames, detrend, n_chunks, n_groups, window,
-                       c->w4_tables, scale, edge_scale, (float2*)out, nullptr};
-        const dim3 grid((unsigned)stft4k::grid_size(n_groups, n_chunks));
-        return power ? launch(c, "stft@4k", stft4k::k_stft<true>, grid, stft4k::NT, stft4k::LDS_BYTES, a)
-                     : launch(c, "stft@4k", stft4k::k_stft<false>, grid, stft4k::NT, stft4k::LDS_BYTES, a);
-    }
-    // 8192 / 16384 points: one radix-2 / radix-4 decimation-in-frequency stage on the windowed samples, then the
-    // 4096-point kernel's structure per residue (kernels_stft4096.hpp, k_stft_dif)
-    if ((nfft == 8192 || nfft == 16384) && W <= nfft && (W == nfft || !detrend) && !stft_generic &&
-        stft4k::fits_long(n_samples, pad_front, nfft)) {
-        CHK(ensure_table(c, &c->w4_tables, welch4096::host_tables));
-        float2** twn = &c->stft_dif_tw[nfft == 8192 ? 0 : 1];
-        CHK(ensure_table(c, twn, [nfft](std::vector<float2>& h) { stft4k::host_twiddles(nfft, h); }));
-        const int n_groups = (n_ch + 15) / 16;
-        // chunks of (frame, phase) units: two rounds of one workgroup (8 channels) per CU (64 x 512 000 samples, 8192
-        // points: 0.182 ms against 0.198 with one round)
-        int n_chunks = std::max(1, std::min(n_frames, 256 / std::max(1, std::min(256, n_groups))));
-        if (c->cfg.stft4k_chunks > 0) n_chunks = std::min(n_frames, c->cfg.stft4k_chunks);
-        stft4k::Args a{x, n_samples, ld, pad_front, n_ch, W, hop, n_frames, detrend, n_chunks, n_groups, window,
-                       c->w4_tables, scale, edge_scale, (float2*)out, *twn};
-        const dim3 grid((unsigned)stft4k::grid_size(n_groups, n_chunks));
-        if (nfft == 8192)
-            return power ? launch(c, "stft@dif", stft4k::k_stft_dif<2, true>, grid, stft4k::NT, stft4k::Dif<2>::LDS_BYTES, a)
-                         : launch(c, "stft@dif", stft4k::k_stft_dif<2, false>, grid, stft4k::NT, stft4k::Dif<2>::LDS_BYTES, a);
-        return power ? launch(c, "stft@dif", stft4k::k_stft_dif<4, true>, grid, stft4k::NT, stft4k::Dif<4>::LDS_BYTES, a)
-                     : launch(c, "stft@dif", stft4k::k_stft_dif<4, false>, grid, stft4k::NT, stft4k::Dif<4>::LDS_BYTES, a);
-    }
+        StftArgs a{s.x, s.n_samples, s.ld, s.pad_front, s.n_ch, s.W, s.hop, s.n_frames, s.detrend, s.power, ct, fpw, s.window,
+                   tab, s.scale, s.edge_scale, s.out, NN / s.nfft};
+        const dim3 grid((unsigned)((n_fp + fpw - 1) / fpw), (unsigned)n_ct);
+        return dispatch_flag(s.power, [&](auto p) {
+            return launch(c, "stft@wave", stft1k::k_stft_wave<NN, p.value>, grid, threads, lds, a);
+        });
+    });
+}
+// 4096-point transforms: the register-resident transform of the Welch path, four teams of two neighbouring
+// channels per workgroup and frame (kernels_stft4096.hpp)
+static int stft4k_run(ds_ctx* c, const StftCall& s) {
+    CHK(ensure_table(c, &c->w4_tables, welch4096::host_tables));
+    const int n_groups = (s.n_ch + 15) / 16;
+    // chunks of frames: as many as put one workgroup (8 channels) on each of the 256 CUs
+    int n_chunks = std::max(1, std::min(s.n_frames, 128 / std::max(1, std::min(128, n_groups))));
+    if (c->cfg.stft4k_chunks > 0) n_chunks = std::min(s.n_frames, c->cfg.stft4k_chunks);
+    stft4k::Args a{s.x, s.n_samples, s.ld, s.pad_front, s.n_ch, s.W, s.hop, s.n_frames, s.detrend, n_chunks, n_groups,
+                   s.window, c->w4_tables, s.scale, s.edge_scale, s.out, nullptr};
+    const dim3 grid((unsigned)stft4k::grid_size(n_groups, n_chunks));
+    return dispatch_flag(s.power, [&](auto p) {
+        return launch(c, "stft@4k", stft4k::k_stft<p.value>, grid, stft4k::NT, stft4k::LDS_BYTES, a);
+    });
+}
+// 8192 / 16384 points: one radix-2 / radix-4 decimation-in-frequency stage on the windowed samples, then the
+// 4096-point kernel's structure per residue (kernels_stft4096.hpp, k_stft_dif)
+static int stft_dif_run(ds_ctx* c, const StftCall& s) {
+    CHK(ensure_table(c, &c->w4_tables, welch4096::host_tables));
+    float2** twn = &c->stft_dif_tw[s.nfft == 8192 ? 0 : 1];
+    CHK(ensure_table(c, twn, [&s](std::vector<float2>& h) { stft4k::host_twiddles(s.nfft, h); }));
+    const int n_groups = (s.n_ch + 15) / 16;
+    // chunks of (frame, phase) units: two rounds of one workgroup (8 channels) per CU (64 x 512 000 samples, 8192
+    // points: 0.182 ms against 0.198 with one round)
+    int n_chunks = std::max(1, std::min(s.n_frames, 256 / std::max(1, std::min(256, n_groups))));
+    if (c->cfg.stft4k_chunks > 0) n_chunks = std::min(s.n_frames, c->cfg.stft4k_chunks);
+    stft4k::Args a{s.x, s.n_samples, s.ld, s.pad_front, s.n_ch, s.W, s.hop, s.n_frames, s.detrend, n_chunks, n_groups,
+                   s.window, c->w4_tables, s.scale, s.edge_scale, s.out, *twn};
+    const dim3 grid((unsigned)stft4k::grid_size(n_groups, n_chunks));
+    return dispatch<2, 4>(s.nfft / 4096, [&](auto d) {
+        return dispatch_flag(s.power, [&](auto p) {
+            return launch(c, "stft@dif", stft4k::k_stft_dif<d.value, p.value>, grid, stft4k::NT, stft4k::Dif<d.value>::LDS_BYTES, a);
+        });
+    });
+}
+// every other power of two in [8, 16384]: the LDS-resident transform (kernels_generic.hpp)
+static int stft_generic_run(ds_ctx* c, const StftCall& s) {
     const float2* tw;
-    CHK(get_twiddles(c, nfft, &tw));
+    CHK(get_twiddles(c, s.nfft, &tw));
     // channel tile: ct teams of NT threads (<= 1024 threads, <= 74 KB of LDS so two
     // workgroups share a CU; 8 channels = 64-byte runs of the (bins, frames, channels) output for
     // nfft 1024: 0.16 ms instead of 0.23 ms with 4 on the 64-mic CSM shape)
-    int ct = 1;
-    size_t lds = 0;
-    int threads = 0;
-    DISPATCH_N(nfft, {
-        const size_t per = (size_t)stft_ch_stride<NN>() * sizeof(float2);
-        ct = std::min<int>(stft_max_teams<NN>(), n_ch);
+    DISPATCH_N(s.nfft, {
+        int ct = std::min<int>(stft_max_teams<NN>(), s.n_ch);
         // (override: fewer teams only, the kernel is compiled for the maximum)
-        if (const int v = c->cfg.stft_ct; v >= 1 && v <= stft_max_teams<NN>()) ct = std::min(v, std::max(1, n_ch));
+        if (const int v = c->cfg.stft_ct; v >= 1 && v <= stft_max_teams<NN>()) ct = std::min(v, std::max(1, s.n_ch));
         while (ct & (ct - 1)) ct &= ct - 1;  // power of two (shift-only index math in the kernel)
-        lds = per * ct;
-        threads = ct * Cfg<NN>::NT;
+        // frame pairs per workgroup: as few as keep the whole grid resident at once (two workgroups
+        // on each of the 256 CUs: no second, partly filled round), at most 16
+        const int n_fp = (s.n_frames + 1) / 2, n_ct = (s.n_ch + ct - 1) / ct;
+        int fpw = std::max(1, std::min(16, (int)(((int64_t)n_fp * n_ct + 511) / 512)));
+        if (c->cfg.stft_fpw > 0) fpw = c->cfg.stft_fpw;
+        StftArgs a{s.x, s.n_samples, s.ld, s.pad_front, s.n_ch, s.W, s.hop, s.n_frames, s.detrend, s.power, ct, fpw,
+                   s.window, tw, s.scale, s.edge_scale, s.out};
+        CHK(launch(c, "stft@generic", k_stft<NN>, dim3((unsigned)((n_fp + fpw - 1) / fpw), (unsigned)n_ct), ct * Cfg<NN>::NT,
+                   (size_t)stft_ch_stride<NN>() * sizeof(float2) * ct, a));
     });
-    // frame pairs per workgroup: as few as keep the whole grid resident at once (two workgroups
-    // on each of the 256 CUs: no second, partly filled round), at most 16
-    const int n_fp = (n_frames + 1) / 2, n_ct = (n_ch + ct - 1) / ct;
-    int fpw = std::max(1, std::min(16, (int)(((int64_t)n_fp * n_ct + 511) / 512)));
-    if (c->cfg.stft_fpw > 0) fpw = c->cfg.stft_fpw;
-    StftArgs a{x, n_samples, ld, pad_front, n_ch, W, hop, n_frames, detrend, power, ct, fpw, window, tw,
-               scale, edge_scale, (float2*)out};
-    dim3 grid((unsigned)((n_fp + fpw - 1) / fpw), (unsigned)n_ct);
-    DISPATCH_N(nfft, CHK(launch(c, "stft@generic", k_stft<NN>, grid, threads, lds, a)));
     return DS_OK;
+}
+using StftRunner = int (*)(ds_ctx*, const StftCall&);
+// The kernel family of a checked call: the register kernels of its length where they apply, the generic one otherwise.
+static StftRunner stft_route(const ds_ctx* c, const StftCall& s) {
+    const int nfft = s.nfft;
+    if (!is_pow2(nfft) || nfft < kMinFft) return stft_any_run;  // numpy's rfft(n=...) takes any n: crop or pad
+    // the register kernels: full frames, or shorter ones that are not detrended
+    const bool reg = s.W <= nfft && (s.W == nfft || !s.detrend) && !c->cfg.stft_generic;
+    if (stftl::classes_of(nfft) && reg && (s.n_ch + 1) / 2 <= 65535) return stft_long_run;
+    if (nfft > kMaxFft) return stft_big_run;
+    const int nfft_k = (nfft == 128 || nfft == 64 || nfft == 32) ? 256 : nfft;
+    if ((nfft_k == 2048 || nfft_k == 1024 || nfft_k == 512 || nfft_k == 256) && reg &&
+        stft1k::stft_wave_fits(s.n_samples, s.n_ch, s.ld, s.pad_front, nfft_k))
+        return stft_wave_run;
+    if (nfft == 4096 && reg && stft4k::fits(s.n_samples, s.pad_front)) return stft4k_run;
+    if ((nfft == 8192 || nfft == 16384) && reg && stft4k::fits_long(s.n_samples, s.pad_front, nfft)) return stft_dif_run;
+    return stft_generic_run;
+}
+extern "C" int ds_stft_r2c_dev(ds_ctx* c, const float* x, int64_t n_samples, int n_ch, int64_t ld,
+                               int W, int hop, int nfft, int64_t pad_front, int n_frames,
+                               const float* window, int detrend, float scale, float edge_scale,
+                               int power, ds_c32* out) {
+    const StftCall s{"ds_stft_r2c_dev", x, n_samples, n_ch, ld, W, hop, nfft, pad_front, n_frames, window, detrend,
+                     scale, edge_scale, power, (float2*)out};
+    CHK(stft_check(c, s));
+    return stft_route(c, s)(c, s);
 }
 
 // ---- inverse STFT ----------------------------------------------------------
+// One call of ds_istft_dev, as every iSTFT runner takes it (checked by istft_check; `who`: the entry point called)
+struct IstftCall {
+    const char* who;
+    const float2* stft; int n_bins, n_frames, n_ch, nfft, W, step, frame_offset, n_frames_total; const float* window;
+    float scale; int64_t total_length; float* out; int64_t ld_out;
+};
+static int istft_check(ds_ctx* c, const IstftCall& q) {
+    const std::string w(q.who);
+    if (!c || !q.stft || !q.window || !q.out) return fail(c, DS_ERR_ARG, w + ": null argument");
+    if (q.n_bins <= 0 || q.n_frames <= 0 || q.n_ch <= 0 || q.W <= 0 || q.step <= 0 || q.step > q.W || q.frame_offset < 0 ||
+        q.n_frames_total < q.n_frames + q.frame_offset || q.total_length <= 0 || q.ld_out < q.total_length)
+        return fail(c, DS_ERR_ARG, w + ": bad shape");
+    if (q.W > q.nfft) return fail(c, DS_ERR_ARG, w + ": window longer than the FFT length");
+    return DS_OK;
+}
+// overlap-add of the frames [c][f][W] into the output rows; four samples per thread (vec4) where every row and frame
+// boundary is a multiple of four samples (and 16-byte aligned)
+static int launch_ola(ds_ctx* c, const IstftCall& q, const float* frames, bool vec4) {
+    IstftOlaArgs o{frames, q.n_frames, q.n_ch, q.W, q.step, q.frame_offset, q.n_frames_total, q.window, q.total_length,
+                   q.ld_out, q.out};
+    if (vec4 && q.W % 4 == 0 && q.step % 4 == 0 && q.total_length % 4 == 0 && q.ld_out % 4 == 0 &&
+        ((uintptr_t)q.out & 15) == 0 && ((uintptr_t)q.window & 15) == 0)
+        return launch(c, "istft_ola", k_istft_ola4, dim3((unsigned)((q.total_length / 4 + 255) / 256), q.n_ch), 256, 0, o);
+    return launch(c, "istft_ola", k_istft_ola, dim3((unsigned)((q.total_length + 255) / 256), q.n_ch), 256, 0, o);
+}
+// 8192 ... 262144 points: class transforms on the 4096-point register kernel, then the radix-R stage with the
+// overlap-add fused where frames overlap by half (kernels_istft_long.hpp)
+static int istft_long_run(ds_ctx* c, const IstftCall& q) {
+    const int R = istftl::classes_of(q.nfft);
+    int lgR;
+    const float2* twl;
+    CHK(long_tables(c, R, &lgR, &twl));
+    const int n_pc = (q.n_ch + 1) / 2, n_groups = (q.n_ch + 15) / 16;
+    // (fused: the class sequences of ALL frames at once, addressed through a raw-buffer descriptor: below 4 GB)
+    const bool fused = q.W == q.nfft && 2 * q.step == q.nfft && R <= 16 &&
+                       (int64_t)n_pc * q.n_frames * q.nfft * 8 < ((int64_t)1 << 32) - 16;
+    const int per = fused ? q.n_frames : istftl::frames_per_group(q.n_ch, q.nfft, q.n_frames);
+    float2* cq;
+    float* frames;
+    CHK(carve(c, &c->ws, &c->ws_bytes, [&](Carver& cv) {
+        cq = cv.take<float2>((size_t)n_pc * per * q.nfft);
+        frames = fused ? nullptr : cv.take<float>((size_t)q.n_ch * q.n_frames * q.W);
+    }));
+    istftl::Args a{q.stft, q.n_bins, q.n_frames, q.n_ch, q.W, q.step, 1, n_groups, R, lgR, 0, q.n_frames, q.window,
+                   c->w4_tables, twl, q.scale, cq, frames, q.frame_offset, q.n_frames_total, q.total_length, q.ld_out, q.out};
+    for (int f0 = 0; f0 < q.n_frames; f0 += per) {
+        a.f0 = f0;
+        a.nf = std::min(per, q.n_frames - f0);
+        const int n_units = a.nf * (R - 1);
+        a.n_chunks = std::max(1, std::min(n_units, 256 / std::max(1, std::min(256, n_groups))));
+        const dim3 gc((unsigned)stft4k::grid_size(n_groups, a.n_chunks));
+        CHK(dispatch_flag((q.n_ch & 1) == 0, [&](auto p) {
+            return launch(c, "istft_long_cls", istftl::k_icls<p.value>, gc, istftl::NT, istftl::LDS_BYTES, a);
+        }));
+        if (fused) break;
+        const dim3 gd(16, (unsigned)a.nf, (unsigned)n_pc);
+        CHK((dispatch<2, 4, 8, 16, 32, 64>(R, [&](auto r) {
+            return launch(c, "istft@long", istftl::k_isdif_frames<r.value>, gd, 256, istftl::xch_bytes(r.value), a);
+        })));
+    }
+    if (!fused) return launch_ola(c, q, frames, true);
+    // chunks of frames (+ 1 frame each for the carry): 8192 workgroups of 256 threads where the frames allow
+    // (a thread has only R loads in flight), at least 4 frames per chunk
+    const int want = std::max(1, 8192 / std::max(1, 16 * n_pc));
+    a.n_chunks = std::max(1, std::min((q.n_frames + 3) / 4, want));
+    if (c->cfg.istft_fpw > 0) a.n_chunks = std::min(q.n_frames, c->cfg.istft_fpw);
+    const dim3 gd(16, (unsigned)a.n_chunks, (unsigned)n_pc);
+    return dispatch<2, 4, 8, 16>(R, [&](auto r) {
+        return launch(c, "istft@long_ola", istftl::k_isdif_ola<r.value>, gd, 256, istftl::xch_bytes(r.value), a);
+    });
+}
+
 // ---- inverse STFT with an FFT length that is not a power of two (transforms/transforms.py:548-577 calls
 // np.fft.irfft(stft, n=fft_length_samples) with any n) ------------------------------------------------------
 // Every (channel, frame) spectrum is one "channel" of the spectral-division machinery, which already
@@ -774,9 +873,14 @@ __global__ void k_istft_scale(float* frames, int64_t total, int W, const float* 
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < total) frames[i] *= scale * window[i % W];
 }
-static int istft_any_frames(ds_ctx* c, const float2* stft, int n_bins, int n_frames, int n_ch, int nfft, int W,
-                            const float* window, float scale, float* frames /* [c][f][W] */) {
-    CHK(check_blue_len(c, nfft, "ds_istft nfft"));
+static int istft_any_run(ds_ctx* c, const IstftCall& q) {
+    const int n_ch = q.n_ch, n_frames = q.n_frames, nfft = q.nfft, W = q.W;
+    // (ws, io and aux are all taken -- the division's scratch, the host entry point's staging, the
+    // per-group spectra -- so the frames live in a fourth context-owned reserve: grown on demand like
+    // the others, no allocation, synchronisation or free per call; this route is correct, not tuned)
+    CHK(reserve(c, &c->frames, &c->frames_bytes, sizeof(float) * (size_t)n_ch * n_frames * W));
+    float* frames = (float*)c->frames;  // [c][f][W]
+    CHK(check_blue_len(c, nfft, (std::string(q.who) + " nfft").c_str()));
     const int nb = nfft / 2 + 1;
     // groups of frames: the division's scratch is ~4 x 8 bytes x (frames x channels / 2) x transform length
     const int64_t m_len = blue_len(nfft);
@@ -792,222 +896,137 @@ static int istft_any_frames(ds_ctx* c, const float2* stft, int n_bins, int n_fra
     for (int f0 = 0; f0 < n_frames; f0 += group) {
         const int nf = std::min(group, n_frames - f0);
         const int64_t total = (int64_t)n_ch * nf * nb;
-        hipLaunchKernelGGL(k_istft_spec, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, c->stream, stft, n_bins, n_frames,
-                           n_ch, f0, nf, nb, r, ones);
+        hipLaunchKernelGGL(k_istft_spec, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, c->stream, q.stft, q.n_bins,
+                           n_frames, n_ch, f0, nf, nb, r, ones);
         HIPCHK(c, hipGetLastError());
         CHK(ds_deconv_dev(c, ones, 1, n_ch * nf, 1, 1, nfft, (const ds_c32*)r, 1, W, W, part));
         // part: [(ch nf + f) W + m] -> frames [(ch n_frames + f0 + f) W + m], windowed and scaled
         const int64_t tw = (int64_t)n_ch * nf * W;
         // (`scale` is defined against an UNnormalised inverse transform, as k_istft computes it; the division
         // machinery returns numpy's normalised irfft)
-        hipLaunchKernelGGL(k_istft_scale, dim3((unsigned)((tw + 255) / 256)), dim3(256), 0, c->stream, part, tw, W, window,
-                           scale * (float)nfft);
+        hipLaunchKernelGGL(k_istft_scale, dim3((unsigned)((tw + 255) / 256)), dim3(256), 0, c->stream, part, tw, W, q.window,
+                           q.scale * (float)nfft);
         HIPCHK(c, hipGetLastError());
         for (int ch = 0; ch < n_ch; ++ch)
             HIPCHK(c, hipMemcpyAsync(frames + ((int64_t)ch * n_frames + f0) * W, part + (int64_t)ch * nf * W,
                                      sizeof(float) * (size_t)nf * W, hipMemcpyDeviceToDevice, c->stream));
     }
+    return launch_ola(c, q, frames, false);
+}
+// The fused runners below: 50 % overlap of full-length frames, transform and overlap-add in one kernel, no frames in
+// memory.  Every power-of-two route in [8, 16384] uploads the generic twiddles of its length first, used or not.
+// ... on the wave-level transform for 256 ... 2048 points (kernels_stft1024.hpp, k_istft_wave)
+static int istft_wave_run(ds_ctx* c, const IstftCall& q) {
+    return dispatch<256, 512, 1024, 2048>(q.nfft, [&](auto n) {
+        constexpr int NN = n.value;
+        const float2 *tw, *tab;
+        CHK(get_twiddles(c, NN, &tw));
+        CHK(wave_tables<NN>(c, &tab));
+        // (2048 points: 45 registers over the 128 of a 1024-thread workgroup: four teams = 512 threads there)
+        const int lanes = NN / 16;
+        int ct = std::min(NN == 2048 ? 4 : 16, q.n_ch);
+        while (ct & (ct - 1)) ct &= ct - 1;
+        const size_t lds = stft1k::istft_lds_bytes<NN>(ct);
+        const int threads = lanes * ct;
+        const int n_fp = (q.n_frames + 1) / 2, n_ct = (q.n_ch + ct - 1) / ct;
+        const int per_cu = std::max(1, std::min<int>((int)((160 * 1024) / lds), 2048 / std::max(64, threads)));
+        // frame pairs per workgroup (+ 1 for the carry): two rounds of resident workgroups, at least 4 (1024 points: 8)
+        // -- 64 x 512 000 samples: 0.154 / 0.130 / 0.135 ms at 256 / 512 / 1024 points, 0.18 / 0.13 / 0.145 one step off
+        int fpw = std::max(NN >= 1024 ? 8 : 4, std::min(64, (int)(((int64_t)n_fp * n_ct + 512 * per_cu - 1) / (512 * per_cu))));
+        if (c->cfg.istft_fpw > 0) fpw = c->cfg.istft_fpw;
+        IstftFusedArgs fa{IstftArgs{q.stft, q.n_bins, q.n_frames, q.n_ch, q.W, q.window, tab, q.scale, nullptr, ct, fpw},
+                          q.frame_offset, q.n_frames_total, q.total_length, q.ld_out, q.out};
+        const dim3 grid((unsigned)((n_fp + fpw - 1) / fpw), (unsigned)n_ct);
+        return launch(c, "istft@wave", stft1k::k_istft_wave<NN>, grid, threads, lds, fa);
+    });
+}
+// ... on the 4096-point register transform, two neighbouring channels per team (kernels_stft4096.hpp, k_istft)
+static int istft4k_run(ds_ctx* c, const IstftCall& q) {
+    const float2* tw;
+    CHK(get_twiddles(c, q.nfft, &tw));
+    CHK(ensure_table(c, &c->w4_tables, welch4096::host_tables));
+    const int n_groups = (q.n_ch + 15) / 16;
+    // chunks of frames (+ 1 frame each for the carry): two rounds of one workgroup (8 channels) per CU
+    int n_chunks = std::max(1, std::min((q.n_frames + 3) / 4, 256 / std::max(1, std::min(256, n_groups))));
+    if (c->cfg.istft_fpw > 0) n_chunks = std::min(q.n_frames, c->cfg.istft_fpw);
+    IstftFusedArgs fa{IstftArgs{q.stft, q.n_bins, q.n_frames, q.n_ch, q.W, q.window, c->w4_tables, q.scale, nullptr, 1, n_chunks},
+                      q.frame_offset, q.n_frames_total, q.total_length, q.ld_out, q.out};
+    const dim3 g4((unsigned)stft4k::grid_size(n_groups, n_chunks));
+    return dispatch_flag((q.n_ch & 1) == 0, [&](auto p) {
+        return launch(c, "istft@4k", stft4k::k_istft<p.value>, g4, stft4k::NT, stft4k::ISTFT_LDS_BYTES, fa);
+    });
+}
+// ... and on the LDS-resident transform where it has more than one team and whole 2 NT-point steps (kernels_generic.hpp)
+template <int NN> static constexpr bool istft_fuses() { return stft_max_teams<NN>() > 1 && NN % (2 * Cfg<NN>::NT) == 0; }
+static int istft_fused_run(ds_ctx* c, const IstftCall& q) {
+    const float2* tw;
+    CHK(get_twiddles(c, q.nfft, &tw));
+    DISPATCH_N(q.nfft, if constexpr (istft_fuses<NN>()) {
+        int ct = std::min<int>(stft_max_teams<NN>(), q.n_ch);
+        while (ct & (ct - 1)) ct &= ct - 1;
+        const size_t lds = (size_t)stft_ch_stride<NN>() * sizeof(float2) * ct + sizeof(float) * (size_t)(NN / 2);  // + 1 / envelope
+        const int n_fp = (q.n_frames + 1) / 2, n_ct = (q.n_ch + ct - 1) / ct;
+        // frame pairs per workgroup: every workgroup transforms one more pair (the carry in front of its range)
+        // (64 x 512 000 samples, windows of 256 / 1024 / 4096: ~250 workgroups measured best: 0.21 / 0.21 / 0.29 ms)
+        int fpw = std::max(4, std::min(64, (int)(((int64_t)n_fp * n_ct + 255) / 256)));
+        if (c->cfg.istft_fpw > 0) fpw = c->cfg.istft_fpw;
+        IstftFusedArgs fa{IstftArgs{q.stft, q.n_bins, q.n_frames, q.n_ch, q.W, q.window, tw, q.scale, nullptr, ct, fpw},
+                          q.frame_offset, q.n_frames_total, q.total_length, q.ld_out, q.out};
+        CHK(launch(c, "istft@fused", k_istft_fused<NN>, dim3((unsigned)((n_fp + fpw - 1) / fpw), (unsigned)n_ct),
+                   ct * Cfg<NN>::NT, lds, fa));
+    });
     return DS_OK;
 }
-
+// Every other power of two in [8, 16384]: the frames into the workspace, then the overlap-add.  ct neighbouring
+// channels per workgroup (runs of 8 ct bytes of the channel-fastest spectrogram) wherever more than one image fits;
+// DSPTOOLBOX_AMD_ISTFT_CT=1 keeps one channel per workgroup
+static int istft_frames_run(ds_ctx* c, const IstftCall& q) {
+    const float2* tw;
+    CHK(get_twiddles(c, q.nfft, &tw));
+    CHK(reserve(c, &c->ws, &c->ws_bytes, sizeof(float) * (size_t)q.n_ch * q.n_frames * q.W));
+    float* frames = (float*)c->ws;
+    IstftArgs a{q.stft, q.n_bins, q.n_frames, q.n_ch, q.W, q.window, tw, q.scale, frames};
+    DISPATCH_N(q.nfft, {
+        int ct = std::min<int>(stft_max_teams<NN>(), q.n_ch);
+        while (ct & (ct - 1)) ct &= ct - 1;
+        if (ct == 1 || c->cfg.istft_one_ch) {
+            CHK(launch(c, "istft@generic", k_istft<NN>, dim3((q.n_frames + 1) / 2, q.n_ch), Cfg<NN>::NT, Cfg<NN>::LDS_BYTES, a));
+        } else if constexpr (stft_max_teams<NN>() > 1) {
+            const int n_fp = (q.n_frames + 1) / 2, n_ct = (q.n_ch + ct - 1) / ct;
+            a.ct = ct;
+            a.fpw = std::max(1, std::min(16, (int)(((int64_t)n_fp * n_ct + 511) / 512)));
+            CHK(launch(c, "istft@ct", k_istft_ct<NN>, dim3((unsigned)((n_fp + a.fpw - 1) / a.fpw), (unsigned)n_ct),
+                       ct * Cfg<NN>::NT, (size_t)stft_ch_stride<NN>() * sizeof(float2) * ct, a));
+        }
+    });
+    return launch_ola(c, q, frames, true);
+}
+using IstftRunner = int (*)(ds_ctx*, const IstftCall&);
+// The kernel family of a checked call, in the order the routes were written down: the long-window classes, any
+// length, the fused kernels at 50 % overlap of full frames, the two-launch path.
+static IstftRunner istft_route(const ds_ctx* c, const IstftCall& q) {
+    const int nfft = q.nfft;
+    const bool fused = c->cfg.istft_fused, wave = c->cfg.istft_wave;
+    // (the spectrogram through a raw-buffer descriptor: below 4 GiB)
+    const bool spec_fits = (int64_t)q.n_bins * q.n_frames * q.n_ch * 8 < ((int64_t)1 << 32) - 16;
+    if (istftl::classes_of(nfft) && wave && fused && q.n_frames <= 65535 && (q.n_ch + 1) / 2 <= 65535 && spec_fits)
+        return istft_long_run;
+    if (!is_pow2(nfft) || nfft < kMinFft || nfft > kMaxFft) return istft_any_run;
+    const bool half = q.W == nfft && 2 * q.step == nfft && q.n_ch > 1 && fused;
+    // (the wave kernels' team count, min(16, n_ch) or at 2048 points min(4, n_ch), is > 1 wherever n_ch > 1)
+    if (half && wave && (nfft == 2048 || nfft == 1024 || nfft == 512 || nfft == 256) && spec_fits) return istft_wave_run;
+    if (half && nfft == 4096 && wave && q.total_length < ((int64_t)1 << 31) && spec_fits) return istft4k_run;
+    bool fuses = false;  // (its team count min(stft_max_teams, n_ch) is > 1 wherever stft_max_teams and n_ch are)
+    DISPATCH_N_OR(nfft, break, fuses = istft_fuses<NN>());
+    return half && fuses ? istft_fused_run : istft_frames_run;
+}
 extern "C" int ds_istft_dev(ds_ctx* c, const ds_c32* stft, int n_bins, int n_frames, int n_ch, int nfft,
                             int W, int step, int frame_offset, int n_frames_total, const float* window,
                             float scale, int64_t total_length, float* out, int64_t ld_out) {
-    if (!c || !stft || !window || !out) return fail(c, DS_ERR_ARG, "ds_istft: null argument");
-    if (n_bins <= 0 || n_frames <= 0 || n_ch <= 0 || W <= 0 || step <= 0 || step > W || frame_offset < 0 ||
-        n_frames_total < n_frames + frame_offset || total_length <= 0 || ld_out < total_length)
-        return fail(c, DS_ERR_ARG, "ds_istft: bad shape");
-    if (W > nfft) return fail(c, DS_ERR_ARG, "ds_istft: window longer than the FFT length");
-    // 8192 ... 262144 points: class transforms on the 4096-point register kernel, then the radix-R stage with the
-    // overlap-add fused where frames overlap by half (kernels_istft_long.hpp)
-    if (const int R = istftl::classes_of(nfft); R && c->cfg.istft_wave && c->cfg.istft_fused && n_frames <= 65535 &&
-                                                 (n_ch + 1) / 2 <= 65535 &&
-                                                 (int64_t)n_bins * n_frames * n_ch * 8 < ((int64_t)1 << 32) - 16) {
-        int lgR = 0;
-        while ((1 << lgR) < R) ++lgR;
-        CHK(ensure_table(c, &c->w4_tables, welch4096::host_tables));
-        float2** slot = &c->wl_tables[lgR - 1];
-        CHK(ensure_table(c, slot, [R](std::vector<float2>& h) { welchl::host_tables(R, h); }));
-        const int n_pc = (n_ch + 1) / 2, n_groups = (n_ch + 15) / 16;
-        // (fused: the class sequences of ALL frames at once, addressed through a raw-buffer descriptor: below 4 GB)
-        const bool fused = W == nfft && 2 * step == nfft && R <= 16 &&
-                           (int64_t)n_pc * n_frames * nfft * 8 < ((int64_t)1 << 32) - 16;
-        const int per = fused ? n_frames : istftl::frames_per_group(n_ch, nfft, n_frames);
-        float2* cq;
-        float* frames;
-        CHK(carve(c, &c->ws, &c->ws_bytes, [&](Carver& cv) {
-            cq = cv.take<float2>((size_t)n_pc * per * nfft);
-            frames = fused ? nullptr : cv.take<float>((size_t)n_ch * n_frames * W);
-        }));
-        istftl::Args a{(const float2*)stft, n_bins, n_frames, n_ch, W, step, 1, n_groups, R, lgR, 0, n_frames, window,
-                       c->w4_tables, *slot, scale, cq, frames, frame_offset, n_frames_total, total_length, ld_out, out};
-        for (int f0 = 0; f0 < n_frames; f0 += per) {
-            a.f0 = f0;
-            a.nf = std::min(per, n_frames - f0);
-            const int n_units = a.nf * (R - 1);
-            a.n_chunks = std::max(1, std::min(n_units, 256 / std::max(1, std::min(256, n_groups))));
-            const dim3 gc((unsigned)stft4k::grid_size(n_groups, a.n_chunks));
-            CHK((n_ch & 1) ? launch(c, "istft_long_cls", istftl::k_icls<false>, gc, istftl::NT, istftl::LDS_BYTES, a)
-                           : launch(c, "istft_long_cls", istftl::k_icls<true>, gc, istftl::NT, istftl::LDS_BYTES, a));
-            if (fused) break;
-            const dim3 gd(16, (unsigned)a.nf, (unsigned)n_pc);
-            switch (R) {
-                case 2: CHK(launch(c, "istft@long", istftl::k_isdif_frames<2>, gd, 256, istftl::xch_bytes(2), a)); break;
-                case 4: CHK(launch(c, "istft@long", istftl::k_isdif_frames<4>, gd, 256, istftl::xch_bytes(4), a)); break;
-                case 8: CHK(launch(c, "istft@long", istftl::k_isdif_frames<8>, gd, 256, istftl::xch_bytes(8), a)); break;
-                case 16: CHK(launch(c, "istft@long", istftl::k_isdif_frames<16>, gd, 256, istftl::xch_bytes(16), a)); break;
-                case 32: CHK(launch(c, "istft@long", istftl::k_isdif_frames<32>, gd, 256, istftl::xch_bytes(32), a)); break;
-                default: CHK(launch(c, "istft@long", istftl::k_isdif_frames<64>, gd, 256, istftl::xch_bytes(64), a)); break;
-            }
-        }
-        if (fused) {
-            // chunks of frames (+ 1 frame each for the carry): 8192 workgroups of 256 threads where the frames allow
-            // (a thread has only R loads in flight), at least 4 frames per chunk
-            const int want = std::max(1, 8192 / std::max(1, 16 * n_pc));
-            a.n_chunks = std::max(1, std::min((n_frames + 3) / 4, want));
-            if (c->cfg.istft_fpw > 0) a.n_chunks = std::min(n_frames, c->cfg.istft_fpw);
-            const dim3 gd(16, (unsigned)a.n_chunks, (unsigned)n_pc);
-            switch (R) {
-                case 2: return launch(c, "istft@long_ola", istftl::k_isdif_ola<2>, gd, 256, istftl::xch_bytes(2), a);
-                case 4: return launch(c, "istft@long_ola", istftl::k_isdif_ola<4>, gd, 256, istftl::xch_bytes(4), a);
-                case 8: return launch(c, "istft@long_ola", istftl::k_isdif_ola<8>, gd, 256, istftl::xch_bytes(8), a);
-                default: return launch(c, "istft@long_ola", istftl::k_isdif_ola<16>, gd, 256, istftl::xch_bytes(16), a);
-            }
-        }
-        IstftOlaArgs o{frames, n_frames, n_ch, W, step, frame_offset, n_frames_total, window, total_length, ld_out, out};
-        if (W % 4 == 0 && step % 4 == 0 && total_length % 4 == 0 && ld_out % 4 == 0 && ((uintptr_t)out & 15) == 0 &&
-            ((uintptr_t)window & 15) == 0)
-            return launch(c, "istft_ola", k_istft_ola4, dim3((unsigned)((total_length / 4 + 255) / 256), n_ch), 256, 0, o);
-        return launch(c, "istft_ola", k_istft_ola, dim3((unsigned)((total_length + 255) / 256), n_ch), 256, 0, o);
-    }
-    if (!is_pow2(nfft) || nfft < kMinFft || nfft > kMaxFft) {
-        // (ws, io and aux are all taken -- the division's scratch, the host entry point's staging, the
-        // per-group spectra -- so the frames live in a fourth context-owned reserve: grown on demand like
-        // the others, no allocation, synchronisation or free per call; this route is correct, not tuned)
-        CHK(reserve(c, &c->frames, &c->frames_bytes, sizeof(float) * (size_t)n_ch * n_frames * W));
-        float* frames = (float*)c->frames;
-        CHK(istft_any_frames(c, (const float2*)stft, n_bins, n_frames, n_ch, nfft, W, window, scale, frames));
-        IstftOlaArgs o{frames, n_frames, n_ch, W, step, frame_offset, n_frames_total, window, total_length, ld_out, out};
-        return launch(c, "istft_ola", k_istft_ola, dim3((unsigned)((total_length + 255) / 256), n_ch), 256, 0, o);
-    }
-    CHK(check_fft_len(c, nfft, "ds_istft nfft"));
-    const float2* tw;
-    CHK(get_twiddles(c, nfft, &tw));
-    // 50 % overlap of full-length frames: transform and overlap-add in one kernel, no frames in memory
-    const bool no_fuse = !c->cfg.istft_fused;
-    // ... on the wave-level transform for 256 ... 2048 points (kernels_stft1024.hpp, k_istft_wave)
-    const bool no_wave = !c->cfg.istft_wave;
-    if (W == nfft && 2 * step == nfft && n_ch > 1 && !no_fuse && !no_wave &&
-        (nfft == 2048 || nfft == 1024 || nfft == 512 || nfft == 256) &&
-        (int64_t)n_bins * n_frames * n_ch * 8 < ((int64_t)1 << 32) - 16) {
-        // (2048 points: 45 registers over the 128 of a 1024-thread workgroup: four teams = 512 threads there)
-        const int slot = nfft == 1024 ? 0 : (nfft == 512 ? 1 : (nfft == 256 ? 2 : 3));
-        float2** tab = slot == 0 ? &c->stft1k_tables : &c->stft_wave_tables[slot - 1];
-        CHK(ensure_table(c, tab, [nfft](std::vector<float2>& h) {
-            if (nfft == 2048) stft1k::host_tables<2048>(h);
-            else if (nfft == 1024) stft1k::host_tables<1024>(h);
-            else if (nfft == 512) stft1k::host_tables<512>(h);
-            else stft1k::host_tables<256>(h);
-        }));
-        const int lanes = nfft / 16;
-        int ct = std::min(nfft == 2048 ? 4 : 16, n_ch);
-        while (ct & (ct - 1)) ct &= ct - 1;
-        if (ct > 1) {
-            const size_t lds = nfft == 2048 ? stft1k::istft_lds_bytes<2048>(ct) : nfft == 1024 ? stft1k::istft_lds_bytes<1024>(ct)
-                                            : (nfft == 512 ? stft1k::istft_lds_bytes<512>(ct) : stft1k::istft_lds_bytes<256>(ct));
-            const int threads = lanes * ct;
-            const int n_fp = (n_frames + 1) / 2, n_ct = (n_ch + ct - 1) / ct;
-            const int per_cu = std::max(1, std::min<int>((int)((160 * 1024) / lds), 2048 / std::max(64, threads)));
-            // frame pairs per workgroup (+ 1 for the carry): two rounds of resident workgroups, at least 4 (1024 points: 8)
-            // -- 64 x 512 000 samples: 0.154 / 0.130 / 0.135 ms at 256 / 512 / 1024 points, 0.18 / 0.13 / 0.145 one step off
-            int fpw = std::max(nfft >= 1024 ? 8 : 4, std::min(64, (int)(((int64_t)n_fp * n_ct + 512 * per_cu - 1) / (512 * per_cu))));
-            if (c->cfg.istft_fpw > 0) fpw = c->cfg.istft_fpw;
-            IstftFusedArgs fa{IstftArgs{(const float2*)stft, n_bins, n_frames, n_ch, W, window, *tab, scale, nullptr, ct, fpw},
-                              frame_offset, n_frames_total, total_length, ld_out, out};
-            const dim3 grid((unsigned)((n_fp + fpw - 1) / fpw), (unsigned)n_ct);
-            if (nfft == 2048) return launch(c, "istft@wave", stft1k::k_istft_wave<2048>, grid, threads, lds, fa);
-            if (nfft == 1024) return launch(c, "istft@wave", stft1k::k_istft_wave<1024>, grid, threads, lds, fa);
-            if (nfft == 512) return launch(c, "istft@wave", stft1k::k_istft_wave<512>, grid, threads, lds, fa);
-            return launch(c, "istft@wave", stft1k::k_istft_wave<256>, grid, threads, lds, fa);
-        }
-    }
-    // ... and on the 4096-point register transform, two neighbouring channels per team (kernels_stft4096.hpp, k_istft)
-    if (W == nfft && nfft == 4096 && 2 * step == nfft && n_ch > 1 && !no_fuse && !no_wave &&
-        total_length < ((int64_t)1 << 31) && (int64_t)n_bins * n_frames * n_ch * 8 < ((int64_t)1 << 32) - 16) {
-        CHK(ensure_table(c, &c->w4_tables, welch4096::host_tables));
-        const int n_groups = (n_ch + 15) / 16;
-        // chunks of frames (+ 1 frame each for the carry): two rounds of one workgroup (8 channels) per CU
-        int n_chunks = std::max(1, std::min((n_frames + 3) / 4, 256 / std::max(1, std::min(256, n_groups))));
-        if (c->cfg.istft_fpw > 0) n_chunks = std::min(n_frames, c->cfg.istft_fpw);
-        IstftFusedArgs fa{IstftArgs{(const float2*)stft, n_bins, n_frames, n_ch, W, window, c->w4_tables, scale, nullptr, 1, n_chunks},
-                          frame_offset, n_frames_total, total_length, ld_out, out};
-        const dim3 g4((unsigned)stft4k::grid_size(n_groups, n_chunks));
-        return (n_ch & 1) ? launch(c, "istft@4k", stft4k::k_istft<false>, g4, stft4k::NT, stft4k::ISTFT_LDS_BYTES, fa)
-                          : launch(c, "istft@4k", stft4k::k_istft<true>, g4, stft4k::NT, stft4k::ISTFT_LDS_BYTES, fa);
-    }
-    if (W == nfft && 2 * step == nfft && n_ch > 1 && !no_fuse) {
-        int ct = 1;
-        size_t lds = 0;
-        int threads = 0, nt = 64;
-        DISPATCH_N(nfft, {
-            ct = std::min<int>(stft_max_teams<NN>(), n_ch);
-            while (ct & (ct - 1)) ct &= ct - 1;
-            lds = (size_t)stft_ch_stride<NN>() * sizeof(float2) * ct + sizeof(float) * (size_t)(NN / 2);  // + 1 / envelope
-            threads = ct * Cfg<NN>::NT;
-            nt = Cfg<NN>::NT;
-        });
-        if (ct > 1 && nfft % (2 * nt) == 0) {
-            const int n_fp = (n_frames + 1) / 2, n_ct = (n_ch + ct - 1) / ct;
-            // frame pairs per workgroup: every workgroup transforms one more pair (the carry in front of its range)
-            // (64 x 512 000 samples, windows of 256 / 1024 / 4096: ~250 workgroups measured best: 0.21 / 0.21 / 0.29 ms)
-            int fpw = std::max(4, std::min(64, (int)(((int64_t)n_fp * n_ct + 255) / 256)));
-            if (c->cfg.istft_fpw > 0) fpw = c->cfg.istft_fpw;
-            IstftFusedArgs fa{IstftArgs{(const float2*)stft, n_bins, n_frames, n_ch, W, window, tw, scale, nullptr, ct, fpw},
-                              frame_offset, n_frames_total, total_length, ld_out, out};
-            DISPATCH_N(nfft, {
-                if constexpr (stft_max_teams<NN>() > 1 && NN % (2 * Cfg<NN>::NT) == 0)  // (ct > 1 never holds otherwise)
-                    CHK(launch(c, "istft@fused", k_istft_fused<NN>, dim3((unsigned)((n_fp + fpw - 1) / fpw), (unsigned)n_ct),
-                               threads, lds, fa));
-            });
-            return DS_OK;
-        }
-    }
-    CHK(reserve(c, &c->ws, &c->ws_bytes, sizeof(float) * (size_t)n_ch * n_frames * W));
-    float* frames = (float*)c->ws;
-    IstftArgs a{(const float2*)stft, n_bins, n_frames, n_ch, W, window, tw, scale, frames};
-    // ct neighbouring channels per workgroup (runs of 8 ct bytes of the channel-fastest spectrogram) wherever more
-    // than one image fits; DSPTOOLBOX_AMD_ISTFT_CT=1 keeps one channel per workgroup
-    const bool one_ch = c->cfg.istft_one_ch;
-    int ct = 1;
-    size_t lds = 0;
-    int threads = 0;
-    DISPATCH_N(nfft, {
-        ct = std::min<int>(stft_max_teams<NN>(), n_ch);
-        while (ct & (ct - 1)) ct &= ct - 1;
-        lds = (size_t)stft_ch_stride<NN>() * sizeof(float2) * ct;
-        threads = ct * Cfg<NN>::NT;
-    });
-    if (ct > 1 && !one_ch) {
-        const int n_fp = (n_frames + 1) / 2, n_ct = (n_ch + ct - 1) / ct;
-        a.ct = ct;
-        a.fpw = std::max(1, std::min(16, (int)(((int64_t)n_fp * n_ct + 511) / 512)));
-        DISPATCH_N(nfft, {
-            if constexpr (stft_max_teams<NN>() > 1)
-                CHK(launch(c, "istft@ct", k_istft_ct<NN>, dim3((unsigned)((n_fp + a.fpw - 1) / a.fpw), (unsigned)n_ct), threads,
-                           lds, a));
-        });
-    } else {
-        DISPATCH_N(nfft, CHK(launch(c, "istft@generic", k_istft<NN>, dim3((n_frames + 1) / 2, n_ch), Cfg<NN>::NT,
-                                    Cfg<NN>::LDS_BYTES, a)));
-    }
-    IstftOlaArgs o{frames, n_frames, n_ch, W, step, frame_offset, n_frames_total, window, total_length, ld_out, out};
-    // four samples per thread where every row and frame boundary is a multiple of four samples (and 16-byte aligned)
-    if (W % 4 == 0 && step % 4 == 0 && total_length % 4 == 0 && ld_out % 4 == 0 && ((uintptr_t)out & 15) == 0 &&
-        ((uintptr_t)window & 15) == 0)
-        CHK(launch(c, "istft_ola", k_istft_ola4, dim3((unsigned)((total_length / 4 + 255) / 256), n_ch), 256, 0, o));
-    else
-        CHK(launch(c, "istft_ola", k_istft_ola, dim3((unsigned)((total_length + 255) / 256), n_ch), 256, 0, o));
-    return DS_OK;
+    const IstftCall q{"ds_istft_dev", (const float2*)stft, n_bins, n_frames, n_ch, nfft, W, step, frame_offset,
+                      n_frames_total, window, scale, total_length, out, ld_out};
+    CHK(istft_check(c, q));
+    return istft_route(c, q)(c, q);
 }
 
 // ---- band powers of a spectrogram (mel spectrogram / MFCC) ----------------------------------
@@ -1398,11 +1417,9 @@ static int welch_long_run(ds_ctx* c, int kind, const float* x, int n_cx, int64_t
     namespace wl = welchl;
     const bool auto_only = kind == 1;
     const int R = wl::classes_of(W);
-    int lgR = 0;
-    while ((1 << lgR) < R) ++lgR;
-    CHK(ensure_table(c, &c->w4_tables, welch4096::host_tables));
-    float2** slot = &c->wl_tables[lgR - 1];
-    CHK(ensure_table(c, slot, [R](std::vector<float2>& h) { wl::host_tables(R, h); }));
+    int lgR;
+    const float2* twl;
+    CHK(long_tables(c, R, &lgR, &twl));
     const int nf = frames_to_visit(n_samples, hop, n_frames), nb = W / 2 + 1;
     const int n_out = auto_only ? n_cx : n_cy;  // channels that are accumulated
     wl::Plan pl = wl::plan(nf, n_out, R);
@@ -1420,17 +1437,11 @@ static int welch_long_run(ds_ctx* c, int kind, const float* x, int n_cx, int64_t
         pyy = cv.take<float>((size_t)pl.n_chunks * n_out * nb);
         pu = cv.take<float>((size_t)pl.n_chunks * n_out * W);
     }));
-    wl::Args ax{x, n_samples, ldx, n_cx, hop, nf, pl.n_pairs, detrend, pl.n_chunks, R, lgR, window, c->w4_tables, *slot,
+    wl::Args ax{x, n_samples, ldx, n_cx, hop, nf, pl.n_pairs, detrend, pl.n_chunks, R, lgR, window, c->w4_tables, twl,
                 bx, (float4*)xs, pxu, pxy, pyy, psx, n_cx, tu, pu};
     auto dif = [&](const wl::Args& a, int n_ch) {
         const dim3 grid(wl::M / wl::NT, pl.n_pairs, n_ch);
-        switch (R) {
-            case 4: return launch(c, "welch_long_dif", wl::k_dif<4>, grid, wl::NT, 0, a);
-            case 8: return launch(c, "welch_long_dif", wl::k_dif<8>, grid, wl::NT, 0, a);
-            case 16: return launch(c, "welch_long_dif", wl::k_dif<16>, grid, wl::NT, 0, a);
-            case 32: return launch(c, "welch_long_dif", wl::k_dif<32>, grid, wl::NT, 0, a);
-            default: return launch(c, "welch_long_dif", wl::k_dif<64>, grid, wl::NT, 0, a);
-        }
+        return dispatch<4, 8, 16, 32, 64>(R, [&](auto r) { return launch(c, "welch_long_dif", wl::k_dif<r.value>, grid, wl::NT, 0, a); });
     };
     CHK(dif(ax, n_cx));
     const dim3 fold_grid((nb + 255) / 256, pl.n_chunks * n_out);
@@ -1457,15 +1468,6 @@ static int welch_long_run(ds_ctx* c, int kind, const float* x, int n_cx, int64_t
     WelchFinArgs f{psx, pxy, pyy, pl.n_chunks, pl.n_chunks, n_cx, n_cy, kind, mode,
                    FinishPar{norm_scale / (double)n_frames, factor, halve_edges, amp_sqrt, nb}, out_c, out_r};
     return launch_finish(c, f);
-}
-
-// twiddle tables of the wave-level transforms (stft1k::host_tables<N>), cached per context
-template <int NN>
-static int wave_tables(ds_ctx* c, const float2** out) {
-    float2** tab = NN == 1024 ? &c->stft1k_tables : &c->stft_wave_tables[NN == 512 ? 0 : (NN == 256 ? 1 : 2)];
-    CHK(ensure_table(c, tab, stft1k::host_tables<NN>));
-    *out = *tab;
-    return DS_OK;
 }
 
 // windows of 256 / 512 / 1024 / 2048 samples (1024 = the reference's default): wave-level register transforms
@@ -2933,23 +2935,22 @@ static int upload_signal(ds_ctx* c, const float* x, const double* x64, int64_t n
 static int stft_host(ds_ctx* c, const char* who, const float* x, const double* x64, int64_t n_samples, int n_ch, int W,
                      int hop, int nfft, int64_t pad_front, int n_frames, const float* window, int detrend, float scale,
                      float edge_scale, int power, ds_c32* out, double* out64) {
-    if (!c || (!x && !x64) || !window || (!out && !out64)) return fail(c, DS_ERR_ARG, std::string(who) + ": null argument");
-    if (n_ch <= 0 || n_samples <= 0 || W <= 0 || n_frames <= 0 || nfft <= 0)
-        return fail(c, DS_ERR_ARG, std::string(who) + ": bad shape");
+    // (the host pointers, only checked: the staged copies replace them below)
+    StftCall s{who, x ? x : (const float*)x64, n_samples, n_ch, n_samples, W, hop, nfft, pad_front, n_frames, window,
+               detrend, scale, edge_scale, power, out ? (float2*)out : (float2*)out64};
+    CHK(stft_check(c, s));
     const size_t no = (size_t)(nfft / 2 + 1) * n_frames * n_ch;
     float *dx, *dw;
-    float2* dout;
     CHK(carve(c, &c->io, &c->io_bytes, [&](Carver& cv) {
-        dx = cv.take<float>((size_t)n_ch * n_samples);
-        dw = cv.take<float>(W);
-        dout = cv.take<float2>(no);
+        s.x = dx = cv.take<float>((size_t)n_ch * n_samples);
+        s.window = dw = cv.take<float>(W);
+        s.out = cv.take<float2>(no);
     }));
     CHK(upload_signal(c, x, x64, n_samples, n_ch, dx));
     CHK(ds_upload(c, dw, window, (size_t)W * 4));
-    CHK(ds_stft_r2c_dev(c, dx, n_samples, n_ch, n_samples, W, hop, nfft, pad_front, n_frames, dw, detrend,
-                        scale, edge_scale, power, (ds_c32*)dout));
-    if (out64) return download_widen(c, (const float*)dout, (int64_t)no * 2, out64);
-    return ds_download(c, out, dout, no * 8);
+    CHK(stft_route(c, s)(c, s));
+    if (out64) return download_widen(c, (const float*)s.out, (int64_t)no * 2, out64);
+    return ds_download(c, out, s.out, no * 8);
 }
 extern "C" int ds_stft_r2c(ds_ctx* c, const float* x, int64_t n_samples, int n_ch, int W, int hop,
                            int nfft, int64_t pad_front, int n_frames, const float* window, int detrend,
@@ -2971,27 +2972,23 @@ extern "C" int ds_stft_r2c_f64(ds_ctx* c, const double* x, int64_t n_samples, in
 static int istft_host(ds_ctx* c, const char* who, const ds_c32* stft, const double* stft64, int n_bins, int n_frames,
                       int n_ch, int nfft, int W, int step, int frame_offset, int n_frames_total, const float* window,
                       float scale, int64_t total_length, float* out, double* out64) {
-    if (!c || (!stft && !stft64) || !window || (!out && !out64))
-        return fail(c, DS_ERR_ARG, std::string(who) + ": null argument");
-    if (n_bins <= 0 || n_frames <= 0 || n_ch <= 0 || W <= 0 || total_length <= 0)
-        return fail(c, DS_ERR_ARG, std::string(who) + ": bad shape");
+    // (the host pointers, only checked: the staged copies replace them below)
+    IstftCall q{who, stft ? (const float2*)stft : (const float2*)stft64, n_bins, n_frames, n_ch, nfft, W, step,
+                frame_offset, n_frames_total, window, scale, total_length, out ? out : (float*)out64, total_length};
+    CHK(istft_check(c, q));
     const size_t ns = (size_t)n_bins * n_frames * n_ch, no = (size_t)n_ch * total_length;
     float2* ds;
-    float *dw, *dout;
+    float* dw;
     CHK(carve(c, &c->io, &c->io_bytes, [&](Carver& cv) {
-        ds = cv.take<float2>(ns);
-        dw = cv.take<float>(W);
-        dout = cv.take<float>(no);
+        q.stft = ds = cv.take<float2>(ns);
+        q.window = dw = cv.take<float>(W);
+        q.out = cv.take<float>(no);
     }));
-    if (stft64)
-        CHK(upload_narrow_f64(c, stft64, (int64_t)ns * 2, (float*)ds));
-    else
-        CHK(ds_upload(c, ds, stft, ns * 8));
+    CHK(stft64 ? upload_narrow_f64(c, stft64, (int64_t)ns * 2, (float*)ds) : ds_upload(c, ds, stft, ns * 8));
     CHK(ds_upload(c, dw, window, (size_t)W * 4));
-    CHK(ds_istft_dev(c, (const ds_c32*)ds, n_bins, n_frames, n_ch, nfft, W, step, frame_offset, n_frames_total,
-                     dw, scale, total_length, dout, total_length));
-    if (out64) return download_interleave(c, dout, total_length, n_ch, total_length, out64);
-    return ds_download(c, out, dout, no * 4);
+    CHK(istft_route(c, q)(c, q));
+    if (out64) return download_interleave(c, q.out, total_length, n_ch, total_length, out64);
+    return ds_download(c, out, q.out, no * 4);
 }
 extern "C" int ds_istft(ds_ctx* c, const ds_c32* stft, int n_bins, int n_frames, int n_ch, int nfft, int W,
                         int step, int frame_offset, int n_frames_total, const float* window, float scale,

@@ -2702,6 +2702,141 @@ def test_welch_routes_per_window(switch, kind, W, monkeypatch):
     assert seen == want
 
 
+# ---- which kernel family each STFT / iSTFT length runs on, per entry point (tests/golden/stft_routes.json) ----------
+# Keys "<switch>|stft|<nfft>|<window>|<detrend>|<channels>" and "<switch>|istft|<nfft>|<window>|<step divisor>|<channels>"
+# (window: "full" = nfft samples, "short" = 3 nfft / 4); the launch names were recorded through the same helpers on the
+# library before the STFT and iSTFT dispatch became one route choice each (csrc/api.hip, stft_route / istft_route).
+STFT_ROUTE_SWITCHES = {"default": {}, "STFT_GENERIC": {"DSPTOOLBOX_AMD_STFT_GENERIC": "1"}}
+STFT_ROUTE_NFFTS = [8, 16, 32, 64, 128, 256, 512, 1000, 1024, 2048, 4096, 8192, 16384, 32768, 262144, 2**19, 2**20]
+ISTFT_ROUTE_SWITCHES = {"default": {}, "ISTFT_FUSED=0": {"DSPTOOLBOX_AMD_ISTFT_FUSED": "0"},
+                        "ISTFT_WAVE=0": {"DSPTOOLBOX_AMD_ISTFT_WAVE": "0"}, "ISTFT_CT=1": {"DSPTOOLBOX_AMD_ISTFT_CT": "1"}}
+ISTFT_ROUTE_NFFTS = [16, 256, 1000, 1024, 2048, 4096, 8192, 16384, 32768, 2**19]
+STFT_ROUTE_ENTRIES = {"stft": ("stft", "stft_f64", "stft_dev"), "istft": ("istft", "istft_f64", "istft_dev")}
+
+
+def _route_call(ctx, fn, args):
+    """(launch names) of one C-ABI call, or ["ERR<code>"] where the call returns an error."""
+    rc = fn(ctx.handle, *args)
+    return sorted(ctx.routes()) if rc == 0 else [f"ERR{rc}"]
+
+
+def _stft_route_case(entry, nfft, short, detrend, n_ch, power=0):
+    """One short spectrogram through one C-ABI entry point -> (output array, launch names)."""
+    import ctypes as C
+    from dsptoolbox_amd._lib import DeviceBuffer, DevicePlanar, get_context
+    ctx = get_context()
+    p = lambda a: a.ctypes.data_as(C.c_void_p)
+    W = 3 * nfft // 4 if short else nfft
+    hop, n = W // 2, 2 * nfft + 3000
+    n_frames, B = 1 + (n - W) // hop, nfft // 2 + 1
+    rng = np.random.default_rng(nfft + n_ch)
+    x = rng.standard_normal((n, n_ch)) * 0.5 + 0.25
+    xp = np.ascontiguousarray(x.T, dtype=np.float32)
+    w = (0.5 - 0.5 * np.cos(2 * np.pi * np.arange(W) / W)).astype(np.float32)
+    tail = (nfft, 0, n_frames)
+    par = (int(detrend), C.c_float(1.0 / W), C.c_float(0.5), power)
+    ctx.routes()
+    if entry.endswith("_dev"):
+        dx, dw, do = DevicePlanar.from_planar(ctx, xp), DeviceBuffer.from_array(ctx, w), DeviceBuffer(ctx, B * n_frames * n_ch * 8)
+        routes = _route_call(ctx, ctx.lib.ds_stft_r2c_dev, (C.c_void_p(dx.ptr), n, n_ch, dx.ld, W, hop, *tail,
+                                                            C.c_void_p(dw.ptr), *par, C.c_void_p(do.ptr)))
+        out = do.to_array((B, n_frames, n_ch), np.complex64)
+        for b in (dx.owner, dw, do):
+            b.free()
+        return out, routes
+    f64 = entry.endswith("_f64")
+    out = np.zeros((B, n_frames, n_ch), np.complex128 if f64 else np.complex64)
+    fn = ctx.lib.ds_stft_r2c_f64 if f64 else ctx.lib.ds_stft_r2c
+    routes = _route_call(ctx, fn, (p(np.ascontiguousarray(x) if f64 else xp), n, n_ch, W, hop, *tail, p(w), *par, p(out)))
+    return out, routes
+
+
+def _istft_route_case(entry, nfft, short, step_div, n_ch):
+    """One short inverse transform through one C-ABI entry point -> (output array, launch names).  Three channels
+    give an odd output length: the one-sample overlap-add kernel as well as the four-sample one."""
+    import ctypes as C
+    from dsptoolbox_amd._lib import DeviceBuffer, get_context
+    ctx = get_context()
+    p = lambda a: a.ctypes.data_as(C.c_void_p)
+    W = 3 * nfft // 4 if short else nfft
+    step, total = nfft // step_div, 2 * nfft + 3000 + (n_ch == 3)
+    n_frames, B = 1 + (total - W) // step, nfft // 2 + 1
+    rng = np.random.default_rng(nfft + 10 * step_div + n_ch)
+    spec = rng.standard_normal((B, n_frames, n_ch)) + 1j * rng.standard_normal((B, n_frames, n_ch))
+    w = (0.5 - 0.5 * np.cos(2 * np.pi * np.arange(W) / W)).astype(np.float32)
+    mid = (n_ch, nfft, W, step, 0, n_frames)
+    ctx.routes()
+    if entry.endswith("_dev"):
+        ds, dw = DeviceBuffer.from_array(ctx, spec.astype(np.complex64)), DeviceBuffer.from_array(ctx, w)
+        do = DeviceBuffer(ctx, n_ch * total * 4)
+        routes = _route_call(ctx, ctx.lib.ds_istft_dev, (C.c_void_p(ds.ptr), B, n_frames, *mid, C.c_void_p(dw.ptr),
+                                                         C.c_float(1.0 / nfft), total, C.c_void_p(do.ptr), total))
+        out = do.to_array((n_ch, total), np.float32)
+        for b in (ds, dw, do):
+            b.free()
+        return out, routes
+    f64 = entry.endswith("_f64")
+    s = np.ascontiguousarray(spec.astype(np.complex128 if f64 else np.complex64))
+    out = np.zeros((total, n_ch) if f64 else (n_ch, total), np.float64 if f64 else np.float32)
+    fn = ctx.lib.ds_istft_f64 if f64 else ctx.lib.ds_istft
+    routes = _route_call(ctx, fn, (p(s), B, n_frames, *mid, p(w), C.c_float(1.0 / nfft), total, p(out)))
+    return out, routes
+
+
+def _stft_route_matrix(kind, nffts, on_case=None, power=0):
+    """{key: sorted launch names} of every case of the STFT (kind "stft") or iSTFT ("istft") matrix under the current
+    context's switches."""
+    seen = {}
+    for nfft in nffts:
+        for short in (False, True):
+            for a in ((False, True) if kind == "stft" else (2, 4)):  # detrend / step divisor
+                for n_ch in ((1, 3) if kind == "stft" else (1, 2, 3)):
+                    for entry in STFT_ROUTE_ENTRIES[kind]:
+                        if kind == "stft":
+                            out, routes = _stft_route_case(entry, nfft, short, a, n_ch, power)
+                        else:
+                            out, routes = _istft_route_case(entry, nfft, short, a, n_ch)
+                        key = f"{entry}|{nfft}|{'short' if short else 'full'}|{int(a)}|{n_ch}"
+                        seen[key] = routes
+                        if on_case:
+                            on_case(key, out)
+    return seen
+
+
+def _stft_routes_vs_table(kind, switches, switch, nfft, monkeypatch):
+    import json
+    from dsptoolbox_amd import _lib
+    with open(os.path.join(ROOT, "tests", "golden", "stft_routes.json")) as fh:
+        table = json.load(fh)
+    for k, v in switches[switch].items():
+        monkeypatch.setenv(k, v)
+    _lib.reset_context()
+    try:
+        seen = _stft_route_matrix(kind, (nfft,))
+    finally:
+        for k in switches[switch]:
+            monkeypatch.delenv(k, raising=False)
+        _lib.reset_context()
+    # (every entry point of a kind runs the same kernels: the table has one row per kind)
+    want = {k: table[f"{switch}|{kind}|{k.split('|', 1)[1]}"].split() for k in seen}
+    assert seen == want
+
+
+@pytest.mark.parametrize("nfft", STFT_ROUTE_NFFTS)
+@pytest.mark.parametrize("switch", list(STFT_ROUTE_SWITCHES))
+def test_stft_routes_per_length(switch, nfft, monkeypatch):
+    """Each (length, window, detrend, channel count) of every STFT entry point launches the kernels it launched when
+    the table was recorded: a change of route is a change of the rounding of every spectrogram that takes it."""
+    _stft_routes_vs_table("stft", STFT_ROUTE_SWITCHES, switch, nfft, monkeypatch)
+
+
+@pytest.mark.parametrize("nfft", ISTFT_ROUTE_NFFTS)
+@pytest.mark.parametrize("switch", list(ISTFT_ROUTE_SWITCHES))
+def test_istft_routes_per_length(switch, nfft, monkeypatch):
+    """The same for every (length, window, step, channel count) of every inverse STFT entry point."""
+    _stft_routes_vs_table("istft", ISTFT_ROUTE_SWITCHES, switch, nfft, monkeypatch)
+
+
 @pytest.mark.parametrize("route", SWITCH_ROUTES, ids=lambda r: ",".join(f"{k.replace('DSPTOOLBOX_AMD_', '')}={v}"
                                                                         for k, v in r[0].items()) or "default")
 def test_kernel_selecting_switches(route, monkeypatch):
