@@ -26,6 +26,7 @@ NO_SCRATCH = [
     "k_bf_eigh", "k_bf_project", "k_bf_cleansc",
     "k_iir_group", "k_iir_carry", "k_iir_apply",
     "k_delay_sum",
+    "k_cwt_inv", "k_cwt_squeeze",
 ]
 
 

@@ -1458,3 +1458,93 @@ def stack_device(planars, lengths) -> DevicePlanar:
         buf.free()
         raise
     return DevicePlanar(buf, len(planars), n_max, n_max)
+
+
+# ---- continuous wavelet transform (ds_cwt, ds_cwt_dev, ds_cwt_squeeze_dev; csrc/kernels_cwt.hpp) ------------------
+CWT_MAX_TAPS = 1 << 18  # the kernels' limit (DS_ERR_UNSUP above)
+
+
+class DeviceScalogram:
+    """A scalogram that stays in HBM: (frequencies, samples, channels) in `buf`, complex64 as ds_cwt_dev writes it or
+    complex128 after ds_cwt_squeeze_dev.  What `transforms.cwt(on_device=True)` returns; `to_host()` gives the
+    reference's complex128 array."""
+
+    def __init__(self, buf: DeviceBuffer, shape, dtype):
+        self.buf, self.shape, self.dtype = buf, tuple(int(v) for v in shape), np.dtype(dtype)
+
+    def to_host(self) -> np.ndarray:
+        if self.dtype == np.complex128:
+            return self.buf.to_array(self.shape, np.complex128)
+        return DeviceSTFT(self.buf, self.shape, False).to_host()
+
+    def __deepcopy__(self, memo):
+        return self
+
+
+def _cwt_taps(waves):
+    """The normalised float64 wavelets -> (tap lengths int64, all taps back to back as complex64).  Raises
+    NotImplementedError for a wavelet beyond CWT_MAX_TAPS before anything reaches the device."""
+    lens = np.array([len(w) for w in waves], dtype=np.int64)
+    if lens.size and lens.max() > CWT_MAX_TAPS:
+        raise NotImplementedError(f"cwt: wavelets longer than {CWT_MAX_TAPS} taps are not built "
+                                  f"(the longest here has {int(lens.max())})")
+    if lens.size and lens.min() < 1:
+        raise ValueError("cwt: a wavelet has no taps")
+    taps = np.ascontiguousarray(np.concatenate([np.asarray(w).ravel() for w in waves]).astype(np.complex64))
+    return lens, taps
+
+
+def cwt_host(td: np.ndarray, waves) -> np.ndarray:
+    """The scalogram (F, N, C) complex128 of td (N, C) float64 with the normalised wavelets (ds_cwt: fp32 kernels,
+    the result widened on the way down)."""
+    lens, taps = _cwt_taps(waves)
+    xa = np.ascontiguousarray(np.asarray(td, dtype=np.float64))
+    n, n_ch = xa.shape
+    out = np.empty((len(waves), n, n_ch), dtype=np.complex128)
+    ctx = get_context()
+    ctx.check(ctx.lib.ds_cwt(ctx.handle, _ptr(xa), n_ch, n, len(waves), _ptr(lens), _ptr(taps), 1, _ptr(out)),
+              "ds_cwt")
+    return out
+
+
+def cwt_device(x_dev: DevicePlanar, channels, waves) -> DeviceScalogram:
+    """The scalogram of the channels `channels` of device-resident planar float32 samples (ds_cwt_dev), left in HBM
+    as complex64 (F, N, len(channels))."""
+    lens, taps = _cwt_taps(waves)
+    ch = np.ascontiguousarray(np.asarray(channels, dtype=np.int32).ravel())
+    n = x_dev.n_samples
+    ctx = x_dev.ctx
+    buf = DeviceBuffer(ctx, max(8 * len(waves) * n * len(ch), 8))
+    try:
+        ctx.check(ctx.lib.ds_cwt_dev(ctx.handle, C.c_void_p(x_dev.ptr), x_dev.n_ch, x_dev.ld, n, _ptr(ch), len(ch),
+                                     len(waves), _ptr(lens), _ptr(taps), C.c_void_p(buf.ptr)), "ds_cwt_dev")
+    except BaseException:
+        buf.free()
+        raise
+    return DeviceScalogram(buf, (len(waves), n, len(ch)), np.complex64)
+
+
+def cwt_squeeze_device(scal: DeviceScalogram, freqs, fs, delta_w: float = 0.05,
+                       apply_frequency_normalization: bool = False) -> DeviceScalogram:
+    """_squeeze_scalogram (transforms/_transforms.py:227-301) of a complex64 device scalogram (ds_cwt_squeeze_dev,
+    float64 arithmetic) -> a complex128 DeviceScalogram.  The thresholds and normalisations are the reference's numpy
+    expressions."""
+    assert scal.dtype == np.complex64
+    n_f, n, n_ch = scal.shape
+    freqs = np.ascontiguousarray(np.asarray(freqs, dtype=np.float64))
+    delta_f = np.ascontiguousarray(delta_w * freqs)
+    norm = None
+    if apply_frequency_normalization:
+        norm = 1 / (freqs / fs)
+        norm **= -3 / 2
+        norm = np.ascontiguousarray(norm)
+    ctx = scal.buf.ctx
+    buf = DeviceBuffer(ctx, max(16 * n_f * n * n_ch, 16))
+    try:
+        ctx.check(ctx.lib.ds_cwt_squeeze_dev(ctx.handle, C.c_void_p(scal.buf.ptr), n_f, n, n_ch, _ptr(freqs),
+                                             _ptr(delta_f), None if norm is None else _ptr(norm), float(fs),
+                                             C.c_void_p(buf.ptr)), "ds_cwt_squeeze_dev")
+    except BaseException:
+        buf.free()
+        raise
+    return DeviceScalogram(buf, scal.shape, np.complex128)

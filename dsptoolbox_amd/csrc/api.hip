@@ -42,6 +42,7 @@
 #include "kernels_beamform.hpp"
 #include "kernels_iir.hpp"
 #include "kernels_delay.hpp"
+#include "kernels_cwt.hpp"
 
 using namespace dsk;
 
@@ -3592,6 +3593,208 @@ extern "C" int ds_delay_sum(ds_ctx* c, const double* x, int n_src, int64_t n_x, 
                           order, beta, out_len, y ? dy : nullptr, 1, n_rows, peak));
     if (y) CHK(ds_download(c, y, dy, ny * 8));
     return DS_OK;
+}
+
+// ---- continuous wavelet transform and synchrosqueezing (kernels_cwt.hpp) ---------------------------------------
+static int cwt_check(ds_ctx* c, const char* who, int64_t n_samples, int n_freq, const int64_t* tap_len,
+                     const float* taps) {
+    if (!tap_len || !taps) return fail(c, DS_ERR_ARG, std::string(who) + ": null argument");
+    if (n_samples <= 0 || n_freq <= 0) return fail(c, DS_ERR_ARG, std::string(who) + ": bad shape");
+    for (int f = 0; f < n_freq; ++f) {
+        if (tap_len[f] < 1) return fail(c, DS_ERR_ARG, std::string(who) + ": a wavelet has no taps");
+        if (tap_len[f] > dscwt::MAX_TAPS)
+            return fail(c, DS_ERR_UNSUP, std::string(who) + ": wavelets longer than 2^18 taps are not built");
+    }
+    return DS_OK;
+}
+
+// rows sel[0..n_sel) of the scalogram (frequency sel[i] into output row i of out (n_sel, N, n_ch), complex64) of the
+// planar fp32 channels ch[] of x.  tap_off[f] locates wavelet f's tap_len[f] complex taps in taps (host).
+static int cwt_run(ds_ctx* c, const float* x, int64_t ld, int64_t N, const int* ch, int n_ch, const int* sel,
+                   int n_sel, const int64_t* tap_off, const int64_t* tap_len, const float2* taps, float2* out) {
+    using dscwt::Freq;
+    struct Item { int row; int64_t k0, len, hc; };
+    std::map<int, std::vector<Item>> classes;  // by block length M
+    for (int i = 0; i < n_sel; ++i) {
+        const int f = sel[i];
+        const int64_t L = tap_len[f], h = (L - 1) / 2;
+        const int64_t k0 = std::max<int64_t>(0, h - N + 1), k1 = std::min<int64_t>(L - 1, h + N - 1);
+        const int64_t lc = k1 - k0 + 1;
+        int64_t M = dscwt::MIN_M;
+        while (M < 2 * lc) M *= 2;
+        classes[(int)M].push_back(Item{i, k0, lc, h - k0});
+    }
+    const int npair = (n_ch + 1) / 2;
+    for (auto& kv : classes) {
+        const int M = kv.first;
+        const auto& items = kv.second;
+        const int nf = (int)items.size();
+        int64_t cc = 0, hmax = 0, ntaps = 0;
+        for (const Item& it : items) {
+            cc = std::max(cc, it.len - 1 - it.hc);
+            hmax = std::max(hmax, it.hc);
+        }
+        const int64_t V = M - hmax - cc;
+        const int64_t nb64 = (N + V - 1) / V;
+        if (nb64 > INT32_MAX || nf > 65535 || n_ch > 65535)
+            return fail(c, DS_ERR_UNSUP, "cwt: too many blocks, frequencies or channels in one call");
+        const int n_blocks = (int)nb64;
+        std::vector<Freq> fr(nf);
+        for (int i = 0; i < nf; ++i) {
+            fr[i] = Freq{items[i].row, ntaps, items[i].len, items[i].hc + cc};
+            ntaps += items[i].len;
+        }
+        std::vector<float2> ht((size_t)ntaps);
+        for (int i = 0; i < nf; ++i)
+            std::memcpy(&ht[fr[i].toff], taps + tap_off[sel[items[i].row]] + items[i].k0, (size_t)items[i].len * 8);
+        const bool big = M > dscwt::MAX_LDS_M;
+        const int64_t n_items = (int64_t)nf * n_blocks * n_ch;
+        // big route: items per launch pair (the columns stage writes M complex values per item)
+        const int64_t chunk = big ? std::min<int64_t>({n_items, 65535, std::max<int64_t>(1, ((int64_t)256 << 20) / (8 * (int64_t)M))}) : 0;
+        if (big && ((int64_t)npair * n_blocks > 65535))
+            return fail(c, DS_ERR_UNSUP, "cwt: more than 65535 four-step blocks in one call");
+        int* dch;
+        Freq* dfr;
+        float2 *dtaps, *Z, *W, *zs = nullptr;
+        CHK(carve(c, &c->ws, &c->ws_bytes, [&](Carver& cv) {
+            dch = cv.take<int>(n_ch);
+            dfr = cv.take<Freq>(nf);
+            dtaps = cv.take<float2>(ntaps);
+            Z = cv.take<float2>((size_t)npair * n_blocks * M);
+            W = cv.take<float2>((size_t)nf * M);
+            if (big) zs = cv.take<float2>((size_t)std::max<int64_t>({(int64_t)npair * n_blocks, nf, chunk}) * M);
+        }));
+        CHK(ds_upload(c, dch, ch, (size_t)n_ch * 4));
+        CHK(ds_upload(c, dfr, fr.data(), (size_t)nf * sizeof(Freq)));
+        CHK(ds_upload(c, dtaps, ht.data(), (size_t)ntaps * 8));
+        const float inv_m = 1.0f / (float)M;
+        if (!big) {
+            const float2* tw;
+            CHK(get_twiddles(c, M, &tw));
+            dscwt::WspecArgs wa{dtaps, dfr, inv_m, W, tw};
+            dscwt::FwdArgs fa{x, ld, N, dch, n_ch, n_blocks, V, cc, Z, tw};
+            dscwt::InvArgs ia{Z, W, dfr, n_ch, n_blocks, V, N, out, tw};
+            const int rc = dispatch<256, 512, 1024, 2048, 4096, 8192, 16384>(M, [&](auto k) {
+                constexpr int NN = decltype(k)::value;
+                const size_t lds = Plan<NN>::LDS_BYTES;
+                CHK(launch(c, "cwt_wspec", dscwt::k_cwt_wspec<NN>, dim3(nf), Plan<NN>::NT, lds, wa));
+                CHK(launch(c, "cwt_fwd", dscwt::k_cwt_fwd<NN>, dim3(n_blocks, npair), Plan<NN>::NT, lds, fa));
+                return launch(c, "cwt_inv", dscwt::k_cwt_inv<NN>, dim3(n_blocks, n_ch, nf), Plan<NN>::NT, lds, ia);
+            });
+            if (rc != DS_OK) return rc;
+            continue;
+        }
+        // four-step route: tap spectra and block spectra through the bigfft stages, then the fused inverse
+        const int grid_x = (int)std::min<int64_t>(1024, (M + 255) / 256);
+        CHK(launch(c, "cwt_pad@big", dscwt::k_cwt_pad, dim3(grid_x, nf), 256, 0, dscwt::PadArgs{dtaps, dfr, M, inv_m, zs}));
+        CHK(big_cols(c, zs, nullptr, 0, 0, 0, zs, M, nf));
+        CHK(big_rows(c, zs, W, M, nf));
+        CHK(launch(c, "cwt_segments@big", dscwt::k_cwt_segments, dim3(grid_x, npair * n_blocks), 256, 0,
+                   dscwt::SegArgs{x, ld, N, dch, n_ch, n_blocks, V, cc, M, zs}));
+        CHK(big_cols(c, zs, nullptr, 0, 0, 0, zs, M, npair * n_blocks));
+        CHK(big_rows(c, zs, Z, M, npair * n_blocks));
+        constexpr int N1 = dscwt::BIG_N1;
+        const int n2 = M / N1;
+        const float2 *tw1, *tw2;
+        CHK(get_twiddles(c, N1, &tw1));
+        CHK(get_twiddles(c, n2, &tw2));
+        const int ct1 = std::min(8, n2), ct2 = big_rows_ct(n2);
+        for (int64_t i0 = 0; i0 < n_items; i0 += chunk) {
+            const unsigned cnt = (unsigned)std::min<int64_t>(chunk, n_items - i0);
+            dscwt::BigInvArgs a{Z, W, dfr, n_ch, n_blocks, i0, M, V, N, n2, ct1, zs, out, tw1};
+            CHK(launch(c, "cwt_bcols@big", dscwt::k_cwt_bcols<N1>, dim3(n2 / ct1, cnt), ct1 * Cfg<N1>::NT,
+                       (size_t)ct1 * dsbig::ch_stride<N1>() * sizeof(float2), a));
+            a.ct = ct2;
+            a.tw = tw2;
+            const int rc = dispatch<32, 64, 128, 256, 512>(n2, [&](auto k) {
+                constexpr int NN = decltype(k)::value;
+                return launch(c, "cwt_brows@big", dscwt::k_cwt_brows<NN>, dim3(N1 / ct2, cnt), ct2 * Cfg<NN>::NT,
+                              (size_t)ct2 * dsbig::ch_stride<NN>() * sizeof(float2), a);
+            });
+            if (rc != DS_OK) return rc;
+        }
+    }
+    return DS_OK;
+}
+
+static void cwt_offsets(int n_freq, const int64_t* tap_len, std::vector<int64_t>& off) {
+    off.resize(n_freq);
+    int64_t o = 0;
+    for (int f = 0; f < n_freq; ++f) {
+        off[f] = o;
+        o += tap_len[f];
+    }
+}
+
+extern "C" int ds_cwt_dev(ds_ctx* c, const float* x, int n_ch, int64_t ldx, int64_t n_samples, const int* channels,
+                          int n_out_ch, int n_freq, const int64_t* tap_len, const float* taps, float* out) {
+    if (!c || !x || !channels || !out) return fail(c, DS_ERR_ARG, "ds_cwt_dev: null argument");
+    CHK(cwt_check(c, "ds_cwt_dev", n_samples, n_freq, tap_len, taps));
+    if (n_ch <= 0 || n_out_ch <= 0 || ldx < n_samples) return fail(c, DS_ERR_ARG, "ds_cwt_dev: bad shape");
+    for (int i = 0; i < n_out_ch; ++i)
+        if (channels[i] < 0 || channels[i] >= n_ch) return fail(c, DS_ERR_ARG, "ds_cwt_dev: channel out of range");
+    HIPCHK(c, hipSetDevice(c->device));
+    std::vector<int64_t> off;
+    cwt_offsets(n_freq, tap_len, off);
+    std::vector<int> sel(n_freq);
+    for (int f = 0; f < n_freq; ++f) sel[f] = f;
+    return cwt_run(c, x, ldx, n_samples, channels, n_out_ch, sel.data(), n_freq, off.data(), tap_len,
+                   (const float2*)taps, (float2*)out);
+}
+
+// host: x (n_samples, n_ch) float64, out (n_freq, n_samples, n_ch) complex64 (out_f64 = 0) or complex128; the
+// scalogram is computed in frequency chunks of at most 512 MB of complex64 on the device
+extern "C" int ds_cwt(ds_ctx* c, const double* x, int n_ch, int64_t n_samples, int n_freq, const int64_t* tap_len,
+                      const float* taps, int out_f64, void* out) {
+    if (!c || !x || !out) return fail(c, DS_ERR_ARG, "ds_cwt: null argument");
+    CHK(cwt_check(c, "ds_cwt", n_samples, n_freq, tap_len, taps));
+    if (n_ch <= 0) return fail(c, DS_ERR_ARG, "ds_cwt: bad shape");
+    HIPCHK(c, hipSetDevice(c->device));
+    const int64_t row = n_samples * n_ch;  // complex values per frequency
+    const int rows = (int)std::max<int64_t>(1, std::min<int64_t>(n_freq, ((int64_t)512 << 20) / (8 * row)));
+    float* dx;
+    float2* dout;
+    CHK(carve(c, &c->io, &c->io_bytes, [&](Carver& cv) {
+        dx = cv.take<float>((size_t)n_ch * n_samples);
+        dout = cv.take<float2>((size_t)rows * row);
+    }));
+    CHK(upload_signal(c, nullptr, x, n_samples, n_ch, dx));
+    std::vector<int64_t> off;
+    cwt_offsets(n_freq, tap_len, off);
+    std::vector<int> ch(n_ch), sel(n_freq);
+    for (int i = 0; i < n_ch; ++i) ch[i] = i;
+    for (int f = 0; f < n_freq; ++f) sel[f] = f;
+    for (int f0 = 0; f0 < n_freq; f0 += rows) {
+        const int nr = std::min(rows, n_freq - f0);
+        CHK(cwt_run(c, dx, n_samples, n_samples, ch.data(), n_ch, sel.data() + f0, nr, off.data(), tap_len,
+                    (const float2*)taps, dout));
+        if (out_f64)
+            CHK(download_widen(c, (const float*)dout, 2 * nr * row, (double*)out + 2 * f0 * row));
+        else
+            CHK(ds_download(c, (float*)out + 2 * f0 * row, dout, (size_t)nr * row * 8));
+    }
+    return DS_OK;
+}
+
+extern "C" int ds_cwt_squeeze_dev(ds_ctx* c, const float* s, int n_freq, int64_t n_samples, int n_ch,
+                                  const double* freqs, const double* delta_f, const double* norm, double fs,
+                                  double* out) {
+    if (!c || !s || !freqs || !delta_f || !out) return fail(c, DS_ERR_ARG, "ds_cwt_squeeze_dev: null argument");
+    if (n_freq <= 0 || n_ch <= 0 || n_samples < 2)
+        return fail(c, DS_ERR_ARG, "ds_cwt_squeeze_dev: bad shape (the gradient needs two samples)");
+    HIPCHK(c, hipSetDevice(c->device));
+    double *dfq, *ddf, *dn;
+    CHK(carve(c, &c->ws, &c->ws_bytes, [&](Carver& cv) {
+        dfq = cv.take<double>(n_freq);
+        ddf = cv.take<double>(n_freq);
+        dn = cv.take<double>(norm ? n_freq : 0);
+    }));
+    CHK(ds_upload(c, dfq, freqs, (size_t)n_freq * 8));
+    CHK(ds_upload(c, ddf, delta_f, (size_t)n_freq * 8));
+    if (norm) CHK(ds_upload(c, dn, norm, (size_t)n_freq * 8));
+    const int64_t cols = n_samples * n_ch;
+    dscwt::SqueezeArgs a{(const float2*)s, n_freq, n_ch, n_samples, dfq, ddf, norm ? dn : nullptr, fs, (double2*)out};
+    return launch(c, "cwt_squeeze", dscwt::k_cwt_squeeze, dim3((unsigned)((cols + 255) / 256)), 256, 0, a);
 }
 
 // ---- RCCL (resolved at run time so the library loads on machines without it) ----

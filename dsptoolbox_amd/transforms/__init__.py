@@ -2,7 +2,8 @@
 row 1) and the STFT consumers log_mel_spectrogram / mfcc / chroma_stft (:113-203, :335-441, :589-684,
 row 4) on the device.  Same signature, parameter handling and quirks as the reference;
 the frame-wise inverse FFTs and the windowed overlap-add with the squared-window envelope
-(standard/_framed_signal_representation.py:70-137) run in the HIP library (ds_istft)."""
+(standard/_framed_signal_representation.py:70-137) run in the HIP library (ds_istft).  The continuous wavelet
+transform cwt with Wavelet / MorletWavelet (:687-760, transforms/_transforms.py:29-301) lives in _wavelets.py."""
 
 from __future__ import annotations
 
@@ -11,8 +12,9 @@ from scipy.signal import get_window
 
 from .. import backend
 from ..classes.signal import Signal
+from ._wavelets import MorletWavelet, Wavelet, cwt  # noqa: F401
 
-__all__ = ["istft", "mel_filterbank", "log_mel_spectrogram", "mfcc", "chroma_stft"]
+__all__ = ["istft", "mel_filterbank", "log_mel_spectrogram", "mfcc", "chroma_stft", "cwt", "Wavelet", "MorletWavelet"]
 
 
 def _pad_trim(td: np.ndarray, desired_length: int) -> np.ndarray:

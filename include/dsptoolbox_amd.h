@@ -402,6 +402,29 @@ int ds_delay_sum_dev(ds_ctx* ctx, const float* x_dev, int n_src, int64_t ldx, co
                      int n_terms, const int* src, const int64_t* shift, const double* frac, const double* weight,
                      int order, double beta, int64_t out_len, float* y_dev, int64_t ld_y, double* peak);
 
+/* ---- continuous wavelet transform: replaces the loop of the reference's transforms.cwt (transforms/transforms.py:
+ * 687-760) and _squeeze_scalogram (transforms/_transforms.py:227-301).  Row f of the scalogram is the "same"-mode
+ * convolution (scipy.signal.oaconvolve(..., mode="same")) of every channel with wavelet f:
+ *     S[f, n, c] = sum_k w_f[k] x_c[n + (L_f - 1) / 2 - k],   0 <= n < n_samples,
+ * computed in fp32 / complex64 by overlap-save in power-of-two size classes (csrc/kernels_cwt.hpp).  The wavelets are
+ * host arrays: taps holds all of them back to back as interleaved complex64 (wavelet f: tap_len[f] values, already
+ * normalised by the caller), tap_len is [n_freq].  1 <= L_f <= 2^18 (DS_ERR_UNSUP beyond, before any launch).
+ * ds_cwt: x (n_samples, n_ch) float64 host, the reference's layout; out (n_freq, n_samples, n_ch) host, complex64
+ *   (out_f64 = 0) or complex128.
+ * ds_cwt_dev: x_dev planar float32 x_dev[c*ldx + n]; channels[n_out_ch] (host) picks and orders the channels;
+ *   out_dev (n_freq, n_samples, n_out_ch) complex64 on the device.
+ * ds_cwt_squeeze_dev: synchrosqueezing of a device scalogram s_dev (n_freq, n_samples, n_ch) complex64 into out_dev
+ *   of the same shape, complex128, in float64 arithmetic: the gradient along time (np.gradient), the phase
+ *   transform |Im(g / S)| / (2 pi) fs where |S|^2 > 1e-40 (0 elsewhere), the first nearest of freqs[] (host, the
+ *   caller's order) and a skip beyond delta_f[f]; norm (host, [n_freq], or NULL) scales each summed row.
+ *   n_samples >= 2.                                                                                                  */
+int ds_cwt(ds_ctx* ctx, const double* x, int n_ch, int64_t n_samples, int n_freq, const int64_t* tap_len,
+           const float* taps, int out_f64, void* out);
+int ds_cwt_dev(ds_ctx* ctx, const float* x_dev, int n_ch, int64_t ldx, int64_t n_samples, const int* channels,
+               int n_out_ch, int n_freq, const int64_t* tap_len, const float* taps, float* out_dev);
+int ds_cwt_squeeze_dev(ds_ctx* ctx, const float* s_dev, int n_freq, int64_t n_samples, int n_ch, const double* freqs,
+                       const double* delta_f, const double* norm, double fs, double* out_dev);
+
 /* ---- block-streaming FIR classes with device-resident state ------------------------------
  * One process_block of the reference's real-time classes (classes/fir_filter_realtime.py:75-335),
  * executed literally on buffers that stay on the device between calls; per call only the block
