@@ -268,8 +268,11 @@ struct Args {
     const float* xsig;  // tools/exp/kernels_welch4096f.hpp only: the input channel (sig = the output channels)
 };
 
-// twt: fp64-computed tables, [15][256] W4096^(t k1) (k1 = 1..15) then [16][16] W256^(n3 k2)
-constexpr int TWT_LEN = 15 * 256 + 256;
+// twt: fp64-computed tables, [15][256] W4096^(t k1) (k1 = 1..15) then [16][16] W256^(n3 k2); from TWT_R on, the
+// tables of the rotated transform (kernels_welch4096w.hpp, fft4096_wr), t = 16 n2 + n3:
+//   [3][256] W4096^(t k1) W16^(n2 n3) (k1 = 1, 2, 3), [256] W16^(n2 n3), [16][16] W256^(n3 ((m + n3) mod 16))
+constexpr int TWT_R = 16 * 256;
+constexpr int TWT_LEN = TWT_R + 5 * 256;
 __device__ __forceinline__ void init_tables(Tw& tw, float (&win)[16], float2* tw2,
                                             const float* __restrict__ window,
                                             const float2* __restrict__ twt, int tid) {
@@ -291,6 +294,20 @@ inline void host_tables(std::vector<float2>& t) {
         for (int n3 = 0; n3 < 16; ++n3) {
             double a = -2.0 * M_PI * (double)(n3 * k2) / 256.0;
             t[15 * 256 + k2 * 16 + n3] = make_float2((float)std::cos(a), (float)std::sin(a));
+        }
+    for (int tt = 0; tt < 256; ++tt) {
+        const int rot = ((tt >> 4) * (tt & 15)) & 15;  // W16^(n2 n3) = W4096^(256 rot)
+        for (int k1 = 1; k1 < 4; ++k1) {
+            double a = -2.0 * M_PI * (double)(tt * k1 + 256 * rot) / 4096.0;
+            t[TWT_R + (k1 - 1) * 256 + tt] = make_float2((float)std::cos(a), (float)std::sin(a));
+        }
+        double a = -2.0 * M_PI * (double)rot / 16.0;
+        t[TWT_R + 3 * 256 + tt] = make_float2((float)std::cos(a), (float)std::sin(a));
+    }
+    for (int m = 0; m < 16; ++m)
+        for (int n3 = 0; n3 < 16; ++n3) {
+            double a = -2.0 * M_PI * (double)(n3 * ((m + n3) & 15)) / 256.0;
+            t[TWT_R + 4 * 256 + m * 16 + n3] = make_float2((float)std::cos(a), (float)std::sin(a));
         }
 }
 

@@ -17,6 +17,9 @@
 //     only 16 new samples per thread and pair are loaded (8 carried in registers).
 //   * thread tid ends with bins bt + 256 k3, bt = 16 (tid & 15) + (tid >> 4); k_x3 stores the
 //     input spectra thread-major in exactly that mapping.
+//   * k_x3 and k_y3 run fft4096_wr, which does that second exchange with DPP row rotations instead
+//     (no LDS, no wave_sync): it delivers each bin times a unit phase that cancels in conj(W) Z and
+//     |Z|^2, bin k3 in v[posr16(k3)].  Everything else here (fft4096_w, fft4096_wi) stays true.
 #pragma once
 #include <utility>
 
@@ -380,6 +383,118 @@ __device__ __forceinline__ void fft4096_wi(float2 (&v)[16], const Tw6& tw, float
         NoHookI(), NoHookI());
 }
 
+// ---- the rotated transform of the Welch pair loop ------------------------------
+// fft4096_wi without the wave-local transpose through LDS.  Thread t = 16 n2 + n3 also multiplies its pass-1
+// outputs by W16^(n2 n3) (folded into its twiddles: a, and c for k1 = 0 mod 4), so pass 2's DFT output m in lane n3
+// holds k2 = (m + n3) mod 16 and takes the W256 twiddle from the rotated table tw2r[16 m + n3].  DPP row_ror:m then
+// hands lane L of the row, in register m, the k2 = L value of lane (L - m) mod 16, and pass 3 is the plain DFT over
+// the registers: its output m is bin k3 = -m mod 16 (in v[posr16(k3)]) times the unit phase W16^(-k2 k3).  That
+// phase is the same for every transform run this way and cancels in conj(W) Z and |Z|^2, the only quantities
+// k_x3 / k_y3 keep; the result is NOT a spectrum otherwise.  tests/test_rotated_fft4096_model.py models it.
+// Per transform and wave: 16 ds_write_b64 + 16 ds_read_b64 (pass-1 image) and 16 table reads, no wave_sync.
+struct Tw6R {
+    float2 a[3];  // W4096^(t k1) W16^(n2 n3), k1 = 1, 2, 3
+    float2 b[3];  // W4096^(t k1), k1 = 4, 8, 12
+    float2 c;     // W16^(n2 n3)
+};
+constexpr int TW2R = TWT_R + 4 * 256;  // tw2r in twt (host_tables)
+
+__device__ __forceinline__ void load_tw6r(Tw6R& tw, const float2* __restrict__ twt, int tid) {
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        tw.a[j] = twt[TWT_R + j * 256 + tid];
+        tw.b[j] = twt[(4 * (j + 1) - 1) * 256 + tid];
+    }
+    tw.c = twt[TWT_R + 3 * 256 + tid];
+}
+
+// register of bin k3 after fft4096_wr
+__device__ __forceinline__ constexpr int posr16(int k3) { return pos16((16 - k3) & 15); }
+
+// lane L of each 16-lane row <- lane (L - R) mod 16
+template <int R>
+__device__ __forceinline__ float2 row_ror(float2 z) {
+    if constexpr (R == 0) {
+        return z;
+    } else {
+        const int x = __builtin_amdgcn_update_dpp(0, __float_as_int(z.x), 0x120 + R, 0xf, 0xf, true);
+        const int y = __builtin_amdgcn_update_dpp(0, __float_as_int(z.y), 0x120 + R, 0xf, 0xf, true);
+        return make_float2(__int_as_float(x), __int_as_float(y));
+    }
+}
+
+// ld_a(g), ld_b(g): the call-outs of fft4096_wi (pass 1 stage A, pass 2 stage B).  One workgroup barrier behind the
+// pass-1 image stores, one behind this wave's last image read (pass 2): the next transform's stores may begin.
+template <typename LA, typename LB>
+__device__ __forceinline__ void fft4096_wr(float2 (&v)[16], const Tw6R& tw, float2* __restrict__ buf,
+                                           const float2* __restrict__ tw2r, int tid, LA ld_a, LB ld_b) {
+    const int k1u = tid >> 4, n3 = tid & 15;
+    float2* __restrict__ col = buf + tid;
+    dft16_h(
+        v, NoHookI(),
+        [&](int g) {
+            W4_PIN();
+            ld_a(g);
+            W4_PIN();
+        },
+        [&](int g) {
+        // X[k1 = g + 4 j] -> twiddle (and W16^(n2 n3)) -> pass-1 image row k1
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                float2 z = cmul(v[4 * g + j], g ? tw.a[g - 1] : tw.c);
+                if (j) z = cmul(z, tw.b[j - 1]);
+                W4_PIN();
+                col[(g + 4 * j) * L1S] = z;
+                W4_PIN();
+            }
+        });
+    W4_SYNC();
+    const uint32_t a_row = lds_addr(buf + k1u * L1S + n3), a_tw2 = lds_addr(tw2r + n3);
+    W4_PIN();
+    static_for<16>([&](auto ic) {  // pass-2 inputs v[n2] = row[16 n2 + n3], in the order the butterflies use them
+        constexpr int i = decltype(ic)::value, n2 = 4 * (i & 3) + (i >> 2);
+        lds_rd64<16 * n2 * 8>(v[n2], a_row);
+    });
+    float2 w2[16];
+    dft16_h(
+        v,
+        [&](auto) {
+            // butterfly g needs the first 4 (g + 1) of the 16 image reads; 4 g table reads were issued behind them
+            lgkm_wait<12>();
+        },
+        [&](int g) {
+            W4_PIN();
+            static_for<4>([&](auto jc) {
+                constexpr int j = decltype(jc)::value;
+                if (g == 0) lds_rd64<(0 + j) * 16 * 8>(w2[0 + j], a_tw2);
+                if (g == 1) lds_rd64<(4 + j) * 16 * 8>(w2[4 + j], a_tw2);
+                if (g == 2) lds_rd64<(8 + j) * 16 * 8>(w2[8 + j], a_tw2);
+                if (g == 3) lds_rd64<(12 + j) * 16 * 8>(w2[12 + j], a_tw2);
+            });
+            if (g == 3) {
+                lgkm_wait<0>();  // image and table reads are in: the pass-1 image is free for the next transform
+                W4_SYNC();
+            }
+            W4_PIN();
+        },
+        [&](int g) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) v[4 * g + j] = cmul(v[4 * g + j], w2[g + 4 * j]);  // output m = g + 4 j
+            W4_PIN();
+            ld_b(g);
+            W4_PIN();
+        });
+    // the exchange: register m of lane L <- register m of lane (L - m) mod 16 (k2 = L, n3 = (L - m) mod 16)
+    float2 u[16];
+    static_for<16>([&](auto mc) {
+        constexpr int m = decltype(mc)::value;
+        u[m] = row_ror<m>(v[pos16(m)]);
+    });
+#pragma unroll
+    for (int m = 0; m < 16; ++m) v[m] = u[m];
+    dft16(v);
+}
+
 // ---- input spectra -----------------------------------------------------------
 __global__ __launch_bounds__(NT) void k_x3(Args p) {
     extern __shared__ __align__(16) float2 lds[];
@@ -387,7 +502,7 @@ __global__ __launch_bounds__(NT) void k_x3(Args p) {
     float2* tw2 = lds + 16 * L1S;
     const int tid = threadIdx.x;
     const int cx = (int)blockIdx.x / p.n_pairs, pr = (int)blockIdx.x - cx * p.n_pairs;  // one input channel: cx = 0
-    Tw6 tw;
+    Tw6R tw;
     float2 v[16];
     {
         Raw<true> raw;
@@ -396,19 +511,19 @@ __global__ __launch_bounds__(NT) void k_x3(Args p) {
 #pragma unroll
         for (int m = 0; m < 24; ++m) raw.s[m] = ld_sample(rs, off0 + 1024 * m);
         float win[16];
-        load_tw6(tw, p.twt, tid);
+        load_tw6r(tw, p.twt, tid);
 #pragma unroll
         for (int n1 = 0; n1 < 16; ++n1) win[n1] = p.window[tid + 256 * n1];
-        tw2[tid] = p.twt[15 * 256 + tid];
+        tw2[tid] = p.twt[TW2R + tid];
         window_pair<true>(v, raw, win);
         if (needs_drop(p, pr)) drop_second(v);
     }
-    fft4096_w(v, tw, buf, tw2, tid);
-    if (p.detrend && tid == 0) v[pos16(0)] = make_float2(0.f, 0.f);
+    fft4096_wr(v, tw, buf, tw2, tid, NoHookI(), NoHookI());
+    if (p.detrend && tid == 0) v[posr16(0)] = make_float2(0.f, 0.f);
     float4* xo = reinterpret_cast<float4*>(p.xs + ((int64_t)cx * p.n_pairs + pr) * N) + tid;
 #pragma unroll
     for (int g = 0; g < 8; ++g) {
-        float2 z0 = v[pos16(2 * g)], z1 = v[pos16(2 * g + 1)];
+        float2 z0 = v[posr16(2 * g)], z1 = v[posr16(2 * g + 1)];
         xo[256 * g] = make_float4(z0.x, z0.y, z1.x, z1.y);
     }
     float* pw = reinterpret_cast<float*>(buf);
@@ -416,7 +531,7 @@ __global__ __launch_bounds__(NT) void k_x3(Args p) {
     __syncthreads();
 #pragma unroll
     for (int k3 = 0; k3 < 16; ++k3) {
-        float2 z = v[pos16(k3)];
+        float2 z = v[posr16(k3)];
         pw[fold_pos(bt + 256 * k3)] = z.x * z.x + z.y * z.y;
     }
     __syncthreads();
@@ -477,9 +592,9 @@ __global__ __launch_bounds__(NT, W4_OCC) void k_y3(Args p) {
 #if W4_TIMING
     const unsigned long long life_t0 = __builtin_amdgcn_s_memtime(), life_r0 = __builtin_amdgcn_s_memrealtime();
 #endif
-    Tw6 tw;
-    load_tw6(tw, p.twt, tid);
-    tw2[tid] = p.twt[15 * 256 + tid];
+    Tw6R tw;
+    load_tw6r(tw, p.twt, tid);
+    tw2[tid] = p.twt[TW2R + tid];
 #if W4_WIN_GLOBAL
     const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.window), 0, N * 4, 0x00020000);
     (void)winl;
@@ -580,7 +695,7 @@ __global__ __launch_bounds__(NT, W4_OCC) void k_y3(Args p) {
         float2 xw[16];
         const int off1 = 4 * ((2 * pr + 2) * 2048 + tid) + 1024 * 8;
         const int xoff = (pr - p0) * (N * 8) + tid * 16;  // bytes into this chunk's input spectra
-        fft4096_wi(
+        fft4096_wr(
             v, tw, buf, tw2, tid,
             [&](int g) {  // samples of the next pair, four per call-out (past the chunk's last pair
                           // they are simply not used; past the signal the range check gives 0)
@@ -610,12 +725,11 @@ __global__ __launch_bounds__(NT, W4_OCC) void k_y3(Args p) {
                         xw[2 * (2 * g + j) + 1] = make_float2(q4.z, q4.w);
                     }
                 }
-            },
-            ts, level16);
+            });
         ts(10);
 #pragma unroll
         for (int k3 = 0; k3 < 16; ++k3) {
-            float2 z = v[pos16(k3)];
+            float2 z = v[posr16(k3)];
             if (!AUTO) {
                 float2 w = xw[k3];
                 T[k3].x = fmaf(w.x, z.x, fmaf(w.y, z.y, T[k3].x));

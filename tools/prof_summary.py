@@ -12,7 +12,7 @@ def find(pattern):
     return sorted(glob.glob(os.path.join(root, "**", pattern), recursive=True))
 
 
-print("== kernel trace stats (", root, ")")
+print("== kernel trace stats (", os.path.basename(os.path.normpath(root)), ")")
 for f in find("*kernel_stats.csv"):
     with open(f) as fh:
         for row in csv.DictReader(fh):
