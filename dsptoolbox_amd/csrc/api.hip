@@ -54,7 +54,7 @@ struct ds_ctx {
     hipStream_t stream = nullptr;
     hipStream_t side = nullptr;  // second stream for a kernel that may run beside the main one
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    hipEvent_t ev_chunk[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // csm_chunked
+    hipEvent_t ev_chunk[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // csm_chunked_run
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     std::string err;
     std::map<int, float2*> tw;  // twiddle tables by length
@@ -564,17 +564,317 @@ struct BigScratch {  // stft_big's scratch: two groups of four-step transforms a
     float2 *P, *Q;
     float* means;
 };
-static BigScratch take_big_scratch(Carver& cv, int n_ch, int n_frames, int64_t nfft);
+
+// ---- four-step FFT for 2^15 .. 2^24 points (kernels_bigfft.hpp) -------------------
+static int big_rows_ct(int n2) {
+    int nt = dsfft::threads_for(n2);
+    size_t per = (size_t)(((n2 + n2 / 16 + 2 + 30) / 32) * 32 + 1) * sizeof(float2);
+    int ct = std::min<int>({16, 1024 / nt, std::max<int>(1, (int)((70 * 1024) / per))});
+    while (ct & (ct - 1)) ct &= ct - 1;  // power of two: must divide N1
+    return ct;
+}
+
+// cols stage of `batch` a.n_total-point transforms: k_big_cols<1024>, min(8, n2) columns per workgroup (sets n2, ct, tw)
+static int launch_big_cols(ds_ctx* c, dsbig::ColsArgs a, int batch) {
+    constexpr int N1 = 1024;
+    a.n2 = (int)(a.n_total / N1);
+    a.ct = std::min(8, a.n2);
+    CHK(get_twiddles(c, N1, &a.tw));
+    const size_t lds = (size_t)a.ct * dsbig::ch_stride<N1>() * sizeof(float2);
+    return launch(c, "bigfft_cols", dsbig::k_big_cols<N1>, dim3(a.n2 / a.ct, batch), a.ct * Cfg<N1>::NT, lds, a);
+}
+// cols stage: source = complex `zin` (may equal `zout`) or real channel pairs
+static int big_cols(ds_ctx* c, const float2* zin, const float* xreal, int n_ch, int64_t ld_real,
+                    int64_t n_samples, float2* zout, int64_t N, int batch) {
+    return launch_big_cols(c, {zin, xreal, nullptr, n_samples, 0, zout, N, 0, 0, 0, ld_real, n_ch, nullptr}, batch);
+}
+
+static int big_rows(ds_ctx* c, const float2* zin, float2* zout, int64_t N, int batch) {
+    constexpr int N1 = 1024;
+    const int n2 = (int)(N / N1);
+    const float2* tw;
+    CHK(get_twiddles(c, n2, &tw));
+    const int ct = big_rows_ct(n2);
+    dsbig::RowsArgs a{zin, zout, N, N1, ct, tw};
+    size_t lds = 0;
+    DISPATCH_N(n2, lds = (size_t)ct * dsbig::ch_stride<NN>() * sizeof(float2));
+    DISPATCH_N(n2, CHK(launch(c, "bigfft_rows", dsbig::k_big_rows<NN>, dim3(N1 / ct, batch), ct * Cfg<NN>::NT, lds, a)));
+    return DS_OK;
+}
+
+static int check_big_len(ds_ctx* c, int64_t n, const char* what) {
+    if (!is_pow2(n)) return fail(c, DS_ERR_ARG, std::string(what) + ": internal: not a power of two");
+    if (n > kMaxBigFft) return fail(c, DS_ERR_UNSUP, std::string(what) + ": lengths above 2^24 are not built yet");
+    return DS_OK;
+}
+
+// ---- framed transforms beyond the LDS-resident FFT (window / FFT length 2^15 .. 2^24) ------
+// Frame pairs of every channel are one batch of four-step complex FFTs, processed in groups
+// of <= 2^25 complex points per scratch buffer.
+static int64_t stft_big_group(int64_t nfft, int64_t batch) {
+    return std::max<int64_t>(1, std::min<int64_t>({batch, ((int64_t)1 << 25) / nfft, (int64_t)32768}));
+}
+static BigScratch take_big_scratch(Carver& cv, int n_ch, int n_frames, int64_t nfft) {
+    const int64_t grp = stft_big_group(nfft, (int64_t)n_ch * ((n_frames + 1) / 2));
+    BigScratch s;
+    s.P = cv.take<float2>((size_t)grp * nfft);
+    s.Q = cv.take<float2>((size_t)grp * nfft);
+    s.means = cv.take<float>((size_t)n_ch * n_frames);
+    return s;
+}
+// layout 0: out[(c*F + f)*nb + k] (unscaled spectra for the Welch sums), 1: out[(k*F + f)*C + c]
+// s: take_big_scratch() for at least n_ch channels and n_frames frames
 static int stft_big(ds_ctx* c, const BigScratch& s, const float* x, int n_ch, int64_t ld, int64_t n_samples,
                     int W, int hop, int64_t nfft, int64_t pad_front, int n_frames, const float* window,
-                    int detrend, float scale, float edge_scale, int power, int layout, float2* out);
-static int welch_big(ds_ctx* c, int kind, const float* x, int n_cx, int64_t ldx, const float* y,
-                     int n_cy, int64_t ldy, int64_t n_samples, int W, int hop, int n_frames,
-                     const float* window, int detrend, int average, int mode, int amp_sqrt,
-                     double norm_scale, double factor, int halve_edges, float2* out_c, float* out_r);
+                    int detrend, float scale, float edge_scale, int power, int layout, float2* out) {
+    CHK(check_big_len(c, nfft, "framed transform length"));
+    const int64_t batch = (int64_t)n_ch * ((n_frames + 1) / 2);
+    const int64_t grp = stft_big_group(nfft, batch);
+    float2 *P = s.P, *Q = s.Q;
+    float* means = s.means;
+    if (detrend) {
+        dsbig::FrameMeansArgs m{x, n_samples, ld, pad_front, n_ch, W, hop, n_frames, window, means};
+        CHK(launch(c, "bigfft_means", dsbig::k_frame_means, dim3(n_frames, n_ch), 256, 0, m));
+    }
+    for (int64_t b0 = 0; b0 < batch; b0 += grp) {
+        const int nb = (int)std::min<int64_t>(grp, batch - b0);
+        CHK(launch_big_cols(c, {nullptr, x, nullptr, n_samples, 0, P, nfft, 0, 0, 0, ld, n_ch, nullptr, window,
+                                detrend ? means : nullptr, W, hop, n_frames, pad_front, b0}, nb));
+        CHK(big_rows(c, P, Q, nfft, nb));
+        dsbig::UnpackFramesArgs u{Q, nfft, b0, n_ch, n_frames, layout, power, scale, edge_scale, out};
+        CHK(launch(c, "bigfft_unpack", dsbig::k_big_unpack_frames, dim3(64, nb), 256, 0, u));
+    }
+    return DS_OK;
+}
+
+// ---- arbitrary lengths: Bluestein on top of the four-step FFT ------------------------
+static int64_t blue_len(int64_t L) {
+    int64_t m = (int64_t)1 << 15;  // smallest four-step length
+    while (m < 2 * L - 1) m <<= 1;
+    return m;
+}
+
+static int blue_filter(ds_ctx* c, int64_t L, int64_t M, const float2** out) {
+    auto key = std::make_pair(L, M);
+    auto it = c->blue.find(key);
+    if (it != c->blue.end()) {
+        it->second.stamp = ++c->blue_clock;
+        *out = it->second.ptr;
+        return DS_OK;
+    }
+    const size_t bytes = sizeof(float2) * (size_t)M;
+    // make room: drop the least recently used tables (hipFree waits for the device, so a table
+    // still referenced by queued kernels of an earlier call is never pulled from under them)
+    while (!c->blue.empty() && c->blue_bytes + bytes > c->cfg.bluestein_cache_bytes) {
+        auto lru = c->blue.begin();
+        for (auto jt = c->blue.begin(); jt != c->blue.end(); ++jt)
+            if (jt->second.stamp < lru->second.stamp) lru = jt;
+        HIPCHK(c, hipFree(lru->second.ptr));
+        c->blue_bytes -= lru->second.bytes;
+        c->blue.erase(lru);
+    }
+    float2 *bt = nullptr, *bf = nullptr;
+    HIPCHK(c, hipMalloc((void**)&bt, bytes));
+    if (hipMalloc((void**)&bf, bytes) != hipSuccess) {
+        (void)hipFree(bt);
+        return fail(c, DS_ERR_NOMEM, "Bluestein filter table: hipMalloc failed");
+    }
+    int rc = DS_OK;
+    do {
+        hipLaunchKernelGGL(dsblue::k_filter, dim3(1024), dim3(256), 0, c->stream, bt, L, M);
+        if (hipGetLastError() != hipSuccess) { rc = fail(c, DS_ERR_HIP, "Bluestein filter kernel launch failed"); break; }
+        if ((rc = big_cols(c, bt, nullptr, 0, 0, 0, bt, M, 1)) != DS_OK) break;
+        if ((rc = big_rows(c, bt, bf, M, 1)) != DS_OK) break;
+        if (hipStreamSynchronize(c->stream) != hipSuccess) { rc = fail(c, DS_ERR_HIP, "Bluestein filter: stream sync failed"); break; }
+    } while (0);
+    (void)hipFree(bt);
+    if (rc != DS_OK) {
+        (void)hipFree(bf);
+        return rc;
+    }
+    c->blue[key] = ds_ctx::BlueEntry{bf, bytes, ++c->blue_clock};
+    c->blue_bytes += bytes;
+    *out = bf;
+    return DS_OK;
+}
+
+// X[batch][L] = DFT_L of (real channel pairs | complex zin[batch][L]); P, Q: [batch][M] scratch
+static int blue_dft(ds_ctx* c, const float* xreal, int n_ch, int64_t ld_real, int64_t n_samples,
+                    const float2* zin, int batch, int64_t L, int64_t M, float2* P, float2* Q, float2* X) {
+    const float2* bf;
+    CHK(blue_filter(c, L, M, &bf));
+    dsblue::PreArgs pa{xreal, ld_real, n_samples, n_ch, zin, P, L, M};
+    CHK(launch(c, "blue_pre", dsblue::k_pre, dim3(512, batch), 256, 0, pa));
+    CHK(big_cols(c, P, nullptr, 0, 0, 0, P, M, batch));
+    CHK(big_rows(c, P, Q, M, batch));
+    hipLaunchKernelGGL(dsblue::k_mul_filter, dim3(512, batch), dim3(256), 0, c->stream, Q, bf, M);
+    HIPCHK(c, hipGetLastError());
+    CHK(big_cols(c, Q, nullptr, 0, 0, 0, Q, M, batch));
+    CHK(big_rows(c, Q, P, M, batch));
+    hipLaunchKernelGGL(dsblue::k_post, dim3(512, batch), dim3(256), 0, c->stream, (const float2*)P, X, L, M);
+    HIPCHK(c, hipGetLastError());
+    return DS_OK;
+}
+
+static int check_blue_len(ds_ctx* c, int64_t L, const char* what) {
+    if (L < 2) return fail(c, DS_ERR_ARG, std::string(what) + ": length must be >= 2");
+    if (2 * L - 1 > kMaxBigFft) return fail(c, DS_ERR_UNSUP, std::string(what) + ": non-power-of-two lengths above 2^23 are not built yet");
+    return DS_OK;
+}
+
+// ---- whole-signal rFFT, deconvolution ---------------------------------------
+// One call of ds_rfft_dev (x -> spec) or ds_deconv_dev (y = x, r -> ir), checked by xform_check; `who`: the entry called
+struct XformCall {
+    const char* who;
+    const float* x; int n_items, n_ch; int64_t ld, n_samples; int n_fft;
+    float scale; float2* spec;                                             // rFFT
+    const float2* r; int r_per_channel; int64_t n_out, ld_out; float* ir;  // deconvolution
+};
+static int xform_check(ds_ctx* c, const XformCall& q, bool deconv) {
+    const std::string w(q.who), what = w + " n_fft";
+    if (!c || !q.x || (deconv ? !q.r || !q.ir : !q.spec)) return fail(c, DS_ERR_ARG, w + ": null argument");
+    if (q.n_items <= 0 || q.n_ch <= 0 || q.n_samples <= 0 || q.ld < q.n_samples || q.n_samples > q.n_fft ||
+        (deconv && (q.n_out <= 0 || q.n_out > q.n_fft || q.ld_out < q.n_out)))
+        return fail(c, DS_ERR_ARG, w + (deconv ? ": bad shape" : ": bad shape (n_samples must be <= n_fft)"));
+    if (!is_pow2(q.n_fft)) return check_blue_len(c, q.n_fft, what.c_str());
+    if (q.n_fft > kMaxFft) return check_big_len(c, q.n_fft, what.c_str());
+    return check_fft_len(c, q.n_fft, what.c_str());
+}
+
+// lengths that are not powers of two: Bluestein's DFT of the channel pairs, then (rFFT) the spectra unpacked, or
+// (deconvolution) multiplied by r, transformed back and stored
+static int xform_blue_run(ds_ctx* c, const XformCall& q) {
+    const int npair = (q.n_ch + 1) / 2, batch = q.n_items * npair;
+    const int64_t L = q.n_fft, M = blue_len(L);
+    float2 *P, *Q, *X, *Y;
+    CHK(carve(c, &c->ws, &c->ws_bytes, [&](Carver& cv) {
+        P = cv.take<float2>((size_t)batch * M);
+        Q = cv.take<float2>((size_t)batch * M);
+        X = cv.take<float2>((size_t)batch * L);
+        Y = q.spec ? nullptr : cv.take<float2>((size_t)batch * L);
+    }));
+    CHK(blue_dft(c, q.x, q.n_ch, q.ld, q.n_samples, nullptr, batch, L, M, P, Q, X));
+    if (q.spec) {
+        hipLaunchKernelGGL(dsblue::k_unpack, dim3(512, npair), dim3(256), 0, c->stream, (const float2*)X, L, q.n_ch,
+                           q.scale, q.spec);
+    } else {
+        hipLaunchKernelGGL(dsblue::k_mul_r, dim3(512, batch), dim3(256), 0, c->stream, X, L, q.n_ch, q.r_per_channel, q.r);
+        HIPCHK(c, hipGetLastError());
+        CHK(blue_dft(c, nullptr, q.n_ch, 0, 0, X, batch, L, M, P, Q, Y));
+        hipLaunchKernelGGL(dsblue::k_store, dim3(512, batch), dim3(256), 0, c->stream, (const float2*)Y, L, q.n_out,
+                           q.ld_out, q.n_ch, q.ir);
+    }
+    HIPCHK(c, hipGetLastError());
+    return DS_OK;
+}
+// powers of two beyond the LDS-resident FFT: four-step transforms of the channel pairs, then (rFFT) the spectra
+// unpacked, or (deconvolution) multiplied by r, transformed back and stored
+static int xform_big_run(ds_ctx* c, const XformCall& q) {
+    const int npair = (q.n_ch + 1) / 2, batch = q.n_items * npair;
+    const int64_t N = q.n_fft;
+    float2 *P, *Q;
+    CHK(carve(c, &c->ws, &c->ws_bytes, [&](Carver& cv) {
+        P = cv.take<float2>((size_t)batch * N);
+        Q = cv.take<float2>((size_t)batch * N);
+    }));
+    CHK(big_cols(c, nullptr, q.x, q.n_ch, q.ld, q.n_samples, P, N, batch));
+    CHK(big_rows(c, P, Q, N, batch));
+    if (q.spec) {
+        dsbig::UnpackArgs u{Q, N, q.n_ch, q.scale, q.spec, q.n_ch, 1};
+        return launch(c, "bigfft_unpack", dsbig::k_big_unpack, dim3(1024, npair), 256, 0, u);
+    }
+    dsbig::MulArgs m{Q, N, q.n_ch, q.r_per_channel, q.r};
+    CHK(launch(c, "bigfft_mul", dsbig::k_big_mul, dim3(1024, batch), 256, 0, m));
+    CHK(big_cols(c, Q, nullptr, q.n_ch, 0, 0, Q, N, batch));
+    CHK(big_rows(c, Q, P, N, batch));
+    dsbig::StoreArgs st{P, N, q.n_out, q.ld_out, q.n_ch, q.ir};
+    return launch(c, "bigfft_store", dsbig::k_big_store, dim3(1024, batch), 256, 0, st);
+}
+static int rfft_lds_run(ds_ctx* c, const XformCall& q) {
+    const float2* tw;
+    CHK(get_twiddles(c, q.n_fft, &tw));
+    RfftArgs a{q.x, q.n_samples, q.ld, q.n_ch, tw, q.scale, q.spec};
+    DISPATCH_N(q.n_fft, CHK(launch(c, "rfft", k_rfft<NN>, dim3((q.n_ch + 1) / 2), Cfg<NN>::NT, Cfg<NN>::LDS_BYTES, a)));
+    return DS_OK;
+}
+
+// 8192 points, one inverse spectrum for all channels: two register-resident 4096-point transforms per channel pair,
+// the packed spectrum multiplied directly (kernels_deconv8k.hpp).
+// Default since round 5: two persistent workgroups per CU, the next unit's samples in flight during this unit's
+// transforms, the inverse spectrum from a permuted copy (k_rperm + k_deconv_p).  DSPTOOLBOX_AMD_DECONV_PERSIST=0 keeps
+// one unit per workgroup: four workgroups per CU (k_deconv3q: all 1024 pairs of the benchmark resident at once), or
+// three with DSPTOOLBOX_AMD_DECONV_4PERCU=0 (k_deconv3, 168 registers).  DSPTOOLBOX_AMD_DECONV_2PERCU=1 keeps the
+// 512-thread kernel (A/B).
+static int deconv8k_run(ds_ctx* c, const XformCall& q) {
+    CHK(ensure_table(c, &c->w4_tables, welch4096::host_tables));
+    CHK(ensure_table(c, &c->deconv8k_tables, deconv8k::host_tables));
+    deconv8k::Args a8{q.x, q.n_samples, q.ld, q.n_out, q.ld_out, q.n_ch, c->w4_tables, c->deconv8k_tables, q.r, q.ir};
+    const int64_t n_units = (int64_t)((q.n_ch + 1) / 2) * q.n_items;
+    const bool two = c->cfg.deconv_2percu;
+    // (n_units + grid stays an int inside the kernel: u + gridDim.x is formed for the prefetch past the last unit)
+    if (c->cfg.deconv_persist && !two && n_units < ((int64_t)1 << 31) - 4096 && c->n_cu > 0) {
+        if (!c->deconv_rperm) HIPCHK(c, hipMalloc((void**)&c->deconv_rperm, sizeof(float2) * deconv8k::RPERM_LEN));
+        CHK(launch(c, "deconv_rperm", deconv8k::k_rperm, dim3(32), 256, 0, deconv8k::RpArgs{q.r, c->deconv_rperm}));
+        deconv8k::PArgs pa{a8, c->deconv_rperm, (int)n_units};
+        const int grid = (int)std::min<int64_t>(n_units, 2 * (int64_t)c->n_cu);
+        return launch(c, "deconv@8k_persist", deconv8k::k_deconv_p, dim3((unsigned)grid), 256, deconv8k::LDS_BYTES_3, pa);
+    }
+    if (!two && c->cfg.deconv_4percu && n_units < ((int64_t)1 << 31))
+        return launch(c, "deconv@8k_4percu", deconv8k::k_deconv3q, dim3((unsigned)n_units), 256, deconv8k::LDS_BYTES_3, a8);
+    if (!two && n_units < ((int64_t)1 << 31))
+        return launch(c, "deconv@8k_3percu", deconv8k::k_deconv3, dim3((unsigned)n_units), 256, deconv8k::LDS_BYTES_3, a8);
+    return launch(c, "deconv@8k_512", deconv8k::k_deconv, dim3((q.n_ch + 1) / 2, q.n_items), deconv8k::NTB,
+                  deconv8k::LDS_BYTES, a8);
+}
+static int deconv_generic_run(ds_ctx* c, const XformCall& q) {
+    const float2* tw;
+    CHK(get_twiddles(c, q.n_fft, &tw));
+    DeconvArgs a{q.x, q.n_samples, q.ld, q.n_out, q.ld_out, q.n_ch, q.r_per_channel, tw, q.r, q.ir};
+    const dim3 grid((q.n_ch + 1) / 2, q.n_items);
+    DISPATCH_N(q.n_fft, CHK(launch(c, "deconv@generic", k_deconv<NN>, grid, Cfg<NN>::NT, Cfg<NN>::LDS_BYTES, a)));
+    return DS_OK;
+}
+
+using XformRunner = int (*)(ds_ctx*, const XformCall&);
+// The kernel family of a checked call: Bluestein for lengths that are not powers of two, the four-step FFT beyond the
+// LDS-resident one
+static XformRunner rfft_route(const XformCall& q) {
+    if (!is_pow2(q.n_fft)) return xform_blue_run;
+    return q.n_fft > kMaxFft ? xform_big_run : rfft_lds_run;
+}
+static XformRunner deconv_route(const ds_ctx* c, const XformCall& q) {
+    if (!is_pow2(q.n_fft)) return xform_blue_run;
+    if (q.n_fft > kMaxFft) return xform_big_run;
+    if (q.n_fft == deconv8k::N && !q.r_per_channel && !c->cfg.deconv_generic) return deconv8k_run;
+    return deconv_generic_run;
+}
 
 extern "C" int ds_rfft_dev(ds_ctx* c, const float* x, int n_ch, int64_t ld, int64_t n_samples,
-                           int n_fft, float scale, ds_c32* spec);
+                           int n_fft, float scale, ds_c32* spec) {
+    const XformCall q{"ds_rfft_dev", x, 1, n_ch, ld, n_samples, n_fft, scale, (float2*)spec};
+    CHK(xform_check(c, q, false));
+    return rfft_route(q)(c, q);
+}
+
+extern "C" int ds_deconv_inverse_dev(ds_ctx* c, const ds_c32* xspec, int n_ch, int n_bins,
+                                     const float* eps, ds_c32* r) {
+    if (!c || !xspec || !r || n_ch <= 0 || n_bins <= 0)
+        return fail(c, DS_ERR_ARG, "ds_deconv_inverse: bad argument");
+    int64_t total = (int64_t)n_ch * n_bins;
+    hipLaunchKernelGGL(k_deconv_inverse, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, c->stream,
+                       (const float2*)xspec, n_ch, n_bins, eps, (float2*)r);
+    HIPCHK(c, hipGetLastError());
+    return DS_OK;
+}
+
+extern "C" int ds_deconv_dev(ds_ctx* c, const float* y, int n_items, int n_ch, int64_t ld,
+                             int64_t n_samples, int n_fft, const ds_c32* r, int r_per_channel,
+                             int64_t n_out, int64_t ld_out, float* ir) {
+    const XformCall q{"ds_deconv_dev", y, n_items, n_ch, ld, n_samples, n_fft, 1.0f, nullptr, (const float2*)r, r_per_channel,
+                      n_out, ld_out, ir};
+    CHK(xform_check(c, q, true));
+    return deconv_route(c, q)(c, q);
+}
 
 // ---- STFT ------------------------------------------------------------------
 // One call of ds_stft_r2c_dev, as every STFT runner takes it (checked by stft_check; `who`: the entry point called)
@@ -856,10 +1156,6 @@ static int istft_long_run(ds_ctx* c, const IstftCall& q) {
 // numerator.  k_istft_spec lays the spectra out per (channel, frame) -- cropped or zero-padded to
 // n / 2 + 1 bins as numpy does --, the division writes the frames [c][f][W], k_istft_scale applies the
 // synthesis window and the scale; the overlap-add kernel is the same as for powers of two.
-extern "C" int ds_deconv_dev(ds_ctx* c, const float* y, int n_items, int n_ch, int64_t ld, int64_t n_samples, int n_fft,
-                             const ds_c32* r, int r_per_channel, int64_t n_out, int64_t ld_out, float* ir);
-static int64_t blue_len(int64_t L);
-static int check_blue_len(ds_ctx* c, int64_t L, const char* what);
 __global__ void k_istft_spec(const float2* stft, int n_bins, int n_frames, int n_ch, int f0, int nf, int nb, float2* r,
                              float* ones) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, total = (int64_t)n_ch * nf * nb;
@@ -1106,6 +1402,52 @@ static int median_bins_per_block(int series, int n_frames, size_t* lds) {
         }
     }
     return 0;
+}
+
+// Welch for window lengths beyond the LDS-resident FFT: spectra of every frame -> frame sums
+// (or per-bin medians) -> the usual finish
+static int welch_big(ds_ctx* c, int kind, const float* x, int n_cx, int64_t ldx, const float* y,
+                     int n_cy, int64_t ldy, int64_t n_samples, int W, int hop, int n_frames,
+                     const float* window, int detrend, int average, int mode, int amp_sqrt,
+                     double norm_scale, double factor, int halve_edges, float2* out_c, float* out_r) {
+    const int nb = W / 2 + 1;
+    const int nyc = kind == 1 ? 0 : n_cy;
+    const int nmax = std::max(n_cx, nyc);
+    size_t med_lds = 0;
+    const int med_bpb = median_bins_per_block(3, n_frames, &med_lds);
+    if (average == DS_AVG_MEDIAN && !med_bpb)
+        return fail(c, DS_ERR_UNSUP, "welch: median averaging over more than 12 799 frames is not built yet");
+    float2 *xsp, *ysp, *pxy;
+    float *pxx, *pyy;
+    BigScratch s;  // the FFT scratch is reused by both signals
+    CHK(carve(c, &c->ws, &c->ws_bytes, [&](Carver& cv) {
+        xsp = cv.take<float2>((size_t)n_cx * n_frames * nb);
+        ysp = cv.take<float2>((size_t)std::max(1, nyc) * n_frames * nb);
+        pxx = cv.take<float>((size_t)n_cx * nb);
+        pxy = cv.take<float2>((size_t)std::max(1, nyc) * nb);
+        pyy = cv.take<float>((size_t)std::max(1, nyc) * nb);
+        s = take_big_scratch(cv, nmax, n_frames, W);
+    }));
+    CHK(stft_big(c, s, x, n_cx, ldx, n_samples, W, hop, W, 0, n_frames, window, detrend, 1.0f, 1.0f, 0,
+                 0, xsp));
+    if (nyc) {
+        CHK(stft_big(c, s, y, nyc, ldy, n_samples, W, hop, W, 0, n_frames, window, detrend, 1.0f, 1.0f,
+                     0, 0, ysp));
+    }
+    double count = (double)n_frames;
+    if (average == DS_AVG_MEDIAN) {
+        MedianArgs m{xsp, nyc ? ysp : nullptr, n_cx, nyc, n_frames, nb, kind, med_bpb, pxx, pxy, pyy};
+        CHK(launch(c, "welch_median", k_welch_median, dim3((nb + med_bpb - 1) / med_bpb, kind == 1 ? n_cx : n_cy), 256,
+                   med_lds, m));
+        const int nbias = (n_frames & 1) ? n_frames : n_frames - 1;
+        count = 1.0 / (double)std::max(1, nbias);
+    } else {
+        dsbig::SpecSumArgs sa{xsp, nyc ? ysp : nullptr, n_cx, nyc, n_frames, nb, kind, pxx, pxy, pyy};
+        CHK(launch(c, "welch_specsum", dsbig::k_spec_sum, dim3((nb + 255) / 256, kind == 1 ? n_cx : n_cy), 256, 0, sa));
+    }
+    WelchFinArgs f{pxx, pxy, pyy, 1, 1, n_cx, n_cy, kind, mode,
+                   FinishPar{norm_scale / count, factor, halve_edges, amp_sqrt, nb}, out_c, out_r};
+    return launch_finish(c, f);
 }
 
 static int welch_common(ds_ctx* c, int kind, const float* x, int n_cx, int64_t ldx, const float* y,
@@ -1833,14 +2175,73 @@ extern "C" int ds_csm_x64(ds_ctx* c, const double* x, int n_ch, int64_t n_sample
 }
 
 // ---- CSM -------------------------------------------------------------------
+// One call of ds_csm_dev / ds_csm_bins_dev (bins [bin_start, bin_start + bin_count)), checked by csm_check; `who`: its name
+struct CsmCall {
+    const char* who;
+    const float* x; int n_ch; int64_t ld, n_samples; int W, hop, n_frames; const float* window; int detrend, average;
+    int amp_sqrt; double norm_scale, factor; int halve_edges, bin_start, bin_count; float2* csm;
+    bool big() const { return W > kMaxFft && is_pow2(W); }  // window beyond the LDS-resident FFT: four-step transforms
+    bool all_bins() const { return bin_start == 0 && bin_count == W / 2 + 1; }
+};
+static int csm_check(ds_ctx* c, const CsmCall& q) {
+    const std::string w(q.who);
+    if (!c || !q.x || !q.window || !q.csm) return fail(c, DS_ERR_ARG, w + ": null argument");
+    if (q.n_ch < 1 || q.n_samples <= 0 || q.hop <= 0 || q.hop > q.W || q.n_frames <= 0 || q.ld < q.n_samples)
+        return fail(c, DS_ERR_ARG, w + ": bad shape");
+    if (q.average != DS_AVG_MEAN && q.average != DS_AVG_MEDIAN)
+        return fail(c, DS_ERR_ARG, w + ": average must be mean (0) or median (1)");
+    if (!q.big()) CHK(check_fft_len(c, q.W, (w + " window length").c_str()));
+    if (q.bin_start < 0 || q.bin_count <= 0 || q.bin_start + q.bin_count > q.W / 2 + 1)
+        return fail(c, DS_ERR_ARG, w + ": bad bin range");
+    if (q.average == DS_AVG_MEDIAN && !q.all_bins())
+        return fail(c, DS_ERR_UNSUP, w + ": a bin range with median averaging is not built yet");
+    size_t lds = 0;
+    if (q.average == DS_AVG_MEDIAN && !median_bins_per_block(2, q.n_frames, &lds))
+        return fail(c, DS_ERR_UNSUP, w + ": median averaging over more than 19 199 frames is not built yet");
+    return DS_OK;
+}
+
+// spectra of every frame [c][F][nb] -> per-pair, per-bin medians
+static int csm_median_run(ds_ctx* c, const CsmCall& q) {
+    const int nb = q.W / 2 + 1;
+    size_t lds = 0;
+    const int bpb = median_bins_per_block(2, q.n_frames, &lds);
+    WelchPlan pl = plan_welch(q.n_frames, q.n_ch);
+    float2* xsp;
+    BigScratch s;
+    float* scratch;
+    CHK(carve(c, &c->ws, &c->ws_bytes, [&](Carver& cv) {
+        xsp = cv.take<float2>((size_t)q.n_ch * q.n_frames * nb);
+        if (q.big()) s = take_big_scratch(cv, q.n_ch, q.n_frames, q.W);
+        else scratch = cv.take<float>((size_t)pl.n_chunks * q.n_ch * nb);
+    }));
+    if (q.big()) {
+        CHK(stft_big(c, s, q.x, q.n_ch, q.ld, q.n_samples, q.W, q.hop, q.W, 0, q.n_frames, q.window, q.detrend, 1.0f, 1.0f, 0,
+                     0, xsp));
+    } else {
+        const float2* tw;
+        CHK(get_twiddles(c, q.W, &tw));
+        XspecArgs ax{q.x, q.n_samples, q.ld, q.n_ch, q.W, q.hop, q.n_frames, q.detrend, pl.fpc, q.window, tw, xsp, scratch};
+        DISPATCH_N(q.W, CHK(launch(c, "welch_xspec", k_xspec<NN>, dim3(pl.n_chunks, q.n_ch), Cfg<NN>::NT, Cfg<NN>::LDS_BYTES, ax)));
+    }
+    const int nbias = (q.n_frames & 1) ? q.n_frames : q.n_frames - 1;
+    CsmMedianArgs m{xsp, q.n_ch, q.n_frames, bpb,
+                    FinishPar{q.norm_scale * (double)std::max(1, nbias), q.factor, q.halve_edges, q.amp_sqrt, nb}, q.csm};
+    return launch(c, "csm_median", k_csm_median, dim3((nb + bpb - 1) / bpb, q.n_ch * (q.n_ch + 1) / 2), 256, lds, m);
+}
+
+// Round 5: the 64-microphone shape in frame chunks on two streams.  Transform and product are both streams of the
+// spectrogram X (written once, read once: 4.9 x the algorithmic bytes of the step, and each kernel alone reaches
+// 0.4 of the HBM roofline); with the frames cut into chunks the transform of chunk k + 1 (main stream) runs beside
+// the product of chunk k (side stream), the products carrying their raw fp32 sums from chunk to chunk
+// (CsmArgs::part_in / part_out: 8.5 MB per hand-over against 66 MB of spectrogram per chunk).
+static int csm_chunks(const ds_ctx* c, const CsmCall& q) { return std::min(c->cfg.csm_chunks, q.n_frames / 64); }
 // frame f of a chunk that starts at frame f0 is frame f0 + f of the signal: the chunk's transform reads x + f0 hop
 static bool pad_ok_for_chunks(int64_t n_samples, int hop, int n_frames) {
     return (int64_t)(n_frames - 1) * hop < n_samples;  // every chunk starts inside the signal
 }
-static int csm_chunked(ds_ctx* c, const float* x, int n_ch, int64_t ld, int64_t n_samples, int W, int hop, int n_frames,
-                       const float* window, int detrend, int amp_sqrt, double norm_scale, double factor, int halve_edges,
-                       int K, float2* csm) {
-    const int nb = W / 2 + 1;
+static int csm_chunked_run(ds_ctx* c, const CsmCall& q) {
+    const int nb = q.W / 2 + 1, n_ch = q.n_ch, n_frames = q.n_frames, hop = q.hop, K = csm_chunks(c, q);
     const size_t part_elems = (size_t)nb * n_ch * n_ch;
     float2 *X, *part;
     CHK(carve(c, &c->ws, &c->ws_bytes, [&](Carver& cv) {
@@ -1857,12 +2258,12 @@ static int csm_chunked(ds_ctx* c, const float* x, int n_ch, int64_t ld, int64_t 
     for (int k = 0; k < K && rc == DS_OK; ++k) {
         const int f0 = (int)((int64_t)k * n_frames / K), f1 = (int)((int64_t)(k + 1) * n_frames / K), fk = f1 - f0;
         float2* Xk = X + (size_t)nb * f0 * n_ch;  // chunk k: [nb][fk][n_ch]
-        rc = ds_stft_r2c_dev(c, x + (int64_t)f0 * hop, n_samples - (int64_t)f0 * hop, n_ch, ld, W, hop, W, 0, fk, window, detrend,
-                             1.0f, 1.0f, 0, (ds_c32*)Xk);
+        rc = ds_stft_r2c_dev(c, q.x + (int64_t)f0 * hop, q.n_samples - (int64_t)f0 * hop, n_ch, q.ld, q.W, hop, q.W, 0, fk,
+                             q.window, q.detrend, 1.0f, 1.0f, 0, (ds_c32*)Xk);
         if (rc != DS_OK) break;
         HIPCHK(c, hipEventRecord(c->ev_chunk[k], main_stream));
         HIPCHK(c, hipStreamWaitEvent(c->side, c->ev_chunk[k], 0));
-        CsmArgs a{Xk, n_ch, fk, FinishPar{norm_scale / (double)n_frames, factor, halve_edges, amp_sqrt, nb}, csm, 0};
+        CsmArgs a{Xk, n_ch, fk, FinishPar{q.norm_scale / (double)n_frames, q.factor, q.halve_edges, q.amp_sqrt, nb}, q.csm, 0};
         a.part_in = k > 0 ? part : nullptr;
         a.part_out = k + 1 < K ? part : nullptr;
         c->stream = c->side;  // launch() enqueues on the context's stream
@@ -1875,114 +2276,66 @@ static int csm_chunked(ds_ctx* c, const float* x, int n_ch, int64_t ld, int64_t 
     return rc;
 }
 
-static int csm_dev(ds_ctx* c, const float* x, int n_ch, int64_t ld, int64_t n_samples, int W, int hop,
-                   int n_frames, const float* window, int detrend, int average, int amp_sqrt,
-                   double norm_scale, double factor, int halve_edges, int bin_start, int bin_count,
-                   ds_c32* csm) {
-    if (!c || !x || !window || !csm) return fail(c, DS_ERR_ARG, "ds_csm: null argument");
-    if (n_ch < 1 || n_samples <= 0 || hop <= 0 || hop > W || n_frames <= 0 || ld < n_samples)
-        return fail(c, DS_ERR_ARG, "ds_csm: bad shape");
-    if (average != DS_AVG_MEAN && average != DS_AVG_MEDIAN)
-        return fail(c, DS_ERR_ARG, "ds_csm: average must be mean (0) or median (1)");
-    const bool big = W > kMaxFft && is_pow2(W);
-    if (!big) CHK(check_fft_len(c, W, "ds_csm window length"));
-    const int nb = W / 2 + 1;
-    const bool all_bins = bin_start == 0 && bin_count == nb;
-    if (bin_start < 0 || bin_count <= 0 || bin_start + bin_count > nb)
-        return fail(c, DS_ERR_ARG, "ds_csm: bad bin range");
-    if (average == DS_AVG_MEDIAN && !all_bins)
-        return fail(c, DS_ERR_UNSUP, "ds_csm: a bin range with median averaging is not built yet");
-    if (average == DS_AVG_MEDIAN) {
-        // spectra of every frame [c][F][nb] -> per-pair, per-bin medians
-        size_t lds = 0;
-        const int bpb = median_bins_per_block(2, n_frames, &lds);
-        if (!bpb)
-            return fail(c, DS_ERR_UNSUP, "ds_csm: median averaging over more than 19 199 frames is not built yet");
-        WelchPlan pl = plan_welch(n_frames, n_ch);
-        float2* xsp;
-        BigScratch s;
-        float* scratch;
-        CHK(carve(c, &c->ws, &c->ws_bytes, [&](Carver& cv) {
-            xsp = cv.take<float2>((size_t)n_ch * n_frames * nb);
-            if (big) s = take_big_scratch(cv, n_ch, n_frames, W);
-            else scratch = cv.take<float>((size_t)pl.n_chunks * n_ch * nb);
-        }));
-        if (big) {
-            CHK(stft_big(c, s, x, n_ch, ld, n_samples, W, hop, W, 0, n_frames, window, detrend, 1.0f, 1.0f, 0, 0, xsp));
-        } else {
-            const float2* tw;
-            CHK(get_twiddles(c, W, &tw));
-            XspecArgs ax{x, n_samples, ld, n_ch, W, hop, n_frames, detrend, pl.fpc, window, tw, xsp, scratch};
-            DISPATCH_N(W, CHK(launch(c, "welch_xspec", k_xspec<NN>, dim3(pl.n_chunks, n_ch), Cfg<NN>::NT, Cfg<NN>::LDS_BYTES, ax)));
-        }
-        const int nbias = (n_frames & 1) ? n_frames : n_frames - 1;
-        CsmMedianArgs m{xsp, n_ch, n_frames, bpb,
-                        FinishPar{norm_scale * (double)std::max(1, nbias), factor, halve_edges, amp_sqrt, nb},
-                        (float2*)csm};
-        CHK(launch(c, "csm_median", k_csm_median, dim3((nb + bpb - 1) / bpb, n_ch * (n_ch + 1) / 2), 256, lds, m));
-        return DS_OK;
-    }
-    // Round 5: the 64-microphone shape in frame chunks on two streams.  Transform and product are both streams of the
-    // spectrogram X (written once, read once: 4.9 x the algorithmic bytes of the step, and each kernel alone reaches
-    // 0.4 of the HBM roofline); with the frames cut into chunks the transform of chunk k + 1 (main stream) runs beside
-    // the product of chunk k (side stream), the products carrying their raw fp32 sums from chunk to chunk
-    // (CsmArgs::part_in / part_out: 8.5 MB per hand-over against 66 MB of spectrogram per chunk).
-    {
-        const int K = std::min(c->cfg.csm_chunks, n_frames / 64);  // >= 64 frames per chunk
-        if (K >= 2 && !big && all_bins && n_ch <= 64 && nb >= 3 && !c->cfg.csm_generic && !c->cfg.csm_f32 &&
-            csmb3::fits(n_ch, n_frames) && pad_ok_for_chunks(n_samples, hop, n_frames))
-            return csm_chunked(c, x, n_ch, ld, n_samples, W, hop, n_frames, window, detrend, amp_sqrt, norm_scale, factor,
-                               halve_edges, K, (float2*)csm);
-    }
-    // the STFT buffer X[b][f][c] (+ the four-step scratch for long windows) in the workspace
+// the STFT X[b][f][c] (+ the four-step scratch for long windows) in the workspace, then one of the products
+static int csm_gemm_run(ds_ctx* c, const CsmCall& q) {
+    const int nb = q.W / 2 + 1, n_ch = q.n_ch;
     float2* X;
     BigScratch s;
     CHK(carve(c, &c->ws, &c->ws_bytes, [&](Carver& cv) {
-        X = cv.take<float2>((size_t)nb * n_frames * n_ch);
-        if (big) s = take_big_scratch(cv, n_ch, n_frames, W);
+        X = cv.take<float2>((size_t)nb * q.n_frames * n_ch);
+        if (q.big()) s = take_big_scratch(cv, n_ch, q.n_frames, q.W);
     }));
-    if (big)
-        CHK(stft_big(c, s, x, n_ch, ld, n_samples, W, hop, W, 0, n_frames, window, detrend, 1.0f, 1.0f, 0, 1, X));
+    if (q.big())
+        CHK(stft_big(c, s, q.x, n_ch, q.ld, q.n_samples, q.W, q.hop, q.W, 0, q.n_frames, q.window, q.detrend, 1.0f, 1.0f, 0, 1, X));
     else
-        CHK(ds_stft_r2c_dev(c, x, n_samples, n_ch, ld, W, hop, W, 0, n_frames, window, detrend, 1.0f, 1.0f,
+        CHK(ds_stft_r2c_dev(c, q.x, q.n_samples, n_ch, q.ld, q.W, q.hop, q.W, 0, q.n_frames, q.window, q.detrend, 1.0f, 1.0f,
                             0, (ds_c32*)X));
-    const int nt = (n_ch + 31) / 32;
-    CsmArgs a{X, n_ch, n_frames,
-              FinishPar{norm_scale / (double)n_frames, factor, halve_edges, amp_sqrt, nb},
-              (float2*)csm, bin_start};
+    CsmArgs a{X, n_ch, q.n_frames, FinishPar{q.norm_scale / (double)q.n_frames, q.factor, q.halve_edges, q.amp_sqrt, nb},
+              q.csm, q.bin_start};
+    // matrix-core products from 8 frames on (DSPTOOLBOX_AMD_CSM_GENERIC=1: never); b3: from bf16 triples on the 16 x faster
+    // bf16 matrix pipe (kernels_csm_b3.hpp; DSPTOOLBOX_AMD_CSM_F32=1 keeps the fp32 matrix instructions)
+    const bool mfma = q.n_frames >= 8 && !c->cfg.csm_generic, b3 = mfma && !c->cfg.csm_f32;
     // up to 64 channels: one workgroup per bin shares the operand loads between the three tile
     // pairs (the spectra of an even-length real transform are purely real at both edge bins,
     // which the kernel relies on)
-    const bool no64 = c->cfg.csm_generic;
-    // the same product from bf16 triples on the 16 x faster bf16 matrix pipe
-    // (kernels_csm_b3.hpp; DSPTOOLBOX_AMD_CSM_F32=1 keeps the fp32 matrix instructions)
-    const bool f32_only = c->cfg.csm_f32;
-    const bool one_wg_per_bin = all_bins && n_ch <= 64 && n_frames >= 8 && nb >= 3 && !no64;
-    if (one_wg_per_bin && !f32_only && csmb3::fits(n_ch, n_frames))
-        CHK(launch(c, "csm_gemm@b3", csmb3::k_csm_gemm64_b3, dim3(nb - 1), 256, 0, a));
-    else if (one_wg_per_bin)
-        CHK(launch(c, "csm_gemm@f32", k_csm_gemm64, dim3(nb - 1), 256, 0, a));
-    else if (!all_bins && n_ch <= 64 && n_frames >= 8 && !no64 && !f32_only && csmb3::fits(n_ch, n_frames))
-        CHK(launch(c, "csm_gemm@b3_range", csmb3::k_csm_gemm64_b3_range, dim3(bin_count), 256, 0, a));
-    else if (n_ch > 64 && n_frames >= 8 && !no64 && !f32_only && csmb3::fits_groups(n_ch, n_frames)) {
+    if (n_ch <= 64 && mfma && q.all_bins() && nb >= 3) {
+        if (b3 && csmb3::fits(n_ch, q.n_frames)) return launch(c, "csm_gemm@b3", csmb3::k_csm_gemm64_b3, dim3(nb - 1), 256, 0, a);
+        return launch(c, "csm_gemm@f32", k_csm_gemm64, dim3(nb - 1), 256, 0, a);
+    }
+    if (n_ch <= 64 && b3 && !q.all_bins() && csmb3::fits(n_ch, q.n_frames))
+        return launch(c, "csm_gemm@b3_range", csmb3::k_csm_gemm64_b3_range, dim3(q.bin_count), 256, 0, a);
+    if (n_ch > 64 && b3 && csmb3::fits_groups(n_ch, q.n_frames)) {
         // groups of 64 channels: the diagonal blocks, then the blocks below the diagonal (two workgroups each)
         const int ng = (n_ch + 63) / 64;
         a.n_groups = ng;
-        a.n_groups_bins = bin_count;
-        CHK(launch(c, "csm_gemm@group_b3", csmb3::k_csm_group_b3, dim3(bin_count, ng), 256, 0, a));
-        CHK(launch(c, "csm_gemm_offdiag", csmb3::k_csm_offdiag_b3, dim3(16 * ((bin_count + 7) / 8), ng * (ng - 1) / 2),
-                   256, 0, a));
+        a.n_groups_bins = q.bin_count;
+        CHK(launch(c, "csm_gemm@group_b3", csmb3::k_csm_group_b3, dim3(q.bin_count, ng), 256, 0, a));
+        return launch(c, "csm_gemm_offdiag", csmb3::k_csm_offdiag_b3, dim3(16 * ((q.bin_count + 7) / 8), ng * (ng - 1) / 2),
+                      256, 0, a);
     }
-    else
-        CHK(launch(c, "csm_gemm@generic", k_csm_gemm, dim3(bin_count, nt * (nt + 1) / 2), 256, 0, a));
-    return DS_OK;
+    const int nt = (n_ch + 31) / 32;
+    return launch(c, "csm_gemm@generic", k_csm_gemm, dim3(q.bin_count, nt * (nt + 1) / 2), 256, 0, a);
+}
+
+using CsmRunner = int (*)(ds_ctx*, const CsmCall&);
+// The runner of a checked call: medians, the frame-chunked product (DSPTOOLBOX_AMD_CSM_CHUNKS), or transform + product
+static CsmRunner csm_route(const ds_ctx* c, const CsmCall& q) {
+    if (q.average == DS_AVG_MEDIAN) return csm_median_run;
+    if (csm_chunks(c, q) >= 2 && !q.big() && q.all_bins() && q.n_ch <= 64 && q.W / 2 + 1 >= 3 && !c->cfg.csm_generic &&
+        !c->cfg.csm_f32 && csmb3::fits(q.n_ch, q.n_frames) && pad_ok_for_chunks(q.n_samples, q.hop, q.n_frames))
+        return csm_chunked_run;
+    return csm_gemm_run;
+}
+static int csm_dev(ds_ctx* c, const CsmCall& q) {
+    CHK(csm_check(c, q));
+    return csm_route(c, q)(c, q);
 }
 
 extern "C" int ds_csm_dev(ds_ctx* c, const float* x, int n_ch, int64_t ld, int64_t n_samples, int W,
                           int hop, int n_frames, const float* window, int detrend, int average,
                           int amp_sqrt, double norm_scale, double factor, int halve_edges, ds_c32* csm) {
-    return csm_dev(c, x, n_ch, ld, n_samples, W, hop, n_frames, window, detrend, average, amp_sqrt, norm_scale,
-                   factor, halve_edges, 0, W / 2 + 1, csm);
+    return csm_dev(c, {"ds_csm_dev", x, n_ch, ld, n_samples, W, hop, n_frames, window, detrend, average, amp_sqrt, norm_scale,
+                       factor, halve_edges, 0, W / 2 + 1, (float2*)csm});
 }
 
 // bins [bin_start, bin_start + bin_count) only (csm_dev[0] = matrix of bin_start): the multi-GPU
@@ -1991,8 +2344,8 @@ extern "C" int ds_csm_bins_dev(ds_ctx* c, const float* x, int n_ch, int64_t ld, 
                                int hop, int n_frames, const float* window, int detrend, int amp_sqrt,
                                double norm_scale, double factor, int halve_edges, int bin_start,
                                int bin_count, ds_c32* csm) {
-    return csm_dev(c, x, n_ch, ld, n_samples, W, hop, n_frames, window, detrend, DS_AVG_MEAN, amp_sqrt,
-                   norm_scale, factor, halve_edges, bin_start, bin_count, csm);
+    return csm_dev(c, {"ds_csm_bins_dev", x, n_ch, ld, n_samples, W, hop, n_frames, window, detrend, DS_AVG_MEAN, amp_sqrt,
+                       norm_scale, factor, halve_edges, bin_start, bin_count, (float2*)csm});
 }
 
 extern "C" int ds_csm_spec_dev(ds_ctx* c, const ds_c32* X, int n_bins, int n_frames, int n_ch,
@@ -2177,385 +2530,22 @@ extern "C" int ds_bf_cleansc(ds_ctx* c, const double* csm, const double* h, int 
     return ds_download(c, map, dm, nm * 8);
 }
 
-// ---- four-step FFT for 2^15 .. 2^24 points (kernels_bigfft.hpp) -------------------
-static int big_rows_ct(int n2) {
-    int nt = dsfft::threads_for(n2);
-    size_t per = (size_t)(((n2 + n2 / 16 + 2 + 30) / 32) * 32 + 1) * sizeof(float2);
-    int ct = std::min<int>({16, 1024 / nt, std::max<int>(1, (int)((70 * 1024) / per))});
-    while (ct & (ct - 1)) ct &= ct - 1;  // power of two: must divide N1
-    return ct;
-}
-
-// cols stage: source = complex `zin` (may equal `zout`) or real channel pairs
-static int big_cols(ds_ctx* c, const float2* zin, const float* xreal, int n_ch, int64_t ld_real,
-                    int64_t n_samples, float2* zout, int64_t N, int batch) {
-    constexpr int N1 = 1024;
-    const int n2 = (int)(N / N1);
-    const float2* tw;
-    CHK(get_twiddles(c, N1, &tw));
-    const int ct = std::min(8, n2);
-    dsbig::ColsArgs a{zin, xreal, nullptr, n_samples, 0, zout, N, n2, ct, 0, ld_real, n_ch, tw};
-    size_t lds = (size_t)ct * dsbig::ch_stride<N1>() * sizeof(float2);
-    CHK(launch(c, "bigfft_cols", dsbig::k_big_cols<N1>, dim3(n2 / ct, batch), ct * Cfg<N1>::NT, lds, a));
-    return DS_OK;
-}
-
-static int big_rows(ds_ctx* c, const float2* zin, float2* zout, int64_t N, int batch) {
-    constexpr int N1 = 1024;
-    const int n2 = (int)(N / N1);
-    const float2* tw;
-    CHK(get_twiddles(c, n2, &tw));
-    const int ct = big_rows_ct(n2);
-    dsbig::RowsArgs a{zin, zout, N, N1, ct, tw};
-    size_t lds = 0;
-    DISPATCH_N(n2, lds = (size_t)ct * dsbig::ch_stride<NN>() * sizeof(float2));
-    DISPATCH_N(n2, CHK(launch(c, "bigfft_rows", dsbig::k_big_rows<NN>, dim3(N1 / ct, batch), ct * Cfg<NN>::NT, lds, a)));
-    return DS_OK;
-}
-
-static int check_big_len(ds_ctx* c, int64_t n, const char* what) {
-    if (!is_pow2(n)) return fail(c, DS_ERR_ARG, std::string(what) + ": internal: not a power of two");
-    if (n > kMaxBigFft) return fail(c, DS_ERR_UNSUP, std::string(what) + ": lengths above 2^24 are not built yet");
-    return DS_OK;
-}
-
-static int rfft_big(ds_ctx* c, const float* x, int n_ch, int64_t ld, int64_t n_samples, int64_t N,
-                    float scale, float2* spec) {
-    const int npair = (n_ch + 1) / 2;
-    float2 *P, *Q;
-    CHK(carve(c, &c->ws, &c->ws_bytes, [&](Carver& cv) {
-        P = cv.take<float2>((size_t)npair * N);
-        Q = cv.take<float2>((size_t)npair * N);
-    }));
-    CHK(big_cols(c, nullptr, x, n_ch, ld, n_samples, P, N, npair));
-    CHK(big_rows(c, P, Q, N, npair));
-    dsbig::UnpackArgs u{Q, N, n_ch, scale, spec, n_ch, 1};
-    CHK(launch(c, "bigfft_unpack", dsbig::k_big_unpack, dim3(1024, npair), 256, 0, u));
-    return DS_OK;
-}
-
-static int deconv_big(ds_ctx* c, const float* y, int n_items, int n_ch, int64_t ld, int64_t n_samples,
-                      int64_t N, const float2* r, int r_per_channel, int64_t n_out, int64_t ld_out,
-                      float* ir) {
-    const int npair = (n_ch + 1) / 2, batch = n_items * npair;
-    float2 *P, *Q;
-    CHK(carve(c, &c->ws, &c->ws_bytes, [&](Carver& cv) {
-        P = cv.take<float2>((size_t)batch * N);
-        Q = cv.take<float2>((size_t)batch * N);
-    }));
-    CHK(big_cols(c, nullptr, y, n_ch, ld, n_samples, P, N, batch));
-    CHK(big_rows(c, P, Q, N, batch));
-    dsbig::MulArgs m{Q, N, n_ch, r_per_channel, r};
-    CHK(launch(c, "bigfft_mul", dsbig::k_big_mul, dim3(1024, batch), 256, 0, m));
-    CHK(big_cols(c, Q, nullptr, n_ch, 0, 0, Q, N, batch));
-    CHK(big_rows(c, Q, P, N, batch));
-    dsbig::StoreArgs st{P, N, n_out, ld_out, n_ch, ir};
-    CHK(launch(c, "bigfft_store", dsbig::k_big_store, dim3(1024, batch), 256, 0, st));
-    return DS_OK;
-}
-
-// ---- framed transforms beyond the LDS-resident FFT (window / FFT length 2^15 .. 2^24) ------
-// Frame pairs of every channel are one batch of four-step complex FFTs, processed in groups
-// of <= 2^25 complex points per scratch buffer.
-static int64_t stft_big_group(int64_t nfft, int64_t batch) {
-    return std::max<int64_t>(1, std::min<int64_t>({batch, ((int64_t)1 << 25) / nfft, (int64_t)32768}));
-}
-static BigScratch take_big_scratch(Carver& cv, int n_ch, int n_frames, int64_t nfft) {
-    const int64_t grp = stft_big_group(nfft, (int64_t)n_ch * ((n_frames + 1) / 2));
-    BigScratch s;
-    s.P = cv.take<float2>((size_t)grp * nfft);
-    s.Q = cv.take<float2>((size_t)grp * nfft);
-    s.means = cv.take<float>((size_t)n_ch * n_frames);
-    return s;
-}
-// layout 0: out[(c*F + f)*nb + k] (unscaled spectra for the Welch sums), 1: out[(k*F + f)*C + c]
-// s: take_big_scratch() for at least n_ch channels and n_frames frames
-static int stft_big(ds_ctx* c, const BigScratch& s, const float* x, int n_ch, int64_t ld, int64_t n_samples,
-                    int W, int hop, int64_t nfft, int64_t pad_front, int n_frames, const float* window,
-                    int detrend, float scale, float edge_scale, int power, int layout, float2* out) {
-    CHK(check_big_len(c, nfft, "framed transform length"));
-    constexpr int N1 = 1024;
-    const int n2 = (int)(nfft / N1);
-    const int64_t batch = (int64_t)n_ch * ((n_frames + 1) / 2);
-    const int64_t grp = stft_big_group(nfft, batch);
-    float2 *P = s.P, *Q = s.Q;
-    float* means = s.means;
-    if (detrend) {
-        dsbig::FrameMeansArgs m{x, n_samples, ld, pad_front, n_ch, W, hop, n_frames, window, means};
-        CHK(launch(c, "bigfft_means", dsbig::k_frame_means, dim3(n_frames, n_ch), 256, 0, m));
-    }
-    const float2* tw;
-    CHK(get_twiddles(c, N1, &tw));
-    const int ct = std::min(8, n2);
-    const size_t lds = (size_t)ct * dsbig::ch_stride<N1>() * sizeof(float2);
-    for (int64_t b0 = 0; b0 < batch; b0 += grp) {
-        const int nb = (int)std::min<int64_t>(grp, batch - b0);
-        dsbig::ColsArgs a{nullptr, x, nullptr, n_samples, 0, P, nfft, n2, ct, 0, ld, n_ch, tw,
-                          window, detrend ? means : nullptr, W, hop, n_frames, pad_front, b0};
-        CHK(launch(c, "bigfft_cols", dsbig::k_big_cols<N1>, dim3(n2 / ct, nb), ct * Cfg<N1>::NT, lds, a));
-        CHK(big_rows(c, P, Q, nfft, nb));
-        dsbig::UnpackFramesArgs u{Q, nfft, b0, n_ch, n_frames, layout, power, scale, edge_scale, out};
-        CHK(launch(c, "bigfft_unpack", dsbig::k_big_unpack_frames, dim3(64, nb), 256, 0, u));
-    }
-    return DS_OK;
-}
-
-// Welch for window lengths beyond the LDS-resident FFT: spectra of every frame -> frame sums
-// (or per-bin medians) -> the usual finish
-static int welch_big(ds_ctx* c, int kind, const float* x, int n_cx, int64_t ldx, const float* y,
-                     int n_cy, int64_t ldy, int64_t n_samples, int W, int hop, int n_frames,
-                     const float* window, int detrend, int average, int mode, int amp_sqrt,
-                     double norm_scale, double factor, int halve_edges, float2* out_c, float* out_r) {
-    const int nb = W / 2 + 1;
-    const int nyc = kind == 1 ? 0 : n_cy;
-    const int nmax = std::max(n_cx, nyc);
-    size_t med_lds = 0;
-    const int med_bpb = median_bins_per_block(3, n_frames, &med_lds);
-    if (average == DS_AVG_MEDIAN && !med_bpb)
-        return fail(c, DS_ERR_UNSUP, "welch: median averaging over more than 12 799 frames is not built yet");
-    float2 *xsp, *ysp, *pxy;
-    float *pxx, *pyy;
-    BigScratch s;  // the FFT scratch is reused by both signals
-    CHK(carve(c, &c->ws, &c->ws_bytes, [&](Carver& cv) {
-        xsp = cv.take<float2>((size_t)n_cx * n_frames * nb);
-        ysp = cv.take<float2>((size_t)std::max(1, nyc) * n_frames * nb);
-        pxx = cv.take<float>((size_t)n_cx * nb);
-        pxy = cv.take<float2>((size_t)std::max(1, nyc) * nb);
-        pyy = cv.take<float>((size_t)std::max(1, nyc) * nb);
-        s = take_big_scratch(cv, nmax, n_frames, W);
-    }));
-    CHK(stft_big(c, s, x, n_cx, ldx, n_samples, W, hop, W, 0, n_frames, window, detrend, 1.0f, 1.0f, 0,
-                 0, xsp));
-    if (nyc) {
-        CHK(stft_big(c, s, y, nyc, ldy, n_samples, W, hop, W, 0, n_frames, window, detrend, 1.0f, 1.0f,
-                     0, 0, ysp));
-    }
-    double count = (double)n_frames;
-    if (average == DS_AVG_MEDIAN) {
-        MedianArgs m{xsp, nyc ? ysp : nullptr, n_cx, nyc, n_frames, nb, kind, med_bpb, pxx, pxy, pyy};
-        CHK(launch(c, "welch_median", k_welch_median, dim3((nb + med_bpb - 1) / med_bpb, kind == 1 ? n_cx : n_cy), 256,
-                   med_lds, m));
-        const int nbias = (n_frames & 1) ? n_frames : n_frames - 1;
-        count = 1.0 / (double)std::max(1, nbias);
-    } else {
-        dsbig::SpecSumArgs sa{xsp, nyc ? ysp : nullptr, n_cx, nyc, n_frames, nb, kind, pxx, pxy, pyy};
-        CHK(launch(c, "welch_specsum", dsbig::k_spec_sum, dim3((nb + 255) / 256, kind == 1 ? n_cx : n_cy), 256, 0, sa));
-    }
-    WelchFinArgs f{pxx, pxy, pyy, 1, 1, n_cx, n_cy, kind, mode,
-                   FinishPar{norm_scale / count, factor, halve_edges, amp_sqrt, nb}, out_c, out_r};
-    return launch_finish(c, f);
-}
-
-// ---- arbitrary lengths: Bluestein on top of the four-step FFT ------------------------
-static int64_t blue_len(int64_t L) {
-    int64_t m = (int64_t)1 << 15;  // smallest four-step length
-    while (m < 2 * L - 1) m <<= 1;
-    return m;
-}
-
-static int blue_filter(ds_ctx* c, int64_t L, int64_t M, const float2** out) {
-    auto key = std::make_pair(L, M);
-    auto it = c->blue.find(key);
-    if (it != c->blue.end()) {
-        it->second.stamp = ++c->blue_clock;
-        *out = it->second.ptr;
-        return DS_OK;
-    }
-    const size_t bytes = sizeof(float2) * (size_t)M;
-    // make room: drop the least recently used tables (hipFree waits for the device, so a table
-    // still referenced by queued kernels of an earlier call is never pulled from under them)
-    while (!c->blue.empty() && c->blue_bytes + bytes > c->cfg.bluestein_cache_bytes) {
-        auto lru = c->blue.begin();
-        for (auto jt = c->blue.begin(); jt != c->blue.end(); ++jt)
-            if (jt->second.stamp < lru->second.stamp) lru = jt;
-        HIPCHK(c, hipFree(lru->second.ptr));
-        c->blue_bytes -= lru->second.bytes;
-        c->blue.erase(lru);
-    }
-    float2 *bt = nullptr, *bf = nullptr;
-    HIPCHK(c, hipMalloc((void**)&bt, bytes));
-    if (hipMalloc((void**)&bf, bytes) != hipSuccess) {
-        (void)hipFree(bt);
-        return fail(c, DS_ERR_NOMEM, "Bluestein filter table: hipMalloc failed");
-    }
-    int rc = DS_OK;
-    do {
-        hipLaunchKernelGGL(dsblue::k_filter, dim3(1024), dim3(256), 0, c->stream, bt, L, M);
-        if (hipGetLastError() != hipSuccess) { rc = fail(c, DS_ERR_HIP, "Bluestein filter kernel launch failed"); break; }
-        if ((rc = big_cols(c, bt, nullptr, 0, 0, 0, bt, M, 1)) != DS_OK) break;
-        if ((rc = big_rows(c, bt, bf, M, 1)) != DS_OK) break;
-        if (hipStreamSynchronize(c->stream) != hipSuccess) { rc = fail(c, DS_ERR_HIP, "Bluestein filter: stream sync failed"); break; }
-    } while (0);
-    (void)hipFree(bt);
-    if (rc != DS_OK) {
-        (void)hipFree(bf);
-        return rc;
-    }
-    c->blue[key] = ds_ctx::BlueEntry{bf, bytes, ++c->blue_clock};
-    c->blue_bytes += bytes;
-    *out = bf;
-    return DS_OK;
-}
-
-// X[batch][L] = DFT_L of (real channel pairs | complex zin[batch][L]); P, Q: [batch][M] scratch
-static int blue_dft(ds_ctx* c, const float* xreal, int n_ch, int64_t ld_real, int64_t n_samples,
-                    const float2* zin, int batch, int64_t L, int64_t M, float2* P, float2* Q, float2* X) {
-    const float2* bf;
-    CHK(blue_filter(c, L, M, &bf));
-    dsblue::PreArgs pa{xreal, ld_real, n_samples, n_ch, zin, P, L, M};
-    CHK(launch(c, "blue_pre", dsblue::k_pre, dim3(512, batch), 256, 0, pa));
-    CHK(big_cols(c, P, nullptr, 0, 0, 0, P, M, batch));
-    CHK(big_rows(c, P, Q, M, batch));
-    hipLaunchKernelGGL(dsblue::k_mul_filter, dim3(512, batch), dim3(256), 0, c->stream, Q, bf, M);
-    HIPCHK(c, hipGetLastError());
-    CHK(big_cols(c, Q, nullptr, 0, 0, 0, Q, M, batch));
-    CHK(big_rows(c, Q, P, M, batch));
-    hipLaunchKernelGGL(dsblue::k_post, dim3(512, batch), dim3(256), 0, c->stream, (const float2*)P, X, L, M);
-    HIPCHK(c, hipGetLastError());
-    return DS_OK;
-}
-
-static int check_blue_len(ds_ctx* c, int64_t L, const char* what) {
-    if (L < 2) return fail(c, DS_ERR_ARG, std::string(what) + ": length must be >= 2");
-    if (2 * L - 1 > kMaxBigFft) return fail(c, DS_ERR_UNSUP, std::string(what) + ": non-power-of-two lengths above 2^23 are not built yet");
-    return DS_OK;
-}
-
-static int rfft_blue(ds_ctx* c, const float* x, int n_ch, int64_t ld, int64_t n_samples, int64_t L,
-                     float scale, float2* spec) {
-    const int npair = (n_ch + 1) / 2;
-    const int64_t M = blue_len(L);
-    float2 *P, *Q, *X;
-    CHK(carve(c, &c->ws, &c->ws_bytes, [&](Carver& cv) {
-        P = cv.take<float2>((size_t)npair * M);
-        Q = cv.take<float2>((size_t)npair * M);
-        X = cv.take<float2>((size_t)npair * L);
-    }));
-    CHK(blue_dft(c, x, n_ch, ld, n_samples, nullptr, npair, L, M, P, Q, X));
-    hipLaunchKernelGGL(dsblue::k_unpack, dim3(512, npair), dim3(256), 0, c->stream, (const float2*)X, L, n_ch,
-                       scale, spec);
-    HIPCHK(c, hipGetLastError());
-    return DS_OK;
-}
-
-static int deconv_blue(ds_ctx* c, const float* y, int n_items, int n_ch, int64_t ld, int64_t n_samples,
-                       int64_t L, const float2* r, int r_per_channel, int64_t n_out, int64_t ld_out,
-                       float* ir) {
-    const int npair = (n_ch + 1) / 2, batch = n_items * npair;
-    const int64_t M = blue_len(L);
-    float2 *P, *Q, *X, *Y;
-    CHK(carve(c, &c->ws, &c->ws_bytes, [&](Carver& cv) {
-        P = cv.take<float2>((size_t)batch * M);
-        Q = cv.take<float2>((size_t)batch * M);
-        X = cv.take<float2>((size_t)batch * L);
-        Y = cv.take<float2>((size_t)batch * L);
-    }));
-    CHK(blue_dft(c, y, n_ch, ld, n_samples, nullptr, batch, L, M, P, Q, X));
-    hipLaunchKernelGGL(dsblue::k_mul_r, dim3(512, batch), dim3(256), 0, c->stream, X, L, n_ch, r_per_channel, r);
-    HIPCHK(c, hipGetLastError());
-    CHK(blue_dft(c, nullptr, n_ch, 0, 0, X, batch, L, M, P, Q, Y));
-    hipLaunchKernelGGL(dsblue::k_store, dim3(512, batch), dim3(256), 0, c->stream, (const float2*)Y, L, n_out,
-                       ld_out, n_ch, ir);
-    HIPCHK(c, hipGetLastError());
-    return DS_OK;
-}
-
-// ---- whole-signal rFFT, deconvolution ---------------------------------------
-extern "C" int ds_rfft_dev(ds_ctx* c, const float* x, int n_ch, int64_t ld, int64_t n_samples,
-                           int n_fft, float scale, ds_c32* spec) {
-    if (!c || !x || !spec) return fail(c, DS_ERR_ARG, "ds_rfft: null argument");
-    if (n_ch <= 0 || n_samples <= 0 || ld < n_samples || n_samples > n_fft)
-        return fail(c, DS_ERR_ARG, "ds_rfft: bad shape (n_samples must be <= n_fft)");
-    if (!is_pow2(n_fft)) {
-        CHK(check_blue_len(c, n_fft, "ds_rfft n_fft"));
-        return rfft_blue(c, x, n_ch, ld, n_samples, n_fft, scale, (float2*)spec);
-    }
-    if (n_fft > kMaxFft) {
-        CHK(check_big_len(c, n_fft, "ds_rfft n_fft"));
-        return rfft_big(c, x, n_ch, ld, n_samples, n_fft, scale, (float2*)spec);
-    }
-    CHK(check_fft_len(c, n_fft, "ds_rfft n_fft"));
-    const float2* tw;
-    CHK(get_twiddles(c, n_fft, &tw));
-    RfftArgs a{x, n_samples, ld, n_ch, tw, scale, (float2*)spec};
-    DISPATCH_N(n_fft, CHK(launch(c, "rfft", k_rfft<NN>, dim3((n_ch + 1) / 2), Cfg<NN>::NT, Cfg<NN>::LDS_BYTES, a)));
-    return DS_OK;
-}
-
-extern "C" int ds_deconv_inverse_dev(ds_ctx* c, const ds_c32* xspec, int n_ch, int n_bins,
-                                     const float* eps, ds_c32* r) {
-    if (!c || !xspec || !r || n_ch <= 0 || n_bins <= 0)
-        return fail(c, DS_ERR_ARG, "ds_deconv_inverse: bad argument");
-    int64_t total = (int64_t)n_ch * n_bins;
-    hipLaunchKernelGGL(k_deconv_inverse, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, c->stream,
-                       (const float2*)xspec, n_ch, n_bins, eps, (float2*)r);
-    HIPCHK(c, hipGetLastError());
-    return DS_OK;
-}
-
-extern "C" int ds_deconv_dev(ds_ctx* c, const float* y, int n_items, int n_ch, int64_t ld,
-                             int64_t n_samples, int n_fft, const ds_c32* r, int r_per_channel,
-                             int64_t n_out, int64_t ld_out, float* ir) {
-    if (!c || !y || !r || !ir) return fail(c, DS_ERR_ARG, "ds_deconv: null argument");
-    if (n_items <= 0 || n_ch <= 0 || n_samples <= 0 || ld < n_samples || n_samples > n_fft ||
-        n_out <= 0 || n_out > n_fft || ld_out < n_out)
-        return fail(c, DS_ERR_ARG, "ds_deconv: bad shape");
-    if (!is_pow2(n_fft)) {
-        CHK(check_blue_len(c, n_fft, "ds_deconv n_fft"));
-        return deconv_blue(c, y, n_items, n_ch, ld, n_samples, n_fft, (const float2*)r, r_per_channel, n_out,
-                           ld_out, ir);
-    }
-    if (n_fft > kMaxFft) {
-        CHK(check_big_len(c, n_fft, "ds_deconv n_fft"));
-        return deconv_big(c, y, n_items, n_ch, ld, n_samples, n_fft, (const float2*)r, r_per_channel,
-                          n_out, ld_out, ir);
-    }
-    CHK(check_fft_len(c, n_fft, "ds_deconv n_fft"));
-    const bool no8k = c->cfg.deconv_generic;
-    if (n_fft == deconv8k::N && !r_per_channel && !no8k) {
-        // 8192 points, one inverse spectrum for all channels: two register-resident 4096-point
-        // transforms per channel pair, the packed spectrum multiplied directly (kernels_deconv8k.hpp)
-        CHK(ensure_table(c, &c->w4_tables, welch4096::host_tables));
-        CHK(ensure_table(c, &c->deconv8k_tables, deconv8k::host_tables));
-        deconv8k::Args a8{y, n_samples, ld, n_out, ld_out, n_ch, c->w4_tables, c->deconv8k_tables,
-                          (const float2*)r, ir};
-        // one 256-thread group per channel pair, its two sub-spectra one after the other: three independent
-        // workgroups per CU (k_deconv3); DSPTOOLBOX_AMD_DECONV_2PERCU=1 keeps the 512-thread kernel (A/B)
-        // default since round 5: two persistent workgroups per CU, the next unit's samples in flight during this unit's
-        // transforms, the inverse spectrum from a permuted copy (k_rperm + k_deconv_p); DSPTOOLBOX_AMD_DECONV_PERSIST=0
-        // keeps the one-unit-per-workgroup kernels below
-        const int64_t n_units = (int64_t)((n_ch + 1) / 2) * n_items;
-        // (n_units + grid stays an int inside the kernel: u + gridDim.x is formed for the prefetch past the last unit)
-        if (c->cfg.deconv_persist && !c->cfg.deconv_2percu && n_units < ((int64_t)1 << 31) - 4096 && c->n_cu > 0) {
-            if (!c->deconv_rperm) HIPCHK(c, hipMalloc((void**)&c->deconv_rperm, sizeof(float2) * deconv8k::RPERM_LEN));
-            CHK(launch(c, "deconv_rperm", deconv8k::k_rperm, dim3(32), 256, 0, deconv8k::RpArgs{(const float2*)r, c->deconv_rperm}));
-            deconv8k::PArgs pa{a8, c->deconv_rperm, (int)n_units};
-            const int grid = (int)std::min<int64_t>(n_units, 2 * (int64_t)c->n_cu);
-            return launch(c, "deconv@8k_persist", deconv8k::k_deconv_p, dim3((unsigned)grid), 256, deconv8k::LDS_BYTES_3, pa);
-        }
-        const bool two = c->cfg.deconv_2percu;
-        // four workgroups per CU (k_deconv3q: all 1024 pairs of the benchmark resident at once) unless
-        // DSPTOOLBOX_AMD_DECONV_4PERCU=0 (k_deconv3: three, 168 registers)
-        const bool four = c->cfg.deconv_4percu;
-        if (!two && four && (int64_t)((n_ch + 1) / 2) * n_items < ((int64_t)1 << 31))
-            return launch(c, "deconv@8k_4percu", deconv8k::k_deconv3q, dim3((unsigned)(((n_ch + 1) / 2) * n_items)), 256,
-                          deconv8k::LDS_BYTES_3, a8);
-        if (!two && (int64_t)((n_ch + 1) / 2) * n_items < ((int64_t)1 << 31))
-            return launch(c, "deconv@8k_3percu", deconv8k::k_deconv3, dim3((unsigned)(((n_ch + 1) / 2) * n_items)), 256,
-                          deconv8k::LDS_BYTES_3, a8);
-        CHK(launch(c, "deconv@8k_512", deconv8k::k_deconv, dim3((n_ch + 1) / 2, n_items), deconv8k::NTB,
-                   deconv8k::LDS_BYTES, a8));
-        return DS_OK;
-    }
-    const float2* tw;
-    CHK(get_twiddles(c, n_fft, &tw));
-    DeconvArgs a{y, n_samples, ld, n_out, ld_out, n_ch, r_per_channel, tw, (const float2*)r, ir};
-    dim3 grid((n_ch + 1) / 2, n_items);
-    DISPATCH_N(n_fft, CHK(launch(c, "deconv@generic", k_deconv<NN>, grid, Cfg<NN>::NT, Cfg<NN>::LDS_BYTES, a)));
-    return DS_OK;
-}
-
 // ---- FIR ---------------------------------------------------------------------
+// One call of ds_fir_ola_dev, checked by fir_check (`who`: the entry called); the runners apply the parallel mode
+struct FirCall {
+    const char* who;
+    const float* x; int n_ch; int64_t ldx, n_samples; const float* taps; int n_filt, n_taps, mode; float* y; int64_t ld_y;
+};
+static int fir_check(ds_ctx* c, const FirCall& f) {
+    const std::string w(f.who);
+    if (!c || !f.x || !f.taps || !f.y) return fail(c, DS_ERR_ARG, w + ": null argument");
+    if (f.n_ch <= 0 || f.n_samples <= 0 || f.n_filt <= 0 || f.n_taps <= 0 || f.ldx < f.n_samples || f.ld_y < f.n_samples)
+        return fail(c, DS_ERR_ARG, w + ": bad shape");
+    if (f.mode != DS_FB_PARALLEL && f.mode != DS_FB_SUMMED && f.mode != DS_FB_SEQUENTIAL)
+        return fail(c, DS_ERR_ARG, w + ": invalid filter bank apply mode");
+    return DS_OK;
+}
+
 static int fir_block_len(int n_taps, int v = 0) {  // v: forced block length (DSPTOOLBOX_AMD_FIR_BLOCK), 0 = none
     int n = 1024;
     while (n < 4 * n_taps && n < kMaxFft) n <<= 1;
@@ -2567,13 +2557,114 @@ static int fir_block_len(int n_taps, int v = 0) {  // v: forced block length (DS
     return n;
 }
 
+// a signal shorter than the filter (or a tiny one): the direct sum in float64 -- no rounding floor set by the block's
+// peak, which is what an FFT convolution leaves on an output far below (peak of the block) x (size of the taps)
+// (kernels_freqz.hpp; DESIGN section 2, limit (x))
+static int fir_direct_run(ds_ctx* c, const FirCall& f) {
+    freqz::DirectArgs a{f.x, f.taps, f.n_samples, f.ldx, f.ld_y, f.n_ch, f.n_taps, f.y};
+    return launch(c, "fir@direct_f64", freqz::k_fir_direct, dim3((unsigned)((f.n_samples + 255) / 256), f.n_ch, f.n_filt), 256,
+                  0, a);
+}
+
+// Up to 4097 taps: uniformly partitioned overlap-save on the 4096-point register transform, three independent
+// workgroups per CU (kernels_fir4k.hpp; two partitions: k_fir3 since round 5, DSPTOOLBOX_AMD_FIR_3PERCU=0 keeps the
+// two-per-CU k_fir<2> with its tap-spectrum prefetch).
+static int fir4k_run(ds_ctx* c, const FirCall& f) {
+    namespace f4 = fir4k;
+    CHK(ensure_table(c, &c->w4_tables, welch4096::host_tables));
+    const int P = f4::partitions(f.n_taps);
+    float4* hp;
+    CHK(carve(c, &c->ws, &c->ws_bytes, [&](Carver& cv) { hp = cv.take<float4>((size_t)f.n_filt * P * 8 * 256); }));
+    f4::TapArgs ta{f.taps, f.n_filt, f.n_taps, P, c->w4_tables, hp};
+    CHK(launch(c, "fir_taps", f4::k_taps, dim3((unsigned)(f.n_filt * P)), f4::NT, f4::LDS_BYTES, ta));
+    const int pairs = (f.n_ch + 1) / 2;
+    const int n_blocks = (int)((f.n_samples + f4::HOP - 1) / f4::HOP);
+    // every workgroup resident at once (3 or 2 per CU): a run of blocks each, one extra forward
+    // transform per run with two partitions
+    const bool three = P == 2 && c->cfg.fir_3percu && !c->cfg.fir_stage;
+    int chunks = std::max(1, ((P == 1 || three) ? 768 : 512) / pairs);
+    if (c->cfg.fir_chunks > 0) chunks = c->cfg.fir_chunks;
+    chunks = std::min(chunks, n_blocks);
+    f4::Args a{f.x, f.n_samples, f.ldx, f.ld_y, f.n_ch, f.n_filt, n_blocks, chunks, c->w4_tables, hp, f.y};
+    const dim3 grid((unsigned)(pairs * chunks));
+    if (c->cfg.fir_stage) {  // round-5 experiment: stores through a per-wave LDS strip (profiles/r05_fir_staged_stores.txt)
+        if (P == 1) return launch(c, "fir@4k_p1_staged", f4::k_fir<1, true>, grid, f4::NT, f4::LDS_BYTES + f4::STAGE_BYTES, a);
+        return launch(c, "fir@4k_p2_staged", f4::k_fir<2, true>, grid, f4::NT, f4::LDS_BYTES + f4::STAGE_BYTES, a);
+    }
+    if (P == 1) return launch(c, "fir@4k_p1", f4::k_fir<1>, grid, f4::NT, f4::LDS_BYTES, a);
+    if (three) return launch(c, "fir@4k_p2_3percu", f4::k_fir3<0>, grid, f4::NT, f4::LDS_BYTES, a);
+    return launch(c, "fir@4k_p2", f4::k_fir<2>, grid, f4::NT, f4::LDS_BYTES, a);
+}
+
+// tap spectra of N-point blocks, hs[n_filt][N] (perm: room for their permuted copy behind them)
+static int fir_block_taps(ds_ctx* c, const FirCall& f, int N, bool perm, const float2** tw, float2** hs, float2** hperm) {
+    CHK(get_twiddles(c, N, tw));
+    CHK(carve(c, &c->ws, &c->ws_bytes, [&](Carver& cv) {
+        *hs = cv.take<float2>((size_t)f.n_filt * N);
+        *hperm = perm ? cv.take<float2>((size_t)f.n_filt * N) : nullptr;
+    }));
+    FirTapsArgs a{f.taps, f.n_filt, f.n_taps, *tw, *hs};
+    DISPATCH_N(N, CHK(launch(c, "fir_taps", k_fir_taps<NN>, dim3((f.n_filt + 1) / 2), Cfg<NN>::NT, Cfg<NN>::LDS_BYTES, a)));
+    return DS_OK;
+}
+
+// 16384-point blocks: four 4096-point register transforms per block (kernels_fir16k.hpp)
+static int fir16k_run(ds_ctx* c, const FirCall& f) {
+    const int N = fir16k::NBIG;
+    const float2* tw;
+    float2 *hs, *hperm;
+    CHK(fir_block_taps(c, f, N, true, &tw, &hs, &hperm));
+    const int L = N - (f.n_taps - 1);
+    const int64_t n_blocks = (f.n_samples + L - 1) / L;
+    const int pairs = (f.n_ch + 1) / 2;
+    CHK(ensure_table(c, &c->w4_tables, welch4096::host_tables));
+    CHK(ensure_table(c, &c->fir16k_tables, fir16k::host_tables));
+    fir16k::PermArgs pa{hs, f.n_filt, hperm};
+    CHK(launch(c, "fir_taps", fir16k::k_permute, dim3((unsigned)(((int64_t)f.n_filt * N + 255) / 256)), 256, 0, pa));
+    fir16k::Args a{f.x, f.n_samples, f.ldx, f.ld_y, f.n_ch, f.n_filt, f.n_taps, c->w4_tables, c->fir16k_tables, hperm, f.y, 0};
+    // interior blocks of a 4097-tap filter with 16-byte aligned rows: the store-everything variant
+    int64_t n_plain = 0;
+    if (((f.n_taps - 1) & 3) == 0 && (f.ld_y & 3) == 0 && (((uintptr_t)f.y) & 15) == 0) n_plain = f.n_samples / L;
+    const bool ragged = n_blocks > n_plain;
+    if (n_plain == 0) {
+        return launch(c, "fir@16k_ragged", fir16k::k_fir<false>, dim3((unsigned)n_blocks, pairs), fir16k::NTB,
+                      fir16k::LDS_BYTES, a);
+    }
+    // The few ragged blocks go to the side stream so they run beside the main grid's last,
+    // partly filled round instead of after it (fork after the tap spectra, join at the end).
+    if (ragged) {
+        HIPCHK(c, hipFuncSetAttribute((const void*)fir16k::k_fir<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      (int)fir16k::LDS_BYTES));
+        HIPCHK(c, hipEventRecord(c->ev_fork, c->stream));
+        HIPCHK(c, hipStreamWaitEvent(c->side, c->ev_fork, 0));
+        fir16k::Args ar = a;
+        ar.block0 = (int)n_plain;
+        hipLaunchKernelGGL(fir16k::k_fir<false>, dim3((unsigned)(n_blocks - n_plain), pairs), dim3(fir16k::NTB),
+                           fir16k::LDS_BYTES, c->side, ar);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipEventRecord(c->ev_join, c->side));
+    }
+    // one workgroup per CU: split the filter loop over 1, 2 or 4 workgroups per block when that
+    // fills the last round better (cost ~ rounds x (filters per slice + 1 forward transform))
+    int split = 1;
+    for (int64_t s = 1, best = -1, wgs = n_plain * pairs; s <= 4 && s <= f.n_filt; s *= 2) {
+        const int64_t cost = ((wgs * s + 255) / 256) * ((f.n_filt + s - 1) / s + 1);
+        if (best < 0 || cost < best) best = cost, split = (int)s;
+    }
+    if (c->cfg.fir_split > 0) split = std::min(c->cfg.fir_split, f.n_filt);
+    CHK(launch(c, "fir@16k", fir16k::k_fir<true>, dim3((unsigned)n_plain, pairs, split), fir16k::NTB, fir16k::LDS_BYTES, a));
+    if (ragged) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_join, 0));
+    return DS_OK;
+}
+
 // Long filters (more taps than half the largest LDS-resident block): overlap-save on the
 // four-step FFT with blocks of 2^15 .. 2^24 points.  Per block: one forward transform of the
 // channel pairs, then groups of filters: multiply by the tap spectra, inverse, store.
-static int fir_long(ds_ctx* c, const float* x, int n_ch, int64_t ldx, int64_t n_samples,
-                    const float* taps, int n_filt, int n_taps, float* y, int64_t ld_y) {
+static int fir_long_run(ds_ctx* c, const FirCall& f) {
+    const int n_ch = f.n_ch, n_filt = f.n_filt, n_taps = f.n_taps;
+    const int64_t n_samples = f.n_samples;
     if ((int64_t)n_taps - 1 > kMaxBigFft / 2)
-        return fail(c, DS_ERR_UNSUP, "ds_fir_ola: more than 2^23 + 1 taps is not built yet");
+        return fail(c, DS_ERR_UNSUP, std::string(f.who) + ": more than 2^23 + 1 taps is not built yet");
     int64_t L = (int64_t)1 << 15;
     while (L < 4 * (int64_t)n_taps && L < kMaxBigFft) L <<= 1;
     while (L > ((int64_t)1 << 15) && L / 2 >= n_samples + n_taps - 1) L >>= 1;  // short signals: one block
@@ -2588,24 +2679,17 @@ static int fir_long(ds_ctx* c, const float* x, int n_ch, int64_t ldx, int64_t n_
         P = cv.take<float2>(scratch);
         S = cv.take<float2>(scratch);
     }));
-    constexpr int N1 = 1024;
-    const int n2 = (int)(L / N1);
-    const float2* tw;
-    CHK(get_twiddles(c, N1, &tw));
-    const int ct = std::min(8, n2);
-    const size_t lds = (size_t)ct * dsbig::ch_stride<N1>() * sizeof(float2);
     // tap spectra R[k][nb], 2*G*npair filters per pass through the scratch buffers
     for (int k0 = 0; k0 < n_filt; k0 += 2 * G * npair) {
         const int nf = std::min(2 * G * npair, n_filt - k0), bt = (nf + 1) / 2;
-        CHK(big_cols(c, nullptr, taps + (int64_t)k0 * n_taps, nf, n_taps, n_taps, P, L, bt));
+        CHK(big_cols(c, nullptr, f.taps + (int64_t)k0 * n_taps, nf, n_taps, n_taps, P, L, bt));
         CHK(big_rows(c, P, S, L, bt));
         dsbig::UnpackArgs u{S, L, nf, 1.0f, R + (int64_t)k0 * nb, 1, nb};
         CHK(launch(c, "bigfft_unpack", dsbig::k_big_unpack, dim3(1024, bt), 256, 0, u));
     }
     for (int64_t b0 = 0; b0 < n_samples; b0 += step) {
-        dsbig::ColsArgs a{nullptr, x, nullptr, n_samples, 0, P, L, n2, ct, 0, ldx, n_ch, tw,
-                          nullptr, nullptr, 0, 0, 0, 0, 0, b0 - (n_taps - 1)};
-        CHK(launch(c, "bigfft_cols", dsbig::k_big_cols<N1>, dim3(n2 / ct, npair), ct * Cfg<N1>::NT, lds, a));
+        CHK(launch_big_cols(c, {nullptr, f.x, nullptr, n_samples, 0, P, L, 0, 0, 0, f.ldx, n_ch, nullptr,
+                                nullptr, nullptr, 0, 0, 0, 0, 0, b0 - (n_taps - 1)}, npair));
         CHK(big_rows(c, P, Qs, L, npair));  // spectrum of the block, kept while the filter groups reuse P / S
         const int64_t n_out = std::min<int64_t>(step, n_samples - b0);
         for (int k0 = 0; k0 < n_filt; k0 += G) {
@@ -2614,133 +2698,42 @@ static int fir_long(ds_ctx* c, const float* x, int n_ch, int64_t ldx, int64_t n_
             CHK(launch(c, "bigfft_mul", dsbig::k_big_mul_bank, dim3(1024, bt), 256, 0, m));
             CHK(big_cols(c, P, nullptr, n_ch, 0, 0, P, L, bt));
             CHK(big_rows(c, P, S, L, bt));
-            dsbig::StoreArgs st{S, L, n_out, ld_y, n_ch, y + (int64_t)k0 * n_ch * ld_y + b0, (int64_t)n_taps - 1};
+            dsbig::StoreArgs st{S, L, n_out, f.ld_y, n_ch, f.y + (int64_t)k0 * n_ch * f.ld_y + b0, (int64_t)n_taps - 1};
             CHK(launch(c, "bigfft_store", dsbig::k_big_store, dim3(1024, bt), 256, 0, st));
         }
     }
     return DS_OK;
 }
 
-// Up to 4097 taps: uniformly partitioned overlap-save on the 4096-point register transform, three independent
-// workgroups per CU (kernels_fir4k.hpp; two partitions: k_fir3 since round 5, DSPTOOLBOX_AMD_FIR_3PERCU=0 keeps the
-// two-per-CU k_fir<2> with its tap-spectrum prefetch).
-// DSPTOOLBOX_AMD_FIR_4K=0 keeps the block kernels below (A/B); =1 also sends the short filters here.
-static int fir4k_run(ds_ctx* c, const float* x, int n_ch, int64_t ldx, int64_t n_samples, const float* taps,
-                     int n_filt, int n_taps, float* y, int64_t ld_y) {
-    namespace f4 = fir4k;
-    CHK(ensure_table(c, &c->w4_tables, welch4096::host_tables));
-    const int P = f4::partitions(n_taps);
-    float4* hp;
-    CHK(carve(c, &c->ws, &c->ws_bytes, [&](Carver& cv) { hp = cv.take<float4>((size_t)n_filt * P * 8 * 256); }));
-    f4::TapArgs ta{taps, n_filt, n_taps, P, c->w4_tables, hp};
-    CHK(launch(c, "fir_taps", f4::k_taps, dim3((unsigned)(n_filt * P)), f4::NT, f4::LDS_BYTES, ta));
-    const int pairs = (n_ch + 1) / 2;
-    const int n_blocks = (int)((n_samples + f4::HOP - 1) / f4::HOP);
-    // every workgroup resident at once (3 or 2 per CU): a run of blocks each, one extra forward
-    // transform per run with two partitions
-    const bool three = P == 2 && c->cfg.fir_3percu && !c->cfg.fir_stage;
-    int chunks = std::max(1, ((P == 1 || three) ? 768 : 512) / pairs);
-    if (c->cfg.fir_chunks > 0) chunks = c->cfg.fir_chunks;
-    chunks = std::min(chunks, n_blocks);
-    f4::Args a{x, n_samples, ldx, ld_y, n_ch, n_filt, n_blocks, chunks, c->w4_tables, hp, y};
-    if (c->cfg.fir_stage) {  // round-5 experiment: stores through a per-wave LDS strip (profiles/r05_fir_staged_stores.txt)
-        if (P == 1)
-            return launch(c, "fir@4k_p1_staged", f4::k_fir<1, true>, dim3((unsigned)(pairs * chunks)), f4::NT, f4::LDS_BYTES + f4::STAGE_BYTES, a);
-        return launch(c, "fir@4k_p2_staged", f4::k_fir<2, true>, dim3((unsigned)(pairs * chunks)), f4::NT, f4::LDS_BYTES + f4::STAGE_BYTES, a);
-    }
-    if (P == 1) return launch(c, "fir@4k_p1", f4::k_fir<1>, dim3((unsigned)(pairs * chunks)), f4::NT, f4::LDS_BYTES, a);
-    if (three) return launch(c, "fir@4k_p2_3percu", f4::k_fir3<0>, dim3((unsigned)(pairs * chunks)), f4::NT, f4::LDS_BYTES, a);
-    return launch(c, "fir@4k_p2", f4::k_fir<2>, dim3((unsigned)(pairs * chunks)), f4::NT, f4::LDS_BYTES, a);
-}
-
-static int fir_once(ds_ctx* c, const float* x, int n_ch, int64_t ldx, int64_t n_samples,
-                    const float* taps, int n_filt, int n_taps, float* y, int64_t ld_y) {
-    // a signal shorter than the filter (or a tiny one): the direct sum in float64 -- no rounding floor set by the block's
-    // peak, which is what an FFT convolution leaves on an output far below (peak of the block) x (size of the taps)
-    // (kernels_freqz.hpp; DESIGN section 2, limit (x)).  At most 2^28 multiply-adds.
-    // Every output sample is one thread's sum over min(n_samples, n_taps) products: at most 16384 of them (a 2^20-tap
-    // filter on 256 samples would be 256 threads of a million dependent steps each).  DSPTOOLBOX_AMD_FIR_DIRECT=0 turns
-    // the route off (A/B against the FFT routes on the same shape).
-    if (c->cfg.fir_direct && (n_samples < n_taps || n_samples <= 512) && std::min<int64_t>(n_samples, n_taps) <= 16384 &&
-        n_samples * std::min<int64_t>(n_samples, n_taps) * n_ch * n_filt <= ((int64_t)1 << 28) && n_filt <= 65535 && n_ch <= 65535) {
-        freqz::DirectArgs a{x, taps, n_samples, ldx, ld_y, n_ch, n_taps, y};
-        return launch(c, "fir@direct_f64", freqz::k_fir_direct, dim3((unsigned)((n_samples + 255) / 256), n_ch, n_filt), 256, 0, a);
-    }
-    if (n_taps >= c->cfg.fir4k_min_taps && fir4k::partitions(n_taps) <= 2 && fir4k::fits(n_samples) && n_filt <= 16384)
-        return fir4k_run(c, x, n_ch, ldx, n_samples, taps, n_filt, n_taps, y, ld_y);
-    const int N = fir_block_len(n_taps, c->cfg.fir_block);
-    if (n_taps - 1 > N / 2) return fir_long(c, x, n_ch, ldx, n_samples, taps, n_filt, n_taps, y, ld_y);
+// every other block length: the LDS-resident transform (kernels_generic.hpp)
+static int fir_generic_run(ds_ctx* c, const FirCall& f) {
+    const int N = fir_block_len(f.n_taps, c->cfg.fir_block);
     const float2* tw;
-    CHK(get_twiddles(c, N, &tw));
-    const bool no16k = c->cfg.fir_generic;
-    const bool use16k = N == fir16k::NBIG && !no16k;
-    float2 *hs, *hperm;  // tap spectra (16384-point blocks: and their permuted copy)
-    CHK(carve(c, &c->ws, &c->ws_bytes, [&](Carver& cv) {
-        hs = cv.take<float2>((size_t)n_filt * N);
-        hperm = use16k ? cv.take<float2>((size_t)n_filt * N) : nullptr;
-    }));
-    {
-        FirTapsArgs a{taps, n_filt, n_taps, tw, hs};
-        DISPATCH_N(N, CHK(launch(c, "fir_taps", k_fir_taps<NN>, dim3((n_filt + 1) / 2), Cfg<NN>::NT, Cfg<NN>::LDS_BYTES, a)));
-    }
-    const int L = N - (n_taps - 1);
-    const int64_t n_blocks = (n_samples + L - 1) / L;
-    if (use16k) {
-        // 16384-point blocks: four 4096-point register transforms per block (kernels_fir16k.hpp)
-        CHK(ensure_table(c, &c->w4_tables, welch4096::host_tables));
-        CHK(ensure_table(c, &c->fir16k_tables, fir16k::host_tables));
-        fir16k::PermArgs pa{hs, n_filt, hperm};
-        CHK(launch(c, "fir_taps", fir16k::k_permute, dim3((unsigned)(((int64_t)n_filt * N + 255) / 256)), 256, 0, pa));
-        fir16k::Args a{x, n_samples, ldx, ld_y, n_ch, n_filt, n_taps, c->w4_tables, c->fir16k_tables, hperm, y, 0};
-        // interior blocks of a 4097-tap filter with 16-byte aligned rows: the store-everything variant
-        int64_t n_plain = 0;
-        if (((n_taps - 1) & 3) == 0 && (ld_y & 3) == 0 && (((uintptr_t)y) & 15) == 0) n_plain = n_samples / L;
-        // The few ragged blocks go to the side stream so they run beside the main grid's last,
-        // partly filled round instead of after it (fork after the tap spectra, join at the end).
-        const bool ragged = n_blocks > n_plain;
-        if (ragged && n_plain > 0) {
-            HIPCHK(c, hipFuncSetAttribute((const void*)fir16k::k_fir<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                          (int)fir16k::LDS_BYTES));
-            HIPCHK(c, hipEventRecord(c->ev_fork, c->stream));
-            HIPCHK(c, hipStreamWaitEvent(c->side, c->ev_fork, 0));
-            fir16k::Args ar = a;
-            ar.block0 = (int)n_plain;
-            hipLaunchKernelGGL(fir16k::k_fir<false>, dim3((unsigned)(n_blocks - n_plain), (n_ch + 1) / 2),
-                               dim3(fir16k::NTB), fir16k::LDS_BYTES, c->side, ar);
-            HIPCHK(c, hipGetLastError());
-            HIPCHK(c, hipEventRecord(c->ev_join, c->side));
-        }
-        if (n_plain > 0) {
-            // one workgroup per CU: split the filter loop over 1, 2 or 4 workgroups per block when that
-            // fills the last round better (cost ~ rounds x (filters per slice + 1 forward transform))
-            int split = 1;
-            {
-                const int64_t wgs = n_plain * ((n_ch + 1) / 2);
-                int64_t best = -1;
-                for (int s = 1; s <= 4 && s <= n_filt; s *= 2) {
-                    const int64_t cost = ((wgs * s + 255) / 256) * ((n_filt + s - 1) / s + 1);
-                    if (best < 0 || cost < best) {
-                        best = cost;
-                        split = s;
-                    }
-                }
-                if (c->cfg.fir_split > 0) split = std::min(c->cfg.fir_split, n_filt);
-            }
-            CHK(launch(c, "fir@16k", fir16k::k_fir<true>, dim3((unsigned)n_plain, (n_ch + 1) / 2, split), fir16k::NTB,
-                       fir16k::LDS_BYTES, a));
-        }
-        if (ragged && n_plain > 0) {
-            HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_join, 0));
-        } else if (ragged) {
-            CHK(launch(c, "fir@16k_ragged", fir16k::k_fir<false>, dim3((unsigned)n_blocks, (n_ch + 1) / 2), fir16k::NTB,
-                       fir16k::LDS_BYTES, a));
-        }
-        return DS_OK;
-    }
-    FirArgs a{x, n_samples, ldx, ld_y, n_ch, n_filt, n_taps, tw, hs, y};
-    dim3 grid((unsigned)n_blocks, (n_ch + 1) / 2);
+    float2 *hs, *hperm;
+    CHK(fir_block_taps(c, f, N, false, &tw, &hs, &hperm));
+    const int L = N - (f.n_taps - 1);
+    FirArgs a{f.x, f.n_samples, f.ldx, f.ld_y, f.n_ch, f.n_filt, f.n_taps, tw, hs, f.y};
+    const dim3 grid((unsigned)((f.n_samples + L - 1) / L), (f.n_ch + 1) / 2);
     DISPATCH_N(N, CHK(launch(c, "fir@generic", k_fir<NN>, grid, Cfg<NN>::NT, Cfg<NN>::LDS_BYTES, a)));
     return DS_OK;
+}
+
+using FirRunner = int (*)(ds_ctx*, const FirCall&);
+// The kernel family of a checked parallel-mode call.
+static FirRunner fir_route(const ds_ctx* c, const FirCall& f) {
+    // The direct sum: at most 2^28 multiply-adds, every output sample one thread's sum over min(n_samples, n_taps)
+    // products, at most 16384 of them (a 2^20-tap filter on 256 samples would be 256 threads of a million dependent steps
+    // each).  DSPTOOLBOX_AMD_FIR_DIRECT=0 turns the route off (A/B against the FFT routes on the same shape).
+    const int64_t terms = std::min<int64_t>(f.n_samples, f.n_taps);
+    if (c->cfg.fir_direct && (f.n_samples < f.n_taps || f.n_samples <= 512) && terms <= 16384 &&
+        f.n_samples * terms * f.n_ch * f.n_filt <= ((int64_t)1 << 28) && f.n_filt <= 65535 && f.n_ch <= 65535)
+        return fir_direct_run;
+    // DSPTOOLBOX_AMD_FIR_4K=0 keeps the block kernels below (A/B); =1 also sends the short filters to fir4k
+    if (f.n_taps >= c->cfg.fir4k_min_taps && fir4k::partitions(f.n_taps) <= 2 && fir4k::fits(f.n_samples) && f.n_filt <= 16384)
+        return fir4k_run;
+    const int N = fir_block_len(f.n_taps, c->cfg.fir_block);
+    if (f.n_taps - 1 > N / 2) return fir_long_run;
+    return N == fir16k::NBIG && !c->cfg.fir_generic ? fir16k_run : fir_generic_run;
 }
 
 __global__ void k_sum_taps(const float* taps, int n_filt, int n_taps, float* out) {
@@ -2769,67 +2762,75 @@ __global__ void k_conv_taps(const double* a, int na, const float* b, int nb, dou
     out[n] = s;
 }
 
-extern "C" int ds_fir_ola_dev(ds_ctx* c, const float* x, int n_ch, int64_t ldx, int64_t n_samples,
-                              const float* taps, int n_filt, int n_taps, int mode, float* y,
-                              int64_t ld_y) {
-    if (!c || !x || !taps || !y) return fail(c, DS_ERR_ARG, "ds_fir_ola: null argument");
-    if (n_ch <= 0 || n_samples <= 0 || n_filt <= 0 || n_taps <= 0 || ldx < n_samples || ld_y < n_samples)
-        return fail(c, DS_ERR_ARG, "ds_fir_ola: bad shape");
-    if (mode == DS_FB_PARALLEL) return fir_once(c, x, n_ch, ldx, n_samples, taps, n_filt, n_taps, y, ld_y);
+// a checked call in any bank mode: the summed and sequential banks are parallel-mode calls with one filter
+static int fir_bank(ds_ctx* c, const FirCall& f) {
+    if (f.mode == DS_FB_PARALLEL) return fir_route(c, f)(c, f);
+    const float* taps = f.taps;
+    const int n_filt = f.n_filt, n_taps = f.n_taps;
+    FirCall one = f;
+    one.n_filt = 1;
     // (combined taps and the cascade's intermediate signal live in the context's aux scratch: no
     // allocation, free or synchronisation per call; everything stays ordered on the stream)
-    if (mode == DS_FB_SUMMED) {
+    if (f.mode == DS_FB_SUMMED) {
         // sum_k (x * b_k) = x * (sum_k b_k): one filter with the summed taps
         CHK(reserve(c, &c->aux, &c->aux_bytes, sizeof(float) * (size_t)n_taps));
         float* bs = (float*)c->aux;
         hipLaunchKernelGGL(k_sum_taps, dim3((n_taps + 255) / 256), dim3(256), 0, c->stream, taps, n_filt, n_taps, bs);
         HIPCHK(c, hipGetLastError());
-        return fir_once(c, x, n_ch, ldx, n_samples, bs, 1, n_taps, y, ld_y);
+        one.taps = bs;
+        return fir_route(c, one)(c, one);
     }
-    if (mode == DS_FB_SEQUENTIAL) {
-        // ((x*b1)[:N]*b2)[:N]... = (x*(b1*b2*...))[:N] for causal filters: when the combined
-        // response fits one block transform, convolve the taps (fp64, on the device) and
-        // filter once -- no fp32 round trip of the intermediate signals through HBM.
-        const int64_t n_comb = (int64_t)n_filt * (n_taps - 1) + 1;
-        if (n_filt > 1 && n_comb - 1 <= kMaxBigFft / 2 && (double)n_comb * n_taps <= 1.0e10) {
-            double *pa, *pb;
-            float* bf;
-            CHK(carve(c, &c->aux, &c->aux_bytes, [&](Carver& cv) {
-                pa = cv.take<double>((size_t)n_comb);
-                pb = cv.take<double>((size_t)n_comb);
-                bf = cv.take<float>((size_t)n_comb);
-            }));
-            hipLaunchKernelGGL(k_taps_to_f64, dim3((n_taps + 255) / 256), dim3(256), 0, c->stream, taps, n_taps, pa);
-            int len = n_taps;
-            for (int k = 1; k < n_filt; ++k) {
-                int nl = len + n_taps - 1;
-                hipLaunchKernelGGL(k_conv_taps, dim3((nl + 255) / 256), dim3(256), 0, c->stream, pa, len,
-                                   taps + (int64_t)k * n_taps, n_taps, pb);
-                std::swap(pa, pb);
-                len = nl;
-            }
-            hipLaunchKernelGGL(k_f64_to_taps, dim3((len + 255) / 256), dim3(256), 0, c->stream, pa, len, bf);
-            HIPCHK(c, hipGetLastError());
-            return fir_once(c, x, n_ch, ldx, n_samples, bf, 1, len, y, ld_y);
+    // ((x*b1)[:N]*b2)[:N]... = (x*(b1*b2*...))[:N] for causal filters: when the combined
+    // response fits one block transform, convolve the taps (fp64, on the device) and
+    // filter once -- no fp32 round trip of the intermediate signals through HBM.
+    const int64_t n_comb = (int64_t)n_filt * (n_taps - 1) + 1;
+    if (n_filt > 1 && n_comb - 1 <= kMaxBigFft / 2 && (double)n_comb * n_taps <= 1.0e10) {
+        double *pa, *pb;
+        float* bf;
+        CHK(carve(c, &c->aux, &c->aux_bytes, [&](Carver& cv) {
+            pa = cv.take<double>((size_t)n_comb);
+            pb = cv.take<double>((size_t)n_comb);
+            bf = cv.take<float>((size_t)n_comb);
+        }));
+        hipLaunchKernelGGL(k_taps_to_f64, dim3((n_taps + 255) / 256), dim3(256), 0, c->stream, taps, n_taps, pa);
+        int len = n_taps;
+        for (int k = 1; k < n_filt; ++k) {
+            int nl = len + n_taps - 1;
+            hipLaunchKernelGGL(k_conv_taps, dim3((nl + 255) / 256), dim3(256), 0, c->stream, pa, len,
+                               taps + (int64_t)k * n_taps, n_taps, pb);
+            std::swap(pa, pb);
+            len = nl;
         }
-        // long cascades: stage by stage, each truncated to n_samples like the reference loop
-        float* tmp = nullptr;
-        if (n_filt > 1) {
-            CHK(reserve(c, &c->aux, &c->aux_bytes, sizeof(float) * (size_t)n_ch * n_samples));
-            tmp = (float*)c->aux;
-        }
-        const float* src = x;
-        int64_t lds = ldx;
-        for (int k = 0; k < n_filt; ++k) {
-            float* dst = ((n_filt - 1 - k) % 2 == 0) ? y : tmp;  // ping-pong, last stage lands in y
-            int64_t ldd = (dst == y) ? ld_y : n_samples;
-            CHK(fir_once(c, src, n_ch, lds, n_samples, taps + (int64_t)k * n_taps, 1, n_taps, dst, ldd));
-            src = dst;
-            lds = ldd;
-        }
-        return DS_OK;
+        hipLaunchKernelGGL(k_f64_to_taps, dim3((len + 255) / 256), dim3(256), 0, c->stream, pa, len, bf);
+        HIPCHK(c, hipGetLastError());
+        one.taps = bf;
+        one.n_taps = len;
+        return fir_route(c, one)(c, one);
     }
-    return fail(c, DS_ERR_ARG, "ds_fir_ola: invalid filter bank apply mode");
+    // long cascades: stage by stage, each truncated to n_samples like the reference loop
+    float* tmp = nullptr;
+    if (n_filt > 1) {
+        CHK(reserve(c, &c->aux, &c->aux_bytes, sizeof(float) * (size_t)f.n_ch * f.n_samples));
+        tmp = (float*)c->aux;
+    }
+    for (int k = 0; k < n_filt; ++k) {
+        float* dst = ((n_filt - 1 - k) % 2 == 0) ? f.y : tmp;  // ping-pong, last stage lands in y
+        one.taps = taps + (int64_t)k * n_taps;
+        one.y = dst;
+        one.ld_y = (dst == f.y) ? f.ld_y : f.n_samples;
+        CHK(fir_route(c, one)(c, one));
+        one.x = dst;
+        one.ldx = one.ld_y;
+    }
+    return DS_OK;
+}
+
+extern "C" int ds_fir_ola_dev(ds_ctx* c, const float* x, int n_ch, int64_t ldx, int64_t n_samples,
+                              const float* taps, int n_filt, int n_taps, int mode, float* y,
+                              int64_t ld_y) {
+    const FirCall f{"ds_fir_ola_dev", x, n_ch, ldx, n_samples, taps, n_filt, n_taps, mode, y, ld_y};
+    CHK(fir_check(c, f));
+    return fir_bank(c, f);
 }
 
 #if W4_TIMING
@@ -3009,19 +3010,20 @@ extern "C" int ds_istft_f64(ds_ctx* c, const double* stft_c128, int n_bins, int 
 // spec: (bins, channels)
 static int rfft_host(ds_ctx* c, const char* who, const float* x, const double* x64, int n_ch, int64_t n_samples,
                      int n_fft, float scale, ds_c32* spec, double* spec64) {
-    if (!c || (!x && !x64) || (!spec && !spec64)) return fail(c, DS_ERR_ARG, std::string(who) + ": null argument");
-    if (n_ch <= 0 || n_samples <= 0 || n_fft < (x64 ? 2 : 1)) return fail(c, DS_ERR_ARG, std::string(who) + ": bad shape");
+    // (the host pointers, only checked: the staged copies replace them below)
+    XformCall q{who, x ? x : (const float*)x64, 1, n_ch, n_samples, n_samples, n_fft, scale,
+                spec ? (float2*)spec : (float2*)spec64};
+    CHK(xform_check(c, q, false));
     const size_t no = (size_t)(n_fft / 2 + 1) * n_ch;
     float* dx;
-    float2* ds;
     CHK(carve(c, &c->io, &c->io_bytes, [&](Carver& cv) {
-        dx = cv.take<float>((size_t)n_ch * n_samples);
-        ds = cv.take<float2>(no);
+        q.x = dx = cv.take<float>((size_t)n_ch * n_samples);
+        q.spec = cv.take<float2>(no);
     }));
     CHK(upload_signal(c, x, x64, n_samples, n_ch, dx));
-    CHK(ds_rfft_dev(c, dx, n_ch, n_samples, n_samples, n_fft, scale, (ds_c32*)ds));
-    if (spec64) return download_widen(c, (const float*)ds, (int64_t)no * 2, spec64);
-    return ds_download(c, spec, ds, no * 8);
+    CHK(rfft_route(q)(c, q));
+    if (spec64) return download_widen(c, (const float*)q.spec, (int64_t)no * 2, spec64);
+    return ds_download(c, spec, q.spec, no * 8);
 }
 extern "C" int ds_rfft(ds_ctx* c, const float* x, int n_ch, int64_t n_samples, int n_fft, float scale,
                        ds_c32* spec) {
@@ -3034,45 +3036,61 @@ extern "C" int ds_rfft_f64(ds_ctx* c, const double* x, int n_ch, int64_t n_sampl
     return rfft_host(c, "ds_rfft_f64", nullptr, x, n_ch, n_samples, n_fft, scale, nullptr, spec_c128);
 }
 
+// y: (n_items, n_ch, n_samples) float32, ir: (n_items, n_ch, n_out) float32; or one item in the reference's layouts,
+// y64 (n_samples, n_ch) and ir64 (n_out, n_ch) float64
+static int deconv_host(ds_ctx* c, const char* who, const float* y, const double* y64, int n_items, int n_ch,
+                       int64_t n_samples, int n_fft, const ds_c32* r, int r_per_channel, int64_t n_out, float* ir,
+                       double* ir64) {
+    // (the host pointers, only checked: the staged copies replace them below)
+    XformCall q{who, y ? y : (const float*)y64, n_items, n_ch, n_samples, n_samples, n_fft, 1.0f, nullptr,
+                (const float2*)r, r_per_channel, n_out, n_out, ir ? ir : (float*)ir64};
+    CHK(xform_check(c, q, true));
+    const size_t nr = (size_t)(r_per_channel ? n_ch : 1) * (n_fft / 2 + 1), no = (size_t)n_items * n_ch * n_out;
+    float* dy;
+    float2* dr;
+    CHK(carve(c, &c->io, &c->io_bytes, [&](Carver& cv) {
+        q.x = dy = cv.take<float>((size_t)n_items * n_ch * n_samples);
+        q.r = dr = cv.take<float2>(nr);
+        q.ir = cv.take<float>(no);
+    }));
+    CHK(upload_signal(c, y, y64, n_samples, n_items * n_ch, dy));
+    CHK(ds_upload(c, dr, r, nr * 8));
+    CHK(deconv_route(c, q)(c, q));
+    if (ir64) return download_interleave(c, q.ir, n_out, n_ch, n_out, ir64);
+    return ds_download(c, ir, q.ir, no * 4);
+}
+extern "C" int ds_deconv(ds_ctx* c, const float* y, int n_items, int n_ch, int64_t n_samples, int n_fft,
+                         const ds_c32* r, int r_per_channel, int64_t n_out, float* ir) {
+    return deconv_host(c, "ds_deconv", y, nullptr, n_items, n_ch, n_samples, n_fft, r, r_per_channel, n_out, ir, nullptr);
+}
 // ds_deconv for ONE item in the reference's layouts: y (n_samples, n_ch) float64 in, the impulse responses
 // (n_out, n_ch) float64 out (_spectral_deconvolve, transfer_functions/_transfer_functions.py:19-42).
 extern "C" int ds_deconv_f64(ds_ctx* c, const double* y, int n_ch, int64_t n_samples, int n_fft, const ds_c32* r,
                              int r_per_channel, int64_t n_out, double* ir) {
-    if (!c || !y || !r || !ir) return fail(c, DS_ERR_ARG, "ds_deconv_f64: null argument");
-    if (n_ch <= 0 || n_samples <= 0 || n_fft < 2 || n_out <= 0 || n_out > n_fft) return fail(c, DS_ERR_ARG, "ds_deconv_f64: bad shape");
-    const size_t nr = (size_t)(r_per_channel ? n_ch : 1) * (n_fft / 2 + 1);
-    float *dy, *dout;
-    float2* dr;
-    CHK(carve(c, &c->io, &c->io_bytes, [&](Carver& cv) {
-        dy = cv.take<float>((size_t)n_ch * n_samples);
-        dr = cv.take<float2>(nr);
-        dout = cv.take<float>((size_t)n_ch * n_out);
-    }));
-    CHK(upload_signal(c, nullptr, y, n_samples, n_ch, dy));
-    CHK(ds_upload(c, dr, r, nr * 8));
-    CHK(ds_deconv_dev(c, dy, 1, n_ch, n_samples, n_samples, n_fft, (const ds_c32*)dr, r_per_channel, n_out, n_out, dout));
-    return download_interleave(c, dout, n_out, n_ch, n_out, ir);
+    return deconv_host(c, "ds_deconv_f64", nullptr, y, 1, n_ch, n_samples, n_fft, r, r_per_channel, n_out, nullptr, ir);
 }
 
 // y: (bands or 1, n_ch, n_samples) float32, or y64: (bands or 1, n_samples, n_ch) float64
 static int fir_ola_host(ds_ctx* c, const char* who, const float* x, const double* x64, int n_ch, int64_t n_samples,
                         const float* taps, int n_filt, int n_taps, int mode, float* y, double* y64) {
-    if (!c || (!x && !x64) || !taps || (!y && !y64)) return fail(c, DS_ERR_ARG, std::string(who) + ": null argument");
-    if (n_ch <= 0 || n_samples <= 0 || n_filt <= 0 || n_taps <= 0) return fail(c, DS_ERR_ARG, std::string(who) + ": bad shape");
+    // (the host pointers, only checked: the staged copies replace them below)
+    FirCall f{who, x ? x : (const float*)x64, n_ch, n_samples, n_samples, taps, n_filt, n_taps, mode, y ? y : (float*)y64,
+              n_samples};
+    CHK(fir_check(c, f));
     const int n_out = mode == DS_FB_PARALLEL ? n_filt : 1;
     const size_t nt = (size_t)n_filt * n_taps, no = (size_t)n_out * n_ch * n_samples;
-    float *dx, *dt, *dy;
+    float *dx, *dt;
     CHK(carve(c, &c->io, &c->io_bytes, [&](Carver& cv) {
-        dx = cv.take<float>((size_t)n_ch * n_samples);
-        dt = cv.take<float>(nt);
-        dy = cv.take<float>(no);
+        f.x = dx = cv.take<float>((size_t)n_ch * n_samples);
+        f.taps = dt = cv.take<float>(nt);
+        f.y = cv.take<float>(no);
     }));
     CHK(upload_signal(c, x, x64, n_samples, n_ch, dx));
     CHK(ds_upload(c, dt, taps, nt * 4));
-    CHK(ds_fir_ola_dev(c, dx, n_ch, n_samples, n_samples, dt, n_filt, n_taps, mode, dy, n_samples));
-    if (!y64) return ds_download(c, y, dy, no * 4);
+    CHK(fir_bank(c, f));
+    if (!y64) return ds_download(c, y, f.y, no * 4);
     for (int k = 0; k < n_out; ++k)
-        CHK(download_interleave(c, dy + (size_t)k * n_ch * n_samples, n_samples, n_ch, n_samples,
+        CHK(download_interleave(c, f.y + (size_t)k * n_ch * n_samples, n_samples, n_ch, n_samples,
                                 y64 + (size_t)k * n_samples * n_ch));
     return DS_OK;
 }
@@ -3199,56 +3217,36 @@ extern "C" int ds_welch_csd_f64(ds_ctx* c, const double* x, const double* y, int
                           norm_scale, factor, halve_edges, csd);
 }
 
-static int csm_host(ds_ctx* c, const float* x, const double* x64, int n_ch, int64_t n_samples, int W, int hop,
-                    int n_frames, const float* window, int detrend, int average, int amp_sqrt,
+static int csm_host(ds_ctx* c, const char* who, const float* x, const double* x64, int n_ch, int64_t n_samples, int W,
+                    int hop, int n_frames, const float* window, int detrend, int average, int amp_sqrt,
                     double norm_scale, double factor, int halve_edges, ds_c32* csm) {
-    if (!c || (!x && !x64) || !window || !csm) return fail(c, DS_ERR_ARG, "ds_csm: null argument");
-    if (n_ch <= 0 || n_samples <= 0 || W <= 0) return fail(c, DS_ERR_ARG, "ds_csm: bad shape");
+    // (the host pointers, only checked: the staged copies replace them below)
+    CsmCall q{who, x ? x : (const float*)x64, n_ch, n_samples, n_samples, W, hop, n_frames, window, detrend, average,
+              amp_sqrt, norm_scale, factor, halve_edges, 0, W / 2 + 1, (float2*)csm};
+    CHK(csm_check(c, q));
     const size_t no = (size_t)(W / 2 + 1) * n_ch * n_ch;
     float *dx, *dw;
-    float2* dc;
     CHK(carve(c, &c->io, &c->io_bytes, [&](Carver& cv) {
-        dx = cv.take<float>((size_t)n_ch * n_samples);
-        dw = cv.take<float>(W);
-        dc = cv.take<float2>(no);
+        q.x = dx = cv.take<float>((size_t)n_ch * n_samples);
+        q.window = dw = cv.take<float>(W);
+        q.csm = cv.take<float2>(no);
     }));
     CHK(upload_signal(c, x, x64, n_samples, n_ch, dx));
     CHK(ds_upload(c, dw, window, (size_t)W * 4));
-    CHK(ds_csm_dev(c, dx, n_ch, n_samples, n_samples, W, hop, n_frames, dw, detrend, average, amp_sqrt,
-                   norm_scale, factor, halve_edges, (ds_c32*)dc));
-    return ds_download(c, csm, dc, no * 8);
+    CHK(csm_route(c, q)(c, q));
+    return ds_download(c, csm, q.csm, no * 8);
 }
 extern "C" int ds_csm(ds_ctx* c, const float* x, int n_ch, int64_t n_samples, int W, int hop,
                       int n_frames, const float* window, int detrend, int average, int amp_sqrt,
                       double norm_scale, double factor, int halve_edges, ds_c32* csm) {
-    return csm_host(c, x, nullptr, n_ch, n_samples, W, hop, n_frames, window, detrend, average, amp_sqrt,
+    return csm_host(c, "ds_csm", x, nullptr, n_ch, n_samples, W, hop, n_frames, window, detrend, average, amp_sqrt,
                     norm_scale, factor, halve_edges, csm);
 }
 extern "C" int ds_csm_f64(ds_ctx* c, const double* x, int n_ch, int64_t n_samples, int W, int hop,
                           int n_frames, const float* window, int detrend, int average, int amp_sqrt,
                           double norm_scale, double factor, int halve_edges, ds_c32* csm) {
-    return csm_host(c, nullptr, x, n_ch, n_samples, W, hop, n_frames, window, detrend, average, amp_sqrt,
+    return csm_host(c, "ds_csm_f64", nullptr, x, n_ch, n_samples, W, hop, n_frames, window, detrend, average, amp_sqrt,
                     norm_scale, factor, halve_edges, csm);
-}
-
-extern "C" int ds_deconv(ds_ctx* c, const float* y, int n_items, int n_ch, int64_t n_samples, int n_fft,
-                         const ds_c32* r, int r_per_channel, int64_t n_out, float* ir) {
-    if (!c || !y || !r || !ir) return fail(c, DS_ERR_ARG, "ds_deconv: null argument");
-    if (n_items <= 0 || n_ch <= 0 || n_samples <= 0 || n_fft <= 0 || n_out <= 0) return fail(c, DS_ERR_ARG, "ds_deconv: bad shape");
-    size_t ny = (size_t)n_items * n_ch * n_samples, nr = (size_t)(r_per_channel ? n_ch : 1) * (n_fft / 2 + 1),
-           no = (size_t)n_items * n_ch * n_out;
-    float *dy, *dir;
-    float2* dr;
-    CHK(carve(c, &c->io, &c->io_bytes, [&](Carver& cv) {
-        dy = cv.take<float>(ny);
-        dr = cv.take<float2>(nr);
-        dir = cv.take<float>(no);
-    }));
-    CHK(ds_upload(c, dy, y, ny * 4));
-    CHK(ds_upload(c, dr, r, nr * 8));
-    CHK(ds_deconv_dev(c, dy, n_items, n_ch, n_samples, n_samples, n_fft, (const ds_c32*)dr, r_per_channel,
-                      n_out, n_out, dir));
-    return ds_download(c, ir, dir, no * 4);
 }
 
 // ---- block-streaming FIR classes, state on the device (kernels_fir_stream.hpp) ----------

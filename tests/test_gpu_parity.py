@@ -2837,6 +2837,286 @@ def test_istft_routes_per_length(switch, nfft, monkeypatch):
     _stft_routes_vs_table("istft", ISTFT_ROUTE_SWITCHES, switch, nfft, monkeypatch)
 
 
+# ---- which kernel family each FIR, rFFT, deconvolution and CSM call runs on, per entry point ------------------------
+# (tests/golden/fir_routes.json, xform_routes.json, csm_routes.json).  Keys "<switch>|<family>|<case>": the host
+# float32, host float64 and device entries of a family run the same kernels on the same case, so each case has one
+# row; a rejected call records "ERR<code>".  The launch names were recorded through these helpers on the library
+# before each of the four dispatches became one route choice (csrc/api.hip, fir_route / rfft_route / deconv_route /
+# csm_route).
+def _routes_under(switches, switch, matrix, monkeypatch):
+    """matrix() on a fresh context under one switch setting."""
+    from dsptoolbox_amd import _lib
+    for k, v in switches[switch].items():
+        monkeypatch.setenv(k, v)
+    _lib.reset_context()
+    try:
+        return matrix()
+    finally:
+        for k in switches[switch]:
+            monkeypatch.delenv(k, raising=False)
+        _lib.reset_context()
+
+
+def _routes_vs_table(name, family, switch, seen):
+    import json
+    with open(os.path.join(ROOT, "tests", "golden", name)) as fh:
+        table = json.load(fh)
+    want = {k: table[f"{switch}|{family}|{k.split('|', 1)[1]}"].split() for k in seen}
+    assert seen == want
+
+
+FIR_ROUTE_SWITCHES = {"default": {},
+                      "FIR_GENERIC=1+FIR_4K=0": {"DSPTOOLBOX_AMD_FIR_GENERIC": "1", "DSPTOOLBOX_AMD_FIR_4K": "0"},
+                      "FIR_4K=0": {"DSPTOOLBOX_AMD_FIR_4K": "0"}, "FIR_4K=1": {"DSPTOOLBOX_AMD_FIR_4K": "1"},
+                      "FIR_3PERCU=0": {"DSPTOOLBOX_AMD_FIR_3PERCU": "0"}, "FIR_STAGE=1": {"DSPTOOLBOX_AMD_FIR_STAGE": "1"},
+                      "FIR_DIRECT=0": {"DSPTOOLBOX_AMD_FIR_DIRECT": "0"}}
+FIR_ROUTE_TAPS = [1, 2, 64, 1024, 1025, 2049, 4097, 8193, 2**15 + 1]
+FIR_ROUTE_MODES = {"parallel": backend.DS_FB_PARALLEL, "summed": backend.DS_FB_SUMMED,
+                   "sequential": backend.DS_FB_SEQUENTIAL}
+# (entry, output row stride): "odd" = a device output stride that is not a multiple of 4 (no plain 16k blocks)
+FIR_ROUTE_ENTRIES = (("fir_ola", "n"), ("fir_ola_f64", "n"), ("fir_ola_dev", "n"), ("fir_ola_dev", "odd"))
+
+
+def _fir_route_case(entry, ld, n_taps, n, n_filt, mode, n_ch=3):
+    """One filter bank through one C-ABI entry point -> (output array, launch names).  n may be 0 (rejected)."""
+    import ctypes as C
+    from dsptoolbox_amd._lib import DeviceBuffer, DevicePlanar, get_context
+    ctx = get_context()
+    p = lambda a: a.ctypes.data_as(C.c_void_p)
+    rng = np.random.default_rng(n_taps + n + n_filt)
+    x = rng.standard_normal((max(n, 1), n_ch)) * 0.5 + 0.25
+    taps = (rng.standard_normal((n_filt, n_taps)) / np.sqrt(n_taps)).astype(np.float32)
+    m, n_out, ns = FIR_ROUTE_MODES[mode], (n_filt if mode == "parallel" else 1), max(n, 1)
+    xp = np.ascontiguousarray(x.T, dtype=np.float32)
+    ctx.routes()
+    if entry.endswith("_dev"):
+        ld_y = ns | 1 if ld == "odd" else ns
+        dx, dt, dy = DevicePlanar.from_planar(ctx, xp), DeviceBuffer.from_array(ctx, taps), DeviceBuffer(ctx, n_out * n_ch * ld_y * 4)
+        routes = _route_call(ctx, ctx.lib.ds_fir_ola_dev, (C.c_void_p(dx.ptr), n_ch, dx.ld, n, C.c_void_p(dt.ptr), n_filt,
+                                                           n_taps, m, C.c_void_p(dy.ptr), ld_y))
+        out = dy.to_array((n_out, n_ch, ld_y), np.float32)[..., :n]
+        for b in (dx.owner, dt, dy):
+            b.free()
+        return out, routes
+    f64 = entry.endswith("_f64")
+    out = np.zeros((n_out, ns, n_ch), np.float64) if f64 else np.zeros((n_out, n_ch, ns), np.float32)
+    fn = ctx.lib.ds_fir_ola_f64 if f64 else ctx.lib.ds_fir_ola
+    routes = _route_call(ctx, fn, (p(np.ascontiguousarray(x) if f64 else xp), n_ch, n, p(taps), n_filt, n_taps, m, p(out)))
+    return out, routes
+
+
+def _fir_route_matrix(taps_list, modes, on_case=None):
+    seen = {}
+    for n_taps in taps_list:
+        for n in (n_taps - 1, 5000, 50000):  # shorter than the filter, a few blocks, several 16k blocks
+            for n_filt in (1, 3):
+                for mode in modes:
+                    for entry, ld in FIR_ROUTE_ENTRIES:
+                        out, routes = _fir_route_case(entry, ld, n_taps, n, n_filt, mode)
+                        key = f"{entry}|{n_taps}|{n}|{n_filt}|{mode}|{ld}"
+                        seen[key] = routes
+                        if on_case:
+                            on_case(key, out)
+    return seen
+
+
+@pytest.mark.parametrize("n_taps", FIR_ROUTE_TAPS)
+@pytest.mark.parametrize("switch", list(FIR_ROUTE_SWITCHES))
+def test_fir_routes_per_shape(switch, n_taps, monkeypatch):
+    """Each (taps, signal length, filter count, bank mode, output stride) of every FIR entry point launches the kernels
+    it launched when the table was recorded.  The switches choose among the parallel mode's kernels; the summed and
+    sequential modes run the parallel route on combined taps, so they are pinned with the default switches only."""
+    modes = list(FIR_ROUTE_MODES) if switch == "default" else ["parallel"]
+    seen = _routes_under(FIR_ROUTE_SWITCHES, switch, lambda: _fir_route_matrix((n_taps,), modes), monkeypatch)
+    _routes_vs_table("fir_routes.json", "fir", switch, seen)
+
+
+XFORM_ROUTE_NFFTS = [1, 2, 3, 4, 8, 1000, 1024, 8192, 16384, 32768, 100000, 2**20]
+DECONV_ROUTE_SWITCHES = {"default": {}, "DECONV_GENERIC": {"DSPTOOLBOX_AMD_DECONV_GENERIC": "1"},
+                         "DECONV_2PERCU": {"DSPTOOLBOX_AMD_DECONV_2PERCU": "1"},
+                         "DECONV_PERSIST=0": {"DSPTOOLBOX_AMD_DECONV_PERSIST": "0"},
+                         "DECONV_PERSIST=0+DECONV_4PERCU=0": {"DSPTOOLBOX_AMD_DECONV_PERSIST": "0",
+                                                             "DSPTOOLBOX_AMD_DECONV_4PERCU": "0"}}
+
+
+def _xform_signal(n_fft, short, n_rows, seed):
+    """(n_samples, rows x n_samples float64): "full" = n_fft samples, "short" = half of them (rounded up)."""
+    n = (n_fft + 1) // 2 if short else n_fft
+    return n, np.random.default_rng(seed).standard_normal((n_rows, n)) * 0.5 + 0.25
+
+
+def _rfft_route_case(entry, n_fft, short, n_ch):
+    """One whole-signal spectrum through one C-ABI entry point -> (output array, launch names)."""
+    import ctypes as C
+    from dsptoolbox_amd._lib import DeviceBuffer, DevicePlanar, get_context
+    ctx = get_context()
+    p = lambda a: a.ctypes.data_as(C.c_void_p)
+    n, x = _xform_signal(n_fft, short, n_ch, n_fft + n_ch)
+    xp, B, scale = np.ascontiguousarray(x, dtype=np.float32), n_fft // 2 + 1, C.c_float(1.0 / n_fft)
+    ctx.routes()
+    if entry.endswith("_dev"):
+        dx, do = DevicePlanar.from_planar(ctx, xp), DeviceBuffer(ctx, B * n_ch * 8)
+        routes = _route_call(ctx, ctx.lib.ds_rfft_dev, (C.c_void_p(dx.ptr), n_ch, dx.ld, n, n_fft, scale, C.c_void_p(do.ptr)))
+        out = do.to_array((B, n_ch), np.complex64)
+        for b in (dx.owner, do):
+            b.free()
+        return out, routes
+    f64 = entry.endswith("_f64")
+    out = np.zeros((B, n_ch), np.complex128 if f64 else np.complex64)
+    fn = ctx.lib.ds_rfft_f64 if f64 else ctx.lib.ds_rfft
+    routes = _route_call(ctx, fn, (p(np.ascontiguousarray(x.T) if f64 else xp), n_ch, n, n_fft, scale, p(out)))
+    return out, routes
+
+
+def _deconv_route_case(entry, n_fft, short, r_per_channel, n_items, n_ch=3):
+    """One batch of deconvolutions through one C-ABI entry point -> (output array, launch names).  ds_deconv_f64 takes
+    one item."""
+    import ctypes as C
+    from dsptoolbox_amd._lib import DeviceBuffer, DevicePlanar, get_context
+    ctx = get_context()
+    p = lambda a: a.ctypes.data_as(C.c_void_p)
+    n, y = _xform_signal(n_fft, short, n_items * n_ch, n_fft + 10 * n_items + r_per_channel)
+    B, n_out = n_fft // 2 + 1, n_fft
+    rng = np.random.default_rng(n_fft)
+    r = (rng.standard_normal(((n_ch if r_per_channel else 1), B)) + 1j * rng.standard_normal(((n_ch if r_per_channel else 1), B)))
+    r = r.astype(np.complex64)
+    yp = np.ascontiguousarray(y, dtype=np.float32)
+    ctx.routes()
+    if entry.endswith("_dev"):
+        dy, dr, do = DevicePlanar.from_planar(ctx, yp), DeviceBuffer.from_array(ctx, r), DeviceBuffer(ctx, yp.shape[0] * n_out * 4)
+        routes = _route_call(ctx, ctx.lib.ds_deconv_dev, (C.c_void_p(dy.ptr), n_items, n_ch, dy.ld, n, n_fft, C.c_void_p(dr.ptr),
+                                                          r_per_channel, n_out, n_out, C.c_void_p(do.ptr)))
+        out = do.to_array((n_items, n_ch, n_out), np.float32)
+        for b in (dy.owner, dr, do):
+            b.free()
+        return out, routes
+    if entry.endswith("_f64"):
+        out = np.zeros((n_out, n_ch), np.float64)
+        routes = _route_call(ctx, ctx.lib.ds_deconv_f64, (p(np.ascontiguousarray(y.T)), n_ch, n, n_fft, p(r), r_per_channel,
+                                                          n_out, p(out)))
+        return out, routes
+    out = np.zeros((n_items, n_ch, n_out), np.float32)
+    routes = _route_call(ctx, ctx.lib.ds_deconv, (p(yp), n_items, n_ch, n, n_fft, p(r), r_per_channel, n_out, p(out)))
+    return out, routes
+
+
+def _rfft_route_matrix(nffts, on_case=None):
+    seen = {}
+    for n_fft in nffts:
+        for short in (False, True):
+            for n_ch in (1, 3):
+                for entry in ("rfft", "rfft_f64", "rfft_dev"):
+                    out, routes = _rfft_route_case(entry, n_fft, short, n_ch)
+                    key = f"{entry}|{n_fft}|{'short' if short else 'full'}|{n_ch}"
+                    seen[key] = routes
+                    if on_case:
+                        on_case(key, out)
+    return seen
+
+
+def _deconv_route_matrix(nffts, on_case=None):
+    seen = {}
+    for n_fft in nffts:
+        for short in (False, True):
+            for rpc in (0, 1):
+                for n_items in (1, 2):
+                    for entry in ("deconv", "deconv_f64", "deconv_dev") if n_items == 1 else ("deconv", "deconv_dev"):
+                        out, routes = _deconv_route_case(entry, n_fft, short, rpc, n_items)
+                        key = f"{entry}|{n_fft}|{'short' if short else 'full'}|{rpc}|{n_items}"
+                        seen[key] = routes
+                        if on_case:
+                            on_case(key, out)
+    return seen
+
+
+@pytest.mark.parametrize("n_fft", XFORM_ROUTE_NFFTS)
+def test_rfft_routes_per_length(n_fft, monkeypatch):
+    """Each (length, signal length, channel count) of every whole-signal rFFT entry point launches the kernels it
+    launched when the table was recorded."""
+    seen = _routes_under({"default": {}}, "default", lambda: _rfft_route_matrix((n_fft,)), monkeypatch)
+    _routes_vs_table("xform_routes.json", "rfft", "default", seen)
+
+
+@pytest.mark.parametrize("n_fft", XFORM_ROUTE_NFFTS)
+@pytest.mark.parametrize("switch", list(DECONV_ROUTE_SWITCHES))
+def test_deconv_routes_per_length(switch, n_fft, monkeypatch):
+    """The same for every (length, signal length, inverse per channel, item count) of every deconvolution entry."""
+    seen = _routes_under(DECONV_ROUTE_SWITCHES, switch, lambda: _deconv_route_matrix((n_fft,)), monkeypatch)
+    _routes_vs_table("xform_routes.json", "deconv", switch, seen)
+
+
+CSM_ROUTE_SWITCHES = {"default": {}, "CSM_GENERIC": {"DSPTOOLBOX_AMD_CSM_GENERIC": "1"},
+                      "CSM_F32": {"DSPTOOLBOX_AMD_CSM_F32": "1"}, "CSM_CHUNKS=3": {"DSPTOOLBOX_AMD_CSM_CHUNKS": "3"}}
+CSM_ROUTE_WINDOWS = [32, 1000, 1024, 4096, 16384, 32768]
+
+
+def _csm_route_case(entry, W, average, n_ch, n_frames, bins):
+    """One cross-spectral matrix through one C-ABI entry point -> (output array, launch names).  bins: "all", or
+    "part" (ds_csm_bins_dev: a quarter of the bins from the first quarter on)."""
+    import ctypes as C
+    from dsptoolbox_amd._lib import DeviceBuffer, DevicePlanar, get_context
+    ctx = get_context()
+    p = lambda a: a.ctypes.data_as(C.c_void_p)
+    hop = W // 2
+    n, nb = (n_frames - 1) * hop + W, W // 2 + 1
+    x = np.random.default_rng(W + n_ch + n_frames).standard_normal((n, n_ch)) * 0.5 + 0.25
+    xp = np.ascontiguousarray(x.T, dtype=np.float32)
+    w = (0.5 - 0.5 * np.cos(2 * np.pi * np.arange(W) / W)).astype(np.float32)
+    b0, bc = (nb // 4, max(1, nb // 4)) if bins == "part" else (0, nb)
+    mid = (W, hop, n_frames)
+    fin = (0, C.c_double(1.0 / W), C.c_double(2.0), 1)  # amp_sqrt, norm_scale, factor, halve_edges
+    ctx.routes()
+    if entry.endswith("_dev"):
+        dx, dw, do = DevicePlanar.from_planar(ctx, xp), DeviceBuffer.from_array(ctx, w), DeviceBuffer(ctx, bc * n_ch * n_ch * 8)
+        if entry == "csm_bins_dev":
+            routes = _route_call(ctx, ctx.lib.ds_csm_bins_dev, (C.c_void_p(dx.ptr), n_ch, dx.ld, n, *mid, C.c_void_p(dw.ptr),
+                                                                1, *fin, b0, bc, C.c_void_p(do.ptr)))
+        else:
+            routes = _route_call(ctx, ctx.lib.ds_csm_dev, (C.c_void_p(dx.ptr), n_ch, dx.ld, n, *mid, C.c_void_p(dw.ptr), 1,
+                                                           backend.DS_AVG[average], *fin, C.c_void_p(do.ptr)))
+        out = do.to_array((bc, n_ch, n_ch), np.complex64)
+        for b in (dx.owner, dw, do):
+            b.free()
+        return out, routes
+    f64 = entry.endswith("_f64")
+    out = np.zeros((nb, n_ch, n_ch), np.complex64)
+    fn = ctx.lib.ds_csm_f64 if f64 else ctx.lib.ds_csm
+    routes = _route_call(ctx, fn, (p(np.ascontiguousarray(x) if f64 else xp), n_ch, n, *mid, p(w), 1, backend.DS_AVG[average],
+                                   *fin, p(out)))
+    return out, routes
+
+
+def _csm_route_matrix(windows, on_case=None):
+    """Up to 1024-sample windows: 1 ... 130 channels and also 192 frames (three chunks of >= 64 frames under
+    CSM_CHUNKS=3); at 4096 samples up to 65 channels; longer windows 1 and 3 channels (a 32768-sample matrix of 130
+    channels alone is 2.2 GB)."""
+    seen = {}
+    for W in windows:
+        chans = (1, 3, 64, 65, 130) if W <= 1024 else ((1, 3, 64, 65) if W <= 4096 else (1, 3))
+        for average in ("mean", "median"):
+            for n_ch in chans:
+                for n_frames in (4, 8, 192) if W <= 1024 else (4, 8):
+                    cases = [("csm", "all"), ("csm_f64", "all"), ("csm_dev", "all")]
+                    if average == "mean":
+                        cases += [("csm_bins_dev", "all"), ("csm_bins_dev", "part")]
+                    for entry, bins in cases:
+                        out, routes = _csm_route_case(entry, W, average, n_ch, n_frames, bins)
+                        key = f"{entry}|{W}|{average}|{n_ch}|{n_frames}|{bins}"
+                        seen[key] = routes
+                        if on_case:
+                            on_case(key, out)
+    return seen
+
+
+@pytest.mark.parametrize("W", CSM_ROUTE_WINDOWS)
+@pytest.mark.parametrize("switch", list(CSM_ROUTE_SWITCHES))
+def test_csm_routes_per_shape(switch, W, monkeypatch):
+    """Each (window, averaging, channel count, frame count, bin range) of every CSM entry point launches the kernels
+    it launched when the table was recorded."""
+    seen = _routes_under(CSM_ROUTE_SWITCHES, switch, lambda: _csm_route_matrix((W,)), monkeypatch)
+    _routes_vs_table("csm_routes.json", "csm", switch, seen)
+
+
 @pytest.mark.parametrize("route", SWITCH_ROUTES, ids=lambda r: ",".join(f"{k.replace('DSPTOOLBOX_AMD_', '')}={v}"
                                                                         for k, v in r[0].items()) or "default")
 def test_kernel_selecting_switches(route, monkeypatch):
