@@ -608,45 +608,6 @@ static int check_big_len(ds_ctx* c, int64_t n, const char* what) {
     return DS_OK;
 }
 
-// ---- framed transforms beyond the LDS-resident FFT (window / FFT length 2^15 .. 2^24) ------
-// Frame pairs of every channel are one batch of four-step complex FFTs, processed in groups
-// of <= 2^25 complex points per scratch buffer.
-static int64_t stft_big_group(int64_t nfft, int64_t batch) {
-    return std::max<int64_t>(1, std::min<int64_t>({batch, ((int64_t)1 << 25) / nfft, (int64_t)32768}));
-}
-static BigScratch take_big_scratch(Carver& cv, int n_ch, int n_frames, int64_t nfft) {
-    const int64_t grp = stft_big_group(nfft, (int64_t)n_ch * ((n_frames + 1) / 2));
-    BigScratch s;
-    s.P = cv.take<float2>((size_t)grp * nfft);
-    s.Q = cv.take<float2>((size_t)grp * nfft);
-    s.means = cv.take<float>((size_t)n_ch * n_frames);
-    return s;
-}
-// layout 0: out[(c*F + f)*nb + k] (unscaled spectra for the Welch sums), 1: out[(k*F + f)*C + c]
-// s: take_big_scratch() for at least n_ch channels and n_frames frames
-static int stft_big(ds_ctx* c, const BigScratch& s, const float* x, int n_ch, int64_t ld, int64_t n_samples,
-                    int W, int hop, int64_t nfft, int64_t pad_front, int n_frames, const float* window,
-                    int detrend, float scale, float edge_scale, int power, int layout, float2* out) {
-    CHK(check_big_len(c, nfft, "framed transform length"));
-    const int64_t batch = (int64_t)n_ch * ((n_frames + 1) / 2);
-    const int64_t grp = stft_big_group(nfft, batch);
-    float2 *P = s.P, *Q = s.Q;
-    float* means = s.means;
-    if (detrend) {
-        dsbig::FrameMeansArgs m{x, n_samples, ld, pad_front, n_ch, W, hop, n_frames, window, means};
-        CHK(launch(c, "bigfft_means", dsbig::k_frame_means, dim3(n_frames, n_ch), 256, 0, m));
-    }
-    for (int64_t b0 = 0; b0 < batch; b0 += grp) {
-        const int nb = (int)std::min<int64_t>(grp, batch - b0);
-        CHK(launch_big_cols(c, {nullptr, x, nullptr, n_samples, 0, P, nfft, 0, 0, 0, ld, n_ch, nullptr, window,
-                                detrend ? means : nullptr, W, hop, n_frames, pad_front, b0}, nb));
-        CHK(big_rows(c, P, Q, nfft, nb));
-        dsbig::UnpackFramesArgs u{Q, nfft, b0, n_ch, n_frames, layout, power, scale, edge_scale, out};
-        CHK(launch(c, "bigfft_unpack", dsbig::k_big_unpack_frames, dim3(64, nb), 256, 0, u));
-    }
-    return DS_OK;
-}
-
 // ---- arbitrary lengths: Bluestein on top of the four-step FFT ------------------------
 static int64_t blue_len(int64_t L) {
     int64_t m = (int64_t)1 << 15;  // smallest four-step length
@@ -891,6 +852,50 @@ static int stft_check(ds_ctx* c, const StftCall& s) {
     if (s.nfft < 2) return fail(c, DS_ERR_ARG, w + ": fft length must be >= 2");
     return DS_OK;
 }
+
+// ---- framed transforms beyond the LDS-resident FFT (window / FFT length 2^15 .. 2^24) ------
+// Frame pairs of every channel are one batch of four-step complex FFTs, processed in groups
+// of <= 2^25 complex points per scratch buffer.
+static int64_t stft_big_group(int64_t nfft, int64_t batch) {
+    return std::max<int64_t>(1, std::min<int64_t>({batch, ((int64_t)1 << 25) / nfft, (int64_t)32768}));
+}
+static BigScratch take_big_scratch(Carver& cv, int n_ch, int n_frames, int64_t nfft) {
+    const int64_t grp = stft_big_group(nfft, (int64_t)n_ch * ((n_frames + 1) / 2));
+    BigScratch s;
+    s.P = cv.take<float2>((size_t)grp * nfft);
+    s.Q = cv.take<float2>((size_t)grp * nfft);
+    s.means = cv.take<float>((size_t)n_ch * n_frames);
+    return s;
+}
+// layout 0: out[(c*F + f)*nb + k] (unscaled spectra for the Welch sums), 1: out[(k*F + f)*C + c]
+// s: take_big_scratch() for at least q.n_ch channels and q.n_frames frames
+static int stft_big(ds_ctx* c, const BigScratch& s, const StftCall& q, int layout) {
+    const int64_t nfft = q.nfft;
+    CHK(check_big_len(c, nfft, "framed transform length"));
+    const int64_t batch = (int64_t)q.n_ch * ((q.n_frames + 1) / 2);
+    const int64_t grp = stft_big_group(nfft, batch);
+    float2 *P = s.P, *Q = s.Q;
+    float* means = s.means;
+    if (q.detrend) {
+        dsbig::FrameMeansArgs m{q.x, q.n_samples, q.ld, q.pad_front, q.n_ch, q.W, q.hop, q.n_frames, q.window, means};
+        CHK(launch(c, "bigfft_means", dsbig::k_frame_means, dim3(q.n_frames, q.n_ch), 256, 0, m));
+    }
+    for (int64_t b0 = 0; b0 < batch; b0 += grp) {
+        const int nb = (int)std::min<int64_t>(grp, batch - b0);
+        CHK(launch_big_cols(c, {nullptr, q.x, nullptr, q.n_samples, 0, P, nfft, 0, 0, 0, q.ld, q.n_ch, nullptr, q.window,
+                                q.detrend ? means : nullptr, q.W, q.hop, q.n_frames, q.pad_front, b0}, nb));
+        CHK(big_rows(c, P, Q, nfft, nb));
+        dsbig::UnpackFramesArgs u{Q, nfft, b0, q.n_ch, q.n_frames, layout, q.power, q.scale, q.edge_scale, q.out};
+        CHK(launch(c, "bigfft_unpack", dsbig::k_big_unpack_frames, dim3(64, nb), 256, 0, u));
+    }
+    return DS_OK;
+}
+// the call for the unscaled spectra of q's whole windows (q: a WelchCall or a CsmCall), as the Welch and CSM sums take them
+template <class Q>
+static StftCall window_spectra(const Q& q, const float* x, int n_ch, int64_t ld, float2* out) {
+    return {q.who, x, q.n_samples, n_ch, ld, q.W, q.hop, q.W, 0, q.n_frames, q.window, q.detrend, 1.0f, 1.0f, 0, out};
+}
+
 // any fft length (kernels_stft_any.hpp): rows = windowed frames -> ds_rfft_dev -> scaling pass
 static int stft_any_run(ds_ctx* c, const StftCall& s) {
     const int nfft = s.nfft, keep = std::min(s.W, nfft), B = nfft / 2 + 1;
@@ -953,8 +958,7 @@ static int stft_long_run(ds_ctx* c, const StftCall& s) {
 static int stft_big_run(ds_ctx* c, const StftCall& s) {
     BigScratch b;
     CHK(carve(c, &c->ws, &c->ws_bytes, [&](Carver& cv) { b = take_big_scratch(cv, s.n_ch, s.n_frames, s.nfft); }));
-    return stft_big(c, b, s.x, s.n_ch, s.ld, s.n_samples, s.W, s.hop, s.nfft, s.pad_front, s.n_frames, s.window, s.detrend,
-                    s.scale, s.edge_scale, s.power, 1, s.out);
+    return stft_big(c, b, s, 1);
 }
 // 256-, 512-, 1024- and 2048-point transforms (1024 = the reference's default frame): wave-level register transforms,
 // one frame pair per team of NN / 16 lanes (kernels_stft1024.hpp).  Frames of 128 / 64 / 32 samples (NN = 256): their
@@ -1390,7 +1394,37 @@ static WelchPlan plan_welch(int n_frames, int units) {
     return {n_chunks, fpc};
 }
 
-// kind 0: tf+coh, 1: psd of x, 2: csd of (x[c], y[c])
+// What a Welch call estimates; the values are kernel arguments (k_welch_finish, k_welch_median, dsbig::k_spec_sum)
+enum WelchKind { TF = 0, PSD = 1, CSD = 2 };
+// One call of a Welch entry, as every Welch runner takes it (checked by welch_check; `who`: the entry point called).
+// TF: transfer function and coherence of y against x (out_c, out_r); PSD: auto spectra of x (out_r; y and out_c null,
+// n_cy = ldy = mode = 0); CSD: cross spectra conj(X_c) Y_c (out_c; out_r null, mode 0)
+struct WelchCall {
+    const char* who;
+    WelchKind kind;
+    const float* x; int n_cx; int64_t ldx; const float* y; int n_cy; int64_t ldy, n_samples; int W, hop, n_frames;
+    const float* window; int detrend, average, mode, amp_sqrt; double norm_scale, factor; int halve_edges;
+    float2* out_c; float* out_r;
+    bool auto_only() const { return kind == PSD; }
+    int n_out() const { return auto_only() ? n_cx : n_cy; }  // channels that are accumulated
+    int nyc() const { return auto_only() ? 0 : n_cy; }       // channels of y that are transformed
+    bool big() const { return W > kMaxFft && is_pow2(W); }   // window beyond the LDS-resident FFT: four-step transforms
+};
+// What every Welch runner hands to launch_finish: the partial slabs of n_chunks chunks and nb bins (pxx: of the input
+// channels; auto spectra: of x), scaled for the mean over the call's frames
+static WelchFinArgs welch_fin(const WelchCall& q, const float* pxx, const float2* pxy, const float* pyy, int n_chunks, int nb) {
+    return {pxx, pxy, pyy, n_chunks, n_chunks, q.n_cx, q.n_cy, q.kind, q.mode,
+            FinishPar{q.norm_scale / (double)q.n_frames, q.factor, q.halve_edges, q.amp_sqrt, nb}, q.out_c, q.out_r};
+}
+// a register kernel's arguments for the y signal: those of x with y's samples, row stride and channel count
+template <class A>
+static A y_args(A a, const WelchCall& q) {
+    a.sig = q.y;
+    a.ld = q.ldy;
+    a.n_ch = q.n_cy;
+    return a;
+}
+
 // Median kernels keep `series` float series of n_frames values (padded to a power of two) per bin in LDS: the number of bins
 // per workgroup (8, 4, 2 or 1) that fits 150 KB; 0 if not even one does.
 static int median_bins_per_block(int series, int n_frames, size_t* lds) {
@@ -1406,16 +1440,13 @@ static int median_bins_per_block(int series, int n_frames, size_t* lds) {
 
 // Welch for window lengths beyond the LDS-resident FFT: spectra of every frame -> frame sums
 // (or per-bin medians) -> the usual finish
-static int welch_big(ds_ctx* c, int kind, const float* x, int n_cx, int64_t ldx, const float* y,
-                     int n_cy, int64_t ldy, int64_t n_samples, int W, int hop, int n_frames,
-                     const float* window, int detrend, int average, int mode, int amp_sqrt,
-                     double norm_scale, double factor, int halve_edges, float2* out_c, float* out_r) {
-    const int nb = W / 2 + 1;
-    const int nyc = kind == 1 ? 0 : n_cy;
+static int welch_big_run(ds_ctx* c, const WelchCall& q) {
+    const int n_cx = q.n_cx, n_frames = q.n_frames, nb = q.W / 2 + 1;
+    const int nyc = q.nyc();
     const int nmax = std::max(n_cx, nyc);
     size_t med_lds = 0;
     const int med_bpb = median_bins_per_block(3, n_frames, &med_lds);
-    if (average == DS_AVG_MEDIAN && !med_bpb)
+    if (q.average == DS_AVG_MEDIAN && !med_bpb)
         return fail(c, DS_ERR_UNSUP, "welch: median averaging over more than 12 799 frames is not built yet");
     float2 *xsp, *ysp, *pxy;
     float *pxx, *pyy;
@@ -1426,79 +1457,74 @@ static int welch_big(ds_ctx* c, int kind, const float* x, int n_cx, int64_t ldx,
         pxx = cv.take<float>((size_t)n_cx * nb);
         pxy = cv.take<float2>((size_t)std::max(1, nyc) * nb);
         pyy = cv.take<float>((size_t)std::max(1, nyc) * nb);
-        s = take_big_scratch(cv, nmax, n_frames, W);
+        s = take_big_scratch(cv, nmax, n_frames, q.W);
     }));
-    CHK(stft_big(c, s, x, n_cx, ldx, n_samples, W, hop, W, 0, n_frames, window, detrend, 1.0f, 1.0f, 0,
-                 0, xsp));
-    if (nyc) {
-        CHK(stft_big(c, s, y, nyc, ldy, n_samples, W, hop, W, 0, n_frames, window, detrend, 1.0f, 1.0f,
-                     0, 0, ysp));
-    }
-    double count = (double)n_frames;
-    if (average == DS_AVG_MEDIAN) {
-        MedianArgs m{xsp, nyc ? ysp : nullptr, n_cx, nyc, n_frames, nb, kind, med_bpb, pxx, pxy, pyy};
-        CHK(launch(c, "welch_median", k_welch_median, dim3((nb + med_bpb - 1) / med_bpb, kind == 1 ? n_cx : n_cy), 256,
-                   med_lds, m));
+    CHK(stft_big(c, s, window_spectra(q, q.x, n_cx, q.ldx, xsp), 0));
+    if (nyc) CHK(stft_big(c, s, window_spectra(q, q.y, nyc, q.ldy, ysp), 0));
+    WelchFinArgs f = welch_fin(q, pxx, pxy, pyy, 1, nb);
+    if (q.average == DS_AVG_MEDIAN) {
+        MedianArgs m{xsp, nyc ? ysp : nullptr, n_cx, nyc, n_frames, nb, q.kind, med_bpb, pxx, pxy, pyy};
+        CHK(launch(c, "welch_median", k_welch_median, dim3((nb + med_bpb - 1) / med_bpb, q.n_out()), 256, med_lds, m));
         const int nbias = (n_frames & 1) ? n_frames : n_frames - 1;
-        count = 1.0 / (double)std::max(1, nbias);
+        const double count = 1.0 / (double)std::max(1, nbias);
+        f.fin.inv = q.norm_scale / count;
     } else {
-        dsbig::SpecSumArgs sa{xsp, nyc ? ysp : nullptr, n_cx, nyc, n_frames, nb, kind, pxx, pxy, pyy};
-        CHK(launch(c, "welch_specsum", dsbig::k_spec_sum, dim3((nb + 255) / 256, kind == 1 ? n_cx : n_cy), 256, 0, sa));
+        dsbig::SpecSumArgs sa{xsp, nyc ? ysp : nullptr, n_cx, nyc, n_frames, nb, q.kind, pxx, pxy, pyy};
+        CHK(launch(c, "welch_specsum", dsbig::k_spec_sum, dim3((nb + 255) / 256, q.n_out()), 256, 0, sa));
     }
-    WelchFinArgs f{pxx, pxy, pyy, 1, 1, n_cx, n_cy, kind, mode,
-                   FinishPar{norm_scale / count, factor, halve_edges, amp_sqrt, nb}, out_c, out_r};
     return launch_finish(c, f);
 }
 
-static int welch_common(ds_ctx* c, int kind, const float* x, int n_cx, int64_t ldx, const float* y,
-                        int n_cy, int64_t ldy, int64_t n_samples, int W, int hop, int n_frames,
-                        const float* window, int detrend, int average, int mode, int amp_sqrt,
-                        double norm_scale, double factor, int halve_edges, float2* out_c,
-                        float* out_r) {
-    if (W > kMaxFft && is_pow2(W))
-        return welch_big(c, kind, x, n_cx, ldx, y, n_cy, ldy, n_samples, W, hop, n_frames, window, detrend,
-                         average, mode, amp_sqrt, norm_scale, factor, halve_edges, out_c, out_r);
+// Median averaging for windows up to 16384 samples: frame spectra of x (and y) -> per-bin medians -> the usual finish
+// with bias n (n = F or F-1, odd; the reference's `csd /= sum((-1)**(n+1)/n)` multiplies by n)
+static int welch_median_run(ds_ctx* c, const WelchCall& q) {
+    const int n_cx = q.n_cx, n_frames = q.n_frames, W = q.W;
     CHK(check_fft_len(c, W, "welch window length"));
     const float2* tw;
     CHK(get_twiddles(c, W, &tw));
     const int nb = W / 2 + 1;
-    const int units = kind == 1 ? n_cx : (n_cy + 1) / 2;
-    WelchPlan pl = plan_welch(n_frames, units);
-    if (average == DS_AVG_MEDIAN) {
-        // frame spectra of x (and y) -> per-bin medians -> the usual finish with bias n
-        // (n = F or F-1, odd; the reference's `csd /= sum((-1)**(n+1)/n)` multiplies by n)
-        const int nyc = kind == 1 ? 0 : n_cy;
-        size_t lds = 0;
-        const int bpb = median_bins_per_block(3, n_frames, &lds);
-        if (!bpb)
-            return fail(c, DS_ERR_UNSUP, "welch: median averaging over more than 12 799 frames is not built yet");
-        float2 *xsp, *ysp, *mxy;
-        float *scratch, *mxx, *myy;
-        CHK(carve(c, &c->ws, &c->ws_bytes, [&](Carver& cv) {
-            xsp = cv.take<float2>((size_t)n_cx * n_frames * nb);
-            ysp = nyc ? cv.take<float2>((size_t)nyc * n_frames * nb) : nullptr;
-            scratch = cv.take<float>((size_t)pl.n_chunks * std::max(n_cx, nyc) * nb);
-            mxx = cv.take<float>((size_t)n_cx * nb);
-            mxy = cv.take<float2>((size_t)std::max(1, nyc) * nb);
-            myy = cv.take<float>((size_t)std::max(1, nyc) * nb);
-        }));
-        {
-            XspecArgs ax{x, n_samples, ldx, n_cx, W, hop, n_frames, detrend, pl.fpc, window, tw, xsp, scratch};
-            DISPATCH_N(W, CHK(launch(c, "welch_xspec", k_xspec<NN>, dim3(pl.n_chunks, n_cx), Cfg<NN>::NT, Cfg<NN>::LDS_BYTES, ax)));
-        }
-        if (nyc) {
-            XspecArgs ay{y, n_samples, ldy, nyc, W, hop, n_frames, detrend, pl.fpc, window, tw, ysp, scratch};
-            DISPATCH_N(W, CHK(launch(c, "welch_xspec", k_xspec<NN>, dim3(pl.n_chunks, nyc), Cfg<NN>::NT, Cfg<NN>::LDS_BYTES, ay)));
-        }
-        MedianArgs m{xsp, ysp, n_cx, nyc, n_frames, nb, kind, bpb, mxx, mxy, myy};
-        CHK(launch(c, "welch_median", k_welch_median, dim3((nb + bpb - 1) / bpb, kind == 1 ? n_cx : n_cy), 256, lds, m));
-        const int nbias = (n_frames & 1) ? n_frames : n_frames - 1;
-        WelchFinArgs f{mxx, mxy, myy, 1, 1, n_cx, n_cy, kind, mode,
-                       FinishPar{norm_scale * (double)std::max(1, nbias), factor, halve_edges, amp_sqrt, nb},
-                       out_c, out_r};
-        return launch_finish(c, f);
+    WelchPlan pl = plan_welch(n_frames, q.auto_only() ? n_cx : (q.n_cy + 1) / 2);
+    const int nyc = q.nyc();
+    size_t lds = 0;
+    const int bpb = median_bins_per_block(3, n_frames, &lds);
+    if (!bpb)
+        return fail(c, DS_ERR_UNSUP, "welch: median averaging over more than 12 799 frames is not built yet");
+    float2 *xsp, *ysp, *mxy;
+    float *scratch, *mxx, *myy;
+    CHK(carve(c, &c->ws, &c->ws_bytes, [&](Carver& cv) {
+        xsp = cv.take<float2>((size_t)n_cx * n_frames * nb);
+        ysp = nyc ? cv.take<float2>((size_t)nyc * n_frames * nb) : nullptr;
+        scratch = cv.take<float>((size_t)pl.n_chunks * std::max(n_cx, nyc) * nb);
+        mxx = cv.take<float>((size_t)n_cx * nb);
+        mxy = cv.take<float2>((size_t)std::max(1, nyc) * nb);
+        myy = cv.take<float>((size_t)std::max(1, nyc) * nb);
+    }));
+    {
+        XspecArgs ax{q.x, q.n_samples, q.ldx, n_cx, W, q.hop, n_frames, q.detrend, pl.fpc, q.window, tw, xsp, scratch};
+        DISPATCH_N(W, CHK(launch(c, "welch_xspec", k_xspec<NN>, dim3(pl.n_chunks, n_cx), Cfg<NN>::NT, Cfg<NN>::LDS_BYTES, ax)));
     }
-    const bool need_xs = kind != 1;
+    if (nyc) {
+        XspecArgs ay{q.y, q.n_samples, q.ldy, nyc, W, q.hop, n_frames, q.detrend, pl.fpc, q.window, tw, ysp, scratch};
+        DISPATCH_N(W, CHK(launch(c, "welch_xspec", k_xspec<NN>, dim3(pl.n_chunks, nyc), Cfg<NN>::NT, Cfg<NN>::LDS_BYTES, ay)));
+    }
+    MedianArgs m{xsp, ysp, n_cx, nyc, n_frames, nb, q.kind, bpb, mxx, mxy, myy};
+    CHK(launch(c, "welch_median", k_welch_median, dim3((nb + bpb - 1) / bpb, q.n_out()), 256, lds, m));
+    const int nbias = (n_frames & 1) ? n_frames : n_frames - 1;
+    WelchFinArgs f = welch_fin(q, mxx, mxy, myy, 1, nb);
+    f.fin.inv = q.norm_scale * (double)std::max(1, nbias);
+    return launch_finish(c, f);
+}
+
+// Every other window up to 16384 samples: the LDS-resident transform (kernels_generic.hpp), spectra of x, then the sums
+// of y against them
+static int welch_mean_run(ds_ctx* c, const WelchCall& q) {
+    const int n_cx = q.n_cx, n_cy = q.n_cy, n_frames = q.n_frames, W = q.W;
+    CHK(check_fft_len(c, W, "welch window length"));
+    const float2* tw;
+    CHK(get_twiddles(c, W, &tw));
+    const int nb = W / 2 + 1;
+    WelchPlan pl = plan_welch(n_frames, q.auto_only() ? n_cx : (n_cy + 1) / 2);
+    const bool need_xs = !q.auto_only();
     float *pxx, *pyy = nullptr;
     float2 *xs = nullptr, *pxy = nullptr;
     CHK(carve(c, &c->ws, &c->ws_bytes, [&](Carver& cv) {
@@ -1510,19 +1536,16 @@ static int welch_common(ds_ctx* c, int kind, const float* x, int n_cx, int64_t l
         }
     }));
     {
-        XspecArgs a{x, n_samples, ldx, n_cx, W, hop, n_frames, detrend, pl.fpc, window, tw, xs, pxx};
+        XspecArgs a{q.x, q.n_samples, q.ldx, n_cx, W, q.hop, n_frames, q.detrend, pl.fpc, q.window, tw, xs, pxx};
         dim3 grid(pl.n_chunks, n_cx);
         DISPATCH_N(W, CHK(launch(c, "welch_xspec", k_xspec<NN>, grid, Cfg<NN>::NT, Cfg<NN>::LDS_BYTES, a)));
     }
     if (need_xs) {
-        YaccArgs a{y, n_samples, ldy, n_cy, n_cx, W, hop, n_frames, detrend, pl.fpc, window, tw, xs, pxy, pyy};
+        YaccArgs a{q.y, q.n_samples, q.ldy, n_cy, n_cx, W, q.hop, n_frames, q.detrend, pl.fpc, q.window, tw, xs, pxy, pyy};
         dim3 grid(pl.n_chunks, (n_cy + 1) / 2);
         DISPATCH_N(W, CHK(launch(c, "welch_yacc", k_yacc<NN>, grid, Cfg<NN>::NT, Cfg<NN>::LDS_BYTES, a)));
     }
-    WelchFinArgs f{pxx, pxy, pyy, pl.n_chunks, pl.n_chunks, n_cx, n_cy, kind, mode,
-                   FinishPar{norm_scale / (double)n_frames, factor, halve_edges, amp_sqrt, nb},
-                   out_c, out_r};
-    return launch_finish(c, f);
+    return launch_finish(c, welch_fin(q, pxx, pxy, pyy, pl.n_chunks, nb));
 }
 
 // Frames the kernels have to visit: a frame that starts at or past the end of the signal is all
@@ -1534,22 +1557,16 @@ static int frames_to_visit(int64_t n_samples, int hop, int n_frames) {
     return (int)std::min<int64_t>(n_frames, 2 * pairs);
 }
 
-// Every Welch runner below takes welch_common's arguments, already checked by welch_check, and handles the three kinds:
-// 0: transfer function + coherence (out_c, out_r), 1: auto spectra of x (out_r; y null), 2: cross spectra (out_c).
-
 // nfft 4096: register-resident radix-16 FFT path (kernels_welch4096.hpp); three workgroups per CU at 50 % overlap
 // (kernels_welch4096w.hpp), two otherwise
-static int welch4096_run(ds_ctx* c, int kind, const float* x, int n_cx, int64_t ldx, const float* y, int n_cy,
-                         int64_t ldy, int64_t n_samples, int W, int hop, int n_frames, const float* window, int detrend,
-                         int average, int mode, int amp_sqrt, double norm_scale, double factor, int halve_edges,
-                         float2* out_c, float* out_r) {
+static int welch4096_run(ds_ctx* c, const WelchCall& q) {
     namespace w4 = welch4096;
     CHK(ensure_table(c, &c->w4_tables, w4::host_tables));
-    const bool auto_only = kind == 1;
-    const int n_out = auto_only ? n_cx : n_cy;  // channels that are accumulated
-    const int nf = frames_to_visit(n_samples, hop, n_frames);
-    const bool half = hop == 2048;
-    const bool three = half && !c->cfg.w4_two_per_cu && w4::fits3(n_samples, nf);
+    const bool auto_only = q.auto_only();
+    const int n_cx = q.n_cx, n_cy = q.n_cy, n_out = q.n_out();
+    const int nf = frames_to_visit(q.n_samples, q.hop, q.n_frames);
+    const bool half = q.hop == 2048;
+    const bool three = half && !c->cfg.w4_two_per_cu && w4::fits3(q.n_samples, nf);
     w4::Plan pl = three ? w4::plan3(nf, n_out, c->cfg.welch_chunks) : w4::plan(nf, n_out, c->cfg.welch_chunks);
     float2 *xs = nullptr, *pxy = nullptr;
     float *px = nullptr, *psx = nullptr, *pyy;
@@ -1562,7 +1579,7 @@ static int welch4096_run(ds_ctx* c, int kind, const float* x, int n_cx, int64_t 
         }
         pyy = cv.take<float>((size_t)pl.n_chunks * n_out * w4::NB);
     }));
-    w4::Args ax{x, n_samples, ldx, auto_only ? n_cx : 1, hop, nf, pl.n_pairs, detrend, pl.n_chunks, pl.ppc, window,
+    w4::Args ax{q.x, q.n_samples, q.ldx, auto_only ? n_cx : 1, q.hop, nf, pl.n_pairs, q.detrend, pl.n_chunks, pl.ppc, q.window,
                 c->w4_tables, xs, px, pxy, pyy, psx};
     if (auto_only) {
         if (three) {
@@ -1574,10 +1591,7 @@ static int welch4096_run(ds_ctx* c, int kind, const float* x, int n_cx, int64_t 
         }
     } else {
         ax.n_cx = n_cx;
-        w4::Args ay = ax;
-        ay.sig = y;
-        ay.ld = ldy;
-        ay.n_ch = n_cy;
+        w4::Args ay = y_args(ax, q);
         if (three) {
             w4::place_remainder(ay, n_cy);
             CHK(launch(c, "welch4096_x", w4::k_x3, dim3(pl.n_pairs * n_cx), w4::NT, w4::LDS3_BYTES, ax));
@@ -1591,27 +1605,22 @@ static int welch4096_run(ds_ctx* c, int kind, const float* x, int n_cx, int64_t 
             CHK(launch(c, "welch4096_main@2", ky, dim3(pl.n_chunks * n_cy), w4::NT, w4::LDS_BYTES_2, ay));
         }
     }
-    WelchFinArgs f{auto_only ? pyy : psx, pxy, auto_only ? nullptr : pyy, pl.n_chunks, pl.n_chunks, n_cx, n_cy, kind, mode,
-                   FinishPar{norm_scale / (double)n_frames, factor, halve_edges, amp_sqrt, w4::NB}, out_c, out_r};
-    return launch_finish(c, f);
+    return launch_finish(c, welch_fin(q, auto_only ? pyy : psx, pxy, auto_only ? nullptr : pyy, pl.n_chunks, w4::NB));
 }
 
 // window 2048 at 50 % overlap: two 2048-point pair transforms per pass of the 4096-point register machine
 // (kernels_welch2048h.hpp)
-static bool welch2048h_applies(const ds_ctx* c, int W, int hop, int average, int64_t n_samples, int n_frames) {
-    return c && W == 2048 && hop == 1024 && average == DS_AVG_MEAN && !c->cfg.welch_generic && !c->cfg.w2048_wave &&
-           welch2048h::fits(n_samples, n_frames);
+static bool welch2048h_applies(const ds_ctx* c, const WelchCall& q) {
+    return q.W == 2048 && q.hop == 1024 && q.average == DS_AVG_MEAN && !c->cfg.welch_generic && !c->cfg.w2048_wave &&
+           welch2048h::fits(q.n_samples, q.n_frames);
 }
-static int welch2048h_run(ds_ctx* c, int kind, const float* x, int n_cx, int64_t ldx, const float* y, int n_cy,
-                          int64_t ldy, int64_t n_samples, int W, int hop, int n_frames, const float* window, int detrend,
-                          int average, int mode, int amp_sqrt, double norm_scale, double factor, int halve_edges,
-                          float2* out_c, float* out_r) {
+static int welch2048h_run(ds_ctx* c, const WelchCall& q) {
     namespace wh = welch2048h;
     namespace w4 = welch4096;
-    const bool auto_only = kind == 1;
+    const bool auto_only = q.auto_only();
     CHK(ensure_table(c, &c->w4_tables, w4::host_tables));
-    const int nf = frames_to_visit(n_samples, wh::HOP, n_frames);
-    const int n_out = auto_only ? n_cx : n_cy;
+    const int n_cx = q.n_cx, n_cy = q.n_cy, n_out = q.n_out();
+    const int nf = frames_to_visit(q.n_samples, wh::HOP, q.n_frames);
     wh::Plan pl = wh::plan(nf, n_out, auto_only ? 0 : n_cx, c->cfg.welch_chunks);
     float2 *xs, *pxy;
     float *px, *psx, *pyy;
@@ -1623,40 +1632,31 @@ static int welch2048h_run(ds_ctx* c, int kind, const float* x, int n_cx, int64_t
         pyy = cv.take<float>((size_t)pl.n_chunks * n_out * wh::NBW);
     }));
     // (Args::n_pairs counts passes of four frames here)
-    w4::Args ax{x, n_samples, ldx, 1, wh::HOP, nf, pl.n_passes, detrend, pl.n_chunks, 0, window, c->w4_tables, xs, px, pxy, pyy, psx};
+    w4::Args ax{q.x, q.n_samples, q.ldx, 1, wh::HOP, nf, pl.n_passes, q.detrend, pl.n_chunks, 0, q.window, c->w4_tables, xs, px,
+                pxy, pyy, psx};
     ax.n_cx = n_cx;
     if (auto_only) {
         ax.n_ch = n_cx;
         w4::place_remainder(ax, n_cx);
         CHK(launch(c, "welch2048_main@4k", wh::k_y2h<true>, dim3(pl.n_chunks * n_cx), w4::NT, wh::LDS_BYTES, ax));
-        WelchFinArgs f{pyy, nullptr, nullptr, pl.n_chunks, pl.n_chunks, n_cx, 0, 1, 0,
-                       FinishPar{norm_scale / (double)n_frames, factor, halve_edges, amp_sqrt, wh::NBW}, nullptr, out_r};
-        return launch_finish(c, f);
+        return launch_finish(c, welch_fin(q, pyy, nullptr, nullptr, pl.n_chunks, wh::NBW));
     }
-    w4::Args ay = ax;
-    ay.sig = y;
-    ay.ld = ldy;
-    ay.n_ch = n_cy;
+    w4::Args ay = y_args(ax, q);
     w4::place_remainder(ay, n_cy);
     CHK(launch(c, "welch2048_x", wh::k_x2h, dim3(pl.n_passes * n_cx), w4::NT, wh::LDS_BYTES, ax));
     if (n_cx > 1) CHK(launch(c, "welch2048_pxsum", wh::k_px_sum, dim3(pl.n_chunks, n_cx), 256, 0, ay));
     CHK(launch(c, "welch2048_main@4k", wh::k_y2h<false>, dim3(pl.n_chunks * n_cy), w4::NT, wh::LDS_BYTES, ay));
-    WelchFinArgs f{psx, pxy, pyy, pl.n_chunks, pl.n_chunks, n_cx, n_cy, kind, mode,
-                   FinishPar{norm_scale / (double)n_frames, factor, halve_edges, amp_sqrt, wh::NBW}, out_c, out_r};
-    return launch_finish(c, f);
+    return launch_finish(c, welch_fin(q, psx, pxy, pyy, pl.n_chunks, wh::NBW));
 }
 
 // window 8192: two 4096-point register transforms per frame pair (kernels_welch8192.hpp)
-static int welch8192_run(ds_ctx* c, int kind, const float* x, int n_cx, int64_t ldx, const float* y, int n_cy,
-                         int64_t ldy, int64_t n_samples, int W, int hop, int n_frames, const float* window, int detrend,
-                         int average, int mode, int amp_sqrt, double norm_scale, double factor, int halve_edges,
-                         float2* out_c, float* out_r) {
+static int welch8192_run(ds_ctx* c, const WelchCall& q) {
     namespace w8 = welch8k;
     CHK(ensure_table(c, &c->w4_tables, welch4096::host_tables));
     CHK(ensure_table(c, &c->deconv8k_tables, deconv8k::host_tables));
-    const bool auto_only = kind == 1;
-    const int n_out = auto_only ? n_cx : n_cy;
-    const int nf = frames_to_visit(n_samples, hop, n_frames);
+    const bool auto_only = q.auto_only();
+    const int n_cx = q.n_cx, n_cy = q.n_cy, n_out = q.n_out();
+    const int nf = frames_to_visit(q.n_samples, q.hop, q.n_frames);
     w8::Plan pl = w8::plan(nf, n_out, auto_only ? 1 : n_cx);
     float2 *xs = nullptr, *pxy = nullptr;
     float *px = nullptr, *psx = nullptr, *pyy;
@@ -1669,8 +1669,8 @@ static int welch8192_run(ds_ctx* c, int kind, const float* x, int n_cx, int64_t 
         }
         pyy = cv.take<float>((size_t)pl.n_chunks * n_out * w8::NB);
     }));
-    const bool half = hop == 4096;
-    w8::Args ax{x, n_samples, ldx, n_cx, hop, nf, pl.n_pairs, detrend, pl.n_chunks, window,
+    const bool half = q.hop == 4096;
+    w8::Args ax{q.x, q.n_samples, q.ldx, n_cx, q.hop, nf, pl.n_pairs, q.detrend, pl.n_chunks, q.window,
                 c->w4_tables, c->deconv8k_tables, (float4*)xs, px, pxy, pyy, psx, auto_only ? 0 : n_cx};
     // window in LDS + one exchange buffer per group (0.226 ms; the global-window / two-buffer
     // variant measured 0.280 ms and spilled: removed)
@@ -1681,30 +1681,21 @@ static int welch8192_run(ds_ctx* c, int kind, const float* x, int n_cx, int64_t 
         auto kx = half ? w8::k_x<true> : w8::k_x<false>;
         CHK(launch(c, "welch8192_x", kx, dim3(pl.n_pairs, n_cx), w8::NTB, w8::LDS_BYTES, ax));
         if (n_cx > 1) CHK(launch(c, "welch8192_pxsum", w8::k_px_sum, dim3(pl.n_chunks, n_cx), 256, 0, ax));
-        w8::Args ay = ax;
-        ay.sig = y;
-        ay.ld = ldy;
-        ay.n_ch = n_cy;
         auto ky = half ? w8::k_y<true, true> : w8::k_y<false, true>;
-        CHK(launch(c, "welch8192_main", ky, dim3(pl.n_chunks * n_cy), w8::NTB, w8::LDS_BYTES_WINLDS, ay));
+        CHK(launch(c, "welch8192_main", ky, dim3(pl.n_chunks * n_cy), w8::NTB, w8::LDS_BYTES_WINLDS, y_args(ax, q)));
     }
-    WelchFinArgs f{auto_only ? pyy : psx, pxy, auto_only ? nullptr : pyy, pl.n_chunks, pl.n_chunks, n_cx, n_cy, kind, mode,
-                   FinishPar{norm_scale / (double)n_frames, factor, halve_edges, amp_sqrt, w8::NB}, out_c, out_r};
-    return launch_finish(c, f);
+    return launch_finish(c, welch_fin(q, auto_only ? pyy : psx, pxy, auto_only ? nullptr : pyy, pl.n_chunks, w8::NB));
 }
 
 // window 16384: four 4096-point register transforms per frame pair, two per slot of 256 threads
 // (kernels_welch16384.hpp)
-static int welch16384_run(ds_ctx* c, int kind, const float* x, int n_cx, int64_t ldx, const float* y, int n_cy,
-                          int64_t ldy, int64_t n_samples, int W, int hop, int n_frames, const float* window, int detrend,
-                          int average, int mode, int amp_sqrt, double norm_scale, double factor, int halve_edges,
-                          float2* out_c, float* out_r) {
+static int welch16384_run(ds_ctx* c, const WelchCall& q) {
     namespace w16 = welch16k;
     CHK(ensure_table(c, &c->w4_tables, welch4096::host_tables));
     CHK(ensure_table(c, &c->fir16k_tables, fir16k::host_tables));
-    const bool auto_only = kind == 1;
-    const int n_out = auto_only ? n_cx : n_cy;
-    const int nf = frames_to_visit(n_samples, hop, n_frames);
+    const bool auto_only = q.auto_only();
+    const int n_cx = q.n_cx, n_cy = q.n_cy, n_out = q.n_out();
+    const int nf = frames_to_visit(q.n_samples, q.hop, q.n_frames);
     w16::Plan pl = w16::plan(nf, n_out, auto_only ? 1 : n_cx);
     float2 *xs = nullptr, *pxy = nullptr, *tu = nullptr;
     float *pxu = nullptr, *psx = nullptr, *pyy, *pu;
@@ -1719,7 +1710,7 @@ static int welch16384_run(ds_ctx* c, int kind, const float* x, int n_cx, int64_t
         if (!auto_only) tu = cv.take<float2>((size_t)pl.n_chunks * n_cy * w16::N);
         pu = cv.take<float>((size_t)pl.n_chunks * n_out * w16::N);
     }));
-    w16::Args ax{x, n_samples, ldx, n_cx, hop, nf, pl.n_pairs, detrend, pl.n_chunks, window,
+    w16::Args ax{q.x, q.n_samples, q.ldx, n_cx, q.hop, nf, pl.n_pairs, q.detrend, pl.n_chunks, q.window,
                  c->w4_tables, c->fir16k_tables, (float4*)xs, pxu, pxy, pyy, psx, auto_only ? 1 : n_cx, tu, pu};
     if (auto_only) {
         CHK(launch(c, "welch16384_main", w16::k_y<true>, dim3(pl.n_chunks * n_cx, 1, 4), w16::NTB, w16::LDS_BYTES, ax));
@@ -1727,25 +1718,21 @@ static int welch16384_run(ds_ctx* c, int kind, const float* x, int n_cx, int64_t
     } else {
         CHK(launch(c, "welch16384_x", w16::k_x, dim3(pl.n_pairs, n_cx, 4), w16::NTB, w16::LDS_BYTES, ax));
         CHK(launch(c, "welch16384_pxsum", w16::k_px_sum, dim3((w16::NB + 255) / 256, pl.n_chunks, n_cx), 256, 0, ax));
-        w16::Args ay = ax;
-        ay.sig = y;
-        ay.ld = ldy;
-        ay.n_ch = n_cy;
+        const w16::Args ay = y_args(ax, q);
         CHK(launch(c, "welch16384_main", w16::k_y<false>, dim3(pl.n_chunks * n_cy, 1, 4), w16::NTB, w16::LDS_BYTES, ay));
         CHK(launch(c, "welch16384_fold", w16::k_fold<false>, dim3((w16::NB + 255) / 256, pl.n_chunks * n_cy), 256, 0, ay));
     }
-    WelchFinArgs f{auto_only ? pyy : psx, pxy, auto_only ? nullptr : pyy, pl.n_chunks, pl.n_chunks, n_cx, n_cy, kind, mode,
-                   FinishPar{norm_scale / (double)n_frames, factor, halve_edges, amp_sqrt, w16::NB}, out_c, out_r};
-    return launch_finish(c, f);
+    return launch_finish(c, welch_fin(q, auto_only ? pyy : psx, pxy, auto_only ? nullptr : pyy, pl.n_chunks, w16::NB));
 }
 
 // Windows of 2^15 ... 2^18 samples: decimation in frequency into R = W / 4096 class sequences (k_dif), the headline
 // kernel's loop on them (k_xc / k_yc), fold across the classes, finish (kernels_welch_long.hpp).
-static bool welch_long_applies(const ds_ctx* c, int W, int n_ch_total, int64_t n_samples, int n_frames, int hop, int average) {
-    if (!c || c->cfg.welch_generic || average != DS_AVG_MEAN || !welchl::classes_of(W) || W < c->cfg.welch_long_min) return false;
-    if (hop <= 0 || hop > W || !welchl::buf_fits(n_samples, n_frames, hop, W)) return false;
+static bool welch_long_applies(const ds_ctx* c, const WelchCall& q) {
+    const int W = q.W, n_ch_total = q.n_cx + q.nyc();
+    if (c->cfg.welch_generic || q.average != DS_AVG_MEAN || !welchl::classes_of(W) || W < c->cfg.welch_long_min) return false;
+    if (!welchl::buf_fits(q.n_samples, q.n_frames, q.hop, W)) return false;
     // the class sequences: one complex value per sample of every frame pair (8 bytes per sample at 50 % overlap)
-    const int64_t pairs = ((int64_t)frames_to_visit(n_samples, hop, n_frames) + 1) / 2;
+    const int64_t pairs = ((int64_t)frames_to_visit(q.n_samples, q.hop, q.n_frames) + 1) / 2;
     // launch grids: k_dif puts the frame pairs on grid.y and the channels on grid.z, k_fold (chunk, channel) units on
     // grid.y (chunks <= max(768 / R, pairs / 64), kernels_welch_long.hpp plan()); shapes beyond 65535 there (99 %
     // overlap on 2^25 samples, ...) fall through to the routes behind this one
@@ -1753,18 +1740,16 @@ static bool welch_long_applies(const ds_ctx* c, int W, int n_ch_total, int64_t n
     if (pairs > 65535 || n_ch_total > 65535 || chunks_max * n_ch_total > 65535) return false;
     return (int64_t)n_ch_total * pairs * W * 8 <= ((int64_t)16 << 30);
 }
-static int welch_long_run(ds_ctx* c, int kind, const float* x, int n_cx, int64_t ldx, const float* y, int n_cy,
-                          int64_t ldy, int64_t n_samples, int W, int hop, int n_frames, const float* window, int detrend,
-                          int average, int mode, int amp_sqrt, double norm_scale, double factor, int halve_edges,
-                          float2* out_c, float* out_r) {
+static int welch_long_run(ds_ctx* c, const WelchCall& q) {
     namespace wl = welchl;
-    const bool auto_only = kind == 1;
+    const bool auto_only = q.auto_only();
+    const int n_cx = q.n_cx, n_cy = q.n_cy, W = q.W;
     const int R = wl::classes_of(W);
     int lgR;
     const float2* twl;
     CHK(long_tables(c, R, &lgR, &twl));
-    const int nf = frames_to_visit(n_samples, hop, n_frames), nb = W / 2 + 1;
-    const int n_out = auto_only ? n_cx : n_cy;  // channels that are accumulated
+    const int nf = frames_to_visit(q.n_samples, q.hop, q.n_frames), nb = W / 2 + 1;
+    const int n_out = q.n_out();
     wl::Plan pl = wl::plan(nf, n_out, R);
     const size_t seq = (size_t)pl.n_pairs * W;  // complex values per channel
     float2 *bx, *by, *xs, *pxy, *tu;
@@ -1780,7 +1765,7 @@ static int welch_long_run(ds_ctx* c, int kind, const float* x, int n_cx, int64_t
         pyy = cv.take<float>((size_t)pl.n_chunks * n_out * nb);
         pu = cv.take<float>((size_t)pl.n_chunks * n_out * W);
     }));
-    wl::Args ax{x, n_samples, ldx, n_cx, hop, nf, pl.n_pairs, detrend, pl.n_chunks, R, lgR, window, c->w4_tables, twl,
+    wl::Args ax{q.x, q.n_samples, q.ldx, n_cx, q.hop, nf, pl.n_pairs, q.detrend, pl.n_chunks, R, lgR, q.window, c->w4_tables, twl,
                 bx, (float4*)xs, pxu, pxy, pyy, psx, n_cx, tu, pu};
     auto dif = [&](const wl::Args& a, int n_ch) {
         const dim3 grid(wl::M / wl::NT, pl.n_pairs, n_ch);
@@ -1791,16 +1776,11 @@ static int welch_long_run(ds_ctx* c, int kind, const float* x, int n_cx, int64_t
     if (auto_only) {
         CHK(launch(c, "welch_long_main", wl::k_yc<true>, dim3((unsigned)(pl.n_chunks * n_cx * R)), wl::NT, wl::LDS_BYTES, ax));
         CHK(launch(c, "welch_long_fold", wl::k_fold<true>, fold_grid, 256, 0, ax));
-        WelchFinArgs f{pyy, nullptr, nullptr, pl.n_chunks, pl.n_chunks, n_cx, 0, 1, 0,
-                       FinishPar{norm_scale / (double)n_frames, factor, halve_edges, amp_sqrt, nb}, nullptr, out_r};
-        return launch_finish(c, f);
+        return launch_finish(c, welch_fin(q, pyy, nullptr, nullptr, pl.n_chunks, nb));
     }
     CHK(launch(c, "welch_long_x", wl::k_xc, dim3((unsigned)(pl.n_pairs * R * n_cx)), wl::NT, wl::LDS_BYTES, ax));
     CHK(launch(c, "welch_long_pxsum", wl::k_px_sum, dim3((nb + 255) / 256, pl.n_chunks, n_cx), 256, 0, ax));
-    wl::Args ay = ax;
-    ay.sig = y;
-    ay.ld = ldy;
-    ay.n_ch = n_cy;
+    wl::Args ay = y_args(ax, q);
     ay.b = by;
     CHK(dif(ay, n_cy));
     if (c->cfg.welch_long_3percu)
@@ -1808,9 +1788,7 @@ static int welch_long_run(ds_ctx* c, int kind, const float* x, int n_cx, int64_t
     else
         CHK(launch(c, "welch_long_main", wl::k_yc<false>, dim3((unsigned)(pl.n_chunks * n_cy * R)), wl::NT, wl::LDS_BYTES, ay));
     CHK(launch(c, "welch_long_fold", wl::k_fold<false>, fold_grid, 256, 0, ay));
-    WelchFinArgs f{psx, pxy, pyy, pl.n_chunks, pl.n_chunks, n_cx, n_cy, kind, mode,
-                   FinishPar{norm_scale / (double)n_frames, factor, halve_edges, amp_sqrt, nb}, out_c, out_r};
-    return launch_finish(c, f);
+    return launch_finish(c, welch_fin(q, psx, pxy, pyy, pl.n_chunks, nb));
 }
 
 // windows of 256 / 512 / 1024 / 2048 samples (1024 = the reference's default): wave-level register transforms
@@ -1818,18 +1796,15 @@ static int welch_long_run(ds_ctx* c, int kind, const float* x, int n_cx, int64_t
 // transformed zero-padded to NN points and every (NN / W)-th bin is kept (removing a frame's mean still only clears
 // bin 0 of the kept bins)
 template <int NN>
-static int welch_wave_run(ds_ctx* c, int kind, const float* x, int n_cx, int64_t ldx, const float* y, int n_cy,
-                          int64_t ldy, int64_t n_samples, int W, int hop, int n_frames, const float* window, int detrend,
-                          int average, int mode, int amp_sqrt, double norm_scale, double factor, int halve_edges,
-                          float2* out_c, float* out_r) {
+static int welch_wave_run(ds_ctx* c, const WelchCall& q) {
     namespace w1 = welch1k;
     using G = w1::WG<NN>;
     const float2* tab;
     CHK(wave_tables<NN>(c, &tab));
-    const bool auto_only = kind == 1;
-    const int n_out = auto_only ? n_cx : n_cy;
-    const int decim = NN / W;
-    const int nf = frames_to_visit(n_samples, hop, n_frames);
+    const bool auto_only = q.auto_only();
+    const int n_cx = q.n_cx, n_cy = q.n_cy, n_out = q.n_out();
+    const int decim = NN / q.W;
+    const int nf = frames_to_visit(q.n_samples, q.hop, q.n_frames);
     w1::Plan pl = w1::plan<NN>(nf, n_out, auto_only ? 1 : n_cx, c->cfg.welch1k_chunks);
     float *wz, *px = nullptr, *psx = nullptr, *pyy;
     float2 *xs = nullptr, *pxy = nullptr;
@@ -1843,13 +1818,14 @@ static int welch_wave_run(ds_ctx* c, int kind, const float* x, int n_cx, int64_t
         }
         pyy = cv.take<float>((size_t)pl.n_chunks * n_out * G::NB);
     }));
+    const float* window = q.window;
     if (decim > 1) {  // the window, zero-padded to the transform length
         HIPCHK(c, hipMemsetAsync(wz, 0, sizeof(float) * NN, c->stream));
         HIPCHK(c, hipMemcpyAsync(wz, window, sizeof(float) * (NN / decim), hipMemcpyDeviceToDevice, c->stream));
         window = wz;
     }
-    const bool half = hop == NN / 2;
-    w1::Args ax{x, n_samples, ldx, n_cx, hop, nf, pl.n_pairs, detrend, pl.n_chunks, pl.ppc, window,
+    const bool half = q.hop == NN / 2;
+    w1::Args ax{q.x, q.n_samples, q.ldx, n_cx, q.hop, nf, pl.n_pairs, q.detrend, pl.n_chunks, pl.ppc, window,
                 tab, (float4*)xs, px, pxy, pyy, psx, auto_only ? 1 : n_cx};
     const int n_grp = (n_out + G::TPB - 1) / G::TPB;
     if (auto_only) {
@@ -1860,74 +1836,61 @@ static int welch_wave_run(ds_ctx* c, int kind, const float* x, int n_cx, int64_t
         auto ky = half ? w1::k_y<NN, true> : w1::k_y<NN, false>;
         CHK(launch(c, "welch1024_x", kx, dim3((pl.n_pairs + G::TPB - 1) / G::TPB, n_cx), w1::NTB, G::LDS_BYTES, ax));
         if (n_cx > 1) CHK(launch(c, "welch1024_pxsum", w1::k_px_sum<NN>, dim3(pl.n_chunks, n_cx), 256, 0, ax));
-        w1::Args ay = ax;
-        ay.sig = y;
-        ay.ld = ldy;
-        ay.n_ch = n_cy;
-        CHK(launch(c, "welch1024_main", ky, dim3(pl.n_chunks * n_grp), w1::NTB, G::LDS_BYTES, ay));
+        CHK(launch(c, "welch1024_main", ky, dim3(pl.n_chunks * n_grp), w1::NTB, G::LDS_BYTES, y_args(ax, q)));
     }
-    WelchFinArgs f{auto_only ? pyy : psx, pxy, auto_only ? nullptr : pyy, pl.n_chunks, pl.n_chunks, n_cx, n_cy, kind, mode,
-                   FinishPar{norm_scale / (double)n_frames, factor, halve_edges, amp_sqrt, NN / decim / 2 + 1},
-                   out_c, out_r, G::NB, decim};
+    WelchFinArgs f = welch_fin(q, auto_only ? pyy : psx, pxy, auto_only ? nullptr : pyy, pl.n_chunks, NN / decim / 2 + 1);
+    f.in_nb = G::NB;
+    f.in_step = decim;
     return launch_finish(c, f);
 }
 
-// What welch_common checks of its arguments, once per call: `who` is the entry point named in the message.
-static int welch_check(ds_ctx* c, const char* who, int kind, const float* x, int n_cx, int64_t ldx, const float* y,
-                       int n_cy, int64_t ldy, int64_t n_samples, int W, int hop, int n_frames, const float* window,
-                       int average, int mode) {
-    const std::string w(who);
-    if (!c || !x || !window) return fail(c, DS_ERR_ARG, w + ": null argument");
-    if (average != DS_AVG_MEAN && average != DS_AVG_MEDIAN)
+// What every Welch entry checks of its call, once, before anything is staged or launched
+static int welch_check(ds_ctx* c, const WelchCall& q) {
+    const std::string w(q.who);
+    if (!c || !q.x || !q.window) return fail(c, DS_ERR_ARG, w + ": null argument");
+    if ((q.kind != PSD && !q.out_c) || (q.kind != CSD && !q.out_r)) return fail(c, DS_ERR_ARG, w + ": null output");
+    if (q.average != DS_AVG_MEAN && q.average != DS_AVG_MEDIAN)
         return fail(c, DS_ERR_ARG, w + ": average must be mean (0) or median (1)");
-    if (kind != 1 && !y) return fail(c, DS_ERR_ARG, w + ": null output-signal pointer");
-    if (n_cx <= 0 || n_samples <= 0 || hop <= 0 || hop > W || n_frames <= 0 || ldx < n_samples)
+    if (!q.auto_only() && !q.y) return fail(c, DS_ERR_ARG, w + ": null output-signal pointer");
+    if (q.n_cx <= 0 || q.n_samples <= 0 || q.hop <= 0 || q.hop > q.W || q.n_frames <= 0 || q.ldx < q.n_samples)
         return fail(c, DS_ERR_ARG, w + ": bad shape");
-    if (kind != 1 && (n_cy <= 0 || ldy < n_samples || !(n_cx == 1 || n_cx == n_cy)))
+    if (!q.auto_only() && (q.n_cy <= 0 || q.ldy < q.n_samples || !(q.n_cx == 1 || q.n_cx == q.n_cy)))
         return fail(c, DS_ERR_ARG, w + ": input must have 1 channel or as many as the output");
-    if (kind == 0 && (mode < DS_TF_H1 || mode > DS_TF_H3))
+    if (q.kind == TF && (q.mode < DS_TF_H1 || q.mode > DS_TF_H3))
         return fail(c, DS_ERR_ARG, w + ": unsupported transfer function type");
     return DS_OK;
 }
 
-using WelchRunner = int (*)(ds_ctx*, int, const float*, int, int64_t, const float*, int, int64_t, int64_t, int, int, int,
-                            const float*, int, int, int, int, double, double, int, float2*, float*);
-
-// The kernel family of a checked call: the register kernels of its window where they apply, welch_common otherwise.
-static WelchRunner welch_route(const ds_ctx* c, int kind, int W, int hop, int average, int n_cx, int64_t ldx, int n_cy,
-                               int64_t ldy, int64_t n_samples, int n_frames) {
-    if (average != DS_AVG_MEAN) return welch_common;
+using WelchRunner = int (*)(ds_ctx*, const WelchCall&);
+// The kernel family of a checked call: the register kernels of its window where they apply; behind them the four-step
+// transforms for windows beyond the LDS-resident FFT and the generic LDS kernels (medians, means) for the others.
+static WelchRunner welch_route(const ds_ctx* c, const WelchCall& q) {
+    const int W = q.W;
+    const WelchRunner rest = q.big() ? welch_big_run : (q.average == DS_AVG_MEDIAN ? welch_median_run : welch_mean_run);
+    if (q.average != DS_AVG_MEAN) return rest;
     const bool generic = c->cfg.welch_generic;
     // (DSPTOOLBOX_AMD_WELCH_GENERIC keeps transfer functions with 4096-sample windows on the register kernels)
-    if (W == 4096 && !c->cfg.no_welch4096 && (kind == 0 || !generic)) return welch4096_run;
-    if (welch_long_applies(c, W, kind == 1 ? n_cx : n_cx + n_cy, n_samples, n_frames, hop, average)) return welch_long_run;
-    if (generic) return welch_common;
-    if (W == 16384 && welch16k::buf_fits(n_samples, n_frames, hop)) return welch16384_run;
-    if (W == 8192 && welch8k::buf_fits(n_samples, n_frames, hop)) return welch8192_run;
-    if (welch2048h_applies(c, W, hop, average, n_samples, n_frames)) return welch2048h_run;
+    if (W == 4096 && !c->cfg.no_welch4096 && (q.kind == TF || !generic)) return welch4096_run;
+    if (welch_long_applies(c, q)) return welch_long_run;
+    if (generic) return rest;
+    if (W == 16384 && welch16k::buf_fits(q.n_samples, q.n_frames, q.hop)) return welch16384_run;
+    if (W == 8192 && welch8k::buf_fits(q.n_samples, q.n_frames, q.hop)) return welch8192_run;
+    if (welch2048h_applies(c, q)) return welch2048h_run;
     // the wave kernels: the accumulated channels (y; auto spectra: x) must fit their buffer descriptors
-    if (W > 2048 || W < 32 || !welch1k::buf_fits(n_samples, kind == 1 ? n_cx : n_cy, kind == 1 ? ldx : ldy))
-        return welch_common;
+    if (W > 2048 || W < 32 || !welch1k::buf_fits(q.n_samples, q.n_out(), q.auto_only() ? q.ldx : q.ldy)) return rest;
     switch (W) {
         case 2048: return welch_wave_run<2048>;
         case 1024: return welch_wave_run<1024>;
         case 512: return welch_wave_run<512>;
         case 256: case 128: case 64: case 32: return welch_wave_run<256>;
-        default: return welch_common;
+        default: return rest;
     }
 }
 
-// The three device entry points: check, choose the route, run it.
-static int welch_dev(ds_ctx* c, const char* who, int kind, const float* x, int n_cx, int64_t ldx, const float* y,
-                     int n_cy, int64_t ldy, int64_t n_samples, int W, int hop, int n_frames, const float* window,
-                     int detrend, int average, int mode, int amp_sqrt, double norm_scale, double factor,
-                     int halve_edges, float2* out_c, float* out_r) {
-    CHK(welch_check(c, who, kind, x, n_cx, ldx, y, n_cy, ldy, n_samples, W, hop, n_frames, window, average, mode));
-    const WelchRunner run = welch_route(c, kind, W, hop, average, n_cx, ldx, n_cy, ldy, n_samples, n_frames);
-    // (cross spectra: the finish reads no mode; the register kernels have always been handed H1, welch_common 0)
-    if (kind == 2 && run != welch_common) mode = DS_TF_H1;
-    return run(c, kind, x, n_cx, ldx, y, n_cy, ldy, n_samples, W, hop, n_frames, window, detrend, average, mode, amp_sqrt,
-               norm_scale, factor, halve_edges, out_c, out_r);
+// The device entry points: check, choose the route, run it.
+static int welch_dev(ds_ctx* c, const WelchCall& q) {
+    CHK(welch_check(c, q));
+    return welch_route(c, q)(c, q);
 }
 
 extern "C" int ds_welch_tf_dev(ds_ctx* c, const float* x, int n_cx, int64_t ldx, const float* y,
@@ -1935,27 +1898,15 @@ extern "C" int ds_welch_tf_dev(ds_ctx* c, const float* x, int n_cx, int64_t ldx,
                                const float* window, int detrend, int average, int mode, int amp_sqrt,
                                double norm_scale, double factor, int halve_edges, ds_c32* tf,
                                float* coh) {
-    if (!tf || !coh) return fail(c, DS_ERR_ARG, "ds_welch_tf: null output");
-    return welch_dev(c, "ds_welch_tf", 0, x, n_cx, ldx, y, n_cy, ldy, n_samples, W, hop, n_frames, window, detrend, average,
-                     mode, amp_sqrt, norm_scale, factor, halve_edges, (float2*)tf, coh);
+    return welch_dev(c, {"ds_welch_tf_dev", TF, x, n_cx, ldx, y, n_cy, ldy, n_samples, W, hop, n_frames, window, detrend,
+                         average, mode, amp_sqrt, norm_scale, factor, halve_edges, (float2*)tf, coh});
 }
 extern "C" int ds_welch_psd_dev(ds_ctx* c, const float* x, int n_cx, int64_t ldx, int64_t n_samples,
                                 int W, int hop, int n_frames, const float* window, int detrend,
                                 int average, int amp_sqrt, double norm_scale, double factor,
                                 int halve_edges, float* psd) {
-    if (!psd) return fail(c, DS_ERR_ARG, "ds_welch_psd: null output");
-    return welch_dev(c, "ds_welch_psd", 1, x, n_cx, ldx, nullptr, 0, 0, n_samples, W, hop, n_frames, window, detrend,
-                     average, 0, amp_sqrt, norm_scale, factor, halve_edges, nullptr, psd);
-}
-// csd_i = mean_f conj(X_i) Y_i is the cross sum a transfer function with one input channel per
-// output channel accumulates: the same kernels with the finish of kind 2
-static int welch_csd_dev(ds_ctx* c, const float* x, const float* y, int n_ch, int64_t ld,
-                         int64_t n_samples, int W, int hop, int n_frames, const float* window,
-                         int detrend, int average, int amp_sqrt, double norm_scale, double factor,
-                         int halve_edges, ds_c32* csd) {
-    if (!csd) return fail(c, DS_ERR_ARG, "ds_welch_csd: null output");
-    return welch_dev(c, "ds_welch_csd", 2, x, n_ch, ld, y, n_ch, ld, n_samples, W, hop, n_frames, window, detrend, average,
-                     0, amp_sqrt, norm_scale, factor, halve_edges, (float2*)csd, nullptr);
+    return welch_dev(c, {"ds_welch_psd_dev", PSD, x, n_cx, ldx, nullptr, 0, 0, n_samples, W, hop, n_frames, window, detrend,
+                         average, 0, amp_sqrt, norm_scale, factor, halve_edges, nullptr, psd});
 }
 // float64 frame spectra of a device-resident (samples, channels) float64 array: W <= 16384 one workgroup per
 // (frame, channel); 2^15 ... 2^18 one per (frame, class, channel) + the split (class spectra in the workspace)
@@ -2216,8 +2167,7 @@ static int csm_median_run(ds_ctx* c, const CsmCall& q) {
         else scratch = cv.take<float>((size_t)pl.n_chunks * q.n_ch * nb);
     }));
     if (q.big()) {
-        CHK(stft_big(c, s, q.x, q.n_ch, q.ld, q.n_samples, q.W, q.hop, q.W, 0, q.n_frames, q.window, q.detrend, 1.0f, 1.0f, 0,
-                     0, xsp));
+        CHK(stft_big(c, s, window_spectra(q, q.x, q.n_ch, q.ld, xsp), 0));
     } else {
         const float2* tw;
         CHK(get_twiddles(c, q.W, &tw));
@@ -2286,7 +2236,7 @@ static int csm_gemm_run(ds_ctx* c, const CsmCall& q) {
         if (q.big()) s = take_big_scratch(cv, n_ch, q.n_frames, q.W);
     }));
     if (q.big())
-        CHK(stft_big(c, s, q.x, n_ch, q.ld, q.n_samples, q.W, q.hop, q.W, 0, q.n_frames, q.window, q.detrend, 1.0f, 1.0f, 0, 1, X));
+        CHK(stft_big(c, s, window_spectra(q, q.x, n_ch, q.ld, X), 1));
     else
         CHK(ds_stft_r2c_dev(c, q.x, q.n_samples, n_ch, q.ld, q.W, q.hop, q.W, 0, q.n_frames, q.window, q.detrend, 1.0f, 1.0f,
                             0, (ds_c32*)X));
@@ -3105,31 +3055,29 @@ extern "C" int ds_fir_ola_f64(ds_ctx* c, const double* x, int n_ch, int64_t n_sa
     return fir_ola_host(c, "ds_fir_ola_f64", nullptr, x, n_ch, n_samples, taps, n_filt, n_taps, mode, nullptr, y);
 }
 
-static int welch_tf_host(ds_ctx* c, const char* who, const float* x, const float* y, const double* x64,
-                         const double* y64, int n_cx, int n_cy, int64_t n_samples, int W, int hop, int n_frames,
-                         const float* window, int detrend, int average, int mode, int amp_sqrt, double norm_scale,
-                         double factor, int halve_edges, ds_c32* tf, float* coh) {
-    if (!c || (!x && !x64) || (!y && !y64) || !window || !tf || !coh)
-        return fail(c, DS_ERR_ARG, std::string(who) + ": null argument");
-    if (n_cx <= 0 || n_cy <= 0 || n_samples <= 0 || W <= 0) return fail(c, DS_ERR_ARG, std::string(who) + ": bad shape");
-    const size_t no = (size_t)(W / 2 + 1) * n_cy;
-    float *dx, *dy, *dw, *dcoh;
-    float2* dtf;
+// The body of the six host Welch entries: q with the host pointers (x / y planar float32 [n_ch][n_samples], or cast from
+// x64 / y64: the reference's (n_samples, n_ch) float64 C-order arrays as they are, classes/signal.py:222-301)
+static int welch_host(ds_ctx* c, WelchCall q, const double* x64, const double* y64) {
+    // (the host pointers, only checked: the staged copies replace them below)
+    CHK(welch_check(c, q));
+    const float *hx = q.x, *hy = q.y, *hw = q.window;
+    float2* const hc = q.out_c;
+    float* const hr = q.out_r;
+    const size_t no = (size_t)(q.W / 2 + 1) * q.n_out();
+    float *dx, *dy, *dw;
     CHK(carve(c, &c->io, &c->io_bytes, [&](Carver& cv) {
-        dx = cv.take<float>((size_t)n_cx * n_samples);
-        dy = cv.take<float>((size_t)n_cy * n_samples);
-        dw = cv.take<float>(W);
-        dtf = cv.take<float2>(no);
-        dcoh = cv.take<float>(no);
+        q.x = dx = cv.take<float>((size_t)q.n_cx * q.n_samples);
+        if (hy) q.y = dy = cv.take<float>((size_t)q.n_cy * q.n_samples);
+        q.window = dw = cv.take<float>(q.W);
+        if (hc) q.out_c = cv.take<float2>(no);
+        if (hr) q.out_r = cv.take<float>(no);
     }));
-    CHK(upload_signal(c, x, x64, n_samples, n_cx, dx));
-    CHK(upload_signal(c, y, y64, n_samples, n_cy, dy));
-    CHK(ds_upload(c, dw, window, (size_t)W * 4));
-    CHK(ds_welch_tf_dev(c, dx, n_cx, n_samples, dy, n_cy, n_samples, n_samples, W, hop, n_frames, dw,
-                        detrend, average, mode, amp_sqrt, norm_scale, factor, halve_edges, (ds_c32*)dtf,
-                        dcoh));
-    CHK(ds_download(c, tf, dtf, no * 8));
-    return ds_download(c, coh, dcoh, no * 4);
+    CHK(upload_signal(c, hx, x64, q.n_samples, q.n_cx, dx));
+    if (hy) CHK(upload_signal(c, hy, y64, q.n_samples, q.n_cy, dy));
+    CHK(ds_upload(c, dw, hw, (size_t)q.W * 4));
+    CHK(welch_route(c, q)(c, q));
+    if (hc) CHK(ds_download(c, hc, q.out_c, no * 8));
+    return hr ? ds_download(c, hr, q.out_r, no * 4) : DS_OK;
 }
 // ds_welch_tf with the reference's own array layout at the boundary: x (n_samples, n_cx) and
 // y (n_samples, n_cy) float64 C-order (classes/signal.py:222-301), outputs as ds_welch_tf.
@@ -3137,84 +3085,47 @@ extern "C" int ds_welch_tf_f64(ds_ctx* c, const double* x, int n_cx, const doubl
                                int64_t n_samples, int W, int hop, int n_frames, const float* window,
                                int detrend, int average, int mode, int amp_sqrt, double norm_scale,
                                double factor, int halve_edges, ds_c32* tf, float* coh) {
-    return welch_tf_host(c, "ds_welch_tf_f64", nullptr, nullptr, x, y, n_cx, n_cy, n_samples, W, hop, n_frames, window,
-                         detrend, average, mode, amp_sqrt, norm_scale, factor, halve_edges, tf, coh);
+    return welch_host(c, {"ds_welch_tf_f64", TF, (const float*)x, n_cx, n_samples, (const float*)y, n_cy, n_samples, n_samples,
+                          W, hop, n_frames, window, detrend, average, mode, amp_sqrt, norm_scale, factor, halve_edges,
+                          (float2*)tf, coh}, x, y);
 }
 extern "C" int ds_welch_tf(ds_ctx* c, const float* x, int n_cx, const float* y, int n_cy,
                            int64_t n_samples, int W, int hop, int n_frames, const float* window,
                            int detrend, int average, int mode, int amp_sqrt, double norm_scale,
                            double factor, int halve_edges, ds_c32* tf, float* coh) {
-    return welch_tf_host(c, "ds_welch_tf", x, y, nullptr, nullptr, n_cx, n_cy, n_samples, W, hop, n_frames, window,
-                         detrend, average, mode, amp_sqrt, norm_scale, factor, halve_edges, tf, coh);
+    return welch_host(c, {"ds_welch_tf", TF, x, n_cx, n_samples, y, n_cy, n_samples, n_samples, W, hop, n_frames, window,
+                          detrend, average, mode, amp_sqrt, norm_scale, factor, halve_edges, (float2*)tf, coh}, nullptr, nullptr);
 }
 
-static int welch_psd_host(ds_ctx* c, const float* x, const double* x64, int n_cx, int64_t n_samples, int W,
-                          int hop, int n_frames, const float* window, int detrend, int average, int amp_sqrt,
-                          double norm_scale, double factor, int halve_edges, float* psd) {
-    if (!c || (!x && !x64) || !window || !psd) return fail(c, DS_ERR_ARG, "ds_welch_psd: null argument");
-    if (n_cx <= 0 || n_samples <= 0 || W <= 0) return fail(c, DS_ERR_ARG, "ds_welch_psd: bad shape");
-    const size_t no = (size_t)(W / 2 + 1) * n_cx;
-    float *dx, *dw, *dp;
-    CHK(carve(c, &c->io, &c->io_bytes, [&](Carver& cv) {
-        dx = cv.take<float>((size_t)n_cx * n_samples);
-        dw = cv.take<float>(W);
-        dp = cv.take<float>(no);
-    }));
-    CHK(upload_signal(c, x, x64, n_samples, n_cx, dx));
-    CHK(ds_upload(c, dw, window, (size_t)W * 4));
-    CHK(ds_welch_psd_dev(c, dx, n_cx, n_samples, n_samples, W, hop, n_frames, dw, detrend, average,
-                         amp_sqrt, norm_scale, factor, halve_edges, dp));
-    return ds_download(c, psd, dp, no * 4);
-}
 extern "C" int ds_welch_psd(ds_ctx* c, const float* x, int n_cx, int64_t n_samples, int W, int hop,
                             int n_frames, const float* window, int detrend, int average, int amp_sqrt,
                             double norm_scale, double factor, int halve_edges, float* psd) {
-    return welch_psd_host(c, x, nullptr, n_cx, n_samples, W, hop, n_frames, window, detrend, average, amp_sqrt,
-                          norm_scale, factor, halve_edges, psd);
+    return welch_host(c, {"ds_welch_psd", PSD, x, n_cx, n_samples, nullptr, 0, 0, n_samples, W, hop, n_frames, window, detrend,
+                          average, 0, amp_sqrt, norm_scale, factor, halve_edges, nullptr, psd}, nullptr, nullptr);
 }
 extern "C" int ds_welch_psd_f64(ds_ctx* c, const double* x, int n_cx, int64_t n_samples, int W, int hop,
                                 int n_frames, const float* window, int detrend, int average, int amp_sqrt,
                                 double norm_scale, double factor, int halve_edges, float* psd) {
-    return welch_psd_host(c, nullptr, x, n_cx, n_samples, W, hop, n_frames, window, detrend, average, amp_sqrt,
-                          norm_scale, factor, halve_edges, psd);
+    return welch_host(c, {"ds_welch_psd_f64", PSD, (const float*)x, n_cx, n_samples, nullptr, 0, 0, n_samples, W, hop, n_frames,
+                          window, detrend, average, 0, amp_sqrt, norm_scale, factor, halve_edges, nullptr, psd}, x, nullptr);
 }
 
-// x / y: planar float32 [n_ch][n_samples], or x64 / y64: the reference's (n_samples, n_ch) float64 arrays as they are
-static int welch_csd_host(ds_ctx* c, const float* x, const float* y, const double* x64, const double* y64, int n_ch,
-                          int64_t n_samples, int W, int hop, int n_frames, const float* window, int detrend, int average,
-                          int amp_sqrt, double norm_scale, double factor, int halve_edges, ds_c32* csd) {
-    if (!c || (!x && !x64) || (!y && !y64) || !window || !csd) return fail(c, DS_ERR_ARG, "ds_welch_csd: null argument");
-    if (n_ch <= 0 || n_samples <= 0 || W <= 0) return fail(c, DS_ERR_ARG, "ds_welch_csd: bad shape");
-    const size_t nx = (size_t)n_ch * n_samples, no = (size_t)(W / 2 + 1) * n_ch;
-    float *dx, *dy, *dw;
-    float2* dc;
-    CHK(carve(c, &c->io, &c->io_bytes, [&](Carver& cv) {
-        dx = cv.take<float>(nx);
-        dy = cv.take<float>(nx);
-        dw = cv.take<float>(W);
-        dc = cv.take<float2>(no);
-    }));
-    CHK(upload_signal(c, x, x64, n_samples, n_ch, dx));
-    CHK(upload_signal(c, y, y64, n_samples, n_ch, dy));
-    CHK(ds_upload(c, dw, window, (size_t)W * 4));
-    CHK(welch_csd_dev(c, dx, dy, n_ch, n_samples, n_samples, W, hop, n_frames, dw, detrend, average,
-                      amp_sqrt, norm_scale, factor, halve_edges, (ds_c32*)dc));
-    return ds_download(c, csd, dc, no * 8);
-}
+// csd_i = mean_f conj(X_i) Y_i is the cross sum a transfer function with one input channel per
+// output channel accumulates: the same kernels with the finish of kind CSD
 extern "C" int ds_welch_csd(ds_ctx* c, const float* x, const float* y, int n_ch, int64_t n_samples,
                             int W, int hop, int n_frames, const float* window, int detrend,
                             int average, int amp_sqrt, double norm_scale, double factor,
                             int halve_edges, ds_c32* csd) {
-    return welch_csd_host(c, x, y, nullptr, nullptr, n_ch, n_samples, W, hop, n_frames, window, detrend, average, amp_sqrt,
-                          norm_scale, factor, halve_edges, csd);
+    return welch_host(c, {"ds_welch_csd", CSD, x, n_ch, n_samples, y, n_ch, n_samples, n_samples, W, hop, n_frames, window,
+                          detrend, average, 0, amp_sqrt, norm_scale, factor, halve_edges, (float2*)csd, nullptr}, nullptr, nullptr);
 }
 extern "C" int ds_welch_csd_f64(ds_ctx* c, const double* x, const double* y, int n_ch, int64_t n_samples,
                                 int W, int hop, int n_frames, const float* window, int detrend,
                                 int average, int amp_sqrt, double norm_scale, double factor,
                                 int halve_edges, ds_c32* csd) {
-    if (!x || !y) return fail(c, DS_ERR_ARG, "ds_welch_csd_f64: null argument");
-    return welch_csd_host(c, nullptr, nullptr, x, y, n_ch, n_samples, W, hop, n_frames, window, detrend, average, amp_sqrt,
-                          norm_scale, factor, halve_edges, csd);
+    return welch_host(c, {"ds_welch_csd_f64", CSD, (const float*)x, n_ch, n_samples, (const float*)y, n_ch, n_samples, n_samples,
+                          W, hop, n_frames, window, detrend, average, 0, amp_sqrt, norm_scale, factor, halve_edges,
+                          (float2*)csd, nullptr}, x, y);
 }
 
 static int csm_host(ds_ctx* c, const char* who, const float* x, const double* x64, int n_ch, int64_t n_samples, int W,

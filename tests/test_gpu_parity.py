@@ -2702,6 +2702,86 @@ def test_welch_routes_per_window(switch, kind, W, monkeypatch):
     assert seen == want
 
 
+# ---- calls every Welch entry point refuses (tests/golden/welch_rejected.json) ----------------------------------------
+# Keys "<entry>|<what is wrong>", values "ERR<code>" as _route_call records them.  Each call is a valid small estimate
+# (256-sample window, three channels, arrays of full size) with ONE argument spoilt, so it is refused by the argument
+# checks and launches nothing.  Recorded on the library before the Welch runners took one call struct (csrc/api.hip,
+# WelchCall); "mode9" and "2in3out" exist for the transfer function only, "short_ld" for the device entries only.
+WELCH_REJECTED = ("hop0", "hop>W", "frames0", "average2", "mode9", "2in3out", "null_window", "null_output", "short_ld")
+
+
+def _welch_rejected_applies(entry, bad):
+    if bad in ("mode9", "2in3out"):
+        return entry.startswith("tf")
+    return bad != "short_ld" or entry.endswith("_dev")
+
+
+def _welch_rejected_case(entry, bad, W=256, n_ch=3):
+    """One refused estimate through one C-ABI entry point -> ["ERR<code>"] (or the launch names, were it accepted)."""
+    import ctypes as C
+    from dsptoolbox_amd._lib import DeviceBuffer, DevicePlanar, get_context
+    ctx = get_context()
+    kind, dev, f64 = entry.split("_")[0], entry.endswith("_dev"), entry.endswith("_f64")
+    n, B = 2 * W + 3000, W // 2 + 1
+    n_cx = 2 if bad == "2in3out" else n_ch
+    hop = {"hop0": 0, "hop>W": W + 1}.get(bad, W // 2)
+    n_frames = 0 if bad == "frames0" else -(-n // (W // 2))
+    average = 2 if bad == "average2" else backend.DS_AVG["mean"]
+    mode = 9 if bad == "mode9" else backend.DS_TF["H2"]
+    rng = np.random.default_rng(W)
+    x, y = rng.standard_normal((n, n_cx)), rng.standard_normal((n, n_ch))
+    w = (0.5 - 0.5 * np.cos(2 * np.pi * np.arange(W) / W)).astype(np.float32)
+    tail = (1, average) + ((mode,) if kind == "tf" else ()) + (0, 1.0 / W, 2.0, 1)
+    held = []  # device buffers, freed below
+    if dev:
+        dx, dy = (DevicePlanar.from_planar(ctx, np.ascontiguousarray(a.T, dtype=np.float32)) for a in (x, y))
+        dw, do = DeviceBuffer.from_array(ctx, w), DeviceBuffer(ctx, B * n_ch * 12)
+        held = [dx.owner, dy.owner, dw, do]
+        sx, sy = (C.c_void_p(dx.ptr), n_cx, n - 1 if bad == "short_ld" else dx.ld), (C.c_void_p(dy.ptr), n_ch, dy.ld)
+        pw, po, po2 = C.c_void_p(dw.ptr), C.c_void_p(do.ptr), C.c_void_p(do.ptr + B * n_ch * 8)
+    else:
+        p = lambda a: a.ctypes.data_as(C.c_void_p)
+        xa, ya = (np.ascontiguousarray(a if f64 else a.T, dtype=np.float64 if f64 else np.float32) for a in (x, y))
+        out, out2 = np.zeros((B, n_ch), np.complex64), np.zeros((B, n_ch), np.float32)
+        sx, sy, pw = (p(xa), n_cx), (p(ya), n_ch), p(w)
+        po, po2 = p(out.view(np.float32) if kind == "psd" else out), p(out2)
+    if bad == "null_window":
+        pw = None
+    if bad == "null_output":
+        po = None
+    mid = (n, W, hop, n_frames, pw)
+    ctx.routes()
+    if kind == "tf":
+        fn = ctx.lib.ds_welch_tf_dev if dev else (ctx.lib.ds_welch_tf_f64 if f64 else ctx.lib.ds_welch_tf)
+        routes = _route_call(ctx, fn, (*sx, *sy, *mid, *tail, po, po2))
+    elif kind == "psd":
+        fn = ctx.lib.ds_welch_psd_dev if dev else (ctx.lib.ds_welch_psd_f64 if f64 else ctx.lib.ds_welch_psd)
+        routes = _route_call(ctx, fn, (*sx, *mid, *tail, po))
+    else:
+        fn = ctx.lib.ds_welch_csd_f64 if f64 else ctx.lib.ds_welch_csd
+        routes = _route_call(ctx, fn, (sx[0], sy[0], n_ch, *mid, *tail, po))
+    for b in held:
+        b.free()
+    return routes
+
+
+def _welch_rejected_matrix():
+    """{key: ["ERR<code>"]} of every refused call of every Welch entry point."""
+    return {f"{entry}|{bad}": _welch_rejected_case(entry, bad)
+            for entries in WELCH_ROUTE_ENTRIES.values() for entry in entries
+            for bad in WELCH_REJECTED if _welch_rejected_applies(entry, bad)}
+
+
+@pytest.mark.gpu
+def test_welch_rejected_calls():
+    """Every Welch entry point refuses a spoilt call with the code it returned when the table was recorded."""
+    import json
+    with open(os.path.join(ROOT, "tests", "golden", "welch_rejected.json")) as fh:
+        table = json.load(fh)
+    seen = _welch_rejected_matrix()
+    assert seen == {k: v.split() for k, v in table.items()}
+
+
 # ---- which kernel family each STFT / iSTFT length runs on, per entry point (tests/golden/stft_routes.json) ----------
 # Keys "<switch>|stft|<nfft>|<window>|<detrend>|<channels>" and "<switch>|istft|<nfft>|<window>|<step divisor>|<channels>"
 # (window: "full" = nfft samples, "short" = 3 nfft / 4); the launch names were recorded through the same helpers on the
