@@ -2783,16 +2783,6 @@ extern "C" int ds_fir_ola_dev(ds_ctx* c, const float* x, int n_ch, int64_t ldx, 
     return fir_bank(c, f);
 }
 
-#if W4_TIMING
-// dev only (built with -DW4_TIMING=1): read and reset the per-phase cycle stamps
-extern "C" int ds_debug_welch_timing(unsigned long long out[16]) {
-    unsigned long long z[16] = {};
-    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(welch4096::w4_timing), sizeof(z)) != hipSuccess) return -1;
-    if (hipMemcpyToSymbol(HIP_SYMBOL(welch4096::w4_timing), z, sizeof(z)) != hipSuccess) return -1;
-    return 0;
-}
-#endif
-
 // ---- host-pointer entry points -------------------------------------------------
 // Each stages its arrays in ctx->io around the _dev entry.  The *_f64 entries take the reference's own float64 layouts
 // and cross the boundary through the pinned pipelines below; the others copy planar fp32 arrays as they are.

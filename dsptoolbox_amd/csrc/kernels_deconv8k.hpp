@@ -248,10 +248,9 @@ __global__ __launch_bounds__(256, 3) void k_deconv3(Args p) {
     fir4k::fill_tw2p(tw2p, p.twt, tid);
     float2 rf[16];
     gather(rf, 0);
-    w4::Stamp ts;
     auto none = [](int) {};
     __syncthreads();  // the tables
-    w4::fft4096_wi(v, tw, buf, tw2, tid, none, none, ts, 0);
+    w4::fft4096_wi(v, tw, buf, tw2, tid, none, none);
 #pragma unroll
     for (int s = 0; s < 16; ++s) v[s] = cmul(v[s], rf[s]);
     gather(rf, 1);  // in flight during the transform back
@@ -263,7 +262,7 @@ __global__ __launch_bounds__(256, 3) void k_deconv3(Args p) {
         v[n1] = b1[n1];
     }
     __syncthreads();  // the column reads of the transform back: the forward transform stores into the image at once
-    w4::fft4096_wi(v, tw, buf, tw2, tid, none, none, ts, 0);
+    w4::fft4096_wi(v, tw, buf, tw2, tid, none, none);
 #pragma unroll
     for (int s = 0; s < 16; ++s) v[s] = cmul(v[s], rf[s]);
     fir4k::ifft4096_wi(v, tw, buf, tw2p, tid, none, none);
@@ -339,10 +338,9 @@ __global__ __launch_bounds__(256, 4) void k_deconv3q(Args p) {
     float2* tw2p = lds + 16 * w4::L1S + 256;
     fir4k::fill_tw2p(tw2p, p.twt, tid);
     float2 rf[16];
-    w4::Stamp ts;
     auto none = [](int) {};
     __syncthreads();  // the tables
-    w4::fft4096_wi(v, tw, buf, tw2, tid, none, none, ts, 0);
+    w4::fft4096_wi(v, tw, buf, tw2, tid, none, none);
     gather(rf, 0);
 #pragma unroll
     for (int s = 0; s < 16; ++s) v[s] = cmul(v[s], rf[s]);
@@ -354,7 +352,7 @@ __global__ __launch_bounds__(256, 4) void k_deconv3q(Args p) {
         v[n1] = b1[n1];
     }
     __syncthreads();  // the column reads of the transform back: the forward transform stores into the image at once
-    w4::fft4096_wi(v, tw, buf, tw2, tid, none, none, ts, 0);
+    w4::fft4096_wi(v, tw, buf, tw2, tid, none, none);
     gather(rf, 1);
 #pragma unroll
     for (int s = 0; s < 16; ++s) v[s] = cmul(v[s], rf[s]);
@@ -462,7 +460,6 @@ __global__ __launch_bounds__(256, 2) void k_deconv_p(PArgs pp) {
         for (int s = 0; s < 16; ++s)
             rf[s] = __builtin_bit_cast(float2, __builtin_amdgcn_raw_buffer_load_b64(rr, ((q * 16 + s) * 256) * 8 + 8 * tid, 0, 0));
     };
-    w4::Stamp ts;
     auto none = [](int) {};
     __syncthreads();  // the tables
     for (; u < pp.n_units; u += gridDim.x) {
@@ -477,7 +474,7 @@ __global__ __launch_bounds__(256, 2) void k_deconv_p(PArgs pp) {
         request(u + (int)gridDim.x);  // the next unit's samples: in flight during this unit's transforms
         __builtin_amdgcn_sched_barrier(0);
         float2 rf[16];
-        w4::fft4096_wi(v, tw, buf, tw2, tid, none, none, ts, 0);
+        w4::fft4096_wi(v, tw, buf, tw2, tid, none, none);
         spectrum(rf, 0);
 #pragma unroll
         for (int s = 0; s < 16; ++s) v[s] = cmul(v[s], rf[s]);
@@ -489,7 +486,7 @@ __global__ __launch_bounds__(256, 2) void k_deconv_p(PArgs pp) {
             v[n1] = b1[n1];
         }
         __syncthreads();  // the column reads of the transform back: the forward transform stores into the image at once
-        w4::fft4096_wi(v, tw, buf, tw2, tid, none, none, ts, 0);
+        w4::fft4096_wi(v, tw, buf, tw2, tid, none, none);
         spectrum(rf, 1);
 #pragma unroll
         for (int s = 0; s < 16; ++s) v[s] = cmul(v[s], rf[s]);

@@ -31,9 +31,7 @@ namespace w4 = welch4096;
 constexpr int NBIG = 16384, M = 4096, NTB = 1024;
 constexpr int LDS_BYTES = (4 * w4::BUF_C + 256) * 8;  // four exchange buffers + W256 table: 149 504 B
 
-__device__ __forceinline__ float2 cmul(float2 a, float2 b) {
-    return make_float2(fmaf(a.x, b.x, -a.y * b.y), fmaf(a.x, b.y, a.y * b.x));
-}
+using w4::cmul;
 __device__ __forceinline__ float2 cmulc(float2 a, float2 b) {  // a * conj(b)
     return make_float2(fmaf(a.x, b.x, a.y * b.y), fmaf(a.y, b.x, -a.x * b.y));
 }

@@ -210,7 +210,6 @@ __global__ __launch_bounds__(NT) void k_icls(Args p) {
         // still counts as outstanding at the head of the loop costs a full wait there -- which the hidden stores join
         asm volatile("" ::"v"(ge.x), "v"(ge.y));
     };
-    Stamp ts;
     __syncthreads();  // tables
     place(decode(p0));
     for (int pi = p0; pi < p1; ++pi) {
@@ -232,7 +231,7 @@ __global__ __launch_bounds__(NT) void k_icls(Args p) {
         const Pass nx = decode(more ? pi + 1 : pi);
         fft4096_wi(
             v, tw, buf, tw2, tl, [&](int g) { request(nx, 2 * g, 2 * g + 2); },  // (behind the last pass: the same addresses again)
-            [&](int) {}, ts, 0);
+            [&](int) {});
         // (fft4096_wi ends with a barrier behind its last image read)
         place(nx);  // (unconditionally -- behind the last pass its own values once more: a request left unconsumed on one
                     // path makes the compiler wait for it, and with it for the hidden stores, at the head of the loop)

@@ -36,6 +36,7 @@ using dsk::RawPair;
 using dsk::StftArgs;
 using w4::cmul;
 using w4::pos16;
+using w4::wave_sync;
 
 // Geometry of the wave-level transform of N = 256, 512 or 1024 points: N = 16 x 16 x R3 on
 // L = N/16 lanes (1, 2 or 4 transforms per wave), 16 complex values per lane.
@@ -82,14 +83,6 @@ inline void host_tables(std::vector<float2>& t) {
         }
 }
 inline void host_tables(std::vector<float2>& t) { host_tables<1024>(t); }
-
-// order the LDS traffic of ONE wave (hardware executes it in program order; this keeps the
-// compiler from moving a read above the write of another lane it cannot see)
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 // synchronise the lanes of one transform: up to 64 lanes are (part of) one wave; a 128-lane team
 // (2048 points) spans two waves and takes the workgroup barrier -- every team of the workgroup then

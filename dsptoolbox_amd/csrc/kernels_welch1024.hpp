@@ -28,6 +28,7 @@ namespace welch1k {
 using stft1k::fft_wave;
 using stft1k::team_sync;
 using stft1k::wave_sync;
+using welchc::needs_drop;
 constexpr int NTB = 256;  // threads per workgroup
 template <int NN>
 struct WG {
@@ -141,10 +142,6 @@ __device__ __forceinline__ void window_pair(float2 (&v)[16], const Raw<HALF_HOP>
         v[n1] = make_float2(r.s[n1] * w, b * w);
     }
 }
-// the last pair of an odd frame count when frame F would still overlap the signal
-__device__ __forceinline__ bool needs_drop(const Args& p, int pr) {
-    return pr == p.n_pairs - 1 && (p.n_frames & 1) && (int64_t)p.n_frames * p.hop < p.n_samples;
-}
 
 // twiddle tables and the window into LDS (the window is read from there at every pair: 16
 // registers less per lane than keeping it)
@@ -214,12 +211,7 @@ __global__ __launch_bounds__(256) void k_px_sum(Args p) {
     constexpr int NB = WG<NN>::NB;
     const int q = blockIdx.x, cx = blockIdx.y;
     const int p0 = (int)((int64_t)q * p.n_pairs / p.n_chunks), p1 = (int)((int64_t)(q + 1) * p.n_pairs / p.n_chunks);
-    const float* __restrict__ px = p.px + (int64_t)cx * p.n_pairs * NB;
-    for (int k = threadIdx.x; k < NB; k += 256) {
-        double sum = 0.0;
-        for (int pr = p0; pr < p1; ++pr) sum += (double)px[(int64_t)pr * NB + k];
-        p.psx[((int64_t)q * p.n_cx + cx) * NB + k] = (float)sum;
-    }
+    welchc::px_sum<NB>(p, q, cx, p0, p1);
 }
 
 // ---- output channels: grid = n_chunks * ceil(n_ch / TPB) --------------------------

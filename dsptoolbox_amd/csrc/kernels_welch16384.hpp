@@ -30,6 +30,8 @@ namespace welch16k {
 
 namespace w4 = welch4096;
 using w4::cmul;
+using w4::needs_drop;
+using welchc::fold_index;
 using w4::pos16;
 constexpr int N = 16384, M = 4096, NB = N / 2 + 1, NTB = 256;
 constexpr int LDS_BYTES = (2 * w4::BUF_C + 256) * 8;  // two exchange buffers + W256 table: 76 800 B, two workgroups per CU
@@ -55,11 +57,6 @@ struct Args {
 // samples must be addressable with 32-bit byte offsets through the channel's buffer descriptor
 inline bool buf_fits(int64_t n_samples, int n_frames, int hop) {
     return n_samples < ((int64_t)1 << 29) && (int64_t)(n_frames + 2) * hop + N < ((int64_t)1 << 29);
-}
-
-// the last pair of an odd frame count when frame F would still overlap the signal
-__device__ __forceinline__ bool needs_drop(const Args& p, int pr) {
-    return pr == p.n_pairs - 1 && (p.n_frames & 1) && (int64_t)p.n_frames * p.hop < p.n_samples;
 }
 
 // Window, pack the two frames (a at sample a0, b at a0 + hop) and run the radix-4 front end of class
@@ -108,9 +105,6 @@ __device__ __forceinline__ void front(float2 (&v)[16], __amdgpu_buffer_rsrc_t rs
     }
 }
 
-// fold partner of bin 4 k' + q: class of the partner and its index
-__device__ __forceinline__ int fold_index(int q, int kp) { return q == 0 ? ((M - kp) & (M - 1)) : (M - 1 - kp); }
-
 // ---- input spectra: grid = (n_pairs, n_cx, 4) ---------------------------------------
 __global__ __launch_bounds__(NTB, 2) void k_x(Args p) {
     extern __shared__ __align__(16) float2 lds[];
@@ -149,15 +143,7 @@ __global__ __launch_bounds__(NTB, 2) void k_x(Args p) {
 // ---- input auto spectra per chunk: psx[q][cx][k] = sum over the chunk's pairs of the folded
 // |W|^2 (fp64), one thread per bin.  grid = (ceil(NB / 256), n_chunks, n_cx)
 __global__ __launch_bounds__(256) void k_px_sum(Args p) {
-    const int k = blockIdx.x * 256 + threadIdx.x, cq = blockIdx.y, cx = blockIdx.z;
-    if (k >= NB) return;
-    const int p0 = (int)((int64_t)cq * p.n_pairs / p.n_chunks), p1 = (int)((int64_t)(cq + 1) * p.n_pairs / p.n_chunks);
-    const float* __restrict__ pxu = p.pxu + (int64_t)cx * p.n_pairs * N;
-    const int q = k & 3, kp = (k >> 2) & (M - 1), qm = (4 - q) & 3;
-    const int ia = q * M + kp, ib = qm * M + fold_index(q, kp);
-    double sum = 0.0;
-    for (int pr = p0; pr < p1; ++pr) sum += (double)pxu[(int64_t)pr * N + ia] + (double)pxu[(int64_t)pr * N + ib];
-    p.psx[((int64_t)cq * p.n_cx + cx) * NB + k] = (float)(0.5 * sum);
+    welchc::px_sum_folded(p, 4, 2);
 }
 
 // ---- output channels: grid = (n_chunks * n_ch, 1, 4) -----------------------------------
@@ -221,12 +207,7 @@ __global__ __launch_bounds__(NTB, 2) void k_y(Args p) {
             }
             __builtin_amdgcn_sched_barrier(0);
         };
-#if W4_TIMING
-        unsigned long long ph[12] = {}, prev = 0;
-        w4::fft4096<true>(v, tw, buf, tw2, t, ph, prev, w4::NoHook(), issue_xs);
-#else
         w4::fft4096<true>(v, tw, buf, tw2, t, w4::NoHook(), issue_xs);
-#endif
 #pragma unroll
         for (int k3 = 0; k3 < 16; ++k3) {
             const float2 z = v[pos16(k3)];

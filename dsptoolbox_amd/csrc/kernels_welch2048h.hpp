@@ -23,6 +23,7 @@ namespace welch2048h {
 namespace w4 = welch4096;
 using w4::Args;
 using w4::cmul;
+using w4::fold_pos;
 using w4::L1S;
 using w4::L3S;
 using w4::NT;
@@ -146,9 +147,8 @@ __device__ __forceinline__ void fft2x2048_wi(float2 (&v)[16], const Tw7& tw, flo
         w4::NoHookI(), w4::NoHookI());
 }
 
-// position of this thread's bin k3 in the 2 x 2048 fold image (A at 0, B at 2048), and the padded LDS slot of a position
+// position of this thread's bin k3 in the 2 x 2048 fold image (A at 0, B at 2048); w4::fold_pos gives its padded LDS slot
 __device__ __forceinline__ int bin_base(int tid) { return ((tid >> 7) << 11) + ((tid >> 4) & 7) + 8 * (tid & 15); }
-__device__ __forceinline__ int fold_pos(int p) { return p + (p >> 4); }
 
 // zero the frames of pass `pr` that lie at or past n_frames (only a caller that asks for fewer frames than the signal
 // holds gets there: past the signal the buffer range check has delivered zeros already)
@@ -221,11 +221,7 @@ __global__ __launch_bounds__(256) void k_px_sum(Args p) {
     const int q = blockIdx.x, cx = blockIdx.y;
     int p0, p1;
     w4::chunk_range(p, q, p0, p1);
-    for (int k = threadIdx.x; k < NBW; k += 256) {
-        double sum = 0.0;
-        for (int pr = p0; pr < p1; ++pr) sum += (double)p.px[((int64_t)cx * p.n_pairs + pr) * NBW + k];
-        p.psx[((int64_t)q * p.n_cx + cx) * NBW + k] = (float)sum;
-    }
+    welchc::px_sum<NBW>(p, q, cx, p0, p1);
 }
 
 // ---- output channels: workgroup = (chunk of passes, channel) -------------------------------------------------------

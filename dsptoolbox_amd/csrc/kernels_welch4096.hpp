@@ -37,33 +37,9 @@
 #include <vector>
 
 #include "kernels_finish.hpp"
+#include "welch_common.hpp"
 
 namespace welch4096 {
-
-#ifndef W4_ABLATE
-#define W4_ABLATE 0  // timing-only diagnostics (wrong results): 1 no xs loads, 2 no sample loads, 4 no LDS
-#endif
-
-#ifndef W4_AB
-#define W4_AB 0  // timing-only ablations (wrong results), see kernels_welch4096w.hpp; 16: no internal W16 twiddles in dft16_h
-#endif
-
-#ifndef W4_TIMING
-#define W4_TIMING 0  // dev only: per-phase s_memtime stamps of wave 0 / workgroup 0 -> w4_timing[]
-#endif
-#if W4_TIMING
-__device__ unsigned long long w4_timing[16];
-#define W4_TS(i)                                                  \
-    do {                                                          \
-        __builtin_amdgcn_sched_barrier(0);                        \
-        unsigned long long t_ = __builtin_amdgcn_s_memtime();     \
-        __builtin_amdgcn_sched_barrier(0);                        \
-        if ((i) > 0) w4_ph[(i)-1] += t_ - w4_prev;                \
-        w4_prev = t_;                                             \
-    } while (0)
-#else
-#define W4_TS(i)
-#endif
 
 constexpr int N = 4096, NT = 256, NB = N / 2 + 1;
 constexpr int L1S = 272, L2S = 18;
@@ -71,9 +47,11 @@ constexpr int BUF_C = 256 * L2S;  // 4608 complex >= 16 * 272
 constexpr int LDS_BYTES = BUF_C * 8 + 256 * 8;        // one exchange buffer + W256 table
 constexpr int LDS_BYTES_2 = 2 * BUF_C * 8 + 256 * 8;  // two exchange buffers: 2 barriers per FFT
 
-__device__ __forceinline__ float2 cmul(float2 a, float2 b) {
-    return make_float2(fmaf(a.x, b.x, -a.y * b.y), fmaf(a.x, b.y, a.y * b.x));
-}
+using welchc::cmul;
+using welchc::fold_pos;
+using welchc::needs_drop;
+using welchc::pos16;
+using welchc::wave_sync;
 
 // in-place radix-4 butterfly on (a,b,c,d), forward
 __device__ __forceinline__ void r4(float2& a, float2& b, float2& c, float2& d) {
@@ -107,7 +85,6 @@ __device__ __forceinline__ void dft16(float2 (&v)[16]) {
 #pragma unroll
     for (int k1 = 0; k1 < 4; ++k1) r4(v[4 * k1], v[4 * k1 + 1], v[4 * k1 + 2], v[4 * k1 + 3]);
 }
-__device__ __forceinline__ constexpr int pos16(int k) { return 4 * (k & 3) + (k >> 2); }
 
 // dft16 with a call-out after each of its eight radix-4 butterflies: stage A (n0 = 0..3, its
 // three internal W16 twiddles folded in) then stage B (k1g = 0..3; afterwards v[4 k1g + j] holds
@@ -128,27 +105,21 @@ __device__ __forceinline__ void dft16_h(float2 (&v)[16], PA pre_a, HA after_a, H
     after_a(0);
     pre_a(std::integral_constant<int, 1>{});
     r4(v[1], v[5], v[9], v[13]);
-    if (!(W4_AB & 16)) {
     v[5] = mulw(v[5], C8, S8);                                                  // W16^1
     v[9] = make_float2((v[9].x + v[9].y) * R2, (v[9].y - v[9].x) * R2);         // W16^2
     v[13] = mulw(v[13], S8, C8);                                                // W16^3
-    }
     after_a(1);
     pre_a(std::integral_constant<int, 2>{});
     r4(v[2], v[6], v[10], v[14]);
-    if (!(W4_AB & 16)) {
     v[6] = make_float2((v[6].x + v[6].y) * R2, (v[6].y - v[6].x) * R2);         // W16^2
     v[10] = make_float2(v[10].y, -v[10].x);                                     // W16^4 = -i
     v[14] = make_float2((v[14].y - v[14].x) * R2, -(v[14].x + v[14].y) * R2);   // W16^6
-    }
     after_a(2);
     pre_a(std::integral_constant<int, 3>{});
     r4(v[3], v[7], v[11], v[15]);
-    if (!(W4_AB & 16)) {
     v[7] = mulw(v[7], S8, C8);                                                  // W16^3
     v[11] = make_float2((v[11].y - v[11].x) * R2, -(v[11].x + v[11].y) * R2);   // W16^6
     v[15] = mulw(v[15], -C8, -S8);                                              // W16^9
-    }
     after_a(3);
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
@@ -178,71 +149,48 @@ struct NoHook {
 // put there (issuing global loads) runs while the workgroup drains its LDS stores and waits.
 template <bool TWO_BUF, typename Hook = NoHook, typename Hook2 = NoHook>
 __device__ __forceinline__ void fft4096(float2 (&v)[16], const Tw& tw, float2* __restrict__ buf,
-                                        const float2* __restrict__ tw2, int tid
-#if W4_TIMING
-                                        , unsigned long long (&w4_ph)[12], unsigned long long& w4_prev
-#endif
-                                        , Hook behind_ex1 = Hook(), Hook2 behind_ex2 = Hook2()) {
+                                        const float2* __restrict__ tw2, int tid,
+                                        Hook behind_ex1 = Hook(), Hook2 behind_ex2 = Hook2()) {
     float2* __restrict__ bufB = TWO_BUF ? buf + BUF_C : buf;
     dft16(v);
 #pragma unroll
     for (int k1 = 1; k1 < 16; ++k1) v[pos16(k1)] = cmul(v[pos16(k1)], tw.w[k1 - 1]);
-    W4_TS(2);
     const int k1u = tid >> 4, n3 = tid & 15;
-    if (!(W4_ABLATE & 4)) {
-        if (!TWO_BUF) __syncthreads();  // previous readers of buf are done
+    if (!TWO_BUF) __syncthreads();  // previous readers of buf are done
 #pragma unroll
-        for (int k1 = 0; k1 < 16; ++k1) buf[k1 * L1S + tid] = v[pos16(k1)];
-    }
+    for (int k1 = 0; k1 < 16; ++k1) buf[k1 * L1S + tid] = v[pos16(k1)];
     // the pass-2 twiddles do not depend on the exchange: fetch them (into the registers the
     // stored values just left) before the barrier, so their latency hides behind it
     float2 w2[15];
 #pragma unroll
     for (int k2 = 1; k2 < 16; ++k2) w2[k2 - 1] = tw2[k2 * 16 + n3];
     behind_ex1();
-    if (!(W4_ABLATE & 4)) {
-        W4_TS(3);
-        __syncthreads();
-        W4_TS(4);
+    __syncthreads();
 #pragma unroll
-        for (int n2 = 0; n2 < 16; ++n2) v[n2] = buf[k1u * L1S + 16 * n2 + n3];
-    }
-    W4_TS(5);
+    for (int n2 = 0; n2 < 16; ++n2) v[n2] = buf[k1u * L1S + 16 * n2 + n3];
     dft16(v);
 #pragma unroll
     for (int k2 = 1; k2 < 16; ++k2) v[pos16(k2)] = cmul(v[pos16(k2)], w2[k2 - 1]);
-    W4_TS(6);
-    if (!(W4_ABLATE & 4)) {
-        if (!TWO_BUF) __syncthreads();  // all pass-2 reads done
+    if (!TWO_BUF) __syncthreads();  // all pass-2 reads done
 #pragma unroll
-        for (int k2 = 0; k2 < 16; ++k2) bufB[(16 * k2 + k1u) * L2S + n3] = v[pos16(k2)];
-        behind_ex2();
-        W4_TS(7);
-        __syncthreads();
-        W4_TS(8);
-        const float4* row = reinterpret_cast<const float4*>(bufB + tid * L2S);
+    for (int k2 = 0; k2 < 16; ++k2) bufB[(16 * k2 + k1u) * L2S + n3] = v[pos16(k2)];
+    behind_ex2();
+    __syncthreads();
+    const float4* row = reinterpret_cast<const float4*>(bufB + tid * L2S);
 #pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            float4 r = row[j];
-            v[2 * j] = make_float2(r.x, r.y);
-            v[2 * j + 1] = make_float2(r.z, r.w);
-        }
+    for (int j = 0; j < 8; ++j) {
+        float4 r = row[j];
+        v[2 * j] = make_float2(r.x, r.y);
+        v[2 * j + 1] = make_float2(r.z, r.w);
     }
-    W4_TS(9);
     dft16(v);
-    W4_TS(10);
 }
 
-// the transform without the dev-only phase stamps (other kernels built on it)
+// the transform without call-outs (the name the other kernel families use)
 template <bool TWO_BUF>
 __device__ __forceinline__ void fft4096_plain(float2 (&v)[16], const Tw& tw, float2* __restrict__ buf,
                                               const float2* __restrict__ tw2, int tid) {
-#if W4_TIMING
-    unsigned long long ph[12] = {}, prev = 0;
-    fft4096<TWO_BUF>(v, tw, buf, tw2, tid, ph, prev);
-#else
     fft4096<TWO_BUF>(v, tw, buf, tw2, tid);
-#endif
 }
 
 struct Args {
@@ -363,10 +311,6 @@ __device__ __forceinline__ void window_pair(float2 (&v)[16], const Raw<HALF_HOP>
     }
 }
 
-// the last pair of an odd frame count when frame F would still overlap the signal
-__device__ __forceinline__ bool needs_drop(const Args& p, int pr) {
-    return pr == p.n_pairs - 1 && (p.n_frames & 1) && (int64_t)p.n_frames * p.hop < p.n_samples;
-}
 __device__ __forceinline__ void drop_second(float2 (&v)[16]) {
 #pragma unroll
     for (int n1 = 0; n1 < 16; ++n1) v[n1].y = 0.f;
@@ -480,12 +424,8 @@ __global__ __launch_bounds__(NT, 2) void k_y(Args p) {
         // and the input spectrum of pair pr are in flight while pair pr is transformed
         Raw<HALF_HOP> raw;
         if (p0 < p1) load_raw<HALF_HOP>(raw, ch, p.n_samples, (int64_t)(2 * p0) * p.hop, p.hop, tid);
-#if W4_TIMING
-        unsigned long long w4_ph[12] = {}, w4_prev = 0;
-#endif
         for (int pr = p0; pr < p1; ++pr) {
             float2 v[16];
-            W4_TS(0);
             window_pair<HALF_HOP>(v, raw, win);
             if (needs_drop(p, pr)) drop_second(v);
             float2 xw[16];
@@ -495,34 +435,24 @@ __global__ __launch_bounds__(NT, 2) void k_y(Args p) {
             // first butterfly.  (They are consumed thousands of cycles later.)
             auto issue_loads = [&]() {
                 __builtin_amdgcn_sched_barrier(0);
-                if (!(W4_ABLATE & 2) && pr + 1 < p1)
+                if (pr + 1 < p1)
                     load_raw<HALF_HOP>(raw, ch, p.n_samples, (int64_t)(2 * pr + 2) * p.hop, p.hop, tid);
                 __builtin_amdgcn_sched_barrier(0);
             };
             auto issue_xs = [&]() {
                 if (AUTO) return;
                 __builtin_amdgcn_sched_barrier(0);
-                if (W4_ABLATE & 1) {
+                const float4* __restrict__ xp =
+                    reinterpret_cast<const float4*>(p.xs + ((int64_t)(p.n_cx > 1 ? c : 0) * p.n_pairs + pr) * N) + tid;
 #pragma unroll
-                    for (int k3 = 0; k3 < 16; ++k3) xw[k3] = tw.w[k3 % 15];
-                } else {
-                    const float4* __restrict__ xp =
-                        reinterpret_cast<const float4*>(p.xs + ((int64_t)(p.n_cx > 1 ? c : 0) * p.n_pairs + pr) * N) + tid;
-#pragma unroll
-                    for (int g = 0; g < 8; ++g) {
-                        float4 q = xp[256 * g];
-                        xw[2 * g] = make_float2(q.x, q.y);
-                        xw[2 * g + 1] = make_float2(q.z, q.w);
-                    }
+                for (int g = 0; g < 8; ++g) {
+                    float4 q = xp[256 * g];
+                    xw[2 * g] = make_float2(q.x, q.y);
+                    xw[2 * g + 1] = make_float2(q.z, q.w);
                 }
                 __builtin_amdgcn_sched_barrier(0);
             };
-            W4_TS(1);
-#if W4_TIMING
-            fft4096<TWO_BUF>(v, tw, buf, tw2, tid, w4_ph, w4_prev, issue_loads, issue_xs);
-#else
             fft4096<TWO_BUF>(v, tw, buf, tw2, tid, issue_loads, issue_xs);
-#endif
 #pragma unroll
             for (int k3 = 0; k3 < 16; ++k3) {
                 float2 z = v[pos16(k3)];
@@ -533,14 +463,7 @@ __global__ __launch_bounds__(NT, 2) void k_y(Args p) {
                 }
                 P[k3] = fmaf(z.x, z.x, fmaf(z.y, z.y, P[k3]));
             }
-            W4_TS(11);
         }
-#if W4_TIMING
-        if (blockIdx.x == 0 && tid == 0) {
-            for (int i = 0; i < 11; ++i) atomicAdd(&w4_timing[i], w4_ph[i]);
-            atomicAdd(&w4_timing[15], (unsigned long long)(p1 - p0));
-        }
-#endif
     }
     if (p.detrend && tid == 0) P[0] = 0.f;  // xs bin 0 is already 0 -> T[0] = 0
     // fold k <-> N-k once per chunk, through LDS

@@ -11,10 +11,17 @@
 //   * ONE exchange buffer (34 KB) + the window in LDS (16 KB) + W256 table = 52 KB -> three
 //     workgroups per CU; two workgroup barriers per transform, back to back around the pass-1
 //     image stores, so the waves of a workgroup meet once per transform.
-//   * <= 168 VGPRs: window values come from LDS, the W4096 twiddles are rebuilt from six base
+//     Why three: the pair loop is bound by instruction issue, and a third resident workgroup fills
+//     the slots two leave idle (0.84 x the time of k_y; the same loop built for two per CU with
+//     window and all fifteen twiddles in registers, 203 VGPRs, reaches 0.92 x).  Four per CU
+//     (window by L1-resident buffer loads, 36 KB of LDS) measured no faster in steady state, and the
+//     cross loop spills at the 128 registers it allows (profiles/r04_welch_four_per_cu.txt).
+//   * <= 168 VGPRs, the budget of three per CU, is what puts the window in LDS and the twiddles on
+//     six bases: the window values are read from LDS at the end of an iteration, into registers the
+//     accumulation has just freed, for the next one; the W4096 twiddles are rebuilt from six base
 //     values (W^t, W^2t, W^3t, W^4t, W^8t, W^12t: one extra complex product for nine of the
-//     fifteen), and with hop = N/2 the last half block of a pair is the first of the next, so
-//     only 16 new samples per thread and pair are loaded (8 carried in registers).
+//     fifteen, 12 registers instead of 30); and with hop = N/2 the last half block of a pair is the
+//     first of the next, so only 16 new samples per thread and pair are loaded (8 carried in registers).
 //   * thread tid ends with bins bt + 256 k3, bt = 16 (tid & 15) + (tid >> 4); k_x3 stores the
 //     input spectra thread-major in exactly that mapping.
 //   * k_x3 and k_y3 run fft4096_wr, which does that second exchange with DPP row rotations instead
@@ -27,91 +34,24 @@
 
 namespace welch4096 {
 
-// dev only (-DW4_TIMING=1): per-phase s_memtime stamps of workgroup 0 / lane 0 -> w3_timing[]
-#if W4_TIMING
-__device__ unsigned long long w3_timing[16];
-__device__ unsigned long long w3_life[4096][8];  // per workgroup: memtime start/end, memrealtime start/end, loop start/end, HW_ID, XCC_ID
-struct Stamp {
-    unsigned long long ph[12] = {}, prev = 0;
-    __device__ __forceinline__ void operator()(int i) {
-        __builtin_amdgcn_sched_barrier(0);
-        unsigned long long t;
-        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-        __builtin_amdgcn_sched_barrier(0);
-        if (i > 0) ph[i - 1] += t - prev;
-        prev = t;
-    }
-};
-#else
-struct Stamp {
-    __device__ __forceinline__ void operator()(int) {}
-};
-#endif
-
 constexpr int L3S = 17;                                       // transposed row stride (complex)
 constexpr int LDS3_BYTES = 16 * L1S * 8 + 256 * 8 + N * 4;    // exchange + W256 + window = 53248
 
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-#ifndef W4_OCC
-#define W4_OCC 3  // workgroups per CU the kernel is built for (2: twiddles and window in registers)
-#endif
-#ifndef W4_WIN_ROT
-#define W4_WIN_ROT 1
-#endif
-#ifndef W4_TW6
-#define W4_TW6 (W4_OCC == 3)
-#endif
-#ifndef W4_NO_READ2
-#define W4_NO_READ2 1
-#endif
-#ifndef W4_TW2_REG
-#define W4_TW2_REG 0  // experiment (round 5): the W256 twiddles of pass 2 rebuilt from six per-thread values instead of 15 LDS reads
-#endif
-#ifndef W4_WIN_GLOBAL
-#define W4_WIN_GLOBAL 0  // experiment (tools/exp): window values by buffer loads (L1-resident 16 KB) instead of the LDS copy
-#endif
-constexpr int LDS3G_BYTES = 16 * L1S * 8 + 256 * 8;  // ... which leaves exchange + W256 = 36864 bytes: four workgroups per CU
-
+// W4096^(t k1) for k1 = 1..15 from six values: k1 = lo + 4 hi takes a[lo - 1] times b[hi - 1]
 struct Tw6 {
-#if W4_TW6
     float2 a[3];  // W4096^(t k1), k1 = 1, 2, 3
     float2 b[3];  // W4096^(t k1), k1 = 4, 8, 12
-#else
-    float2 w[15];
-#endif
-#if W4_TW2_REG
-    float2 c[3];  // W256^(n3 k2), k2 = 1, 2, 3
-    float2 d[3];  // W256^(n3 k2), k2 = 4, 8, 12
-#endif
 };
 
 __device__ __forceinline__ void load_tw6(Tw6& tw, const float2* __restrict__ twt, int tid) {
-#if W4_TW6
 #pragma unroll
     for (int j = 0; j < 3; ++j) {
         tw.a[j] = twt[j * 256 + tid];
         tw.b[j] = twt[(4 * (j + 1) - 1) * 256 + tid];
     }
-#else
-#pragma unroll
-    for (int k1 = 1; k1 < 16; ++k1) tw.w[k1 - 1] = twt[(k1 - 1) * 256 + tid];
-#endif
-#if W4_TW2_REG
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        tw.c[j] = twt[15 * 256 + (j + 1) * 16 + (tid & 15)];        // tw2[k2 * 16 + n3]
-        tw.d[j] = twt[15 * 256 + 4 * (j + 1) * 16 + (tid & 15)];
-    }
-#endif
 }
 
 __device__ __forceinline__ void apply_tw6(float2 (&v)[16], const Tw6& tw) {
-#if W4_TW6
 #pragma unroll
     for (int k1 = 1; k1 < 16; ++k1) {
         const int lo = k1 & 3, hi = k1 >> 2;
@@ -120,10 +60,6 @@ __device__ __forceinline__ void apply_tw6(float2 (&v)[16], const Tw6& tw) {
         if (hi) z = cmul(z, tw.b[hi - 1]);
         v[pos16(k1)] = z;
     }
-#else
-#pragma unroll
-    for (int k1 = 1; k1 < 16; ++k1) v[pos16(k1)] = cmul(v[pos16(k1)], tw.w[k1 - 1]);
-#endif
 }
 
 // One channel as a raw buffer: the hardware range check returns 0 for every sample at or past
@@ -168,8 +104,6 @@ __device__ __forceinline__ void static_for(F&& f) {
 
 // bins held by thread tid after fft4096_w: bt + 256 k3 (v[pos16(k3)])
 __device__ __forceinline__ int bin_thread(int tid) { return ((tid & 15) << 4) | (tid >> 4); }
-// padded position of bin k in the fold image (stride-16 bins of neighbouring lanes -> 17)
-__device__ __forceinline__ int fold_pos(int k) { return k + (k >> 4); }
 
 // v[n1] = z[tid + 256 n1]  ->  Z[bt + 256 k3] in v[pos16(k3)].  `buf`: the workgroup's ONE exchange
 // image (16 rows of L1S complex).  Two workgroup barriers, both around the pass-1 stores.
@@ -211,22 +145,7 @@ __device__ __forceinline__ void fft4096_w(float2 (&v)[16], const Tw6& tw, float2
 // workgroup's priority falls as its own work gets done (16 levels: 4 hardware levels, dithered
 // over consecutive iterations), so whoever is behind wins the arbitration and the three
 // finish together.  One update per iteration (the immediate operand costs a scalar branch chain).
-#ifndef W4_PRIO
-#define W4_PRIO 1
-#endif
-#ifndef W4_XS_EARLY
-#define W4_XS_EARLY 0
-#endif
-#ifndef W4_AB
-#define W4_AB 0  // timing-only ablations (wrong results): 1 no xs loads, 2 no sample loads, 4 no LDS traffic, 8 no barriers,
-                 // 16 no internal W16 twiddles, 32 no window (no LDS window reads), 64 single twiddle products (no rebuild)
-#endif
-#define W4_SYNC()                          \
-    do {                                   \
-        if (!(W4_AB & 8)) __syncthreads(); \
-    } while (0)
 __device__ __forceinline__ void set_prio(int level16, int dither) {
-#if W4_PRIO
     const int pr = min(3, (level16 + dither) >> 2);
     if (pr == 0)
         __builtin_amdgcn_s_setprio(0);
@@ -236,7 +155,6 @@ __device__ __forceinline__ void set_prio(int level16, int dither) {
         __builtin_amdgcn_s_setprio(2);
     else
         __builtin_amdgcn_s_setprio(3);
-#endif
 }
 
 // fft4096_w with the exchange traffic spread between the butterflies.
@@ -250,11 +168,12 @@ __device__ __forceinline__ void set_prio(int level16, int dither) {
 // transform's last LDS read, so the next transform's pass-1 stores can start while its own
 // butterflies are still running.
 //   mid():            called by every wave right behind the mid-transform barrier (before the first
-//                      ld_b): the fused kernel waits there, once, for its chunk's input spectra
+//                      ld_b): the one-launch kernel (tools/exp/kernels_welch4096f.hpp) waits there,
+//                      once, for its chunk's input spectra
 template <typename LA, typename LB, typename MID = NoHook>
 __device__ __forceinline__ void fft4096_wi(float2 (&v)[16], const Tw6& tw, float2* __restrict__ buf,
                                            const float2* __restrict__ tw2, int tid, LA ld_a, LB ld_b,
-                                           Stamp& ts, int level16, MID mid = MID()) {
+                                           MID mid = MID()) {
     const int k1u = tid >> 4, n3 = tid & 15;
     float2* __restrict__ col = buf + tid;
     dft16_h(
@@ -269,36 +188,23 @@ __device__ __forceinline__ void fft4096_wi(float2 (&v)[16], const Tw6& tw, float
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             float2 z = v[4 * g + j];
-#if W4_TW6
             if (g) z = cmul(z, tw.a[g - 1]);
-            if (j && !((W4_AB & 64) && g)) z = cmul(z, tw.b[j - 1]);
-#else
-            if (g + 4 * j) z = cmul(z, tw.w[g + 4 * j - 1]);
-#endif
+            if (j) z = cmul(z, tw.b[j - 1]);
             W4_PIN();
-            if (W4_AB & 4)
-                asm volatile("" ::"v"(z.x), "v"(z.y));
-            else
-                col[(g + 4 * j) * L1S] = z;
+            col[(g + 4 * j) * L1S] = z;
             W4_PIN();
         }
     });
-    ts(2);
-    W4_SYNC();
+    __syncthreads();
     mid();
-    ts(3);
     float2* __restrict__ row = buf + k1u * L1S;
     const uint32_t a_row = lds_addr(row + n3), a_tw2 = lds_addr(tw2 + n3);
     // pass-2 inputs v[n2] = row[16 n2 + n3], requested in the order the butterflies consume them
     W4_PIN();
     static_for<16>([&](auto ic) {
         constexpr int i = decltype(ic)::value, n2 = 4 * (i & 3) + (i >> 2);
-        if (W4_AB & 4)
-            asm volatile("" : "=v"(v[n2].x), "=v"(v[n2].y));
-        else
-            lds_rd64<16 * n2 * 8>(v[n2], a_row);
+        lds_rd64<16 * n2 * 8>(v[n2], a_row);
     });
-    ts(4);
     float2 w2[16];
     dft16_h(
         v,
@@ -306,15 +212,10 @@ __device__ __forceinline__ void fft4096_wi(float2 (&v)[16], const Tw6& tw, float
             // 16 reads issued, then 3 + 4 + 4 table reads behind the first three butterflies:
             // butterfly g needs the first 4 (g + 1) of the 16
             constexpr int g = decltype(gc)::value;
-#if W4_TW2_REG
-            lgkm_wait<12 - 4 * g>();
-#else
             lgkm_wait<(g == 0 ? 12 : 11)>();
-#endif
         },
         [&](int g) {
             W4_PIN();
-#if !W4_TW2_REG
             static_for<4>([&](auto jc) {
                 constexpr int j = decltype(jc)::value;
                 // (the compiler folds g; the offset must be a constant for the asm operand)
@@ -323,14 +224,7 @@ __device__ __forceinline__ void fft4096_wi(float2 (&v)[16], const Tw6& tw, float
                 if (g == 2) lds_rd64<(8 + j) * 16 * 8>(w2[8 + j], a_tw2);
                 if (g == 3) lds_rd64<(12 + j) * 16 * 8>(w2[12 + j], a_tw2);
             });
-#endif
-#if W4_XS_EARLY
-            ld_b(g);
-#endif
-            if (g == 3) {
-                lgkm_wait<0>();  // every table value is in before stage B multiplies
-                ts(5);
-            }
+            if (g == 3) lgkm_wait<0>();  // every table value is in before stage B multiplies
             W4_PIN();
         },
         [&](int g) {
@@ -338,47 +232,28 @@ __device__ __forceinline__ void fft4096_wi(float2 (&v)[16], const Tw6& tw, float
             for (int j = 0; j < 4; ++j) {
                 const int k2 = g + 4 * j;
                 float2 z = v[4 * g + j];
-#if W4_TW2_REG
-                if (g) z = cmul(z, tw.c[g - 1]);
-                if (j) z = cmul(z, tw.d[j - 1]);
-#else
                 if (k2) z = cmul(z, w2[k2]);
-#endif
                 W4_PIN();
-                if (W4_AB & 4)
-                    asm volatile("" ::"v"(z.x), "v"(z.y));
-                else
-                    row[n3 * L3S + k2] = z;
+                row[n3 * L3S + k2] = z;
                 W4_PIN();
             }
-#if !W4_XS_EARLY
             W4_PIN();
             ld_b(g);
             W4_PIN();
-#endif
         });
-    ts(6);
     wave_sync();
     W4_PIN();
     static_for<16>([&](auto ic) {  // lane now plays k2 = n3
         constexpr int i = decltype(ic)::value, j = 4 * (i & 3) + (i >> 2);
-        if (W4_AB & 4)
-            asm volatile("" : "=v"(v[j].x), "=v"(v[j].y));
-        else
-            lds_rd64<j * L3S * 8>(v[j], a_row);
+        lds_rd64<j * L3S * 8>(v[j], a_row);
     });
-    ts(7);
     dft16_h(
         v,
         [&](auto gc) {
             constexpr int g = decltype(gc)::value;
             lgkm_wait<12 - 4 * g>();
             // all reads of the image are back: the next transform's pass-1 stores may begin
-            if (g == 3) {
-                ts(8);
-                W4_SYNC();
-                ts(9);
-            }
+            if (g == 3) __syncthreads();
         },
         NoHookI(), NoHookI());
 }
@@ -448,7 +323,7 @@ __device__ __forceinline__ void fft4096_wr(float2 (&v)[16], const Tw6R& tw, floa
                 W4_PIN();
             }
         });
-    W4_SYNC();
+    __syncthreads();
     const uint32_t a_row = lds_addr(buf + k1u * L1S + n3), a_tw2 = lds_addr(tw2r + n3);
     W4_PIN();
     static_for<16>([&](auto ic) {  // pass-2 inputs v[n2] = row[16 n2 + n3], in the order the butterflies use them
@@ -473,7 +348,7 @@ __device__ __forceinline__ void fft4096_wr(float2 (&v)[16], const Tw6R& tw, floa
             });
             if (g == 3) {
                 lgkm_wait<0>();  // image and table reads are in: the pass-1 image is free for the next transform
-                W4_SYNC();
+                __syncthreads();
             }
             W4_PIN();
         },
@@ -564,16 +439,12 @@ __global__ __launch_bounds__(256) void k_px_sum(Args p) {
     const int q = blockIdx.x, cx = blockIdx.y;
     int p0, p1;
     chunk_range(p, q, p0, p1);
-    for (int k = threadIdx.x; k < NB; k += 256) {
-        double sum = 0.0;
-        for (int pr = p0; pr < p1; ++pr) sum += (double)p.px[((int64_t)cx * p.n_pairs + pr) * NB + k];
-        p.psx[((int64_t)q * p.n_cx + cx) * NB + k] = (float)sum;
-    }
+    welchc::px_sum<NB>(p, q, cx, p0, p1);
 }
 
 // ---- output channels ---------------------------------------------------------
 template <bool AUTO = false>
-__global__ __launch_bounds__(NT, W4_OCC) void k_y3(Args p) {
+__global__ __launch_bounds__(NT, 3) void k_y3(Args p) {
     extern __shared__ __align__(16) float2 lds[];
     float2* buf = lds;
     float2* tw2 = lds + 16 * L1S;
@@ -589,23 +460,11 @@ __global__ __launch_bounds__(NT, W4_OCC) void k_y3(Args p) {
         q = u / p.n_ch;
         c = u - q * p.n_ch;
     }
-#if W4_TIMING
-    const unsigned long long life_t0 = __builtin_amdgcn_s_memtime(), life_r0 = __builtin_amdgcn_s_memrealtime();
-#endif
     Tw6R tw;
     load_tw6r(tw, p.twt, tid);
     tw2[tid] = p.twt[TW2R + tid];
-#if W4_WIN_GLOBAL
-    const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.window), 0, N * 4, 0x00020000);
-    (void)winl;
-#elif W4_OCC == 3
 #pragma unroll
     for (int n1 = 0; n1 < 16; ++n1) winl[tid + 256 * n1] = p.window[tid + 256 * n1];
-#else
-    float winr[16];
-#pragma unroll
-    for (int n1 = 0; n1 < 16; ++n1) winr[n1] = p.window[tid + 256 * n1];
-#endif
     const float* ch = p.sig + (int64_t)c * p.ld;
     int p0, p1;
     chunk_range(p, q, p0, p1);
@@ -658,40 +517,24 @@ __global__ __launch_bounds__(NT, W4_OCC) void k_y3(Args p) {
 #pragma unroll
         for (int j = 0; j < 16; ++j) nx[j] = ld_sample(rs, off0 + 1024 * (8 + j));
     }
-    Stamp ts;
-#if W4_TIMING
-    const unsigned long long life_r1 = __builtin_amdgcn_s_memrealtime();
-#endif
-#if W4_WIN_GLOBAL
-    float winr[16];
-#pragma unroll
-    for (int n1 = 0; n1 < 16; ++n1) winr[n1] = ld_sample(wrs, 4 * (tid + 256 * n1));
-#elif W4_OCC == 3 && W4_WIN_ROT
     // the window values of an iteration are requested from LDS at the end of the previous one (into
     // registers the accumulation has just freed) instead of in front of their first use
     float winr[16];
 #pragma unroll
     for (int n1 = 0; n1 < 16; ++n1) winr[n1] = winl[tid + 256 * n1];
-#endif
     for (int pr = p0; pr < p1; ++pr) {
         float2 v[16];
-        ts(0);
         const int level16 = ((p1 - pr - 1) * 16) / (p1 - p0);  // 15 ... 0 as the chunk gets done
         set_prio(level16, (pr * 5) & 3);
 #pragma unroll
         for (int n1 = 0; n1 < 16; ++n1) {
-#if W4_OCC == 3 && !W4_WIN_ROT && !W4_WIN_GLOBAL
-            const float w = winl[tid + 256 * n1];
-#else
             const float w = winr[n1];
-#endif
             const float a = n1 < 8 ? carry[n1] : nx[n1 - 8];
-            v[n1] = (W4_AB & 32) ? make_float2(a, nx[n1]) : make_float2(a * w, nx[n1] * w);
+            v[n1] = make_float2(a * w, nx[n1] * w);
         }
 #pragma unroll
         for (int j = 0; j < 8; ++j) carry[j] = nx[8 + j];
         if (needs_drop(p, pr)) drop_second(v);
-        ts(1);
         float2 xw[16];
         const int off1 = 4 * ((2 * pr + 2) * 2048 + tid) + 1024 * 8;
         const int xoff = (pr - p0) * (N * 8) + tid * 16;  // bytes into this chunk's input spectra
@@ -700,33 +543,19 @@ __global__ __launch_bounds__(NT, W4_OCC) void k_y3(Args p) {
             [&](int g) {  // samples of the next pair, four per call-out (past the chunk's last pair
                           // they are simply not used; past the signal the range check gives 0)
 #pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    if (W4_AB & 2)
-                        asm volatile("" : "=v"(nx[4 * g + j]));
-                    else
-                        nx[4 * g + j] = ld_sample(rs, off1 + 1024 * (4 * g + j));
-                }
+                for (int j = 0; j < 4; ++j) nx[4 * g + j] = ld_sample(rs, off1 + 1024 * (4 * g + j));
             },
             [&](int g) {  // input spectrum of this pair, two 16-byte loads per call-out
-#if W4_WIN_GLOBAL
-                // the next pair's window values (their registers are free since the windowing above)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) winr[4 * g + j] = ld_sample(wrs, 4 * (tid + 256 * (4 * g + j)));
-#endif
                 if (!AUTO) {
 #pragma unroll
                     for (int j = 0; j < 2; ++j) {
-                        float4 q4;
-                        if (W4_AB & 1)
-                            asm volatile("" : "=v"(q4.x), "=v"(q4.y), "=v"(q4.z), "=v"(q4.w));
-                        else
-                            q4 = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(xrs, xoff + 4096 * (2 * g + j), 0, 0));
+                        const float4 q4 =
+                            __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(xrs, xoff + 4096 * (2 * g + j), 0, 0));
                         xw[2 * (2 * g + j)] = make_float2(q4.x, q4.y);
                         xw[2 * (2 * g + j) + 1] = make_float2(q4.z, q4.w);
                     }
                 }
             });
-        ts(10);
 #pragma unroll
         for (int k3 = 0; k3 < 16; ++k3) {
             float2 z = v[posr16(k3)];
@@ -737,22 +566,11 @@ __global__ __launch_bounds__(NT, W4_OCC) void k_y3(Args p) {
             }
             P[k3] = fmaf(z.x, z.x, fmaf(z.y, z.y, P[k3]));
         }
-#if W4_OCC == 3 && W4_WIN_ROT && !W4_WIN_GLOBAL
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-        for (int n1 = 0; n1 < 16; ++n1)
-            if (!(W4_AB & 32)) winr[n1] = winl[tid + 256 * n1];
+        for (int n1 = 0; n1 < 16; ++n1) winr[n1] = winl[tid + 256 * n1];
         __builtin_amdgcn_sched_barrier(0);
-#endif
-        ts(11);
     }
-#if W4_TIMING
-    const unsigned long long life_r2 = __builtin_amdgcn_s_memrealtime();
-    if (blockIdx.x == 0 && tid == 0) {
-        for (int i = 0; i < 11; ++i) atomicAdd(&w3_timing[i], ts.ph[i]);
-        atomicAdd(&w3_timing[15], (unsigned long long)(p1 - p0));
-    }
-#endif
     if (p.detrend && tid == 0) P[0] = 0.f;
     // fold k <-> N-k once per chunk, through LDS (padded image: 4096 + 256 = 16 x 272)
     const int bt = bin_thread(tid);
@@ -773,18 +591,6 @@ __global__ __launch_bounds__(NT, W4_OCC) void k_y3(Args p) {
     for (int k3 = 0; k3 < 16; ++k3) pw[fold_pos(bt + 256 * k3)] = P[k3];
     __syncthreads();
     for (int k = tid; k < NB; k += NT) p.pyy[so + k] = 0.5f * (pw[fold_pos(k)] + pw[fold_pos((N - k) & (N - 1))]);
-#if W4_TIMING
-    if (tid == 0 && blockIdx.x < 4096) {
-        w3_life[blockIdx.x][0] = life_t0;
-        w3_life[blockIdx.x][1] = __builtin_amdgcn_s_memtime();
-        w3_life[blockIdx.x][2] = life_r0;
-        w3_life[blockIdx.x][3] = __builtin_amdgcn_s_memrealtime();
-        w3_life[blockIdx.x][4] = life_r1;
-        w3_life[blockIdx.x][5] = life_r2;
-        w3_life[blockIdx.x][6] = __builtin_amdgcn_s_getreg((4) | (0 << 6) | (31 << 11));   // HW_REG_HW_ID
-        w3_life[blockIdx.x][7] = __builtin_amdgcn_s_getreg((20) | (0 << 6) | (31 << 11));  // HW_REG_XCC_ID
-    }
-#endif
 }
 
 // ---- host side -----------------------------------------------------------------

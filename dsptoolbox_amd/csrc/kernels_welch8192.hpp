@@ -22,6 +22,8 @@ namespace welch8k {
 
 namespace w4 = welch4096;
 using w4::cmul;
+using w4::needs_drop;
+using welchc::fold_index;
 using w4::pos16;
 constexpr int N = 8192, M = 4096, NB = N / 2 + 1, NTB = 512;
 constexpr int LDS_BYTES = (4 * w4::BUF_C + 256) * 8;  // 149 504 B
@@ -123,14 +125,8 @@ __device__ __forceinline__ void front(float2 (&v)[16], const Raw<HALF_HOP>& r, c
     }
 }
 
-// the last pair of an odd frame count when frame F would still overlap the signal
-__device__ __forceinline__ bool needs_drop(const Args& p, int pr) {
-    return pr == p.n_pairs - 1 && (p.n_frames & 1) && (int64_t)p.n_frames * p.hop < p.n_samples;
-}
-
 // fold k <-> N - k of one class from a natural-order LDS image img[k'] (k' < 4096):
-// class 0 bin 2k' (k' <= 2048) pairs with (4096 - k') & 4095, class 1 bin 2k'+1 (k' <= 2047) with 4095 - k'
-__device__ __forceinline__ int fold_partner(int q, int kp) { return q == 0 ? ((M - kp) & (M - 1)) : (M - 1 - kp); }
+// class 0 bin 2k' (k' <= 2048) pairs with (4096 - k') & 4095, class 1 bin 2k'+1 (k' <= 2047) with 4095 - k': fold_index
 __device__ __forceinline__ int fold_count(int q) { return q == 0 ? M / 2 + 1 : M / 2; }
 
 // ---- input spectra: grid = n_pairs ------------------------------------------------
@@ -169,7 +165,7 @@ __global__ __launch_bounds__(NTB) void k_x(Args p) {
     }
     __syncthreads();
     float* po = p.px + ((int64_t)cx * p.n_pairs + pr) * NB;
-    for (int kp = t; kp < fold_count(q); kp += 256) po[2 * kp + q] = 0.5f * (pw[kp] + pw[fold_partner(q, kp)]);
+    for (int kp = t; kp < fold_count(q); kp += 256) po[2 * kp + q] = 0.5f * (pw[kp] + pw[fold_index(q, kp)]);
 }
 
 // ---- output channels: grid = n_chunks * n_ch ----------------------------------------
@@ -253,12 +249,7 @@ __global__ __launch_bounds__(NTB, 1) void k_y(Args p) {
             }
             __builtin_amdgcn_sched_barrier(0);
         };
-#if W4_TIMING
-        unsigned long long ph[12] = {}, prev = 0;
-        w4::fft4096<!WINLDS>(v, tw, buf, tw2, t, ph, prev, issue_loads, issue_xs);
-#else
         w4::fft4096<!WINLDS>(v, tw, buf, tw2, t, issue_loads, issue_xs);
-#endif
 #pragma unroll
         for (int k3 = 0; k3 < 16; ++k3) {
             const float2 z = v[pos16(k3)];
@@ -279,7 +270,7 @@ __global__ __launch_bounds__(NTB, 1) void k_y(Args p) {
         for (int k3 = 0; k3 < 16; ++k3) buf[t + 256 * k3] = T[k3];
         __syncthreads();
         for (int kp = t; kp < fold_count(q); kp += 256) {
-            const float2 a = buf[kp], b = buf[fold_partner(q, kp)];
+            const float2 a = buf[kp], b = buf[fold_index(q, kp)];
             p.pxy[so + 2 * kp + q] = make_float2(0.5f * (a.x + b.x), 0.5f * (a.y - b.y));
         }
         __syncthreads();
@@ -288,7 +279,7 @@ __global__ __launch_bounds__(NTB, 1) void k_y(Args p) {
 #pragma unroll
     for (int k3 = 0; k3 < 16; ++k3) pw[t + 256 * k3] = P[k3];
     __syncthreads();
-    for (int kp = t; kp < fold_count(q); kp += 256) p.pyy[so + 2 * kp + q] = 0.5f * (pw[kp] + pw[fold_partner(q, kp)]);
+    for (int kp = t; kp < fold_count(q); kp += 256) p.pyy[so + 2 * kp + q] = 0.5f * (pw[kp] + pw[fold_index(q, kp)]);
 }
 
 // ---- host side ------------------------------------------------------------------------
@@ -297,12 +288,7 @@ __global__ __launch_bounds__(NTB, 1) void k_y(Args p) {
 __global__ __launch_bounds__(256) void k_px_sum(Args p) {
     const int q = blockIdx.x, cx = blockIdx.y;
     const int p0 = (int)((int64_t)q * p.n_pairs / p.n_chunks), p1 = (int)((int64_t)(q + 1) * p.n_pairs / p.n_chunks);
-    const float* __restrict__ px = p.px + (int64_t)cx * p.n_pairs * NB;
-    for (int k = threadIdx.x; k < NB; k += 256) {
-        double sum = 0.0;
-        for (int pr = p0; pr < p1; ++pr) sum += (double)px[(int64_t)pr * NB + k];
-        p.psx[((int64_t)q * p.n_cx + cx) * NB + k] = (float)sum;
-    }
+    welchc::px_sum<NB>(p, q, cx, p0, p1);
 }
 
 struct Plan {

@@ -33,6 +33,8 @@ namespace welchl {
 
 namespace w4 = welch4096;
 using w4::cmul;
+using w4::needs_drop;
+using welchc::fold_index;
 using w4::pos16;
 constexpr int M = 4096, NT = 256;
 constexpr int LDS_BYTES = (16 * w4::L1S + 256) * 8;  // exchange image + W256 table: 36 864 B
@@ -78,10 +80,6 @@ inline bool buf_fits(int64_t n_samples, int n_frames, int hop, int W) {
 }
 inline int classes_of(int W) {
     return (W == 16384 || W == 32768 || W == 65536 || W == 131072 || W == 262144) ? W / M : 0;
-}
-
-__device__ __forceinline__ bool needs_drop(const Args& p, int pr) {
-    return pr == p.n_pairs - 1 && (p.n_frames & 1) && (int64_t)p.n_frames * p.hop < p.n_samples;
 }
 
 // R-point DFT over s in registers: z[s] in, Z[r] out in natural order (forward, W_R = exp(-2 pi i / R)).
@@ -160,9 +158,6 @@ __global__ __launch_bounds__(NT) void k_dif(Args p) {
     for (int r = 0; r < R; ++r) out[(int64_t)r * M] = r ? cmul(z[r], p.twl[(size_t)r * M + m]) : z[0];
 }
 
-// fold partner of bin R k' + r: class (R - r) mod R, index
-__device__ __forceinline__ int fold_index(int r, int kp) { return r == 0 ? ((M - kp) & (M - 1)) : (M - 1 - kp); }
-
 // ---- input spectra: one transform per workgroup.  grid = n_pairs * R * n_cx ---------------------------------
 __global__ __launch_bounds__(NT) void k_xc(Args p) {
     extern __shared__ __align__(16) float2 lds[];
@@ -198,16 +193,7 @@ __global__ __launch_bounds__(NT) void k_xc(Args p) {
 // ---- input auto spectra per chunk: psx[q][cx][k] = sum over the chunk's pairs of the folded |W|^2 (fp64).
 // grid = (ceil(NB / 256), n_chunks, n_cx)
 __global__ __launch_bounds__(256) void k_px_sum(Args p) {
-    const int nb = p.R * (M / 2) + 1, N = p.R * M;
-    const int k = blockIdx.x * 256 + threadIdx.x, cq = blockIdx.y, cx = blockIdx.z;
-    if (k >= nb) return;
-    const int p0 = (int)((int64_t)cq * p.n_pairs / p.n_chunks), p1 = (int)((int64_t)(cq + 1) * p.n_pairs / p.n_chunks);
-    const float* __restrict__ pxu = p.pxu + (int64_t)cx * p.n_pairs * N;
-    const int r = k & (p.R - 1), kp = (k >> p.lgR) & (M - 1), rm = (p.R - r) & (p.R - 1);
-    const int ia = r * M + kp, ib = rm * M + fold_index(r, kp);
-    double sum = 0.0;
-    for (int pr = p0; pr < p1; ++pr) sum += (double)pxu[(int64_t)pr * N + ia] + (double)pxu[(int64_t)pr * N + ib];
-    p.psx[((int64_t)cq * p.n_cx + cx) * nb + k] = (float)(0.5 * sum);
+    welchc::px_sum_folded(p, p.R, p.lgR);
 }
 
 // ---- output channels: one workgroup per (chunk, channel, class).  grid = n_chunks * n_ch * R ------------------
@@ -252,7 +238,6 @@ __global__ __launch_bounds__(NT, (AUTO || JIT) ? 3 : 2) void k_yc(Args p) {  // 
 #pragma unroll
         for (int n1 = 0; n1 < 16; ++n1) nx[n1] = ld8(brs, 8 * (tid + 256 * n1));
     }
-    w4::Stamp ts;
     __syncthreads();  // the W256 table
     const int pstep = (int)(pair_stride * 8);  // bytes between consecutive pairs (R <= 64: 2 MB)
     for (int pr = p0; pr < p1; ++pr) {
@@ -285,8 +270,7 @@ __global__ __launch_bounds__(NT, (AUTO || JIT) ? 3 : 2) void k_yc(Args p) {  // 
                         xw[2 * (2 * g + j) + 1] = make_float2(q4.z, q4.w);
                     }
                 }
-            },
-            ts, 0);
+            });
 #pragma unroll
         for (int k3 = 0; k3 < 16; ++k3) {
             const float2 z = v[pos16(k3)];

@@ -223,7 +223,6 @@ __global__ __launch_bounds__(NT, 3) void k_h1f(FusedArgs fa) {
 #pragma unroll
         for (int j = 0; j < 16; ++j) nx[j] = ld_sample(rs, off0 + 1024 * (8 + j));
     }
-    Stamp ts;
     float winr[16];
 #pragma unroll
     for (int n1 = 0; n1 < 16; ++n1) winr[n1] = winl[tid + 256 * n1];
@@ -258,7 +257,6 @@ __global__ __launch_bounds__(NT, 3) void k_h1f(FusedArgs fa) {
                     xw[2 * (2 * g + j) + 1] = make_float2(q4.z, q4.w);
                 }
             },
-            ts, level16,
             [&]() {
                 // the chunk's input spectra: polled once, in front of their first use
                 if (pr == p0) {

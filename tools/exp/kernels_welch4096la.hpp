@@ -192,7 +192,6 @@ __global__ __launch_bounds__(NT, 3) void k_y3la(LaArgs la) {
 #pragma unroll
         for (int j = 0; j < 16; ++j) nx[j] = ld_sample(rs, off0 + 1024 * (8 + j));
     }
-    Stamp ts;
     float winr[16];  // (a thread reads back the window values it wrote itself: no barrier)
 #pragma unroll
     for (int n1 = 0; n1 < 16; ++n1) winr[n1] = winl[tid + 256 * n1];
@@ -226,8 +225,7 @@ __global__ __launch_bounds__(NT, 3) void k_y3la(LaArgs la) {
                     xw[2 * (2 * g + j)] = make_float2(q4.x, q4.y);
                     xw[2 * (2 * g + j) + 1] = make_float2(q4.z, q4.w);
                 }
-            },
-            ts, level16);
+            });
 #pragma unroll
         for (int k3 = 0; k3 < 16; ++k3) {
             const float2 z = v[pos16(k3)];
