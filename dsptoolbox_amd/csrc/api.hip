@@ -3457,6 +3457,11 @@ static int delay_shape_ok(ds_ctx* c, const char* who, int n_src, const int64_t* 
         if (src_len[s] < 0 || src_len[s] > n_avail) return fail(c, DS_ERR_ARG, std::string(who) + ": bad source length");
     if (order < 1 || order > dly::MAX_ORDER)
         return fail(c, DS_ERR_UNSUP, std::string(who) + ": filter orders 1 to 255 are built");
+    // the kernel's window starts and spans are int64 sums of a tile start, a shift and the taps: a quarter of the
+    // range leaves them room
+    for (size_t e = 0, n_t = (size_t)n_rows * n_terms; e < n_t; ++e)
+        if (shift[e] > INT64_MAX / 4 || shift[e] < -(INT64_MAX / 4))
+            return fail(c, DS_ERR_ARG, std::string(who) + ": a term's shift is beyond +-INT64_MAX / 4");
     return DS_OK;
 }
 

@@ -388,7 +388,7 @@ int ds_iir_sos_dev(ds_ctx* ctx, const float* x_dev, int n_ch, int64_t ldx, int64
  *     y[g, t] = sum_{j < n_terms} w[g,j] sum_{k <= order} h(frac[g,j])[k] x_{src[g,j]}[t - shift[g,j] - k]
  * with x_c[n] = 0 outside [0, src_len[c]).  h(f) is the reference's Kaiser-windowed sinc for the fractional delay f
  * (0 <= f < 1, side lobe parameter beta = _kaiser_window_beta(...)); a term with frac < 0 is a pass-through, the
- * single unit tap of a delay of exactly 0.  shift may be negative.  The per-term arrays src (int), shift (int64),
+ * single unit tap of a delay of exactly 0.  shift may be negative, |shift| <= INT64_MAX / 4 (DS_ERR_ARG beyond).  The per-term arrays src (int), shift (int64),
  * frac and weight (float64) are host pointers laid out [n_rows][n_terms]; src_len is a host array [n_src].
  * peak (host, [n_rows], or NULL) receives each row's max |y| as computed, before any rounding of the output type;
  * y may be NULL when only the peaks are wanted.  Orders 1 to 255 and at most 262140 rows: DS_ERR_UNSUP beyond.

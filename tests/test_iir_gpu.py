@@ -1,6 +1,6 @@
 """IIR filtering on the device (csrc/kernels_iir.hpp through ds_iir_sos / ds_iir_sos_dev): the reference's own outputs
-(tests/golden/iir/cases.npz), scipy parity of sosfilt / sosfiltfilt / lfilter on random stable cascades, the
-fractional-octave bank on a long multichannel signal, filter state across calls, the device-resident path and the
+(tests/golden/iir/cases.npz), scipy parity of sosfilt / sosfiltfilt / lfilter on random stable cascades, the lengths
+around a multiple of the block and of the group, banks with a state in all three modes, the fractional-octave bank on a long multichannel signal, filter state across calls, the device-resident path and the
 section cap."""
 
 import os
@@ -87,6 +87,67 @@ def test_sosfilt_parity_random_cascades(n_sec):
         assert relmax(y, ref) < TOL and relmax(zf, ref_zf) < TOL, (n_sec, n)
     x = rng.standard_normal((5000, 2))
     assert relmax(backend._sosfiltfilt(sos, x), sig.sosfiltfilt(sos, x, axis=0)) < TOL
+
+
+# The block is L = 32 samples and the group G = 2048: at these lengths the last block is full, one short or one long,
+# the group pass is skipped (one group), runs over full groups only, or leaves a one-sample last group, and the lane
+# that writes the final state changes with them.  Poles at radius 0.99 keep the carry's rounding
+# far inside 1e-9 of the reference's peak, the bound test_golden_cases holds the float64 entry to; TOL would let a
+# carry that is wrong at a group edge pass for a well-damped filter.
+EDGE_TOL = 1e-9
+EDGE_LENGTHS = [31, 32, 33, 63, 64, 65, 2047, 2048, 2049, 4095, 4096, 4097]
+
+
+@pytest.mark.parametrize("n_sec", [1, 3, 32])
+@pytest.mark.parametrize("n", EDGE_LENGTHS)
+def test_sosfilt_block_and_group_edges(n, n_sec):
+    rng = np.random.default_rng(1000 * n_sec + n)
+    sos = _random_sos(rng, n_sec, 0.99)
+    x = rng.standard_normal((n, 2))
+    zi = rng.standard_normal((n_sec, 2, 2))
+    ref, ref_zf = sig.sosfilt(sos, x, axis=0, zi=zi)
+    y, zf = backend._sosfilt(sos, x, zi)
+    assert y.shape == ref.shape and zf.shape == ref_zf.shape
+    e_y, e_zf = relmax(y, ref), relmax(zf, ref_zf)
+    print(f"n={n}, {n_sec} sections: y {e_y:.2e}, zf {e_zf:.2e} of the reference's peak")
+    assert e_y <= EDGE_TOL and e_zf <= EDGE_TOL, (n, n_sec, e_y, e_zf)
+
+
+@pytest.fixture(scope="module")
+def bank_with_state():
+    """three filters of 2 sections, two full groups and one block more, a state per filter, and sosfilt per filter"""
+    rng = np.random.default_rng(77)
+    sos = [_random_sos(rng, 2, 0.99) for _ in range(3)]
+    x = rng.standard_normal((4096 + 32, 2))
+    zi = rng.standard_normal((3, 2, 2, 2))
+    per_filter = [sig.sosfilt(sos[k], x, axis=0, zi=zi[k]) for k in range(3)]
+    return sos, x, zi, per_filter
+
+
+def test_bank_parallel_with_state(bank_with_state):
+    sos, x, zi, per_filter = bank_with_state
+    y, zf = backend.iir_sos_filter(x, sos, backend.DS_FB_PARALLEL, zi=zi)
+    assert y.shape == (3,) + x.shape and zf.shape == zi.shape
+    for k, (ref, ref_zf) in enumerate(per_filter):
+        assert relmax(y[k], ref) <= EDGE_TOL and relmax(zf[k], ref_zf) <= EDGE_TOL, k
+
+
+def test_bank_summed_with_state(bank_with_state):
+    sos, x, zi, per_filter = bank_with_state
+    y, zf = backend.iir_sos_filter(x, sos, backend.DS_FB_SUMMED, zi=zi)
+    assert y.shape == x.shape and zf.shape == zi.shape
+    assert relmax(y, sum(ref for ref, _ in per_filter)) <= EDGE_TOL
+    for k, (_, ref_zf) in enumerate(per_filter):
+        assert relmax(zf[k], ref_zf) <= EDGE_TOL, k
+
+
+def test_bank_sequential_with_state(bank_with_state):
+    """the (filters, sections, 2, C) state is the state of the one cascade of all six sections, in the same memory"""
+    sos, x, zi, _ = bank_with_state
+    ref, ref_zf = sig.sosfilt(np.concatenate(sos), x, axis=0, zi=zi.reshape(6, 2, 2))
+    y, zf = backend.iir_sos_filter(x, sos, backend.DS_FB_SEQUENTIAL, zi=zi)
+    assert y.shape == x.shape and zf.shape == zi.shape
+    assert relmax(y, ref) <= EDGE_TOL and relmax(zf.reshape(6, 2, 2), ref_zf) <= EDGE_TOL
 
 
 def test_lfilter_and_filtfilt_parity():
