@@ -5,13 +5,13 @@ banks) behind the reference's Signal / Filter / FilterBank API."""
 from . import beamforming, filterbanks, room_acoustics, standard, tools, transfer_functions, transforms
 from .classes import Filter, FilterBank, ImpulseResponse, MultiBandSignal, Signal, Spectrum
 from .standard.enums import (BiquadEqType, FilterBankMode, FilterCoefficientsType, FilterPassType,
-                             IirDesignMethod, SpectrumMethod, SpectrumScaling, SpectrumType, Window)
+                             FrequencySpacing, IirDesignMethod, SpectrumMethod, SpectrumScaling, SpectrumType, Window)
 from .standard import fractional_delay
 from .transfer_functions.enums import TransferFunctionType
 
 __version__ = "0.1.0"
 __all__ = ["Signal", "ImpulseResponse", "Spectrum", "Filter", "FilterBank", "MultiBandSignal",
-           "SpectrumMethod", "SpectrumScaling", "SpectrumType", "Window", "FilterBankMode",
+           "SpectrumMethod", "SpectrumScaling", "SpectrumType", "FrequencySpacing", "Window", "FilterBankMode",
            "FilterPassType", "FilterCoefficientsType", "IirDesignMethod", "BiquadEqType", "TransferFunctionType",
            "transfer_functions", "transforms", "room_acoustics", "beamforming", "filterbanks", "tools", "standard",
            "fractional_delay"]

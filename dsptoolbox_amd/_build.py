@@ -27,6 +27,7 @@ NO_SCRATCH = [
     "k_iir_group", "k_iir_carry", "k_iir_apply",
     "k_delay_sum",
     "k_cwt_inv", "k_cwt_squeeze",
+    "k_to_log", "k_smooth", "k_to_lin", "k_polar", "k_unwrap", "k_recombine",
 ]
 
 

@@ -1548,3 +1548,102 @@ def cwt_squeeze_device(scal: DeviceScalogram, freqs, fs, delta_w: float = 0.05,
         buf.free()
         raise
     return DeviceScalogram(buf, scal.shape, np.complex128)
+
+
+# ---- fractional-octave smoothing (ds_octave_smooth, ds_octave_smooth_complex; csrc/kernels_smooth.hpp) ------------
+SMOOTH_MAX_WORK = 1e13  # bins x window x channels of one call (csrc/size_guards.hpp; DS_ERR_UNSUP above)
+
+
+def _smooth_guard(n_bins: int, n_window: int, n_ch: int) -> None:
+    """NotImplementedError for a call beyond the direct summation's work bound, before anything reaches the device."""
+    if float(n_bins) * float(n_window) * float(n_ch) > SMOOTH_MAX_WORK:
+        raise NotImplementedError(f"fractional-octave smoothing of {n_bins} bins x {n_ch} channels with a window of "
+                                  f"{n_window} taps is beyond the device kernel's work bound ({SMOOTH_MAX_WORK:.0e} "
+                                  "multiply-adds per call)")
+
+
+def _smooth_axis(n_bins: int, bin_spacing_octaves):
+    """(k_log or None, beta) of helpers/smoothing.py:55-67: numpy's own values of N ** (arange(N) / (N - 1)) -- the
+    last one is exactly N, which keeps the last linear bin an interpolation."""
+    if bin_spacing_octaves is not None:
+        return None, bin_spacing_octaves
+    if n_bins < 2:
+        raise ValueError("fractional-octave smoothing of linearly spaced bins needs at least two bins")
+    k_log = n_bins ** (np.arange(n_bins, dtype=np.float64) / (n_bins - 1))
+    return k_log, np.log2(k_log[1])
+
+
+def _smooth_window_length(num_fractions, beta) -> int:
+    n_window = int(1 / (num_fractions * beta) + 0.5)  # round
+    return n_window + 1 - n_window % 2                # odd: the delay is a whole number of bins
+
+
+def _smooth_window(n_window: int, window_type, window_vec) -> np.ndarray:
+    """The window of helpers/smoothing.py:74-98 (scipy on the host: n_window values) with the reference's two
+    assertions and its gaussian alpha -> sigma rule.  A caller's vector is copied, not normalised in place."""
+    if window_type is not None:
+        assert window_vec is None, "When window type is passed, no window vector should be added"
+        if "gauss" in window_type[0]:
+            window_type = ("gaussian", (n_window - 1) / (2 * window_type[1]))
+        return np.ascontiguousarray(get_window(window_type, n_window, fftbins=False), dtype=np.float64)
+    assert window_vec is not None, "When using a window as a vector, window type should be None"
+    return np.array(window_vec, dtype=np.float64).ravel()
+
+
+def fractional_octave_smoothing(vector, bin_spacing_octaves=None, num_fractions=3, window_type="hann",
+                                window_vec=None, clip_values: bool = False):
+    """_fractional_octave_smoothing (helpers/smoothing.py:9-129) along the first axis of a real (N,) or (N, C) array,
+    on the device in float64: PCHIP to a logarithmic axis (linear bins, bin_spacing_octaves None), an edge-padded
+    convolution with the unit-sum window, linear interpolation back, optional clip at 0.
+
+    The reference pads by the odd window length it derives from the spacing even when the caller hands in a window
+    vector of another length L, and so returns N + n_window - L points for logarithmic bins (and fails to interpolate
+    back for linear ones): reproduced, the padding of that corner made on the host."""
+    vector = np.asarray(vector, dtype=np.float64)
+    assert vector.ndim in (1, 2), "the vector to smooth is (bins,) or (bins, channels)"
+    one_dim = vector.ndim == 1
+    v = np.ascontiguousarray(vector[:, None] if one_dim else vector)
+    n_bins, n_ch = v.shape
+    k_log, beta = _smooth_axis(n_bins, bin_spacing_octaves)
+    n_window = _smooth_window_length(num_fractions, beta)
+    window = _smooth_window(n_window, window_type, window_vec)
+    crop = None
+    if len(window) != n_window:
+        if k_log is not None:
+            raise ValueError(f"a window vector of {len(window)} values on linearly spaced bins: the reference pads for "
+                             f"{n_window} and cannot interpolate its {n_bins + n_window - len(window)} points back")
+        if n_bins + n_window - len(window) < 1:
+            raise ValueError("the window vector is longer than the padded data")
+        # pad for n_window as the reference does; the entry's own (clamped) padding then never shows in the crop
+        v = np.ascontiguousarray(np.pad(v, ((n_window // 2, n_window // 2), (0, 0)), mode="edge"))
+        crop = (len(window) // 2, n_bins + n_window - len(window))
+        n_bins = v.shape[0]
+    _smooth_guard(n_bins, len(window), n_ch)
+    out = np.empty_like(v)
+    ctx = get_context()
+    ctx.check(ctx.lib.ds_octave_smooth(ctx.handle, _ptr(v), n_bins, n_ch, None if k_log is None else _ptr(k_log),
+                                       _ptr(window), len(window), int(bool(clip_values)), _ptr(out)), "ds_octave_smooth")
+    if crop is not None:
+        out = out[crop[0]:crop[0] + crop[1]].copy()
+    return out.squeeze() if one_dim else out
+
+
+def smooth_complex_spectrum(spectrum, num_fractions, bin_spacing_octaves=None, window_type="hann",
+                            clip_magnitude: bool = False):
+    """A complex (N, C) spectrum smoothed as the reference's callers do it (classes/signal.py:913-928, classes/
+    spectrum.py:859-868): |z| (clipped at 0 if clip_magnitude) and np.unwrap(np.angle(z), axis=0) through
+    fractional_octave_smoothing, recombined as mag * exp(1j * phase) -- one upload, one download
+    (ds_octave_smooth_complex), float64 / complex128."""
+    z = np.ascontiguousarray(spectrum, dtype=np.complex128)
+    assert z.ndim == 2, "the spectrum is (bins, channels)"
+    n_bins, n_ch = z.shape
+    k_log, beta = _smooth_axis(n_bins, bin_spacing_octaves)
+    n_window = _smooth_window_length(num_fractions, beta)
+    window = _smooth_window(n_window, window_type, None)
+    _smooth_guard(n_bins, n_window, 2 * n_ch)
+    out = np.empty_like(z)
+    ctx = get_context()
+    ctx.check(ctx.lib.ds_octave_smooth_complex(ctx.handle, _ptr(z), n_bins, n_ch, None if k_log is None else _ptr(k_log),
+                                               _ptr(window), n_window, int(bool(clip_magnitude)), _ptr(out)),
+              "ds_octave_smooth_complex")
+    return out

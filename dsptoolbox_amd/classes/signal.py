@@ -365,8 +365,6 @@ class Signal(MultichannelData):
         else:
             fft_length = (next_fast_len(self.length_samples, True)
                           if par["pad_to_fast_length"] else self.length_samples)
-            if par["smoothing"] != 0:
-                raise NotImplementedError("spectrum smoothing is outside the GPU hot path")
             if hasattr(self, "window"):
                 raise NotImplementedError("time-windowed signals are outside the GPU hot path")
             scaling = self.spectrum_scaling
@@ -374,6 +372,9 @@ class Signal(MultichannelData):
             scale = 1.0 if norm == "backward" else (
                 1.0 / fft_length if norm == "forward" else fft_length**-0.5)
             spectrum = backend.rfft_spectrum(self.time_data, fft_length, scale)
+            if par["smoothing"] != 0:
+                # classes/signal.py:913-928: magnitude (clipped) and unwrapped phase, before the physical-units scaling
+                spectrum = backend.smooth_complex_spectrum(spectrum, par["smoothing"], clip_magnitude=True)
             if scaling.has_physical_units():
                 # helpers/spectrum_utilities.py:268-328 (per-bin scalars on the device result)
                 factor = scaling.get_scaling_factor(fft_length, self.sampling_rate_hz, None)

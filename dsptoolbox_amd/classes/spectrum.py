@@ -1,13 +1,13 @@
 """Spectrum container returned by compute_transfer_function
 (API mirror of dsptoolbox/classes/spectrum.py: ctor :31-53, setters :138-269,
-set_coherence :871-885).  Interpolation, smoothing and plotting of the
-reference class are outside the hot path."""
+set_coherence :871-885, apply_octave_smoothing :805-869 on the device).
+Interpolation and plotting of the reference class are outside the hot path."""
 
 from copy import deepcopy
 
 import numpy as np
 
-from ..standard.enums import SpectrumType
+from ..standard.enums import FrequencySpacing, SpectrumType, Window
 from ._multichannel_data import MultichannelData
 
 
@@ -70,6 +70,19 @@ class Spectrum(MultichannelData):
         self.__frequency_vector_hz = f
 
     @property
+    def frequency_vector_type(self) -> FrequencySpacing:
+        """Linear, Logarithmic or Other spacing of the frequency vector (classes/spectrum.py:317-331)."""
+        f = self.frequency_vector_hz
+        try:
+            if np.all(np.isclose(np.ediff1d(f), f[-1] - f[-2])):
+                return FrequencySpacing.Linear
+            if np.all(np.isclose(f[2:] / f[1:-1], f[-1] / f[-2])):
+                return FrequencySpacing.Logarithmic
+        except Exception as e:
+            print(e)
+        return FrequencySpacing.Other
+
+    @property
     def number_frequency_bins(self) -> int:
         return len(self.frequency_vector_hz)
 
@@ -118,6 +131,27 @@ class Spectrum(MultichannelData):
             "Length of signals and given coherence do not match"
         assert not np.iscomplexobj(coherence), "Coherence cannot be complex"
         self.coherence = coherence
+
+    def apply_octave_smoothing(self, octave_fraction: float, window_type: Window = Window.Hann) -> "Spectrum":
+        """Fractional-octave smoothing of the spectral data in place (classes/spectrum.py:805-869), on the device:
+        a magnitude spectrum directly, a complex one as magnitude and unwrapped phase.  Linear and logarithmic
+        frequency vectors; for any other spacing the reference first interpolates the spectrum to 1 Hz bins, which
+        is not in this project."""
+        spacing = self.frequency_vector_type
+        if spacing == FrequencySpacing.Other:
+            raise NotImplementedError("octave smoothing of a spectrum whose frequency vector is neither linear nor "
+                                      "logarithmic needs the reference's spectrum interpolation (outside the GPU "
+                                      "hot path)")
+        from .. import backend
+        beta = (np.log2(self.frequency_vector_hz[-1] / self.frequency_vector_hz[-2])
+                if spacing == FrequencySpacing.Logarithmic else None)
+        if self.is_magnitude:
+            self.spectral_data = backend.fractional_octave_smoothing(self.spectral_data, beta, octave_fraction,
+                                                                     window_type.to_scipy_format())
+        else:
+            self.spectral_data = backend.smooth_complex_spectrum(self.spectral_data, octave_fraction, beta,
+                                                                 window_type.to_scipy_format())
+        return self
 
     def sum_channels(self, power_sum: bool = True) -> "Spectrum":
         """One-channel spectrum of all channels: the root of the summed powers (default), or the plain sum of the

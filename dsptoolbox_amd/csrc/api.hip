@@ -43,6 +43,8 @@
 #include "kernels_iir.hpp"
 #include "kernels_delay.hpp"
 #include "kernels_cwt.hpp"
+#include "kernels_smooth.hpp"
+#include "size_guards.hpp"
 
 using namespace dsk;
 
@@ -3699,6 +3701,115 @@ extern "C" int ds_cwt_squeeze_dev(ds_ctx* c, const float* s, int n_freq, int64_t
     const int64_t cols = n_samples * n_ch;
     dscwt::SqueezeArgs a{(const float2*)s, n_freq, n_ch, n_samples, dfq, ddf, norm ? dn : nullptr, fs, (double2*)out};
     return launch(c, "cwt_squeeze", dscwt::k_cwt_squeeze, dim3((unsigned)((cols + 255) / 256)), 256, 0, a);
+}
+
+// ---- fractional-octave smoothing (kernels_smooth.hpp), float64 -----------------------------------------------
+static int smooth_check(ds_ctx* c, const char* who, int64_t n_bins, int n_ch, const double* k_log, const double* window,
+                        int64_t n_window) {
+    const std::string w(who);
+    if (n_bins < 1 || n_ch < 1 || n_window < 1 || (int64_t)n_ch * 2 > INT32_MAX / 2)
+        return fail(c, DS_ERR_ARG, w + ": bad shape");
+    if (k_log) {
+        // k_to_lin brackets every linear bin 1 .. N between two points of k_log: no extrapolation, as in the reference
+        if (n_bins < 2) return fail(c, DS_ERR_ARG, w + ": the logarithmic axis needs two bins");
+        if (!(k_log[0] <= 1.0) || !(k_log[n_bins - 1] >= (double)n_bins))
+            return fail(c, DS_ERR_ARG, w + ": k_log does not span the bins 1 .. n_bins");
+        for (int64_t i = 1; i < n_bins; ++i)
+            if (!(k_log[i] > k_log[i - 1])) return fail(c, DS_ERR_ARG, w + ": k_log is not strictly ascending");
+    }
+    double sum = 0.0;
+    for (int64_t k = 0; k < n_window; ++k) sum += window[k];
+    if (!(std::fabs(sum) > 0.0) || !std::isfinite(sum)) return fail(c, DS_ERR_ARG, w + ": the window sums to zero");
+    if (smooth_work_too_large(n_bins, n_window, n_ch))
+        return fail(c, DS_ERR_UNSUP, w + ": bins x window x channels is beyond the direct summation's work bound");
+    if ((n_bins * n_ch + dssmooth::NT - 1) / dssmooth::NT > INT32_MAX)
+        return fail(c, DS_ERR_UNSUP, w + ": more values than one launch covers");
+    return DS_OK;
+}
+
+// the three real passes on a dense device array v (n_bins, n_ch); the result lands in `out`, a and b are two more
+// arrays of that size.  klog / wr: device copies of k_log (or nullptr) and of the reversed window.
+static int smooth_run(ds_ctx* c, const double* v, int64_t n_bins, int n_ch, const double* klog, const double* wr,
+                      int64_t n_window, int clip_ch, double* a, double* b, double* out) {
+    using namespace dssmooth;
+    const dim3 flat((unsigned)((n_bins * n_ch + NT - 1) / NT));
+    int tc = 1, lg = 0;
+    while (tc < MAX_TC && tc < n_ch) tc <<= 1, ++lg;
+    const dim3 tiles((unsigned)((n_bins + smooth_tile_bins(tc) - 1) / smooth_tile_bins(tc)), (unsigned)((n_ch + tc - 1) / tc));
+    if (!klog) {
+        CHK(launch(c, "smooth", k_smooth, tiles, NT, 0, SmoothArgs{v, wr, n_bins, n_window, n_ch, tc, lg, out}));
+        if (clip_ch > 0) CHK(launch(c, "smooth_clip", k_clip, flat, NT, 0, ClipArgs{out, n_bins, n_ch, clip_ch}));
+        return DS_OK;
+    }
+    CHK(launch(c, "smooth_to_log", k_to_log, flat, NT, 0, LogArgs{v, klog, n_bins, n_ch, a}));
+    CHK(launch(c, "smooth", k_smooth, tiles, NT, 0, SmoothArgs{a, wr, n_bins, n_window, n_ch, tc, lg, b}));
+    return launch(c, "smooth_to_lin", k_to_lin, flat, NT, 0,
+                  LinArgs{b, klog, n_bins, n_ch, clip_ch, (double)(n_bins - 1) / std::log((double)n_bins), out});
+}
+
+// k_log and the normalised, reversed window on the device
+static int smooth_tables(ds_ctx* c, int64_t n_bins, const double* k_log, const double* window, int64_t n_window,
+                         double* dklog, double* dwr) {
+    double sum = 0.0;
+    for (int64_t k = 0; k < n_window; ++k) sum += window[k];
+    std::vector<double> wr(n_window);
+    for (int64_t k = 0; k < n_window; ++k) wr[k] = window[n_window - 1 - k] / sum;
+    CHK(ds_upload(c, dwr, wr.data(), (size_t)n_window * 8));
+    if (k_log) CHK(ds_upload(c, dklog, k_log, (size_t)n_bins * 8));
+    return DS_OK;
+}
+
+extern "C" int ds_octave_smooth(ds_ctx* c, const double* v, int64_t n_bins, int n_ch, const double* k_log,
+                                const double* window, int64_t n_window, int clip, double* out) {
+    if (!c || !v || !window || !out) return fail(c, DS_ERR_ARG, "ds_octave_smooth: null argument");
+    CHK(smooth_check(c, "ds_octave_smooth", n_bins, n_ch, k_log, window, n_window));
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t n = (size_t)n_bins * n_ch;
+    double *dv, *da, *db, *dout, *dklog, *dwr;
+    CHK(carve(c, &c->ws, &c->ws_bytes, [&](Carver& cv) {
+        dv = cv.take<double>(n);
+        da = cv.take<double>(k_log ? n : 0);
+        db = cv.take<double>(k_log ? n : 0);
+        dout = cv.take<double>(n);
+        dklog = cv.take<double>(k_log ? n_bins : 0);
+        dwr = cv.take<double>(n_window);
+    }));
+    CHK(smooth_tables(c, n_bins, k_log, window, n_window, dklog, dwr));
+    CHK(ds_upload(c, dv, v, n * 8));
+    CHK(smooth_run(c, dv, n_bins, n_ch, k_log ? dklog : nullptr, dwr, n_window, clip ? n_ch : 0, da, db, dout));
+    return ds_download(c, out, dout, n * 8);
+}
+
+// z, out: (n_bins, n_ch) complex128.  |z| and the unwrapped phase are smoothed as the 2 n_ch columns of one real array
+// and recombined; everything between the upload of z and the download of the result stays on the device.
+extern "C" int ds_octave_smooth_complex(ds_ctx* c, const double* z, int64_t n_bins, int n_ch, const double* k_log,
+                                        const double* window, int64_t n_window, int clip_magnitude, double* out) {
+    using namespace dssmooth;
+    if (!c || !z || !window || !out) return fail(c, DS_ERR_ARG, "ds_octave_smooth_complex: null argument");
+    CHK(smooth_check(c, "ds_octave_smooth_complex", n_bins, 2 * n_ch, k_log, window, n_window));
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t n = (size_t)n_bins * n_ch;
+    double *dz, *dmp, *dun, *da, *db, *dout, *dklog, *dwr;
+    CHK(carve(c, &c->ws, &c->ws_bytes, [&](Carver& cv) {
+        dz = cv.take<double>(2 * n);   // the spectrum, then the result
+        dmp = cv.take<double>(2 * n);  // (its magnitude columns stay unused) | wrapped phase
+        dun = cv.take<double>(2 * n);  // magnitude | unwrapped phase
+        da = cv.take<double>(k_log ? 2 * n : 0);
+        db = cv.take<double>(k_log ? 2 * n : 0);
+        dout = cv.take<double>(2 * n);
+        dklog = cv.take<double>(k_log ? n_bins : 0);
+        dwr = cv.take<double>(n_window);
+    }));
+    CHK(smooth_tables(c, n_bins, k_log, window, n_window, dklog, dwr));
+    CHK(ds_upload(c, dz, z, n * 16));
+    const dim3 flat((unsigned)((n + NT - 1) / NT));
+    CHK(launch(c, "smooth_polar", k_polar, flat, NT, 0, PolarArgs{(const double2*)dz, n_bins, n_ch, dun, dmp}));
+    CHK(launch(c, "smooth_unwrap", k_unwrap, dim3((unsigned)n_ch), NT, 0,
+               UnwrapArgs{dmp + n_ch, n_bins, 2 * (int64_t)n_ch, dun + n_ch}));
+    CHK(smooth_run(c, dun, n_bins, 2 * n_ch, k_log ? dklog : nullptr, dwr, n_window, clip_magnitude ? n_ch : 0, da, db,
+                   dout));
+    CHK(launch(c, "smooth_recombine", k_recombine, flat, NT, 0, RecombineArgs{dout, n_bins, n_ch, (double2*)dz}));
+    return ds_download(c, out, dz, n * 16);
 }
 
 // ---- RCCL (resolved at run time so the library loads on machines without it) ----

@@ -3,7 +3,7 @@
 Only the members and methods the hot path touches are provided:
 SpectrumMethod (:7-18), SpectrumScaling (:21-229), FilterCoefficientsType
 (:232-243), BiquadEqType (:246-276), FilterBankMode (:279-292), FilterPassType
-(:295-305), IirDesignMethod (:308-338), Window (:341-437), SpectrumType.
+(:295-305), IirDesignMethod (:308-338), Window (:341-437), SpectrumType, FrequencySpacing (:525-528).
 """
 
 from enum import Enum, auto
@@ -97,6 +97,14 @@ class SpectrumType(Enum):
     Magnitude = auto()
     Complex = auto()
     Db = auto()
+
+
+class FrequencySpacing(Enum):
+    """Spacing of a Spectrum's frequency vector."""
+
+    Logarithmic = auto()
+    Linear = auto()
+    Other = auto()
 
 
 class FilterCoefficientsType(Enum):

@@ -1,7 +1,10 @@
 """tools: the fractional-octave band arithmetic of the reference's tools.fractional_octave_frequencies
-(dsptoolbox/tools.py:186-255), after the band definitions of IEC 61260-1:2014 / ANSI S1.11-2004."""
+(dsptoolbox/tools.py:186-255), after the band definitions of IEC 61260-1:2014 / ANSI S1.11-2004, and
+fractional_octave_smoothing (dsptoolbox/tools.py:22-23) on the device."""
 
 import numpy as np
+
+from .backend import fractional_octave_smoothing  # noqa: F401
 
 # base-ten octave ratio and reference frequency of IEC 61260-1 (5.2, 5.4)
 _G = 10 ** (3 / 10)

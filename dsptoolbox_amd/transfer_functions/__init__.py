@@ -145,14 +145,13 @@ def spectral_deconvolve(output: Signal, input: Signal, apply_regularization: boo
     if not apply_regularization:
         assert start_stop_hz is None, \
             "No start_stop_hz vector can be passed when using standard mode"
-    for s in (output, input):
-        if s._spectrum_parameters["smoothing"] != 0:
-            raise NotImplementedError("fractional-octave spectrum smoothing is outside the GPU hot path")
     # Only the spectrum METHOD is forced (transfer_functions.py:142-143): each signal's own scaling still
-    # applies inside get_spectrum (classes/signal.py:899-938).  The defaults (FFTBackward) give the plain
-    # transform and take the fused device path below; any other scaling goes through the general one.
+    # and smoothing still apply inside get_spectrum (classes/signal.py:899-938).  The defaults (FFTBackward, no
+    # smoothing) give the plain transform and take the fused device path below; anything else goes through the
+    # general one.
     plain = all(s._spectrum_parameters["scaling"].fft_norm() == "backward"
-                and not s._spectrum_parameters["scaling"].has_physical_units() for s in (output, input))
+                and not s._spectrum_parameters["scaling"].has_physical_units()
+                and s._spectrum_parameters["smoothing"] == 0 for s in (output, input))
     if not plain:
         return _spectral_deconvolve_scaled(output, input, apply_regularization, start_stop_hz, threshold_db,
                                            padding, keep_original_length, multichannel)

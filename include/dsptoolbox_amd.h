@@ -425,6 +425,26 @@ int ds_cwt_dev(ds_ctx* ctx, const float* x_dev, int n_ch, int64_t ldx, int64_t n
 int ds_cwt_squeeze_dev(ds_ctx* ctx, const float* s_dev, int n_freq, int64_t n_samples, int n_ch, const double* freqs,
                        const double* delta_f, const double* norm, double fs, double* out_dev);
 
+/* ---- fractional-octave smoothing, float64: replaces the reference's _fractional_octave_smoothing (helpers/
+ * smoothing.py:9-129) and the magnitude / unwrapped-phase smoothing around it in Signal.get_spectrum (classes/
+ * signal.py:913-928) and Spectrum.apply_octave_smoothing (classes/spectrum.py:805-869).  v, out: (n_bins, n_ch) host
+ * arrays, channel fastest.  k_log (host, [n_bins]): the logarithmic axis n_bins ** (arange(n_bins) / (n_bins - 1)) of
+ * linearly spaced bins, computed by the caller; strictly ascending with k_log[0] <= 1 and k_log[n_bins - 1] >=
+ * n_bins (DS_ERR_ARG otherwise).  The data goes to that axis with scipy's PchipInterpolator (knots 1 .. n_bins), is
+ * smoothed, and comes back by linear interpolation.  k_log = NULL: the bins are logarithmic already, both
+ * interpolations are skipped.  window (host, [n_window], any non-zero sum: normalised to unit sum here): the data is
+ * edge-padded by n_window / 2 in front and n_window / 2 - (1 - n_window % 2) behind and convolved in valid mode,
+ *     out[i] = sum_k window[k] v[clamp(i + n_window - 1 - k - n_window / 2, 0, n_bins - 1)] / sum(window),
+ * by direct summation.  clip != 0: negative results become 0.  n_bins * n_window * n_ch beyond the work bound of
+ * csrc/size_guards.hpp: DS_ERR_UNSUP, before any launch.
+ * ds_octave_smooth_complex: z, out (n_bins, n_ch) complex128 (interleaved doubles); |z| (clipped if clip_magnitude)
+ * and numpy.unwrap(angle(z)) along the bins are smoothed as above and recombined as mag * exp(i phase); the work
+ * counts 2 n_ch channels.                                                                                       */
+int ds_octave_smooth(ds_ctx* ctx, const double* v, int64_t n_bins, int n_ch, const double* k_log, const double* window,
+                     int64_t n_window, int clip, double* out);
+int ds_octave_smooth_complex(ds_ctx* ctx, const double* z, int64_t n_bins, int n_ch, const double* k_log,
+                             const double* window, int64_t n_window, int clip_magnitude, double* out);
+
 /* ---- block-streaming FIR classes with device-resident state ------------------------------
  * One process_block of the reference's real-time classes (classes/fir_filter_realtime.py:75-335),
  * executed literally on buffers that stay on the device between calls; per call only the block
