@@ -653,7 +653,10 @@ __global__ __launch_bounds__(stft_max_teams<N>() * Cfg<N>::NT) void k_istft_fuse
 #pragma unroll
             for (int j = 0; j < H; ++j) {
                 const int n = tid + NT * j;
-                const float2 lo = buf[lidx(n)], hi = buf[lidx(n + STEP)];
+                float2 lo = buf[lidx(n)], hi = buf[lidx(n + STEP)];
+                // a last pair without a second frame: the imaginary part is the transform's rounding of frame f0, not
+                // zero, and the envelope's floor behind the last frame multiplies it by 1e4
+                if (!v1) lo.y = hi.y = 0.f;
                 const float wl = p.window[n] * p.scale, wh = p.window[n + STEP] * p.scale;
                 if (owned) {
                     const float s0 = carry[j] + lo.x * wl;       // second half of the frame before + first half of f0
@@ -667,7 +670,7 @@ __global__ __launch_bounds__(stft_max_teams<N>() * Cfg<N>::NT) void k_istft_fuse
                     else
                         emit(P0 + STEP + n, s1);
                 }
-                carry[j] = hi.y * wh;                                // second half of f0 + 1 (zero if it does not exist)
+                carry[j] = hi.y * wh;                                // second half of f0 + 1 (0 if it does not exist)
             }
         }
     }

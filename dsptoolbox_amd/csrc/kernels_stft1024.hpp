@@ -496,8 +496,10 @@ __global__ __launch_bounds__(NN == 2048 ? 512 : (NN >= 1024 ? 1024 : NN)) void k
                 const int n = t + L * m;
                 // frame f0: Re, frame f0 + 1: -Im (the result is the conjugate of a + i b)
                 const float wl = wv(m), wh = wv(m + 8);
-                const float a_lo = z[m].x * wl, b_lo = -z[m].y * wl;
-                const float a_hi = z[m + 8].x * wh, b_hi = -z[m + 8].y * wh;
+                // (a last pair without a second frame: -Im is the transform's rounding of frame f0, not zero, and the
+                // envelope's floor behind the last frame multiplies it by 1e4)
+                const float a_lo = z[m].x * wl, b_lo = v1 ? -z[m].y * wl : 0.f;
+                const float a_hi = z[m + 8].x * wh, b_hi = v1 ? -z[m + 8].y * wh : 0.f;
                 if (owned) {
                     const float s0 = carry[m] + a_lo;  // second half of the frame before + first half of f0
                     const float s1 = a_hi + b_lo;      // second half of f0 + first half of f0 + 1
@@ -510,7 +512,7 @@ __global__ __launch_bounds__(NN == 2048 ? 512 : (NN >= 1024 ? 1024 : NN)) void k
                     else
                         emit(P0 + STEP + n, s1);
                 }
-                carry[m] = b_hi;  // second half of f0 + 1 (zero if it does not exist)
+                carry[m] = b_hi;  // second half of f0 + 1 (0 if it does not exist)
             }
         }
     }

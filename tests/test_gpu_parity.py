@@ -16,6 +16,8 @@ from dsptoolbox_amd.standard.enums import (FilterBankMode, FilterPassType, Spect
 from dsptoolbox_amd.transfer_functions import TransferFunctionType
 from oracle import dsp_oracle as orc
 from conftest import load_golden
+import route_cases as rcs
+import route_oracles as ros
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-6
@@ -2600,29 +2602,21 @@ SWITCH_ROUTES = [
 # helper on the library before the Welch dispatch became one route choice (csrc/api.hip, welch_route).
 WELCH_ROUTE_SWITCHES = {"default": {}, "WELCH_GENERIC": {"DSPTOOLBOX_AMD_WELCH_GENERIC": "1"},
                         "NO_WELCH4096": {"DSPTOOLBOX_AMD_NO_WELCH4096": "1"}}
-WELCH_ROUTE_WINDOWS = [32, 64, 128, 256, 1024, 2048, 4096, 8192, 16384, 32768, 2**20]
-# the transfer function, auto and cross spectra: host float32, host float64 and (tf, psd) device-resident entries
-WELCH_ROUTE_ENTRIES = {"tf": ("tf", "tf_f64", "tf_dev"), "psd": ("psd", "psd_f64", "psd_dev"), "csd": ("csd", "csd_f64")}
+WELCH_ROUTE_WINDOWS, WELCH_ROUTE_ENTRIES = rcs.WELCH_ROUTE_WINDOWS, rcs.WELCH_ROUTE_ENTRIES
 
 
-def _welch_route_case(entry, W, hop_div, average, one_in, n_ch=3):
-    """One small estimate through one C-ABI entry point -> (output arrays, launch names).  `one_in`: one input channel
-    (transfer function) / one channel (spectra); otherwise n_ch of them."""
+def _welch_route_case(entry, q):
+    """One small estimate (the problem q of route_cases.welch_problem) through one C-ABI entry point -> (output
+    arrays, launch names)."""
     import ctypes as C
     from dsptoolbox_amd._lib import DeviceBuffer, DevicePlanar, get_context
     ctx = get_context()
     p = lambda a: a.ctypes.data_as(C.c_void_p)
-    hop, n = W // hop_div, 2 * W + 3000
-    n_frames = -(-n // hop)
-    rng = np.random.default_rng(W + hop_div)
-    y = rng.standard_normal((n, n_ch))
-    x = (y[:, :1] if one_in else y) * 0.5 + 0.1 * rng.standard_normal((n, 1 if one_in else n_ch))
-    x = np.ascontiguousarray(x)
-    xp, yp = np.ascontiguousarray(x.T, dtype=np.float32), np.ascontiguousarray(y.T, dtype=np.float32)
-    w = (0.5 - 0.5 * np.cos(2 * np.pi * np.arange(W) / W)).astype(np.float32)
-    B, avg, kind = W // 2 + 1, backend.DS_AVG[average], entry.split("_")[0]
-    tail = (1, avg) + ((backend.DS_TF["H2"],) if kind == "tf" else ()) + (0, 1.0 / W, 2.0, 1)
-    n_out = n_ch if kind == "tf" else x.shape[1]
+    x, y, xp, yp, w = q["x"], q["y"], q["xp"], q["yp"], q["w"]
+    W, hop, n, n_frames, B, n_ch, n_out = q["W"], q["hop"], q["n"], q["n_frames"], q["B"], q["n_cy"], q["n_out"]
+    avg, kind = backend.DS_AVG[q["average"]], q["kind"]
+    tail = (q["detrend"], avg) + ((backend.DS_TF[q["mode"]],) if kind == "tf" else ()) + \
+        (q["amp_sqrt"], q["norm_scale"], q["factor"], q["halve_edges"])
     ctx.routes()
     if entry.endswith("_dev"):
         dx, dy = DevicePlanar.from_planar(ctx, xp), DevicePlanar.from_planar(ctx, yp)
@@ -2653,7 +2647,6 @@ def _welch_route_case(entry, W, hop_div, average, one_in, n_ch=3):
         ctx.check(fn(ctx.handle, p(xa), n_out, n, W, hop, n_frames, p(w), *tail, p(psd)), entry)
         out = (psd,)
     else:
-        ya = np.ascontiguousarray(ya[:, :n_out] if f64 else ya[:n_out])
         csd = np.empty((B, n_out), np.complex64)
         fn = ctx.lib.ds_welch_csd_f64 if f64 else ctx.lib.ds_welch_csd
         ctx.check(fn(ctx.handle, p(xa), p(ya), n_out, n, W, hop, n_frames, p(w), *tail, p(csd)), entry)
@@ -2669,12 +2662,13 @@ def _welch_route_matrix(kinds=("tf", "psd", "csd"), windows=WELCH_ROUTE_WINDOWS,
             for hop_div in (2, 4):
                 for average in ("mean", "median"):
                     for one_in in (True, False):
+                        q = rcs.welch_problem(kind, W, hop_div, average, one_in)
                         for entry in WELCH_ROUTE_ENTRIES[kind]:
-                            out, routes = _welch_route_case(entry, W, hop_div, average, one_in)
+                            out, routes = _welch_route_case(entry, q)
                             key = f"{entry}|{W}|{hop_div}|{average}|{1 if one_in else 3}"
                             seen[key] = sorted(routes)
                             if on_case:
-                                on_case(key, out)
+                                on_case(key, entry, q, out, seen[key])
     return seen
 
 
@@ -2691,14 +2685,16 @@ def test_welch_routes_per_window(switch, kind, W, monkeypatch):
     for k, v in WELCH_ROUTE_SWITCHES[switch].items():
         monkeypatch.setenv(k, v)
     _lib.reset_context()
+    judged = _RouteJudge(f"welch {kind} W={W} {switch}")
     try:
-        seen = _welch_route_matrix((kind,), (W,))
+        seen = _welch_route_matrix((kind,), (W,), on_case=judged)
     finally:
         for k in WELCH_ROUTE_SWITCHES[switch]:
             monkeypatch.delenv(k, raising=False)
         _lib.reset_context()
     # (every entry point of a kind runs the same kernels: the table has one row per kind)
     want = {k: table[f"{switch}|{kind}|{k.split('|', 1)[1]}"].split() for k in seen}
+    judged.report()
     assert seen == want
 
 
@@ -2787,11 +2783,31 @@ def test_welch_rejected_calls():
 # (window: "full" = nfft samples, "short" = 3 nfft / 4); the launch names were recorded through the same helpers on the
 # library before the STFT and iSTFT dispatch became one route choice each (csrc/api.hip, stft_route / istft_route).
 STFT_ROUTE_SWITCHES = {"default": {}, "STFT_GENERIC": {"DSPTOOLBOX_AMD_STFT_GENERIC": "1"}}
-STFT_ROUTE_NFFTS = [8, 16, 32, 64, 128, 256, 512, 1000, 1024, 2048, 4096, 8192, 16384, 32768, 262144, 2**19, 2**20]
+STFT_ROUTE_NFFTS, ISTFT_ROUTE_NFFTS, STFT_ROUTE_ENTRIES = rcs.STFT_ROUTE_NFFTS, rcs.ISTFT_ROUTE_NFFTS, rcs.STFT_ROUTE_ENTRIES
 ISTFT_ROUTE_SWITCHES = {"default": {}, "ISTFT_FUSED=0": {"DSPTOOLBOX_AMD_ISTFT_FUSED": "0"},
                         "ISTFT_WAVE=0": {"DSPTOOLBOX_AMD_ISTFT_WAVE": "0"}, "ISTFT_CT=1": {"DSPTOOLBOX_AMD_ISTFT_CT": "1"}}
-ISTFT_ROUTE_NFFTS = [16, 256, 1000, 1024, 2048, 4096, 8192, 16384, 32768, 2**19]
-STFT_ROUTE_ENTRIES = {"stft": ("stft", "stft_f64", "stft_dev"), "istft": ("istft", "istft_f64", "istft_dev")}
+
+
+class _RouteJudge:
+    """The on_case hook of the route matrices: every output a matrix produces is held against the float64 oracle of
+    its problem (tests/route_oracles.py) -- a rejected call against the zeros its arrays were made with -- BEFORE the
+    launch names are compared with the table, so a test shows a wrong value and a changed route."""
+
+    def __init__(self, what):
+        self.what, self.worst, self.at, self.n, self.t0 = what, 0.0, None, 0, ros.seconds["oracle"]
+
+    def __call__(self, key, entry, q, out, routes):
+        if routes and routes[0].startswith("ERR"):
+            return ros.judge_rejected(key, entry, out)
+        frac = ros.judge_case(key, entry, q, out)
+        self.n += 1
+        if frac >= self.worst:
+            self.worst, self.at = frac, key
+        return frac
+
+    def report(self):
+        print(f"route oracle {self.what}: {self.n} outputs judged, worst error / bound {self.worst:.3f} at {self.at}; "
+              f"oracles took {ros.seconds['oracle'] - self.t0:.1f} s of CPU")
 
 
 def _route_call(ctx, fn, args):
@@ -2800,21 +2816,15 @@ def _route_call(ctx, fn, args):
     return sorted(ctx.routes()) if rc == 0 else [f"ERR{rc}"]
 
 
-def _stft_route_case(entry, nfft, short, detrend, n_ch, power=0):
-    """One short spectrogram through one C-ABI entry point -> (output array, launch names)."""
+def _stft_route_case(entry, q):
+    """One short spectrogram (route_cases.stft_problem) through one C-ABI entry point -> (output array, launch names)."""
     import ctypes as C
     from dsptoolbox_amd._lib import DeviceBuffer, DevicePlanar, get_context
     ctx = get_context()
     p = lambda a: a.ctypes.data_as(C.c_void_p)
-    W = 3 * nfft // 4 if short else nfft
-    hop, n = W // 2, 2 * nfft + 3000
-    n_frames, B = 1 + (n - W) // hop, nfft // 2 + 1
-    rng = np.random.default_rng(nfft + n_ch)
-    x = rng.standard_normal((n, n_ch)) * 0.5 + 0.25
-    xp = np.ascontiguousarray(x.T, dtype=np.float32)
-    w = (0.5 - 0.5 * np.cos(2 * np.pi * np.arange(W) / W)).astype(np.float32)
-    tail = (nfft, 0, n_frames)
-    par = (int(detrend), C.c_float(1.0 / W), C.c_float(0.5), power)
+    x, xp, w, W, hop, n, n_ch, n_frames, B = (q[k] for k in ("x", "xp", "w", "W", "hop", "n", "n_ch", "n_frames", "B"))
+    tail = (q["nfft"], q["pad_front"], n_frames)
+    par = (q["detrend"], C.c_float(q["scale"]), C.c_float(q["edge_scale"]), q["power"])
     ctx.routes()
     if entry.endswith("_dev"):
         dx, dw, do = DevicePlanar.from_planar(ctx, xp), DeviceBuffer.from_array(ctx, w), DeviceBuffer(ctx, B * n_frames * n_ch * 8)
@@ -2827,39 +2837,34 @@ def _stft_route_case(entry, nfft, short, detrend, n_ch, power=0):
     f64 = entry.endswith("_f64")
     out = np.zeros((B, n_frames, n_ch), np.complex128 if f64 else np.complex64)
     fn = ctx.lib.ds_stft_r2c_f64 if f64 else ctx.lib.ds_stft_r2c
-    routes = _route_call(ctx, fn, (p(np.ascontiguousarray(x) if f64 else xp), n, n_ch, W, hop, *tail, p(w), *par, p(out)))
+    routes = _route_call(ctx, fn, (p(x if f64 else xp), n, n_ch, W, hop, *tail, p(w), *par, p(out)))
     return out, routes
 
 
-def _istft_route_case(entry, nfft, short, step_div, n_ch):
-    """One short inverse transform through one C-ABI entry point -> (output array, launch names).  Three channels
-    give an odd output length: the one-sample overlap-add kernel as well as the four-sample one."""
+def _istft_route_case(entry, q):
+    """One short inverse transform (route_cases.istft_problem) through one C-ABI entry point -> (output array, launch
+    names)."""
     import ctypes as C
     from dsptoolbox_amd._lib import DeviceBuffer, get_context
     ctx = get_context()
     p = lambda a: a.ctypes.data_as(C.c_void_p)
-    W = 3 * nfft // 4 if short else nfft
-    step, total = nfft // step_div, 2 * nfft + 3000 + (n_ch == 3)
-    n_frames, B = 1 + (total - W) // step, nfft // 2 + 1
-    rng = np.random.default_rng(nfft + 10 * step_div + n_ch)
-    spec = rng.standard_normal((B, n_frames, n_ch)) + 1j * rng.standard_normal((B, n_frames, n_ch))
-    w = (0.5 - 0.5 * np.cos(2 * np.pi * np.arange(W) / W)).astype(np.float32)
-    mid = (n_ch, nfft, W, step, 0, n_frames)
+    spec, w, W, total, nfft, n_ch, n_frames, B = (q[k] for k in ("spec", "w", "W", "total", "nfft", "n_ch", "n_frames", "B"))
+    mid = (n_ch, nfft, W, q["step"], q["frame_offset"], q["n_frames_total"])
     ctx.routes()
     if entry.endswith("_dev"):
-        ds, dw = DeviceBuffer.from_array(ctx, spec.astype(np.complex64)), DeviceBuffer.from_array(ctx, w)
+        ds, dw = DeviceBuffer.from_array(ctx, q["spec32"]), DeviceBuffer.from_array(ctx, w)
         do = DeviceBuffer(ctx, n_ch * total * 4)
         routes = _route_call(ctx, ctx.lib.ds_istft_dev, (C.c_void_p(ds.ptr), B, n_frames, *mid, C.c_void_p(dw.ptr),
-                                                         C.c_float(1.0 / nfft), total, C.c_void_p(do.ptr), total))
+                                                         C.c_float(q["scale"]), total, C.c_void_p(do.ptr), total))
         out = do.to_array((n_ch, total), np.float32)
         for b in (ds, dw, do):
             b.free()
         return out, routes
     f64 = entry.endswith("_f64")
-    s = np.ascontiguousarray(spec.astype(np.complex128 if f64 else np.complex64))
+    s = np.ascontiguousarray(spec) if f64 else q["spec32"]
     out = np.zeros((total, n_ch) if f64 else (n_ch, total), np.float64 if f64 else np.float32)
     fn = ctx.lib.ds_istft_f64 if f64 else ctx.lib.ds_istft
-    routes = _route_call(ctx, fn, (p(s), B, n_frames, *mid, p(w), C.c_float(1.0 / nfft), total, p(out)))
+    routes = _route_call(ctx, fn, (p(s), B, n_frames, *mid, p(w), C.c_float(q["scale"]), total, p(out)))
     return out, routes
 
 
@@ -2871,15 +2876,13 @@ def _stft_route_matrix(kind, nffts, on_case=None, power=0):
         for short in (False, True):
             for a in ((False, True) if kind == "stft" else (2, 4)):  # detrend / step divisor
                 for n_ch in ((1, 3) if kind == "stft" else (1, 2, 3)):
+                    q = rcs.stft_problem(nfft, short, a, n_ch, power) if kind == "stft" else rcs.istft_problem(nfft, short, a, n_ch)
                     for entry in STFT_ROUTE_ENTRIES[kind]:
-                        if kind == "stft":
-                            out, routes = _stft_route_case(entry, nfft, short, a, n_ch, power)
-                        else:
-                            out, routes = _istft_route_case(entry, nfft, short, a, n_ch)
+                        out, routes = (_stft_route_case if kind == "stft" else _istft_route_case)(entry, q)
                         key = f"{entry}|{nfft}|{'short' if short else 'full'}|{int(a)}|{n_ch}"
                         seen[key] = routes
                         if on_case:
-                            on_case(key, out)
+                            on_case(key, entry, q, out, routes)
     return seen
 
 
@@ -2891,14 +2894,16 @@ def _stft_routes_vs_table(kind, switches, switch, nfft, monkeypatch):
     for k, v in switches[switch].items():
         monkeypatch.setenv(k, v)
     _lib.reset_context()
+    judged = _RouteJudge(f"{kind} nfft={nfft} {switch}")
     try:
-        seen = _stft_route_matrix(kind, (nfft,))
+        seen = _stft_route_matrix(kind, (nfft,), on_case=judged)
     finally:
         for k in switches[switch]:
             monkeypatch.delenv(k, raising=False)
         _lib.reset_context()
     # (every entry point of a kind runs the same kernels: the table has one row per kind)
     want = {k: table[f"{switch}|{kind}|{k.split('|', 1)[1]}"].split() for k in seen}
+    judged.report()
     assert seen == want
 
 
@@ -2913,8 +2918,35 @@ def test_stft_routes_per_length(switch, nfft, monkeypatch):
 @pytest.mark.parametrize("nfft", ISTFT_ROUTE_NFFTS)
 @pytest.mark.parametrize("switch", list(ISTFT_ROUTE_SWITCHES))
 def test_istft_routes_per_length(switch, nfft, monkeypatch):
-    """The same for every (length, window, step, channel count) of every inverse STFT entry point."""
+    """The same for every (length, window, step, channel count) of every inverse STFT entry point.
+
+    (Judging the values found a fault here: "2048|full|2|2" -- five frames of two channels on istft@wave and istft@fused --
+    was off by 2.3e-4 of the row rms, 14 times its bound, and held non-zero samples behind the last frame; see
+    test_istft_last_frame_dropped_vs_oracle.  It is now within 0.27 of the bound.)"""
     _stft_routes_vs_table("istft", ISTFT_ROUTE_SWITCHES, switch, nfft, monkeypatch)
+
+
+@pytest.mark.parametrize("nfft", [256, 1024, 2048])  # (lengths of the matrix: their bounds are recorded)
+@pytest.mark.parametrize("switch", ["default", "ISTFT_WAVE=0", "ISTFT_FUSED=0"])
+def test_istft_last_frame_dropped_vs_oracle(switch, nfft, monkeypatch):
+    """The 50 % overlap problems of test_istft_routes_per_length without their last frame: 25 and 7 frames at 256 and
+    1024 points, where the matrix has even frame counts only, and 4 frames at 2048 points, the EVEN count the matrix
+    lacks there (it has 5).  The fused kernels (istft@wave, istft@fused) transform frames in pairs; a last pair without
+    a second frame used to overlap-add the transform's rounding of its first frame (the imaginary part, about 1e-8 of
+    the frame) as if it were a frame, and behind the last frame the envelope's floor of 1e-4 multiplies that by 1e4.
+    New launches, because no case of the matrix reaches this below 2048 points; under the matrix's bounds."""
+    def run():
+        worst = 0.0
+        for n_ch in (2, 3):
+            q = rcs.istft_problem(nfft, False, 2, n_ch, drop_last=True)
+            for entry in STFT_ROUTE_ENTRIES["istft"]:
+                out, routes = _istft_route_case(entry, q)
+                if switch != "ISTFT_FUSED=0":
+                    assert routes == ["istft@wave" if switch == "default" else "istft@fused"], routes
+                worst = max(worst, ros.judge_case(f"{entry}|{nfft}|odd|{n_ch}", entry, q, out))
+        return worst
+    worst = _routes_under(ISTFT_ROUTE_SWITCHES, switch, run, monkeypatch)
+    print(f"route oracle istft nfft={nfft} without the last frame, {switch}: worst error / bound {worst:.3f}")
 
 
 # ---- which kernel family each FIR, rFFT, deconvolution and CSM call runs on, per entry point ------------------------
@@ -2950,24 +2982,22 @@ FIR_ROUTE_SWITCHES = {"default": {},
                       "FIR_4K=0": {"DSPTOOLBOX_AMD_FIR_4K": "0"}, "FIR_4K=1": {"DSPTOOLBOX_AMD_FIR_4K": "1"},
                       "FIR_3PERCU=0": {"DSPTOOLBOX_AMD_FIR_3PERCU": "0"}, "FIR_STAGE=1": {"DSPTOOLBOX_AMD_FIR_STAGE": "1"},
                       "FIR_DIRECT=0": {"DSPTOOLBOX_AMD_FIR_DIRECT": "0"}}
-FIR_ROUTE_TAPS = [1, 2, 64, 1024, 1025, 2049, 4097, 8193, 2**15 + 1]
+FIR_ROUTE_TAPS, FIR_ROUTE_ENTRIES = rcs.FIR_ROUTE_TAPS, rcs.FIR_ROUTE_ENTRIES
 FIR_ROUTE_MODES = {"parallel": backend.DS_FB_PARALLEL, "summed": backend.DS_FB_SUMMED,
                    "sequential": backend.DS_FB_SEQUENTIAL}
-# (entry, output row stride): "odd" = a device output stride that is not a multiple of 4 (no plain 16k blocks)
-FIR_ROUTE_ENTRIES = (("fir_ola", "n"), ("fir_ola_f64", "n"), ("fir_ola_dev", "n"), ("fir_ola_dev", "odd"))
+# (FIR_ROUTE_ENTRIES: (entry, output row stride); "odd" = a device output stride that is not a multiple of 4)
 
 
-def _fir_route_case(entry, ld, n_taps, n, n_filt, mode, n_ch=3):
-    """One filter bank through one C-ABI entry point -> (output array, launch names).  n may be 0 (rejected)."""
+def _fir_route_case(entry, ld, q):
+    """One filter bank (route_cases.fir_problem) through one C-ABI entry point -> (output array, launch names).  n may
+    be 0 (rejected)."""
     import ctypes as C
     from dsptoolbox_amd._lib import DeviceBuffer, DevicePlanar, get_context
     ctx = get_context()
     p = lambda a: a.ctypes.data_as(C.c_void_p)
-    rng = np.random.default_rng(n_taps + n + n_filt)
-    x = rng.standard_normal((max(n, 1), n_ch)) * 0.5 + 0.25
-    taps = (rng.standard_normal((n_filt, n_taps)) / np.sqrt(n_taps)).astype(np.float32)
-    m, n_out, ns = FIR_ROUTE_MODES[mode], (n_filt if mode == "parallel" else 1), max(n, 1)
-    xp = np.ascontiguousarray(x.T, dtype=np.float32)
+    x, xp, taps, n_taps, n, ns, n_filt, n_ch, n_out = (q[k] for k in ("x", "xp", "taps", "n_taps", "n", "ns", "n_filt",
+                                                                      "n_ch", "n_out"))
+    m = FIR_ROUTE_MODES[q["mode"]]
     ctx.routes()
     if entry.endswith("_dev"):
         ld_y = ns | 1 if ld == "odd" else ns
@@ -2981,7 +3011,7 @@ def _fir_route_case(entry, ld, n_taps, n, n_filt, mode, n_ch=3):
     f64 = entry.endswith("_f64")
     out = np.zeros((n_out, ns, n_ch), np.float64) if f64 else np.zeros((n_out, n_ch, ns), np.float32)
     fn = ctx.lib.ds_fir_ola_f64 if f64 else ctx.lib.ds_fir_ola
-    routes = _route_call(ctx, fn, (p(np.ascontiguousarray(x) if f64 else xp), n_ch, n, p(taps), n_filt, n_taps, m, p(out)))
+    routes = _route_call(ctx, fn, (p(x if f64 else xp), n_ch, n, p(taps), n_filt, n_taps, m, p(out)))
     return out, routes
 
 
@@ -2991,12 +3021,13 @@ def _fir_route_matrix(taps_list, modes, on_case=None):
         for n in (n_taps - 1, 5000, 50000):  # shorter than the filter, a few blocks, several 16k blocks
             for n_filt in (1, 3):
                 for mode in modes:
+                    q = rcs.fir_problem(n_taps, n, n_filt, mode)
                     for entry, ld in FIR_ROUTE_ENTRIES:
-                        out, routes = _fir_route_case(entry, ld, n_taps, n, n_filt, mode)
+                        out, routes = _fir_route_case(entry, ld, q)
                         key = f"{entry}|{n_taps}|{n}|{n_filt}|{mode}|{ld}"
                         seen[key] = routes
                         if on_case:
-                            on_case(key, out)
+                            on_case(key, entry, q, out, routes)
     return seen
 
 
@@ -3007,11 +3038,13 @@ def test_fir_routes_per_shape(switch, n_taps, monkeypatch):
     it launched when the table was recorded.  The switches choose among the parallel mode's kernels; the summed and
     sequential modes run the parallel route on combined taps, so they are pinned with the default switches only."""
     modes = list(FIR_ROUTE_MODES) if switch == "default" else ["parallel"]
-    seen = _routes_under(FIR_ROUTE_SWITCHES, switch, lambda: _fir_route_matrix((n_taps,), modes), monkeypatch)
+    judged = _RouteJudge(f"fir taps={n_taps} {switch}")
+    seen = _routes_under(FIR_ROUTE_SWITCHES, switch, lambda: _fir_route_matrix((n_taps,), modes, on_case=judged), monkeypatch)
+    judged.report()
     _routes_vs_table("fir_routes.json", "fir", switch, seen)
 
 
-XFORM_ROUTE_NFFTS = [1, 2, 3, 4, 8, 1000, 1024, 8192, 16384, 32768, 100000, 2**20]
+XFORM_ROUTE_NFFTS = rcs.XFORM_ROUTE_NFFTS
 DECONV_ROUTE_SWITCHES = {"default": {}, "DECONV_GENERIC": {"DSPTOOLBOX_AMD_DECONV_GENERIC": "1"},
                          "DECONV_2PERCU": {"DSPTOOLBOX_AMD_DECONV_2PERCU": "1"},
                          "DECONV_PERSIST=0": {"DSPTOOLBOX_AMD_DECONV_PERSIST": "0"},
@@ -3019,20 +3052,14 @@ DECONV_ROUTE_SWITCHES = {"default": {}, "DECONV_GENERIC": {"DSPTOOLBOX_AMD_DECON
                                                              "DSPTOOLBOX_AMD_DECONV_4PERCU": "0"}}
 
 
-def _xform_signal(n_fft, short, n_rows, seed):
-    """(n_samples, rows x n_samples float64): "full" = n_fft samples, "short" = half of them (rounded up)."""
-    n = (n_fft + 1) // 2 if short else n_fft
-    return n, np.random.default_rng(seed).standard_normal((n_rows, n)) * 0.5 + 0.25
-
-
-def _rfft_route_case(entry, n_fft, short, n_ch):
-    """One whole-signal spectrum through one C-ABI entry point -> (output array, launch names)."""
+def _rfft_route_case(entry, q):
+    """One whole-signal spectrum (route_cases.rfft_problem) through one C-ABI entry point -> (output array, launch
+    names)."""
     import ctypes as C
     from dsptoolbox_amd._lib import DeviceBuffer, DevicePlanar, get_context
     ctx = get_context()
     p = lambda a: a.ctypes.data_as(C.c_void_p)
-    n, x = _xform_signal(n_fft, short, n_ch, n_fft + n_ch)
-    xp, B, scale = np.ascontiguousarray(x, dtype=np.float32), n_fft // 2 + 1, C.c_float(1.0 / n_fft)
+    x, xp, n, n_fft, n_ch, B, scale = q["x"], q["xp"], q["n"], q["n_fft"], q["n_ch"], q["B"], C.c_float(q["scale"])
     ctx.routes()
     if entry.endswith("_dev"):
         dx, do = DevicePlanar.from_planar(ctx, xp), DeviceBuffer(ctx, B * n_ch * 8)
@@ -3048,19 +3075,15 @@ def _rfft_route_case(entry, n_fft, short, n_ch):
     return out, routes
 
 
-def _deconv_route_case(entry, n_fft, short, r_per_channel, n_items, n_ch=3):
-    """One batch of deconvolutions through one C-ABI entry point -> (output array, launch names).  ds_deconv_f64 takes
-    one item."""
+def _deconv_route_case(entry, q):
+    """One batch of deconvolutions (route_cases.deconv_problem) through one C-ABI entry point -> (output array, launch
+    names).  ds_deconv_f64 takes one item."""
     import ctypes as C
     from dsptoolbox_amd._lib import DeviceBuffer, DevicePlanar, get_context
     ctx = get_context()
     p = lambda a: a.ctypes.data_as(C.c_void_p)
-    n, y = _xform_signal(n_fft, short, n_items * n_ch, n_fft + 10 * n_items + r_per_channel)
-    B, n_out = n_fft // 2 + 1, n_fft
-    rng = np.random.default_rng(n_fft)
-    r = (rng.standard_normal(((n_ch if r_per_channel else 1), B)) + 1j * rng.standard_normal(((n_ch if r_per_channel else 1), B)))
-    r = r.astype(np.complex64)
-    yp = np.ascontiguousarray(y, dtype=np.float32)
+    y, yp, r, n, n_fft, n_ch, n_items, r_per_channel, n_out = (q[k] for k in ("y", "yp", "r", "n", "n_fft", "n_ch", "n_items",
+                                                                             "r_per_channel", "n_out"))
     ctx.routes()
     if entry.endswith("_dev"):
         dy, dr, do = DevicePlanar.from_planar(ctx, yp), DeviceBuffer.from_array(ctx, r), DeviceBuffer(ctx, yp.shape[0] * n_out * 4)
@@ -3085,12 +3108,13 @@ def _rfft_route_matrix(nffts, on_case=None):
     for n_fft in nffts:
         for short in (False, True):
             for n_ch in (1, 3):
+                q = rcs.rfft_problem(n_fft, short, n_ch)
                 for entry in ("rfft", "rfft_f64", "rfft_dev"):
-                    out, routes = _rfft_route_case(entry, n_fft, short, n_ch)
+                    out, routes = _rfft_route_case(entry, q)
                     key = f"{entry}|{n_fft}|{'short' if short else 'full'}|{n_ch}"
                     seen[key] = routes
                     if on_case:
-                        on_case(key, out)
+                        on_case(key, entry, q, out, routes)
     return seen
 
 
@@ -3100,12 +3124,13 @@ def _deconv_route_matrix(nffts, on_case=None):
         for short in (False, True):
             for rpc in (0, 1):
                 for n_items in (1, 2):
+                    q = rcs.deconv_problem(n_fft, short, rpc, n_items)
                     for entry in ("deconv", "deconv_f64", "deconv_dev") if n_items == 1 else ("deconv", "deconv_dev"):
-                        out, routes = _deconv_route_case(entry, n_fft, short, rpc, n_items)
+                        out, routes = _deconv_route_case(entry, q)
                         key = f"{entry}|{n_fft}|{'short' if short else 'full'}|{rpc}|{n_items}"
                         seen[key] = routes
                         if on_case:
-                            on_case(key, out)
+                            on_case(key, entry, q, out, routes)
     return seen
 
 
@@ -3113,7 +3138,9 @@ def _deconv_route_matrix(nffts, on_case=None):
 def test_rfft_routes_per_length(n_fft, monkeypatch):
     """Each (length, signal length, channel count) of every whole-signal rFFT entry point launches the kernels it
     launched when the table was recorded."""
-    seen = _routes_under({"default": {}}, "default", lambda: _rfft_route_matrix((n_fft,)), monkeypatch)
+    judged = _RouteJudge(f"rfft n_fft={n_fft}")
+    seen = _routes_under({"default": {}}, "default", lambda: _rfft_route_matrix((n_fft,), on_case=judged), monkeypatch)
+    judged.report()
     _routes_vs_table("xform_routes.json", "rfft", "default", seen)
 
 
@@ -3121,38 +3148,38 @@ def test_rfft_routes_per_length(n_fft, monkeypatch):
 @pytest.mark.parametrize("switch", list(DECONV_ROUTE_SWITCHES))
 def test_deconv_routes_per_length(switch, n_fft, monkeypatch):
     """The same for every (length, signal length, inverse per channel, item count) of every deconvolution entry."""
-    seen = _routes_under(DECONV_ROUTE_SWITCHES, switch, lambda: _deconv_route_matrix((n_fft,)), monkeypatch)
+    judged = _RouteJudge(f"deconv n_fft={n_fft} {switch}")
+    seen = _routes_under(DECONV_ROUTE_SWITCHES, switch, lambda: _deconv_route_matrix((n_fft,), on_case=judged), monkeypatch)
+    judged.report()
     _routes_vs_table("xform_routes.json", "deconv", switch, seen)
 
 
 CSM_ROUTE_SWITCHES = {"default": {}, "CSM_GENERIC": {"DSPTOOLBOX_AMD_CSM_GENERIC": "1"},
                       "CSM_F32": {"DSPTOOLBOX_AMD_CSM_F32": "1"}, "CSM_CHUNKS=3": {"DSPTOOLBOX_AMD_CSM_CHUNKS": "3"}}
-CSM_ROUTE_WINDOWS = [32, 1000, 1024, 4096, 16384, 32768]
+CSM_ROUTE_WINDOWS = rcs.CSM_ROUTE_WINDOWS
 
 
-def _csm_route_case(entry, W, average, n_ch, n_frames, bins):
-    """One cross-spectral matrix through one C-ABI entry point -> (output array, launch names).  bins: "all", or
-    "part" (ds_csm_bins_dev: a quarter of the bins from the first quarter on)."""
+def _csm_route_case(entry, q):
+    """One cross-spectral matrix (route_cases.csm_problem) through one C-ABI entry point -> (output array, launch
+    names).  ds_csm_bins_dev: the problem's bin range."""
     import ctypes as C
     from dsptoolbox_amd._lib import DeviceBuffer, DevicePlanar, get_context
     ctx = get_context()
     p = lambda a: a.ctypes.data_as(C.c_void_p)
-    hop = W // 2
-    n, nb = (n_frames - 1) * hop + W, W // 2 + 1
-    x = np.random.default_rng(W + n_ch + n_frames).standard_normal((n, n_ch)) * 0.5 + 0.25
-    xp = np.ascontiguousarray(x.T, dtype=np.float32)
-    w = (0.5 - 0.5 * np.cos(2 * np.pi * np.arange(W) / W)).astype(np.float32)
-    b0, bc = (nb // 4, max(1, nb // 4)) if bins == "part" else (0, nb)
+    x, xp, w, W, hop, n, n_ch, n_frames, nb, b0, bc = (q[k] for k in ("x", "xp", "w", "W", "hop", "n", "n_ch", "n_frames",
+                                                                      "nb", "b0", "bc"))
+    average = q["average"]
     mid = (W, hop, n_frames)
-    fin = (0, C.c_double(1.0 / W), C.c_double(2.0), 1)  # amp_sqrt, norm_scale, factor, halve_edges
+    # amp_sqrt, norm_scale, factor, halve_edges
+    fin = (q["amp_sqrt"], C.c_double(q["norm_scale"]), C.c_double(q["factor"]), q["halve_edges"])
     ctx.routes()
     if entry.endswith("_dev"):
         dx, dw, do = DevicePlanar.from_planar(ctx, xp), DeviceBuffer.from_array(ctx, w), DeviceBuffer(ctx, bc * n_ch * n_ch * 8)
         if entry == "csm_bins_dev":
             routes = _route_call(ctx, ctx.lib.ds_csm_bins_dev, (C.c_void_p(dx.ptr), n_ch, dx.ld, n, *mid, C.c_void_p(dw.ptr),
-                                                                1, *fin, b0, bc, C.c_void_p(do.ptr)))
+                                                                q["detrend"], *fin, b0, bc, C.c_void_p(do.ptr)))
         else:
-            routes = _route_call(ctx, ctx.lib.ds_csm_dev, (C.c_void_p(dx.ptr), n_ch, dx.ld, n, *mid, C.c_void_p(dw.ptr), 1,
+            routes = _route_call(ctx, ctx.lib.ds_csm_dev, (C.c_void_p(dx.ptr), n_ch, dx.ld, n, *mid, C.c_void_p(dw.ptr), q["detrend"],
                                                            backend.DS_AVG[average], *fin, C.c_void_p(do.ptr)))
         out = do.to_array((bc, n_ch, n_ch), np.complex64)
         for b in (dx.owner, dw, do):
@@ -3161,7 +3188,7 @@ def _csm_route_case(entry, W, average, n_ch, n_frames, bins):
     f64 = entry.endswith("_f64")
     out = np.zeros((nb, n_ch, n_ch), np.complex64)
     fn = ctx.lib.ds_csm_f64 if f64 else ctx.lib.ds_csm
-    routes = _route_call(ctx, fn, (p(np.ascontiguousarray(x) if f64 else xp), n_ch, n, *mid, p(w), 1, backend.DS_AVG[average],
+    routes = _route_call(ctx, fn, (p(x if f64 else xp), n_ch, n, *mid, p(w), q["detrend"], backend.DS_AVG[average],
                                    *fin, p(out)))
     return out, routes
 
@@ -3180,11 +3207,12 @@ def _csm_route_matrix(windows, on_case=None):
                     if average == "mean":
                         cases += [("csm_bins_dev", "all"), ("csm_bins_dev", "part")]
                     for entry, bins in cases:
-                        out, routes = _csm_route_case(entry, W, average, n_ch, n_frames, bins)
+                        q = rcs.csm_problem(W, average, n_ch, n_frames, bins)
+                        out, routes = _csm_route_case(entry, q)
                         key = f"{entry}|{W}|{average}|{n_ch}|{n_frames}|{bins}"
                         seen[key] = routes
                         if on_case:
-                            on_case(key, out)
+                            on_case(key, entry, q, out, routes)
     return seen
 
 
@@ -3193,7 +3221,9 @@ def _csm_route_matrix(windows, on_case=None):
 def test_csm_routes_per_shape(switch, W, monkeypatch):
     """Each (window, averaging, channel count, frame count, bin range) of every CSM entry point launches the kernels
     it launched when the table was recorded."""
-    seen = _routes_under(CSM_ROUTE_SWITCHES, switch, lambda: _csm_route_matrix((W,)), monkeypatch)
+    judged = _RouteJudge(f"csm W={W} {switch}")
+    seen = _routes_under(CSM_ROUTE_SWITCHES, switch, lambda: _csm_route_matrix((W,), on_case=judged), monkeypatch)
+    judged.report()
     _routes_vs_table("csm_routes.json", "csm", switch, seen)
 
 
