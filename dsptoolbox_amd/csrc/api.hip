@@ -420,6 +420,28 @@ static int carve(ds_ctx* c, void** buf, size_t* cap, F&& lay) {
     return DS_OK;
 }
 
+// How a host entry runs its _dev twin.  Each of its arrays is one Staged piece: `count` elements of `elem` bytes, copied
+// from `src` before the run and to `dst` after it where these are given (an optional array the caller left out is only
+// carved: it keeps its place).  staged() carves the pieces out of c->io in list order, uploads, calls run(d) with d[i] the
+// device address of piece i, and downloads.  The entry validates before it calls this.
+struct Staged { size_t elem, count; const void* src; void* dst; };
+template <class F>
+static int staged(ds_ctx* c, std::initializer_list<Staged> pieces, F&& run) {
+    const Staged* p = pieces.begin();
+    const size_t n = pieces.size();
+    void* d[8];
+    if (n > 8) return fail(c, DS_ERR_ARG, "staged: more than 8 pieces");
+    CHK(carve(c, &c->io, &c->io_bytes, [&](Carver& cv) {
+        for (size_t i = 0; i < n; ++i) d[i] = cv.take<char>(p[i].elem * p[i].count);
+    }));
+    for (size_t i = 0; i < n; ++i)
+        if (p[i].src) CHK(ds_upload(c, d[i], p[i].src, p[i].elem * p[i].count));
+    CHK(run(d));
+    for (size_t i = 0; i < n; ++i)
+        if (p[i].dst) CHK(ds_download(c, p[i].dst, d[i], p[i].elem * p[i].count));
+    return DS_OK;
+}
+
 static int prof_event(ds_ctx* c, hipEvent_t* ev) {
     if (!c->prof_pool.empty()) {
         *ev = c->prof_pool.back();
@@ -1333,13 +1355,20 @@ extern "C" int ds_istft_dev(ds_ctx* c, const ds_c32* stft, int n_bins, int n_fra
 }
 
 // ---- band powers of a spectrogram (mel spectrogram / MFCC) ----------------------------------
+// what ds_band_power and its _dev twin both refuse (the pointers are the host's or the device's)
+static int band_power_check(ds_ctx* c, const void* stft, const void* weights, const void* band_start, const void* band_stop,
+                            const void* out, int n_bins, int64_t n_fc, int n_bands) {
+    if (!c || !stft || !weights || !band_start || !band_stop || !out)
+        return fail(c, DS_ERR_ARG, "ds_band_power: null argument");
+    if (n_bins <= 0 || n_fc <= 0 || n_bands <= 0) return fail(c, DS_ERR_ARG, "ds_band_power: bad shape");
+    return DS_OK;
+}
+
 extern "C" int ds_band_power_dev(ds_ctx* c, const ds_c32* stft, int n_bins, int64_t n_fc, const float* weights,
                                  const int* band_start, const int* band_stop, int n_bands, int to_db,
                                  int dct_abs, float* out) {
-    if (!c || !stft || !weights || !band_start || !band_stop || !out)
-        return fail(c, DS_ERR_ARG, "ds_band_power: null argument");
-    if (n_bins <= 0 || n_fc <= 0 || n_bands <= 0 || n_bands > 65535)
-        return fail(c, DS_ERR_ARG, "ds_band_power: bad shape");
+    CHK(band_power_check(c, stft, weights, band_start, band_stop, out, n_bins, n_fc, n_bands));
+    if (n_bands > 65535) return fail(c, DS_ERR_ARG, "ds_band_power: bad shape");  // (the grid's y extent)
     float* dst = out;
     if (dct_abs) {
         CHK(reserve(c, &c->ws, &c->ws_bytes, sizeof(float) * (size_t)n_bands * n_fc));
@@ -1358,26 +1387,14 @@ extern "C" int ds_band_power_dev(ds_ctx* c, const ds_c32* stft, int n_bins, int6
 extern "C" int ds_band_power(ds_ctx* c, const ds_c32* stft, int n_bins, int64_t n_fc, const float* weights,
                              const int* band_start, const int* band_stop, int n_bands, int to_db, int dct_abs,
                              float* out) {
-    if (!c || !stft || !weights || !band_start || !band_stop || !out)
-        return fail(c, DS_ERR_ARG, "ds_band_power: null argument");
-    if (n_bins <= 0 || n_fc <= 0 || n_bands <= 0) return fail(c, DS_ERR_ARG, "ds_band_power: bad shape");
-    const size_t ns = (size_t)n_bins * n_fc, nw = (size_t)n_bands * n_bins, no = (size_t)n_bands * n_fc;
-    float2* dx;
-    float *dw, *dout;
-    int *d0, *d1;
-    CHK(carve(c, &c->io, &c->io_bytes, [&](Carver& cv) {
-        dx = cv.take<float2>(ns);
-        dw = cv.take<float>(nw);
-        d0 = cv.take<int>(n_bands);
-        d1 = cv.take<int>(n_bands);
-        dout = cv.take<float>(no);
-    }));
-    CHK(ds_upload(c, dx, stft, ns * 8));
-    CHK(ds_upload(c, dw, weights, nw * 4));
-    CHK(ds_upload(c, d0, band_start, (size_t)n_bands * 4));
-    CHK(ds_upload(c, d1, band_stop, (size_t)n_bands * 4));
-    CHK(ds_band_power_dev(c, (const ds_c32*)dx, n_bins, n_fc, dw, d0, d1, n_bands, to_db, dct_abs, dout));
-    return ds_download(c, out, dout, no * 4);
+    CHK(band_power_check(c, stft, weights, band_start, band_stop, out, n_bins, n_fc, n_bands));
+    const size_t ns = (size_t)n_bins * n_fc, nw = (size_t)n_bands * n_bins, no = (size_t)n_bands * n_fc, nbd = n_bands;
+    return staged(c, {{8, ns, stft, nullptr}, {4, nw, weights, nullptr}, {4, nbd, band_start, nullptr},
+                      {4, nbd, band_stop, nullptr}, {4, no, nullptr, out}},
+                  [&](void* const* d) {
+                      return ds_band_power_dev(c, (const ds_c32*)d[0], n_bins, n_fc, (const float*)d[1], (const int*)d[2],
+                                               (const int*)d[3], n_bands, to_db, dct_abs, (float*)d[4]);
+                  });
 }
 
 // ---- Welch -----------------------------------------------------------------
@@ -1910,22 +1927,84 @@ extern "C" int ds_welch_psd_dev(ds_ctx* c, const float* x, int n_cx, int64_t ldx
     return welch_dev(c, {"ds_welch_psd_dev", PSD, x, n_cx, ldx, nullptr, 0, 0, n_samples, W, hop, n_frames, window, detrend,
                          average, 0, amp_sqrt, norm_scale, factor, halve_edges, nullptr, psd});
 }
+// ---- Welch in float64 end to end (kernels_welch_f64.hpp) ---------------------------------------------------------
+// The three entries below take host arrays in the reference's own layouts, (samples, channels) float64, and answer in
+// complex128 / float64.  Each fills one X64Call, has x64_check judge it (and adds the limits only it has), carves its pieces
+// out of c->io, fills the tables, has x64_frames upload and transform each signal, launches its own mean or median kernel
+// on x64_finish's FinishPar, downloads and synchronises once.  `who` is the entry's name in its error messages.
+static const int kMaxX64Window = 262144;
+static const int64_t kMaxX64PlanarSamples = (int64_t)0x7fffffff * 32;  // w64::k_planar: 32 samples per workgroup of grid.x
+
+// ds_welch_tf_x64: out (tf) and coh of y against x, n_cx = 1 or n_cy.  ds_welch_spec_x64: auto spectra of x or, with y, the
+// cross spectra conj(X_i) Y_i (n_cy = 0 or n_cx); ds_csm_x64: the matrix of x (y null).  These two: coh null, mode 0.
+struct X64Call {
+    const char* who;
+    const double* x; int n_cx; const double* y; int n_cy; int64_t n_samples; int W, hop, n_frames;
+    const double* window; int detrend, average, mode, amp_sqrt; double norm_scale, factor; int halve_edges;
+    double *out, *coh;
+    int nb() const { return W / 2 + 1; }
+    bool median() const { return average == DS_AVG_MEDIAN; }
+};
+// What all three refuse.  n_spectra_x / n_spectra_y: the channels of x and y whose frame spectra the call holds: 2 GiB at most
+static int x64_check(ds_ctx* c, const X64Call& q, int n_spectra_x, int n_spectra_y) {
+    const std::string w(q.who);
+    if (!c || !q.x || !q.window || !q.out) return fail(c, DS_ERR_ARG, w + ": null argument");
+    if (q.average != DS_AVG_MEAN && q.average != DS_AVG_MEDIAN)
+        return fail(c, DS_ERR_ARG, w + ": average must be mean (0) or median (1)");
+    if (q.median() && q.n_frames > 4096)
+        return fail(c, DS_ERR_UNSUP, w + ": median averaging over more than 4096 frames (use the fp32 entry point)");
+    if (n_spectra_x <= 0 || n_spectra_y < 0 || q.n_samples <= 0 || q.hop <= 0 || q.hop > q.W || q.n_frames <= 0)
+        return fail(c, DS_ERR_ARG, w + ": bad shape");
+    if (!is_pow2(q.W) || q.W < 8 || q.W > kMaxX64Window)
+        return fail(c, DS_ERR_UNSUP, w + ": window length must be a power of two in [8, 262144]");
+    if (((size_t)n_spectra_x + (size_t)n_spectra_y) * q.n_frames * q.nb() * sizeof(double2) > ((size_t)2 << 30))
+        return fail(c, DS_ERR_UNSUP, w + ": problem too large for the float64 route (use the fp32 entry point)");
+    return DS_OK;
+}
+// the finish of the mean over the frames, or of the median with the reference's bias correction
+static FinishPar x64_finish(const X64Call& q, int nb) {
+    const int nbias = (q.n_frames & 1) ? q.n_frames : q.n_frames - 1;
+    return {q.median() ? q.norm_scale * (double)std::max(1, nbias) : q.norm_scale / (double)q.n_frames, q.factor, q.halve_edges,
+            q.amp_sqrt, nb};
+}
+
+// planar[n_ch][n_samples] of the device-resident (samples, channels) array dsig
+static int x64_planar(ds_ctx* c, const double* dsig, int64_t n_samples, int n_ch, double* planar) {
+    if (n_samples > kMaxX64PlanarSamples)
+        return fail(c, DS_ERR_UNSUP, "float64 Welch route: signal too long for the long-window kernels");
+    hipLaunchKernelGGL(w64::k_planar, dim3((unsigned)((n_samples + 31) / 32), (unsigned)((n_ch + 31) / 32)), dim3(256), 0, c->stream,
+                       dsig, n_samples, n_ch, planar);
+    HIPCHK(c, hipGetLastError());
+    return DS_OK;
+}
+
+// the float64 window and twiddle tables of the x64 entries: carved by take_x64_tables, filled by x64_tables
+struct X64Tables {
+    double* dw;
+    double2* tw;
+};
+static X64Tables take_x64_tables(Carver& cv, int W) { return {cv.take<double>(W), cv.take<double2>(W / 2)}; }
+static int x64_tables(ds_ctx* c, const X64Tables& t, const double* window, int W) {
+    HIPCHK(c, hipMemcpyAsync(t.dw, window, (size_t)W * 8, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(w64::k_twiddles, dim3((W / 2 + 255) / 256), dim3(256), 0, c->stream, t.tw, W / 2);
+    HIPCHK(c, hipGetLastError());
+    return DS_OK;
+}
+
 // float64 frame spectra of a device-resident (samples, channels) float64 array: W <= 16384 one workgroup per
 // (frame, channel); 2^15 ... 2^18 one per (frame, class, channel) + the split (class spectra in the workspace)
-static const int kMaxX64Window = 262144;
-static int x64_launch_frames(ds_ctx* c, const double* dsig, int n_ch, int64_t n_samples, int W, int hop, int n_frames,
-                             int detrend, const double* dw, const double2* tw, double2* spec) {
+static int x64_launch_frames(ds_ctx* c, const X64Call& q, const X64Tables& t, const double* dsig, int n_ch, double2* spec) {
+    const int W = q.W, n_frames = q.n_frames;
+    const int64_t n_samples = q.n_samples;
     int lg = 0;
     while ((1 << lg) < W) ++lg;
-    w64::FrameArgs fa{dsig, n_samples, n_ch, W, lg, hop, n_frames, detrend, dw, tw, spec, n_ch, 1};
+    w64::FrameArgs fa{dsig, n_samples, n_ch, W, lg, q.hop, n_frames, q.detrend, t.dw, t.tw, spec, n_ch, 1};
     if (W <= 16384) {
         // four channels or more: read a planar copy (one 8-byte value per 32-byte sector otherwise)
-        if (n_ch >= 4 && (n_samples + 31) / 32 <= 0x7fffffff) {
+        if (n_ch >= 4 && n_samples <= kMaxX64PlanarSamples) {
             CHK(reserve(c, &c->ws, &c->ws_bytes, sizeof(double) * (size_t)n_ch * n_samples));
             double* planar = (double*)c->ws;
-            hipLaunchKernelGGL(w64::k_planar, dim3((unsigned)((n_samples + 31) / 32), (unsigned)((n_ch + 31) / 32)), dim3(256), 0,
-                               c->stream, dsig, n_samples, n_ch, planar);
-            HIPCHK(c, hipGetLastError());
+            CHK(x64_planar(c, dsig, n_samples, n_ch, planar));
             fa.sig = planar;
             fa.s_stride = 1;
             fa.c_stride = n_samples;
@@ -1946,50 +2025,31 @@ static int x64_launch_frames(ds_ctx* c, const double* dsig, int n_ch, int64_t n_
         zc = cv.take<double2>((size_t)n_ch * n_frames * (W / 2));
         planar = cv.take<double>((size_t)n_ch * n_samples);
     }));
-    if ((n_samples + 31) / 32 > 0x7fffffff) return fail(c, DS_ERR_UNSUP, "float64 Welch route: signal too long for the long-window kernels");
-    hipLaunchKernelGGL(w64::k_planar, dim3((unsigned)((n_samples + 31) / 32), (unsigned)((n_ch + 31) / 32)), dim3(256), 0, c->stream,
-                       dsig, n_samples, n_ch, planar);
-    HIPCHK(c, hipGetLastError());
+    CHK(x64_planar(c, dsig, n_samples, n_ch, planar));  // (these kernels read nothing else: an over-long signal ends here)
     w64::LongArgs la{fa, rc, lg_rc, zc, planar};
     CHK(launch(c, "welch_f64_frames@long", w64::k_frames_cls, dim3((unsigned)(n_frames * rc), n_ch), 256,
                (size_t)w64::LONG_M * 16 + 256 * 8, la));
     return launch(c, "welch_f64_split", w64::k_split, dim3((W / 2 + 1 + 255) / 256, n_frames, n_ch), 256, 0, la);
 }
-
-// the float64 window and twiddle tables of the x64 entries: carved by take_x64_tables, filled by x64_tables
-struct X64Tables {
-    double* dw;
-    double2* tw;
-};
-static X64Tables take_x64_tables(Carver& cv, int W) { return {cv.take<double>(W), cv.take<double2>(W / 2)}; }
-static int x64_tables(ds_ctx* c, const X64Tables& t, const double* window, int W) {
-    HIPCHK(c, hipMemcpyAsync(t.dw, window, (size_t)W * 8, hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(w64::k_twiddles, dim3((W / 2 + 255) / 256), dim3(256), 0, c->stream, t.tw, W / 2);
-    HIPCHK(c, hipGetLastError());
-    return DS_OK;
+// the same of a host array sig: uploaded to dsig first
+static int x64_frames(ds_ctx* c, const X64Call& q, const X64Tables& t, const double* sig, double* dsig, int n_ch, double2* spec) {
+    HIPCHK(c, hipMemcpyAsync(dsig, sig, (size_t)q.n_samples * n_ch * 8, hipMemcpyHostToDevice, c->stream));
+    return x64_launch_frames(c, q, t, dsig, n_ch, spec);
 }
 
-// float64 end to end (kernels_welch_f64.hpp): host arrays in the reference's own layout
 extern "C" int ds_welch_tf_x64(ds_ctx* c, const double* x, int n_cx, const double* y, int n_cy,
                                int64_t n_samples, int W, int hop, int n_frames, const double* window,
                                int detrend, int average, int mode, int amp_sqrt, double norm_scale,
                                double factor, int halve_edges, double* tf, double* coh) {
-    if (!c || !x || !y || !window || !tf || !coh) return fail(c, DS_ERR_ARG, "ds_welch_tf_x64: null argument");
-    if (average != DS_AVG_MEAN && average != DS_AVG_MEDIAN)
-        return fail(c, DS_ERR_ARG, "welch: average must be mean (0) or median (1)");
-    if (average == DS_AVG_MEDIAN && n_frames > 4096)
-        return fail(c, DS_ERR_UNSUP, "ds_welch_tf_x64: median averaging over more than 4096 frames (use ds_welch_tf)");
-    if (n_cy <= 0 || (n_cx != 1 && n_cx != n_cy) || n_samples <= 0 || hop <= 0 || hop > W || n_frames <= 0)
-        return fail(c, DS_ERR_ARG, "ds_welch_tf_x64: bad shape");
-    if (!is_pow2(W) || W < 8 || W > kMaxX64Window)
-        return fail(c, DS_ERR_UNSUP, "ds_welch_tf_x64: window length must be a power of two in [8, 262144]");
-    if (mode < DS_TF_H1 || mode > DS_TF_H3) return fail(c, DS_ERR_ARG, "welch: unsupported transfer function type");
-    const int nb = W / 2 + 1;
-    const size_t spec_x = (size_t)n_cx * n_frames * nb, spec_y = (size_t)n_cy * n_frames * nb;
-    if ((spec_x + spec_y) * sizeof(double2) > ((size_t)2 << 30))
-        return fail(c, DS_ERR_UNSUP, "ds_welch_tf_x64: problem too large for the float64 route (use ds_welch_tf)");
+    const X64Call q{"ds_welch_tf_x64", x, n_cx, y, n_cy, n_samples, W, hop, n_frames, window, detrend, average, mode,
+                    amp_sqrt, norm_scale, factor, halve_edges, tf, coh};
+    // (its own argument errors first: beside a window or a size that is not built they stay DS_ERR_ARG)
+    if (!y || !coh) return fail(c, DS_ERR_ARG, "ds_welch_tf_x64: null argument");
+    if (n_cy <= 0 || (n_cx != 1 && n_cx != n_cy)) return fail(c, DS_ERR_ARG, "ds_welch_tf_x64: bad shape");
+    if (mode < DS_TF_H1 || mode > DS_TF_H3) return fail(c, DS_ERR_ARG, "ds_welch_tf_x64: unsupported transfer function type");
+    CHK(x64_check(c, q, n_cx, n_cy));
     HIPCHK(c, hipSetDevice(c->device));
-    const size_t bx = (size_t)n_samples * n_cx * 8, by = (size_t)n_samples * n_cy * 8;
+    const int nb = q.nb();
     const size_t bout = (size_t)nb * n_cy;
     double *dx, *dy, *dcoh;
     double2 *xs, *ys, *dtf;
@@ -1998,64 +2058,37 @@ extern "C" int ds_welch_tf_x64(ds_ctx* c, const double* x, int n_cx, const doubl
         dx = cv.take<double>((size_t)n_samples * n_cx);
         dy = cv.take<double>((size_t)n_samples * n_cy);
         t = take_x64_tables(cv, W);
-        xs = cv.take<double2>(spec_x);
-        ys = cv.take<double2>(spec_y);
+        xs = cv.take<double2>((size_t)n_cx * n_frames * nb);
+        ys = cv.take<double2>((size_t)n_cy * n_frames * nb);
         dtf = cv.take<double2>(bout);
         dcoh = cv.take<double>(bout);
     }));
-    HIPCHK(c, hipMemcpyAsync(dx, x, bx, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(dy, y, by, hipMemcpyHostToDevice, c->stream));
     CHK(x64_tables(c, t, window, W));
-    CHK(x64_launch_frames(c, dx, n_cx, n_samples, W, hop, n_frames, detrend, t.dw, t.tw, xs));
-    CHK(x64_launch_frames(c, dy, n_cy, n_samples, W, hop, n_frames, detrend, t.dw, t.tw, ys));
-    if (average == DS_AVG_MEDIAN) {
-        const int nbias = (n_frames & 1) ? n_frames : n_frames - 1;
-        w64::TfArgs ta{xs, ys, n_cx, n_cy, n_frames, mode,
-                       FinishPar{norm_scale * (double)std::max(1, nbias), factor, halve_edges, amp_sqrt, nb}, dtf, dcoh};
+    CHK(x64_frames(c, q, t, x, dx, n_cx, xs));
+    CHK(x64_frames(c, q, t, y, dy, n_cy, ys));
+    w64::TfArgs ta{xs, ys, n_cx, n_cy, n_frames, mode, x64_finish(q, nb), dtf, dcoh};
+    if (q.median())
         CHK(launch(c, "welch_f64_tf_median", w64::k_tf_median, dim3(nb, n_cy), 256,
                    sizeof(double) * (4 * (size_t)n_frames + 8), ta));
-    } else {
-        w64::TfArgs ta{xs, ys, n_cx, n_cy, n_frames, mode,
-                       FinishPar{norm_scale / (double)n_frames, factor, halve_edges, amp_sqrt, nb}, dtf, dcoh};
+    else
         CHK(launch(c, "welch_f64_tf", w64::k_tf, dim3((nb + 255) / 256, n_cy), 256, 0, ta));
-    }
     HIPCHK(c, hipMemcpyAsync(tf, dtf, bout * 16, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(coh, dcoh, bout * 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return DS_OK;
 }
 
-// float64 frame spectra of a host (samples, channels) float64 array: upload, k_frames on the window / twiddle tables
-// (take_x64_tables() carves them, x64_tables() fills them)
-static int x64_frames(ds_ctx* c, const X64Tables& t, const double* sig, double* dsig, int n_ch, int64_t n_samples, int W,
-                      int hop, int n_frames, int detrend, double2* spec) {
-    HIPCHK(c, hipMemcpyAsync(dsig, sig, (size_t)n_samples * n_ch * 8, hipMemcpyHostToDevice, c->stream));
-    return x64_launch_frames(c, dsig, n_ch, n_samples, W, hop, n_frames, detrend, t.dw, t.tw, spec);
-}
-static int x64_shape_ok(ds_ctx* c, const char* who, int n_ch, int64_t n_samples, int W, int hop, int n_frames, int average) {
-    if (average != DS_AVG_MEAN && average != DS_AVG_MEDIAN)
-        return fail(c, DS_ERR_ARG, "welch: average must be mean (0) or median (1)");
-    if (average == DS_AVG_MEDIAN && n_frames > 4096)
-        return fail(c, DS_ERR_UNSUP, std::string(who) + ": median averaging over more than 4096 frames (use the fp32 entry point)");
-    if (n_ch <= 0 || n_samples <= 0 || hop <= 0 || hop > W || n_frames <= 0) return fail(c, DS_ERR_ARG, std::string(who) + ": bad shape");
-    if (!is_pow2(W) || W < 8 || W > kMaxX64Window)
-        return fail(c, DS_ERR_UNSUP, std::string(who) + ": window length must be a power of two in [8, 262144]");
-    return DS_OK;
-}
-
-// _welch in float64 end to end (auto spectra: y = NULL; cross spectra conj(X_i) Y_i otherwise): the route
-// backend._welch takes for SHORT estimates.  out: [nb][n_ch] complex128 (auto spectra: imaginary part 0).
+// _welch (auto spectra: y = NULL; cross spectra conj(X_i) Y_i otherwise): the route backend._welch takes for SHORT
+// estimates.  out: [nb][n_ch] complex128 (auto spectra: imaginary part 0).
 extern "C" int ds_welch_spec_x64(ds_ctx* c, const double* x, const double* y, int n_ch, int64_t n_samples, int W,
                                  int hop, int n_frames, const double* window, int detrend, int average, int amp_sqrt,
                                  double norm_scale, double factor, int halve_edges, double* out) {
-    if (!c || !x || !window || !out) return fail(c, DS_ERR_ARG, "ds_welch_spec_x64: null argument");
-    CHK(x64_shape_ok(c, "ds_welch_spec_x64", n_ch, n_samples, W, hop, n_frames, average));
-    const int nb = W / 2 + 1, n_in = y ? 2 : 1;
-    const size_t spec = (size_t)n_ch * n_frames * nb;
-    if (spec * n_in * sizeof(double2) > ((size_t)2 << 30))
-        return fail(c, DS_ERR_UNSUP, "ds_welch_spec_x64: problem too large for the float64 route (use ds_welch_psd / ds_welch_csd)");
+    const X64Call q{"ds_welch_spec_x64", x, n_ch, y, y ? n_ch : 0, n_samples, W, hop, n_frames, window, detrend, average, 0,
+                    amp_sqrt, norm_scale, factor, halve_edges, out, nullptr};
+    CHK(x64_check(c, q, n_ch, q.n_cy));
     HIPCHK(c, hipSetDevice(c->device));
-    const size_t bout = (size_t)nb * n_ch;
+    const int nb = q.nb();
+    const size_t spec = (size_t)n_ch * n_frames * nb, bout = (size_t)nb * n_ch;
     X64Tables t;
     double *dx, *dy = nullptr;
     double2 *xs, *ys = nullptr, *dout;
@@ -2070,54 +2103,49 @@ extern "C" int ds_welch_spec_x64(ds_ctx* c, const double* x, const double* y, in
         dout = cv.take<double2>(bout);
     }));
     CHK(x64_tables(c, t, window, W));
-    CHK(x64_frames(c, t, x, dx, n_ch, n_samples, W, hop, n_frames, detrend, xs));
-    if (y) CHK(x64_frames(c, t, y, dy, n_ch, n_samples, W, hop, n_frames, detrend, ys));
-    if (average == DS_AVG_MEDIAN) {
-        const int nbias = (n_frames & 1) ? n_frames : n_frames - 1;
-        w64::SpecArgs sa{xs, ys, n_ch, n_frames, FinishPar{norm_scale * (double)std::max(1, nbias), factor, halve_edges, amp_sqrt, nb}, dout};
+    CHK(x64_frames(c, q, t, x, dx, n_ch, xs));
+    if (y) CHK(x64_frames(c, q, t, y, dy, n_ch, ys));
+    w64::SpecArgs sa{xs, ys, n_ch, n_frames, x64_finish(q, nb), dout};
+    if (q.median())
         CHK(launch(c, "welch_f64_spec_median", w64::k_spec_median, dim3(nb, n_ch), 256, sizeof(double) * (2 * (size_t)n_frames + 4), sa));
-    } else {
-        w64::SpecArgs sa{xs, ys, n_ch, n_frames, FinishPar{norm_scale / (double)n_frames, factor, halve_edges, amp_sqrt, nb}, dout};
+    else
         CHK(launch(c, "welch_f64_spec", w64::k_spec, dim3((nb + 255) / 256, n_ch), 256, 0, sa));
-    }
     HIPCHK(c, hipMemcpyAsync(out, dout, bout * 16, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return DS_OK;
 }
 
-// _csm_welch in float64 end to end (up to 1024 channels; median averaging: up to 128 frames): csm [nb][n_ch][n_ch] complex128
+// _csm_welch (up to 1024 channels; median averaging: up to 128 frames): csm [nb][n_ch][n_ch] complex128
 extern "C" int ds_csm_x64(ds_ctx* c, const double* x, int n_ch, int64_t n_samples, int W, int hop, int n_frames,
                           const double* window, int detrend, int average, int amp_sqrt, double norm_scale, double factor,
                           int halve_edges, double* csm) {
-    if (!c || !x || !window || !csm) return fail(c, DS_ERR_ARG, "ds_csm_x64: null argument");
-    CHK(x64_shape_ok(c, "ds_csm_x64", n_ch, n_samples, W, hop, n_frames, average));
+    const X64Call q{"ds_csm_x64", x, n_ch, nullptr, 0, n_samples, W, hop, n_frames, window, detrend, average, 0,
+                    amp_sqrt, norm_scale, factor, halve_edges, csm, nullptr};
+    CHK(x64_check(c, q, n_ch, 0));
     if (n_ch > w64::CSM_MAX_CH) return fail(c, DS_ERR_UNSUP, "ds_csm_x64: more than 1024 channels (use ds_csm)");
-    if (average == DS_AVG_MEDIAN && n_frames > w64::CSM_MEDIAN_MAX_FRAMES)
+    if (q.median() && n_frames > w64::CSM_MEDIAN_MAX_FRAMES)
         return fail(c, DS_ERR_UNSUP, "ds_csm_x64: median averaging over more than 128 frames (use ds_csm)");
-    const int nb = W / 2 + 1;
-    const size_t spec = (size_t)n_ch * n_frames * nb, bout = (size_t)nb * n_ch * n_ch;
-    if (spec * sizeof(double2) > ((size_t)2 << 30))
-        return fail(c, DS_ERR_UNSUP, "ds_csm_x64: problem too large for the float64 route (use ds_csm)");
     HIPCHK(c, hipSetDevice(c->device));
+    const int nb = q.nb();
+    const size_t bout = (size_t)nb * n_ch * n_ch;
     X64Tables t;
     double* dx;
     double2 *xs, *dcsm;
     CHK(carve(c, &c->io, &c->io_bytes, [&](Carver& cv) {
         t = take_x64_tables(cv, W);
         dx = cv.take<double>((size_t)n_samples * n_ch);
-        xs = cv.take<double2>(spec);
+        xs = cv.take<double2>((size_t)n_ch * n_frames * nb);
         dcsm = cv.take<double2>(bout);
     }));
     CHK(x64_tables(c, t, window, W));
-    CHK(x64_frames(c, t, x, dx, n_ch, n_samples, W, hop, n_frames, detrend, xs));
-    if (average == DS_AVG_MEDIAN) {
-        const int nbias = (n_frames & 1) ? n_frames : n_frames - 1;  // as ds_welch_spec_x64
-        w64::CsmArgs ca{xs, n_ch, n_frames, FinishPar{norm_scale * (double)std::max(1, nbias), factor, halve_edges, amp_sqrt, nb}, dcsm};
+    CHK(x64_frames(c, q, t, x, dx, n_ch, xs));
+    w64::CsmArgs ca{xs, n_ch, n_frames, x64_finish(q, nb), dcsm};
+    if (q.median()) {
         CHK(launch(c, "csm_f64_median", w64::k_csm_median, dim3(nb, w64::csm_median_tile_pairs(n_ch)), 256,
                    w64::csm_median_lds(n_ch, n_frames), ca));
     } else {
         const int tile = std::max(1, std::min(n_frames, 4096 / n_ch));  // <= 64 KB of frame values per workgroup
-        w64::CsmArgs ca{xs, n_ch, n_frames, FinishPar{norm_scale / (double)n_frames, factor, halve_edges, amp_sqrt, nb}, dcsm};
+        // (k_csm takes `tile` as a second kernel argument, which launch() does not pass: launched and recorded by hand)
         hipLaunchKernelGGL(w64::k_csm, dim3(nb, w64::csm_pair_groups(n_ch)), dim3(256), (size_t)n_ch * tile * 16, c->stream, ca, tile);
         HIPCHK(c, hipGetLastError());
         c->routes.insert("csm_f64");
@@ -2300,11 +2328,16 @@ extern "C" int ds_csm_bins_dev(ds_ctx* c, const float* x, int n_ch, int64_t ld, 
                        norm_scale, factor, halve_edges, bin_start, bin_count, (float2*)csm});
 }
 
+static int csm_spec_check(ds_ctx* c, const void* X, const void* csm, int n_bins, int n_frames, int n_ch) {
+    if (!c || !X || !csm) return fail(c, DS_ERR_ARG, "ds_csm_spec: null argument");
+    if (n_bins <= 0 || n_frames <= 0 || n_ch <= 0) return fail(c, DS_ERR_ARG, "ds_csm_spec: bad shape");
+    return DS_OK;
+}
+
 extern "C" int ds_csm_spec_dev(ds_ctx* c, const ds_c32* X, int n_bins, int n_frames, int n_ch,
                                int amp_sqrt, double norm_scale, double factor, int halve_edges,
                                ds_c32* csm) {
-    if (!c || !X || !csm) return fail(c, DS_ERR_ARG, "ds_csm_spec: null argument");
-    if (n_bins <= 0 || n_frames <= 0 || n_ch <= 0) return fail(c, DS_ERR_ARG, "ds_csm_spec: bad shape");
+    CHK(csm_spec_check(c, X, csm, n_bins, n_frames, n_ch));
     const int nt = (n_ch + 31) / 32;
     CsmArgs a{(const float2*)X, n_ch, n_frames,
               FinishPar{norm_scale / (double)n_frames, factor, halve_edges, amp_sqrt, n_bins},
@@ -2315,22 +2348,24 @@ extern "C" int ds_csm_spec_dev(ds_ctx* c, const ds_c32* X, int n_bins, int n_fra
 
 extern "C" int ds_csm_spec(ds_ctx* c, const ds_c32* X, int n_bins, int n_frames, int n_ch, int amp_sqrt,
                            double norm_scale, double factor, int halve_edges, ds_c32* csm) {
-    if (!c || !X || !csm) return fail(c, DS_ERR_ARG, "ds_csm_spec: null argument");
-    if (n_bins <= 0 || n_frames <= 0 || n_ch <= 0) return fail(c, DS_ERR_ARG, "ds_csm_spec: bad shape");
-    size_t nx = (size_t)n_bins * n_frames * n_ch, no = (size_t)n_bins * n_ch * n_ch;
-    float2 *dx, *dc;
-    CHK(carve(c, &c->io, &c->io_bytes, [&](Carver& cv) { dx = cv.take<float2>(nx); dc = cv.take<float2>(no); }));
-    CHK(ds_upload(c, dx, X, nx * 8));
-    CHK(ds_csm_spec_dev(c, (const ds_c32*)dx, n_bins, n_frames, n_ch, amp_sqrt, norm_scale, factor,
-                        halve_edges, (ds_c32*)dc));
-    return ds_download(c, csm, dc, no * 8);
+    CHK(csm_spec_check(c, X, csm, n_bins, n_frames, n_ch));
+    const size_t nx = (size_t)n_bins * n_frames * n_ch, no = (size_t)n_bins * n_ch * n_ch;
+    return staged(c, {{8, nx, X, nullptr}, {8, no, nullptr, csm}}, [&](void* const* d) {
+        return ds_csm_spec_dev(c, (const ds_c32*)d[0], n_bins, n_frames, n_ch, amp_sqrt, norm_scale, factor, halve_edges,
+                               (ds_c32*)d[1]);
+    });
 }
 
 // ---- delay-and-sum beamformer map ---------------------------------------------------
-extern "C" int ds_das_map_dev(ds_ctx* c, const ds_c32* csm, const ds_c32* h, int n_bins, int n_ch,
-                              int n_grid, float* map) {
+static int das_map_check(ds_ctx* c, const void* csm, const void* h, const void* map, int n_bins, int n_ch, int n_grid) {
     if (!c || !csm || !h || !map) return fail(c, DS_ERR_ARG, "ds_das_map: null argument");
     if (n_bins <= 0 || n_ch <= 0 || n_grid <= 0) return fail(c, DS_ERR_ARG, "ds_das_map: bad shape");
+    return DS_OK;
+}
+
+extern "C" int ds_das_map_dev(ds_ctx* c, const ds_c32* csm, const ds_c32* h, int n_bins, int n_ch,
+                              int n_grid, float* map) {
+    CHK(das_map_check(c, csm, h, map, n_bins, n_ch, n_grid));
     if (n_bins > 65535) return fail(c, DS_ERR_UNSUP, "ds_das_map: more than 65535 bins per call is not built yet");
     DasArgs a{(const float2*)csm, (const float2*)h, n_bins, n_ch, n_grid, map};
     CHK(launch(c, "das_map", k_das_map, dim3((n_grid + 127) / 128, n_bins), 256, 0, a));
@@ -2357,24 +2392,19 @@ extern "C" int ds_csm_das_prepare_dev(ds_ctx* c, const ds_c32* csm, int n_bins, 
 }
 extern "C" int ds_das_map(ds_ctx* c, const ds_c32* csm, const ds_c32* h, int n_bins, int n_ch, int n_grid,
                           float* map) {
-    if (!c || !csm || !h || !map) return fail(c, DS_ERR_ARG, "ds_das_map: null argument");
-    if (n_bins <= 0 || n_ch <= 0 || n_grid <= 0) return fail(c, DS_ERR_ARG, "ds_das_map: bad shape");
-    size_t nc = (size_t)n_bins * n_ch * n_ch, nh = (size_t)n_bins * n_ch * n_grid, nm = (size_t)n_grid * n_bins;
-    float2 *dc, *dh;
-    float* dm;
-    CHK(carve(c, &c->io, &c->io_bytes, [&](Carver& cv) {
-        dc = cv.take<float2>(nc);
-        dh = cv.take<float2>(nh);
-        dm = cv.take<float>(nm);
-    }));
-    CHK(ds_upload(c, dc, csm, nc * 8));
-    CHK(ds_upload(c, dh, h, nh * 8));
-    CHK(ds_das_map_dev(c, (const ds_c32*)dc, (const ds_c32*)dh, n_bins, n_ch, n_grid, dm));
-    return ds_download(c, map, dm, nm * 4);
+    CHK(das_map_check(c, csm, h, map, n_bins, n_ch, n_grid));
+    const size_t nc = (size_t)n_bins * n_ch * n_ch, nh = (size_t)n_bins * n_ch * n_grid, nm = (size_t)n_grid * n_bins;
+    return staged(c, {{8, nc, csm, nullptr}, {8, nh, h, nullptr}, {4, nm, nullptr, map}}, [&](void* const* d) {
+        return ds_das_map_dev(c, (const ds_c32*)d[0], (const ds_c32*)d[1], n_bins, n_ch, n_grid, (float*)d[2]);
+    });
 }
 
 // ---- MVDR / Functional / Orthogonal / CLEAN-SC beamformer maps (kernels_beamform.hpp) -----------
-static int bf_shape_ok(ds_ctx* c, const char* who, int n_bins, int n_ch, int n_grid) {
+// what every entry of this family and its _dev twin refuse: a null context or array (in, in2, out: the host's or the
+// device's), a bad shape, a matrix or a grid beyond the kernels
+static int bf_check(ds_ctx* c, const char* who, const void* in, const void* in2, const void* out, int n_bins, int n_ch,
+                    int n_grid) {
+    if (!c || !in || !in2 || !out) return fail(c, DS_ERR_ARG, std::string(who) + ": null argument");
     if (n_bins <= 0 || n_ch <= 0 || n_grid <= 0) return fail(c, DS_ERR_ARG, std::string(who) + ": bad shape");
     if (n_ch > bf::MAX_CH)
         return fail(c, DS_ERR_UNSUP, std::string(who) + ": more than 64 microphones is not built (one bin's C x C "
@@ -2384,33 +2414,22 @@ static int bf_shape_ok(ds_ctx* c, const char* who, int n_bins, int n_ch, int n_g
 }
 
 extern "C" int ds_bf_eigh_dev(ds_ctx* c, const double* a, int n_bins, int n_ch, double* w, double* v) {
-    if (!c || !a || !w || !v) return fail(c, DS_ERR_ARG, "ds_bf_eigh: null argument");
-    CHK(bf_shape_ok(c, "ds_bf_eigh", n_bins, n_ch, 1));
+    CHK(bf_check(c, "ds_bf_eigh", a, w, v, n_bins, n_ch, 1));
     bf::EighArgs ea{(const double2*)a, n_ch, w, (double2*)v};
     return launch(c, "bf_eigh", bf::k_bf_eigh, dim3(n_bins), bf::THREADS, 0, ea);
 }
 
 extern "C" int ds_bf_eigh(ds_ctx* c, const double* a, int n_bins, int n_ch, double* w, double* v) {
-    if (!c || !a || !w || !v) return fail(c, DS_ERR_ARG, "ds_bf_eigh: null argument");
-    CHK(bf_shape_ok(c, "ds_bf_eigh", n_bins, n_ch, 1));
+    CHK(bf_check(c, "ds_bf_eigh", a, w, v, n_bins, n_ch, 1));
     const size_t nm = (size_t)n_bins * n_ch * n_ch, nw = (size_t)n_bins * n_ch;
-    double2 *da, *dv;
-    double* dw;
-    CHK(carve(c, &c->io, &c->io_bytes, [&](Carver& cv) {
-        da = cv.take<double2>(nm);
-        dv = cv.take<double2>(nm);
-        dw = cv.take<double>(nw);
-    }));
-    CHK(ds_upload(c, da, a, nm * 16));
-    CHK(ds_bf_eigh_dev(c, (const double*)da, n_bins, n_ch, dw, (double*)dv));
-    CHK(ds_download(c, w, dw, nw * 8));
-    return ds_download(c, v, dv, nm * 16);
+    return staged(c, {{16, nm, a, nullptr}, {16, nm, nullptr, v}, {8, nw, nullptr, w}}, [&](void* const* d) {
+        return ds_bf_eigh_dev(c, (const double*)d[0], n_bins, n_ch, (double*)d[2], (double*)d[1]);
+    });
 }
 
 extern "C" int ds_bf_eig_map_dev(ds_ctx* c, const double* csm, const double* h, int n_bins, int n_ch, int n_grid,
                                  int method, double gamma, int n_eig, double* map) {
-    if (!c || !csm || !h || !map) return fail(c, DS_ERR_ARG, "ds_bf_eig_map: null argument");
-    CHK(bf_shape_ok(c, "ds_bf_eig_map", n_bins, n_ch, n_grid));
+    CHK(bf_check(c, "ds_bf_eig_map", csm, h, map, n_bins, n_ch, n_grid));
     if (method != bf::MVDR && method != bf::FUNCTIONAL && method != bf::ORTHOGONAL)
         return fail(c, DS_ERR_ARG, "ds_bf_eig_map: method must be 0 (MVDR), 1 (Functional) or 2 (Orthogonal)");
     if (method == bf::ORTHOGONAL && (n_eig <= 0 || n_eig > n_ch))
@@ -2434,26 +2453,17 @@ extern "C" int ds_bf_eig_map_dev(ds_ctx* c, const double* csm, const double* h, 
 
 extern "C" int ds_bf_eig_map(ds_ctx* c, const double* csm, const double* h, int n_bins, int n_ch, int n_grid,
                              int method, double gamma, int n_eig, double* map) {
-    if (!c || !csm || !h || !map) return fail(c, DS_ERR_ARG, "ds_bf_eig_map: null argument");
-    CHK(bf_shape_ok(c, "ds_bf_eig_map", n_bins, n_ch, n_grid));
+    CHK(bf_check(c, "ds_bf_eig_map", csm, h, map, n_bins, n_ch, n_grid));
     const size_t nc = (size_t)n_bins * n_ch * n_ch, nh = (size_t)n_bins * n_ch * n_grid, nm = (size_t)n_grid * n_bins;
-    double2 *dc, *dh;
-    double* dm;
-    CHK(carve(c, &c->io, &c->io_bytes, [&](Carver& cv) {
-        dc = cv.take<double2>(nc);
-        dh = cv.take<double2>(nh);
-        dm = cv.take<double>(nm);
-    }));
-    CHK(ds_upload(c, dc, csm, nc * 16));
-    CHK(ds_upload(c, dh, h, nh * 16));
-    CHK(ds_bf_eig_map_dev(c, (const double*)dc, (const double*)dh, n_bins, n_ch, n_grid, method, gamma, n_eig, dm));
-    return ds_download(c, map, dm, nm * 8);
+    return staged(c, {{16, nc, csm, nullptr}, {16, nh, h, nullptr}, {8, nm, nullptr, map}}, [&](void* const* d) {
+        return ds_bf_eig_map_dev(c, (const double*)d[0], (const double*)d[1], n_bins, n_ch, n_grid, method, gamma, n_eig,
+                                 (double*)d[2]);
+    });
 }
 
 extern "C" int ds_bf_cleansc_dev(ds_ctx* c, const double* csm, const double* h, int n_bins, int n_ch, int n_grid,
                                  int max_iter, double safety, int remove_diagonal, double* map) {
-    if (!c || !csm || !h || !map) return fail(c, DS_ERR_ARG, "ds_bf_cleansc: null argument");
-    CHK(bf_shape_ok(c, "ds_bf_cleansc", n_bins, n_ch, n_grid));
+    CHK(bf_check(c, "ds_bf_cleansc", csm, h, map, n_bins, n_ch, n_grid));
     if (max_iter <= 0) return fail(c, DS_ERR_ARG, "ds_bf_cleansc: max_iter must be positive");
     if (!(safety > 0.0 && safety <= 1.0)) return fail(c, DS_ERR_ARG, "ds_bf_cleansc: safety factor must be in (0, 1]");
     double* dr;
@@ -2465,21 +2475,12 @@ extern "C" int ds_bf_cleansc_dev(ds_ctx* c, const double* csm, const double* h, 
 
 extern "C" int ds_bf_cleansc(ds_ctx* c, const double* csm, const double* h, int n_bins, int n_ch, int n_grid,
                              int max_iter, double safety, int remove_diagonal, double* map) {
-    if (!c || !csm || !h || !map) return fail(c, DS_ERR_ARG, "ds_bf_cleansc: null argument");
-    CHK(bf_shape_ok(c, "ds_bf_cleansc", n_bins, n_ch, n_grid));
+    CHK(bf_check(c, "ds_bf_cleansc", csm, h, map, n_bins, n_ch, n_grid));
     const size_t nc = (size_t)n_bins * n_ch * n_ch, nh = (size_t)n_bins * n_ch * n_grid, nm = (size_t)n_grid * n_bins;
-    double2 *dc, *dh;
-    double* dm;
-    CHK(carve(c, &c->io, &c->io_bytes, [&](Carver& cv) {
-        dc = cv.take<double2>(nc);
-        dh = cv.take<double2>(nh);
-        dm = cv.take<double>(nm);
-    }));
-    CHK(ds_upload(c, dc, csm, nc * 16));
-    CHK(ds_upload(c, dh, h, nh * 16));
-    CHK(ds_bf_cleansc_dev(c, (const double*)dc, (const double*)dh, n_bins, n_ch, n_grid, max_iter, safety,
-                          remove_diagonal, dm));
-    return ds_download(c, map, dm, nm * 8);
+    return staged(c, {{16, nc, csm, nullptr}, {16, nh, h, nullptr}, {8, nm, nullptr, map}}, [&](void* const* d) {
+        return ds_bf_cleansc_dev(c, (const double*)d[0], (const double*)d[1], n_bins, n_ch, n_grid, max_iter, safety,
+                                 remove_diagonal, (double*)d[2]);
+    });
 }
 
 // ---- FIR ---------------------------------------------------------------------
@@ -3386,20 +3387,11 @@ extern "C" int ds_iir_sos(ds_ctx* c, const double* x, int n_ch, int64_t n_sample
     HIPCHK(c, hipSetDevice(c->device));
     const int n_out = mode == DS_FB_PARALLEL ? n_filt : 1;
     const size_t nx = (size_t)n_ch * n_samples, ny = nx * n_out, nz = (size_t)n_filt * n_sec * 2 * n_ch;
-    double *dx, *dy, *dzi, *dzf;
-    CHK(carve(c, &c->io, &c->io_bytes, [&](Carver& cv) {
-        dx = cv.take<double>(nx);
-        dy = cv.take<double>(ny);
-        dzi = cv.take<double>(nz);
-        dzf = cv.take<double>(nz);
-    }));
-    CHK(ds_upload(c, dx, x, nx * 8));
-    if (zi) CHK(ds_upload(c, dzi, zi, nz * 8));
-    CHK(iir_run<double>(c, "ds_iir_sos", dx, 1, n_ch, n_samples, n_ch, sos, n_filt, n_sec, zi ? dzi : nullptr, mode,
-                        dy, (int64_t)nx, 1, n_ch, zf ? dzf : nullptr));
-    CHK(ds_download(c, y, dy, ny * 8));
-    if (zf) CHK(ds_download(c, zf, dzf, nz * 8));
-    return DS_OK;
+    return staged(c, {{8, nx, x, nullptr}, {8, ny, nullptr, y}, {8, nz, zi, nullptr}, {8, nz, nullptr, zf}}, [&](void* const* d) {
+        return iir_run<double>(c, "ds_iir_sos", (const double*)d[0], 1, n_ch, n_samples, n_ch, sos, n_filt, n_sec,
+                               zi ? (const double*)d[2] : nullptr, mode, (double*)d[1], (int64_t)nx, 1, n_ch,
+                               zf ? (double*)d[3] : nullptr);
+    });
 }
 
 // ---- weighted sums of fractionally delayed channels (kernels_delay.hpp) -----------------------------------------
@@ -3489,16 +3481,10 @@ extern "C" int ds_delay_sum(ds_ctx* c, const double* x, int n_src, int64_t n_x, 
                        out_len));
     HIPCHK(c, hipSetDevice(c->device));
     const size_t nx = (size_t)n_src * n_x, ny = y ? (size_t)n_rows * out_len : 0;
-    double *dx, *dy;
-    CHK(carve(c, &c->io, &c->io_bytes, [&](Carver& cv) {
-        dx = cv.take<double>(nx);
-        dy = cv.take<double>(ny);
-    }));
-    CHK(ds_upload(c, dx, x, nx * 8));
-    CHK(delay_run<double>(c, "ds_delay_sum", dx, 1, n_src, n_src, src_len, n_rows, n_terms, src, shift, frac, weight,
-                          order, beta, out_len, y ? dy : nullptr, 1, n_rows, peak));
-    if (y) CHK(ds_download(c, y, dy, ny * 8));
-    return DS_OK;
+    return staged(c, {{8, nx, x, nullptr}, {8, ny, nullptr, y}}, [&](void* const* d) {
+        return delay_run<double>(c, "ds_delay_sum", (const double*)d[0], 1, n_src, n_src, src_len, n_rows, n_terms, src, shift,
+                                 frac, weight, order, beta, out_len, y ? (double*)d[1] : nullptr, 1, n_rows, peak);
+    });
 }
 
 // ---- continuous wavelet transform and synchrosqueezing (kernels_cwt.hpp) ---------------------------------------
