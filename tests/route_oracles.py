@@ -26,7 +26,7 @@ Every `_f64` entry narrows its float64 arrays to float32 while it uploads them (
 upload_narrow_f64 in stft_host, istft_host, rfft_host, deconv_host, fir_ola_host, welch_host, csm_host) and runs the
 kernels of the float32 entry; the device entries take float32.  So there is ONE oracle per problem for all its
 entries, on the float32-rounded samples, taps, window and spectra, computed in float64.  No entry of these matrices
-computes in float64.
+computes in float64 (the float64 Welch entries have a matrix of their own, judged in long double: tests/x64_cases.py).
 
 The error rule.  |out - oracle| <= tol * scale elementwise, scale = the root mean square of the oracle over the
 transform axis of that row (rfft: bins of a channel; deconv, istft, fir: samples of a row; stft: bins of a frame of
@@ -125,7 +125,8 @@ def tolerance(tk):
 
 # ---- the restatements: dt = numpy.float64 is the oracle, numpy.float32 the single-precision emulation ----------------
 def _cdt(dt):
-    return np.complex64 if dt == np.float32 else np.complex128
+    # (long double: the oracle of the float64 Welch entries, tests/x64_cases.py)
+    return np.complex64 if dt == np.float32 else np.clongdouble if dt == np.longdouble else np.complex128
 
 
 def frames(x, W, hop, n_frames, pad_front=0):

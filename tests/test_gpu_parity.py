@@ -2288,7 +2288,7 @@ def test_short_estimates_through_the_api_hold_1e6(W, monkeypatch):
                         _, rm = orc.csm_welch(y, 48000, W, "hann", 50, det, "mean", sc.name)
                         worst["csm"] = max(worst["csm"], relmax(m[lo:], rm[lo:]))
     print("short estimates through the API, worst rel-max", worst)
-    assert max(worst.values()) < TOL, worst
+    assert max(worst.values()) < 1e-11, worst  # (float64 kernels, asserted above: the bound of this route, not TOL)
 
 
 def test_csm_short_estimate_of_70_channels(monkeypatch):
@@ -2538,7 +2538,7 @@ def test_short_estimates_with_long_windows_hold_1e6(W, monkeypatch):
                 worst["tf"] = max(worst["tf"], relmax(tf[lo:], rt[lo:]))
                 worst["coh"] = max(worst["coh"], relmax(coh[lo:], rc[lo:]))
     print("short estimates with long windows through the API, worst rel-max", W, worst)
-    assert max(worst.values()) < TOL, worst
+    assert max(worst.values()) < 1e-11, worst  # (float64 kernels, asserted above: the bound of this route, not TOL)
 
 
 @pytest.mark.parametrize("n_frames", [117, 500])
