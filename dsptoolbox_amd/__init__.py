@@ -7,11 +7,11 @@ from .classes import Filter, FilterBank, ImpulseResponse, MultiBandSignal, Signa
 from .standard.enums import (BiquadEqType, FilterBankMode, FilterCoefficientsType, FilterPassType,
                              FrequencySpacing, IirDesignMethod, SpectrumMethod, SpectrumScaling, SpectrumType, Window)
 from .standard import fractional_delay
-from .transfer_functions.enums import TransferFunctionType
+from .transfer_functions.enums import SmoothingDomain, TransferFunctionType
 
 __version__ = "0.1.0"
 __all__ = ["Signal", "ImpulseResponse", "Spectrum", "Filter", "FilterBank", "MultiBandSignal",
            "SpectrumMethod", "SpectrumScaling", "SpectrumType", "FrequencySpacing", "Window", "FilterBankMode",
-           "FilterPassType", "FilterCoefficientsType", "IirDesignMethod", "BiquadEqType", "TransferFunctionType",
+           "FilterPassType", "FilterCoefficientsType", "IirDesignMethod", "BiquadEqType", "TransferFunctionType", "SmoothingDomain",
            "transfer_functions", "transforms", "room_acoustics", "beamforming", "filterbanks", "tools", "standard",
            "fractional_delay"]

@@ -28,6 +28,7 @@ NO_SCRATCH = [
     "k_delay_sum",
     "k_cwt_inv", "k_cwt_squeeze",
     "k_to_log", "k_smooth", "k_to_lin", "k_polar", "k_unwrap", "k_recombine",
+    "k_dft", "k_csmooth", "k_colmap",
 ]
 
 

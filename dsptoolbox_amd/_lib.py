@@ -128,6 +128,12 @@ SIGNATURES = {
     "ds_octave_smooth": (C.c_int, [ctx_p, C.c_void_p, i64, C.c_int, C.c_void_p, C.c_void_p, i64, C.c_int, C.c_void_p]),
     "ds_octave_smooth_complex": (C.c_int, [ctx_p, C.c_void_p, i64, C.c_int, C.c_void_p, C.c_void_p, i64, C.c_int,
                                            C.c_void_p]),
+    "ds_dft": (C.c_int, [ctx_p, C.c_void_p, i64, C.c_int, C.c_void_p, i64, C.c_double, C.c_void_p, C.c_void_p, C.c_double,
+                         C.c_double, C.c_void_p]),
+    "ds_dft_dev": (C.c_int, [ctx_p, C.c_void_p, C.c_int, i64, i64, C.c_void_p, i64, C.c_double, C.c_void_p, C.c_void_p,
+                             C.c_double, C.c_double, C.c_void_p]),
+    "ds_complex_smooth": (C.c_int, [ctx_p, C.c_void_p, i64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "ds_welch_tf_x64": (C.c_int, [ctx_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, i64, C.c_int, C.c_int, C.c_int,
                                   C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int,
                                   C.c_void_p, C.c_void_p]),

@@ -1647,3 +1647,126 @@ def smooth_complex_spectrum(spectrum, num_fractions, bin_spacing_octaves=None, w
                                                _ptr(window), n_window, int(bool(clip_magnitude)), _ptr(out)),
               "ds_octave_smooth_complex")
     return out
+
+
+# ---- direct sums (ds_dft, ds_dft_dev, ds_complex_smooth; csrc/kernels_direct.hpp) ---------------------------------
+# terms of one call (csrc/size_guards.hpp; DS_ERR_UNSUP above)
+DFT_MAX_WORK = 1e12           # frequencies x samples x channels of the plain DFT
+DFT_WINDOWED_MAX_WORK = 2e10  # kept window terms of the windowed DFT
+CSMOOTH_MAX_WORK = 2e11       # band lengths x channels of complex smoothing
+DFT_MIN_WEIGHT_LOG2 = -70.0   # window terms below 2^-70 are skipped
+SMOOTHING_DOMAINS = ("RealImaginary", "PowerPhase", "MagnitudePhase", "Power", "Magnitude", "EquivalentComplex")
+
+
+def _dft_guard(terms: float, windowed: bool = False) -> None:
+    """NotImplementedError for a direct DFT beyond the work bound, before anything reaches the device."""
+    bound = DFT_WINDOWED_MAX_WORK if windowed else DFT_MAX_WORK
+    if float(terms) > bound:
+        raise NotImplementedError(f"a direct DFT of {float(terms):.3g} terms is beyond the device kernel's work bound "
+                                  f"({bound:.0e} terms per call)")
+
+
+def _csmooth_guard(terms: float) -> None:
+    if float(terms) > CSMOOTH_MAX_WORK:
+        raise NotImplementedError(f"complex smoothing of {float(terms):.3g} band terms is beyond the device kernel's "
+                                  f"work bound ({CSMOOTH_MAX_WORK:.0e} terms per call)")
+
+
+def _windowed_kept_distance(alpha, half: float, n_samples: int, min_weight_log2: float = DFT_MIN_WEIGHT_LOG2):
+    """Per bin, the largest distance from the peak whose weight exp(-alpha (d / half)^2 / 2) reaches
+    2^min_weight_log2 (the rule of ds_dft), at most n_samples."""
+    with np.errstate(divide="ignore", invalid="ignore"):
+        d = half * np.sqrt(-2.0 * np.log(2.0) * min_weight_log2 / np.asarray(alpha, dtype=np.float64))
+    return np.where(d < n_samples, d, n_samples).astype(np.int64)
+
+
+def _windowed_kept_terms(alpha, peak, half: float, n_samples: int,
+                         min_weight_log2: float = DFT_MIN_WEIGHT_LOG2) -> float:
+    d = _windowed_kept_distance(alpha, half, n_samples, min_weight_log2)[:, None]
+    pk = np.asarray(peak, dtype=np.int64)[None, :]
+    return float((np.minimum(n_samples, pk + d + 1) - np.maximum(0, pk - d)).sum())
+
+
+def _dft_call(samples, freqs_hz, fs, alpha, peak, half, min_weight_log2):
+    freqs = np.ascontiguousarray(freqs_hz, dtype=np.float64).ravel()
+    resident = isinstance(samples, DevicePlanar)
+    if resident:
+        n, n_ch = samples.n_samples, samples.n_ch
+    else:
+        samples = np.ascontiguousarray(samples, dtype=np.float64)
+        assert samples.ndim == 2, "the samples are (samples, channels)"
+        n, n_ch = samples.shape
+    windowed = alpha is not None
+    if windowed:
+        alpha = np.ascontiguousarray(alpha, dtype=np.float64).ravel()
+        peak = np.ascontiguousarray(peak, dtype=np.int64).ravel()
+        assert len(alpha) == len(freqs) and len(peak) == n_ch, "alpha is per frequency, peak per channel"
+        _dft_guard(_windowed_kept_terms(alpha, peak, half, n, min_weight_log2), True)
+    else:
+        _dft_guard(float(len(freqs)) * n * n_ch)
+    out = np.empty((len(freqs), n_ch), dtype=np.complex128)
+    tail = (_ptr(freqs), len(freqs), float(fs), _ptr(alpha) if windowed else None, _ptr(peak) if windowed else None,
+            float(half), float(min_weight_log2), _ptr(out))
+    if resident:
+        ctx = samples.ctx
+        ctx.check(ctx.lib.ds_dft_dev(ctx.handle, C.c_void_p(samples.ptr), n_ch, samples.ld, n, *tail), "ds_dft_dev")
+    else:
+        ctx = get_context()
+        ctx.check(ctx.lib.ds_dft(ctx.handle, _ptr(samples), n, n_ch, *tail), "ds_dft")
+    return out
+
+
+def dft(time_data, freqs_hz, fs):
+    """X[k, c] = sum_n x[n, c] exp(-2 pi i f_k n / fs) at any frequencies (transforms/_transforms.py:_dft_backend),
+    float64 on the device.  time_data: (samples, channels) float64 on the host or a `DevicePlanar`."""
+    return _dft_call(time_data, freqs_hz, fs, None, None, 1.0, DFT_MIN_WEIGHT_LOG2)
+
+
+def windowed_dft(time_data, freqs_hz, fs, alpha, peak, half, min_weight_log2: float = DFT_MIN_WEIGHT_LOG2):
+    """The same sum under the Gaussian window exp(alpha_k * -0.5 ((n - peak_c) / half)^2) per bin and channel
+    (transfer_functions/_transfer_functions.py:_fdw_backend).  Terms whose weight is below 2^min_weight_log2 are
+    skipped; -inf keeps all of them."""
+    return _dft_call(time_data, freqs_hz, fs, alpha, peak, half, min_weight_log2)
+
+
+def _csmooth_indices(freqs_hz, octave_fraction):
+    """(ind_low, ind_high, window_length, pass) per bin in the statements of _complex_smoothing_backend
+    (transfer_functions/_transfer_functions.py:519-541), int32: the band clipped to the spectrum, its unclipped
+    length, and the bins the reference copies."""
+    f = np.asarray(freqs_hz, dtype=np.float64)
+    delta_f = f[1] - f[0]
+    factor = 2.0 ** (1.0 / octave_fraction / 2.0)
+    i = np.arange(len(f), dtype=np.int64)
+    ind_low = i - ((f - f / factor) / delta_f + 0.5).astype(np.int64)        # int(x + 0.5) of x >= 0
+    ind_high = i + ((f * factor - f) / delta_f + 0.5).astype(np.int64) + 1
+    window_length = ind_high - ind_low
+    ind_low = np.maximum(ind_low, 0)
+    ind_high = np.minimum(ind_high, len(f))
+    passed = ind_low + 2 >= ind_high
+    return tuple(np.ascontiguousarray(a, dtype=np.int32) for a in (ind_low, ind_high, window_length, passed))
+
+
+def complex_smoothing(spectrum, freqs_hz, octave_fraction, domain, window_values):
+    """_complex_smoothing_backend and the domain transforms of transfer_functions.complex_smoothing
+    (transfer_functions.py:1827-1875) on a float64 / complex128 (bins, channels) spectrum over linearly spaced
+    frequencies: one upload, one download (ds_complex_smooth).  domain: a name of SMOOTHING_DOMAINS (or an enum
+    member carrying one); window_values: the window prototype on linspace(-1, 1, len(window_values))."""
+    name = getattr(domain, "name", domain)
+    if name not in SMOOTHING_DOMAINS:
+        raise ValueError("Invalid smoothing domain")
+    assert octave_fraction > 0.0, "Octave fraction must be greater than 0"
+    z = np.ascontiguousarray(spectrum, dtype=np.complex128)
+    assert z.ndim == 2, "the spectrum is (bins, channels)"
+    n_bins, n_ch = z.shape
+    freqs = np.asarray(freqs_hz, dtype=np.float64)
+    assert len(freqs) == n_bins and n_bins >= 2, "one frequency per bin, at least two bins"
+    lo, hi, wlen, passed = _csmooth_indices(freqs, octave_fraction)
+    _csmooth_guard(float((hi - lo)[passed == 0].sum()) * n_ch)
+    wy = np.ascontiguousarray(window_values, dtype=np.float64)
+    wx = np.linspace(-1.0, 1.0, len(wy), endpoint=True)
+    out = np.empty_like(z)
+    ctx = get_context()
+    ctx.check(ctx.lib.ds_complex_smooth(ctx.handle, _ptr(z), n_bins, n_ch, _ptr(lo), _ptr(hi), _ptr(wlen), _ptr(passed),
+                                        _ptr(wx), _ptr(wy), len(wy), SMOOTHING_DOMAINS.index(name), _ptr(out)),
+              "ds_complex_smooth")
+    return out

@@ -44,6 +44,7 @@
 #include "kernels_delay.hpp"
 #include "kernels_cwt.hpp"
 #include "kernels_smooth.hpp"
+#include "kernels_direct.hpp"
 #include "size_guards.hpp"
 
 using namespace dsk;
@@ -3795,6 +3796,229 @@ extern "C" int ds_octave_smooth_complex(ds_ctx* c, const double* z, int64_t n_bi
     CHK(smooth_run(c, dun, n_bins, 2 * n_ch, k_log ? dklog : nullptr, dwr, n_window, clip_magnitude ? n_ch : 0, da, db,
                    dout));
     CHK(launch(c, "smooth_recombine", k_recombine, flat, NT, 0, RecombineArgs{dout, n_bins, n_ch, (double2*)dz}));
+    return ds_download(c, out, dz, n * 16);
+}
+
+// ---- direct sums (kernels_direct.hpp), float64 --------------------------------------------------------------
+// Everything ds_dft and ds_dft_dev share.  x: device samples, element (n, c) at x[n ss + c cs].
+struct DftCall {
+    const char* who;
+    int64_t n_samples;
+    int n_ch;
+    const double* freqs_hz;
+    int64_t n_freq;
+    double fs;
+    const double* alpha;  // nullptr: the plain DFT
+    const int64_t* peak;
+    double half, min_weight_log2;
+    double* out;          // host (n_freq, n_ch) complex128
+};
+
+// validation, the kept distances of the windowed form and the work bound; nothing touches the device.  *empty: the
+// result has no elements.
+static int dft_check(ds_ctx* c, const DftCall& q, std::vector<int64_t>& dist, bool* empty) {
+    const std::string w(q.who);
+    *empty = q.n_freq == 0 || q.n_ch == 0;
+    if (q.n_freq < 0 || q.n_ch < 0 || q.n_samples < 1 || !(q.fs > 0.0)) return fail(c, DS_ERR_ARG, w + ": bad shape");
+    if (*empty) return DS_OK;
+    const double N = (double)q.n_samples, C = (double)q.n_ch;
+    // an upper bound first: it needs no array, and a frequency count beyond it is never walked
+    if (!q.alpha && dft_work_too_large((double)q.n_freq * N * C, false))
+        return fail(c, DS_ERR_UNSUP, w + ": frequencies x samples x channels is beyond the direct summation's work bound");
+    if ((q.n_freq + dsdirect::FT - 1) / dsdirect::FT > INT32_MAX || (q.n_ch + dsdirect::CT - 1) / dsdirect::CT > 65535 ||
+        q.n_freq * q.n_ch > INT64_MAX / 64)
+        return fail(c, DS_ERR_UNSUP, w + ": more frequencies or channels than one launch covers");
+    if (!q.freqs_hz || !q.out) return fail(c, DS_ERR_ARG, w + ": null argument");
+    if (!q.alpha) return DS_OK;
+    // every (bin, channel) keeps its peak sample at least
+    if (dft_work_too_large((double)q.n_freq * C, true) || q.n_freq > ((int64_t)1 << 28))
+        return fail(c, DS_ERR_UNSUP, w + ": the kept window terms are beyond the direct summation's work bound");
+    if (!q.peak || !(q.half > 0.0) || std::isnan(q.min_weight_log2) || q.min_weight_log2 > 0.0)
+        return fail(c, DS_ERR_ARG, w + ": the windowed form needs peak, half > 0 and min_weight_log2 <= 0");
+    for (int ch = 0; ch < q.n_ch; ++ch)
+        if (q.peak[ch] < 0 || q.peak[ch] >= q.n_samples) return fail(c, DS_ERR_ARG, w + ": peak outside the signal");
+    // weight(d) = exp(-alpha (d / half)^2 / 2) >= 2^min_weight_log2  <=>  d <= half sqrt(-2 ln2 min_weight_log2 / alpha)
+    dist.resize(q.n_freq);
+    double terms = 0.0;
+    for (int64_t k = 0; k < q.n_freq; ++k) {
+        const double a = q.alpha[k];
+        if (std::isnan(a)) return fail(c, DS_ERR_ARG, w + ": alpha is NaN");
+        const double d = a > 0.0 ? q.half * std::sqrt(-2.0 * 0.6931471805599453 * q.min_weight_log2 / a) : N;
+        dist[k] = d < N ? (int64_t)d : q.n_samples;
+        for (int ch = 0; ch < q.n_ch; ++ch)
+            terms += (double)(std::min(q.n_samples, q.peak[ch] + dist[k] + 1) - std::max<int64_t>(0, q.peak[ch] - dist[k]));
+    }
+    if (dft_work_too_large(terms, true))
+        return fail(c, DS_ERR_UNSUP, w + ": the kept window terms are beyond the direct summation's work bound");
+    return DS_OK;
+}
+
+template <typename T>
+static int dft_run(ds_ctx* c, const DftCall& q, const T* x, int64_t ss, int64_t cs, const std::vector<int64_t>& dist) {
+    using namespace dsdirect;
+    const int64_t F = q.n_freq, n_out = F * q.n_ch;
+    const int64_t ftiles = (F + FT - 1) / FT, ctiles = (q.n_ch + CT - 1) / CT;
+    // sample chunks: enough workgroups to fill the device when the frequencies alone do not
+    const int64_t units = (q.n_samples + CHUNK_UNIT - 1) / CHUNK_UNIT;
+    const int64_t want = std::max<int64_t>(1, 4096 / (ftiles * ctiles));
+    const int64_t chunk = (units + std::min(units, want) - 1) / std::min(units, want) * CHUNK_UNIT;
+    const int n_chunks = (int)((q.n_samples + chunk - 1) / chunk);
+    double *dfq, *dal;
+    int64_t *dpk, *dds;
+    double2 *dpart, *dout;
+    CHK(carve(c, &c->ws, &c->ws_bytes, [&](Carver& cv) {
+        dfq = cv.take<double>(F);
+        dal = cv.take<double>(q.alpha ? F : 0);
+        dds = cv.take<int64_t>(q.alpha ? F : 0);
+        dpk = cv.take<int64_t>(q.alpha ? q.n_ch : 0);
+        dpart = cv.take<double2>((size_t)n_chunks * n_out);
+        dout = cv.take<double2>(n_out);
+    }));
+    CHK(ds_upload(c, dfq, q.freqs_hz, (size_t)F * 8));
+    if (q.alpha) {
+        CHK(ds_upload(c, dal, q.alpha, (size_t)F * 8));
+        CHK(ds_upload(c, dds, dist.data(), (size_t)F * 8));
+        CHK(ds_upload(c, dpk, q.peak, (size_t)q.n_ch * 8));
+    }
+    DftArgs a{x, ss, cs, q.n_samples, q.n_ch, dfq, F, q.fs, dal, dpk, dds, q.half, chunk, dpart};
+    const dim3 grid((unsigned)ftiles, (unsigned)n_chunks, (unsigned)ctiles);
+    if (q.alpha)
+        CHK(launch(c, "dft@windowed", k_dft<T, true>, grid, NT, 0, a));
+    else
+        CHK(launch(c, "dft", k_dft<T, false>, grid, NT, 0, a));
+    CHK(launch(c, "dft_combine", k_dft_combine, dim3((unsigned)((n_out + NT - 1) / NT)), NT, 0,
+               CombineArgs{dpart, n_out, n_chunks, dout}));
+    return ds_download(c, q.out, dout, (size_t)n_out * 16);
+}
+
+extern "C" int ds_dft(ds_ctx* c, const double* x, int64_t n_samples, int n_ch, const double* freqs_hz, int64_t n_freq,
+                      double fs_hz, const double* alpha, const int64_t* peak, double half, double min_weight_log2,
+                      double* out) {
+    if (!c) return fail(c, DS_ERR_ARG, "ds_dft: null context");
+    const DftCall q{"ds_dft", n_samples, n_ch, freqs_hz, n_freq, fs_hz, alpha, peak, half, min_weight_log2, out};
+    std::vector<int64_t> dist;
+    bool empty;
+    CHK(dft_check(c, q, dist, &empty));
+    if (empty) return DS_OK;
+    if (!x) return fail(c, DS_ERR_ARG, "ds_dft: null argument");
+    HIPCHK(c, hipSetDevice(c->device));
+    double* dx;
+    CHK(carve(c, &c->io, &c->io_bytes, [&](Carver& cv) { dx = cv.take<double>((size_t)n_samples * n_ch); }));
+    CHK(ds_upload(c, dx, x, (size_t)n_samples * n_ch * 8));
+    return dft_run<double>(c, q, dx, n_ch, 1, dist);
+}
+
+extern "C" int ds_dft_dev(ds_ctx* c, const float* x, int n_ch, int64_t ldx, int64_t n_samples, const double* freqs_hz,
+                          int64_t n_freq, double fs_hz, const double* alpha, const int64_t* peak, double half,
+                          double min_weight_log2, double* out) {
+    if (!c) return fail(c, DS_ERR_ARG, "ds_dft_dev: null context");
+    const DftCall q{"ds_dft_dev", n_samples, n_ch, freqs_hz, n_freq, fs_hz, alpha, peak, half, min_weight_log2, out};
+    std::vector<int64_t> dist;
+    bool empty;
+    CHK(dft_check(c, q, dist, &empty));
+    if (empty) return DS_OK;
+    if (!x || ldx < n_samples) return fail(c, DS_ERR_ARG, "ds_dft_dev: null samples or ldx < n_samples");
+    HIPCHK(c, hipSetDevice(c->device));
+    return dft_run<float>(c, q, x, 1, ldx, dist);
+}
+
+// z, out: host (n_bins, n_ch) complex128.  ind_low / ind_high: the band of every bin clipped to [0, n_bins];
+// window_length: its unclipped length; pass: bins copied unchanged.  domain: DS_SMOOTH_* of the header.
+extern "C" int ds_complex_smooth(ds_ctx* c, const double* z, int64_t n_bins, int n_ch, const int32_t* ind_low,
+                                 const int32_t* ind_high, const int32_t* window_length, const int32_t* pass,
+                                 const double* window_x, const double* window_y, int n_window, int domain, double* out) {
+    using namespace dsdirect;
+    if (!c) return fail(c, DS_ERR_ARG, "ds_complex_smooth: null context");
+    if (n_bins < 0 || n_ch < 0 || n_bins > INT32_MAX / 2 || n_ch > INT32_MAX / 4 || n_window < 2)
+        return fail(c, DS_ERR_ARG, "ds_complex_smooth: bad shape");
+    if (domain < DS_SMOOTH_REAL_IMAGINARY || domain > DS_SMOOTH_EQUIVALENT_COMPLEX)
+        return fail(c, DS_ERR_ARG, "ds_complex_smooth: unknown domain");
+    if (n_bins == 0 || n_ch == 0) return DS_OK;
+    if (!z || !ind_low || !ind_high || !window_length || !pass || !window_x || !window_y || !out)
+        return fail(c, DS_ERR_ARG, "ds_complex_smooth: null argument");
+    double terms = 0.0;
+    for (int64_t i = 0; i < n_bins; ++i) {
+        if (pass[i]) continue;
+        if (ind_low[i] < 0 || ind_high[i] > n_bins || ind_low[i] >= ind_high[i] ||
+            window_length[i] < ind_high[i] - ind_low[i])
+            return fail(c, DS_ERR_ARG, "ds_complex_smooth: a band leaves the spectrum or its window");
+        terms += (double)(ind_high[i] - ind_low[i]);
+    }
+    if (csmooth_work_too_large(terms * (double)n_ch))
+        return fail(c, DS_ERR_UNSUP, "ds_complex_smooth: band lengths x channels is beyond the direct summation's work bound");
+    for (int k = 1; k < n_window; ++k)
+        if (!(window_x[k] > window_x[k - 1])) return fail(c, DS_ERR_ARG, "ds_complex_smooth: window_x is not ascending");
+    if ((n_bins + WAVES - 1) / WAVES > INT32_MAX || (2 * (int64_t)n_ch + WCT - 1) / WCT > 65535)
+        return fail(c, DS_ERR_UNSUP, "ds_complex_smooth: more bins or channels than one launch covers");
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t n = (size_t)n_bins * n_ch;
+    const int64_t ld = 2 * (int64_t)n_ch;
+    double *dz, *da, *db, *ds, *dwx, *dwy;
+    int *dlo, *dhi, *dwl, *dps;
+    CHK(carve(c, &c->ws, &c->ws_bytes, [&](Carver& cv) {
+        dz = cv.take<double>(2 * n);  // the spectrum, then the result
+        da = cv.take<double>(2 * n);  // the domain's quantity: (bins, 2 C) real columns
+        db = cv.take<double>(2 * n);  // wrapped phases, values nobody reads
+        ds = cv.take<double>(2 * n);  // smoothed columns
+        dwx = cv.take<double>(n_window);
+        dwy = cv.take<double>(n_window);
+        dlo = cv.take<int>(n_bins);
+        dhi = cv.take<int>(n_bins);
+        dwl = cv.take<int>(n_bins);
+        dps = cv.take<int>(n_bins);
+    }));
+    CHK(ds_upload(c, dwx, window_x, (size_t)n_window * 8));
+    CHK(ds_upload(c, dwy, window_y, (size_t)n_window * 8));
+    CHK(ds_upload(c, dlo, ind_low, (size_t)n_bins * 4));
+    CHK(ds_upload(c, dhi, ind_high, (size_t)n_bins * 4));
+    CHK(ds_upload(c, dwl, window_length, (size_t)n_bins * 4));
+    CHK(ds_upload(c, dps, pass, (size_t)n_bins * 4));
+    CHK(ds_upload(c, dz, z, n * 16));
+    const dim3 flat((unsigned)((n + NT - 1) / NT));
+    // the band sums of the leading n_cols columns of a (bins, 2 C) array
+    auto smooth = [&](const double* v, double* o, int n_cols) {
+        return launch(c, "csmooth", k_csmooth, dim3((unsigned)((n_bins + WAVES - 1) / WAVES), (unsigned)((n_cols + WCT - 1) / WCT)),
+                      NT, 0, CsmoothArgs{v, ld, o, ld, n_cols, n_bins, dlo, dhi, dwl, dps, dwx, dwy, n_window});
+    };
+    auto polar = [&](const double* zz, double* mag, double* ph) {
+        return launch(c, "csmooth_polar", dssmooth::k_polar, flat, NT, 0,
+                      dssmooth::PolarArgs{(const double2*)zz, n_bins, n_ch, mag, ph});
+    };
+    auto colmap = [&](double* v, int root) {
+        return launch(c, "csmooth_map", k_colmap, flat, NT, 0, ColmapArgs{v, n_bins, ld, n_ch, root});
+    };
+    auto recombine = [&](const double* mp) {
+        return launch(c, "csmooth_recombine", dssmooth::k_recombine, flat, NT, 0,
+                      dssmooth::RecombineArgs{mp, n_bins, n_ch, (double2*)dz});
+    };
+    const bool power = domain == DS_SMOOTH_POWER_PHASE || domain == DS_SMOOTH_POWER || domain == DS_SMOOTH_EQUIVALENT_COMPLEX;
+    switch (domain) {
+    case DS_SMOOTH_REAL_IMAGINARY:  // (re, im) interleaved are 2 C real columns as they stand
+        CHK(smooth(dz, ds, 2 * n_ch));
+        return ds_download(c, out, ds, n * 16);
+    case DS_SMOOTH_MAGNITUDE_PHASE:
+    case DS_SMOOTH_POWER_PHASE:  // da = magnitude or power | unwrapped phase, all smoothed
+        CHK(polar(dz, da, db));
+        CHK(launch(c, "csmooth_unwrap", dssmooth::k_unwrap, dim3((unsigned)n_ch), NT, 0,
+                   dssmooth::UnwrapArgs{db + n_ch, n_bins, ld, da + n_ch}));
+        if (power) CHK(colmap(da, 0));
+        CHK(smooth(da, ds, 2 * n_ch));
+        break;
+    case DS_SMOOTH_MAGNITUDE:
+    case DS_SMOOTH_POWER:  // the phase of the input goes straight into ds; only the magnitudes are smoothed
+        CHK(polar(dz, da, ds));
+        if (power) CHK(colmap(da, 0));
+        CHK(smooth(da, ds, n_ch));
+        break;
+    default:  // DS_SMOOTH_EQUIVALENT_COMPLEX: the phase of the smoothed spectrum, the smoothed power
+        CHK(smooth(dz, da, 2 * n_ch));
+        CHK(polar(da, db, ds));
+        CHK(polar(dz, da, db));
+        CHK(colmap(da, 0));
+        CHK(smooth(da, ds, n_ch));
+    }
+    if (power) CHK(colmap(ds, 1));
+    CHK(recombine(ds));
     return ds_download(c, out, dz, n * 16);
 }
 

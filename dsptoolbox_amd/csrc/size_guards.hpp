@@ -24,3 +24,19 @@ constexpr double kSmoothMaxWork = 1e13;
 DS_HD inline bool smooth_work_too_large(int64_t n_bins, int64_t n_window, int64_t n_ch) {
     return (double)n_bins * (double)n_window * (double)n_ch > kSmoothMaxWork;
 }
+
+// k_dft and k_csmooth (kernels_direct.hpp) sum directly as well.  Their work is counted in the terms really summed:
+// frequencies x samples x channels for the plain DFT, the kept sample ranges of every (bin, channel) for the windowed
+// one (each term there costs an exp), the clipped band lengths x channels for complex smoothing (each band point costs a
+// pow).  One call is kept under about a second of device time; the bounds are the measured rates
+// rounded down to one digit: 1.20e12 terms per second for the plain DFT (8 channels x 2^20 samples x 1024 frequencies),
+// 2.03e10 kept terms per second for the windowed one (8 x 65536 samples, 5 cycles: the few low bins that keep the whole
+// signal set the time; with nothing skipped it sums 6.3e11 per second), 2.53e11 for complex smoothing (8 x 65537 bins,
+// 1/3 octave).  Beyond them the entries answer DS_ERR_UNSUP.
+constexpr double kDftMaxWork = 1e12;
+constexpr double kDftWindowedMaxWork = 2e10;
+constexpr double kCsmoothMaxWork = 2e11;
+DS_HD inline bool dft_work_too_large(double terms, bool windowed) {
+    return terms > (windowed ? kDftWindowedMaxWork : kDftMaxWork);
+}
+DS_HD inline bool csmooth_work_too_large(double terms) { return terms > kCsmoothMaxWork; }

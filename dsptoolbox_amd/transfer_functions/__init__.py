@@ -1,7 +1,7 @@
 """compute_transfer_function and spectral_deconvolve
 (API mirror of dsptoolbox/transfer_functions/transfer_functions.py:419-539 and
 :61-184; regularisation window helpers/windows.py:8-76, band detection
-helpers/other.py:9-41)."""
+helpers/other.py:9-41), window_frequency_dependent (:1288-1377) and complex_smoothing (:1788-1876)."""
 
 import numpy as np
 from scipy.fft import next_fast_len
@@ -9,10 +9,11 @@ from scipy.signal.windows import get_window
 
 from .. import backend
 from ..classes import ImpulseResponse, Signal, Spectrum
-from ..standard.enums import SpectrumMethod
-from .enums import TransferFunctionType
+from ..standard.enums import SpectrumMethod, Window
+from .enums import SmoothingDomain, TransferFunctionType
 
-__all__ = ["compute_transfer_function", "spectral_deconvolve", "TransferFunctionType"]
+__all__ = ["compute_transfer_function", "spectral_deconvolve", "window_frequency_dependent", "complex_smoothing",
+           "TransferFunctionType", "SmoothingDomain"]
 
 
 def compute_transfer_function(output: Signal, input: Signal, window_length_samples: int,
@@ -215,3 +216,45 @@ def spectral_deconvolve(output: Signal, input: Signal, apply_regularization: boo
     if padding and keep_original_length:
         new_sig.time_data = new_sig.time_data[:original_length].copy()
     return new_sig
+
+
+# ---- frequency-dependent windowing and complex smoothing (direct sums on the device) -----------------------------
+def _fdw_parameters(time_data: np.ndarray, fs: int, cycles, end_window_value_db: float):
+    """(f, alpha, peak, half) of window_frequency_dependent in the reference's statements
+    (transfer_functions.py:1335-1358): the bins above DC, the Gaussian exponent factor per bin, the peak sample per
+    channel and half the signal's span."""
+    length = time_data.shape[0]
+    end_window_value = 10 ** (end_window_value_db / 20.0)
+    f = np.fft.rfftfreq(length, 1 / fs)[1:]
+    cycles_per_freq_samples = np.round(fs / f * cycles).astype(int)
+    if np.any(cycles_per_freq_samples == 0):
+        raise ValueError("cycles gives a window of zero samples for the highest bins")
+    half = (length - 1) / 2
+    alpha_factor = np.log(1 / (end_window_value) ** 2) ** 0.5 * half
+    peak = np.argmax(np.abs(time_data), axis=0)
+    alpha = (alpha_factor / cycles_per_freq_samples) ** 2.0
+    return f, alpha, peak, half
+
+
+def window_frequency_dependent(ir: ImpulseResponse, cycles: int, end_window_value_db: float = -50.0) -> Spectrum:
+    """The spectrum of an impulse response under a Gaussian window per frequency bin, centred on each channel's peak
+    and `cycles` periods of the bin's frequency wide where it reaches `end_window_value_db`.  The windowed sums run on
+    the device in float64 (ds_dft); window terms below 2^-70 are skipped."""
+    assert type(ir) is ImpulseResponse, "This is only valid for an impulse response"
+    assert end_window_value_db < 0.0, "Window ends must be less than 0 dB"
+    fs = ir.sampling_rate_hz
+    f, alpha, peak, half = _fdw_parameters(ir.time_data, fs, cycles, end_window_value_db)
+    spec = backend.windowed_dft(ir.time_data, f, fs, alpha, peak, half)
+    return Spectrum(np.hstack([0.0, f]), np.pad(spec, ((1, 0), (0, 0))))
+
+
+def complex_smoothing(ir: ImpulseResponse, octave_fraction: float, smoothing_domain: SmoothingDomain,
+                      window: Window = Window.Hann) -> Spectrum:
+    """Complex smoothing of an impulse response's spectrum over +- 1 / (2 octave_fraction) octave around every bin
+    (Hatziantoniou and Mourjopoulos), in the chosen domain, on the device (ds_complex_smooth)."""
+    assert octave_fraction > 0.0, "Octave fraction must be greater than 0"
+    if not isinstance(smoothing_domain, SmoothingDomain):
+        raise ValueError("Invalid smoothing domain")
+    f, sp = ir.get_spectrum()
+    window_values = window(3000, True).astype(np.float64, order="C")
+    return Spectrum(f, backend.complex_smoothing(sp, f, octave_fraction, smoothing_domain, window_values))

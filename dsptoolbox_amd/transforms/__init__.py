@@ -3,7 +3,8 @@ row 1) and the STFT consumers log_mel_spectrogram / mfcc / chroma_stft (:113-203
 row 4) on the device.  Same signature, parameter handling and quirks as the reference;
 the frame-wise inverse FFTs and the windowed overlap-add with the squared-window envelope
 (standard/_framed_signal_representation.py:70-137) run in the HIP library (ds_istft).  The continuous wavelet
-transform cwt with Wavelet / MorletWavelet (:687-760, transforms/_transforms.py:29-301) lives in _wavelets.py."""
+transform cwt with Wavelet / MorletWavelet (:687-760, transforms/_transforms.py:29-301) lives in _wavelets.py.
+dft (:1286-1327) is the direct sum at arbitrary frequencies (ds_dft)."""
 
 from __future__ import annotations
 
@@ -14,7 +15,17 @@ from .. import backend
 from ..classes.signal import Signal
 from ._wavelets import MorletWavelet, Wavelet, cwt  # noqa: F401
 
-__all__ = ["istft", "mel_filterbank", "log_mel_spectrogram", "mfcc", "chroma_stft", "cwt", "Wavelet", "MorletWavelet"]
+__all__ = ["istft", "mel_filterbank", "log_mel_spectrogram", "mfcc", "chroma_stft", "cwt", "Wavelet", "MorletWavelet",
+           "dft"]
+
+
+def dft(signal: Signal, frequency_vector_hz) -> np.ndarray:
+    """DFT for any set of frequencies: the (frequency bin, channel) complex128 spectrum of the direct sum, on the
+    device in float64.  The samples of a device-resident signal are read where they are."""
+    freqs = np.asarray(frequency_vector_hz, dtype=np.float64)
+    if signal.on_device and not signal.is_complex_signal:
+        return backend.dft(signal.device_samples, freqs, signal.sampling_rate_hz)
+    return backend.dft(signal.time_data, freqs, signal.sampling_rate_hz)
 
 
 def _pad_trim(td: np.ndarray, desired_length: int) -> np.ndarray:

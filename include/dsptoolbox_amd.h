@@ -445,6 +445,38 @@ int ds_octave_smooth(ds_ctx* ctx, const double* v, int64_t n_bins, int n_ch, con
 int ds_octave_smooth_complex(ds_ctx* ctx, const double* z, int64_t n_bins, int n_ch, const double* k_log,
                              const double* window, int64_t n_window, int clip_magnitude, double* out);
 
+/* ---- direct sums, float64 (csrc/kernels_direct.hpp) --------------------------------------------------------------
+ * ds_dft: out[k][c] = sum_n x[n][c] w_k,c[n] exp(-2 pi i freqs_hz[k] n / fs_hz) for ANY frequencies (0, negative and
+ * beyond fs / 2 included) -- transforms.dft of the reference (transforms/transforms.py:1286-1327).  x (n_samples, n_ch)
+ * float64 and out (n_freq, n_ch) complex128 are host arrays.  alpha NULL: w = 1.  Otherwise the Gaussian window of
+ * transfer_functions.window_frequency_dependent (transfer_functions/transfer_functions.py:1288-1377):
+ * w_k,c[n] = exp(alpha[k] * -0.5 ((n - peak[c]) / half)^2), alpha [n_freq], peak [n_ch] sample indices; terms whose
+ * weight is below 2^min_weight_log2 are skipped per (bin, channel) (-70 keeps the skipped sum 12 orders below the
+ * result; -INFINITY keeps every term).  ds_dft_dev: the same on device-resident planar float32 samples
+ * (x_dev[c * ldx + n]), widened on load.  n_freq = 0 or n_ch = 0: nothing is launched.  The terms summed -- n_freq *
+ * n_samples * n_ch, or the kept ranges of the windowed form -- are bounded per call (csrc/size_guards.hpp):
+ * DS_ERR_UNSUP beyond, before anything is uploaded.
+ * ds_complex_smooth: the band sums of transfer_functions.complex_smoothing (:1788-1876) and the domain transforms
+ * around them.  z, out (n_bins, n_ch) complex128 on the host.  Per bin i the caller gives the band [ind_low, ind_high)
+ * clipped to the spectrum, its unclipped window_length and pass (non-zero: the bin is copied); the device evaluates
+ * W_i[m] = interp(10^linspace(log10 3, 0, window_length)[m] - 2, window_x, window_y) on the n_window-point prototype,
+ * and out[i] = sum_m W_i[m] q[ind_low + m] / sum_m W_i[m] with q the domain's quantity.  The band lengths x n_ch are
+ * bounded as above.                                                                                               */
+#define DS_SMOOTH_REAL_IMAGINARY     0
+#define DS_SMOOTH_POWER_PHASE        1
+#define DS_SMOOTH_MAGNITUDE_PHASE    2
+#define DS_SMOOTH_POWER              3
+#define DS_SMOOTH_MAGNITUDE          4
+#define DS_SMOOTH_EQUIVALENT_COMPLEX 5
+int ds_dft(ds_ctx* ctx, const double* x, int64_t n_samples, int n_ch, const double* freqs_hz, int64_t n_freq,
+           double fs_hz, const double* alpha, const int64_t* peak, double half, double min_weight_log2, double* out);
+int ds_dft_dev(ds_ctx* ctx, const float* x_dev, int n_ch, int64_t ldx, int64_t n_samples, const double* freqs_hz,
+               int64_t n_freq, double fs_hz, const double* alpha, const int64_t* peak, double half,
+               double min_weight_log2, double* out);
+int ds_complex_smooth(ds_ctx* ctx, const double* z, int64_t n_bins, int n_ch, const int32_t* ind_low,
+                      const int32_t* ind_high, const int32_t* window_length, const int32_t* pass,
+                      const double* window_x, const double* window_y, int n_window, int domain, double* out);
+
 /* ---- block-streaming FIR classes with device-resident state ------------------------------
  * One process_block of the reference's real-time classes (classes/fir_filter_realtime.py:75-335),
  * executed literally on buffers that stay on the device between calls; per call only the block
