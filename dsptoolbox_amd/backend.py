@@ -21,6 +21,8 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+from contextlib import contextmanager
+from typing import NamedTuple
 from warnings import warn
 
 import numpy as np
@@ -156,69 +158,44 @@ def _welch_framing(n_samples: int, W: int, overlap_percent: float, window: np.nd
     return hop, n_frames
 
 
-def _welch(x, y, fs_hz: int, window_type, window_length_samples: int, overlap_percent: float,
-           detrend: bool, average: str, scaling: SpectrumScaling):
-    """Welch auto (y None) or cross spectrum; shapes as in the reference."""
-    auto = y is None
-    x = np.asarray(x).squeeze()
-    if not auto:
-        y = np.asarray(y).squeeze()
-        assert x.shape == y.shape, "Shapes of data do not match"
-    assert x.ndim <= 2, f"{x.shape} are too many dimensions. Use flat arrays or 2D-Arrays instead"
-    multi = x.ndim == 2
+class _WelchPlan(NamedTuple):
+    """Everything a Welch call derives from its parameters before it looks at the samples' layout: built once per call by
+    _welch_plan, handed to _welch_route and to the one call the function makes."""
+    W: int
+    B: int            # W // 2 + 1 bins
+    hop: int
+    n_frames: int
+    window: np.ndarray  # float64, read-only (one of _window_array's)
+    detrend: int      # detrend and avg as the ints the C entries take
+    avg: int
+    average: str      # "mean" / "median": what the precision rules ask
+    amp: int          # _finish_params
+    norm_scale: float
+    factor: float
+    phys: int
+
+    def window_for(self, route: str) -> np.ndarray:
+        """The window in the precision of the route's kernels."""
+        return np.ascontiguousarray(self.window, dtype=np.float64) if route == ROUTE_X64 else self.window.astype(np.float32)
+
+    def tail(self, window_ptr, mode: str | None = None, with_avg: bool = True) -> tuple:
+        """The arguments every Welch entry ends with, after its inputs and before its outputs: W, hop, n_frames, window,
+        detrend, avg, [transfer-function mode], amp, norm_scale, factor, phys.  THE place where their order is written
+        (ds_csm_bins_dev averages by the mean only and takes no avg)."""
+        return ((self.W, self.hop, self.n_frames, window_ptr, self.detrend) + ((self.avg,) if with_avg else ())
+                + (() if mode is None else (DS_TF[mode],)) + (self.amp, self.norm_scale, self.factor, self.phys))
+
+
+def _welch_plan(n_samples: int, fs_hz: int, window_type, window_length_samples: int, overlap_percent: float, detrend: bool,
+                average: str, scaling: SpectrumScaling) -> _WelchPlan:
+    """The reference's assertions (window length, then overlap, then average), the cached window, the framing (with its
+    COLA warning) and the finish parameters."""
     _welch_checks(window_length_samples, overlap_percent, average)
     W = int(window_length_samples)
     window = _window_array(window_type, W)
-    hop, n_frames = _welch_framing(x.shape[0], W, overlap_percent, window)
-    amp, norm_scale, factor, phys = _finish_params(scaling, W, fs_hz, window)
-    avg = DS_AVG[average]
-    ctx = get_context()
-    B = W // 2 + 1
-    n_chan = x.shape[1] if multi else 1
-    if _x64_short(SPEC_PRECISION, (1 if auto else 2) * n_chan, n_frames, W, average):
-        # short estimate: the reference's own float64 arithmetic on the device (ds_welch_spec_x64)
-        x64 = np.ascontiguousarray(x.reshape(x.shape[0], n_chan), dtype=np.float64)
-        y64 = None if auto else np.ascontiguousarray(y.reshape(x.shape[0], n_chan), dtype=np.float64)
-        w64 = np.ascontiguousarray(window, dtype=np.float64)
-        out = np.empty((B, n_chan), dtype=np.complex128)
-        ctx.check(ctx.lib.ds_welch_spec_x64(ctx.handle, _ptr(x64), None if auto else _ptr(y64), n_chan, x.shape[0], W, hop,
-                                            n_frames, _ptr(w64), int(bool(detrend)), avg, amp, norm_scale, factor, phys,
-                                            _ptr(out)), "ds_welch_spec_x64")
-        res = out if (not auto or avg) else np.ascontiguousarray(out.real)  # (median auto spectra are complex in the reference)
-        return res if multi else res[:, 0]
-    w32 = window.astype(np.float32)
-    if auto and _fusable(x):
-        n, n_ch = x.shape
-        out = np.empty((B, n_ch), dtype=np.float32)
-        ctx.check(ctx.lib.ds_welch_psd_f64(ctx.handle, _ptr(x), n_ch, n, W, hop, n_frames, _ptr(w32),
-                                           int(bool(detrend)), avg, amp, norm_scale, factor, phys,
-                                           _ptr(out)), "ds_welch_psd_f64")
-        res = out.astype(np.complex128 if avg else np.float64)
-        return res if multi else res[:, 0]
-    if not auto and _fusable(x) and _fusable(y):
-        n, n_ch = x.shape
-        out = np.empty((B, n_ch), dtype=np.complex64)
-        ctx.check(ctx.lib.ds_welch_csd_f64(ctx.handle, _ptr(x), _ptr(y), n_ch, n, W, hop, n_frames, _ptr(w32),
-                                           int(bool(detrend)), avg, amp, norm_scale, factor, phys,
-                                           _ptr(out)), "ds_welch_csd_f64")
-        return _widen(out)
-    xp = _planar_f32(x)
-    n_ch, n = xp.shape
-    if auto:
-        out = np.empty((B, n_ch), dtype=np.float32)
-        ctx.check(ctx.lib.ds_welch_psd(ctx.handle, _ptr(xp), n_ch, n, W, hop, n_frames, _ptr(w32),
-                                       int(bool(detrend)), avg, amp, norm_scale, factor, phys,
-                                       _ptr(out)), "ds_welch_psd")
-        # median averaging makes the reference's autospectrum complex128 (median_re + 1j*median_im)
-        res = out.astype(np.complex128 if avg else np.float64)
-    else:
-        yp = _planar_f32(y)
-        out = np.empty((B, n_ch), dtype=np.complex64)
-        ctx.check(ctx.lib.ds_welch_csd(ctx.handle, _ptr(xp), _ptr(yp), n_ch, n, W, hop, n_frames,
-                                       _ptr(w32), int(bool(detrend)), avg, amp, norm_scale, factor,
-                                       phys, _ptr(out)), "ds_welch_csd")
-        res = out.astype(np.complex128)
-    return res if multi else res[:, 0]
+    hop, n_frames = _welch_framing(n_samples, W, overlap_percent, window)
+    return _WelchPlan(W, W // 2 + 1, hop, n_frames, window, int(bool(detrend)), DS_AVG[average], average,
+                      *_finish_params(scaling, W, fs_hz, window))
 
 
 # Arithmetic of the transfer-function estimate behind the reference-shaped API
@@ -282,6 +259,118 @@ def _tf_x64_applies(precision, n_cx: int, n_cy: int, n_frames: int, W: int, aver
     return False
 
 
+ROUTE_X64, ROUTE_FUSED, ROUTE_PLANAR, ROUTE_RESIDENT = "x64", "fused", "planar", "resident"
+
+
+def _welch_route(plan: _WelchPlan, kind: str, channels, holds: str = "host", precision: str | None = None) -> str:
+    """Transport and precision of one Welch call -- THE place that chooses between
+        ROUTE_X64       float64 kernels fed from host float64 arrays (a caller with resident samples hands in its host copy),
+        ROUTE_FUSED     fp32 kernels, the caller's large float64 array cast + transposed by the library on its way up,
+        ROUTE_PLANAR    fp32 kernels, planar float32 made here and uploaded,
+        ROUTE_RESIDENT  fp32 kernels over samples that are in HBM already.
+    kind: "spectra" (channels = spectra estimated: C auto, 2 C cross), "tf" (channels = (inputs, outputs); precision as
+    welch_transfer_function's) or "matrix" (channels = C).  holds: "host", "fusable" (every array _fusable) or "resident".
+    SPEC_PRECISION is read here, at call time."""
+    if kind == "tf":
+        x64 = _tf_x64_applies(precision, channels[0], channels[1], plan.n_frames, plan.W, plan.average)
+    elif kind == "matrix":
+        x64 = (channels <= 1024 and _x64_short(SPEC_PRECISION, channels, plan.n_frames, plan.W, plan.average, cap=_X64_MATRIX_BYTES)
+               and plan.B * channels * channels * 16 <= _X64_MATRIX_BYTES)  # (the matrix itself, complex128, crosses PCIe too)
+    else:
+        x64 = _x64_short(SPEC_PRECISION, channels, plan.n_frames, plan.W, plan.average)
+    if x64:
+        return ROUTE_X64
+    return ROUTE_RESIDENT if holds == "resident" else ROUTE_FUSED if holds == "fusable" else ROUTE_PLANAR
+
+
+def _host_input(a: np.ndarray, route: str) -> np.ndarray:
+    """An (N, C) array as the host entries of `route` read it: float64 for the float64 kernels, as it is for the fused
+    transport, planar float32 otherwise."""
+    if route == ROUTE_X64:
+        return np.ascontiguousarray(a, dtype=np.float64)
+    return a if route == ROUTE_FUSED else _planar_f32(a)
+
+
+class _DeviceScope:
+    """Device buffers of one call (see device_scope)."""
+    __slots__ = ("ctx", "_temps", "_results")
+
+    def __init__(self, ctx):
+        self.ctx, self._temps, self._results = ctx, [], []
+
+    def alloc(self, nbytes: int, result: bool = False) -> DeviceBuffer:
+        """A buffer of the call; result=True: the one that leaves with what the call returns."""
+        buf = DeviceBuffer(self.ctx, nbytes)
+        (self._results if result else self._temps).append(buf)
+        return buf
+
+    def upload(self, arr: np.ndarray) -> DeviceBuffer:
+        arr = np.ascontiguousarray(arr)
+        buf = self.alloc(arr.nbytes)
+        self.ctx.upload(buf.ptr, arr)
+        return buf
+
+
+@contextmanager
+def device_scope(ctx):
+    """with device_scope(ctx) as dev: the temporaries of dev.alloc / dev.upload are freed on the way out, a result buffer
+    (alloc(..., result=True)) survives a clean exit and is freed when the body raises.  Context-owned or borrowed memory
+    (_window_dev, _result_scratch, a DevicePlanar) is simply not registered.  A kernel that may still read a temporary
+    when the body ends needs its ctx.sync() inside the body."""
+    dev = _DeviceScope(ctx)
+    try:
+        yield dev
+    except BaseException:
+        for buf in dev._results:
+            buf.free()
+        raise
+    finally:
+        for buf in dev._temps:
+            buf.free()
+
+
+def _welch(x, y, fs_hz: int, window_type, window_length_samples: int, overlap_percent: float,
+           detrend: bool, average: str, scaling: SpectrumScaling):
+    """Welch auto (y None) or cross spectrum; shapes as in the reference."""
+    auto = y is None
+    x = np.asarray(x).squeeze()
+    if not auto:
+        y = np.asarray(y).squeeze()
+        assert x.shape == y.shape, "Shapes of data do not match"
+    assert x.ndim <= 2, f"{x.shape} are too many dimensions. Use flat arrays or 2D-Arrays instead"
+    return _spectra_host(_welch_plan(x.shape[0], fs_hz, window_type, window_length_samples, overlap_percent, detrend, average,
+                                     scaling), x, y)
+
+
+def _spectra_host(plan: _WelchPlan, x: np.ndarray, y: np.ndarray | None):
+    """The host routes of the auto (y None) or cross spectra of flat or (N, C) arrays, for a plan of their length."""
+    auto = y is None
+    multi = x.ndim == 2
+    n, n_ch = x.shape[0], (x.shape[1] if multi else 1)
+    # a short estimate takes the reference's own float64 arithmetic on the device (ds_welch_spec_x64)
+    route = _welch_route(plan, "spectra", (1 if auto else 2) * n_ch,
+                         "fusable" if _fusable(x) and (auto or _fusable(y)) else "host")
+    arrays = [_host_input(a.reshape(n, n_ch), route) for a in ((x,) if auto else (x, y))]
+    inputs = [_ptr(a) for a in arrays]
+    w = plan.window_for(route)
+    ctx = get_context()
+    if route == ROUTE_X64:
+        out = np.empty((plan.B, n_ch), dtype=np.complex128)
+        ctx.check(ctx.lib.ds_welch_spec_x64(ctx.handle, inputs[0], None if auto else inputs[1], n_ch, n, *plan.tail(_ptr(w)),
+                                            _ptr(out)), "ds_welch_spec_x64")
+        res = out if (not auto or plan.avg) else np.ascontiguousarray(out.real)
+    else:
+        name = ("ds_welch_psd" if auto else "ds_welch_csd") + ("_f64" if route == ROUTE_FUSED else "")
+        out = np.empty((plan.B, n_ch), dtype=np.float32 if auto else np.complex64)
+        ctx.check(getattr(ctx.lib, name)(ctx.handle, *inputs, n_ch, n, *plan.tail(_ptr(w)), _ptr(out)), name)
+        # median averaging makes the reference's autospectrum complex128 (median_re + 1j*median_im)
+        res = out.astype(np.complex128 if plan.avg else np.float64) if auto else _widen(out)
+    return res if multi else res[:, 0]
+
+
+_TF_ENTRY = {ROUTE_X64: "ds_welch_tf_x64", ROUTE_FUSED: "ds_welch_tf_f64", ROUTE_PLANAR: "ds_welch_tf"}
+
+
 def welch_transfer_function(output_td, input_td, fs_hz: int, window_length_samples: int, mode: str,
                             window_type=Window.Hann, overlap_percent: float = 50.0,
                             detrend: bool = True, average: str = "mean",
@@ -290,77 +379,40 @@ def welch_transfer_function(output_td, input_td, fs_hz: int, window_length_sampl
     """H1/H2/H3 + coherence for every output channel in one device call.
     output_td (N, Cy); input_td (N, 1) or (N, Cy).  -> (tf complex128 (B, Cy),
     coherence float64 (B, Cy)).  precision: "f32" (default), "f64" or "auto" (see TF_PRECISION)."""
-    _welch_checks(window_length_samples, overlap_percent, average)
-    if mode not in DS_TF:
-        raise ValueError("Unsupported transfer function type")
-    W = int(window_length_samples)
-    window = _window_array(window_type, W)
     yo, xi = np.asarray(output_td), np.asarray(input_td)
     if yo.ndim == 1:
         yo = yo[:, None]
     if xi.ndim == 1:
         xi = xi[:, None]
-    if precision not in (None, "f32"):
-        n = yo.shape[0]
-        assert xi.shape[0] == n, "Signal lengths do not match"
-        hop, n_frames = _welch_framing(n, W, overlap_percent, window)
-        if _tf_x64_applies(precision, xi.shape[1], yo.shape[1], n_frames, W, average):
-            amp, norm_scale, factor, phys = _finish_params(scaling, W, fs_hz, window)
-            y64 = np.ascontiguousarray(yo, dtype=np.float64)
-            x64 = np.ascontiguousarray(xi, dtype=np.float64)
-            w64 = np.ascontiguousarray(window, dtype=np.float64)
-            B = W // 2 + 1
-            tf = np.empty((B, yo.shape[1]), dtype=np.complex128)
-            coh = np.empty((B, yo.shape[1]), dtype=np.float64)
-            ctx = get_context()
-            ctx.check(ctx.lib.ds_welch_tf_x64(ctx.handle, _ptr(x64), x64.shape[1], _ptr(y64), y64.shape[1], n, W,
-                                              hop, n_frames, _ptr(w64), int(bool(detrend)), DS_AVG[average], DS_TF[mode], amp,
-                                              norm_scale, factor, phys, _ptr(tf), _ptr(coh)), "ds_welch_tf_x64")
-            return tf, coh
+    return _tf_host(_welch_plan(yo.shape[0], fs_hz, window_type, window_length_samples, overlap_percent, detrend, average,
+                                scaling), yo, xi, mode, precision)
+
+
+def _tf_host(plan: _WelchPlan, yo: np.ndarray, xi: np.ndarray, mode: str, precision: str | None):
+    """The host routes of the transfer function of (N, Cy) outputs and (N, Cx) inputs, for a plan of N samples."""
+    n, n_cy, n_cx = yo.shape[0], yo.shape[1], xi.shape[1]
+    if mode not in DS_TF:
+        raise ValueError("Unsupported transfer function type")
+    assert xi.shape[0] == n, "Signal lengths do not match"
     # large float64 C-order arrays (the reference's own layout) cross the boundary as they are: the
     # library casts + transposes them in threads straight into pinned upload chunks
     fused = _fusable(yo) and xi.ndim == 2 and xi.dtype == np.float64 and xi.flags.c_contiguous
-    if fused:
-        n, n_cy = yo.shape
-        n_cx = xi.shape[1]
-        assert xi.shape[0] == n, "Signal lengths do not match"
-    else:
-        yp, xp = _planar_f32(yo), _planar_f32(xi)
-        n_cy, n = yp.shape
-        n_cx = xp.shape[0]
-        assert xp.shape[1] == n, "Signal lengths do not match"
-    hop, n_frames = _welch_framing(n, W, overlap_percent, window)
-    amp, norm_scale, factor, phys = _finish_params(scaling, W, fs_hz, window)
-    w32 = window.astype(np.float32)
-    B = W // 2 + 1
-    tf = np.empty((B, n_cy), dtype=np.complex64)
-    coh = np.empty((B, n_cy), dtype=np.float32)
+    route = _welch_route(plan, "tf", (n_cx, n_cy), "fusable" if fused else "host", precision)
+    x_in, y_in, w = _host_input(xi, route), _host_input(yo, route), plan.window_for(route)
+    x64 = route == ROUTE_X64
+    tf = np.empty((plan.B, n_cy), dtype=np.complex128 if x64 else np.complex64)
+    coh = np.empty((plan.B, n_cy), dtype=np.float64 if x64 else np.float32)
     ctx = get_context()
-    if fused:
-        ctx.check(ctx.lib.ds_welch_tf_f64(ctx.handle, _ptr(xi), n_cx, _ptr(yo), n_cy, n, W, hop, n_frames,
-                                          _ptr(w32), int(bool(detrend)), DS_AVG[average], DS_TF[mode], amp,
-                                          norm_scale, factor, phys, _ptr(tf), _ptr(coh)), "ds_welch_tf_f64")
-    else:
-        ctx.check(ctx.lib.ds_welch_tf(ctx.handle, _ptr(xp), n_cx, _ptr(yp), n_cy, n, W, hop, n_frames,
-                                      _ptr(w32), int(bool(detrend)), DS_AVG[average], DS_TF[mode], amp,
-                                      norm_scale, factor, phys, _ptr(tf), _ptr(coh)), "ds_welch_tf")
-    return tf.astype(np.complex128), coh.astype(np.float64)
+    ctx.check(getattr(ctx.lib, _TF_ENTRY[route])(ctx.handle, _ptr(x_in), n_cx, _ptr(y_in), n_cy, n, *plan.tail(_ptr(w), mode),
+                                                 _ptr(tf), _ptr(coh)), _TF_ENTRY[route])
+    return (tf, coh) if x64 else (tf.astype(np.complex128), coh.astype(np.float64))
 
 
 # ---- the same calls over samples that are ALREADY in HBM (Signal.to_device / from_planar_f32) -------------------------
 # No cast, no transpose, no upload of the signal; small results come down through the context's page-locked staging
 # buffer, results that are signals stay on the device (DevicePlanar).  Windows and taps are a few KB: uploaded per call.
-class _Borrowed:
-    """A context-owned device buffer lent to one call: free() is a no-op."""
-
-    def __init__(self, buf):  # a DeviceBuffer, or a DevicePlanar (device-resident samples)
-        self.ptr, self.nbytes, self.ctx = buf.ptr, getattr(buf, "nbytes", 0), buf.ctx
-
-    def free(self):
-        pass
-
-
-def _window_dev(ctx, window: np.ndarray):
+# The window and the result scratch below belong to the context: a call borrows them and frees nothing.
+def _window_dev(ctx, window: np.ndarray) -> DeviceBuffer:
     """The float32 window on the device, kept per context (a handful of KB each, keyed by content): a resident call
     neither allocates nor uploads one (hipMalloc + hipFree cost more than the 0.12 ms of kernels they surround)."""
     cache = ctx.__dict__.setdefault("_window_cache", {})
@@ -371,10 +423,10 @@ def _window_dev(ctx, window: np.ndarray):
             cache.pop(next(iter(cache)))[0].free()
         # (the window object rides along: an id is only a key while its object lives)
         hit = cache[key] = (DeviceBuffer.from_array(ctx, np.ascontiguousarray(window, dtype=np.float32)), window)
-    return _Borrowed(hit[0])
+    return hit[0]
 
 
-def _result_scratch(ctx, nbytes: int):
+def _result_scratch(ctx, nbytes: int) -> DeviceBuffer:
     """Context-owned device buffer for SMALL results that are downloaded before the call returns (transfer functions,
     spectra): reused by every call of the thread, grown when needed."""
     cur = ctx.__dict__.get("_result_scratch")
@@ -382,64 +434,56 @@ def _result_scratch(ctx, nbytes: int):
         if cur is not None:
             cur.free()
         cur = ctx.__dict__["_result_scratch"] = DeviceBuffer(ctx, max(int(nbytes), 1 << 22))
-    return _Borrowed(cur)
+    return cur
+
+
+def _tf_resident(plan: _WelchPlan, y_dev: DevicePlanar, x_dev: DevicePlanar, mode: str, narrow: bool):
+    """ROUTE_RESIDENT of the transfer function (ds_welch_tf_dev) for a plan of y_dev.n_samples samples."""
+    if mode not in DS_TF:
+        raise ValueError("Unsupported transfer function type")
+    n, n_cy = y_dev.n_samples, y_dev.n_ch
+    assert x_dev.n_samples == n, "Signal lengths do not match"
+    ctx = y_dev.ctx
+    n_tf = plan.B * n_cy * 8
+    d_w, d_res = _window_dev(ctx, plan.window), _result_scratch(ctx, n_tf + n_tf // 2)
+    ctx.check(ctx.lib.ds_welch_tf_dev(ctx.handle, C.c_void_p(x_dev.ptr), x_dev.n_ch, x_dev.ld, C.c_void_p(y_dev.ptr), n_cy,
+                                      y_dev.ld, n, *plan.tail(C.c_void_p(d_w.ptr), mode), C.c_void_p(d_res.ptr),
+                                      C.c_void_p(d_res.ptr + n_tf)), "ds_welch_tf_dev")
+    raw = ctx.download_result(d_res.ptr, (n_tf + n_tf // 2,), np.uint8)
+    tf = raw[:n_tf].view(np.complex64).reshape(plan.B, n_cy)
+    coh = raw[n_tf:].view(np.float32).reshape(plan.B, n_cy)
+    return (tf, coh) if narrow else (_widen(tf), _widen(coh))
 
 
 def welch_transfer_function_device(y_dev: DevicePlanar, x_dev: DevicePlanar, fs_hz: int, window_length_samples: int,
                                    mode: str, window_type=Window.Hann, overlap_percent: float = 50.0,
                                    detrend: bool = True, average: str = "mean",
                                    scaling: SpectrumScaling = SpectrumScaling.FFTBackward, narrow: bool = False):
-    """welch_transfer_function on device-resident planar float32 samples (fp32 kernels, ds_welch_tf_dev).
+    """welch_transfer_function on device-resident planar float32 samples (fp32 kernels, ds_welch_tf_dev): the resident
+    route whatever _welch_route would say -- a caller that wants the precision rule asks it first, as
+    compute_transfer_function does.
     -> (tf complex128 (B, Cy), coherence float64 (B, Cy)); narrow=True: the complex64 / float32 arrays as they came
     off the device (page-locked, owned by the caller) -- what Spectrum widens on first access."""
-    _welch_checks(window_length_samples, overlap_percent, average)
-    if mode not in DS_TF:
-        raise ValueError("Unsupported transfer function type")
-    W = int(window_length_samples)
-    window = _window_array(window_type, W)
-    n, n_cy, n_cx = y_dev.n_samples, y_dev.n_ch, x_dev.n_ch
-    assert x_dev.n_samples == n, "Signal lengths do not match"
-    hop, n_frames = _welch_framing(n, W, overlap_percent, window)
-    amp, norm_scale, factor, phys = _finish_params(scaling, W, fs_hz, window)
-    B = W // 2 + 1
-    ctx = y_dev.ctx
-    d_w = _window_dev(ctx, window)
-    d_res = _result_scratch(ctx, B * n_cy * 12)
-    try:
-        ctx.check(ctx.lib.ds_welch_tf_dev(ctx.handle, C.c_void_p(x_dev.ptr), n_cx, x_dev.ld, C.c_void_p(y_dev.ptr), n_cy,
-                                          y_dev.ld, n, W, hop, n_frames, C.c_void_p(d_w.ptr), int(bool(detrend)),
-                                          DS_AVG[average], DS_TF[mode], amp, norm_scale, factor, phys,
-                                          C.c_void_p(d_res.ptr), C.c_void_p(d_res.ptr + B * n_cy * 8)), "ds_welch_tf_dev")
-        raw = ctx.download_result(d_res.ptr, (B * n_cy * 12,), np.uint8)
-        tf = raw[:B * n_cy * 8].view(np.complex64).reshape(B, n_cy)
-        coh = raw[B * n_cy * 8:].view(np.float32).reshape(B, n_cy)
-    finally:
-        d_w.free()
-        d_res.free()
-    return (tf, coh) if narrow else (_widen(tf), _widen(coh))
+    plan = _welch_plan(y_dev.n_samples, fs_hz, window_type, window_length_samples, overlap_percent, detrend, average, scaling)
+    return _tf_resident(plan, y_dev, x_dev, mode, narrow)
+
+
+def _psd_resident(plan: _WelchPlan, x_dev: DevicePlanar):
+    """ROUTE_RESIDENT of the auto spectra (ds_welch_psd_dev) for a plan of x_dev.n_samples samples."""
+    ctx = x_dev.ctx
+    d_w, d_o = _window_dev(ctx, plan.window), _result_scratch(ctx, plan.B * x_dev.n_ch * 4)
+    ctx.check(ctx.lib.ds_welch_psd_dev(ctx.handle, C.c_void_p(x_dev.ptr), x_dev.n_ch, x_dev.ld, x_dev.n_samples,
+                                       *plan.tail(C.c_void_p(d_w.ptr)), C.c_void_p(d_o.ptr)), "ds_welch_psd_dev")
+    out = ctx.download_staged(d_o.ptr, (plan.B, x_dev.n_ch), np.float32)
+    return out.astype(np.complex128 if plan.avg else np.float64)
 
 
 def _welch_psd_device(x_dev: DevicePlanar, fs_hz: int, window_type, window_length_samples: int, overlap_percent: float,
                       detrend: bool, average: str, scaling: SpectrumScaling):
-    """Welch auto spectra of every channel of a device-resident signal (ds_welch_psd_dev) -> (B, C) as _welch."""
-    _welch_checks(window_length_samples, overlap_percent, average)
-    W = int(window_length_samples)
-    window = _window_array(window_type, W)
-    hop, n_frames = _welch_framing(x_dev.n_samples, W, overlap_percent, window)
-    amp, norm_scale, factor, phys = _finish_params(scaling, W, fs_hz, window)
-    B = W // 2 + 1
-    ctx = x_dev.ctx
-    d_w = _window_dev(ctx, window)
-    d_o = _result_scratch(ctx, B * x_dev.n_ch * 4)
-    try:
-        ctx.check(ctx.lib.ds_welch_psd_dev(ctx.handle, C.c_void_p(x_dev.ptr), x_dev.n_ch, x_dev.ld, x_dev.n_samples, W, hop,
-                                           n_frames, C.c_void_p(d_w.ptr), int(bool(detrend)), DS_AVG[average], amp, norm_scale,
-                                           factor, phys, C.c_void_p(d_o.ptr)), "ds_welch_psd_dev")
-        out = ctx.download_staged(d_o.ptr, (B, x_dev.n_ch), np.float32)
-        return out.astype(np.complex128 if DS_AVG[average] else np.float64)
-    finally:
-        d_w.free()
-        d_o.free()
+    """Welch auto spectra of every channel of a device-resident signal (ds_welch_psd_dev) -> (B, C) as _welch.  The
+    resident route whatever _welch_route would say (Signal.get_spectrum asks it first)."""
+    return _psd_resident(_welch_plan(x_dev.n_samples, fs_hz, window_type, window_length_samples, overlap_percent, detrend,
+                                     average, scaling), x_dev)
 
 
 class DeviceSTFT:
@@ -480,20 +524,17 @@ def _stft_device(x_dev: DevicePlanar, fs_hz: int, window_length_samples: int, wi
     ctx = x_dev.ctx
     d_w = _window_dev(ctx, pl["w32"])
     shape = (pl["B"], pl["n_frames"], pl["n_ch"])
-    d_s = DeviceBuffer(ctx, int(np.prod(shape)) * 8)
-    try:
+    with device_scope(ctx) as dev:
+        d_s = dev.alloc(int(np.prod(shape)) * 8, result=keep_on_device)
         ctx.check(ctx.lib.ds_stft_r2c_dev(ctx.handle, C.c_void_p(x_dev.ptr), pl["n"], pl["n_ch"], x_dev.ld, pl["W"], pl["hop"],
                                           pl["nfft"], pl["pad_front"], pl["n_frames"], C.c_void_p(d_w.ptr), int(bool(detrend)),
                                           pl["scale"], pl["edge"], pl["power"], C.c_void_p(d_s.ptr)), "ds_stft_r2c_dev")
-        dev = DeviceSTFT(d_s, shape, pl["power"])
+        stft = DeviceSTFT(d_s, shape, pl["power"])
         if keep_on_device:
-            ctx.sync()  # (the window buffer is freed below)
-            return pl["time_s"], pl["freqs_hz"], dev
-        out = dev.to_host()
-        d_s.free()
-        return pl["time_s"], pl["freqs_hz"], out
-    finally:
-        d_w.free()
+            ctx.sync()
+        else:
+            stft = stft.to_host()
+    return pl["time_s"], pl["freqs_hz"], stft
 
 
 class _ShapeOnly:
@@ -511,17 +552,12 @@ def fir_filter_bank_device(x_dev: DevicePlanar, taps_list, mode: int):
     ctx = x_dev.ctx
     n, n_ch = x_dev.n_samples, x_dev.n_ch
     n_out = k if mode == DS_FB_PARALLEL else 1
-    d_t = DeviceBuffer.from_array(ctx, taps)
-    d_y = DeviceBuffer(ctx, n_out * n_ch * n * 4)
-    try:
+    with device_scope(ctx) as dev:
+        d_t = dev.upload(taps)
+        d_y = dev.alloc(n_out * n_ch * n * 4, result=True)
         ctx.check(ctx.lib.ds_fir_ola_dev(ctx.handle, C.c_void_p(x_dev.ptr), n_ch, x_dev.ld, n, C.c_void_p(d_t.ptr), k, t,
                                          int(mode), C.c_void_p(d_y.ptr), n), "ds_fir_ola_dev")
-        ctx.sync()  # (the taps buffer is freed below)
-    except BaseException:
-        d_y.free()
-        raise
-    finally:
-        d_t.free()
+        ctx.sync()  # (the taps buffer is freed on the way out)
     outs = [DevicePlanar(d_y, n_ch, n, n, 4 * i * n_ch * n) for i in range(n_out)]
     return outs if mode == DS_FB_PARALLEL else outs[0]
 
@@ -538,17 +574,12 @@ def _istft_device(stft: DeviceSTFT, nfft: int, W: int, step: int, window, scale:
     total_length = int(step * n_frames_total + W * (1 - step / W))
     ctx = stft.buf.ctx
     d_w = _window_dev(ctx, window)
-    d_o = DeviceBuffer(ctx, n_ch * total_length * 4)
-    try:
+    with device_scope(ctx) as dev:
+        d_o = dev.alloc(n_ch * total_length * 4, result=True)
         ctx.check(ctx.lib.ds_istft_dev(ctx.handle, C.c_void_p(stft.buf.ptr), n_bins, n_frames, n_ch, nfft, W, step,
                                        frame_offset, n_frames_total, C.c_void_p(d_w.ptr), float(scale), total_length,
                                        C.c_void_p(d_o.ptr), total_length), "ds_istft_dev")
         ctx.sync()
-    except BaseException:
-        d_o.free()
-        raise
-    finally:
-        d_w.free()
     return DevicePlanar(d_o, n_ch, total_length)
 
 
@@ -562,28 +593,21 @@ def spectral_division_device(y_dev: DevicePlanar, x_dev: DevicePlanar, n_fft: in
     n, n_cy, n_cx = y_dev.n_samples, y_dev.n_ch, x_dev.n_ch
     assert x_dev.n_samples == n and n <= n_fft and n_out <= n_fft
     B = n_fft // 2 + 1
-    d_xs = DeviceBuffer(ctx, B * n_cx * 8)
-    d_r = DeviceBuffer(ctx, B * n_cx * 8)
-    d_o = DeviceBuffer(ctx, n_cy * int(n_out) * 4)
-    d_e = None
-    try:
+    with device_scope(ctx) as dev:
+        d_xs = dev.alloc(B * n_cx * 8)
+        d_r = dev.alloc(B * n_cx * 8)
+        d_o = dev.alloc(n_cy * int(n_out) * 4, result=True)
+        d_e = None
         ctx.check(ctx.lib.ds_rfft_dev(ctx.handle, C.c_void_p(x_dev.ptr), n_cx, x_dev.ld, n, int(n_fft), 1.0,
                                       C.c_void_p(d_xs.ptr)), "ds_rfft_dev")
         if eps_from_spectrum is not None:
             den = ctx.download_staged(d_xs.ptr, (B, n_cx), np.complex64).astype(np.complex128)
-            d_e = DeviceBuffer.from_array(ctx, np.ascontiguousarray(eps_from_spectrum(den), dtype=np.float32))
+            d_e = dev.upload(np.ascontiguousarray(eps_from_spectrum(den), dtype=np.float32))
         ctx.check(ctx.lib.ds_deconv_inverse_dev(ctx.handle, C.c_void_p(d_xs.ptr), n_cx, B, C.c_void_p(d_e.ptr) if d_e else None,
                                                 C.c_void_p(d_r.ptr)), "ds_deconv_inverse")
         ctx.check(ctx.lib.ds_deconv_dev(ctx.handle, C.c_void_p(y_dev.ptr), 1, n_cy, y_dev.ld, n, int(n_fft), C.c_void_p(d_r.ptr),
                                         int(n_cx > 1), int(n_out), int(n_out), C.c_void_p(d_o.ptr)), "ds_deconv_dev")
         ctx.sync()
-    except BaseException:
-        d_o.free()
-        raise
-    finally:
-        for d in (d_xs, d_r, d_e):
-            if d is not None:
-                d.free()
     return DevicePlanar(d_o, n_cy, int(n_out))
 
 
@@ -683,14 +707,14 @@ def _spectrogram_band_power(x, fs_hz: int, window_length_samples: int, window_ty
     b1 = np.where(nz.any(axis=1), filt.shape[1] - nz[:, ::-1].argmax(axis=1), 0).astype(np.int32)
     ctx = x.ctx if resident else get_context()
     n_fc = pl["n_frames"] * pl["n_ch"]
-    d_x = _Borrowed(x) if resident else DeviceBuffer.from_array(ctx, pl["xp"])
-    x_ld = x.ld if resident else pl["n"]
-    d_w = DeviceBuffer.from_array(ctx, pl["w32"])
-    d_s = DeviceBuffer(ctx, pl["B"] * n_fc * 8)
-    d_f = DeviceBuffer.from_array(ctx, filt)
-    d_b0, d_b1 = DeviceBuffer.from_array(ctx, b0), DeviceBuffer.from_array(ctx, b1)
-    d_o = DeviceBuffer(ctx, n_bands * n_fc * 4)
-    try:
+    with device_scope(ctx) as dev:
+        d_x = x if resident else dev.upload(pl["xp"])
+        x_ld = x.ld if resident else pl["n"]
+        d_w = dev.upload(pl["w32"])
+        d_s = dev.alloc(pl["B"] * n_fc * 8)
+        d_f = dev.upload(filt)
+        d_b0, d_b1 = dev.upload(b0), dev.upload(b1)
+        d_o = dev.alloc(n_bands * n_fc * 4)
         ctx.check(ctx.lib.ds_stft_r2c_dev(ctx.handle, C.c_void_p(d_x.ptr), pl["n"], pl["n_ch"], x_ld, pl["W"],
                                           pl["hop"], pl["nfft"], pl["pad_front"], pl["n_frames"],
                                           C.c_void_p(d_w.ptr), int(bool(detrend)), pl["scale"], pl["edge"],
@@ -700,9 +724,6 @@ def _spectrogram_band_power(x, fs_hz: int, window_length_samples: int, window_ty
                                             int(bool(to_db)), int(bool(dct_abs)), C.c_void_p(d_o.ptr)),
                   "ds_band_power_dev")
         out = d_o.to_array((n_bands, pl["n_frames"], pl["n_ch"]), np.float32)
-    finally:
-        for d in (d_x, d_w, d_s, d_f, d_b0, d_b1, d_o):
-            d.free()
     return pl["time_s"], pl["freqs_hz"], out.astype(np.float64)
 
 
@@ -805,49 +826,34 @@ def _istft(stft, nfft: int, W: int, step: int, window, scale: float, frame_offse
 _STAGED_RESULT_BYTES = 512 << 20  # largest result that goes through the context's page-locked staging buffer (which stays allocated)
 
 
+_CSM_ENTRY = {ROUTE_X64: "ds_csm_x64", ROUTE_FUSED: "ds_csm_f64", ROUTE_PLANAR: "ds_csm"}
+
+
 def _csm_welch(time_data, sampling_rate_hz: int, window_length_samples: int, window_type,
                overlap_percent, detrend: bool, average: str, scaling: SpectrumScaling):
     """-> (f (B,), csm (B, C, C) complex128)."""
-    _welch_checks(window_length_samples, overlap_percent, average)
-    W = int(window_length_samples)
-    window = _window_array(window_type, W)
     td = np.asarray(time_data)
-    fused = _fusable(td)
-    if fused:
-        n, n_ch = td.shape
-    else:
-        xp = _planar_f32(td)
-        n_ch, n = xp.shape
-    hop, n_frames = _welch_framing(n, W, overlap_percent, window)
-    amp, norm_scale, factor, phys = _finish_params(scaling, W, sampling_rate_hz, window)
-    B = W // 2 + 1
-    if n_ch <= 1024 and _x64_short(SPEC_PRECISION, n_ch, n_frames, W, average, cap=_X64_MATRIX_BYTES) \
-            and B * n_ch * n_ch * 16 <= _X64_MATRIX_BYTES:  # (the matrix itself, complex128, crosses PCIe too)
-        # short estimate: float64 end to end on the device (ds_csm_x64)
-        x64 = np.ascontiguousarray(td.reshape(n, n_ch) if td.ndim == 2 else td[:, None], dtype=np.float64)
-        out64 = np.empty((B, n_ch, n_ch), dtype=np.complex128)
-        w64 = np.ascontiguousarray(window, dtype=np.float64)
-        ctx = get_context()
-        ctx.check(ctx.lib.ds_csm_x64(ctx.handle, _ptr(x64), n_ch, n, W, hop, n_frames, _ptr(w64), int(bool(detrend)),
-                                     DS_AVG[average], amp, norm_scale, factor, phys, _ptr(out64)), "ds_csm_x64")
-        return np.fft.rfftfreq(W, 1 / sampling_rate_hz), out64
-    w32 = window.astype(np.float32)
+    if td.ndim == 1:
+        td = td[:, None]
+    n, n_ch = td.shape
+    plan = _welch_plan(n, sampling_rate_hz, window_type, window_length_samples, overlap_percent, detrend, average, scaling)
+    # a short estimate runs in float64 end to end on the device (ds_csm_x64)
+    route = _welch_route(plan, "matrix", n_ch, "fusable" if _fusable(td) else "host")
+    x, w = _host_input(td, route), plan.window_for(route)
     ctx = get_context()
-    # the complex64 matrices land in the context's page-locked staging buffer (the link's full rate, no first-touch faults of
-    # a fresh array) and are widened out of it into the complex128 array the caller gets
-    # (up to 512 MB; a larger result -- hundreds of channels -- comes back into an ordinary array)
-    nbytes = B * n_ch * n_ch * 8
-    out = (ctx.staging(nbytes).view(np.complex64).reshape(B, n_ch, n_ch) if nbytes <= _STAGED_RESULT_BYTES
-           else np.empty((B, n_ch, n_ch), dtype=np.complex64))
-    if fused:
-        ctx.check(ctx.lib.ds_csm_f64(ctx.handle, _ptr(td), n_ch, n, W, hop, n_frames, _ptr(w32),
-                                     int(bool(detrend)), DS_AVG[average], amp, norm_scale, factor, phys,
-                                     _ptr(out)), "ds_csm_f64")
-    else:
-        ctx.check(ctx.lib.ds_csm(ctx.handle, _ptr(xp), n_ch, n, W, hop, n_frames, _ptr(w32),
-                                 int(bool(detrend)), DS_AVG[average], amp, norm_scale, factor, phys,
-                                 _ptr(out)), "ds_csm")
-    return np.fft.rfftfreq(W, 1 / sampling_rate_hz), _widen(out)
+    shape = (plan.B, n_ch, n_ch)
+    nbytes = plan.B * n_ch * n_ch * 8
+    if route == ROUTE_X64:
+        out = np.empty(shape, dtype=np.complex128)
+    elif nbytes <= _STAGED_RESULT_BYTES:
+        # the complex64 matrices land in the context's page-locked staging buffer (the link's full rate, no first-touch faults
+        # of a fresh array) and are widened out of it into the complex128 array the caller gets
+        out = ctx.staging(nbytes).view(np.complex64).reshape(shape)
+    else:  # (up to 512 MB; a larger result -- hundreds of channels -- comes back into an ordinary array)
+        out = np.empty(shape, dtype=np.complex64)
+    ctx.check(getattr(ctx.lib, _CSM_ENTRY[route])(ctx.handle, _ptr(x), n_ch, n, *plan.tail(_ptr(w)), _ptr(out)),
+              _CSM_ENTRY[route])
+    return np.fft.rfftfreq(plan.W, 1 / sampling_rate_hz), out if route == ROUTE_X64 else _widen(out)
 
 
 class DeviceCSM:
@@ -872,41 +878,21 @@ class DeviceCSM:
 
 def _csm_welch_device(time_data, sampling_rate_hz: int, window_length_samples: int, window_type,
                       overlap_percent, detrend: bool, average: str, scaling: SpectrumScaling) -> DeviceCSM:
-    """_csm_welch whose result stays on the device (ds_csm_dev) -> DeviceCSM.  time_data: the (N, C) array, or the
-    DevicePlanar of a device-resident signal (read in place)."""
-    _welch_checks(window_length_samples, overlap_percent, average)
-    W = int(window_length_samples)
-    window = _window_array(window_type, W)
+    """_csm_welch whose result stays on the device (ds_csm_dev, the fp32 kernels for every shape) -> DeviceCSM.
+    time_data: the (N, C) array, or the DevicePlanar of a device-resident signal (read in place)."""
     resident = isinstance(time_data, DevicePlanar)
-    if resident:
-        ctx, n_ch, n, ld = time_data.ctx, time_data.n_ch, time_data.n_samples, time_data.ld
-        d_x = None
-        x_ptr = time_data.ptr
-    else:
-        xp = _planar_f32(np.asarray(time_data))
-        n_ch, n = xp.shape
-        ld = n
-        ctx = get_context()
-        d_x = DeviceBuffer.from_array(ctx, xp)
-        x_ptr = d_x.ptr
-    hop, n_frames = _welch_framing(n, W, overlap_percent, window)
-    amp, norm_scale, factor, phys = _finish_params(scaling, W, sampling_rate_hz, window)
-    B = W // 2 + 1
-    d_w = DeviceBuffer.from_array(ctx, window.astype(np.float32))
-    d_c = DeviceBuffer(ctx, B * n_ch * n_ch * 8)
-    try:
-        ctx.check(ctx.lib.ds_csm_dev(ctx.handle, C.c_void_p(x_ptr), n_ch, ld, n, W, hop, n_frames,
-                                     C.c_void_p(d_w.ptr), int(bool(detrend)), DS_AVG[average], amp, norm_scale, factor,
-                                     phys, C.c_void_p(d_c.ptr)), "ds_csm_dev")
+    td = time_data if resident else np.asarray(time_data)
+    n = td.n_samples if resident else td.shape[0]
+    plan = _welch_plan(n, sampling_rate_hz, window_type, window_length_samples, overlap_percent, detrend, average, scaling)
+    ctx = td.ctx if resident else get_context()
+    with device_scope(ctx) as dev:
+        x = td if resident else DevicePlanar(dev.upload(_planar_f32(td)), 1 if td.ndim == 1 else td.shape[1], n)
+        d_w = dev.upload(plan.window_for(ROUTE_PLANAR))
+        d_c = dev.alloc(plan.B * x.n_ch * x.n_ch * 8, result=True)  # (the matrix only leaves this function inside a DeviceCSM)
+        ctx.check(ctx.lib.ds_csm_dev(ctx.handle, C.c_void_p(x.ptr), x.n_ch, x.ld, n, *plan.tail(C.c_void_p(d_w.ptr)),
+                                     C.c_void_p(d_c.ptr)), "ds_csm_dev")
         ctx.sync()
-    except BaseException:
-        d_c.free()  # (the matrix only leaves this function inside a DeviceCSM)
-        raise
-    finally:
-        if d_x is not None:
-            d_x.free()
-        d_w.free()
-    return DeviceCSM(ctx, d_c, np.fft.rfftfreq(W, 1 / sampling_rate_hz), n_ch)
+    return DeviceCSM(ctx, d_c, np.fft.rfftfreq(plan.W, 1 / sampling_rate_hz), x.n_ch)
 
 
 def _das_map_device(csm: DeviceCSM, id1: int, id2: int, h, remove_csm_diagonal: bool):
@@ -918,10 +904,10 @@ def _das_map_device(csm: DeviceCSM, id1: int, id2: int, h, remove_csm_diagonal: 
     assert hs.ndim == 3 and hs.shape[0] == nb and hs.shape[1] == csm.n_ch, "steering vector must be (bins, C, grid points)"
     n_grid = hs.shape[2]
     ctx = csm.ctx
-    d_h = DeviceBuffer.from_array(ctx, hs)
-    d_s = DeviceBuffer(ctx, nb * csm.n_ch * csm.n_ch * 8)
-    d_m = DeviceBuffer(ctx, n_grid * nb * 4)
-    try:
+    with device_scope(ctx) as dev:
+        d_h = dev.upload(hs)
+        d_s = dev.alloc(nb * csm.n_ch * csm.n_ch * 8)
+        d_m = dev.alloc(n_grid * nb * 4)
         src = csm.buf.ptr + id1 * csm.n_ch * csm.n_ch * 8
         scale = csm.n_ch / (csm.n_ch - 1) if remove_csm_diagonal else 1.0
         ctx.check(ctx.lib.ds_csm_das_prepare_dev(ctx.handle, C.c_void_p(src), nb, csm.n_ch, float(scale),
@@ -929,9 +915,6 @@ def _das_map_device(csm: DeviceCSM, id1: int, id2: int, h, remove_csm_diagonal: 
         ctx.check(ctx.lib.ds_das_map_dev(ctx.handle, C.c_void_p(d_s.ptr), C.c_void_p(d_h.ptr), nb, csm.n_ch, n_grid,
                                          C.c_void_p(d_m.ptr)), "ds_das_map_dev")
         out = d_m.to_array((n_grid, nb), np.float32)
-    finally:
-        for d in (d_h, d_s, d_m):
-            d.free()
     return out.astype(np.float64)
 
 
@@ -940,28 +923,20 @@ def _csm_welch_bins(time_data, sampling_rate_hz: int, window_length_samples: int
                     bin_stop: int):
     """Rows [bin_start, bin_stop) of the Welch CSM (mean averaging): one rank's share when the
     matrix is split by frequency bins.  -> (bin_stop - bin_start, C, C) complex128."""
-    _welch_checks(window_length_samples, overlap_percent, "mean")
-    W = int(window_length_samples)
-    window = _window_array(window_type, W)
-    xp = _planar_f32(time_data)
-    n_ch, n = xp.shape
-    hop, n_frames = _welch_framing(n, W, overlap_percent, window)
-    amp, norm_scale, factor, phys = _finish_params(scaling, W, sampling_rate_hz, window)
+    td = np.asarray(time_data)
+    n, n_ch = td.shape[0], (1 if td.ndim == 1 else td.shape[1])
+    plan = _welch_plan(n, sampling_rate_hz, window_type, window_length_samples, overlap_percent, detrend, "mean", scaling)
     count = int(bin_stop) - int(bin_start)
     if count <= 0:
         return np.zeros((0, n_ch, n_ch), dtype=np.complex128)
     ctx = get_context()
-    d_x = DeviceBuffer.from_array(ctx, xp)
-    d_w = DeviceBuffer.from_array(ctx, window.astype(np.float32))
-    d_c = DeviceBuffer(ctx, count * n_ch * n_ch * 8)
-    try:
-        ctx.check(ctx.lib.ds_csm_bins_dev(ctx.handle, C.c_void_p(d_x.ptr), n_ch, n, n, W, hop, n_frames,
-                                          C.c_void_p(d_w.ptr), int(bool(detrend)), amp, norm_scale, factor,
-                                          phys, int(bin_start), count, C.c_void_p(d_c.ptr)), "ds_csm_bins_dev")
+    with device_scope(ctx) as dev:
+        d_x = dev.upload(_planar_f32(td))
+        d_w = dev.upload(plan.window_for(ROUTE_PLANAR))
+        d_c = dev.alloc(count * n_ch * n_ch * 8)
+        ctx.check(ctx.lib.ds_csm_bins_dev(ctx.handle, C.c_void_p(d_x.ptr), n_ch, n, n, *plan.tail(C.c_void_p(d_w.ptr), with_avg=False),
+                                          int(bin_start), count, C.c_void_p(d_c.ptr)), "ds_csm_bins_dev")
         out = d_c.to_array((count, n_ch, n_ch), np.complex64)
-    finally:
-        for d in (d_x, d_w, d_c):
-            d.free()
     return out.astype(np.complex128)
 
 
@@ -1051,16 +1026,14 @@ def regularized_inverse(denum_spectrum, eps=None):
     xs = np.ascontiguousarray(denum_spectrum, dtype=np.complex64)
     nb, n_ch = xs.shape
     ctx = get_context()
-    d_x = DeviceBuffer.from_array(ctx, xs)
-    d_e = DeviceBuffer.from_array(ctx, np.ascontiguousarray(eps, dtype=np.float32)) if eps is not None else None
-    d_r = DeviceBuffer(ctx, xs.nbytes)
-    ctx.check(ctx.lib.ds_deconv_inverse_dev(ctx.handle, C.c_void_p(d_x.ptr), n_ch, nb,
-                                            C.c_void_p(d_e.ptr) if d_e else None,
-                                            C.c_void_p(d_r.ptr)), "ds_deconv_inverse")
-    r = d_r.to_array((n_ch, nb), np.complex64)
-    for d in (d_x, d_e, d_r):
-        if d is not None:
-            d.free()
+    with device_scope(ctx) as dev:
+        d_x = dev.upload(xs)
+        d_e = dev.upload(np.ascontiguousarray(eps, dtype=np.float32)) if eps is not None else None
+        d_r = dev.alloc(xs.nbytes)
+        ctx.check(ctx.lib.ds_deconv_inverse_dev(ctx.handle, C.c_void_p(d_x.ptr), n_ch, nb,
+                                                C.c_void_p(d_e.ptr) if d_e else None,
+                                                C.c_void_p(d_r.ptr)), "ds_deconv_inverse")
+        r = d_r.to_array((n_ch, nb), np.complex64)
     return r.T.astype(np.complex128)
 
 
@@ -1270,13 +1243,10 @@ def iir_sos_filter_device(x_dev: DevicePlanar, sos_list, mode: int):
     ctx = x_dev.ctx
     n, n_ch = x_dev.n_samples, x_dev.n_ch
     n_out = k if mode == DS_FB_PARALLEL else 1
-    d_y = DeviceBuffer(ctx, n_out * n_ch * n * 4)
-    try:
+    with device_scope(ctx) as dev:
+        d_y = dev.alloc(n_out * n_ch * n * 4, result=True)
         ctx.check(ctx.lib.ds_iir_sos_dev(ctx.handle, C.c_void_p(x_dev.ptr), n_ch, x_dev.ld, n, _ptr(sos), k, n_sec, None,
                                          int(mode), C.c_void_p(d_y.ptr), n, None), "ds_iir_sos_dev")
-    except BaseException:
-        d_y.free()
-        raise
     outs = [DevicePlanar(d_y, n_ch, n, n, 4 * i * n_ch * n) for i in range(n_out)]
     return outs if mode == DS_FB_PARALLEL else outs[0]
 
@@ -1426,15 +1396,12 @@ def delay_sum_device(x_dev: DevicePlanar, src_len, src, shift, frac, weight, ord
     lens = np.ascontiguousarray(np.broadcast_to(np.asarray(src_len, dtype=np.int64), (x_dev.n_ch,)))
     ctx = x_dev.ctx
     out_len = int(out_len)
-    d_y = DeviceBuffer(ctx, n_rows * out_len * 4)
-    try:
+    with device_scope(ctx) as dev:
+        d_y = dev.alloc(n_rows * out_len * 4, result=True)
         ctx.check(ctx.lib.ds_delay_sum_dev(ctx.handle, C.c_void_p(x_dev.ptr), x_dev.n_ch, x_dev.ld, _ptr(lens), n_rows,
                                            n_terms, _ptr(src), _ptr(shift), _ptr(frac), _ptr(weight), int(order),
                                            float(_kaiser_window_beta(side_lobe_suppression_db)), out_len,
                                            C.c_void_p(d_y.ptr), out_len, None), "ds_delay_sum_dev")
-    except BaseException:
-        d_y.free()
-        raise
     return DevicePlanar(d_y, n_rows, out_len, out_len)
 
 
@@ -1443,20 +1410,17 @@ def stack_device(planars, lengths) -> DevicePlanar:
     of planars[j], zeros after them.  Each row is a pass-through of ds_delay_sum_dev (a unit tap: exact)."""
     ctx = planars[0].ctx
     n_max = int(max(lengths))
-    buf = DeviceBuffer(ctx, len(planars) * n_max * 4)
     one = np.zeros((1, 1), dtype=np.int32)
     zero = np.zeros((1, 1), dtype=np.int64)
     through = np.full((1, 1), -1.0)
     w = np.ones((1, 1))
-    try:
+    with device_scope(ctx) as dev:
+        buf = dev.alloc(len(planars) * n_max * 4, result=True)
         for j, (p, n) in enumerate(zip(planars, lengths)):
             lens = np.array([int(n)], dtype=np.int64)
             ctx.check(ctx.lib.ds_delay_sum_dev(ctx.handle, C.c_void_p(p.ptr), 1, p.ld, _ptr(lens), 1, 1, _ptr(one),
                                                _ptr(zero), _ptr(through), _ptr(w), 1, 0.0, n_max,
                                                C.c_void_p(buf.ptr + 4 * j * n_max), n_max, None), "ds_delay_sum_dev")
-    except BaseException:
-        buf.free()
-        raise
     return DevicePlanar(buf, len(planars), n_max, n_max)
 
 
@@ -1514,13 +1478,10 @@ def cwt_device(x_dev: DevicePlanar, channels, waves) -> DeviceScalogram:
     ch = np.ascontiguousarray(np.asarray(channels, dtype=np.int32).ravel())
     n = x_dev.n_samples
     ctx = x_dev.ctx
-    buf = DeviceBuffer(ctx, max(8 * len(waves) * n * len(ch), 8))
-    try:
+    with device_scope(ctx) as dev:
+        buf = dev.alloc(max(8 * len(waves) * n * len(ch), 8), result=True)
         ctx.check(ctx.lib.ds_cwt_dev(ctx.handle, C.c_void_p(x_dev.ptr), x_dev.n_ch, x_dev.ld, n, _ptr(ch), len(ch),
                                      len(waves), _ptr(lens), _ptr(taps), C.c_void_p(buf.ptr)), "ds_cwt_dev")
-    except BaseException:
-        buf.free()
-        raise
     return DeviceScalogram(buf, (len(waves), n, len(ch)), np.complex64)
 
 
@@ -1539,14 +1500,11 @@ def cwt_squeeze_device(scal: DeviceScalogram, freqs, fs, delta_w: float = 0.05,
         norm **= -3 / 2
         norm = np.ascontiguousarray(norm)
     ctx = scal.buf.ctx
-    buf = DeviceBuffer(ctx, max(16 * n_f * n * n_ch, 16))
-    try:
+    with device_scope(ctx) as dev:
+        buf = dev.alloc(max(16 * n_f * n * n_ch, 16), result=True)
         ctx.check(ctx.lib.ds_cwt_squeeze_dev(ctx.handle, C.c_void_p(scal.buf.ptr), n_f, n, n_ch, _ptr(freqs),
                                              _ptr(delta_f), None if norm is None else _ptr(norm), float(fs),
                                              C.c_void_p(buf.ptr)), "ds_cwt_squeeze_dev")
-    except BaseException:
-        buf.free()
-        raise
     return DeviceScalogram(buf, scal.shape, np.complex128)
 
 

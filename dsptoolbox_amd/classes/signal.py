@@ -350,15 +350,16 @@ class Signal(MultichannelData):
             return self.spectrum[0].copy(), self.spectrum[1].copy()
         par = self._spectrum_parameters
         if self.spectrum_method == SpectrumMethod.WelchPeriodogram:
-            if self.on_device and not self._short_estimate(par):
-                spectrum = backend._welch_psd_device(self.device_samples, self.sampling_rate_hz, par["window_type"],
-                                                     par["window_length_samples"], par["overlap_percent"],
-                                                     par["detrend"], par["average"], par["scaling"])
-            else:
+            plan = self._welch_plan(par) if self.on_device else None
+            if plan is None:  # host samples -- or invalid parameters: the reference's assertion comes from here
                 spectrum = backend._welch(self.time_data, None, self.sampling_rate_hz,
                                           par["window_type"], par["window_length_samples"],
                                           par["overlap_percent"], par["detrend"], par["average"],
                                           par["scaling"])
+            elif backend._welch_route(plan, "spectra", self.number_of_channels, "resident") == backend.ROUTE_RESIDENT:
+                spectrum = backend._psd_resident(plan, self.device_samples)
+            else:  # a short estimate (fewer than 128 frames ...): the float64 kernels read the host arrays
+                spectrum = backend._spectra_host(plan, self.time_data, None)
             if spectrum.ndim == 1:
                 spectrum = spectrum[:, None]
             fft_length = par["window_length_samples"]
@@ -390,15 +391,13 @@ class Signal(MultichannelData):
             self.__spectrum_state_update = False
         return freqs, spectrum
 
-    def _short_estimate(self, par) -> bool:
-        """Would backend._welch / _csm_welch send this signal's Welch estimate through the float64 kernels (fewer than
-        128 frames ...)?  Those take the host arrays."""
-        W = par["window_length_samples"]
-        if W not in [2**k for k in range(3, 19)] or not (0 <= par["overlap_percent"] < 100):
-            return True  # (let the host path raise the reference's assertion)
-        hop = W - int(par["overlap_percent"] / 100 * W)
-        n_frames = int(np.ceil(len(self) / hop))
-        return backend._x64_short(backend.SPEC_PRECISION, self.number_of_channels, n_frames, W, par["average"])
+    def _welch_plan(self, par):
+        """backend._welch_plan of this signal's Welch estimate, None when the parameters are invalid."""
+        try:
+            return backend._welch_plan(len(self), self.sampling_rate_hz, par["window_type"], par["window_length_samples"],
+                                       par["overlap_percent"], par["detrend"], par["average"], par["scaling"])
+        except AssertionError:
+            return None
 
     def get_csm(self, force_computation=False, on_device: bool = False):
         """-> (freqs_hz, csm (bins, channels, channels)).  on_device=True (an extension; Welch method only):

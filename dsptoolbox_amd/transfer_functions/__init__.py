@@ -33,22 +33,25 @@ def compute_transfer_function(output: Signal, input: Signal, window_length_sampl
     if not isinstance(mode, TransferFunctionType):
         raise ValueError("Unsupported transfer function type")
     W = int(window_length_samples)
+    # device-resident samples (Signal.to_device / from_planar_f32): the fp32 kernels read them in place -- unless the
+    # precision rule sends this shape through the float64 kernels, which take the host arrays.  One plan serves the
+    # question and whichever route answers it; with invalid parameters there is none and the reference's assertion
+    # comes from the host function.
+    plan = None
     if output.on_device and not output.is_complex_signal and not input.is_complex_signal:
-        # device-resident samples (Signal.to_device / from_planar_f32): the fp32 kernels read them in place -- unless
-        # the precision rule sends this shape through the float64 kernels, which take the host arrays
-        window = backend._window_array(par["window_type"], W) if W in [2**k for k in range(3, 19)] else None
-        if window is not None:
-            _, n_frames = backend._welch_framing(output.length_samples, W, par["overlap_percent"], window)
-            if not backend._tf_x64_applies(backend.TF_PRECISION, input.number_of_channels, output.number_of_channels,
-                                           n_frames, W, par["average"]):
-                tf, coherence = backend.welch_transfer_function_device(
-                    output.device_samples, input.to_device().device_samples, input.sampling_rate_hz, W, mode.name,
-                    narrow=True, **par)
-                return Spectrum._from_device_result(np.fft.rfftfreq(W, 1 / input.sampling_rate_hz), tf, coherence)
-    # small problems run in float64 end to end like the reference (backend.TF_PRECISION)
-    tf, coherence = backend.welch_transfer_function(
-        output.time_data, input.time_data, input.sampling_rate_hz, window_length_samples,
-        mode.name, precision=backend.TF_PRECISION, **par)
+        plan = output._welch_plan({**par, "window_length_samples": W})
+    if plan is None:
+        # small problems run in float64 end to end like the reference (backend.TF_PRECISION)
+        tf, coherence = backend.welch_transfer_function(
+            output.time_data, input.time_data, input.sampling_rate_hz, window_length_samples,
+            mode.name, precision=backend.TF_PRECISION, **par)
+    elif backend._welch_route(plan, "tf", (input.number_of_channels, output.number_of_channels), "resident",
+                              backend.TF_PRECISION) == backend.ROUTE_RESIDENT:
+        tf, coherence = backend._tf_resident(plan, output.device_samples, input.to_device().device_samples, mode.name,
+                                             narrow=True)
+        return Spectrum._from_device_result(np.fft.rfftfreq(W, 1 / input.sampling_rate_hz), tf, coherence)
+    else:
+        tf, coherence = backend._tf_host(plan, output.time_data, input.time_data, mode.name, backend.TF_PRECISION)
     spec = Spectrum(np.fft.rfftfreq(window_length_samples, 1 / input.sampling_rate_hz), tf)
     spec.set_coherence(coherence)
     return spec
