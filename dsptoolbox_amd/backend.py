@@ -10,11 +10,14 @@ names and argument meaning, executed by the HIP library through ctypes.
     rfft_spectrum <- scipy.fft.rfft call of classes/signal.py:899-911
     spectral_division <- transfer_functions/_transfer_functions.py:19-42
 
-Arrays cross the boundary as (samples, channels) float64 like in the
-reference; the shim transposes to planar fp32, the device computes in
-fp32/complex64 (finish() in fp64) and results are cast back to
-float64/complex128.  Anything the device path does not implement raises
-NotImplementedError -- nothing is silently computed on the CPU.
+Arrays cross the boundary as (samples, channels) float64 like in the reference; the shim transposes to planar fp32,
+the device computes in fp32/complex64 (finish() in fp64) and results are cast back to float64/complex128.  Anything
+the device path does not implement raises NotImplementedError -- nothing is silently computed on the CPU.
+
+A call builds ONE plan from its parameters and the shape of its samples (_WelchPlan by _welch_plan, _StftPlan by
+_stft_plan: checks, window, framing, and `tail()`, the one place an entry family's argument order is written), asks
+ONE route (_welch_route for a Welch estimate, _host_route for every other host function), casts by that route
+(_host_input) and makes one call; device buffers of a call live in a device_scope.
 """
 
 from __future__ import annotations
@@ -283,12 +286,27 @@ def _welch_route(plan: _WelchPlan, kind: str, channels, holds: str = "host", pre
     return ROUTE_RESIDENT if holds == "resident" else ROUTE_FUSED if holds == "fusable" else ROUTE_PLANAR
 
 
-def _host_input(a: np.ndarray, route: str) -> np.ndarray:
-    """An (N, C) array as the host entries of `route` read it: float64 for the float64 kernels, as it is for the fused
-    transport, planar float32 otherwise."""
+def _host_route(a, fuses: bool = True) -> str:
+    """Transport of a host function that is no Welch estimate (STFT, rFFT, deconvolution, FIR) -- THE place that chooses
+    between ROUTE_FUSED (the `*_f64` entry: float64 on both sides through the pinned chunk pipelines) and ROUTE_PLANAR (planar
+    float32 made here, the result widened here).  fuses: the function's own condition beside the array being _fusable."""
+    return ROUTE_FUSED if fuses and _fusable(a) else ROUTE_PLANAR
+
+
+def _host_input(a, route: str) -> np.ndarray:
+    """A flat or (N, C) array as the host entries of `route` read it: float64 for the float64 kernels, as it is for the
+    fused transport, planar (C, N) float32 otherwise."""
     if route == ROUTE_X64:
         return np.ascontiguousarray(a, dtype=np.float64)
     return a if route == ROUTE_FUSED else _planar_f32(a)
+
+
+def _samples_shape(x) -> tuple:
+    """(samples, channels) of a flat or (N, C) array or of a DevicePlanar."""
+    if isinstance(x, DevicePlanar):
+        return x.n_samples, x.n_ch
+    n, n_ch = x.shape if x.ndim != 1 else (x.shape[0], 1)
+    return n, n_ch
 
 
 class _DeviceScope:
@@ -519,29 +537,27 @@ def _stft_device(x_dev: DevicePlanar, fs_hz: int, window_length_samples: int, wi
                  fft_length_samples, detrend: bool, padding: bool, scaling: SpectrumScaling, keep_on_device: bool):
     """_stft of a device-resident signal -> (time_s, freqs_hz, stft): stft the (B', F, C) complex128 array, or a
     DeviceSTFT when keep_on_device."""
-    pl = _stft_plan(_ShapeOnly(x_dev.n_samples, x_dev.n_ch), fs_hz, window_length_samples, window_type, overlap_percent,
-                    fft_length_samples, padding, scaling, planar=False)
+    plan = _stft_plan(x_dev.n_samples, x_dev.n_ch, fs_hz, window_length_samples, window_type, overlap_percent,
+                      fft_length_samples, detrend, padding, scaling)
     ctx = x_dev.ctx
-    d_w = _window_dev(ctx, pl["w32"])
-    shape = (pl["B"], pl["n_frames"], pl["n_ch"])
+    d_w = _window_dev(ctx, plan.window32)
     with device_scope(ctx) as dev:
-        d_s = dev.alloc(int(np.prod(shape)) * 8, result=keep_on_device)
-        ctx.check(ctx.lib.ds_stft_r2c_dev(ctx.handle, C.c_void_p(x_dev.ptr), pl["n"], pl["n_ch"], x_dev.ld, pl["W"], pl["hop"],
-                                          pl["nfft"], pl["pad_front"], pl["n_frames"], C.c_void_p(d_w.ptr), int(bool(detrend)),
-                                          pl["scale"], pl["edge"], pl["power"], C.c_void_p(d_s.ptr)), "ds_stft_r2c_dev")
-        stft = DeviceSTFT(d_s, shape, pl["power"])
+        d_s = dev.alloc(int(np.prod(plan.shape)) * 8, result=keep_on_device)
+        ctx.check(ctx.lib.ds_stft_r2c_dev(ctx.handle, C.c_void_p(x_dev.ptr), *plan.tail(C.c_void_p(d_w.ptr), x_dev.ld),
+                                          C.c_void_p(d_s.ptr)), "ds_stft_r2c_dev")
+        stft = DeviceSTFT(d_s, plan.shape, plan.power)
         if keep_on_device:
             ctx.sync()
         else:
             stft = stft.to_host()
-    return pl["time_s"], pl["freqs_hz"], stft
+    return plan.time_s, plan.freqs_hz, stft
 
 
-class _ShapeOnly:
-    """(N, C) shape carrier for _stft_plan(planar=False) when the samples are on the device."""
-
-    def __init__(self, n: int, n_ch: int):
-        self.shape = (int(n), int(n_ch))
+def _bank_outputs(d_y: DeviceBuffer, n_ch: int, n: int, n_out: int, mode: int):
+    """The n_out outputs of a device filter bank, slices of its ONE band-major buffer: the list of them for a Parallel
+    bank, the single one otherwise."""
+    outs = [DevicePlanar(d_y, n_ch, n, n, 4 * i * n_ch * n) for i in range(n_out)]
+    return outs if mode == DS_FB_PARALLEL else outs[0]
 
 
 def fir_filter_bank_device(x_dev: DevicePlanar, taps_list, mode: int):
@@ -558,8 +574,7 @@ def fir_filter_bank_device(x_dev: DevicePlanar, taps_list, mode: int):
         ctx.check(ctx.lib.ds_fir_ola_dev(ctx.handle, C.c_void_p(x_dev.ptr), n_ch, x_dev.ld, n, C.c_void_p(d_t.ptr), k, t,
                                          int(mode), C.c_void_p(d_y.ptr), n), "ds_fir_ola_dev")
         ctx.sync()  # (the taps buffer is freed on the way out)
-    outs = [DevicePlanar(d_y, n_ch, n, n, 4 * i * n_ch * n) for i in range(n_out)]
-    return outs if mode == DS_FB_PARALLEL else outs[0]
+    return _bank_outputs(d_y, n_ch, n, n_out, mode)
 
 
 def _istft_device(stft: DeviceSTFT, nfft: int, W: int, step: int, window, scale: float, frame_offset: int,
@@ -611,14 +626,50 @@ def spectral_division_device(y_dev: DevicePlanar, x_dev: DevicePlanar, n_fft: in
     return DevicePlanar(d_o, n_cy, int(n_out))
 
 
-def _stft_plan(x, fs_hz: int, window_length_samples: int, window_type, overlap_percent: float,
-               fft_length_samples, padding: bool, scaling: SpectrumScaling, planar: bool = True):
-    """Argument checks and launch parameters of the STFT (shared by _stft and the fused
-    spectrogram consumers)."""
+class _StftPlan(NamedTuple):
+    """Everything an STFT derives from its parameters and the SHAPE of the samples, before it looks at the samples: built
+    once per call by _stft_plan, handed to the one call the function makes."""
+    n: int
+    n_ch: int
+    W: int
+    hop: int
+    nfft: int
+    B: int            # nfft // 2 + 1 bins
+    pad_front: int
+    n_frames: int
+    window: np.ndarray  # float64, read-only when it is one of _window_array's
+    detrend: int
+    scale: float
+    edge: float
+    power: int
+    time_s: np.ndarray
+    freqs_hz: np.ndarray
+
+    @property
+    def shape(self) -> tuple:
+        """Of the spectrogram: (bins, frames, channels)."""
+        return (self.B, self.n_frames, self.n_ch)
+
+    @property
+    def window32(self) -> np.ndarray:
+        """The window as the kernels read it (a fresh array: _window_dev keys it by content)."""
+        return self.window.astype(np.float32)
+
+    def tail(self, window_ptr, ld: int | None = None) -> tuple:
+        """The arguments of every ds_stft_r2c* entry between its input and its output: n, n_ch, [leading dimension of
+        resident samples], W, hop, nfft, pad_front, n_frames, window, detrend, scale, edge, power.  THE place where their
+        order is written."""
+        return ((self.n, self.n_ch) + (() if ld is None else (ld,)) + (self.W, self.hop, self.nfft, self.pad_front,
+                self.n_frames, window_ptr, self.detrend, self.scale, self.edge, self.power))
+
+
+def _stft_plan(n_samples: int, n_ch: int, fs_hz: int, window_length_samples: int, window_type, overlap_percent: float,
+               fft_length_samples, detrend: bool, padding: bool, scaling: SpectrumScaling) -> _StftPlan:
+    """Argument checks (the reference's assertions, in its order) and launch parameters of the STFT of n_samples x n_ch
+    samples, wherever they are."""
     assert window_length_samples in [2**k for k in range(4, 17)], (
         "Window length should be a power of 2 between [16, 65536] or [2**4, 2**16]")
-    assert overlap_percent >= 0 and overlap_percent < 100, \
-        "overlap_percent should be between 0 and 100"
+    assert overlap_percent >= 0 and overlap_percent < 100, "overlap_percent should be between 0 and 100"
     W = int(window_length_samples)
     nfft = W if fft_length_samples is None else int(fft_length_samples)
     # any positive length, as numpy's rfft(n=...) (_spectral_methods.py:268): frames are cropped to
@@ -629,14 +680,8 @@ def _stft_plan(x, fs_hz: int, window_length_samples: int, window_type, overlap_p
     overlap = int(overlap_percent / 100 * W + 0.5)  # rounding, _spectral_methods.py:247
     hop = W - overlap
     if not _cola_ok(window, overlap):
-        warn("Selected window type and overlap do not meet the constant "
-             "overlap and add constraint! Results might be distorted")
-    if planar:
-        xp = _planar_f32(x)
-        n_ch, n = xp.shape
-    else:  # the caller hands the (N, C) float64 array to a *_f64 entry point as it is
-        xp = None
-        n, n_ch = x.shape
+        warn("Selected window type and overlap do not meet the constant overlap and add constraint! Results might be distorted")
+    n, n_ch = int(n_samples), int(n_ch)
     pad_front = overlap if padding else 0
     n_padded = n + 2 * pad_front
     n_frames = int(np.ceil(n_padded / hop))
@@ -648,110 +693,88 @@ def _stft_plan(x, fs_hz: int, window_length_samples: int, window_type, overlap_p
         norm = scaling.fft_norm()
         scale = 1.0 if norm == "backward" else (1.0 / nfft if norm == "forward" else nfft**-0.5)
         edge, power = 1.0, 0
-    time_s = np.linspace(0, n_padded / fs_hz, n_frames)
-    freqs_hz = np.fft.rfftfreq(W, 1 / fs_hz)
-    return dict(xp=xp, n=n, n_ch=n_ch, W=W, hop=hop, nfft=nfft, pad_front=pad_front, n_frames=n_frames,
-                w32=window.astype(np.float32), scale=scale, edge=edge, power=power, B=nfft // 2 + 1,
-                time_s=time_s, freqs_hz=freqs_hz)
+    return _StftPlan(n, n_ch, W, hop, nfft, nfft // 2 + 1, pad_front, n_frames, window, int(bool(detrend)), scale, edge, power,
+                     np.linspace(0, n_padded / fs_hz, n_frames), np.fft.rfftfreq(W, 1 / fs_hz))
 
 
 def _stft(x, fs_hz: int, window_length_samples: int, window_type, overlap_percent: float,
           fft_length_samples, detrend: bool, padding: bool, scaling: SpectrumScaling):
     """-> (time_s (F,), freqs_hz (B,), stft (B', F, C))."""
     xa = np.asarray(x)
-    if _fusable(xa):
-        # float64 on both sides: threaded cast into pinned upload chunks, widened back from pinned
-        # download chunks (power scalings keep only the real part: numpy path below)
-        pl = _stft_plan(xa, fs_hz, window_length_samples, window_type, overlap_percent, fft_length_samples,
-                        padding, scaling, planar=False)
-        if not pl["power"]:
-            out = np.empty((pl["B"], pl["n_frames"], pl["n_ch"]), dtype=np.complex128)
-            ctx = get_context()
-            ctx.check(ctx.lib.ds_stft_r2c_f64(ctx.handle, _ptr(xa), pl["n"], pl["n_ch"], pl["W"], pl["hop"],
-                                              pl["nfft"], pl["pad_front"], pl["n_frames"], _ptr(pl["w32"]),
-                                              int(bool(detrend)), pl["scale"], pl["edge"], pl["power"],
-                                              _ptr(out)), "ds_stft_r2c_f64")
-            return pl["time_s"], pl["freqs_hz"], out
-    pl = _stft_plan(x, fs_hz, window_length_samples, window_type, overlap_percent, fft_length_samples,
-                    padding, scaling)
-    out = np.empty((pl["B"], pl["n_frames"], pl["n_ch"]), dtype=np.complex64)
+    plan = _stft_plan(*_samples_shape(xa), fs_hz, window_length_samples, window_type, overlap_percent, fft_length_samples,
+                      detrend, padding, scaling)
+    # the fused entry hands back complex128; a power scaling keeps only the real part, taken here from the complex64 array
+    route = _host_route(xa, fuses=not plan.power)
+    fused = route == ROUTE_FUSED
+    x_in, w32 = _host_input(xa, route), plan.window32
+    out = np.empty(plan.shape, dtype=np.complex128 if fused else np.complex64)
+    name = "ds_stft_r2c_f64" if fused else "ds_stft_r2c"
     ctx = get_context()
-    ctx.check(ctx.lib.ds_stft_r2c(ctx.handle, _ptr(pl["xp"]), pl["n"], pl["n_ch"], pl["W"], pl["hop"],
-                                  pl["nfft"], pl["pad_front"], pl["n_frames"], _ptr(pl["w32"]),
-                                  int(bool(detrend)), pl["scale"], pl["edge"], pl["power"], _ptr(out)),
-              "ds_stft_r2c")
-    stft = out.real.astype(np.float64) if pl["power"] else _widen(out)
-    return pl["time_s"], pl["freqs_hz"], stft
+    ctx.check(getattr(ctx.lib, name)(ctx.handle, _ptr(x_in), *plan.tail(_ptr(w32)), _ptr(out)), name)
+    if not fused:
+        out = out.real.astype(np.float64) if plan.power else _widen(out)
+    return plan.time_s, plan.freqs_hz, out
 
 
-def _spectrogram_band_power(x, fs_hz: int, window_length_samples: int, window_type, overlap_percent: float,
-                            fft_length_samples, detrend: bool, padding: bool, scaling: SpectrumScaling,
-                            band_filters, to_db: bool, dct_abs: bool):
+def _spectrogram_band_power(x, fs_hz: int, window_length_samples: int, window_type, overlap_percent: float, fft_length_samples,
+                            detrend: bool, padding: bool, scaling: SpectrumScaling, band_filters, to_db: bool, dct_abs: bool):
     """STFT -> sum_b filters[band, b] |stft[b]|^2 (-> dB -> |DCT-II| over bands), everything on the
     device: the spectrogram never travels to the host.  band_filters (bands, B').
     -> (time_s, freqs_hz, out (bands, F, C) float64)."""
     resident = isinstance(x, DevicePlanar)  # a device-resident signal: its samples are read in place
-    if resident:
-        pl = _stft_plan(_ShapeOnly(x.n_samples, x.n_ch), fs_hz, window_length_samples, window_type, overlap_percent,
-                        fft_length_samples, padding, scaling, planar=False)
-    else:
-        pl = _stft_plan(x, fs_hz, window_length_samples, window_type, overlap_percent, fft_length_samples,
-                        padding, scaling)
+    if not resident:
+        x = np.asarray(x)
+    plan = _stft_plan(*_samples_shape(x), fs_hz, window_length_samples, window_type, overlap_percent, fft_length_samples,
+                      detrend, padding, scaling)
     filt = np.ascontiguousarray(band_filters, dtype=np.float32)
-    assert filt.ndim == 2 and filt.shape[1] == pl["B"], (
-        f"Shape of the mel filter matrix {filt.shape} does not match the STFT "
-        f"{(pl['B'], pl['n_frames'], pl['n_ch'])}")
+    assert filt.ndim == 2 and filt.shape[1] == plan.B, (
+        f"Shape of the mel filter matrix {filt.shape} does not match the STFT {plan.shape}")
     n_bands = filt.shape[0]
     nz = filt != 0
     b0 = np.where(nz.any(axis=1), nz.argmax(axis=1), 0).astype(np.int32)
     b1 = np.where(nz.any(axis=1), filt.shape[1] - nz[:, ::-1].argmax(axis=1), 0).astype(np.int32)
     ctx = x.ctx if resident else get_context()
-    n_fc = pl["n_frames"] * pl["n_ch"]
+    n_fc = plan.n_frames * plan.n_ch
     with device_scope(ctx) as dev:
-        d_x = x if resident else dev.upload(pl["xp"])
-        x_ld = x.ld if resident else pl["n"]
-        d_w = dev.upload(pl["w32"])
-        d_s = dev.alloc(pl["B"] * n_fc * 8)
+        d_x = x if resident else dev.upload(_planar_f32(x))
+        d_w = dev.upload(plan.window32)
+        d_s = dev.alloc(plan.B * n_fc * 8)
         d_f = dev.upload(filt)
         d_b0, d_b1 = dev.upload(b0), dev.upload(b1)
         d_o = dev.alloc(n_bands * n_fc * 4)
-        ctx.check(ctx.lib.ds_stft_r2c_dev(ctx.handle, C.c_void_p(d_x.ptr), pl["n"], pl["n_ch"], x_ld, pl["W"],
-                                          pl["hop"], pl["nfft"], pl["pad_front"], pl["n_frames"],
-                                          C.c_void_p(d_w.ptr), int(bool(detrend)), pl["scale"], pl["edge"],
-                                          pl["power"], C.c_void_p(d_s.ptr)), "ds_stft_r2c_dev")
-        ctx.check(ctx.lib.ds_band_power_dev(ctx.handle, C.c_void_p(d_s.ptr), pl["B"], n_fc, C.c_void_p(d_f.ptr),
-                                            C.c_void_p(d_b0.ptr), C.c_void_p(d_b1.ptr), n_bands,
-                                            int(bool(to_db)), int(bool(dct_abs)), C.c_void_p(d_o.ptr)),
-                  "ds_band_power_dev")
-        out = d_o.to_array((n_bands, pl["n_frames"], pl["n_ch"]), np.float32)
-    return pl["time_s"], pl["freqs_hz"], out.astype(np.float64)
-
-
-def _das_map(csm, h):
-    """Re(h^H csm h) per grid point and bin: csm (F, C, C), h (F, C, G) -> (G, F) float64."""
-    cs = np.ascontiguousarray(csm, dtype=np.complex64)
-    hs = np.ascontiguousarray(h, dtype=np.complex64)
-    assert cs.ndim == 3 and hs.ndim == 3 and cs.shape[1] == cs.shape[2], "csm must be (bins, C, C)"
-    assert hs.shape[0] == cs.shape[0] and hs.shape[1] == cs.shape[1], \
-        "steering vector must be (bins, C, grid points)"
-    n_bins, n_ch, n_grid = hs.shape
-    out = np.empty((n_grid, n_bins), dtype=np.float32)
-    ctx = get_context()
-    ctx.check(ctx.lib.ds_das_map(ctx.handle, _ptr(cs), _ptr(hs), n_bins, n_ch, n_grid, _ptr(out)),
-              "ds_das_map")
-    return out.astype(np.float64)
+        ctx.check(ctx.lib.ds_stft_r2c_dev(ctx.handle, C.c_void_p(d_x.ptr),
+                                          *plan.tail(C.c_void_p(d_w.ptr), x.ld if resident else plan.n), C.c_void_p(d_s.ptr)),
+                  "ds_stft_r2c_dev")
+        ctx.check(ctx.lib.ds_band_power_dev(ctx.handle, C.c_void_p(d_s.ptr), plan.B, n_fc, C.c_void_p(d_f.ptr),
+                                            C.c_void_p(d_b0.ptr), C.c_void_p(d_b1.ptr), n_bands, int(bool(to_db)),
+                                            int(bool(dct_abs)), C.c_void_p(d_o.ptr)), "ds_band_power_dev")
+        out = d_o.to_array((n_bands, plan.n_frames, plan.n_ch), np.float32)
+    return plan.time_s, plan.freqs_hz, out.astype(np.float64)
 
 
 BF_METHODS = {"mvdr": 0, "functional": 1, "orthogonal": 2}  # ds_bf_eig_map's method codes
 
 
-def _bf_inputs(csm, h):
-    cs = np.ascontiguousarray(csm, dtype=np.complex128)
-    hs = np.ascontiguousarray(h, dtype=np.complex128)
+def _bf_inputs(csm, h, dtype=np.complex128):
+    cs = np.ascontiguousarray(csm, dtype=dtype)
+    hs = np.ascontiguousarray(h, dtype=dtype)
     assert cs.ndim == 3 and hs.ndim == 3 and cs.shape[1] == cs.shape[2], "csm must be (bins, C, C)"
-    assert hs.shape[0] == cs.shape[0] and hs.shape[1] == cs.shape[1], \
-        "steering vector must be (bins, C, grid points)"
+    assert hs.shape[0] == cs.shape[0] and hs.shape[1] == cs.shape[1], "steering vector must be (bins, C, grid points)"
     return cs, hs
+
+
+def _bf_map(entry: str, cs: np.ndarray, hs: np.ndarray, *params) -> np.ndarray:
+    """One beamformer map entry (csm, h, bins, C, grid points, *params, out) over _bf_inputs' arrays -> (G, F), real."""
+    n_bins, n_ch, n_grid = hs.shape
+    out = np.empty((n_grid, n_bins), dtype=hs.real.dtype)
+    ctx = get_context()
+    ctx.check(getattr(ctx.lib, entry)(ctx.handle, _ptr(cs), _ptr(hs), n_bins, n_ch, n_grid, *params, _ptr(out)), entry)
+    return out
+
+
+def _das_map(csm, h):
+    """Re(h^H csm h) per grid point and bin: csm (F, C, C), h (F, C, G) -> (G, F) float64."""
+    return _bf_map("ds_das_map", *_bf_inputs(csm, h, np.complex64)).astype(np.float64)
 
 
 def hermitian_eigh(a):
@@ -771,29 +794,17 @@ def beamformer_eig_map(csm, h, method: str, gamma: float = 10.0, n_eig: int = 0)
     """MVDR, Functional or Orthogonal map per grid point and bin from one eigendecomposition of every bin's CSM
     (ds_bf_eig_map, float64): csm (F, C, C) the selected bins, h (F, C, G) -> (G, F) float64."""
     cs, hs = _bf_inputs(csm, h)
-    n_bins, n_ch, n_grid = hs.shape
-    out = np.empty((n_grid, n_bins), dtype=np.float64)
-    ctx = get_context()
-    ctx.check(ctx.lib.ds_bf_eig_map(ctx.handle, _ptr(cs), _ptr(hs), n_bins, n_ch, n_grid, BF_METHODS[method],
-                                    float(gamma), int(n_eig), _ptr(out)), "ds_bf_eig_map")
-    return out
+    return _bf_map("ds_bf_eig_map", cs, hs, BF_METHODS[method], float(gamma), int(n_eig))
 
 
-def beamformer_cleansc_map(csm, h, maximum_iterations: int, safety_factor: float,
-                           remove_csm_diagonal: bool) -> np.ndarray:
+def beamformer_cleansc_map(csm, h, maximum_iterations: int, safety_factor: float, remove_csm_diagonal: bool) -> np.ndarray:
     """CLEAN-SC clean map per grid point and bin (ds_bf_cleansc, float64): csm (F, C, C) the selected bins,
     h (F, C, G) -> (G, F) float64."""
     cs, hs = _bf_inputs(csm, h)
-    n_bins, n_ch, n_grid = hs.shape
-    out = np.empty((n_grid, n_bins), dtype=np.float64)
-    ctx = get_context()
-    ctx.check(ctx.lib.ds_bf_cleansc(ctx.handle, _ptr(cs), _ptr(hs), n_bins, n_ch, n_grid, int(maximum_iterations),
-                                    float(safety_factor), int(bool(remove_csm_diagonal)), _ptr(out)), "ds_bf_cleansc")
-    return out
+    return _bf_map("ds_bf_cleansc", cs, hs, int(maximum_iterations), float(safety_factor), int(bool(remove_csm_diagonal)))
 
 
-def _istft(stft, nfft: int, W: int, step: int, window, scale: float, frame_offset: int,
-           n_frames_total: int):
+def _istft(stft, nfft: int, W: int, step: int, window, scale: float, frame_offset: int, n_frames_total: int):
     """Frame-wise irfft (length nfft, cropped to W) * scale * window, overlap-added at
     (frame + frame_offset) * step and divided by the squared-window envelope clipped at 1e-4
     (standard/_framed_signal_representation.py:70-137).  stft (B, F, C) -> (total_length, C)."""
@@ -806,21 +817,17 @@ def _istft(stft, nfft: int, W: int, step: int, window, scale: float, frame_offse
         raise ValueError(f"operands could not be broadcast together with shapes ({nfft},{n_frames},{n_ch}) ({W},1,1)")
     # length of the reference's reconstruction buffer (same float expression, :112-115)
     total_length = int(step * n_frames_total + W * (1 - step / W))
-    if stft.dtype == np.complex128 and stft.flags.c_contiguous and stft.size >= (1 << 19):
-        # a large complex128 spectrogram: narrowed in host threads into pinned upload chunks, float64 (N, C) back
-        res = np.empty((total_length, n_ch), dtype=np.float64)
-        w32 = np.ascontiguousarray(window, dtype=np.float32)
-        ctx = get_context()
-        ctx.check(ctx.lib.ds_istft_f64(ctx.handle, _ptr(stft), n_bins, n_frames, n_ch, nfft, W, step, frame_offset,
-                                       n_frames_total, _ptr(w32), float(scale), total_length, _ptr(res)), "ds_istft_f64")
-        return res
-    sp = np.ascontiguousarray(stft, dtype=np.complex64)
-    out = np.empty((n_ch, total_length), dtype=np.float32)
+    # a large complex128 spectrogram is narrowed in host threads into pinned upload chunks, float64 (N, C) comes back
+    # (its own condition: _host_route speaks of (N, C) float64 samples); anything else goes up as complex64, planar comes back
+    fused = stft.dtype == np.complex128 and stft.flags.c_contiguous and stft.size >= (1 << 19)
+    sp = stft if fused else np.ascontiguousarray(stft, dtype=np.complex64)
+    out = np.empty((total_length, n_ch), dtype=np.float64) if fused else np.empty((n_ch, total_length), dtype=np.float32)
     w32 = np.ascontiguousarray(window, dtype=np.float32)
+    name = "ds_istft_f64" if fused else "ds_istft"
     ctx = get_context()
-    ctx.check(ctx.lib.ds_istft(ctx.handle, _ptr(sp), n_bins, n_frames, n_ch, nfft, W, step, frame_offset,
-                               n_frames_total, _ptr(w32), float(scale), total_length, _ptr(out)), "ds_istft")
-    return _interleaved_f64(out)
+    ctx.check(getattr(ctx.lib, name)(ctx.handle, _ptr(sp), n_bins, n_frames, n_ch, nfft, W, step, frame_offset, n_frames_total,
+                                     _ptr(w32), float(scale), total_length, _ptr(out)), name)
+    return out if fused else _interleaved_f64(out)
 
 
 _STAGED_RESULT_BYTES = 512 << 20  # largest result that goes through the context's page-locked staging buffer (which stays allocated)
@@ -963,19 +970,15 @@ def _csm_fft(spectrum, scaling: SpectrumScaling, window, sampling_rate_hz: int):
 
 def rfft_spectrum(time_data, n_fft: int, scale: float = 1.0):
     """rfft(time_data, n=n_fft, axis=0) * scale -> (n_fft/2+1, C) complex128."""
-    if _fusable(time_data):  # float64 in, complex128 out through the pinned chunk pipelines
-        n, n_ch = time_data.shape
-        out = np.empty((n_fft // 2 + 1, n_ch), dtype=np.complex128)
-        ctx = get_context()
-        ctx.check(ctx.lib.ds_rfft_f64(ctx.handle, _ptr(time_data), n_ch, n, int(n_fft), float(scale), _ptr(out)), "ds_rfft_f64")
-        return out
-    xp = _planar_f32(time_data)
-    n_ch, n = xp.shape
-    out = np.empty((n_fft // 2 + 1, n_ch), dtype=np.complex64)
+    route = _host_route(time_data)
+    fused = route == ROUTE_FUSED
+    x_in = _host_input(time_data, route)
+    n, n_ch = x_in.shape if fused else x_in.shape[::-1]
+    out = np.empty((n_fft // 2 + 1, n_ch), dtype=np.complex128 if fused else np.complex64)
+    name = "ds_rfft_f64" if fused else "ds_rfft"
     ctx = get_context()
-    ctx.check(ctx.lib.ds_rfft(ctx.handle, _ptr(xp), n_ch, n, int(n_fft), float(scale), _ptr(out)),
-              "ds_rfft")
-    return out.astype(np.complex128)
+    ctx.check(getattr(ctx.lib, name)(ctx.handle, _ptr(x_in), n_ch, n, int(n_fft), float(scale), _ptr(out)), name)
+    return out if fused else out.astype(np.complex128)
 
 
 def spectral_division(num_td, n_fft: int, inverse_spectrum, n_out: int):
@@ -984,33 +987,29 @@ def spectral_division(num_td, n_fft: int, inverse_spectrum, n_out: int):
     shared or (B, C) per channel.  -> same leading shape, float64."""
     num_td = np.asarray(num_td)
     batched = num_td.ndim == 3
-    if not batched and _fusable(num_td):  # one large item: float64 on both sides through the pinned chunk pipelines
-        n, n_ch = num_td.shape
-        r = np.asarray(inverse_spectrum)
-        per_channel = r.ndim == 2
-        rp = np.ascontiguousarray(r.T if per_channel else r, dtype=np.complex64)
-        assert rp.shape[-1] == n_fft // 2 + 1, "Frequency vector does not match"
-        res = np.empty((int(n_out), n_ch), dtype=np.float64)
-        ctx = get_context()
-        ctx.check(ctx.lib.ds_deconv_f64(ctx.handle, _ptr(num_td), n_ch, n, int(n_fft), _ptr(rp), int(per_channel), int(n_out),
-                                        _ptr(res)), "ds_deconv_f64")
-        return res
+    fused = _host_route(num_td) == ROUTE_FUSED  # one large item only: a batch is 3-D, which _fusable is not
     items = num_td if batched else num_td[None]
     m, n, n_ch = items.shape
-    yp = np.empty((m, n_ch, n), dtype=np.float32)  # (M, C, N)
-    if n * n_ch >= (1 << 20):
-        for i in range(m):
-            yp[i] = _planar_f32(items[i])
-    else:
-        yp[...] = np.transpose(items, (0, 2, 1))
     r = np.asarray(inverse_spectrum)
     per_channel = r.ndim == 2
     rp = np.ascontiguousarray(r.T if per_channel else r, dtype=np.complex64)  # (C, B) or (B,)
     assert rp.shape[-1] == n_fft // 2 + 1, "Frequency vector does not match"
-    out = np.empty((m, n_ch, n_out), dtype=np.float32)
+    if fused:
+        y_in, out = num_td, np.empty((int(n_out), n_ch), dtype=np.float64)
+    else:
+        y_in = np.empty((m, n_ch, n), dtype=np.float32)  # (M, C, N)
+        if n * n_ch >= (1 << 20):
+            for i in range(m):
+                y_in[i] = _planar_f32(items[i])
+        else:
+            y_in[...] = np.transpose(items, (0, 2, 1))
+        out = np.empty((m, n_ch, n_out), dtype=np.float32)
+    name = "ds_deconv_f64" if fused else "ds_deconv"
     ctx = get_context()
-    ctx.check(ctx.lib.ds_deconv(ctx.handle, _ptr(yp), m, n_ch, n, int(n_fft), _ptr(rp),
-                                int(per_channel), int(n_out), _ptr(out)), "ds_deconv")
+    ctx.check(getattr(ctx.lib, name)(ctx.handle, _ptr(y_in), *(() if fused else (m,)), n_ch, n, int(n_fft), _ptr(rp),
+                                     int(per_channel), int(n_out), _ptr(out)), name)
+    if fused:
+        return out
     res = np.empty((m, n_out, n_ch), dtype=np.float64)
     if n_out * n_ch >= (1 << 20):
         for i in range(m):
@@ -1040,27 +1039,23 @@ def regularized_inverse(denum_spectrum, eps=None):
 def fir_filter_bank(x, taps_list, mode: int):
     """x (N, C); taps_list K arrays of equal length T.  Parallel -> (K, N, C);
     Sequential / Summed -> (N, C).  float64."""
-    taps = np.ascontiguousarray(np.stack([np.asarray(t, dtype=np.float64) for t in taps_list]),
-                                dtype=np.float32)
+    taps = np.ascontiguousarray(np.stack([np.asarray(t, dtype=np.float64) for t in taps_list]), dtype=np.float32)
     k, t = taps.shape
     xa = np.asarray(x)
-    if _fusable(xa):  # float64 on both sides through the pinned chunk pipelines
-        n, n_ch = xa.shape
-        res = np.empty(((k if mode == DS_FB_PARALLEL else 1), n, n_ch), dtype=np.float64)
-        ctx = get_context()
-        ctx.check(ctx.lib.ds_fir_ola_f64(ctx.handle, _ptr(xa), n_ch, n, _ptr(taps), k, t, int(mode), _ptr(res)),
-                  "ds_fir_ola_f64")
-        return res if mode == DS_FB_PARALLEL else res[0]
-    xp = _planar_f32(x)
-    n_ch, n = xp.shape
-    out = np.empty(((k if mode == DS_FB_PARALLEL else 1), n_ch, n), dtype=np.float32)
+    route = _host_route(xa)
+    fused = route == ROUTE_FUSED
+    x_in = _host_input(xa, route)
+    n, n_ch = x_in.shape if fused else x_in.shape[::-1]
+    n_out = k if mode == DS_FB_PARALLEL else 1
+    out = np.empty((n_out, n, n_ch), dtype=np.float64) if fused else np.empty((n_out, n_ch, n), dtype=np.float32)
+    name = "ds_fir_ola_f64" if fused else "ds_fir_ola"
     ctx = get_context()
-    ctx.check(ctx.lib.ds_fir_ola(ctx.handle, _ptr(xp), n_ch, n, _ptr(taps), k, t, int(mode),
-                                 _ptr(out)), "ds_fir_ola")
-    res = np.empty((out.shape[0], n, n_ch), dtype=np.float64)
-    for i in range(out.shape[0]):
-        _interleaved_f64(out[i], res[i])
-    return res if mode == DS_FB_PARALLEL else res[0]
+    ctx.check(getattr(ctx.lib, name)(ctx.handle, _ptr(x_in), n_ch, n, _ptr(taps), k, t, int(mode), _ptr(out)), name)
+    if not fused:
+        planar, out = out, np.empty((n_out, n, n_ch), dtype=np.float64)
+        for i in range(n_out):
+            _interleaved_f64(planar[i], out[i])
+    return out if mode == DS_FB_PARALLEL else out[0]
 
 
 def _lfilter_fir(b, a, x, zi=None, axis: int = 0):
@@ -1194,6 +1189,13 @@ def _sos_stack(sos_list) -> np.ndarray:
     return out
 
 
+def _sequential_cascades(sos_list) -> list:
+    """The sections of a Sequential bank, in order, as consecutive cascades of at most IIR_MAX_SECTIONS (one device call
+    each): a list of one for a bank that fits."""
+    sections = np.concatenate([np.atleast_2d(np.asarray(s, dtype=np.float64)) for s in sos_list])
+    return [sections[i0:i0 + IIR_MAX_SECTIONS] for i0 in range(0, len(sections), IIR_MAX_SECTIONS)]
+
+
 def iir_sos_filter(x, sos_list, mode: int, zi=None):
     """sosfilt of x (N, C) float64 through K cascades of second-order sections (the recursion in float64 on the
     device).  Parallel -> (K, N, C); Sequential / Summed -> (N, C).  zi (K, n_max, 2, C) (sosfilt's per-filter
@@ -1203,13 +1205,13 @@ def iir_sos_filter(x, sos_list, mode: int, zi=None):
     if xa.ndim == 1:
         xa = xa[:, None]
     if mode == DS_FB_SEQUENTIAL:
-        sections = np.concatenate([np.atleast_2d(np.asarray(s, dtype=np.float64)) for s in sos_list])
-        if zi is None and len(sections) > IIR_MAX_SECTIONS:
+        cascades = _sequential_cascades(sos_list)
+        if zi is None and len(cascades) > 1:
             y = xa
-            for i0 in range(0, len(sections), IIR_MAX_SECTIONS):
-                y = iir_sos_filter(y, [sections[i0:i0 + IIR_MAX_SECTIONS]], DS_FB_PARALLEL)[0]
+            for sections in cascades:
+                y = iir_sos_filter(y, [sections], DS_FB_PARALLEL)[0]
             return y
-        sos_list = [sections] if zi is None else sos_list
+        sos_list = cascades if zi is None else sos_list
     sos = _sos_stack(sos_list)
     k, n_sec = sos.shape[0], sos.shape[1]
     n, n_ch = xa.shape
@@ -1231,13 +1233,12 @@ def iir_sos_filter_device(x_dev: DevicePlanar, sos_list, mode: int):
     """iir_sos_filter over device-resident samples (ds_iir_sos_dev, no state): Parallel -> a list of K DevicePlanar
     (slices of ONE output buffer), Sequential / Summed -> one DevicePlanar.  Nothing comes down."""
     if mode == DS_FB_SEQUENTIAL:
-        sections = np.concatenate([np.atleast_2d(np.asarray(s, dtype=np.float64)) for s in sos_list])
-        if len(sections) > IIR_MAX_SECTIONS:
+        sos_list = _sequential_cascades(sos_list)
+        if len(sos_list) > 1:
             y = x_dev
-            for i0 in range(0, len(sections), IIR_MAX_SECTIONS):
-                y = iir_sos_filter_device(y, [sections[i0:i0 + IIR_MAX_SECTIONS]], DS_FB_PARALLEL)[0]
+            for sections in sos_list:
+                y = iir_sos_filter_device(y, [sections], DS_FB_PARALLEL)[0]
             return y
-        sos_list = [sections]
     sos = _sos_stack(sos_list)
     k, n_sec = sos.shape[0], sos.shape[1]
     ctx = x_dev.ctx
@@ -1247,8 +1248,7 @@ def iir_sos_filter_device(x_dev: DevicePlanar, sos_list, mode: int):
         d_y = dev.alloc(n_out * n_ch * n * 4, result=True)
         ctx.check(ctx.lib.ds_iir_sos_dev(ctx.handle, C.c_void_p(x_dev.ptr), n_ch, x_dev.ld, n, _ptr(sos), k, n_sec, None,
                                          int(mode), C.c_void_p(d_y.ptr), n, None), "ds_iir_sos_dev")
-    outs = [DevicePlanar(d_y, n_ch, n, n, 4 * i * n_ch * n) for i in range(n_out)]
-    return outs if mode == DS_FB_PARALLEL else outs[0]
+    return _bank_outputs(d_y, n_ch, n, n_out, mode)
 
 
 def _ba_section(b, a) -> np.ndarray:

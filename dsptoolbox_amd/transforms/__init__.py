@@ -150,11 +150,10 @@ def _band_power(signal: Signal, filters, f_hz_check, to_db: bool, dct_abs: bool)
 
 def _spectrogram_axes(signal: Signal):
     par = signal._spectrogram_parameters
-    pl = backend._stft_plan(backend._ShapeOnly(len(signal), signal.number_of_channels), signal.sampling_rate_hz,
-                            par["window_length_samples"],
-                            par["window_type"], par["overlap_percent"], par["fft_length_samples"],
-                            par["padding"], par["scaling"], planar=False)  # axes only: no cast of the data
-    return pl["time_s"], pl["freqs_hz"], pl["B"]
+    plan = backend._stft_plan(len(signal), signal.number_of_channels, signal.sampling_rate_hz, par["window_length_samples"],
+                              par["window_type"], par["overlap_percent"], par["fft_length_samples"], par["detrend"],
+                              par["padding"], par["scaling"])  # from the shape alone: the samples stay where they are
+    return plan.time_s, plan.freqs_hz, plan.B
 
 
 def log_mel_spectrogram(s: Signal, channel: int = 0, range_hz=None, n_bands: int = 40,

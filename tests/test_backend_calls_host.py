@@ -1,7 +1,9 @@
 """The host shim (dsptoolbox_amd/backend.py) against a recording stand-in for Context, no GPU: which C entry every public
 function calls, with which scalar arguments, pointer kinds, allocation sizes, transfers and frees, what it returns (type,
 dtype, shape) and what it raises.  tests/golden/backend_calls.json was recorded by tools/record_backend_calls.py before the
-shim was rebuilt on one Welch plan, one route function and one device-buffer scope; the shim must keep reproducing it."""
+shim was rebuilt on one Welch plan, one route function and one device-buffer scope; tests/golden/backend_calls_xform.json
+(STFT, iSTFT, rFFT, deconvolution, FIR, beamformer maps, IIR) before that half got one STFT plan and one transport choice
+per host function.  The shim must keep reproducing both.  Cases with arrays of 2^20 elements need the built library."""
 import importlib.util
 import json
 import os
@@ -55,6 +57,40 @@ def test_call_transcript(name, recorded, transcript):
         # the one difference allowed: compute_transfer_function used to compute the framing twice, and so to warn twice
         # about a non-COLA window; one plan warns once
         assert len(want["warnings"]) == 2 and got["warnings"] == sorted(set(want["warnings"]))
+        want["warnings"] = got["warnings"]
+    assert got == want
+
+
+# ---- the other half of the shim: STFT, iSTFT, rFFT, deconvolution, FIR, beamformer maps, IIR --------------------------
+@pytest.fixture(scope="module")
+def recorded_xform():
+    with open(rec.FIXTURE_XFORM) as f:
+        return json.load(f)
+
+
+@pytest.fixture(scope="module")
+def transcript_xform():
+    return rec.record(rec.xform_cases)
+
+
+def test_every_xform_entry_is_reached(recorded_xform, transcript_xform):
+    for t in (recorded_xform, transcript_xform):
+        missing = sorted(set(rec.XFORM_ENTRIES) - rec.entries_reached(t))
+        assert not missing, f"no case reaches {missing}"
+
+
+def test_xform_case_list_matches_the_fixture(recorded_xform, transcript_xform):
+    assert sorted(transcript_xform) == sorted(recorded_xform)
+
+
+@pytest.mark.parametrize("name", sorted(rec.xform_cases()))
+def test_xform_call_transcript(name, recorded_xform, transcript_xform):
+    want, got = dict(recorded_xform[name]), transcript_xform[name]
+    if name == "stft/fusable_power_non_cola":
+        # the one difference allowed: _stft used to build its plan twice for a large float64 array with a power scaling
+        # (once for the fused transport, which such a scaling does not take), and so to warn twice about a non-COLA
+        # window; one plan warns once
+        assert len(want["warnings"]) == 2 and got["warnings"] == sorted(set(want["warnings"])) and len(got["warnings"]) == 1
         want["warnings"] = got["warnings"]
     assert got == want
 

@@ -147,10 +147,10 @@ def test_transfer_function_restatement_reproduces_the_golden_estimates():
 def test_stft_restatement_reproduces_the_golden_spectrograms():
     meta, z = load_golden("stft")
     for i, c in enumerate(meta["cases"]):
-        pl = backend._stft_plan(z["x"], meta["fs"], c["W"], "hann", c["overlap"], c["fft_length"], c["padding"],
-                                SpectrumScaling[c["scaling"]], planar=False)
-        out = ros.stft(z["x"], backend._window_array("hann", c["W"]), pl["W"], pl["hop"], pl["nfft"], pl["pad_front"],
-                       pl["n_frames"], int(c["detrend"]), pl["scale"], pl["edge"], pl["power"])
+        pl = backend._stft_plan(*z["x"].shape, meta["fs"], c["W"], "hann", c["overlap"], c["fft_length"], c["detrend"],
+                                c["padding"], SpectrumScaling[c["scaling"]])
+        out = ros.stft(z["x"], backend._window_array("hann", c["W"]), pl.W, pl.hop, pl.nfft, pl.pad_front,
+                       pl.n_frames, int(c["detrend"]), pl.scale, pl.edge, pl.power)
         _gold(f"stft_{i}", out, z[f"stft_{i}"])
 
 

@@ -3,9 +3,14 @@ ds_init.  Every `ctx.lib.ds_*` call returns 0 and is logged as (entry, scalar ar
 "null" / "host" / "dev<allocation>+<offset>"); malloc, upload, free, download*, staging and sync are logged with their
 sizes and are otherwise inert.  Numeric results are uninitialised and are described by type, dtype and shape only.
 
-    python tools/record_backend_calls.py            # rewrites tests/golden/backend_calls.json
-tests/test_backend_calls_host.py compares `record()` with that file: a refactor of the shim must leave it unchanged.
-Only names that the shim has had since the Welch routes were settled are touched."""
+    python tools/record_backend_calls.py welch      # rewrites tests/golden/backend_calls.json        (cases)
+    python tools/record_backend_calls.py xform      # rewrites tests/golden/backend_calls_xform.json  (xform_cases)
+tests/test_backend_calls_host.py compares `record()` with those files: a refactor of the shim must leave them unchanged,
+so a fixture is rewritten only BEFORE the refactor it is to judge.  `cases` (the Welch functions and everything that
+holds device buffers) was recorded before the Welch half of the shim was rebuilt; `xform_cases` (STFT, iSTFT, rFFT,
+deconvolution, FIR, beamformer maps, IIR: their host-pointer paths above all) before the other half was.
+Only names that the shim has had since the Welch routes were settled are touched.  Arrays of 2^20 elements and more
+go through the library's threaded host casts: those cases need the built library (no GPU)."""
 import bisect
 import contextlib
 import ctypes as C
@@ -28,6 +33,11 @@ FIXTURE = os.path.join(ROOT, "tests", "golden", "backend_calls.json")
 WELCH_ENTRIES = ("ds_welch_psd", "ds_welch_psd_f64", "ds_welch_psd_dev", "ds_welch_csd", "ds_welch_csd_f64",
                  "ds_welch_spec_x64", "ds_welch_tf", "ds_welch_tf_f64", "ds_welch_tf_dev", "ds_welch_tf_x64", "ds_csm",
                  "ds_csm_f64", "ds_csm_x64", "ds_csm_dev", "ds_csm_bins_dev")
+FIXTURE_XFORM = os.path.join(ROOT, "tests", "golden", "backend_calls_xform.json")
+XFORM_ENTRIES = ("ds_stft_r2c", "ds_stft_r2c_f64", "ds_stft_r2c_dev", "ds_istft", "ds_istft_f64", "ds_istft_dev",
+                 "ds_band_power_dev", "ds_rfft", "ds_rfft_f64", "ds_rfft_dev", "ds_deconv", "ds_deconv_f64", "ds_deconv_dev",
+                 "ds_deconv_inverse_dev", "ds_fir_ola", "ds_fir_ola_f64", "ds_fir_ola_dev", "ds_fir_freqz", "ds_das_map",
+                 "ds_csm_spec", "ds_bf_eigh", "ds_bf_eig_map", "ds_bf_cleansc", "ds_iir_sos", "ds_iir_sos_dev")
 _DEV_BASE = 0x500000000000
 
 
@@ -507,9 +517,272 @@ def cases():
     return c
 
 
-def record():
-    """name -> transcript of every case."""
-    return {name: run_case(fn, **patch) for name, (fn, patch) in cases().items()}
+def xform_cases():
+    """The same for the functions that are no Welch estimate: name -> (function of the stand-in context, patches)."""
+    fs, hann, bw = 48000, Window.Hann, SpectrumScaling.FFTBackward
+    z = np.zeros
+    big = z((1 << 19, 2))  # _fusable: float64, C order, 2^20 values (never written: shared by the cases)
+    c = {}
+
+    def add(name, fn, **patch):
+        assert name not in c, name
+        c[name] = (fn, patch)
+
+    # ---- _stft: 100 samples x 2 channels, W = 16, 50 % overlap
+    def stft(x, W=16, ov=50.0, nfft=None, det=True, pad=True, sc=bw, win=hann):
+        return lambda ctx: backend._stft(x, fs, W, win, ov, nfft, det, pad, sc)
+    add("stft/planar", stft(z((100, 2))))
+    add("stft/flat", stft(z(100)))
+    add("stft/list", stft([[0.0, 0.0]] * 100))
+    add("stft/fusable", stft(big))
+    add("stft/fusable_under", stft(z(((1 << 19) - 1, 2))))
+    add("stft/large_float32", stft(z((1 << 19, 2), dtype=np.float32)))
+    add("stft/fusable_power", stft(big, sc=SpectrumScaling.PowerSpectrum))  # (the plan used to be built twice)
+    add("stft/fusable_power_non_cola", stft(big, sc=SpectrumScaling.PowerSpectrum, ov=33.0))
+    add("stft/fusable_non_cola", stft(big, ov=33.0))
+    add("stft/fusable_nfft_24_no_padding", stft(big, nfft=24, pad=False, det=False))
+    for s in SpectrumScaling:
+        add(f"stft/scaling_{s.name}", stft(z((100, 2)), sc=s))
+    add("stft/nfft_12", stft(z((100, 2)), nfft=12))
+    add("stft/nfft_32", stft(z((100, 2)), nfft=32))
+    add("stft/nfft_24", stft(z((100, 2)), nfft=24))
+    add("stft/nfft_32_power_density", stft(z((100, 2)), nfft=32, sc=SpectrumScaling.PowerSpectralDensity))
+    add("stft/no_padding", stft(z((100, 2)), pad=False))
+    add("stft/no_detrend", stft(z((100, 2)), det=False))
+    add("stft/non_cola", stft(z((100, 2)), ov=33.0))
+    add("stft/overlap_0", stft(z((100, 2)), ov=0.0))
+    add("stft/window_tuple", stft(z((100, 2)), win=("kaiser", 5.0)))
+    add("stft/reject_window_8", stft(z((100, 2)), W=8))
+    add("stft/reject_window_2_17", stft(z((100, 2)), W=1 << 17))
+    add("stft/reject_overlap_100", stft(z((100, 2)), ov=100.0))
+    add("stft/reject_overlap_negative", stft(z((100, 2)), ov=-1.0))
+    add("stft/reject_nfft_1", stft(z((100, 2)), nfft=1))
+    add("stft/reject_window_before_overlap", stft(z((100, 2)), W=8, ov=100.0, nfft=1))
+    add("stft/reject_overlap_before_nfft", stft(z((100, 2)), ov=100.0, nfft=1))
+    add("stft/reject_ndim", stft(z((100, 2, 2))))
+    add("stft/fusable_reject_window", stft(big, W=8))
+    add("stft/fusable_reject_nfft_1", stft(big, nfft=1, sc=SpectrumScaling.PowerSpectrum))
+
+    def stft_dev(keep, n=100, n_ch=2, ld=None, **kw):
+        return lambda ctx: backend._stft_device(resident(ctx, n, n_ch, ld), fs, kw.get("W", 16), hann, kw.get("ov", 50.0),
+                                                kw.get("nfft"), kw.get("det", True), kw.get("pad", True), kw.get("sc", bw), keep)
+    add("stft_dev/array_ld", stft_dev(False, ld=104))
+    add("stft_dev/keep_no_detrend_nfft_12", stft_dev(True, nfft=12, det=False))
+    add("stft_dev/array_power", stft_dev(False, sc=SpectrumScaling.PowerSpectralDensity))
+    add("stft_dev/array_large", stft_dev(False, n=1 << 17, n_ch=2))  # 2^20 values and more come down in chunks
+    add("stft_dev/reject_overlap", stft_dev(True, ov=100.0))
+    add("stft_dev/reject_nfft", stft_dev(True, nfft=1))
+
+    def stft_dev_twice(ctx):  # the second call finds the window in the context
+        x = resident(ctx, 100, 2)
+        backend._stft_device(x, fs, 16, hann, 50.0, None, True, True, bw, True)
+        return backend._stft_device(x, fs, 16, hann, 50.0, 32, False, True, SpectrumScaling.AmplitudeSpectrum, False)
+    add("stft_dev/twice", stft_dev_twice)
+
+    filt = np.zeros((4, 9))
+    filt[0, 1:4], filt[1, 3:6], filt[3, 5:9] = 1.0, 0.5, 0.25
+
+    def band_power(on_device, filters=filt, to_db=True, dct_abs=False, **kw):
+        return lambda ctx: backend._spectrogram_band_power(
+            resident(ctx, 100, 2, 112) if on_device else kw.get("x", np.zeros((100, 2))), fs, kw.get("W", 16), hann,
+            kw.get("ov", 50.0), kw.get("nfft"), kw.get("det", True), kw.get("pad", True), kw.get("sc", bw), filters, to_db, dct_abs)
+    add("band_power/host", band_power(False))
+    add("band_power/host_flat", band_power(False, x=np.zeros(100)))
+    add("band_power/host_no_detrend_no_padding", band_power(False, det=False, pad=False, to_db=False))
+    add("band_power/host_nfft_24", band_power(False, filters=np.ones((2, 13)), nfft=24))
+    add("band_power/resident", band_power(True, to_db=False, dct_abs=True))
+    add("band_power/resident_non_cola_power", band_power(True, ov=33.0, sc=SpectrumScaling.PowerSpectrum))
+    add("band_power/reject_filters", band_power(False, filters=np.zeros((4, 8))))
+    add("band_power/reject_filters_resident", band_power(True, filters=np.zeros(9)))
+    add("band_power/reject_window", band_power(False, W=8))
+    add("band_power/reject_window_resident", band_power(True, W=8))
+
+    # ---- _istft
+    def istft(spec, nfft=16, W=16, step=8, offset=1, total=None):
+        return lambda ctx: backend._istft(spec, nfft, W, step, np.ones(W), 0.5, offset,
+                                          np.shape(spec)[1] + 2 if total is None else total)
+    add("istft/small", istft(z((9, 13, 2), dtype=np.complex128)))
+    add("istft/small_complex64", istft(z((9, 13, 2), dtype=np.complex64), offset=0, total=13))
+    add("istft/real", istft(z((9, 13, 2))))
+    add("istft/nfft_24_window_16", istft(z((13, 13, 2), dtype=np.complex128), nfft=24))
+    add("istft/fused_at", istft(z((8, 1 << 15, 2), dtype=np.complex128), nfft=14, W=8, step=4))        # 2^19 values
+    add("istft/fused_under", istft(z((1, (1 << 19) - 1, 1), dtype=np.complex128), nfft=2, W=2, step=1))  # (2^19 - 1 is prime)
+    add("istft/large_real", istft(z((8, 1 << 15, 2)), nfft=14, W=8, step=4))
+    add("istft/large_complex64", istft(z((8, 1 << 15, 2), dtype=np.complex64), nfft=14, W=8, step=4))
+    add("istft/large_not_contiguous", istft(z((2, 1 << 15, 8), dtype=np.complex128).transpose(2, 1, 0), nfft=14, W=8, step=4))
+    add("istft/reject_nfft", istft(z((9, 13, 2), dtype=np.complex128), nfft=1))
+    add("istft/reject_window", istft(z((9, 13, 2), dtype=np.complex128), nfft=16, W=32))
+    add("istft/fused_reject_window", istft(z((8, 1 << 15, 2), dtype=np.complex128), nfft=14, W=16))
+
+    def istft_dev(nfft=16, W=16, power=False):
+        def fn(ctx):
+            st = backend.DeviceSTFT(DeviceBuffer(ctx, 9 * 13 * 2 * 8), (9, 13, 2), power)
+            return backend._istft_device(st, nfft, W, 8, np.ones(W), 0.5, 1, 15)
+        return fn
+    add("istft_dev/plain", istft_dev())
+
+    # ---- rfft_spectrum
+    add("rfft/planar", lambda ctx: backend.rfft_spectrum(z((100, 2)), 128))
+    add("rfft/flat", lambda ctx: backend.rfft_spectrum(z(100), 128))
+    add("rfft/list", lambda ctx: backend.rfft_spectrum([[0.0, 0.0]] * 100, 128))
+    add("rfft/scale", lambda ctx: backend.rfft_spectrum(z((100, 2)), 100, 0.5))
+    add("rfft/fusable", lambda ctx: backend.rfft_spectrum(big, 1 << 19))
+    add("rfft/fusable_scale", lambda ctx: backend.rfft_spectrum(big, 1 << 20, 0.25))
+    add("rfft/fusable_under", lambda ctx: backend.rfft_spectrum(z(((1 << 19) - 1, 2)), 1 << 19))
+    add("rfft/large_float32", lambda ctx: backend.rfft_spectrum(z((1 << 19, 2), dtype=np.float32), 1 << 19))
+
+    # ---- spectral_division
+    def division(num, n_fft, inv, n_out):
+        return lambda ctx: backend.spectral_division(num, n_fft, inv, n_out)
+    one = np.ones(65, dtype=complex)
+    add("division/one_shared", division(z((100, 2)), 128, one, 120))
+    add("division/one_per_channel", division(z((100, 2)), 128, np.ones((65, 2), dtype=complex), 120))
+    add("division/batch_3", division(z((3, 100, 2)), 128, one, 120))
+    add("division/batch_3_per_channel", division(z((3, 100, 2)), 128, np.ones((65, 2), dtype=complex), 100))
+    inv_big = np.ones((1 << 18) + 1, dtype=complex)
+    add("division/fusable_shared", division(big, 1 << 19, inv_big, 100))
+    add("division/fusable_per_channel", division(big, 1 << 19, np.ones(((1 << 18) + 1, 2), dtype=complex), 1 << 19))
+    add("division/batch_of_fusable_items", division(z((2, 1 << 19, 2)), 1 << 19, inv_big, 100))
+    add("division/large_float32", division(z((1 << 19, 2), dtype=np.float32), 1 << 19, inv_big, 100))
+    inv_20 = np.ones((1 << 19) + 1, dtype=complex)
+    add("division/transposes_at", division(z((1, 1 << 20, 1)), 1 << 20, inv_20, 1 << 20))  # n * n_ch and n_out * n_ch = 2^20
+    add("division/transposes_under", division(z((1, (1 << 20) - 1, 1)), 1 << 20, inv_20, (1 << 20) - 1))
+    add("division/transpose_in_at_out_under", division(z((1, 1 << 19, 2)), 1 << 20, inv_20, (1 << 19) - 1))
+    add("division/reject_inverse_length", division(z((100, 2)), 128, np.ones(64, dtype=complex), 120))
+    add("division/reject_inverse_length_per_channel", division(z((100, 2)), 128, np.ones((2, 65), dtype=complex), 120))
+    add("division/fusable_reject_inverse_length", division(big, 1 << 19, np.ones(64, dtype=complex), 100))
+
+    def division_dev(n_cx, eps):
+        return lambda ctx: backend.spectral_division_device(resident(ctx, 100, 2), resident(ctx, 100, n_cx, 101), 128, 120,
+                                                            (lambda den: np.ones(den.shape[0])) if eps else None)
+    add("division_dev/plain", division_dev(1, False))
+    add("division_dev/regularized_per_channel", division_dev(2, True))
+
+    # ---- FIR filter banks
+    taps = [np.ones(5), np.ones(5) * 0.5, np.ones(5) * 0.25]
+    modes = (("parallel", backend.DS_FB_PARALLEL), ("sequential", backend.DS_FB_SEQUENTIAL), ("summed", backend.DS_FB_SUMMED))
+    for name, mode in modes:
+        add(f"fir_bank/{name}", lambda ctx, m=mode: backend.fir_filter_bank(z((100, 2)), taps, m))
+        add(f"fir_bank/{name}_fusable", lambda ctx, m=mode: backend.fir_filter_bank(big, taps, m))
+        add(f"fir_bank_dev/{name}", lambda ctx, m=mode: backend.fir_filter_bank_device(resident(ctx, 100, 2, 104), taps, m))
+    add("fir_bank/flat", lambda ctx: backend.fir_filter_bank(z(100), taps[:1], backend.DS_FB_PARALLEL))
+    add("fir_bank/fusable_under", lambda ctx: backend.fir_filter_bank(z(((1 << 19) - 1, 2)), taps[:1], backend.DS_FB_SUMMED))
+    add("fir_bank/unequal_taps", lambda ctx: backend.fir_filter_bank(z((100, 2)), [np.ones(5), np.ones(4)], backend.DS_FB_PARALLEL))
+    add("fir_bank/unequal_taps_fusable", lambda ctx: backend.fir_filter_bank(big, [np.ones(5), np.ones(4)], backend.DS_FB_PARALLEL))
+    add("fir_bank_dev/unequal_taps", lambda ctx: backend.fir_filter_bank_device(resident(ctx, 100, 2), [np.ones(5), np.ones(4)],
+                                                                                 backend.DS_FB_PARALLEL))
+
+    def lfilter(b, x, zi=None, a=(1.0,)):
+        return lambda ctx: backend._lfilter_fir(b, a, x, zi)
+    add("lfilter_fir/plain", lfilter(np.ones(5), z((100, 2))))
+    add("lfilter_fir/column_taps", lfilter(np.ones((5, 1)), z((100, 2))))
+    add("lfilter_fir/zi", lfilter(np.ones(5), z((100, 2)), z((4, 2))))
+    add("lfilter_fir/flat", lfilter(np.ones(5), z(100)))
+    add("lfilter_fir/flat_zi", lfilter(np.ones(5), z(100), z(4)))
+    add("lfilter_fir/complex_taps", lfilter(np.ones(5) * (1 + 1j), z((100, 2))))
+    add("lfilter_fir/complex_taps_zi", lfilter(np.ones(5) * (1 + 1j), z((100, 2)), z((4, 2), dtype=complex)))
+    add("lfilter_fir/complex_taps_flat_zi", lfilter(np.ones(5) * (1 + 1j), z(100), z(4, dtype=complex)))
+    add("lfilter_fir/fusable", lfilter(np.ones(5), big))
+    add("lfilter_fir/reject_a", lfilter(np.ones(5), z((100, 2)), a=(1.0, 0.5)))
+    add("lfilter_fir/reject_taps_2d", lfilter(np.ones((2, 5)), z((100, 2))))
+    add("lfilter_fir/reject_complex_signal", lfilter(np.ones(5), z((100, 2), dtype=complex)))
+    add("lfilter_fir/reject_zi_ndim", lfilter(np.ones(5), z((100, 2)), z(4)))
+    add("lfilter_fir/reject_ndim", lfilter(np.ones(5), z((100, 2, 2))))
+    add("lfilter_fir/reject_ndim_complex_taps", lfilter(np.ones(5) * 1j, z((100, 2, 2))))
+    add("lfilter_fir/reject_a_before_complex_signal", lfilter(np.ones((2, 5)), z((100, 2), dtype=complex), a=(1.0, 0.5)))
+
+    add("fir_freqz/two", lambda ctx: backend.fir_transfer_function([np.ones(5), np.ones(3)], np.linspace(0, 24000, 9), fs))
+    add("fir_freqz/reject_frequencies", lambda ctx: backend.fir_transfer_function([np.ones(5)], z((9, 2)), fs))
+
+    # ---- beamformer maps and their spectra
+    def bf(fn, csm_shape=(4, 3, 3), h_shape=(4, 3, 5), *args):
+        return lambda ctx: fn(np.zeros(csm_shape, dtype=complex), np.ones(h_shape, dtype=complex), *args)
+    for name, fn, args in (("das", backend._das_map, ()), ("eig_map", backend.beamformer_eig_map, ("mvdr",)),
+                           ("cleansc", backend.beamformer_cleansc_map, (10, 0.5, True))):
+        add(f"{name}/plain", bf(fn, (4, 3, 3), (4, 3, 5), *args))
+        add(f"{name}/reject_csm", bf(fn, (4, 3, 2), (4, 3, 5), *args))
+        add(f"{name}/reject_csm_ndim", bf(fn, (3, 3), (4, 3, 5), *args))
+        add(f"{name}/reject_steering_bins", bf(fn, (4, 3, 3), (3, 3, 5), *args))
+        add(f"{name}/reject_steering_channels", bf(fn, (4, 3, 3), (4, 2, 5), *args))
+    add("das/float32_inputs", lambda ctx: backend._das_map(np.zeros((4, 3, 3), dtype=np.float32), np.ones((4, 3, 1))))
+    add("eig_map/functional", bf(backend.beamformer_eig_map, (4, 3, 3), (4, 3, 5), "functional", 4.0))
+    add("eig_map/orthogonal", bf(backend.beamformer_eig_map, (4, 3, 3), (4, 3, 5), "orthogonal", 10.0, 2))
+    add("eig_map/reject_method", bf(backend.beamformer_eig_map, (4, 3, 3), (4, 3, 5), "music"))
+    add("cleansc/keep_diagonal", bf(backend.beamformer_cleansc_map, (4, 3, 3), (4, 3, 5), 3, 0.25, False))
+    add("eigh/plain", lambda ctx: backend.hermitian_eigh(np.zeros((4, 3, 3), dtype=complex)))
+    add("eigh/real", lambda ctx: backend.hermitian_eigh(np.zeros((4, 3, 3))))
+    add("eigh/reject_shape", lambda ctx: backend.hermitian_eigh(np.zeros((4, 3, 2), dtype=complex)))
+    for s in SpectrumScaling:
+        add(f"csm_fft/scaling_{s.name}", lambda ctx, s=s: backend._csm_fft(np.zeros((9, 2), dtype=complex), s, None, fs))
+    add("csm_fft/window", lambda ctx: backend._csm_fft(np.zeros((9, 2), dtype=complex), bw, np.ones(16), fs))
+
+    # ---- IIR cascades
+    ident = [1.0, 0, 0, 1, 0, 0]
+    sos2 = [np.array([ident]), np.array([ident] * 2)]
+    for name, mode in modes:
+        add(f"iir/{name}", lambda ctx, m=mode: backend.iir_sos_filter(z((100, 2)), sos2, m))
+        add(f"iir/{name}_zi", lambda ctx, m=mode: backend.iir_sos_filter(z((100, 2)), sos2, m, zi=z((2, 2, 2, 2))))
+        add(f"iir_dev/{name}", lambda ctx, m=mode: backend.iir_sos_filter_device(resident(ctx, 100, 2, 104), sos2, m))
+    add("iir/flat", lambda ctx: backend.iir_sos_filter(z(100), sos2, backend.DS_FB_PARALLEL))
+    add("iir/one_section_flat", lambda ctx: backend.iir_sos_filter(z((100, 2)), [np.array(ident)], backend.DS_FB_SUMMED))
+    add("iir/sequential_32", lambda ctx: backend.iir_sos_filter(z((100, 2)), [np.array([ident] * 16)] * 2, backend.DS_FB_SEQUENTIAL))
+    add("iir/sequential_40", lambda ctx: backend.iir_sos_filter(z((100, 2)), [np.array([ident] * 20)] * 2, backend.DS_FB_SEQUENTIAL))
+    add("iir/sequential_3x15", lambda ctx: backend.iir_sos_filter(z((100, 2)), [np.array([ident] * 15)] * 3, backend.DS_FB_SEQUENTIAL))
+    add("iir/sequential_40_zi", lambda ctx: backend.iir_sos_filter(z((100, 2)), [np.array([ident] * 20)] * 2,
+                                                                   backend.DS_FB_SEQUENTIAL, zi=z((2, 20, 2, 2))))
+    add("iir/parallel_40", lambda ctx: backend.iir_sos_filter(z((100, 2)), [np.array([ident] * 40)], backend.DS_FB_PARALLEL))
+    add("iir/reject_zi_shape", lambda ctx: backend.iir_sos_filter(z((100, 2)), sos2, backend.DS_FB_PARALLEL, zi=z((2, 2, 2, 3))))
+    add("iir/reject_zi_shape_sequential", lambda ctx: backend.iir_sos_filter(z((100, 2)), sos2, backend.DS_FB_SEQUENTIAL,
+                                                                             zi=z((1, 3, 2, 2))))
+    add("iir_dev/sequential_32", lambda ctx: backend.iir_sos_filter_device(
+        resident(ctx, 100, 2), [np.array([ident] * 16)] * 2, backend.DS_FB_SEQUENTIAL))
+    add("iir_dev/sequential_long", lambda ctx: backend.iir_sos_filter_device(
+        resident(ctx, 100, 2), [np.array([ident] * 20)] * 2, backend.DS_FB_SEQUENTIAL))
+    add("iir_dev/sequential_3x15", lambda ctx: backend.iir_sos_filter_device(
+        resident(ctx, 100, 2, 104), [np.array([ident] * 15)] * 3, backend.DS_FB_SEQUENTIAL))
+
+    # ---- the reference-shaped callers that build an STFT plan
+    def signal(ctx, on_device, n=100, n_ch=2, **par):
+        s = (dsp.Signal.from_planar_f32(resident(ctx, n, n_ch), fs) if on_device else dsp.Signal(None, np.zeros((n, n_ch)), fs))
+        s.set_spectrogram_parameters(**{"window_length_samples": 16, **par})
+        return s
+
+    def spectrogram(sig_on_device, on_device=False, **par):
+        return lambda ctx: signal(ctx, sig_on_device, **par).get_spectrogram(on_device=on_device)
+
+    def round_trip(sig_on_device, on_device, **par):
+        def fn(ctx):
+            s = signal(ctx, sig_on_device, **par)
+            return dsp.transforms.istft(s.get_spectrogram(on_device=on_device)[2], original_signal=s)
+        return fn
+    for where, dev in (("host", False), ("resident", True)):
+        add(f"signal/spectrogram_{where}", spectrogram(dev))
+        add(f"signal/spectrogram_{where}_on_device", spectrogram(dev, True))
+        add(f"signal/spectrogram_{where}_non_cola_power", spectrogram(dev, overlap_percent=33.0, detrend=True,
+                                                                      scaling=SpectrumScaling.PowerSpectrum))
+        add(f"signal/spectrogram_{where}_reject_window", spectrogram(dev, window_length_samples=8))
+        add(f"signal/istft_{where}", round_trip(dev, False))
+        add(f"signal/istft_{where}_on_device", round_trip(dev, True))
+        add(f"signal/istft_{where}_on_device_no_padding", round_trip(dev, True, padding=False, fft_length_samples=32))
+        add(f"signal/log_mel_{where}", lambda ctx, dev=dev: dsp.transforms.log_mel_spectrogram(
+            signal(ctx, dev, n=300, window_length_samples=64), n_bands=4, generate_plot=False))
+        add(f"signal/mfcc_{where}", lambda ctx, dev=dev: dsp.transforms.mfcc(
+            signal(ctx, dev, n=300, window_length_samples=64), mel_filters=np.ones((3, 33)), generate_plot=False))
+        add(f"signal/chroma_{where}", lambda ctx, dev=dev: dsp.transforms.chroma_stft(
+            signal(ctx, dev, n=300, window_length_samples=64)))
+        add(f"signal/axes_{where}", lambda ctx, dev=dev: dsp.transforms._spectrogram_axes(signal(ctx, dev)))
+        add(f"signal/axes_{where}_nfft_24_non_cola", lambda ctx, dev=dev: dsp.transforms._spectrogram_axes(
+            signal(ctx, dev, fft_length_samples=24, overlap_percent=33.0, padding=False)))
+        add(f"signal/axes_{where}_reject_overlap", lambda ctx, dev=dev: dsp.transforms._spectrogram_axes(
+            signal(ctx, dev, overlap_percent=100.0)))
+    add("signal/log_mel_bin_mismatch", lambda ctx: dsp.transforms.log_mel_spectrogram(
+        signal(ctx, False, n=300, window_length_samples=64, fft_length_samples=32), n_bands=4, generate_plot=False))
+    return c
+
+
+def record(case_list=cases):
+    """name -> transcript of every case of `cases` or `xform_cases`."""
+    return {name: run_case(fn, **patch) for name, (fn, patch) in case_list().items()}
 
 
 def entries_reached(transcript):
@@ -517,10 +790,14 @@ def entries_reached(transcript):
 
 
 if __name__ == "__main__":
-    t = record()
-    missing = sorted(set(WELCH_ENTRIES) - entries_reached(t))
+    which = {"welch": (cases, FIXTURE, WELCH_ENTRIES), "xform": (xform_cases, FIXTURE_XFORM, XFORM_ENTRIES)}
+    if len(sys.argv) != 2 or sys.argv[1] not in which:
+        sys.exit("usage: record_backend_calls.py welch|xform   (rewrites that fixture from the shim as it is NOW)")
+    case_list, fixture, entries = which[sys.argv[1]]
+    t = record(case_list)
+    missing = sorted(set(entries) - entries_reached(t))
     assert not missing, f"no case reaches {missing}"
-    with open(FIXTURE, "w") as f:
+    with open(fixture, "w") as f:
         json.dump(t, f, indent=0, sort_keys=True, separators=(",", ":"))
         f.write("\n")
     print(f"{len(t)} cases, {sum(len(c['log']) for c in t.values())} events, entries: {sorted(entries_reached(t))}")

@@ -18,16 +18,15 @@ x = np.random.default_rng(0).standard_normal((n, n_ch))
 sizes = sys.argv[1:] or ["256", "512", "1024", "2048", "4096"]  # "W" or "W:nfft"
 for arg in sizes:
     W, nfft = (int(a) for a in arg.split(":")) if ":" in arg else (int(arg), None)
-    pl = backend._stft_plan(x, 48000, W, Window.Hann, 50, nfft, True, SpectrumScaling.FFTBackward)
-    d_x = DeviceBuffer.from_array(ctx, pl["xp"])
-    d_w = DeviceBuffer.from_array(ctx, pl["w32"])
-    nbytes_out = pl["B"] * pl["n_frames"] * pl["n_ch"] * 8
+    pl = backend._stft_plan(n, n_ch, 48000, W, Window.Hann, 50, nfft, False, True, SpectrumScaling.FFTBackward)
+    xp = backend._planar_f32(x)
+    d_x = DeviceBuffer.from_array(ctx, xp)
+    d_w = DeviceBuffer.from_array(ctx, pl.window32)
+    nbytes_out = int(np.prod(pl.shape)) * 8
     d_s = DeviceBuffer(ctx, nbytes_out)
 
     def step():
-        ctx.check(ctx.lib.ds_stft_r2c_dev(ctx.handle, C.c_void_p(d_x.ptr), pl["n"], pl["n_ch"], pl["n"], pl["W"],
-                                          pl["hop"], pl["nfft"], pl["pad_front"], pl["n_frames"],
-                                          C.c_void_p(d_w.ptr), 0, pl["scale"], pl["edge"], pl["power"],
+        ctx.check(ctx.lib.ds_stft_r2c_dev(ctx.handle, C.c_void_p(d_x.ptr), *pl.tail(C.c_void_p(d_w.ptr), pl.n),
                                           C.c_void_p(d_s.ptr)), "ds_stft_r2c_dev")
     for _ in range(3):
         step()
@@ -38,13 +37,13 @@ for arg in sizes:
         step()
     ctx.sync()
     ms = (time.perf_counter() - t0) / K * 1e3
-    tot = pl["xp"].nbytes + nbytes_out
+    tot = xp.nbytes + nbytes_out
     ctx.profile_enable(True)
     for _ in range(5):
         step()
     ctx.sync()
     print("   kernels (ms over 5 calls):", ctx.profile_report())
     ctx.profile_enable(False)
-    print(f"W {arg:>13s}: {ms:7.3f} ms  frames {pl['n_frames']:6d}  {tot / 1e6:7.1f} MB  {tot / ms / 1e9:5.2f} TB/s", flush=True)
+    print(f"W {arg:>13s}: {ms:7.3f} ms  frames {pl.n_frames:6d}  {tot / 1e6:7.1f} MB  {tot / ms / 1e9:5.2f} TB/s", flush=True)
     for d in (d_x, d_w, d_s):
         d.free()
