@@ -29,6 +29,8 @@ NO_SCRATCH = [
     "k_cwt_inv", "k_cwt_squeeze",
     "k_to_log", "k_smooth", "k_to_lin", "k_polar", "k_unwrap", "k_recombine",
     "k_dft", "k_csmooth", "k_colmap",
+    "k_fft_lds", "5fft6411k_transpose", "5fft647k_chirp", "5fft646k_blue", "5fft646k_load", "5fft647k_store",
+    "5fft647k_point", "5fft6410k_gradient",
 ]
 
 

@@ -134,6 +134,12 @@ SIGNATURES = {
                              C.c_double, C.c_double, C.c_void_p]),
     "ds_complex_smooth": (C.c_int, [ctx_p, C.c_void_p, i64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "ds_fft_c128": (C.c_int, [ctx_p, C.c_void_p, C.c_int, i64, C.c_int, i64, C.c_int, C.c_void_p]),
+    "ds_hilbert": (C.c_int, [ctx_p, C.c_void_p, i64, C.c_int, C.c_void_p]),
+    "ds_cepstrum": (C.c_int, [ctx_p, C.c_void_p, i64, C.c_int, C.c_int, C.c_void_p]),
+    "ds_from_cepstrum": (C.c_int, [ctx_p, C.c_void_p, i64, C.c_int, C.c_void_p]),
+    "ds_min_phase": (C.c_int, [ctx_p, C.c_void_p, i64, C.c_int, i64, C.c_int, i64, C.c_double, C.c_void_p]),
+    "ds_group_delay_phase": (C.c_int, [ctx_p, C.c_void_p, i64, C.c_int, C.c_double, C.c_void_p]),
     "ds_welch_tf_x64": (C.c_int, [ctx_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, i64, C.c_int, C.c_int, C.c_int,
                                   C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int,
                                   C.c_void_p, C.c_void_p]),

@@ -1728,3 +1728,110 @@ def complex_smoothing(spectrum, freqs_hz, octave_fraction, domain, window_values
                                         _ptr(wx), _ptr(wy), len(wy), SMOOTHING_DOMAINS.index(name), _ptr(out)),
               "ds_complex_smooth")
     return out
+
+
+# ---- complex128 transforms of any length and what is built on them (csrc/kernels_fft64.hpp) -----------------------
+# transform lengths of one call (csrc/size_guards.hpp; DS_ERR_UNSUP above)
+FFT64_MAX_POW2 = 1 << 22  # powers of two: the four-step route
+FFT64_MAX_ANY = 1 << 21   # every other length: Bluestein on a power of two >= 2 n - 1
+MIN_PHASE_OUTPUTS = ("spectrum", "phase", "ir", "group_delay")  # DS_MIN_PHASE_* of the header
+
+
+def _fft64_guard(n: int) -> None:
+    """NotImplementedError for a transform length beyond the kernels' bounds, before anything reaches the device."""
+    n = int(n)
+    pow2 = n > 0 and n & (n - 1) == 0
+    if n > (FFT64_MAX_POW2 if pow2 else FFT64_MAX_ANY):
+        raise NotImplementedError(f"a float64 transform of {n} points is beyond the device kernels' bounds "
+                                  f"(powers of two up to {FFT64_MAX_POW2}, other lengths up to {FFT64_MAX_ANY})")
+
+
+def _host_columns(a, dtype):
+    if isinstance(a, DevicePlanar):
+        raise NotImplementedError("device-resident (fp32 planar) inputs are not built for the float64 transforms: "
+                                  "pass the host float64 array")
+    a = np.ascontiguousarray(a, dtype=dtype)
+    assert a.ndim == 2, "the array is (rows, channels)"
+    return a
+
+
+def fft_c128(data, n: int | None = None, inverse: bool = False):
+    """numpy.fft.fft / ifft(data, n, axis=0) of a real or complex (rows, channels) host array on the device, complex128.
+    Any n >= 1 within the bounds; the input is zero-padded or cropped to n rows."""
+    cplx = np.iscomplexobj(data)
+    a = _host_columns(data, np.complex128 if cplx else np.float64)
+    n = a.shape[0] if n is None else int(n)
+    if n < 1 or a.shape[0] < 1 or a.shape[1] < 1:
+        raise ValueError("fft_c128: empty input or n < 1")
+    _fft64_guard(n)
+    out = np.empty((n, a.shape[1]), dtype=np.complex128)
+    ctx = get_context()
+    ctx.check(ctx.lib.ds_fft_c128(ctx.handle, _ptr(a), int(cplx), a.shape[0], a.shape[1], n, int(bool(inverse)),
+                                  _ptr(out)), "ds_fft_c128")
+    return out
+
+
+def hilbert(time_data):
+    """The analytic signal of a real (samples, channels) array (transforms.hilbert), complex128."""
+    a = _host_columns(time_data, np.float64)
+    _fft64_guard(a.shape[0])
+    out = np.empty(a.shape, dtype=np.complex128)
+    ctx = get_context()
+    ctx.check(ctx.lib.ds_hilbert(ctx.handle, _ptr(a), a.shape[0], a.shape[1], _ptr(out)), "ds_hilbert")
+    return out
+
+
+def cepstrum(time_data, complex: bool = True):
+    """ifft(log(fft(x))) -- the principal logarithm -- or, complex False, ifft(log|fft(x)|); complex128 either way, as
+    numpy returns it (transforms.cepstrum)."""
+    a = _host_columns(time_data, np.float64)
+    _fft64_guard(a.shape[0])
+    out = np.empty(a.shape, dtype=np.complex128)
+    ctx = get_context()
+    ctx.check(ctx.lib.ds_cepstrum(ctx.handle, _ptr(a), a.shape[0], a.shape[1], int(bool(complex)), _ptr(out)),
+              "ds_cepstrum")
+    return out
+
+
+def from_complex_cepstrum(cepstrum):
+    """real(ifft(exp(fft(cepstrum)))) of a (quefrency, channels) array (transforms.from_complex_cepstrum), float64."""
+    a = _host_columns(cepstrum, np.complex128)
+    _fft64_guard(a.shape[0])
+    out = np.empty(a.shape, dtype=np.float64)
+    ctx = get_context()
+    ctx.check(ctx.lib.ds_from_cepstrum(ctx.handle, _ptr(a), a.shape[0], a.shape[1], _ptr(out)), "ds_from_cepstrum")
+    return out
+
+
+def min_phase_fft_length(n_samples: int, padding_factor: int) -> int:
+    """The transform length of helpers/minimum_phase.py:30-32."""
+    from scipy.fft import next_fast_len
+    return int(next_fast_len(max(int(n_samples) * int(padding_factor), int(n_samples))))
+
+
+def min_phase(time_data, n_fft: int, output: str, n_out: int = 0, delta_f: float = 1.0):
+    """The real-cepstrum minimum-phase equivalent of a real (samples, channels) array zero-padded to n_fft rows
+    (helpers/minimum_phase.py:8-79), one upload and one download.  output: "spectrum" (n_fft, C) complex128; "phase"
+    of the bins 0 .. n_fft // 2; "ir", the first n_out rows; "group_delay", -gradient(unwrap(phase)) / (2 pi delta_f)."""
+    a = _host_columns(time_data, np.float64)
+    n_fft = int(n_fft)
+    _fft64_guard(n_fft)
+    kind = MIN_PHASE_OUTPUTS.index(output)
+    rows = {"spectrum": n_fft, "ir": int(n_out)}.get(output, n_fft // 2 + 1)
+    out = np.empty((rows, a.shape[1]), dtype=np.complex128 if output == "spectrum" else np.float64)
+    ctx = get_context()
+    ctx.check(ctx.lib.ds_min_phase(ctx.handle, _ptr(a), a.shape[0], a.shape[1], n_fft, kind, int(n_out), float(delta_f),
+                                   _ptr(out)), "ds_min_phase")
+    return out
+
+
+def group_delay_phase(time_data, delta_f: float):
+    """-gradient(unwrap(angle(rfft(x)))) / (2 pi delta_f) on the n // 2 + 1 bins of a real (samples, channels) array
+    (_group_delay_direct of the reference on the spectrum's phase), float64."""
+    a = _host_columns(time_data, np.float64)
+    _fft64_guard(a.shape[0])
+    out = np.empty((a.shape[0] // 2 + 1, a.shape[1]), dtype=np.float64)
+    ctx = get_context()
+    ctx.check(ctx.lib.ds_group_delay_phase(ctx.handle, _ptr(a), a.shape[0], a.shape[1], float(delta_f), _ptr(out)),
+              "ds_group_delay_phase")
+    return out

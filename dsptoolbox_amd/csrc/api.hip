@@ -45,6 +45,7 @@
 #include "kernels_cwt.hpp"
 #include "kernels_smooth.hpp"
 #include "kernels_direct.hpp"
+#include "kernels_fft64.hpp"
 #include "size_guards.hpp"
 
 using namespace dsk;
@@ -71,6 +72,16 @@ struct ds_ctx {
     std::map<std::pair<int64_t, int64_t>, BlueEntry> blue;
     size_t blue_bytes = 0;
     uint64_t blue_clock = 0;
+    // float64 transforms (kernels_fft64.hpp): the 8192-point twiddle table, and per length n Bluestein's chirp w [n]
+    // followed by the spectrum of its filter [M] in one allocation, least recently used out under a byte cap
+    double2* fft64_tw = nullptr;
+    struct Blue64Entry {
+        double2* ptr;
+        size_t bytes;
+        uint64_t stamp;
+    };
+    std::map<int64_t, Blue64Entry> blue64;
+    size_t blue64_bytes = 0;
     float2* w4_tables = nullptr;  // welch4096::host_tables()
     float2* stft_dif_tw[2] = {nullptr, nullptr};  // stft4k::host_twiddles(8192 / 16384)
     float2* fir16k_tables = nullptr;  // fir16k::host_tables()
@@ -205,6 +216,8 @@ extern "C" void ds_destroy(ds_ctx* c) {
     for (float2* t : c->stft_wave_tables)
         if (t) (void)hipFree(t);
     for (auto& kv : c->blue) (void)hipFree(kv.second.ptr);
+    for (auto& kv : c->blue64) (void)hipFree(kv.second.ptr);
+    if (c->fft64_tw) (void)hipFree(c->fft64_tw);
     for (auto& r : c->prof_recs) {
         (void)hipEventDestroy(r.a);
         (void)hipEventDestroy(r.b);
@@ -4020,6 +4033,276 @@ extern "C" int ds_complex_smooth(ds_ctx* c, const double* z, int64_t n_bins, int
     if (power) CHK(colmap(ds, 1));
     CHK(recombine(ds));
     return ds_download(c, out, dz, n * 16);
+}
+
+// ---- complex128 transforms of any length and what is built on them (kernels_fft64.hpp) -----------------------------
+struct Fft64Plan {
+    int64_t n = 0, ld = 0;  // ld: the column stride on the device, n or Bluestein's M
+    int lg = 0;             // log2 of the power-of-two transform that runs (of n or of M)
+    bool blue = false;
+    const double2 *tw = nullptr, *w = nullptr, *B = nullptr;
+};
+static const size_t kBlue64CapBytes = (size_t)256 << 20;
+
+// the power-of-two transform of n_cols columns, unnormalised; the result is in x afterwards (x and tmp may have swapped)
+static int fft64_pow2(ds_ctx* c, const double2* tw, double2*& x, double2*& tmp, int64_t n, int lg, int n_cols,
+                      int64_t col_stride, bool inv) {
+    using namespace fft64;
+    auto lds = [&](double2* buf, int len, int lgl, int64_t batches, int64_t twid_n) {
+        const LdsArgs a{buf, col_stride, len, lgl, tw, twid_n};
+        const dim3 grid((unsigned)batches, (unsigned)n_cols);
+        return inv ? launch(c, "fft64_lds@inv", k_fft_lds<true>, grid, NT, (size_t)len * 16, a)
+                   : launch(c, "fft64_lds", k_fft_lds<false>, grid, NT, (size_t)len * 16, a);
+    };
+    if (n <= LDS_MAX) return n > 1 ? lds(x, (int)n, lg, 1, 0) : DS_OK;
+    const int lg1 = lg / 2, lg2 = lg - lg1, n1 = 1 << lg1, n2 = 1 << lg2;  // x[j1 n2 + j2]
+    auto transpose = [&](const double2* in, double2* out, int rows, int cols) {
+        return launch(c, "fft64_transpose", k_transpose, dim3((unsigned)(cols / 32), (unsigned)(rows / 32), (unsigned)n_cols), NT, 0,
+                      TransposeArgs{in, out, rows, cols, col_stride});
+    };
+    CHK(transpose(x, tmp, n1, n2));  // [j2][j1]
+    CHK(lds(tmp, n1, lg1, n2, n));   // [j2][k1] w_n^(j2 k1)
+    CHK(transpose(tmp, x, n2, n1));  // [k1][j2]
+    CHK(lds(x, n2, lg2, n1, 0));     // [k1][k2]
+    CHK(transpose(x, tmp, n1, n2));  // [k2][k1]: bin k1 + n1 k2
+    std::swap(x, tmp);
+    return DS_OK;
+}
+
+// Bluestein's tables of length n: built once, kept until the cap pushes the least recently used ones out
+static int fft64_blue_tables(ds_ctx* c, Fft64Plan* pl) {
+    using namespace fft64;
+    const int64_t n = pl->n, M = pl->ld;
+    auto it = c->blue64.find(n);
+    if (it == c->blue64.end()) {
+        const size_t bytes = (size_t)(n + M) * 16;
+        while (!c->blue64.empty() && c->blue64_bytes + bytes > kBlue64CapBytes) {
+            auto old = c->blue64.begin();
+            for (auto e = c->blue64.begin(); e != c->blue64.end(); ++e)
+                if (e->second.stamp < old->second.stamp) old = e;
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+            HIPCHK(c, hipFree(old->second.ptr));
+            c->blue64_bytes -= old->second.bytes;
+            c->blue64.erase(old);
+        }
+        double2* tmp;
+        CHK(carve(c, &c->ws, &c->ws_bytes, [&](Carver& cv) { tmp = cv.take<double2>(M); }));
+        double2* tab;
+        if (hipMalloc((void**)&tab, bytes) != hipSuccess) return fail(c, DS_ERR_NOMEM, "fft64: hipMalloc of the chirp tables failed");
+        double2* B = tab + n;
+        int rc = launch(c, "fft64_chirp", k_chirp, dim3((unsigned)((M + NT - 1) / NT)), NT, 0, ChirpArgs{tab, B, n, M});
+        double2* res = B;
+        if (rc == DS_OK) rc = fft64_pow2(c, pl->tw, res, tmp, M, pl->lg, 1, M, false);
+        if (rc == DS_OK && res != B && hipMemcpyAsync(B, res, (size_t)M * 16, hipMemcpyDeviceToDevice, c->stream) != hipSuccess)
+            rc = fail(c, DS_ERR_HIP, "fft64: copy of the chirp spectrum failed");
+        if (rc != DS_OK) {
+            (void)hipStreamSynchronize(c->stream);
+            (void)hipFree(tab);
+            return rc;
+        }
+        it = c->blue64.emplace(n, ds_ctx::Blue64Entry{tab, bytes, 0}).first;
+        c->blue64_bytes += bytes;
+    }
+    it->second.stamp = ++c->blue_clock;
+    pl->w = it->second.ptr;
+    pl->B = it->second.ptr + n;
+    return DS_OK;
+}
+
+// What every entry checks before anything is uploaded: the shape, the two length bounds, the device memory the call
+// will hold (two planar buffers, `extra` bytes of further workspace, `io` bytes of staging, the tables); then the tables.
+// The entry carves its workspace next, still before staged() uploads anything.
+static int fft64_plan(ds_ctx* c, const char* who, int64_t n, int64_t n_ch, size_t extra, size_t io, Fft64Plan* pl) {
+    const std::string w(who);
+    if (n < 1 || n_ch < 1) return fail(c, DS_ERR_ARG, w + ": bad shape");
+    if (fft64_len_unsupported(n))
+        return fail(c, DS_ERR_UNSUP, w + ": transform lengths above 2^22 (powers of two) or 2^21 (any other) are not built");
+    if (n_ch > 65535) return fail(c, DS_ERR_UNSUP, w + ": more than 65535 channels in one call is not built");
+    pl->n = n;
+    pl->blue = !is_pow2(n);
+    int64_t M = 1;
+    int lg = 0;
+    while (M < (pl->blue ? 2 * n - 1 : n)) M <<= 1, ++lg;
+    pl->ld = M;
+    pl->lg = lg;
+    HIPCHK(c, hipSetDevice(c->device));
+    const bool have_tab = pl->blue && c->blue64.count(n);
+    const size_t tables = pl->blue && !have_tab ? (size_t)(n + 2 * M) * 16 : 0;
+    // as reserve() will allocate them: each buffer grows by an eighth and 4 KB; 1 MB for the carves' 256-byte alignment
+    auto reserved = [](size_t bytes) { return bytes + bytes / 8 + 4096; };
+    const size_t need = reserved(2 * (size_t)M * (size_t)n_ch * 16 + extra + (1 << 20)) + reserved(io + (1 << 20)) + tables;
+    size_t free_b = 0, total_b = 0;
+    CHK(ds_mem_info(c, &free_b, &total_b));
+    if (need > free_b + c->ws_bytes + c->io_bytes)
+        return fail(c, DS_ERR_NOMEM, w + ": the call needs more device memory than is free");
+    if (!c->fft64_tw) {
+        HIPCHK(c, hipMalloc((void**)&c->fft64_tw, (size_t)(fft64::LDS_MAX / 2) * 16));
+        hipLaunchKernelGGL(f64c::k_twiddles, dim3(fft64::LDS_MAX / 2 / 256), dim3(256), 0, c->stream, c->fft64_tw, fft64::LDS_MAX / 2);
+        HIPCHK(c, hipGetLastError());
+    }
+    pl->tw = c->fft64_tw;
+    return pl->blue ? fft64_blue_tables(c, pl) : DS_OK;
+}
+
+// One call's device state and its steps; every step works on the planar array x (column stride pl.ld).
+struct Fft64Run {
+    ds_ctx* c;
+    Fft64Plan pl;
+    int n_ch;
+    double2 *x = nullptr, *tmp = nullptr;
+    double *pa = nullptr, *pb = nullptr;  // (n_phase, C) real arrays of the group delay
+    dim3 flat(int64_t count) const { return dim3((unsigned)((count + fft64::NT - 1) / fft64::NT)); }
+    static size_t phase_bytes(int64_t n_phase, int n_ch) { return 2 * (((size_t)n_phase * n_ch * 8 + 255) & ~size_t(255)); }
+    int carve_ws(int64_t n_phase) {
+        return carve(c, &c->ws, &c->ws_bytes, [&](Carver& cv) {
+            x = cv.take<double2>((size_t)pl.ld * n_ch);
+            tmp = cv.take<double2>((size_t)pl.ld * n_ch);
+            pa = cv.take<double>((size_t)n_phase * n_ch);
+            pb = cv.take<double>((size_t)n_phase * n_ch);
+        });
+    }
+    int load(const void* in_dev, bool cplx, int64_t n_in) {
+        return launch(c, "fft64_load", fft64::k_load, flat(pl.ld * n_ch), fft64::NT, 0,
+                      fft64::LoadArgs{(const double*)in_dev, cplx ? 1 : 0, n_in, pl.n, pl.ld, n_ch, x});
+    }
+    int fft(bool inv) {
+        using namespace fft64;
+        if (!pl.blue) return fft64_pow2(c, pl.tw, x, tmp, pl.n, pl.lg, n_ch, pl.ld, inv);
+        auto blue = [&](int mode, const double2* tab, double scale) {
+            const int64_t rows = mode == BLUE_POST ? pl.n : pl.ld;
+            return launch(c, "fft64_blue", k_blue, flat(rows * n_ch), NT, 0, BlueArgs{x, tab, pl.n, pl.ld, n_ch, mode, inv ? 1 : 0, scale});
+        };
+        CHK(blue(BLUE_PRE, pl.w, 1.0));
+        CHK(fft64_pow2(c, pl.tw, x, tmp, pl.ld, pl.lg, n_ch, pl.ld, false));
+        CHK(blue(BLUE_MUL, pl.B, 1.0 / (double)pl.ld));
+        CHK(fft64_pow2(c, pl.tw, x, tmp, pl.ld, pl.lg, n_ch, pl.ld, true));
+        return blue(BLUE_POST, pl.w, 1.0);
+    }
+    int point(int mode, double scale) {
+        return launch(c, "fft64_point", fft64::k_point, flat(pl.n * n_ch), fft64::NT, 0, fft64::PointArgs{x, pl.n, pl.ld, n_ch, mode, scale});
+    }
+    int store(int mode, int64_t rows, double scale, void* out_dev) {
+        return launch(c, "fft64_store", fft64::k_store, flat(rows * n_ch), fft64::NT, 0,
+                      fft64::StoreArgs{x, pl.ld, rows, n_ch, mode, scale, (double*)out_dev});
+    }
+    // -gradient(unwrap(angle(x[0 .. nb)))) / (2 pi delta_f)
+    int group_delay(int64_t nb, double delta_f, void* out_dev) {
+        CHK(store(fft64::STORE_ANGLE, nb, 1.0, pa));
+        CHK(launch(c, "fft64_unwrap", dssmooth::k_unwrap, dim3((unsigned)n_ch), dssmooth::NT, 0,
+                   dssmooth::UnwrapArgs{pa, nb, (int64_t)n_ch, pb}));
+        return launch(c, "fft64_gradient", fft64::k_gradient, flat(nb * n_ch), fft64::NT, 0,
+                      fft64::GradArgs{pb, nb, n_ch, delta_f, (double*)out_dev});
+    }
+};
+
+extern "C" int ds_fft_c128(ds_ctx* c, const double* in, int in_complex, int64_t n_in, int n_ch, int64_t n_fft, int inverse,
+                           double* out) {
+    if (!c || !in || !out) return fail(c, DS_ERR_ARG, "ds_fft_c128: null argument");
+    if (n_in < 1) return fail(c, DS_ERR_ARG, "ds_fft_c128: bad shape");
+    const size_t e_in = in_complex ? 16 : 8;
+    Fft64Run r{c, {}, n_ch};
+    // rows of the input past n_fft are never read: they are not uploaded either
+    const int64_t n_up = std::min(n_in, std::max<int64_t>(n_fft, 1));
+    CHK(fft64_plan(c, "ds_fft_c128", n_fft, n_ch, 0, ((size_t)n_up * e_in + (size_t)n_fft * 16) * (size_t)n_ch, &r.pl));
+    CHK(r.carve_ws(0));
+    return staged(c, {{e_in, (size_t)n_up * n_ch, in, nullptr}, {16, (size_t)n_fft * n_ch, nullptr, out}}, [&](void* const* d) {
+        CHK(r.load(d[0], in_complex != 0, n_up));
+        CHK(r.fft(inverse != 0));
+        return r.store(fft64::STORE_COMPLEX, n_fft, inverse ? 1.0 / (double)n_fft : 1.0, d[1]);
+    });
+}
+
+extern "C" int ds_hilbert(ds_ctx* c, const double* x, int64_t n, int n_ch, double* out) {
+    if (!c || !x || !out) return fail(c, DS_ERR_ARG, "ds_hilbert: null argument");
+    Fft64Run r{c, {}, n_ch};
+    CHK(fft64_plan(c, "ds_hilbert", n, n_ch, 0, (size_t)n * 24 * (size_t)n_ch, &r.pl));
+    CHK(r.carve_ws(0));
+    return staged(c, {{8, (size_t)n * n_ch, x, nullptr}, {16, (size_t)n * n_ch, nullptr, out}}, [&](void* const* d) {
+        CHK(r.load(d[0], false, n));
+        CHK(r.fft(false));
+        CHK(r.point(fft64::POINT_MASK, 1.0));
+        CHK(r.fft(true));
+        return r.store(fft64::STORE_COMPLEX, n, 1.0 / (double)n, d[1]);
+    });
+}
+
+extern "C" int ds_cepstrum(ds_ctx* c, const double* x, int64_t n, int n_ch, int complex_cepstrum, double* out) {
+    if (!c || !x || !out) return fail(c, DS_ERR_ARG, "ds_cepstrum: null argument");
+    Fft64Run r{c, {}, n_ch};
+    CHK(fft64_plan(c, "ds_cepstrum", n, n_ch, 0, (size_t)n * 24 * (size_t)n_ch, &r.pl));
+    CHK(r.carve_ws(0));
+    return staged(c, {{8, (size_t)n * n_ch, x, nullptr}, {16, (size_t)n * n_ch, nullptr, out}}, [&](void* const* d) {
+        CHK(r.load(d[0], false, n));
+        CHK(r.fft(false));
+        CHK(r.point(complex_cepstrum ? fft64::POINT_LOG : fft64::POINT_LOGABS, 1.0));
+        CHK(r.fft(true));
+        return r.store(fft64::STORE_COMPLEX, n, 1.0 / (double)n, d[1]);
+    });
+}
+
+extern "C" int ds_from_cepstrum(ds_ctx* c, const double* cepstrum, int64_t n, int n_ch, double* out) {
+    if (!c || !cepstrum || !out) return fail(c, DS_ERR_ARG, "ds_from_cepstrum: null argument");
+    Fft64Run r{c, {}, n_ch};
+    CHK(fft64_plan(c, "ds_from_cepstrum", n, n_ch, 0, (size_t)n * 24 * (size_t)n_ch, &r.pl));
+    CHK(r.carve_ws(0));
+    return staged(c, {{16, (size_t)n * n_ch, cepstrum, nullptr}, {8, (size_t)n * n_ch, nullptr, out}}, [&](void* const* d) {
+        CHK(r.load(d[0], true, n));
+        CHK(r.fft(false));
+        CHK(r.point(fft64::POINT_EXP, 1.0));
+        CHK(r.fft(true));
+        return r.store(fft64::STORE_REAL, n, 1.0 / (double)n, d[1]);
+    });
+}
+
+extern "C" int ds_min_phase(ds_ctx* c, const double* x, int64_t n, int n_ch, int64_t n_fft, int output, int64_t n_out,
+                            double delta_f, double* out) {
+    if (!c || !x || !out) return fail(c, DS_ERR_ARG, "ds_min_phase: null argument");
+    if (n < 1 || output < DS_MIN_PHASE_SPECTRUM || output > DS_MIN_PHASE_GROUP_DELAY)
+        return fail(c, DS_ERR_ARG, "ds_min_phase: bad shape or unknown output");
+    const int64_t nb = n_fft / 2 + 1;
+    const bool gd = output == DS_MIN_PHASE_GROUP_DELAY;
+    if (output == DS_MIN_PHASE_IR && (n_out < 1 || n_out > n_fft)) return fail(c, DS_ERR_ARG, "ds_min_phase: n_out outside [1, n_fft]");
+    if (gd && (nb < 2 || !(delta_f > 0.0))) return fail(c, DS_ERR_ARG, "ds_min_phase: the group delay needs two bins and delta_f > 0");
+    const size_t e_out = output == DS_MIN_PHASE_SPECTRUM ? 16 : 8;
+    const int64_t rows = output == DS_MIN_PHASE_SPECTRUM ? n_fft : (output == DS_MIN_PHASE_IR ? n_out : nb);
+    Fft64Run r{c, {}, n_ch};
+    const int64_t n_up = std::min(n, std::max<int64_t>(n_fft, 1));
+    CHK(fft64_plan(c, "ds_min_phase", n_fft, n_ch, gd ? Fft64Run::phase_bytes(nb, n_ch) : 0,
+                   ((size_t)n_up * 8 + (size_t)std::max<int64_t>(rows, 0) * e_out) * (size_t)n_ch, &r.pl));
+    CHK(r.carve_ws(gd ? nb : 0));
+    return staged(c, {{8, (size_t)n_up * n_ch, x, nullptr}, {e_out, (size_t)rows * n_ch, nullptr, out}}, [&](void* const* d) {
+        using namespace fft64;
+        const double inv_n = 1.0 / (double)n_fft;
+        CHK(r.load(d[0], false, n_up));
+        CHK(r.fft(false));
+        CHK(r.point(POINT_LOGABS, 1.0));
+        CHK(r.fft(true));
+        CHK(r.point(POINT_FOLD, inv_n));  // the real cepstrum, folded
+        CHK(r.fft(false));
+        CHK(r.point(POINT_EXP, 1.0));     // the minimum-phase spectrum
+        switch (output) {
+        case DS_MIN_PHASE_SPECTRUM: return r.store(STORE_COMPLEX, n_fft, 1.0, d[1]);
+        case DS_MIN_PHASE_PHASE: return r.store(STORE_ANGLE, nb, 1.0, d[1]);
+        case DS_MIN_PHASE_IR:
+            CHK(r.fft(true));
+            return r.store(STORE_REAL, n_out, inv_n, d[1]);
+        default: return r.group_delay(nb, delta_f, d[1]);
+        }
+    });
+}
+
+extern "C" int ds_group_delay_phase(ds_ctx* c, const double* x, int64_t n, int n_ch, double delta_f, double* out) {
+    if (!c || !x || !out) return fail(c, DS_ERR_ARG, "ds_group_delay_phase: null argument");
+    const int64_t nb = n / 2 + 1;
+    if (n < 2 || !(delta_f > 0.0)) return fail(c, DS_ERR_ARG, "ds_group_delay_phase: needs two bins and delta_f > 0");
+    Fft64Run r{c, {}, n_ch};
+    CHK(fft64_plan(c, "ds_group_delay_phase", n, n_ch, Fft64Run::phase_bytes(nb, n_ch), ((size_t)n + (size_t)nb) * 8 * (size_t)n_ch, &r.pl));
+    CHK(r.carve_ws(nb));
+    return staged(c, {{8, (size_t)n * n_ch, x, nullptr}, {8, (size_t)nb * n_ch, nullptr, out}}, [&](void* const* d) {
+        CHK(r.load(d[0], false, n));
+        CHK(r.fft(false));
+        return r.group_delay(nb, delta_f, d[1]);
+    });
 }
 
 // ---- RCCL (resolved at run time so the library loads on machines without it) ----

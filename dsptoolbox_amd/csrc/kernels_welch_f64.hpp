@@ -16,11 +16,13 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "fft64_common.hpp"
 #include "kernels_finish.hpp"
 
 namespace w64 {
 
 using dsk::cd;
+using f64c::k_twiddles;
 
 struct FrameArgs {
     const double* sig;  // (n_samples, n_ch) C order
@@ -33,14 +35,6 @@ struct FrameArgs {
     // the planar copy k_planar makes when there are enough channels for the strided reads to hurt
     int64_t s_stride = 0, c_stride = 1;
 };
-
-__global__ __launch_bounds__(256) void k_twiddles(double2* tw, int half) {
-    const int k = blockIdx.x * 256 + threadIdx.x;
-    if (k >= half) return;
-    double s, c;
-    sincospi(-(double)k / (double)half, &s, &c);  // exp(-2 pi i k / W), W = 2 half
-    tw[k] = make_double2(c, s);
-}
 
 // grid = (n_frames, n_ch); dynamic LDS = W * 16 bytes (+ 256 * 8 for the mean)
 // PACKED (W = 16384: 256 KB of double2 would not fit): the real frame travels as the W/2-point complex
@@ -87,18 +81,7 @@ __global__ __launch_bounds__(256) void k_frames(FrameArgs p) {
     __syncthreads();
     // radix-2 decimation in time, natural order out; tw[k] = exp(-2 pi i k / W): the M-point transform of
     // the packed form uses every second entry
-    for (int s = 0; s < lg; ++s) {
-        const int half = 1 << s;
-        for (int i = tid; i < M / 2; i += 256) {
-            const int j = i & (half - 1), a = ((i >> s) << (s + 1)) + j, b = a + half;
-            const double2 w = p.tw[((size_t)j << (lg - 1 - s)) << (PACKED ? 1 : 0)];
-            const double2 u = buf[a], v = buf[b];
-            const double2 t = make_double2(v.x * w.x - v.y * w.y, v.x * w.y + v.y * w.x);
-            buf[a] = make_double2(u.x + t.x, u.y + t.y);
-            buf[b] = make_double2(u.x - t.x, u.y - t.y);
-        }
-        __syncthreads();
-    }
+    f64c::radix2_lds(buf, M, lg, p.tw, PACKED ? 2 : 1, tid);
     double2* out = p.spec + ((size_t)c * p.n_frames + f) * (W / 2 + 1);
     if (!PACKED) {
         for (int k = tid; k <= W / 2; k += 256) out[k] = buf[k];
@@ -216,18 +199,7 @@ __global__ __launch_bounds__(256) void k_frames_cls(LongArgs q) {
     for (int j = 0; j < M / 256; ++j) buf[__brev((unsigned)(tid + 256 * j)) >> (32 - lg)] = v[j];
     __syncthreads();
     const int tstep = W >> lg;  // exp(-2 pi i k / 8192) = tw[k * W / 8192]
-    for (int s = 0; s < lg; ++s) {
-        const int half = 1 << s;
-        for (int i = tid; i < M / 2; i += 256) {
-            const int j = i & (half - 1), a = ((i >> s) << (s + 1)) + j, b = a + half;
-            const double2 w = p.tw[(size_t)(j << (lg - 1 - s)) * tstep];
-            const double2 u = buf[a], t0 = buf[b];
-            const double2 t = make_double2(t0.x * w.x - t0.y * w.y, t0.x * w.y + t0.y * w.x);
-            buf[a] = make_double2(u.x + t.x, u.y + t.y);
-            buf[b] = make_double2(u.x - t.x, u.y - t.y);
-        }
-        __syncthreads();
-    }
+    f64c::radix2_lds(buf, M, lg, p.tw, tstep, tid);
     double2* out = q.zc + ((((size_t)c * p.n_frames + f) << q.lg_rc) + r) * M;
     for (int k = tid; k < M; k += 256) out[k] = buf[k];
 }

@@ -40,3 +40,13 @@ DS_HD inline bool dft_work_too_large(double terms, bool windowed) {
     return terms > (windowed ? kDftWindowedMaxWork : kDftMaxWork);
 }
 DS_HD inline bool csmooth_work_too_large(double terms) { return terms > kCsmoothMaxWork; }
+
+// The complex128 transforms of kernels_fft64.hpp: powers of two up to 2^22 (four-step, both factors at most 2048 -- one
+// workgroup holds up to 8192 points in LDS -- and 64 MB per column and buffer), every other length up to 2^21 (Bluestein's padded
+// length M >= 2 n - 1 is then at most 2^22).  Beyond them the entries answer DS_ERR_UNSUP.
+constexpr int64_t kFft64MaxPow2 = (int64_t)1 << 22;
+constexpr int64_t kFft64MaxAny = (int64_t)1 << 21;
+DS_HD inline bool fft64_len_unsupported(int64_t n) {
+    const bool pow2 = n > 0 && (n & (n - 1)) == 0;
+    return n > (pow2 ? kFft64MaxPow2 : kFft64MaxAny);
+}

@@ -1,7 +1,9 @@
 """compute_transfer_function and spectral_deconvolve
 (API mirror of dsptoolbox/transfer_functions/transfer_functions.py:419-539 and
 :61-184; regularisation window helpers/windows.py:8-76, band detection
-helpers/other.py:9-41), window_frequency_dependent (:1288-1377) and complex_smoothing (:1788-1876)."""
+helpers/other.py:9-41), window_frequency_dependent (:1288-1377) and complex_smoothing (:1788-1876); the real-cepstrum
+minimum-phase family min_phase_ir / minimum_phase / minimum_group_delay and group_delay / excess_group_delay
+(:789-1083) on the float64 any-length transform (ds_min_phase, ds_group_delay_phase) and the direct DFT (ds_dft)."""
 
 import numpy as np
 from scipy.fft import next_fast_len
@@ -13,7 +15,8 @@ from ..standard.enums import SpectrumMethod, Window
 from .enums import SmoothingDomain, TransferFunctionType
 
 __all__ = ["compute_transfer_function", "spectral_deconvolve", "window_frequency_dependent", "complex_smoothing",
-           "TransferFunctionType", "SmoothingDomain"]
+           "min_phase_ir", "group_delay", "minimum_phase", "minimum_group_delay", "excess_group_delay",
+           "min_phase_from_mag", "lin_phase_from_mag", "TransferFunctionType", "SmoothingDomain"]
 
 
 def compute_transfer_function(output: Signal, input: Signal, window_length_samples: int,
@@ -261,3 +264,146 @@ def complex_smoothing(ir: ImpulseResponse, octave_fraction: float, smoothing_dom
     f, sp = ir.get_spectrum()
     window_values = window(3000, True).astype(np.float64, order="C")
     return Spectrum(f, backend.complex_smoothing(sp, f, octave_fraction, smoothing_domain, window_values))
+
+
+_NO_EQUIRIPPLE = ("use_real_cepstrum=False (scipy's equiripple / Hilbert design method, scipy.signal.minimum_phase) is "
+                  "not built on the device")
+
+
+def _pad_trim(td: np.ndarray, desired_length: int) -> np.ndarray:
+    """helpers/other.py:216-259 for (N, C) data, at the end."""
+    n = td.shape[0]
+    if n >= desired_length:
+        return td[:desired_length].copy()
+    return np.concatenate([td, np.zeros((desired_length - n, td.shape[1]), dtype=td.dtype)])
+
+
+def _group_delay_units(gd: np.ndarray, delta_f: float) -> np.ndarray:
+    """The device returns -gradient(unwrap(phase)) / (2 pi delta_f), seconds.  The reference's _group_delay_direct
+    (standard/_standard_backend.py:57-63) reads a frequency step of exactly 1 as "no step given" and returns
+    -gradient(unwrap(phase)) with no 1 / (2 pi): radians per bin.  A one-second signal (fs == N; 6000 samples at 48 kHz
+    with padding_factor 8) meets that branch, and so does this."""
+    return gd * (2.0 * np.pi) if delta_f == 1 else gd
+
+
+def min_phase_ir(sig: ImpulseResponse, use_real_cepstrum: bool = True, padding_factor: int = 8,
+                 alpha: float = 1.0) -> ImpulseResponse:
+    """The same impulse response with minimum phase by the real-cepstrum method: transform, log magnitude, inverse
+    transform, cepstral fold, transform, exp and inverse transform run on the device in float64 at the length
+    next_fast_len(len * padding_factor).  The alpha ** n scaling before and after stays on the host."""
+    assert type(sig) is ImpulseResponse, "This is only valid for an impulse response"
+    assert padding_factor > 1, "Padding factor should be at least 1"
+    assert alpha <= 1.0 and alpha > 0.0, "Alpha must be in the range ]0, 1]"
+    if not use_real_cepstrum:
+        raise NotImplementedError(_NO_EQUIRIPPLE)
+    new_time_data = sig.time_data.copy()
+    if alpha != 1.0:
+        new_time_data *= (alpha ** (np.arange(new_time_data.shape[0])))[:, None]
+    n = new_time_data.shape[0]
+    # the reference keeps all n_fft rows until the end and crops to len(sig) last: the rows past it are never seen
+    new_time_data = backend.min_phase(new_time_data, backend.min_phase_fft_length(n, padding_factor), "ir", n_out=n)
+    if alpha != 1.0:
+        new_time_data *= (alpha ** (-np.arange(new_time_data.shape[0])))[:, None]
+    return sig.copy_with_new_time_data(new_time_data[: len(sig)])
+
+
+def _group_delay_analytic(b: np.ndarray, n_freq: int, fs: int) -> np.ndarray:
+    """_group_delay_filter([b, [1]], n_freq, fs) (classes/filter_helpers.py:167-205) for the columns of b: the
+    quotient of the direct DFTs of n b[n] and b[n] at omega = linspace(0, pi, n_freq) -- for an odd length these are
+    not FFT bins -- evaluated on the device (ds_dft); the quotient, the non-finite -> 0 rule and / fs on the host."""
+    freqs = np.linspace(0, np.pi, n_freq) / np.pi * (fs / 2)
+    ramp = np.arange(b.shape[0], dtype=np.float64)[:, None]
+    sp = backend.dft(np.concatenate([b * ramp, b], axis=1), freqs, fs)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        gd = np.real(sp[:, :b.shape[1]] / sp[:, b.shape[1]:])  # - len(a) + 1 = 0 for a = [1]
+    gd[~np.isfinite(gd)] = 0
+    return gd / fs
+
+
+def group_delay(signal: Signal, analytic_computation: bool = True, smoothing: int = 0,
+                remove_ir_latency: bool = False):
+    """Group delay in seconds (numerical form with a frequency step of exactly 1 Hz: radians per bin, as the reference
+    returns it there), (frequency vector, (gd, channel) matrix).  analytic_computation: the quotient form of
+    https://www.dsprelated.com/freebooks/filters/Phase_Group_Delay.html from two direct DFTs on the device; otherwise
+    the gradient of the unwrapped phase of the spectrum, transform to gradient on the device (ds_group_delay_phase)."""
+    length_time_signal = (next_fast_len(signal.time_data.shape[0] * 8, True) if remove_ir_latency
+                          else signal.time_data.shape[0])
+    td = _pad_trim(signal.time_data, length_time_signal)
+    fs = signal.sampling_rate_hz
+    f = np.fft.rfftfreq(td.shape[0], 1 / fs)
+    if not analytic_computation:
+        if remove_ir_latency:
+            raise NotImplementedError("group_delay(analytic_computation=False, remove_ir_latency=True) needs the "
+                                      "fractional-latency helpers, which are not built")
+        group_delays = _group_delay_units(backend.group_delay_phase(td, f[1] - f[0]), f[1] - f[0])
+    elif remove_ir_latency:
+        group_delays = np.zeros((length_time_signal // 2 + 1, td.shape[1]))
+        for n in range(signal.number_of_channels):
+            b = td[:, n]
+            b = b[max(int(np.argmax(np.abs(b))) - 1, 0):]
+            group_delays[:, n] = _group_delay_analytic(b[:, None], len(f), fs)[:, 0]
+    else:
+        group_delays = _group_delay_analytic(td, len(f), fs)
+    if smoothing != 0:
+        group_delays = backend.fractional_octave_smoothing(group_delays, None, smoothing)
+    return f, group_delays
+
+
+def _min_phase_frequencies(n_fft: int, fs: int) -> np.ndarray:
+    f = np.fft.fftfreq(n_fft, 1 / fs)
+    if n_fft % 2 == 0:
+        f[n_fft // 2] *= -1
+    return f[f >= 0]
+
+
+def minimum_phase(signal: ImpulseResponse, use_real_cepstrum: bool = True, padding_factor: int = 8):
+    """(frequency vector, (phase, channel) matrix) of the minimum-phase equivalent by the real-cepstrum method, on the
+    non-negative bins of the length next_fast_len(len * padding_factor)."""
+    assert type(signal) is ImpulseResponse, "This is only valid for an impulse response"
+    if not use_real_cepstrum:
+        raise NotImplementedError(_NO_EQUIRIPPLE)
+    n_fft = backend.min_phase_fft_length(signal.time_data.shape[0], padding_factor)
+    return _min_phase_frequencies(n_fft, signal.sampling_rate_hz), backend.min_phase(signal.time_data, n_fft, "phase")
+
+
+def minimum_group_delay(signal: ImpulseResponse, smoothing: int = 0, padding_factor: int = 8):
+    """(frequency vector, (gd, channel) matrix in seconds) of the minimum-phase equivalent: its phase is unwrapped
+    and differentiated on the device.  At a frequency step of exactly 1 Hz the reference returns radians per bin; so
+    does this (_group_delay_units)."""
+    assert type(signal) is ImpulseResponse, "This is only valid for an impulse response"
+    n_fft = backend.min_phase_fft_length(signal.time_data.shape[0], padding_factor)
+    f = _min_phase_frequencies(n_fft, signal.sampling_rate_hz)
+    min_gd = _group_delay_units(backend.min_phase(signal.time_data, n_fft, "group_delay", delta_f=f[1] - f[0]), f[1] - f[0])
+    if smoothing != 0:
+        min_gd = backend.fractional_octave_smoothing(min_gd, None, smoothing)
+    return f, min_gd
+
+
+def excess_group_delay(signal: ImpulseResponse, smoothing: int = 0, remove_ir_latency: bool = False,
+                       analytic_computation: bool = False):
+    """(frequency vector, (excess gd, channel) matrix in seconds): the group delay less the minimum group delay (no
+    zero-padding for the minimum-phase equivalent).  Where the two frequency vectors differ the group delay is
+    interpolated linearly onto the minimum group delay's, 0 outside, on the host."""
+    assert type(signal) is ImpulseResponse, "This is only valid for an impulse response"
+    f_min, min_gd = minimum_group_delay(signal, smoothing=0, padding_factor=1)
+    f, gd = group_delay(signal, smoothing=0, analytic_computation=analytic_computation,
+                        remove_ir_latency=remove_ir_latency)
+    if len(f) != len(f_min):
+        from scipy.interpolate import interp1d
+        gd = interp1d(f, gd, kind="linear", copy=False, bounds_error=False, assume_sorted=True, fill_value=(0.0, 0.0),
+                      axis=0)(f_min)
+    ex_gd = gd - min_gd
+    if smoothing != 0:
+        ex_gd = backend.fractional_octave_smoothing(ex_gd, None, smoothing)
+    return f_min, ex_gd
+
+
+def min_phase_from_mag(spectrum: Spectrum, sampling_rate_hz: int, ir_length_samples: int | None = None):
+    raise NotImplementedError("min_phase_from_mag is not built: it needs Spectrum.get_interpolated_spectrum, which "
+                              "this package does not have")
+
+
+def lin_phase_from_mag(spectrum: Spectrum, sampling_rate_hz: int, group_delay_ms: float | None = None,
+                       check_causality: bool = True, minimum_group_delay_factor: float = 1.0):
+    raise NotImplementedError("lin_phase_from_mag is not built: it needs Spectrum.get_interpolated_spectrum, which "
+                              "this package does not have")

@@ -1,6 +1,7 @@
 """transforms: the inverse STFT (dsptoolbox/transforms/transforms.py:444-586, SURVEY.md section 8(f)
 row 1) and the STFT consumers log_mel_spectrogram / mfcc / chroma_stft (:113-203, :335-441, :589-684,
-row 4) on the device.  Same signature, parameter handling and quirks as the reference;
+row 4) on the device, and hilbert / cepstrum / from_complex_cepstrum (:59-110, :763-809) on the float64 any-length
+transform (ds_hilbert, ds_cepstrum, ds_from_cepstrum).  Same signature, parameter handling and quirks as the reference;
 the frame-wise inverse FFTs and the windowed overlap-add with the squared-window envelope
 (standard/_framed_signal_representation.py:70-137) run in the HIP library (ds_istft).  The continuous wavelet
 transform cwt with Wavelet / MorletWavelet (:687-760, transforms/_transforms.py:29-301) lives in _wavelets.py.
@@ -12,11 +13,12 @@ import numpy as np
 from scipy.signal import get_window
 
 from .. import backend
+from ..classes.multibandsignal import MultiBandSignal
 from ..classes.signal import Signal
 from ._wavelets import MorletWavelet, Wavelet, cwt  # noqa: F401
 
 __all__ = ["istft", "mel_filterbank", "log_mel_spectrogram", "mfcc", "chroma_stft", "cwt", "Wavelet", "MorletWavelet",
-           "dft"]
+           "dft", "hilbert", "cepstrum", "from_complex_cepstrum"]
 
 
 def dft(signal: Signal, frequency_vector_hz) -> np.ndarray:
@@ -220,3 +222,28 @@ def chroma_stft(signal: Signal, tuning_a_hz: float = 440, compression: float = 0
         chroma_transformation[i, i::n_notes] = 1
     chroma = np.tensordot(chroma_transformation, pitch_stft, (1, 0))
     return time_s, np.log(1 + compression * chroma), np.log(1 + compression * pitch_stft)
+
+
+def hilbert(signal: Signal | MultiBandSignal) -> Signal | MultiBandSignal:
+    """The analytic signal: the real part in `time_data`, the imaginary part in `time_data_imaginary`.  The transform,
+    the one-sided mask and the inverse transform run on the device in float64 for any length."""
+    if isinstance(signal, Signal):
+        return signal.copy_with_new_time_data(backend.hilbert(signal.time_data))
+    if type(signal) is MultiBandSignal:
+        new_mb = signal.copy()
+        for ind, b in enumerate(new_mb):
+            new_mb.bands[ind] = hilbert(b)
+        return new_mb
+    raise TypeError("Signal does not have a valid type")
+
+
+def cepstrum(signal: Signal, complex: bool = True) -> np.ndarray:
+    """The cepstrum in the quefrency domain, (quefrency, channel) complex128: ifft(log(fft(x))) with the principal
+    logarithm, or the real cepstrum ifft(log|fft(x)|) when `complex` is False."""
+    return backend.cepstrum(signal.time_data, complex)
+
+
+def from_complex_cepstrum(cepstrum: np.ndarray, sampling_rate_hz: int) -> Signal:
+    """The real signal of a complex cepstrum of shape (quefrency, channel)."""
+    ceps = np.asarray(cepstrum)
+    return Signal.from_time_data(backend.from_complex_cepstrum(ceps[:, None] if ceps.ndim == 1 else ceps), sampling_rate_hz)

@@ -477,6 +477,34 @@ int ds_complex_smooth(ds_ctx* ctx, const double* z, int64_t n_bins, int n_ch, co
                       const int32_t* ind_high, const int32_t* window_length, const int32_t* pass,
                       const double* window_x, const double* window_y, int n_window, int domain, double* out);
 
+/* ---- complex128 transforms of any length along axis 0, and what the reference builds on them (csrc/kernels_fft64.hpp):
+ * transforms.hilbert / cepstrum / from_complex_cepstrum (transforms/transforms.py:59-110, 763-809), the real-cepstrum
+ * minimum-phase equivalent (helpers/minimum_phase.py:8-79) and the group delay from the unwrapped phase
+ * (standard/_standard_backend.py:37-63).  Host pointers, float64 / complex128 (interleaved doubles) arrays in the
+ * reference's (rows, channels) C order; everything between the upload and the download stays on the device.
+ * Lengths: powers of two up to 2^22, every other length up to 2^21, DS_ERR_UNSUP beyond; DS_ERR_NOMEM, before anything
+ * is uploaded, when the device has not the memory free that the call needs.
+ * The generic transform: `in` is (n_in, n_ch) float64 or, with in_complex, complex128; it is zero-padded or cropped to
+ *   n_fft rows; out is (n_fft, n_ch) complex128; the inverse divides by n_fft as numpy does.
+ * The analytic signal, out (n, n_ch) complex128.  The cepstrum ifft(log(fft(x))), or with complex_cepstrum = 0
+ *   ifft(log|fft(x)|), out (n, n_ch) complex128; and its way back real(ifft(exp(fft(cepstrum)))), out (n, n_ch) float64.
+ * The minimum-phase equivalent of x zero-padded (or cropped) to n_fft rows, by `output`: its spectrum (n_fft, n_ch)
+ *   complex128; the phase of its bins 0 .. n_fft / 2, float64; its impulse response, the first n_out rows, float64; its
+ *   group delay -gradient(unwrap(phase)) / (2 pi delta_f) on the same n_fft / 2 + 1 bins, float64.
+ * The group delay of x itself from the phase of its n / 2 + 1 non-negative bins, float64.                          */
+#define DS_MIN_PHASE_SPECTRUM 0
+#define DS_MIN_PHASE_PHASE 1
+#define DS_MIN_PHASE_IR 2
+#define DS_MIN_PHASE_GROUP_DELAY 3
+int ds_fft_c128(ds_ctx* ctx, const double* in, int in_complex, int64_t n_in, int n_ch, int64_t n_fft, int inverse,
+                double* out);
+int ds_hilbert(ds_ctx* ctx, const double* x, int64_t n, int n_ch, double* out);
+int ds_cepstrum(ds_ctx* ctx, const double* x, int64_t n, int n_ch, int complex_cepstrum, double* out);
+int ds_from_cepstrum(ds_ctx* ctx, const double* cepstrum, int64_t n, int n_ch, double* out);
+int ds_min_phase(ds_ctx* ctx, const double* x, int64_t n, int n_ch, int64_t n_fft, int output, int64_t n_out,
+                 double delta_f, double* out);
+int ds_group_delay_phase(ds_ctx* ctx, const double* x, int64_t n, int n_ch, double delta_f, double* out);
+
 /* ---- block-streaming FIR classes with device-resident state ------------------------------
  * One process_block of the reference's real-time classes (classes/fir_filter_realtime.py:75-335),
  * executed literally on buffers that stay on the device between calls; per call only the block

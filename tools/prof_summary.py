@@ -31,7 +31,7 @@ for f in find("*counter_collection.csv"):
             a[0] += v
             a[1] += 1
 for k in acc:
-    if not any(t in k for t in ("welch", "k_y", "k_x", "csm", "fir", "stft", "deconv", "big", "blue")):
+    if not any(t in k for t in ("welch", "k_y", "k_x", "csm", "fir", "stft", "deconv", "big", "blue", "fft64")):
         continue
     print(k)
     for c, (s, n) in sorted(acc[k].items()):
