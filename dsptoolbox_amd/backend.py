@@ -1835,3 +1835,122 @@ def group_delay_phase(time_data, delta_f: float):
     ctx.check(ctx.lib.ds_group_delay_phase(ctx.handle, _ptr(a), a.shape[0], a.shape[1], float(delta_f), _ptr(out)),
               "ds_group_delay_phase")
     return out
+
+
+# ---- linear prediction per (frame, channel) pair (csrc/kernels_lpc.hpp) ---------------------------------------------
+# bounds of one call (csrc/size_guards.hpp; DS_ERR_UNSUP above)
+LPC_MAX_WINDOW = 8192   # a pair's frame (Burg: its two error rows) lives in the LDS of one workgroup
+LPC_MAX_ORDER = 255     # order + 1 coefficients, a lane of the workgroup each
+LPC_MAX_PAIRS = (1 << 31) - 1  # one workgroup per (frame, channel) pair
+LPC_MAX_WORK = 1e11     # frames x channels x window x (order + 1)
+LPC_METHODS = ("yule_walker", "burg")  # DS_LPC_* of the header
+
+
+def _lpc_frames(n_samples: int, hop: int) -> int:
+    """ceil(N / hop): _get_framed_signal(..., keep_last_frames=True) of the reference, the rule of _welch_framing."""
+    return -(-int(n_samples) // int(hop))
+
+
+def _lpc_guard(n_frames: int, n_ch: int, window_length: int, order: int) -> None:
+    """ValueError for an order or a window the estimators cannot take, NotImplementedError beyond the kernels' bounds;
+    before anything reaches the device."""
+    L, order, pairs = int(window_length), int(order), int(n_frames) * int(n_ch)
+    if order < 1:
+        raise ValueError("lpc: the order must be at least 1")
+    if order >= L:
+        raise ValueError(f"lpc: the order ({order}) must be below the window length ({L})")
+    if L > LPC_MAX_WINDOW or order > LPC_MAX_ORDER or pairs > LPC_MAX_PAIRS:
+        raise NotImplementedError(f"linear prediction with a window of {L} samples, order {order} and {pairs} (frame, "
+                                  f"channel) pairs is beyond the device kernels' bounds (windows up to {LPC_MAX_WINDOW}, "
+                                  f"orders up to {LPC_MAX_ORDER}, {LPC_MAX_PAIRS} pairs)")
+    work = float(pairs) * L * (order + 1)
+    if work > LPC_MAX_WORK:
+        raise NotImplementedError(f"linear prediction of {work:.3g} lag products is beyond the device kernels' work "
+                                  f"bound ({LPC_MAX_WORK:.0e} = frames x channels x window x (order + 1) per call)")
+
+
+def lpc(time_data, order: int, window, hop: int, method: str = "yule_walker"):
+    """The AR coefficients a (order + 1, frames, channels), a[0] = 1, and the variances (frames, channels) of every
+    windowed frame of (samples, channels) data -- float64 on the host or a `DevicePlanar` -- by Yule-Walker (biased
+    autocorrelation, Levinson-Durbin; var = the final prediction error) or by Burg's method (var = the running
+    denominator `den` of helpers/ar_estimation.py:200, as the reference returns it).  Frame f covers the samples
+    f hop .. f hop + len(window) - 1, zeros past the end; there are ceil(samples / hop) frames.  A frame of zeros gives
+    NaN (Yule-Walker) or [1, 0, ...] and 0 (Burg).  ValueError("Invalid prediction error: Singular Matrix") when the
+    prediction error of any pair is <= 0 after any order, as in the reference."""
+    window = np.ascontiguousarray(window, dtype=np.float64).ravel()
+    L, hop, order, kind = len(window), int(hop), int(order), LPC_METHODS.index(method)
+    if hop < 1:
+        raise ValueError("lpc: the hop size must be at least 1")
+    resident = isinstance(time_data, DevicePlanar)
+    if resident:
+        n, n_ch = time_data.n_samples, time_data.n_ch
+    else:
+        if np.iscomplexobj(time_data):
+            raise ValueError("lpc: the samples must be real")
+        assert np.ndim(time_data) == 2, "the samples are (samples, channels)"
+        n, n_ch = np.shape(time_data)
+    if n < 1 or n_ch < 1:
+        raise ValueError("lpc: empty input")
+    n_frames = _lpc_frames(n, hop)
+    _lpc_guard(n_frames, n_ch, L, order)
+    a = np.empty((order + 1, n_frames, n_ch), dtype=np.float64)
+    var = np.empty((n_frames, n_ch), dtype=np.float64)
+    singular = C.c_int(0)
+    tail = (_ptr(window), L, hop, order, kind, _ptr(a), _ptr(var), C.byref(singular))
+    if resident:
+        ctx = time_data.ctx
+        ctx.check(ctx.lib.ds_lpc_dev(ctx.handle, C.c_void_p(time_data.ptr), n_ch, time_data.ld, n, *tail), "ds_lpc_dev")
+    else:
+        x = np.ascontiguousarray(time_data, dtype=np.float64)
+        ctx = get_context()
+        ctx.check(ctx.lib.ds_lpc(ctx.handle, _ptr(x), n, n_ch, *tail), "ds_lpc")
+    if singular.value:
+        raise ValueError("Invalid prediction error: Singular Matrix")
+    return a, var
+
+
+def levinson_durbin(r):
+    """_levison_durbin_recursion (helpers/ar_estimation.py:6-68) along axis 0 of an (order + 1, ...) autocorrelation, on
+    the device: (a with a[0] = 1 in r's shape, the prediction errors in r.shape[1:]).  ValueError where the reference
+    raises it: a prediction error <= 0 after any order."""
+    r = np.asarray(r, dtype=np.float64)
+    if r.ndim < 1 or r.shape[0] < 2 or r.size == 0:
+        raise ValueError("levinson_durbin: needs the lags 0 .. order, order >= 1, along axis 0")
+    order = r.shape[0] - 1
+    if order > LPC_MAX_ORDER or r.size // r.shape[0] > LPC_MAX_PAIRS:
+        raise NotImplementedError(f"a Levinson-Durbin recursion of order {order} is beyond the device kernel's bound "
+                                  f"({LPC_MAX_ORDER})")
+    cols = np.ascontiguousarray(r.reshape(order + 1, -1))
+    a = np.empty_like(cols)
+    var = np.empty(cols.shape[1], dtype=np.float64)
+    singular = C.c_int(0)
+    ctx = get_context()
+    ctx.check(ctx.lib.ds_levinson(ctx.handle, _ptr(cols), order, cols.shape[1], _ptr(a), _ptr(var), C.byref(singular)),
+              "ds_levinson")
+    if singular.value:
+        raise ValueError("Invalid prediction error: Singular Matrix")
+    return a.reshape(r.shape), var.reshape(r.shape[1:])
+
+
+def lpc_synthesize(a, sources, window, hop: int, n_out: int):
+    """scipy's lfilter([1], a[:, f, c], sources[:, f, c]) from zero state for every frame and channel, then the
+    overlap-add of _reconstruct_framed_signal (standard/_framed_signal_representation.py:70-137): frames times the
+    window, added at hop spacing, over the envelope sum window^2 clipped below at 1e-4, padded or trimmed to n_out
+    samples.  a: (order + 1, frames, channels); sources: (len(window), frames, channels); returns (n_out, channels)."""
+    window = np.ascontiguousarray(window, dtype=np.float64).ravel()
+    a = np.ascontiguousarray(a, dtype=np.float64)
+    sources = np.ascontiguousarray(sources, dtype=np.float64)
+    L, hop, n_out = len(window), int(hop), int(n_out)
+    assert a.ndim == 3 and sources.ndim == 3, "a is (order + 1, frames, channels), sources (window, frames, channels)"
+    order, n_frames, n_ch = a.shape[0] - 1, a.shape[1], a.shape[2]
+    assert sources.shape == (L, n_frames, n_ch), "sources must be (len(window), frames, channels)"
+    if hop < 1 or n_out < 1 or n_frames < 1 or n_ch < 1:
+        raise ValueError("lpc_synthesize: needs hop >= 1, frames, channels and output samples")
+    _lpc_guard(n_frames, n_ch, L, order)
+    if n_out * n_ch > LPC_MAX_PAIRS * 256:
+        raise NotImplementedError("lpc_synthesize: more output samples than one launch covers")
+    y = np.empty((n_out, n_ch), dtype=np.float64)
+    ctx = get_context()
+    ctx.check(ctx.lib.ds_lpc_synth(ctx.handle, _ptr(a), _ptr(sources), _ptr(window), L, n_frames, n_ch, hop, order, n_out,
+                                   _ptr(y)), "ds_lpc_synth")
+    return y

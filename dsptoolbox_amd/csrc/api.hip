@@ -46,6 +46,7 @@
 #include "kernels_smooth.hpp"
 #include "kernels_direct.hpp"
 #include "kernels_fft64.hpp"
+#include "kernels_lpc.hpp"
 #include "size_guards.hpp"
 
 using namespace dsk;
@@ -4302,6 +4303,138 @@ extern "C" int ds_group_delay_phase(ds_ctx* c, const double* x, int64_t n, int n
         CHK(r.load(d[0], false, n));
         CHK(r.fft(false));
         return r.group_delay(nb, delta_f, d[1]);
+    });
+}
+
+// ---- linear prediction (kernels_lpc.hpp), float64 ------------------------------------------------------------
+// Everything ds_lpc and ds_lpc_dev share.
+struct LpcCall {
+    const char* who;
+    int64_t n_samples;
+    int n_ch;
+    const double* window;  // host [L]
+    int L;
+    int64_t hop;
+    int order, method;
+    double *a, *var;       // host (order + 1, n_frames, n_ch), (n_frames, n_ch)
+    int* singular;         // host
+    int64_t n_frames;      // ceil(n_samples / hop): set by lpc_check
+    size_t pairs() const { return (size_t)n_frames * (size_t)n_ch; }
+};
+
+// The device memory a call will hold, as reserve() allocates it (fft64_plan has the same rule): DS_ERR_NOMEM before
+// anything is uploaded.
+static int lpc_mem_check(ds_ctx* c, const std::string& w, size_t io, size_t ws) {
+    HIPCHK(c, hipSetDevice(c->device));
+    auto reserved = [](size_t bytes) { return bytes + bytes / 8 + 4096; };
+    const size_t need = reserved(ws + (1 << 20)) + reserved(io + (1 << 20));
+    size_t free_b = 0, total_b = 0;
+    CHK(ds_mem_info(c, &free_b, &total_b));
+    if (need > free_b + c->ws_bytes + c->io_bytes)
+        return fail(c, DS_ERR_NOMEM, w + ": the call needs more device memory than is free");
+    return DS_OK;
+}
+
+// shape, bounds and work guard, then the pointers; nothing touches the device
+static int lpc_check(ds_ctx* c, LpcCall& q, const void* x) {
+    const std::string w(q.who);
+    if (q.n_samples < 1 || q.n_ch < 1 || q.L < 2 || q.hop < 1 || q.order < 1 || q.order >= q.L)
+        return fail(c, DS_ERR_ARG, w + ": needs samples, channels, hop >= 1 and 1 <= order < window length");
+    if (q.method != DS_LPC_YULE_WALKER && q.method != DS_LPC_BURG) return fail(c, DS_ERR_ARG, w + ": unknown method");
+    q.n_frames = q.n_samples / q.hop + (q.n_samples % q.hop != 0);
+    if (q.n_frames > kLpcMaxPairs / q.n_ch || lpc_shape_unsupported(q.L, q.order, q.n_frames * q.n_ch))
+        return fail(c, DS_ERR_UNSUP, w + ": windows above 8192 samples, orders above 255 or 2^31 (frame, channel) pairs are not built");
+    if (lpc_work_too_large(q.n_frames * q.n_ch, q.L, q.order))
+        return fail(c, DS_ERR_UNSUP, w + ": frames x channels x window x (order + 1) is beyond the work bound");
+    if (!c || !x || !q.window || !q.a || !q.var || !q.singular) return fail(c, DS_ERR_ARG, w + ": null argument");
+    return DS_OK;
+}
+
+template <typename T>
+static int lpc_launch(ds_ctx* c, const LpcCall& q, const T* x, int64_t ss, int64_t cs, const double* dw, double* da,
+                      double* dvar, int* dflag) {
+    using namespace dslpc;
+    CHK(ds_memset(c, dflag, 0, 4));
+    const LpcArgs a{x, ss, cs, q.n_samples, q.n_ch, q.n_frames, dw, q.L, q.hop, q.order, da, dvar, dflag};
+    const dim3 grid((unsigned)q.pairs());
+    if (q.method == DS_LPC_BURG) return launch(c, "lpc_burg", k_lpc_burg<T>, grid, NT, burg_lds_bytes(q.L), a);
+    return launch(c, "lpc_yw", k_lpc_yw<T>, grid, NT, yw_lds_bytes(q.L), a);
+}
+
+extern "C" int ds_lpc(ds_ctx* c, const double* x, int64_t n_samples, int n_ch, const double* window, int window_length,
+                      int64_t hop, int order, int method, double* a, double* var, int* singular) {
+    LpcCall q{"ds_lpc", n_samples, n_ch, window, window_length, hop, order, method, a, var, singular, 0};
+    CHK(lpc_check(c, q, x));
+    const size_t nx = (size_t)n_samples * n_ch, na = (size_t)(order + 1) * q.pairs();
+    CHK(lpc_mem_check(c, q.who, (nx + (size_t)q.L + na + q.pairs()) * 8 + 4, 0));
+    return staged(c, {{8, nx, x, nullptr}, {8, (size_t)q.L, window, nullptr}, {8, na, nullptr, a}, {8, q.pairs(), nullptr, var},
+                      {4, 1, nullptr, singular}}, [&](void* const* d) {
+        return lpc_launch<double>(c, q, (const double*)d[0], n_ch, 1, (const double*)d[1], (double*)d[2], (double*)d[3], (int*)d[4]);
+    });
+}
+
+extern "C" int ds_lpc_dev(ds_ctx* c, const float* x, int n_ch, int64_t ldx, int64_t n_samples, const double* window,
+                          int window_length, int64_t hop, int order, int method, double* a, double* var, int* singular) {
+    LpcCall q{"ds_lpc_dev", n_samples, n_ch, window, window_length, hop, order, method, a, var, singular, 0};
+    CHK(lpc_check(c, q, x));
+    if (ldx < n_samples) return fail(c, DS_ERR_ARG, "ds_lpc_dev: ldx < n_samples");
+    const size_t na = (size_t)(order + 1) * q.pairs();
+    CHK(lpc_mem_check(c, q.who, 0, ((size_t)q.L + na + q.pairs()) * 8 + 4));
+    double *dw, *da, *dvar;
+    int* dflag;
+    CHK(carve(c, &c->ws, &c->ws_bytes, [&](Carver& cv) {
+        dw = cv.take<double>(q.L);
+        da = cv.take<double>(na);
+        dvar = cv.take<double>(q.pairs());
+        dflag = cv.take<int>(1);
+    }));
+    CHK(ds_upload(c, dw, window, (size_t)q.L * 8));
+    CHK(lpc_launch<float>(c, q, x, 1, ldx, dw, da, dvar, dflag));
+    CHK(ds_download(c, a, da, na * 8));
+    CHK(ds_download(c, var, dvar, q.pairs() * 8));
+    return ds_download(c, singular, dflag, 4);
+}
+
+// r: host (order + 1, n_cols); a: host (order + 1, n_cols) with a[0] = 1; var: host (n_cols)
+extern "C" int ds_levinson(ds_ctx* c, const double* r, int order, int64_t n_cols, double* a, double* var, int* singular) {
+    if (order < 1 || n_cols < 1) return fail(c, DS_ERR_ARG, "ds_levinson: needs order >= 1 and a column");
+    if (order > kLpcMaxOrder || n_cols > kLpcMaxPairs)
+        return fail(c, DS_ERR_UNSUP, "ds_levinson: orders above 255 or 2^31 columns are not built");
+    if (!c || !r || !a || !var || !singular) return fail(c, DS_ERR_ARG, "ds_levinson: null argument");
+    const size_t nr = (size_t)(order + 1) * (size_t)n_cols;
+    CHK(lpc_mem_check(c, "ds_levinson", (2 * nr + (size_t)n_cols) * 8 + 4, 0));
+    return staged(c, {{8, nr, r, nullptr}, {8, nr, nullptr, a}, {8, (size_t)n_cols, nullptr, var}, {4, 1, nullptr, singular}},
+                  [&](void* const* d) {
+        CHK(ds_memset(c, d[3], 0, 4));
+        return launch(c, "lpc_levinson", dslpc::k_levinson, dim3((unsigned)n_cols), 64, 0,
+                      dslpc::LevinsonArgs{(const double*)d[0], order, n_cols, (double*)d[1], (double*)d[2], (int*)d[3]});
+    });
+}
+
+// a: host (order + 1, n_frames, n_ch); sources: host (window_length, n_frames, n_ch); y: host (n_out, n_ch)
+extern "C" int ds_lpc_synth(ds_ctx* c, const double* a, const double* sources, const double* window, int window_length,
+                            int64_t n_frames, int n_ch, int64_t hop, int order, int64_t n_out, double* y) {
+    using namespace dslpc;
+    const int L = window_length;
+    if (n_frames < 1 || n_ch < 1 || L < 2 || hop < 1 || order < 1 || order >= L || n_out < 1)
+        return fail(c, DS_ERR_ARG, "ds_lpc_synth: needs frames, channels, output samples, hop >= 1 and 1 <= order < window length");
+    if (n_frames > kLpcMaxPairs / n_ch || lpc_shape_unsupported(L, order, n_frames * n_ch) ||
+        n_out > kLpcMaxPairs * (int64_t)NT / n_ch)
+        return fail(c, DS_ERR_UNSUP, "ds_lpc_synth: windows above 8192 samples, orders above 255 or 2^31 (frame, channel) pairs are not built");
+    if (lpc_work_too_large(n_frames * n_ch, L, order))
+        return fail(c, DS_ERR_UNSUP, "ds_lpc_synth: frames x channels x window x (order + 1) is beyond the work bound");
+    if (!c || !a || !sources || !window || !y) return fail(c, DS_ERR_ARG, "ds_lpc_synth: null argument");
+    const size_t pairs = (size_t)n_frames * n_ch, na = (size_t)(order + 1) * pairs, ns = (size_t)L * pairs;
+    const size_t ny = (size_t)n_out * n_ch;
+    CHK(lpc_mem_check(c, "ds_lpc_synth", (na + ns + (size_t)L + ny) * 8, ns * 8));
+    double* yf;
+    CHK(carve(c, &c->ws, &c->ws_bytes, [&](Carver& cv) { yf = cv.take<double>(ns); }));
+    return staged(c, {{8, na, a, nullptr}, {8, ns, sources, nullptr}, {8, (size_t)L, window, nullptr}, {8, ny, nullptr, y}},
+                  [&](void* const* d) {
+        CHK(launch(c, "lpc_filter", k_lpc_filter, dim3((unsigned)((pairs + FILT_WAVES - 1) / FILT_WAVES)), 64 * FILT_WAVES, 0,
+                   FilterArgs{(const double*)d[0], (const double*)d[1], L, (int64_t)pairs, order, yf}));
+        return launch(c, "lpc_ola", k_lpc_ola, dim3((unsigned)((ny + NT - 1) / NT)), NT, 0,
+                      OlaArgs{yf, (const double*)d[2], L, n_frames, n_ch, hop, n_out, (double*)d[3]});
     });
 }
 

@@ -50,3 +50,25 @@ DS_HD inline bool fft64_len_unsupported(int64_t n) {
     const bool pow2 = n > 0 && (n & (n - 1)) == 0;
     return n > (pow2 ? kFft64MaxPow2 : kFft64MaxAny);
 }
+
+// Linear prediction (kernels_lpc.hpp).  One workgroup holds a pair's frame in LDS, of which a workgroup may declare
+// 160 KiB = 163840 bytes.  Burg keeps the forward and the backward error row, two coefficient rows of 256 doubles and
+// eight partial sums: (2 L + 520) 8 bytes <= 163840 allows L <= 9980.  Yule-Walker keeps the frame, 260 zeros behind it
+// and two rows of 256: (L + 772) 8 bytes, L <= 19708.  Both methods take the same bound, the power of two below the
+// smaller figure: windows up to 8192 samples (Burg then declares 135232 bytes, Yule-Walker 71712).  Orders up to 255:
+// order + 1 coefficients, one per lane of the 256-lane workgroup (Levinson's and Burg's coefficient update, the
+// recursion's four states per lane of a wave).  The grid is one workgroup per (frame, channel) pair, fewer than 2^31.
+// The work of a call is counted as frames x channels x window x (order + 1) products; one call is kept under about a
+// second of device time.  The rate of these kernels has not been measured yet: the bound is
+// provisional, a tenth of kDftMaxWork, whose kernel sustains 1.2e12 float64 multiply-adds per second, and is to be
+// replaced by the measured rate of tools/time_lpc.py rounded down.  Beyond any of these the entries answer DS_ERR_UNSUP.
+constexpr int kLpcMaxWindow = 8192;
+constexpr int kLpcMaxOrder = 255;
+constexpr int64_t kLpcMaxPairs = ((int64_t)1 << 31) - 1;
+constexpr double kLpcMaxWork = 1e11;
+DS_HD inline bool lpc_shape_unsupported(int64_t window, int64_t order, int64_t pairs) {
+    return window > kLpcMaxWindow || order > kLpcMaxOrder || pairs > kLpcMaxPairs;
+}
+DS_HD inline bool lpc_work_too_large(int64_t pairs, int64_t window, int64_t order) {
+    return (double)pairs * (double)window * (double)(order + 1) > kLpcMaxWork;
+}

@@ -1,7 +1,8 @@
 """transforms: the inverse STFT (dsptoolbox/transforms/transforms.py:444-586, SURVEY.md section 8(f)
 row 1) and the STFT consumers log_mel_spectrogram / mfcc / chroma_stft (:113-203, :335-441, :589-684,
 row 4) on the device, and hilbert / cepstrum / from_complex_cepstrum (:59-110, :763-809) on the float64 any-length
-transform (ds_hilbert, ds_cepstrum, ds_from_cepstrum).  Same signature, parameter handling and quirks as the reference;
+transform (ds_hilbert, ds_cepstrum, ds_from_cepstrum), and lpc (:1199-1283) on the linear-prediction kernels (ds_lpc,
+ds_lpc_synth).  Same signature, parameter handling and quirks as the reference;
 the frame-wise inverse FFTs and the windowed overlap-add with the squared-window envelope
 (standard/_framed_signal_representation.py:70-137) run in the HIP library (ds_istft).  The continuous wavelet
 transform cwt with Wavelet / MorletWavelet (:687-760, transforms/_transforms.py:29-301) lives in _wavelets.py.
@@ -15,10 +16,11 @@ from scipy.signal import get_window
 from .. import backend
 from ..classes.multibandsignal import MultiBandSignal
 from ..classes.signal import Signal
+from ..standard.enums import Window
 from ._wavelets import MorletWavelet, Wavelet, cwt  # noqa: F401
 
 __all__ = ["istft", "mel_filterbank", "log_mel_spectrogram", "mfcc", "chroma_stft", "cwt", "Wavelet", "MorletWavelet",
-           "dft", "hilbert", "cepstrum", "from_complex_cepstrum"]
+           "dft", "hilbert", "cepstrum", "from_complex_cepstrum", "lpc"]
 
 
 def dft(signal: Signal, frequency_vector_hz) -> np.ndarray:
@@ -247,3 +249,46 @@ def from_complex_cepstrum(cepstrum: np.ndarray, sampling_rate_hz: int) -> Signal
     """The real signal of a complex cepstrum of shape (quefrency, channel)."""
     ceps = np.asarray(cepstrum)
     return Signal.from_time_data(backend.from_complex_cepstrum(ceps[:, None] if ceps.ndim == 1 else ceps), sampling_rate_hz)
+
+
+def lpc(signal: Signal, order: int, window_length_samples: int, synthesize_encoded_signal: bool = False,
+        use_burg_method: bool = False, hop_size_samples: int | None = None, window_type: Window = Window.Hann):
+    """Linear-predictive coding of every windowed frame: (a, variances) with a of shape (coefficient, frame, channel),
+    a[0] = 1, and variances (frame, channel); or, with `synthesize_encoded_signal`, only the Signal resynthesized from
+    them with white noise as the source (drawn by np.random.normal as the reference draws it, channel outer, frame
+    inner).  Yule-Walker (biased autocorrelation, Levinson-Durbin) or Burg's method; the hop defaults to half the window.
+    Framing, windowing, the estimators, the all-pole filters and the overlap-add run on the device in float64; the
+    samples of a device-resident real signal are read where they lie.
+
+    Kept from the reference: there are ceil(len(signal) / hop) frames, the last ones zero-padded; Burg returns
+    window_length_samples + 1 coefficient rows (zeros after row `order`) and as "variance" the running denominator of
+    its recursion, not divided by the frame length; a frame that is all zeros after windowing gives NaN coefficients and
+    variance with Yule-Walker and [1, 0, ...], 0 with Burg; ValueError("Invalid prediction error: Singular Matrix")
+    when a Yule-Walker prediction error is <= 0."""
+    L = int(window_length_samples)
+    hop = L // 2 if hop_size_samples is None else int(hop_size_samples)
+    order = int(order)
+    if order < 1:
+        raise ValueError("lpc: the order must be at least 1")
+    if order >= L:
+        raise ValueError(f"lpc: the order ({order}) must be below the window length ({L})")
+    if hop < 1:
+        raise ValueError("lpc: the hop size must be at least 1")
+    if signal.is_complex_signal:
+        raise ValueError("lpc: the signal must be real")
+    window = get_window(window_type.to_scipy_format(), L, fftbins=True)
+    n = len(signal)
+    n_frames = backend._lpc_frames(n, hop)
+    backend._lpc_guard(n_frames, signal.number_of_channels, L, order)
+    samples = signal.device_samples if signal.on_device else signal.time_data
+    a, var = backend.lpc(samples, order, window, hop, "burg" if use_burg_method else "yule_walker")
+    if not synthesize_encoded_signal:
+        if use_burg_method:  # the reference's array has window_length + 1 rows (helpers/ar_estimation.py:168-170)
+            a = np.concatenate([a, np.zeros((L - order,) + a.shape[1:])])
+        return a, var
+    sources = np.empty((L, n_frames, a.shape[2]))
+    for channel in range(a.shape[2]):
+        for n_window in range(n_frames):
+            sources[:, n_window, channel] = np.random.normal(0.0, var[n_window, channel] ** 0.5, L)
+    y = backend.lpc_synthesize(a, sources, window, hop, n)
+    return Signal.from_time_data(y, signal.sampling_rate_hz)

@@ -505,6 +505,39 @@ int ds_min_phase(ds_ctx* ctx, const double* x, int64_t n, int n_ch, int64_t n_ff
                  double delta_f, double* out);
 int ds_group_delay_phase(ds_ctx* ctx, const double* x, int64_t n, int n_ch, double delta_f, double* out);
 
+/* ---- linear prediction per (frame, channel) pair (csrc/kernels_lpc.hpp): transforms.lpc of the reference
+ * (transforms/transforms.py:1199-1283) with its estimators (helpers/ar_estimation.py:6-205) and its framing and
+ * overlap-add (standard/_framed_signal_representation.py:9-137), float64 on the device.
+ * Frames: n_frames = ceil(n_samples / hop); frame f covers the samples f hop .. f hop + window_length - 1, zeros past
+ *   the signal's end, times window[window_length] (host, float64).  Framed and windowed inside the kernel.
+ * The estimate: x is host (n_samples, n_ch) float64, or for the _dev entry planar fp32 on the device, channel c at
+ *   x_dev + c ldx, widened on load.  method DS_LPC_YULE_WALKER: the biased autocorrelation r[k] = sum x[n] x[n + k] /
+ *   window_length, k = 0 .. order, then the Levinson-Durbin recursion (ar_estimation.py:28-60); var is the final
+ *   prediction error.  DS_LPC_BURG: Burg's method with eps(float64) added to the denominator (ar_estimation.py:162-205);
+ *   var is its running denominator `den`, divided by nothing, as the reference returns it.  a: host (order + 1, n_frames,
+ *   n_ch) float64 with a[0] = 1 (the reference pads its Burg result with zero rows up to window_length + 1: the caller's
+ *   business); var: host (n_frames, n_ch).  A frame that is all zeros gives a[1 ..] = var = NaN with Yule-Walker and
+ *   a = [1, 0, ...], var = 0 with Burg, as IEEE division gives them in the reference.  *singular is 1 when the
+ *   prediction error of any pair was <= 0 after any order (where the reference raises "Singular Matrix"; Burg never
+ *   sets it), else 0; a and var are written either way.
+ * The recursion alone on a host (order + 1, n_cols) autocorrelation: a (order + 1, n_cols), var (n_cols), *singular.
+ * The synthesis: scipy's lfilter([1], a[:, f, c], sources[:, f, c]) from zero state for every pair -- a and sources are
+ *   host (order + 1, n_frames, n_ch) and (window_length, n_frames, n_ch) -- then the reference's overlap-add: frames
+ *   times the window, added at hop spacing, over the envelope sum window^2 clipped below at 1e-4, padded with zeros or
+ *   trimmed to n_out samples; y is host (n_out, n_ch).
+ * Bounds: 1 <= order < window_length and hop >= 1 (DS_ERR_ARG); window_length <= 8192, order <= 255, fewer than 2^31
+ *   pairs and frames x channels x window_length x (order + 1) within the work bound of csrc/size_guards.hpp
+ *   (DS_ERR_UNSUP); DS_ERR_NOMEM, before anything is uploaded, when the device has not the memory free.           */
+#define DS_LPC_YULE_WALKER 0
+#define DS_LPC_BURG 1
+int ds_lpc(ds_ctx* ctx, const double* x, int64_t n_samples, int n_ch, const double* window, int window_length,
+           int64_t hop, int order, int method, double* a, double* var, int* singular);
+int ds_lpc_dev(ds_ctx* ctx, const float* x_dev, int n_ch, int64_t ldx, int64_t n_samples, const double* window,
+               int window_length, int64_t hop, int order, int method, double* a, double* var, int* singular);
+int ds_levinson(ds_ctx* ctx, const double* r, int order, int64_t n_cols, double* a, double* var, int* singular);
+int ds_lpc_synth(ds_ctx* ctx, const double* a, const double* sources, const double* window, int window_length,
+                 int64_t n_frames, int n_ch, int64_t hop, int order, int64_t n_out, double* y);
+
 /* ---- block-streaming FIR classes with device-resident state ------------------------------
  * One process_block of the reference's real-time classes (classes/fir_filter_realtime.py:75-335),
  * executed literally on buffers that stay on the device between calls; per call only the block
