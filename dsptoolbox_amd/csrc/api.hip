@@ -128,6 +128,10 @@ static int fail(ds_ctx* c, int code, const std::string& msg) {
     if (c) c->err = msg;
     return code;
 }
+// "<who>: <what>": how an entry that shares its checks with a twin names itself in the message
+static int fail(ds_ctx* c, int code, const char* who, const char* what) {
+    return fail(c, code, std::string(who) + ": " + what);
+}
 #define HIPCHK(c, expr)                                                                   \
     do {                                                                                  \
         hipError_t e_ = (expr);                                                           \
@@ -141,6 +145,7 @@ static int fail(ds_ctx* c, int code, const std::string& msg) {
     } while (0)
 
 static bool is_pow2(int64_t n) { return n > 0 && (n & (n - 1)) == 0; }
+static bool fb_mode_ok(int mode) { return mode == DS_FB_PARALLEL || mode == DS_FB_SUMMED || mode == DS_FB_SEQUENTIAL; }
 static const int kMaxFft = 16384, kMinFft = 8;
 static const int64_t kMaxBigFft = (int64_t)1 << 24;  // four-step path (kernels_bigfft.hpp)
 
@@ -397,16 +402,31 @@ extern "C" const char* ds_routes(ds_ctx* c) {
 // ---- internal helpers ------------------------------------------------------
 static int get_twiddles(ds_ctx* c, int n, const float2** out);
 
+// what reserve() allocates for a request of `bytes`: an eighth and 4 KB of room to grow into
+static size_t reserved_bytes(size_t bytes) { return bytes + bytes / 8 + 4096; }
+
 static int reserve(ds_ctx* c, void** buf, size_t* cap, size_t bytes) {
     if (bytes <= *cap) return DS_OK;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (*buf) HIPCHK(c, hipFree(*buf));
     *buf = nullptr;
     *cap = 0;
-    size_t want = bytes + bytes / 8 + 4096;
+    const size_t want = reserved_bytes(bytes);
     hipError_t e = hipMalloc(buf, want);
     if (e != hipSuccess) return fail(c, DS_ERR_NOMEM, "workspace hipMalloc failed");
     *cap = want;
+    return DS_OK;
+}
+
+// DS_ERR_NOMEM before anything is uploaded, for the families that promise it: the call will hold `ws` bytes of c->ws and
+// `io` bytes of c->io as reserve() allocates them (1 MB each for the carves' 256-byte alignment) and `extra` bytes of
+// its own allocations; what the two buffers hold now is given back first.
+static int mem_check(ds_ctx* c, const char* who, size_t ws, size_t io, size_t extra) {
+    const size_t need = reserved_bytes(ws + (1 << 20)) + reserved_bytes(io + (1 << 20)) + extra;
+    size_t free_b = 0, total_b = 0;
+    CHK(ds_mem_info(c, &free_b, &total_b));
+    if (need > free_b + c->ws_bytes + c->io_bytes)
+        return fail(c, DS_ERR_NOMEM, who, "the call needs more device memory than is free");
     return DS_OK;
 }
 
@@ -435,25 +455,39 @@ static int carve(ds_ctx* c, void** buf, size_t* cap, F&& lay) {
     return DS_OK;
 }
 
-// How a host entry runs its _dev twin.  Each of its arrays is one Staged piece: `count` elements of `elem` bytes, copied
-// from `src` before the run and to `dst` after it where these are given (an optional array the caller left out is only
-// carved: it keeps its place).  staged() carves the pieces out of c->io in list order, uploads, calls run(d) with d[i] the
-// device address of piece i, and downloads.  The entry validates before it calls this.
-struct Staged { size_t elem, count; const void* src; void* dst; };
-template <class F>
-static int staged(ds_ctx* c, std::initializer_list<Staged> pieces, F&& run) {
+// One piece of c->ws or c->io: `count` elements of `elem` bytes, copied from the host array `src` once it is carved where
+// one is given.  An optional piece the caller left out has count 0 or no src: it keeps its place and nothing is copied.
+// `dst` is staged()'s: the host array the piece is copied to after the run.
+struct Staged { size_t elem, count; const void* src = nullptr; void* dst = nullptr; };
+static const size_t kMaxStaged = 12;
+
+// The file's one carve-and-upload loop: carves the pieces out of *buf in list order, uploads those with a source and
+// leaves the device address of piece i in d[i] (room for kMaxStaged).  The copies are synchronous: a source may be a
+// local of the caller.
+static int stage(ds_ctx* c, void** buf, size_t* cap, std::initializer_list<Staged> pieces, void** d) {
     const Staged* p = pieces.begin();
     const size_t n = pieces.size();
-    void* d[8];
-    if (n > 8) return fail(c, DS_ERR_ARG, "staged: more than 8 pieces");
-    CHK(carve(c, &c->io, &c->io_bytes, [&](Carver& cv) {
+    if (n > kMaxStaged) return fail(c, DS_ERR_ARG, "stage: more than 12 pieces");
+    CHK(carve(c, buf, cap, [&](Carver& cv) {
         for (size_t i = 0; i < n; ++i) d[i] = cv.take<char>(p[i].elem * p[i].count);
     }));
     for (size_t i = 0; i < n; ++i)
-        if (p[i].src) CHK(ds_upload(c, d[i], p[i].src, p[i].elem * p[i].count));
+        if (p[i].src && p[i].count) CHK(ds_upload(c, d[i], p[i].src, p[i].elem * p[i].count));
+    return DS_OK;
+}
+
+// How a host entry runs its device code (its _dev twin, or a runner they share).  The rule every entry follows: the
+// caller's input and output arrays are pieces of c->io, staged here; tables and intermediates are pieces of c->ws,
+// staged by stage() or carved by the device code itself -- so a host entry can call any _dev entry without the two
+// overwriting each other.  staged() stages the pieces in c->io, calls run(d) with d[i] the device address of piece i and
+// downloads the pieces that have a dst.  The entry validates before it calls this.
+template <class F>
+static int staged(ds_ctx* c, std::initializer_list<Staged> pieces, F&& run) {
+    void* d[kMaxStaged];
+    CHK(stage(c, &c->io, &c->io_bytes, pieces, d));
     CHK(run(d));
-    for (size_t i = 0; i < n; ++i)
-        if (p[i].dst) CHK(ds_download(c, p[i].dst, d[i], p[i].elem * p[i].count));
+    for (const Staged& p : pieces)
+        if (p.dst) CHK(ds_download(c, p.dst, d[&p - pieces.begin()], p.elem * p.count));
     return DS_OK;
 }
 
@@ -732,7 +766,7 @@ struct XformCall {
 };
 static int xform_check(ds_ctx* c, const XformCall& q, bool deconv) {
     const std::string w(q.who), what = w + " n_fft";
-    if (!c || !q.x || (deconv ? !q.r || !q.ir : !q.spec)) return fail(c, DS_ERR_ARG, w + ": null argument");
+    if (!c || !q.x || (deconv ? !q.r || !q.ir : !q.spec)) return fail(c, DS_ERR_ARG, q.who, "null argument");
     if (q.n_items <= 0 || q.n_ch <= 0 || q.n_samples <= 0 || q.ld < q.n_samples || q.n_samples > q.n_fft ||
         (deconv && (q.n_out <= 0 || q.n_out > q.n_fft || q.ld_out < q.n_out)))
         return fail(c, DS_ERR_ARG, w + (deconv ? ": bad shape" : ": bad shape (n_samples must be <= n_fft)"));
@@ -884,11 +918,10 @@ struct StftCall {
     const float* window; int detrend; float scale, edge_scale; int power; float2* out;
 };
 static int stft_check(ds_ctx* c, const StftCall& s) {
-    const std::string w(s.who);
-    if (!c || !s.x || !s.out || !s.window) return fail(c, DS_ERR_ARG, w + ": null argument");
+    if (!c || !s.x || !s.out || !s.window) return fail(c, DS_ERR_ARG, s.who, "null argument");
     if (s.n_ch <= 0 || s.n_samples <= 0 || s.W <= 0 || s.hop <= 0 || s.n_frames <= 0 || s.ld < s.n_samples)
-        return fail(c, DS_ERR_ARG, w + ": bad shape");
-    if (s.nfft < 2) return fail(c, DS_ERR_ARG, w + ": fft length must be >= 2");
+        return fail(c, DS_ERR_ARG, s.who, "bad shape");
+    if (s.nfft < 2) return fail(c, DS_ERR_ARG, s.who, "fft length must be >= 2");
     return DS_OK;
 }
 
@@ -1127,12 +1160,11 @@ struct IstftCall {
     float scale; int64_t total_length; float* out; int64_t ld_out;
 };
 static int istft_check(ds_ctx* c, const IstftCall& q) {
-    const std::string w(q.who);
-    if (!c || !q.stft || !q.window || !q.out) return fail(c, DS_ERR_ARG, w + ": null argument");
+    if (!c || !q.stft || !q.window || !q.out) return fail(c, DS_ERR_ARG, q.who, "null argument");
     if (q.n_bins <= 0 || q.n_frames <= 0 || q.n_ch <= 0 || q.W <= 0 || q.step <= 0 || q.step > q.W || q.frame_offset < 0 ||
         q.n_frames_total < q.n_frames + q.frame_offset || q.total_length <= 0 || q.ld_out < q.total_length)
-        return fail(c, DS_ERR_ARG, w + ": bad shape");
-    if (q.W > q.nfft) return fail(c, DS_ERR_ARG, w + ": window longer than the FFT length");
+        return fail(c, DS_ERR_ARG, q.who, "bad shape");
+    if (q.W > q.nfft) return fail(c, DS_ERR_ARG, q.who, "window longer than the FFT length");
     return DS_OK;
 }
 // overlap-add of the frames [c][f][W] into the output rows; four samples per thread (vec4) where every row and frame
@@ -1880,18 +1912,17 @@ static int welch_wave_run(ds_ctx* c, const WelchCall& q) {
 
 // What every Welch entry checks of its call, once, before anything is staged or launched
 static int welch_check(ds_ctx* c, const WelchCall& q) {
-    const std::string w(q.who);
-    if (!c || !q.x || !q.window) return fail(c, DS_ERR_ARG, w + ": null argument");
-    if ((q.kind != PSD && !q.out_c) || (q.kind != CSD && !q.out_r)) return fail(c, DS_ERR_ARG, w + ": null output");
+    if (!c || !q.x || !q.window) return fail(c, DS_ERR_ARG, q.who, "null argument");
+    if ((q.kind != PSD && !q.out_c) || (q.kind != CSD && !q.out_r)) return fail(c, DS_ERR_ARG, q.who, "null output");
     if (q.average != DS_AVG_MEAN && q.average != DS_AVG_MEDIAN)
-        return fail(c, DS_ERR_ARG, w + ": average must be mean (0) or median (1)");
-    if (!q.auto_only() && !q.y) return fail(c, DS_ERR_ARG, w + ": null output-signal pointer");
+        return fail(c, DS_ERR_ARG, q.who, "average must be mean (0) or median (1)");
+    if (!q.auto_only() && !q.y) return fail(c, DS_ERR_ARG, q.who, "null output-signal pointer");
     if (q.n_cx <= 0 || q.n_samples <= 0 || q.hop <= 0 || q.hop > q.W || q.n_frames <= 0 || q.ldx < q.n_samples)
-        return fail(c, DS_ERR_ARG, w + ": bad shape");
+        return fail(c, DS_ERR_ARG, q.who, "bad shape");
     if (!q.auto_only() && (q.n_cy <= 0 || q.ldy < q.n_samples || !(q.n_cx == 1 || q.n_cx == q.n_cy)))
-        return fail(c, DS_ERR_ARG, w + ": input must have 1 channel or as many as the output");
+        return fail(c, DS_ERR_ARG, q.who, "input must have 1 channel or as many as the output");
     if (q.kind == TF && (q.mode < DS_TF_H1 || q.mode > DS_TF_H3))
-        return fail(c, DS_ERR_ARG, w + ": unsupported transfer function type");
+        return fail(c, DS_ERR_ARG, q.who, "unsupported transfer function type");
     return DS_OK;
 }
 
@@ -1962,18 +1993,17 @@ struct X64Call {
 };
 // What all three refuse.  n_spectra_x / n_spectra_y: the channels of x and y whose frame spectra the call holds: 2 GiB at most
 static int x64_check(ds_ctx* c, const X64Call& q, int n_spectra_x, int n_spectra_y) {
-    const std::string w(q.who);
-    if (!c || !q.x || !q.window || !q.out) return fail(c, DS_ERR_ARG, w + ": null argument");
+    if (!c || !q.x || !q.window || !q.out) return fail(c, DS_ERR_ARG, q.who, "null argument");
     if (q.average != DS_AVG_MEAN && q.average != DS_AVG_MEDIAN)
-        return fail(c, DS_ERR_ARG, w + ": average must be mean (0) or median (1)");
+        return fail(c, DS_ERR_ARG, q.who, "average must be mean (0) or median (1)");
     if (q.median() && q.n_frames > 4096)
-        return fail(c, DS_ERR_UNSUP, w + ": median averaging over more than 4096 frames (use the fp32 entry point)");
+        return fail(c, DS_ERR_UNSUP, q.who, "median averaging over more than 4096 frames (use the fp32 entry point)");
     if (n_spectra_x <= 0 || n_spectra_y < 0 || q.n_samples <= 0 || q.hop <= 0 || q.hop > q.W || q.n_frames <= 0)
-        return fail(c, DS_ERR_ARG, w + ": bad shape");
+        return fail(c, DS_ERR_ARG, q.who, "bad shape");
     if (!is_pow2(q.W) || q.W < 8 || q.W > kMaxX64Window)
-        return fail(c, DS_ERR_UNSUP, w + ": window length must be a power of two in [8, 262144]");
+        return fail(c, DS_ERR_UNSUP, q.who, "window length must be a power of two in [8, 262144]");
     if (((size_t)n_spectra_x + (size_t)n_spectra_y) * q.n_frames * q.nb() * sizeof(double2) > ((size_t)2 << 30))
-        return fail(c, DS_ERR_UNSUP, w + ": problem too large for the float64 route (use the fp32 entry point)");
+        return fail(c, DS_ERR_UNSUP, q.who, "problem too large for the float64 route (use the fp32 entry point)");
     return DS_OK;
 }
 // the finish of the mean over the frames, or of the median with the reference's bias correction
@@ -2181,19 +2211,19 @@ struct CsmCall {
 };
 static int csm_check(ds_ctx* c, const CsmCall& q) {
     const std::string w(q.who);
-    if (!c || !q.x || !q.window || !q.csm) return fail(c, DS_ERR_ARG, w + ": null argument");
+    if (!c || !q.x || !q.window || !q.csm) return fail(c, DS_ERR_ARG, q.who, "null argument");
     if (q.n_ch < 1 || q.n_samples <= 0 || q.hop <= 0 || q.hop > q.W || q.n_frames <= 0 || q.ld < q.n_samples)
-        return fail(c, DS_ERR_ARG, w + ": bad shape");
+        return fail(c, DS_ERR_ARG, q.who, "bad shape");
     if (q.average != DS_AVG_MEAN && q.average != DS_AVG_MEDIAN)
-        return fail(c, DS_ERR_ARG, w + ": average must be mean (0) or median (1)");
+        return fail(c, DS_ERR_ARG, q.who, "average must be mean (0) or median (1)");
     if (!q.big()) CHK(check_fft_len(c, q.W, (w + " window length").c_str()));
     if (q.bin_start < 0 || q.bin_count <= 0 || q.bin_start + q.bin_count > q.W / 2 + 1)
-        return fail(c, DS_ERR_ARG, w + ": bad bin range");
+        return fail(c, DS_ERR_ARG, q.who, "bad bin range");
     if (q.average == DS_AVG_MEDIAN && !q.all_bins())
-        return fail(c, DS_ERR_UNSUP, w + ": a bin range with median averaging is not built yet");
+        return fail(c, DS_ERR_UNSUP, q.who, "a bin range with median averaging is not built yet");
     size_t lds = 0;
     if (q.average == DS_AVG_MEDIAN && !median_bins_per_block(2, q.n_frames, &lds))
-        return fail(c, DS_ERR_UNSUP, w + ": median averaging over more than 19 199 frames is not built yet");
+        return fail(c, DS_ERR_UNSUP, q.who, "median averaging over more than 19 199 frames is not built yet");
     return DS_OK;
 }
 
@@ -2419,12 +2449,12 @@ extern "C" int ds_das_map(ds_ctx* c, const ds_c32* csm, const ds_c32* h, int n_b
 // device's), a bad shape, a matrix or a grid beyond the kernels
 static int bf_check(ds_ctx* c, const char* who, const void* in, const void* in2, const void* out, int n_bins, int n_ch,
                     int n_grid) {
-    if (!c || !in || !in2 || !out) return fail(c, DS_ERR_ARG, std::string(who) + ": null argument");
-    if (n_bins <= 0 || n_ch <= 0 || n_grid <= 0) return fail(c, DS_ERR_ARG, std::string(who) + ": bad shape");
+    if (!c || !in || !in2 || !out) return fail(c, DS_ERR_ARG, who, "null argument");
+    if (n_bins <= 0 || n_ch <= 0 || n_grid <= 0) return fail(c, DS_ERR_ARG, who, "bad shape");
     if (n_ch > bf::MAX_CH)
-        return fail(c, DS_ERR_UNSUP, std::string(who) + ": more than 64 microphones is not built (one bin's C x C "
-                                     "complex128 matrix is held in LDS; C <= 64)");
-    if (n_bins > 65535) return fail(c, DS_ERR_UNSUP, std::string(who) + ": more than 65535 bins per call is not built yet");
+        return fail(c, DS_ERR_UNSUP, who, "more than 64 microphones is not built (one bin's C x C "
+                                          "complex128 matrix is held in LDS; C <= 64)");
+    if (n_bins > 65535) return fail(c, DS_ERR_UNSUP, who, "more than 65535 bins per call is not built yet");
     return DS_OK;
 }
 
@@ -2505,12 +2535,10 @@ struct FirCall {
     const float* x; int n_ch; int64_t ldx, n_samples; const float* taps; int n_filt, n_taps, mode; float* y; int64_t ld_y;
 };
 static int fir_check(ds_ctx* c, const FirCall& f) {
-    const std::string w(f.who);
-    if (!c || !f.x || !f.taps || !f.y) return fail(c, DS_ERR_ARG, w + ": null argument");
+    if (!c || !f.x || !f.taps || !f.y) return fail(c, DS_ERR_ARG, f.who, "null argument");
     if (f.n_ch <= 0 || f.n_samples <= 0 || f.n_filt <= 0 || f.n_taps <= 0 || f.ldx < f.n_samples || f.ld_y < f.n_samples)
-        return fail(c, DS_ERR_ARG, w + ": bad shape");
-    if (f.mode != DS_FB_PARALLEL && f.mode != DS_FB_SUMMED && f.mode != DS_FB_SEQUENTIAL)
-        return fail(c, DS_ERR_ARG, w + ": invalid filter bank apply mode");
+        return fail(c, DS_ERR_ARG, f.who, "bad shape");
+    if (!fb_mode_ok(f.mode)) return fail(c, DS_ERR_ARG, f.who, "invalid filter bank apply mode");
     return DS_OK;
 }
 
@@ -3252,21 +3280,11 @@ extern "C" int ds_fir_freqz(ds_ctx* c, const double* taps, int n_filt, int n_tap
     if (!c || !taps || !freqs_hz || !out) return fail(c, DS_ERR_ARG, "ds_fir_freqz: null argument");
     if (n_filt <= 0 || n_taps <= 0 || n_freq <= 0 || !(fs_hz > 0.0)) return fail(c, DS_ERR_ARG, "ds_fir_freqz: bad shape");
     HIPCHK(c, hipSetDevice(c->device));
-    const size_t bt = (size_t)n_filt * n_taps * 16, bf = (size_t)n_freq * 8, bo = (size_t)n_filt * n_freq * 16;
-    double2 *dt, *dout;
-    double* df;
-    CHK(carve(c, &c->io, &c->io_bytes, [&](Carver& cv) {
-        dt = cv.take<double2>((size_t)n_filt * n_taps);
-        df = cv.take<double>(n_freq);
-        dout = cv.take<double2>((size_t)n_filt * n_freq);
-    }));
-    HIPCHK(c, hipMemcpyAsync(dt, taps, bt, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(df, freqs_hz, bf, hipMemcpyHostToDevice, c->stream));
-    freqz::Args a{dt, n_filt, n_taps, df, n_freq, fs_hz, dout};
-    CHK(launch(c, "fir_freqz", freqz::k_freqz, dim3((n_freq + 255) / 256, n_filt), 256, 0, a));
-    HIPCHK(c, hipMemcpyAsync(out, dout, bo, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return DS_OK;
+    const size_t nt = (size_t)n_filt * n_taps, no = (size_t)n_filt * n_freq;
+    return staged(c, {{16, nt, taps}, {8, (size_t)n_freq, freqs_hz}, {16, no, nullptr, out}}, [&](void* const* d) {
+        freqz::Args a{(const double2*)d[0], n_filt, n_taps, (const double*)d[1], n_freq, fs_hz, (double2*)d[2]};
+        return launch(c, "fir_freqz", freqz::k_freqz, dim3((n_freq + 255) / 256, n_filt), 256, 0, a);
+    });
 }
 
 // ---- IIR filtering: cascades of second-order sections (kernels_iir.hpp) --------------------------------
@@ -3329,41 +3347,50 @@ static bool iir_tables(const double* sos, int n_filt, int n_sec, std::vector<dou
     return true;
 }
 
-// the three passes over device buffers of either sample type; y element (f, c, n) at y[f syf + c syc + n syn]
+// Everything ds_iir_sos and ds_iir_sos_dev share.  ldx, ld_y: the _dev entry's row strides (the host entry's rows are dense).
+struct IirCall {
+    const char* who;
+    int n_ch;
+    int64_t n_samples, ldx, ld_y;
+    const double* sos;  // host [n_filt][n_sec][6]
+    int n_filt, n_sec, mode;
+};
+
+static int iir_check(ds_ctx* c, const IirCall& q, const void* x, const void* y) {
+    if (!c || !x || !y || !q.sos) return fail(c, DS_ERR_ARG, q.who, "null argument");
+    if (q.n_ch <= 0 || q.n_samples <= 0 || q.n_filt <= 0 || q.n_sec <= 0 || q.ldx < q.n_samples || q.ld_y < q.n_samples)
+        return fail(c, DS_ERR_ARG, q.who, "bad shape");
+    return DS_OK;
+}
+
+// the three passes over device buffers of either sample type; y element (f, c, n) at y[f syf + c syc + n syn]; zi, zf:
+// device arrays or nullptr
 template <typename T>
-static int iir_run(ds_ctx* c, const char* who, const T* x, int64_t sxc, int64_t sxn, int64_t n, int n_ch,
-                   const double* sos, int n_filt, int n_sec, const double* zi, int mode, T* y, int64_t syf,
+static int iir_run(ds_ctx* c, const IirCall& q, const T* x, int64_t sxc, int64_t sxn, const double* zi, T* y, int64_t syf,
                    int64_t syc, int64_t syn, double* zf) {
-    if (mode != DS_FB_PARALLEL && mode != DS_FB_SUMMED && mode != DS_FB_SEQUENTIAL)
-        return fail(c, DS_ERR_ARG, std::string(who) + ": invalid filter bank apply mode");
-    if (mode == DS_FB_SEQUENTIAL) {  // one cascade of all sections: sos and zi keep their memory layout
-        n_sec *= n_filt;
-        n_filt = 1;
-    }
+    if (!fb_mode_ok(q.mode)) return fail(c, DS_ERR_ARG, q.who, "invalid filter bank apply mode");
+    // sequential: one cascade of all sections, sos and zi keep their memory layout
+    const bool seq = q.mode == DS_FB_SEQUENTIAL;
+    const int n_filt = seq ? 1 : q.n_filt, n_sec = seq ? q.n_sec * q.n_filt : q.n_sec, n_ch = q.n_ch;
     if (n_sec > iir::MAX_SEC)
-        return fail(c, DS_ERR_UNSUP, std::string(who) + ": more than 32 second-order sections in one cascade is not "
-                                     "built (the carry's state vector is one value per lane of a wave)");
+        return fail(c, DS_ERR_UNSUP, q.who, "more than 32 second-order sections in one cascade is not "
+                                            "built (the carry's state vector is one value per lane of a wave)");
     if ((int64_t)n_filt * n_ch > 65535)
-        return fail(c, DS_ERR_UNSUP, std::string(who) + ": more than 65535 (filter, channel) streams is not built yet");
-    const int64_t n_groups = (n + iir::G - 1) / iir::G;
-    if (n_groups > INT32_MAX) return fail(c, DS_ERR_UNSUP, std::string(who) + ": signal too long");
+        return fail(c, DS_ERR_UNSUP, q.who, "more than 65535 (filter, channel) streams is not built yet");
+    const int64_t n = q.n_samples, n_groups = (n + iir::G - 1) / iir::G;
+    if (n_groups > INT32_MAX) return fail(c, DS_ERR_UNSUP, q.who, "signal too long");
     std::vector<double> coef, phi, phig;
-    if (!iir_tables(sos, n_filt, n_sec, coef, phi, phig))
-        return fail(c, DS_ERR_ARG, std::string(who) + ": sections must be finite with a0 != 0");
+    if (!iir_tables(q.sos, n_filt, n_sec, coef, phi, phig))
+        return fail(c, DS_ERR_ARG, q.who, "sections must be finite with a0 != 0");
     const int d = 2 * n_sec;
     const size_t n_streams = (size_t)n_filt * n_ch;
-    double *dcoef, *dphi, *dphig, *gst;
-    CHK(carve(c, &c->ws, &c->ws_bytes, [&](Carver& cv) {
-        dcoef = cv.take<double>(coef.size());
-        dphi = cv.take<double>(phi.size());
-        dphig = cv.take<double>(phig.size());
-        gst = cv.take<double>(n_streams * n_groups * d);
-    }));
-    CHK(ds_upload(c, dcoef, coef.data(), coef.size() * 8));
-    CHK(ds_upload(c, dphi, phi.data(), phi.size() * 8));
-    CHK(ds_upload(c, dphig, phig.data(), phig.size() * 8));
-    iir::Args<T> a{x, sxc, sxn, y, mode == DS_FB_PARALLEL ? syf : 0, syc, syn, n, n_ch, n_filt, n_sec,
-                   mode == DS_FB_SUMMED ? 1 : 0, n_groups, dcoef, dphi, dphig, gst, zi, zf};
+    void* t[kMaxStaged];
+    CHK(stage(c, &c->ws, &c->ws_bytes, {{8, coef.size(), coef.data()}, {8, phi.size(), phi.data()}, {8, phig.size(), phig.data()},
+                                        {8, n_streams * n_groups * d}}, t));
+    const double *dcoef = (const double*)t[0], *dphi = (const double*)t[1], *dphig = (const double*)t[2];
+    double* gst = (double*)t[3];
+    iir::Args<T> a{x, sxc, sxn, y, q.mode == DS_FB_PARALLEL ? syf : 0, syc, syn, n, n_ch, n_filt, n_sec,
+                   q.mode == DS_FB_SUMMED ? 1 : 0, n_groups, dcoef, dphi, dphig, gst, zi, zf};
     if (n_groups > 1)
         CHK(launch(c, "iir_group", iir::k_iir_group<T>, dim3((unsigned)(n_groups - 1), (unsigned)n_streams), iir::B,
                    iir::lds_bytes(n_sec, false), a));
@@ -3373,104 +3400,91 @@ static int iir_run(ds_ctx* c, const char* who, const T* x, int64_t sxc, int64_t 
                   iir::lds_bytes(n_sec, true), a);
 }
 
-static int iir_shape_ok(ds_ctx* c, const char* who, int n_ch, int64_t n_samples, const double* sos, int n_filt,
-                        int n_sec) {
-    if (!sos) return fail(c, DS_ERR_ARG, std::string(who) + ": null argument");
-    if (n_ch <= 0 || n_samples <= 0 || n_filt <= 0 || n_sec <= 0)
-        return fail(c, DS_ERR_ARG, std::string(who) + ": bad shape");
-    return DS_OK;
-}
-
 extern "C" int ds_iir_sos_dev(ds_ctx* c, const float* x, int n_ch, int64_t ldx, int64_t n_samples, const double* sos,
                               int n_filt, int n_sec, const double* zi, int mode, float* y, int64_t ld_y, double* zf) {
-    if (!c || !x || !y) return fail(c, DS_ERR_ARG, "ds_iir_sos_dev: null argument");
-    CHK(iir_shape_ok(c, "ds_iir_sos_dev", n_ch, n_samples, sos, n_filt, n_sec));
-    if (ldx < n_samples || ld_y < n_samples) return fail(c, DS_ERR_ARG, "ds_iir_sos_dev: bad shape");
+    const IirCall q{"ds_iir_sos_dev", n_ch, n_samples, ldx, ld_y, sos, n_filt, n_sec, mode};
+    CHK(iir_check(c, q, x, y));
     HIPCHK(c, hipSetDevice(c->device));
-    return iir_run<float>(c, "ds_iir_sos_dev", x, ldx, 1, n_samples, n_ch, sos, n_filt, n_sec, zi, mode, y,
-                          (int64_t)n_ch * ld_y, ld_y, 1, zf);
+    return iir_run<float>(c, q, x, ldx, 1, zi, y, (int64_t)n_ch * ld_y, ld_y, 1, zf);
 }
 
 // host pointers in the reference's layouts: x (n_samples, n_ch), y (n_filt or 1, n_samples, n_ch), float64; the
 // samples cross the link as they are and the kernels read them with the channel stride
 extern "C" int ds_iir_sos(ds_ctx* c, const double* x, int n_ch, int64_t n_samples, const double* sos, int n_filt,
                           int n_sec, const double* zi, int mode, double* y, double* zf) {
-    if (!c || !x || !y) return fail(c, DS_ERR_ARG, "ds_iir_sos: null argument");
-    CHK(iir_shape_ok(c, "ds_iir_sos", n_ch, n_samples, sos, n_filt, n_sec));
-    if (mode != DS_FB_PARALLEL && mode != DS_FB_SUMMED && mode != DS_FB_SEQUENTIAL)
-        return fail(c, DS_ERR_ARG, "ds_iir_sos: invalid filter bank apply mode");
+    const IirCall q{"ds_iir_sos", n_ch, n_samples, n_samples, n_samples, sos, n_filt, n_sec, mode};
+    CHK(iir_check(c, q, x, y));
+    if (!fb_mode_ok(mode)) return fail(c, DS_ERR_ARG, q.who, "invalid filter bank apply mode");  // it sizes y
     HIPCHK(c, hipSetDevice(c->device));
     const int n_out = mode == DS_FB_PARALLEL ? n_filt : 1;
     const size_t nx = (size_t)n_ch * n_samples, ny = nx * n_out, nz = (size_t)n_filt * n_sec * 2 * n_ch;
-    return staged(c, {{8, nx, x, nullptr}, {8, ny, nullptr, y}, {8, nz, zi, nullptr}, {8, nz, nullptr, zf}}, [&](void* const* d) {
-        return iir_run<double>(c, "ds_iir_sos", (const double*)d[0], 1, n_ch, n_samples, n_ch, sos, n_filt, n_sec,
-                               zi ? (const double*)d[2] : nullptr, mode, (double*)d[1], (int64_t)nx, 1, n_ch,
-                               zf ? (double*)d[3] : nullptr);
+    return staged(c, {{8, nx, x}, {8, ny, nullptr, y}, {8, nz, zi}, {8, nz, nullptr, zf}}, [&](void* const* d) {
+        return iir_run<double>(c, q, (const double*)d[0], 1, n_ch, zi ? (const double*)d[2] : nullptr, (double*)d[1],
+                               (int64_t)nx, 1, n_ch, zf ? (double*)d[3] : nullptr);
     });
 }
 
 // ---- weighted sums of fractionally delayed channels (kernels_delay.hpp) -----------------------------------------
-// the taps of every term, then the sum; x element (c, n) at x[c sxc + n sxn], y element (g, t) at y[g syg + t syt]
-template <typename T>
-static int delay_run(ds_ctx* c, const char* who, const T* x, int64_t sxc, int64_t sxn, int n_src,
-                     const int64_t* src_len, int n_rows, int n_terms, const int* src, const int64_t* shift,
-                     const double* frac, const double* weight, int order, double beta, int64_t out_len, T* y,
-                     int64_t syg, int64_t syt, double* peak) {
-    const int ntp = (order + 1 + dly::R - 1) / dly::R * dly::R;
-    const size_t n_t = (size_t)n_rows * n_terms;
-    if ((n_rows + dly::WAVES - 1) / dly::WAVES > 65535)
-        return fail(c, DS_ERR_UNSUP, std::string(who) + ": more than 262140 output rows in one call is not built");
-    if ((out_len + dly::TT - 1) / dly::TT > INT32_MAX || (n_t * ntp + 255) / 256 > (size_t)INT32_MAX)
-        return fail(c, DS_ERR_UNSUP, std::string(who) + ": output too long or too many terms");
-    for (size_t e = 0; e < n_t; ++e)
-        if (src[e] < 0 || src[e] >= n_src || !std::isfinite(weight[e]) || !(frac[e] < 1.0))
-            return fail(c, DS_ERR_ARG, std::string(who) + ": a term's source, weight or fraction is out of range");
-    int64_t *dlen, *dshift;
-    int* dsrc;
-    double *dfrac, *dw, *dtaps;
-    unsigned long long* dpk;
-    CHK(carve(c, &c->ws, &c->ws_bytes, [&](Carver& cv) {
-        dlen = cv.take<int64_t>(n_src);
-        dsrc = cv.take<int>(n_t);
-        dshift = cv.take<int64_t>(n_t);
-        dfrac = cv.take<double>(n_t);
-        dw = cv.take<double>(n_t);
-        dtaps = cv.take<double>(n_t * ntp);
-        dpk = cv.take<unsigned long long>(peak ? n_rows : 0);
-    }));
-    CHK(ds_upload(c, dlen, src_len, (size_t)n_src * 8));
-    CHK(ds_upload(c, dsrc, src, n_t * 4));
-    CHK(ds_upload(c, dshift, shift, n_t * 8));
-    CHK(ds_upload(c, dfrac, frac, n_t * 8));
-    CHK(ds_upload(c, dw, weight, n_t * 8));
-    if (peak) HIPCHK(c, hipMemsetAsync(dpk, 0, (size_t)n_rows * 8, c->stream));
-    dly::TapArgs ta{dfrac, (int)n_t, order, ntp, beta, dtaps};
-    const int64_t n_tap_threads = (int64_t)n_t * ntp;
-    CHK(launch(c, "delay_taps", dly::k_delay_taps, dim3((unsigned)((n_tap_threads + 255) / 256)), 256, 0, ta));
-    dly::Args<T> a{x, sxc, sxn, dlen, y, syg, syt, out_len, n_rows, n_terms, ntp, dsrc, dshift, dw, dtaps,
-                   peak ? dpk : nullptr};
-    CHK(launch(c, "delay_sum", dly::k_delay_sum<T>,
-               dim3((unsigned)((out_len + dly::TT - 1) / dly::TT), (unsigned)((n_rows + dly::WAVES - 1) / dly::WAVES)),
-               dly::THREADS, 0, a));
-    if (peak) CHK(ds_download(c, peak, dpk, (size_t)n_rows * 8));  // the bits of non-negative doubles
+// Everything ds_delay_sum and ds_delay_sum_dev share; the arrays are the host's.
+struct DelayCall {
+    const char* who;
+    int n_src;
+    const int64_t* src_len;  // [n_src], each at most n_avail (the samples a source row holds)
+    int64_t n_avail;
+    int n_rows, n_terms;
+    const int* src;          // [n_rows][n_terms], as shift, frac and weight
+    const int64_t* shift;
+    const double *frac, *weight;
+    int order;
+    double beta;
+    int64_t out_len;
+    double* peak;            // [n_rows] or nullptr
+    size_t terms() const { return (size_t)n_rows * n_terms; }
+};
+
+static int delay_check(ds_ctx* c, const DelayCall& q, const void* x, const void* y) {
+    if (!c || !x || (!y && !q.peak) || !q.src_len || !q.src || !q.shift || !q.frac || !q.weight)
+        return fail(c, DS_ERR_ARG, q.who, "null argument");
+    if (q.n_src <= 0 || q.n_rows <= 0 || q.n_terms <= 0 || q.out_len <= 0 || !std::isfinite(q.beta) || q.beta < 0)
+        return fail(c, DS_ERR_ARG, q.who, "bad shape");
+    for (int s = 0; s < q.n_src; ++s)
+        if (q.src_len[s] < 0 || q.src_len[s] > q.n_avail) return fail(c, DS_ERR_ARG, q.who, "bad source length");
+    if (q.order < 1 || q.order > dly::MAX_ORDER) return fail(c, DS_ERR_UNSUP, q.who, "filter orders 1 to 255 are built");
+    // the kernel's window starts and spans are int64 sums of a tile start, a shift and the taps: a quarter of the
+    // range leaves them room
+    for (size_t e = 0; e < q.terms(); ++e)
+        if (q.shift[e] > INT64_MAX / 4 || q.shift[e] < -(INT64_MAX / 4))
+            return fail(c, DS_ERR_ARG, q.who, "a term's shift is beyond +-INT64_MAX / 4");
     return DS_OK;
 }
 
-static int delay_shape_ok(ds_ctx* c, const char* who, int n_src, const int64_t* src_len, int64_t n_avail, int n_rows,
-                          int n_terms, const int* src, const int64_t* shift, const double* frac,
-                          const double* weight, int order, double beta, int64_t out_len) {
-    if (!src_len || !src || !shift || !frac || !weight) return fail(c, DS_ERR_ARG, std::string(who) + ": null argument");
-    if (n_src <= 0 || n_rows <= 0 || n_terms <= 0 || out_len <= 0 || !std::isfinite(beta) || beta < 0)
-        return fail(c, DS_ERR_ARG, std::string(who) + ": bad shape");
-    for (int s = 0; s < n_src; ++s)
-        if (src_len[s] < 0 || src_len[s] > n_avail) return fail(c, DS_ERR_ARG, std::string(who) + ": bad source length");
-    if (order < 1 || order > dly::MAX_ORDER)
-        return fail(c, DS_ERR_UNSUP, std::string(who) + ": filter orders 1 to 255 are built");
-    // the kernel's window starts and spans are int64 sums of a tile start, a shift and the taps: a quarter of the
-    // range leaves them room
-    for (size_t e = 0, n_t = (size_t)n_rows * n_terms; e < n_t; ++e)
-        if (shift[e] > INT64_MAX / 4 || shift[e] < -(INT64_MAX / 4))
-            return fail(c, DS_ERR_ARG, std::string(who) + ": a term's shift is beyond +-INT64_MAX / 4");
+// the taps of every term, then the sum; x element (c, n) at x[c sxc + n sxn], y element (g, t) at y[g syg + t syt]
+template <typename T>
+static int delay_run(ds_ctx* c, const DelayCall& q, const T* x, int64_t sxc, int64_t sxn, T* y, int64_t syg, int64_t syt) {
+    const int ntp = (q.order + 1 + dly::R - 1) / dly::R * dly::R, n_rows = q.n_rows;
+    const size_t n_t = q.terms();
+    if ((n_rows + dly::WAVES - 1) / dly::WAVES > 65535)
+        return fail(c, DS_ERR_UNSUP, q.who, "more than 262140 output rows in one call is not built");
+    if ((q.out_len + dly::TT - 1) / dly::TT > INT32_MAX || (n_t * ntp + 255) / 256 > (size_t)INT32_MAX)
+        return fail(c, DS_ERR_UNSUP, q.who, "output too long or too many terms");
+    for (size_t e = 0; e < n_t; ++e)
+        if (q.src[e] < 0 || q.src[e] >= q.n_src || !std::isfinite(q.weight[e]) || !(q.frac[e] < 1.0))
+            return fail(c, DS_ERR_ARG, q.who, "a term's source, weight or fraction is out of range");
+    void* t[kMaxStaged];  // the five tables, the taps of every term, the bits of the peaks
+    CHK(stage(c, &c->ws, &c->ws_bytes, {{8, (size_t)q.n_src, q.src_len}, {4, n_t, q.src}, {8, n_t, q.shift}, {8, n_t, q.frac},
+                                        {8, n_t, q.weight}, {8, n_t * ntp}, {8, q.peak ? (size_t)n_rows : 0}}, t));
+    double* dtaps = (double*)t[5];
+    unsigned long long* dpk = q.peak ? (unsigned long long*)t[6] : nullptr;
+    if (dpk) HIPCHK(c, hipMemsetAsync(dpk, 0, (size_t)n_rows * 8, c->stream));
+    dly::TapArgs ta{(const double*)t[3], (int)n_t, q.order, ntp, q.beta, dtaps};
+    const int64_t n_tap_threads = (int64_t)n_t * ntp;
+    CHK(launch(c, "delay_taps", dly::k_delay_taps, dim3((unsigned)((n_tap_threads + 255) / 256)), 256, 0, ta));
+    dly::Args<T> a{x, sxc, sxn, (const int64_t*)t[0], y, syg, syt, q.out_len, n_rows, q.n_terms, ntp, (const int*)t[1],
+                   (const int64_t*)t[2], (const double*)t[4], dtaps, dpk};
+    CHK(launch(c, "delay_sum", dly::k_delay_sum<T>,
+               dim3((unsigned)((q.out_len + dly::TT - 1) / dly::TT), (unsigned)((n_rows + dly::WAVES - 1) / dly::WAVES)),
+               dly::THREADS, 0, a));
+    if (dpk) CHK(ds_download(c, q.peak, dpk, (size_t)n_rows * 8));  // the bits of non-negative doubles
     return DS_OK;
 }
 
@@ -3478,53 +3492,64 @@ extern "C" int ds_delay_sum_dev(ds_ctx* c, const float* x, int n_src, int64_t ld
                                 int n_rows, int n_terms, const int* src, const int64_t* shift, const double* frac,
                                 const double* weight, int order, double beta, int64_t out_len, float* y,
                                 int64_t ld_y, double* peak) {
-    if (!c || !x || (!y && !peak)) return fail(c, DS_ERR_ARG, "ds_delay_sum_dev: null argument");
-    CHK(delay_shape_ok(c, "ds_delay_sum_dev", n_src, src_len, ldx, n_rows, n_terms, src, shift, frac, weight, order,
-                       beta, out_len));
-    if (y && ld_y < out_len) return fail(c, DS_ERR_ARG, "ds_delay_sum_dev: bad shape");
+    const DelayCall q{"ds_delay_sum_dev", n_src, src_len, ldx, n_rows, n_terms, src, shift, frac, weight, order, beta, out_len, peak};
+    CHK(delay_check(c, q, x, y));
+    if (y && ld_y < out_len) return fail(c, DS_ERR_ARG, q.who, "bad shape");
     HIPCHK(c, hipSetDevice(c->device));
-    return delay_run<float>(c, "ds_delay_sum_dev", x, ldx, 1, n_src, src_len, n_rows, n_terms, src, shift, frac,
-                            weight, order, beta, out_len, y, ld_y, 1, peak);
+    return delay_run<float>(c, q, x, ldx, 1, y, ld_y, 1);
 }
 
 // host pointers in the reference's layouts: x (n_x, n_src), y (out_len, n_rows), float64
 extern "C" int ds_delay_sum(ds_ctx* c, const double* x, int n_src, int64_t n_x, const int64_t* src_len, int n_rows,
                             int n_terms, const int* src, const int64_t* shift, const double* frac,
                             const double* weight, int order, double beta, int64_t out_len, double* y, double* peak) {
-    if (!c || !x || (!y && !peak)) return fail(c, DS_ERR_ARG, "ds_delay_sum: null argument");
-    CHK(delay_shape_ok(c, "ds_delay_sum", n_src, src_len, n_x, n_rows, n_terms, src, shift, frac, weight, order, beta,
-                       out_len));
+    const DelayCall q{"ds_delay_sum", n_src, src_len, n_x, n_rows, n_terms, src, shift, frac, weight, order, beta, out_len, peak};
+    CHK(delay_check(c, q, x, y));
     HIPCHK(c, hipSetDevice(c->device));
     const size_t nx = (size_t)n_src * n_x, ny = y ? (size_t)n_rows * out_len : 0;
-    return staged(c, {{8, nx, x, nullptr}, {8, ny, nullptr, y}}, [&](void* const* d) {
-        return delay_run<double>(c, "ds_delay_sum", (const double*)d[0], 1, n_src, n_src, src_len, n_rows, n_terms, src, shift,
-                                 frac, weight, order, beta, out_len, y ? (double*)d[1] : nullptr, 1, n_rows, peak);
+    return staged(c, {{8, nx, x}, {8, ny, nullptr, y}}, [&](void* const* d) {
+        return delay_run<double>(c, q, (const double*)d[0], 1, n_src, y ? (double*)d[1] : nullptr, 1, n_rows);
     });
 }
 
 // ---- continuous wavelet transform and synchrosqueezing (kernels_cwt.hpp) ---------------------------------------
-static int cwt_check(ds_ctx* c, const char* who, int64_t n_samples, int n_freq, const int64_t* tap_len,
-                     const float* taps) {
-    if (!tap_len || !taps) return fail(c, DS_ERR_ARG, std::string(who) + ": null argument");
-    if (n_samples <= 0 || n_freq <= 0) return fail(c, DS_ERR_ARG, std::string(who) + ": bad shape");
-    for (int f = 0; f < n_freq; ++f) {
-        if (tap_len[f] < 1) return fail(c, DS_ERR_ARG, std::string(who) + ": a wavelet has no taps");
-        if (tap_len[f] > dscwt::MAX_TAPS)
-            return fail(c, DS_ERR_UNSUP, std::string(who) + ": wavelets longer than 2^18 taps are not built");
+// Everything ds_cwt and ds_cwt_dev share; the arrays are the host's.
+struct CwtCall {
+    const char* who;
+    int64_t n_samples;
+    int n_freq;
+    const int64_t* tap_len;        // [n_freq]
+    const float2* taps;            // wavelet f's tap_len[f] complex taps at tap_off[f]
+    const int* channels;           // [n_ch] planar channels of x to transform
+    int n_ch;
+    std::vector<int64_t> tap_off;  // set by cwt_check
+};
+
+// a, b, out: the entry's own arrays
+static int cwt_check(ds_ctx* c, CwtCall& q, const void* a, const void* b, const void* out) {
+    if (!c || !a || !b || !out || !q.tap_len || !q.taps) return fail(c, DS_ERR_ARG, q.who, "null argument");
+    if (q.n_samples <= 0 || q.n_freq <= 0) return fail(c, DS_ERR_ARG, q.who, "bad shape");
+    q.tap_off.resize(q.n_freq);
+    int64_t off = 0;
+    for (int f = 0; f < q.n_freq; ++f) {
+        if (q.tap_len[f] < 1) return fail(c, DS_ERR_ARG, q.who, "a wavelet has no taps");
+        if (q.tap_len[f] > dscwt::MAX_TAPS) return fail(c, DS_ERR_UNSUP, q.who, "wavelets longer than 2^18 taps are not built");
+        q.tap_off[f] = off;
+        off += q.tap_len[f];
     }
     return DS_OK;
 }
 
-// rows sel[0..n_sel) of the scalogram (frequency sel[i] into output row i of out (n_sel, N, n_ch), complex64) of the
-// planar fp32 channels ch[] of x.  tap_off[f] locates wavelet f's tap_len[f] complex taps in taps (host).
-static int cwt_run(ds_ctx* c, const float* x, int64_t ld, int64_t N, const int* ch, int n_ch, const int* sel,
-                   int n_sel, const int64_t* tap_off, const int64_t* tap_len, const float2* taps, float2* out) {
+// rows f0 .. f0 + n_sel of the scalogram (frequency f0 + i into output row i of out (n_sel, N, n_ch), complex64) of the
+// planar fp32 channels q.channels of x
+static int cwt_run(ds_ctx* c, const CwtCall& q, const float* x, int64_t ld, int f0, int n_sel, float2* out) {
     using dscwt::Freq;
+    const int64_t N = q.n_samples;
+    const int n_ch = q.n_ch;
     struct Item { int row; int64_t k0, len, hc; };
     std::map<int, std::vector<Item>> classes;  // by block length M
     for (int i = 0; i < n_sel; ++i) {
-        const int f = sel[i];
-        const int64_t L = tap_len[f], h = (L - 1) / 2;
+        const int64_t L = q.tap_len[f0 + i], h = (L - 1) / 2;
         const int64_t k0 = std::max<int64_t>(0, h - N + 1), k1 = std::min<int64_t>(L - 1, h + N - 1);
         const int64_t lc = k1 - k0 + 1;
         int64_t M = dscwt::MIN_M;
@@ -3553,27 +3578,21 @@ static int cwt_run(ds_ctx* c, const float* x, int64_t ld, int64_t N, const int* 
         }
         std::vector<float2> ht((size_t)ntaps);
         for (int i = 0; i < nf; ++i)
-            std::memcpy(&ht[fr[i].toff], taps + tap_off[sel[items[i].row]] + items[i].k0, (size_t)items[i].len * 8);
+            std::memcpy(&ht[fr[i].toff], q.taps + q.tap_off[f0 + items[i].row] + items[i].k0, (size_t)items[i].len * 8);
         const bool big = M > dscwt::MAX_LDS_M;
         const int64_t n_items = (int64_t)nf * n_blocks * n_ch;
         // big route: items per launch pair (the columns stage writes M complex values per item)
         const int64_t chunk = big ? std::min<int64_t>({n_items, 65535, std::max<int64_t>(1, ((int64_t)256 << 20) / (8 * (int64_t)M))}) : 0;
         if (big && ((int64_t)npair * n_blocks > 65535))
             return fail(c, DS_ERR_UNSUP, "cwt: more than 65535 four-step blocks in one call");
-        int* dch;
-        Freq* dfr;
-        float2 *dtaps, *Z, *W, *zs = nullptr;
-        CHK(carve(c, &c->ws, &c->ws_bytes, [&](Carver& cv) {
-            dch = cv.take<int>(n_ch);
-            dfr = cv.take<Freq>(nf);
-            dtaps = cv.take<float2>(ntaps);
-            Z = cv.take<float2>((size_t)npair * n_blocks * M);
-            W = cv.take<float2>((size_t)nf * M);
-            if (big) zs = cv.take<float2>((size_t)std::max<int64_t>({(int64_t)npair * n_blocks, nf, chunk}) * M);
-        }));
-        CHK(ds_upload(c, dch, ch, (size_t)n_ch * 4));
-        CHK(ds_upload(c, dfr, fr.data(), (size_t)nf * sizeof(Freq)));
-        CHK(ds_upload(c, dtaps, ht.data(), (size_t)ntaps * 8));
+        const size_t n_zs = big ? (size_t)std::max<int64_t>({(int64_t)npair * n_blocks, nf, chunk}) * M : 0;
+        void* t[kMaxStaged];
+        CHK(stage(c, &c->ws, &c->ws_bytes, {{4, (size_t)n_ch, q.channels}, {sizeof(Freq), (size_t)nf, fr.data()}, {8, (size_t)ntaps, ht.data()},
+                                            {8, (size_t)npair * n_blocks * M}, {8, (size_t)nf * M}, {8, n_zs}}, t));
+        const int* dch = (const int*)t[0];
+        const Freq* dfr = (const Freq*)t[1];
+        const float2* dtaps = (const float2*)t[2];
+        float2 *Z = (float2*)t[3], *W = (float2*)t[4], *zs = (float2*)t[5];
         const float inv_m = 1.0f / (float)M;
         if (!big) {
             const float2* tw;
@@ -3624,37 +3643,24 @@ static int cwt_run(ds_ctx* c, const float* x, int64_t ld, int64_t N, const int* 
     return DS_OK;
 }
 
-static void cwt_offsets(int n_freq, const int64_t* tap_len, std::vector<int64_t>& off) {
-    off.resize(n_freq);
-    int64_t o = 0;
-    for (int f = 0; f < n_freq; ++f) {
-        off[f] = o;
-        o += tap_len[f];
-    }
-}
-
 extern "C" int ds_cwt_dev(ds_ctx* c, const float* x, int n_ch, int64_t ldx, int64_t n_samples, const int* channels,
                           int n_out_ch, int n_freq, const int64_t* tap_len, const float* taps, float* out) {
-    if (!c || !x || !channels || !out) return fail(c, DS_ERR_ARG, "ds_cwt_dev: null argument");
-    CHK(cwt_check(c, "ds_cwt_dev", n_samples, n_freq, tap_len, taps));
+    CwtCall q{"ds_cwt_dev", n_samples, n_freq, tap_len, (const float2*)taps, channels, n_out_ch};
+    CHK(cwt_check(c, q, x, channels, out));
     if (n_ch <= 0 || n_out_ch <= 0 || ldx < n_samples) return fail(c, DS_ERR_ARG, "ds_cwt_dev: bad shape");
     for (int i = 0; i < n_out_ch; ++i)
         if (channels[i] < 0 || channels[i] >= n_ch) return fail(c, DS_ERR_ARG, "ds_cwt_dev: channel out of range");
     HIPCHK(c, hipSetDevice(c->device));
-    std::vector<int64_t> off;
-    cwt_offsets(n_freq, tap_len, off);
-    std::vector<int> sel(n_freq);
-    for (int f = 0; f < n_freq; ++f) sel[f] = f;
-    return cwt_run(c, x, ldx, n_samples, channels, n_out_ch, sel.data(), n_freq, off.data(), tap_len,
-                   (const float2*)taps, (float2*)out);
+    return cwt_run(c, q, x, ldx, 0, n_freq, (float2*)out);
 }
 
 // host: x (n_samples, n_ch) float64, out (n_freq, n_samples, n_ch) complex64 (out_f64 = 0) or complex128; the
-// scalogram is computed in frequency chunks of at most 512 MB of complex64 on the device
+// scalogram is computed in frequency chunks of at most 512 MB of complex64 on the device, so this entry places and
+// copies its two arrays itself instead of going through staged()
 extern "C" int ds_cwt(ds_ctx* c, const double* x, int n_ch, int64_t n_samples, int n_freq, const int64_t* tap_len,
                       const float* taps, int out_f64, void* out) {
-    if (!c || !x || !out) return fail(c, DS_ERR_ARG, "ds_cwt: null argument");
-    CHK(cwt_check(c, "ds_cwt", n_samples, n_freq, tap_len, taps));
+    CwtCall q{"ds_cwt", n_samples, n_freq, tap_len, (const float2*)taps, nullptr, n_ch};
+    CHK(cwt_check(c, q, x, x, out));
     if (n_ch <= 0) return fail(c, DS_ERR_ARG, "ds_cwt: bad shape");
     HIPCHK(c, hipSetDevice(c->device));
     const int64_t row = n_samples * n_ch;  // complex values per frequency
@@ -3666,15 +3672,12 @@ extern "C" int ds_cwt(ds_ctx* c, const double* x, int n_ch, int64_t n_samples, i
         dout = cv.take<float2>((size_t)rows * row);
     }));
     CHK(upload_signal(c, nullptr, x, n_samples, n_ch, dx));
-    std::vector<int64_t> off;
-    cwt_offsets(n_freq, tap_len, off);
-    std::vector<int> ch(n_ch), sel(n_freq);
+    std::vector<int> ch(n_ch);
     for (int i = 0; i < n_ch; ++i) ch[i] = i;
-    for (int f = 0; f < n_freq; ++f) sel[f] = f;
+    q.channels = ch.data();
     for (int f0 = 0; f0 < n_freq; f0 += rows) {
         const int nr = std::min(rows, n_freq - f0);
-        CHK(cwt_run(c, dx, n_samples, n_samples, ch.data(), n_ch, sel.data() + f0, nr, off.data(), tap_len,
-                    (const float2*)taps, dout));
+        CHK(cwt_run(c, q, dx, n_samples, f0, nr, dout));
         if (out_f64)
             CHK(download_widen(c, (const float*)dout, 2 * nr * row, (double*)out + 2 * f0 * row));
         else
@@ -3690,41 +3693,39 @@ extern "C" int ds_cwt_squeeze_dev(ds_ctx* c, const float* s, int n_freq, int64_t
     if (n_freq <= 0 || n_ch <= 0 || n_samples < 2)
         return fail(c, DS_ERR_ARG, "ds_cwt_squeeze_dev: bad shape (the gradient needs two samples)");
     HIPCHK(c, hipSetDevice(c->device));
-    double *dfq, *ddf, *dn;
-    CHK(carve(c, &c->ws, &c->ws_bytes, [&](Carver& cv) {
-        dfq = cv.take<double>(n_freq);
-        ddf = cv.take<double>(n_freq);
-        dn = cv.take<double>(norm ? n_freq : 0);
-    }));
-    CHK(ds_upload(c, dfq, freqs, (size_t)n_freq * 8));
-    CHK(ds_upload(c, ddf, delta_f, (size_t)n_freq * 8));
-    if (norm) CHK(ds_upload(c, dn, norm, (size_t)n_freq * 8));
+    const size_t nf = (size_t)n_freq;
+    void* t[kMaxStaged];
+    CHK(stage(c, &c->ws, &c->ws_bytes, {{8, nf, freqs}, {8, nf, delta_f}, {8, norm ? nf : 0, norm}}, t));
     const int64_t cols = n_samples * n_ch;
-    dscwt::SqueezeArgs a{(const float2*)s, n_freq, n_ch, n_samples, dfq, ddf, norm ? dn : nullptr, fs, (double2*)out};
+    dscwt::SqueezeArgs a{(const float2*)s, n_freq, n_ch, n_samples, (const double*)t[0], (const double*)t[1],
+                         norm ? (const double*)t[2] : nullptr, fs, (double2*)out};
     return launch(c, "cwt_squeeze", dscwt::k_cwt_squeeze, dim3((unsigned)((cols + 255) / 256)), 256, 0, a);
 }
 
 // ---- fractional-octave smoothing (kernels_smooth.hpp), float64 -----------------------------------------------
+// what both entries refuse (n_ch: real columns); then wr: the window reversed and normalised by its sum, as the kernel
+// reads it
 static int smooth_check(ds_ctx* c, const char* who, int64_t n_bins, int n_ch, const double* k_log, const double* window,
-                        int64_t n_window) {
-    const std::string w(who);
+                        int64_t n_window, std::vector<double>& wr) {
     if (n_bins < 1 || n_ch < 1 || n_window < 1 || (int64_t)n_ch * 2 > INT32_MAX / 2)
-        return fail(c, DS_ERR_ARG, w + ": bad shape");
+        return fail(c, DS_ERR_ARG, who, "bad shape");
     if (k_log) {
         // k_to_lin brackets every linear bin 1 .. N between two points of k_log: no extrapolation, as in the reference
-        if (n_bins < 2) return fail(c, DS_ERR_ARG, w + ": the logarithmic axis needs two bins");
+        if (n_bins < 2) return fail(c, DS_ERR_ARG, who, "the logarithmic axis needs two bins");
         if (!(k_log[0] <= 1.0) || !(k_log[n_bins - 1] >= (double)n_bins))
-            return fail(c, DS_ERR_ARG, w + ": k_log does not span the bins 1 .. n_bins");
+            return fail(c, DS_ERR_ARG, who, "k_log does not span the bins 1 .. n_bins");
         for (int64_t i = 1; i < n_bins; ++i)
-            if (!(k_log[i] > k_log[i - 1])) return fail(c, DS_ERR_ARG, w + ": k_log is not strictly ascending");
+            if (!(k_log[i] > k_log[i - 1])) return fail(c, DS_ERR_ARG, who, "k_log is not strictly ascending");
     }
     double sum = 0.0;
     for (int64_t k = 0; k < n_window; ++k) sum += window[k];
-    if (!(std::fabs(sum) > 0.0) || !std::isfinite(sum)) return fail(c, DS_ERR_ARG, w + ": the window sums to zero");
+    if (!(std::fabs(sum) > 0.0) || !std::isfinite(sum)) return fail(c, DS_ERR_ARG, who, "the window sums to zero");
     if (smooth_work_too_large(n_bins, n_window, n_ch))
-        return fail(c, DS_ERR_UNSUP, w + ": bins x window x channels is beyond the direct summation's work bound");
+        return fail(c, DS_ERR_UNSUP, who, "bins x window x channels is beyond the direct summation's work bound");
     if ((n_bins * n_ch + dssmooth::NT - 1) / dssmooth::NT > INT32_MAX)
-        return fail(c, DS_ERR_UNSUP, w + ": more values than one launch covers");
+        return fail(c, DS_ERR_UNSUP, who, "more values than one launch covers");
+    wr.assign(n_window, 0.0);
+    for (int64_t k = 0; k < n_window; ++k) wr[k] = window[n_window - 1 - k] / sum;
     return DS_OK;
 }
 
@@ -3748,37 +3749,19 @@ static int smooth_run(ds_ctx* c, const double* v, int64_t n_bins, int n_ch, cons
                   LinArgs{b, klog, n_bins, n_ch, clip_ch, (double)(n_bins - 1) / std::log((double)n_bins), out});
 }
 
-// k_log and the normalised, reversed window on the device
-static int smooth_tables(ds_ctx* c, int64_t n_bins, const double* k_log, const double* window, int64_t n_window,
-                         double* dklog, double* dwr) {
-    double sum = 0.0;
-    for (int64_t k = 0; k < n_window; ++k) sum += window[k];
-    std::vector<double> wr(n_window);
-    for (int64_t k = 0; k < n_window; ++k) wr[k] = window[n_window - 1 - k] / sum;
-    CHK(ds_upload(c, dwr, wr.data(), (size_t)n_window * 8));
-    if (k_log) CHK(ds_upload(c, dklog, k_log, (size_t)n_bins * 8));
-    return DS_OK;
-}
-
 extern "C" int ds_octave_smooth(ds_ctx* c, const double* v, int64_t n_bins, int n_ch, const double* k_log,
                                 const double* window, int64_t n_window, int clip, double* out) {
     if (!c || !v || !window || !out) return fail(c, DS_ERR_ARG, "ds_octave_smooth: null argument");
-    CHK(smooth_check(c, "ds_octave_smooth", n_bins, n_ch, k_log, window, n_window));
+    std::vector<double> wr;
+    CHK(smooth_check(c, "ds_octave_smooth", n_bins, n_ch, k_log, window, n_window, wr));
     HIPCHK(c, hipSetDevice(c->device));
-    const size_t n = (size_t)n_bins * n_ch;
-    double *dv, *da, *db, *dout, *dklog, *dwr;
-    CHK(carve(c, &c->ws, &c->ws_bytes, [&](Carver& cv) {
-        dv = cv.take<double>(n);
-        da = cv.take<double>(k_log ? n : 0);
-        db = cv.take<double>(k_log ? n : 0);
-        dout = cv.take<double>(n);
-        dklog = cv.take<double>(k_log ? n_bins : 0);
-        dwr = cv.take<double>(n_window);
-    }));
-    CHK(smooth_tables(c, n_bins, k_log, window, n_window, dklog, dwr));
-    CHK(ds_upload(c, dv, v, n * 8));
-    CHK(smooth_run(c, dv, n_bins, n_ch, k_log ? dklog : nullptr, dwr, n_window, clip ? n_ch : 0, da, db, dout));
-    return ds_download(c, out, dout, n * 8);
+    const size_t n = (size_t)n_bins * n_ch, nl = k_log ? n : 0;
+    void* t[kMaxStaged];  // the two arrays between the passes, k_log, the window
+    CHK(stage(c, &c->ws, &c->ws_bytes, {{8, nl}, {8, nl}, {8, k_log ? (size_t)n_bins : 0, k_log}, {8, wr.size(), wr.data()}}, t));
+    return staged(c, {{8, n, v}, {8, n, nullptr, out}}, [&](void* const* d) {
+        return smooth_run(c, (const double*)d[0], n_bins, n_ch, k_log ? (const double*)t[2] : nullptr, (const double*)t[3],
+                          n_window, clip ? n_ch : 0, (double*)t[0], (double*)t[1], (double*)d[1]);
+    });
 }
 
 // z, out: (n_bins, n_ch) complex128.  |z| and the unwrapped phase are smoothed as the 2 n_ch columns of one real array
@@ -3787,34 +3770,31 @@ extern "C" int ds_octave_smooth_complex(ds_ctx* c, const double* z, int64_t n_bi
                                         const double* window, int64_t n_window, int clip_magnitude, double* out) {
     using namespace dssmooth;
     if (!c || !z || !window || !out) return fail(c, DS_ERR_ARG, "ds_octave_smooth_complex: null argument");
-    CHK(smooth_check(c, "ds_octave_smooth_complex", n_bins, 2 * n_ch, k_log, window, n_window));
+    std::vector<double> wr;
+    CHK(smooth_check(c, "ds_octave_smooth_complex", n_bins, 2 * n_ch, k_log, window, n_window, wr));
     HIPCHK(c, hipSetDevice(c->device));
-    const size_t n = (size_t)n_bins * n_ch;
-    double *dz, *dmp, *dun, *da, *db, *dout, *dklog, *dwr;
-    CHK(carve(c, &c->ws, &c->ws_bytes, [&](Carver& cv) {
-        dz = cv.take<double>(2 * n);   // the spectrum, then the result
-        dmp = cv.take<double>(2 * n);  // (its magnitude columns stay unused) | wrapped phase
-        dun = cv.take<double>(2 * n);  // magnitude | unwrapped phase
-        da = cv.take<double>(k_log ? 2 * n : 0);
-        db = cv.take<double>(k_log ? 2 * n : 0);
-        dout = cv.take<double>(2 * n);
-        dklog = cv.take<double>(k_log ? n_bins : 0);
-        dwr = cv.take<double>(n_window);
-    }));
-    CHK(smooth_tables(c, n_bins, k_log, window, n_window, dklog, dwr));
-    CHK(ds_upload(c, dz, z, n * 16));
-    const dim3 flat((unsigned)((n + NT - 1) / NT));
-    CHK(launch(c, "smooth_polar", k_polar, flat, NT, 0, PolarArgs{(const double2*)dz, n_bins, n_ch, dun, dmp}));
-    CHK(launch(c, "smooth_unwrap", k_unwrap, dim3((unsigned)n_ch), NT, 0,
-               UnwrapArgs{dmp + n_ch, n_bins, 2 * (int64_t)n_ch, dun + n_ch}));
-    CHK(smooth_run(c, dun, n_bins, 2 * n_ch, k_log ? dklog : nullptr, dwr, n_window, clip_magnitude ? n_ch : 0, da, db,
-                   dout));
-    CHK(launch(c, "smooth_recombine", k_recombine, flat, NT, 0, RecombineArgs{dout, n_bins, n_ch, (double2*)dz}));
-    return ds_download(c, out, dz, n * 16);
+    const size_t n = (size_t)n_bins * n_ch, nl = k_log ? 2 * n : 0;
+    void* t[kMaxStaged];
+    CHK(stage(c, &c->ws, &c->ws_bytes, {{8, 2 * n},  // (its magnitude columns stay unused) | wrapped phase
+                                        {8, 2 * n},  // magnitude | unwrapped phase
+                                        {8, nl}, {8, nl}, {8, 2 * n},  // between the passes; the smoothed columns
+                                        {8, k_log ? (size_t)n_bins : 0, k_log}, {8, wr.size(), wr.data()}}, t));
+    double *dmp = (double*)t[0], *dun = (double*)t[1], *dsm = (double*)t[4];
+    return staged(c, {{16, n, z, out}}, [&](void* const* d) {  // the spectrum, then the result
+        double2* dz = (double2*)d[0];
+        const dim3 flat((unsigned)((n + NT - 1) / NT));
+        CHK(launch(c, "smooth_polar", k_polar, flat, NT, 0, PolarArgs{dz, n_bins, n_ch, dun, dmp}));
+        CHK(launch(c, "smooth_unwrap", k_unwrap, dim3((unsigned)n_ch), NT, 0,
+                   UnwrapArgs{dmp + n_ch, n_bins, 2 * (int64_t)n_ch, dun + n_ch}));
+        CHK(smooth_run(c, dun, n_bins, 2 * n_ch, k_log ? (const double*)t[5] : nullptr, (const double*)t[6], n_window,
+                       clip_magnitude ? n_ch : 0, (double*)t[2], (double*)t[3], dsm));
+        return launch(c, "smooth_recombine", k_recombine, flat, NT, 0, RecombineArgs{dsm, n_bins, n_ch, dz});
+    });
 }
 
 // ---- direct sums (kernels_direct.hpp), float64 --------------------------------------------------------------
-// Everything ds_dft and ds_dft_dev share.  x: device samples, element (n, c) at x[n ss + c cs].
+// Everything ds_dft and ds_dft_dev share.  x: device samples, element (n, c) at x[n ss + c cs]; out: the device's copy
+// of q.out.
 struct DftCall {
     const char* who;
     int64_t n_samples;
@@ -3831,44 +3811,44 @@ struct DftCall {
 // validation, the kept distances of the windowed form and the work bound; nothing touches the device.  *empty: the
 // result has no elements.
 static int dft_check(ds_ctx* c, const DftCall& q, std::vector<int64_t>& dist, bool* empty) {
-    const std::string w(q.who);
     *empty = q.n_freq == 0 || q.n_ch == 0;
-    if (q.n_freq < 0 || q.n_ch < 0 || q.n_samples < 1 || !(q.fs > 0.0)) return fail(c, DS_ERR_ARG, w + ": bad shape");
+    if (q.n_freq < 0 || q.n_ch < 0 || q.n_samples < 1 || !(q.fs > 0.0)) return fail(c, DS_ERR_ARG, q.who, "bad shape");
     if (*empty) return DS_OK;
     const double N = (double)q.n_samples, C = (double)q.n_ch;
     // an upper bound first: it needs no array, and a frequency count beyond it is never walked
     if (!q.alpha && dft_work_too_large((double)q.n_freq * N * C, false))
-        return fail(c, DS_ERR_UNSUP, w + ": frequencies x samples x channels is beyond the direct summation's work bound");
+        return fail(c, DS_ERR_UNSUP, q.who, "frequencies x samples x channels is beyond the direct summation's work bound");
     if ((q.n_freq + dsdirect::FT - 1) / dsdirect::FT > INT32_MAX || (q.n_ch + dsdirect::CT - 1) / dsdirect::CT > 65535 ||
         q.n_freq * q.n_ch > INT64_MAX / 64)
-        return fail(c, DS_ERR_UNSUP, w + ": more frequencies or channels than one launch covers");
-    if (!q.freqs_hz || !q.out) return fail(c, DS_ERR_ARG, w + ": null argument");
+        return fail(c, DS_ERR_UNSUP, q.who, "more frequencies or channels than one launch covers");
+    if (!q.freqs_hz || !q.out) return fail(c, DS_ERR_ARG, q.who, "null argument");
     if (!q.alpha) return DS_OK;
     // every (bin, channel) keeps its peak sample at least
     if (dft_work_too_large((double)q.n_freq * C, true) || q.n_freq > ((int64_t)1 << 28))
-        return fail(c, DS_ERR_UNSUP, w + ": the kept window terms are beyond the direct summation's work bound");
+        return fail(c, DS_ERR_UNSUP, q.who, "the kept window terms are beyond the direct summation's work bound");
     if (!q.peak || !(q.half > 0.0) || std::isnan(q.min_weight_log2) || q.min_weight_log2 > 0.0)
-        return fail(c, DS_ERR_ARG, w + ": the windowed form needs peak, half > 0 and min_weight_log2 <= 0");
+        return fail(c, DS_ERR_ARG, q.who, "the windowed form needs peak, half > 0 and min_weight_log2 <= 0");
     for (int ch = 0; ch < q.n_ch; ++ch)
-        if (q.peak[ch] < 0 || q.peak[ch] >= q.n_samples) return fail(c, DS_ERR_ARG, w + ": peak outside the signal");
+        if (q.peak[ch] < 0 || q.peak[ch] >= q.n_samples) return fail(c, DS_ERR_ARG, q.who, "peak outside the signal");
     // weight(d) = exp(-alpha (d / half)^2 / 2) >= 2^min_weight_log2  <=>  d <= half sqrt(-2 ln2 min_weight_log2 / alpha)
     dist.resize(q.n_freq);
     double terms = 0.0;
     for (int64_t k = 0; k < q.n_freq; ++k) {
         const double a = q.alpha[k];
-        if (std::isnan(a)) return fail(c, DS_ERR_ARG, w + ": alpha is NaN");
+        if (std::isnan(a)) return fail(c, DS_ERR_ARG, q.who, "alpha is NaN");
         const double d = a > 0.0 ? q.half * std::sqrt(-2.0 * 0.6931471805599453 * q.min_weight_log2 / a) : N;
         dist[k] = d < N ? (int64_t)d : q.n_samples;
         for (int ch = 0; ch < q.n_ch; ++ch)
             terms += (double)(std::min(q.n_samples, q.peak[ch] + dist[k] + 1) - std::max<int64_t>(0, q.peak[ch] - dist[k]));
     }
     if (dft_work_too_large(terms, true))
-        return fail(c, DS_ERR_UNSUP, w + ": the kept window terms are beyond the direct summation's work bound");
+        return fail(c, DS_ERR_UNSUP, q.who, "the kept window terms are beyond the direct summation's work bound");
     return DS_OK;
 }
 
 template <typename T>
-static int dft_run(ds_ctx* c, const DftCall& q, const T* x, int64_t ss, int64_t cs, const std::vector<int64_t>& dist) {
+static int dft_run(ds_ctx* c, const DftCall& q, const T* x, int64_t ss, int64_t cs, const std::vector<int64_t>& dist,
+                   double2* out) {
     using namespace dsdirect;
     const int64_t F = q.n_freq, n_out = F * q.n_ch;
     const int64_t ftiles = (F + FT - 1) / FT, ctiles = (q.n_ch + CT - 1) / CT;
@@ -3877,32 +3857,20 @@ static int dft_run(ds_ctx* c, const DftCall& q, const T* x, int64_t ss, int64_t 
     const int64_t want = std::max<int64_t>(1, 4096 / (ftiles * ctiles));
     const int64_t chunk = (units + std::min(units, want) - 1) / std::min(units, want) * CHUNK_UNIT;
     const int n_chunks = (int)((q.n_samples + chunk - 1) / chunk);
-    double *dfq, *dal;
-    int64_t *dpk, *dds;
-    double2 *dpart, *dout;
-    CHK(carve(c, &c->ws, &c->ws_bytes, [&](Carver& cv) {
-        dfq = cv.take<double>(F);
-        dal = cv.take<double>(q.alpha ? F : 0);
-        dds = cv.take<int64_t>(q.alpha ? F : 0);
-        dpk = cv.take<int64_t>(q.alpha ? q.n_ch : 0);
-        dpart = cv.take<double2>((size_t)n_chunks * n_out);
-        dout = cv.take<double2>(n_out);
-    }));
-    CHK(ds_upload(c, dfq, q.freqs_hz, (size_t)F * 8));
-    if (q.alpha) {
-        CHK(ds_upload(c, dal, q.alpha, (size_t)F * 8));
-        CHK(ds_upload(c, dds, dist.data(), (size_t)F * 8));
-        CHK(ds_upload(c, dpk, q.peak, (size_t)q.n_ch * 8));
-    }
-    DftArgs a{x, ss, cs, q.n_samples, q.n_ch, dfq, F, q.fs, dal, dpk, dds, q.half, chunk, dpart};
+    const size_t nw = q.alpha ? (size_t)F : 0;  // the windowed form's three tables
+    void* t[kMaxStaged];  // frequencies, alpha, kept distances, peaks, the chunks' partial sums
+    CHK(stage(c, &c->ws, &c->ws_bytes, {{8, (size_t)F, q.freqs_hz}, {8, nw, q.alpha}, {8, nw, dist.data()},
+                                        {8, q.alpha ? (size_t)q.n_ch : 0, q.peak}, {16, (size_t)n_chunks * n_out}}, t));
+    double2* dpart = (double2*)t[4];
+    DftArgs a{x, ss, cs, q.n_samples, q.n_ch, (const double*)t[0], F, q.fs, (const double*)t[1], (const int64_t*)t[3],
+              (const int64_t*)t[2], q.half, chunk, dpart};
     const dim3 grid((unsigned)ftiles, (unsigned)n_chunks, (unsigned)ctiles);
     if (q.alpha)
         CHK(launch(c, "dft@windowed", k_dft<T, true>, grid, NT, 0, a));
     else
         CHK(launch(c, "dft", k_dft<T, false>, grid, NT, 0, a));
-    CHK(launch(c, "dft_combine", k_dft_combine, dim3((unsigned)((n_out + NT - 1) / NT)), NT, 0,
-               CombineArgs{dpart, n_out, n_chunks, dout}));
-    return ds_download(c, q.out, dout, (size_t)n_out * 16);
+    return launch(c, "dft_combine", k_dft_combine, dim3((unsigned)((n_out + NT - 1) / NT)), NT, 0,
+                  CombineArgs{dpart, n_out, n_chunks, out});
 }
 
 extern "C" int ds_dft(ds_ctx* c, const double* x, int64_t n_samples, int n_ch, const double* freqs_hz, int64_t n_freq,
@@ -3916,10 +3884,9 @@ extern "C" int ds_dft(ds_ctx* c, const double* x, int64_t n_samples, int n_ch, c
     if (empty) return DS_OK;
     if (!x) return fail(c, DS_ERR_ARG, "ds_dft: null argument");
     HIPCHK(c, hipSetDevice(c->device));
-    double* dx;
-    CHK(carve(c, &c->io, &c->io_bytes, [&](Carver& cv) { dx = cv.take<double>((size_t)n_samples * n_ch); }));
-    CHK(ds_upload(c, dx, x, (size_t)n_samples * n_ch * 8));
-    return dft_run<double>(c, q, dx, n_ch, 1, dist);
+    return staged(c, {{8, (size_t)n_samples * n_ch, x}, {16, (size_t)n_freq * n_ch, nullptr, out}}, [&](void* const* d) {
+        return dft_run<double>(c, q, (const double*)d[0], n_ch, 1, dist, (double2*)d[1]);
+    });
 }
 
 extern "C" int ds_dft_dev(ds_ctx* c, const float* x, int n_ch, int64_t ldx, int64_t n_samples, const double* freqs_hz,
@@ -3933,7 +3900,9 @@ extern "C" int ds_dft_dev(ds_ctx* c, const float* x, int n_ch, int64_t ldx, int6
     if (empty) return DS_OK;
     if (!x || ldx < n_samples) return fail(c, DS_ERR_ARG, "ds_dft_dev: null samples or ldx < n_samples");
     HIPCHK(c, hipSetDevice(c->device));
-    return dft_run<float>(c, q, x, 1, ldx, dist);
+    return staged(c, {{16, (size_t)n_freq * n_ch, nullptr, out}}, [&](void* const* d) {
+        return dft_run<float>(c, q, x, 1, ldx, dist, (double2*)d[0]);
+    });
 }
 
 // z, out: host (n_bins, n_ch) complex128.  ind_low / ind_high: the band of every bin clipped to [0, n_bins];
@@ -3967,73 +3936,60 @@ extern "C" int ds_complex_smooth(ds_ctx* c, const double* z, int64_t n_bins, int
     HIPCHK(c, hipSetDevice(c->device));
     const size_t n = (size_t)n_bins * n_ch;
     const int64_t ld = 2 * (int64_t)n_ch;
-    double *dz, *da, *db, *ds, *dwx, *dwy;
-    int *dlo, *dhi, *dwl, *dps;
-    CHK(carve(c, &c->ws, &c->ws_bytes, [&](Carver& cv) {
-        dz = cv.take<double>(2 * n);  // the spectrum, then the result
-        da = cv.take<double>(2 * n);  // the domain's quantity: (bins, 2 C) real columns
-        db = cv.take<double>(2 * n);  // wrapped phases, values nobody reads
-        ds = cv.take<double>(2 * n);  // smoothed columns
-        dwx = cv.take<double>(n_window);
-        dwy = cv.take<double>(n_window);
-        dlo = cv.take<int>(n_bins);
-        dhi = cv.take<int>(n_bins);
-        dwl = cv.take<int>(n_bins);
-        dps = cv.take<int>(n_bins);
-    }));
-    CHK(ds_upload(c, dwx, window_x, (size_t)n_window * 8));
-    CHK(ds_upload(c, dwy, window_y, (size_t)n_window * 8));
-    CHK(ds_upload(c, dlo, ind_low, (size_t)n_bins * 4));
-    CHK(ds_upload(c, dhi, ind_high, (size_t)n_bins * 4));
-    CHK(ds_upload(c, dwl, window_length, (size_t)n_bins * 4));
-    CHK(ds_upload(c, dps, pass, (size_t)n_bins * 4));
-    CHK(ds_upload(c, dz, z, n * 16));
-    const dim3 flat((unsigned)((n + NT - 1) / NT));
-    // the band sums of the leading n_cols columns of a (bins, 2 C) array
-    auto smooth = [&](const double* v, double* o, int n_cols) {
-        return launch(c, "csmooth", k_csmooth, dim3((unsigned)((n_bins + WAVES - 1) / WAVES), (unsigned)((n_cols + WCT - 1) / WCT)),
-                      NT, 0, CsmoothArgs{v, ld, o, ld, n_cols, n_bins, dlo, dhi, dwl, dps, dwx, dwy, n_window});
-    };
-    auto polar = [&](const double* zz, double* mag, double* ph) {
-        return launch(c, "csmooth_polar", dssmooth::k_polar, flat, NT, 0,
-                      dssmooth::PolarArgs{(const double2*)zz, n_bins, n_ch, mag, ph});
-    };
-    auto colmap = [&](double* v, int root) {
-        return launch(c, "csmooth_map", k_colmap, flat, NT, 0, ColmapArgs{v, n_bins, ld, n_ch, root});
-    };
-    auto recombine = [&](const double* mp) {
+    const size_t nb = (size_t)n_bins, nw = (size_t)n_window;
+    void* t[kMaxStaged];
+    CHK(stage(c, &c->ws, &c->ws_bytes, {{8, 2 * n},  // the domain's quantity: (bins, 2 C) real columns
+                                        {8, 2 * n},  // wrapped phases, values nobody reads
+                                        {8, 2 * n},  // smoothed columns
+                                        {8, nw, window_x}, {8, nw, window_y}, {4, nb, ind_low}, {4, nb, ind_high},
+                                        {4, nb, window_length}, {4, nb, pass}}, t));
+    double *da = (double*)t[0], *db = (double*)t[1], *ds = (double*)t[2];
+    return staged(c, {{16, n, z}, {16, n, nullptr, out}}, [&](void* const* d) {
+        const double* dz = (const double*)d[0];
+        double* dres = (double*)d[1];
+        const dim3 flat((unsigned)((n + NT - 1) / NT));
+        // the band sums of the leading n_cols columns of a (bins, 2 C) array
+        auto smooth = [&](const double* v, double* o, int n_cols) {
+            return launch(c, "csmooth", k_csmooth, dim3((unsigned)((n_bins + WAVES - 1) / WAVES), (unsigned)((n_cols + WCT - 1) / WCT)),
+                          NT, 0, CsmoothArgs{v, ld, o, ld, n_cols, n_bins, (const int*)t[5], (const int*)t[6], (const int*)t[7],
+                                             (const int*)t[8], (const double*)t[3], (const double*)t[4], n_window});
+        };
+        auto polar = [&](const double* zz, double* mag, double* ph) {
+            return launch(c, "csmooth_polar", dssmooth::k_polar, flat, NT, 0,
+                          dssmooth::PolarArgs{(const double2*)zz, n_bins, n_ch, mag, ph});
+        };
+        auto colmap = [&](double* v, int root) {
+            return launch(c, "csmooth_map", k_colmap, flat, NT, 0, ColmapArgs{v, n_bins, ld, n_ch, root});
+        };
+        const bool power = domain == DS_SMOOTH_POWER_PHASE || domain == DS_SMOOTH_POWER || domain == DS_SMOOTH_EQUIVALENT_COMPLEX;
+        switch (domain) {
+        case DS_SMOOTH_REAL_IMAGINARY:  // (re, im) interleaved are 2 C real columns as they stand
+            return smooth(dz, dres, 2 * n_ch);
+        case DS_SMOOTH_MAGNITUDE_PHASE:
+        case DS_SMOOTH_POWER_PHASE:  // da = magnitude or power | unwrapped phase, all smoothed
+            CHK(polar(dz, da, db));
+            CHK(launch(c, "csmooth_unwrap", dssmooth::k_unwrap, dim3((unsigned)n_ch), NT, 0,
+                       dssmooth::UnwrapArgs{db + n_ch, n_bins, ld, da + n_ch}));
+            if (power) CHK(colmap(da, 0));
+            CHK(smooth(da, ds, 2 * n_ch));
+            break;
+        case DS_SMOOTH_MAGNITUDE:
+        case DS_SMOOTH_POWER:  // the phase of the input goes straight into ds; only the magnitudes are smoothed
+            CHK(polar(dz, da, ds));
+            if (power) CHK(colmap(da, 0));
+            CHK(smooth(da, ds, n_ch));
+            break;
+        default:  // DS_SMOOTH_EQUIVALENT_COMPLEX: the phase of the smoothed spectrum, the smoothed power
+            CHK(smooth(dz, da, 2 * n_ch));
+            CHK(polar(da, db, ds));
+            CHK(polar(dz, da, db));
+            CHK(colmap(da, 0));
+            CHK(smooth(da, ds, n_ch));
+        }
+        if (power) CHK(colmap(ds, 1));
         return launch(c, "csmooth_recombine", dssmooth::k_recombine, flat, NT, 0,
-                      dssmooth::RecombineArgs{mp, n_bins, n_ch, (double2*)dz});
-    };
-    const bool power = domain == DS_SMOOTH_POWER_PHASE || domain == DS_SMOOTH_POWER || domain == DS_SMOOTH_EQUIVALENT_COMPLEX;
-    switch (domain) {
-    case DS_SMOOTH_REAL_IMAGINARY:  // (re, im) interleaved are 2 C real columns as they stand
-        CHK(smooth(dz, ds, 2 * n_ch));
-        return ds_download(c, out, ds, n * 16);
-    case DS_SMOOTH_MAGNITUDE_PHASE:
-    case DS_SMOOTH_POWER_PHASE:  // da = magnitude or power | unwrapped phase, all smoothed
-        CHK(polar(dz, da, db));
-        CHK(launch(c, "csmooth_unwrap", dssmooth::k_unwrap, dim3((unsigned)n_ch), NT, 0,
-                   dssmooth::UnwrapArgs{db + n_ch, n_bins, ld, da + n_ch}));
-        if (power) CHK(colmap(da, 0));
-        CHK(smooth(da, ds, 2 * n_ch));
-        break;
-    case DS_SMOOTH_MAGNITUDE:
-    case DS_SMOOTH_POWER:  // the phase of the input goes straight into ds; only the magnitudes are smoothed
-        CHK(polar(dz, da, ds));
-        if (power) CHK(colmap(da, 0));
-        CHK(smooth(da, ds, n_ch));
-        break;
-    default:  // DS_SMOOTH_EQUIVALENT_COMPLEX: the phase of the smoothed spectrum, the smoothed power
-        CHK(smooth(dz, da, 2 * n_ch));
-        CHK(polar(da, db, ds));
-        CHK(polar(dz, da, db));
-        CHK(colmap(da, 0));
-        CHK(smooth(da, ds, n_ch));
-    }
-    if (power) CHK(colmap(ds, 1));
-    CHK(recombine(ds));
-    return ds_download(c, out, dz, n * 16);
+                      dssmooth::RecombineArgs{ds, n_bins, n_ch, (double2*)dres});
+    });
 }
 
 // ---- complex128 transforms of any length and what is built on them (kernels_fft64.hpp) -----------------------------
@@ -4111,14 +4067,14 @@ static int fft64_blue_tables(ds_ctx* c, Fft64Plan* pl) {
 }
 
 // What every entry checks before anything is uploaded: the shape, the two length bounds, the device memory the call
-// will hold (two planar buffers, `extra` bytes of further workspace, `io` bytes of staging, the tables); then the tables.
+// will hold (mem_check: two planar buffers, `extra` bytes of further workspace, `io` bytes of staging, the tables); then
+// the tables.
 // The entry carves its workspace next, still before staged() uploads anything.
 static int fft64_plan(ds_ctx* c, const char* who, int64_t n, int64_t n_ch, size_t extra, size_t io, Fft64Plan* pl) {
-    const std::string w(who);
-    if (n < 1 || n_ch < 1) return fail(c, DS_ERR_ARG, w + ": bad shape");
+    if (n < 1 || n_ch < 1) return fail(c, DS_ERR_ARG, who, "bad shape");
     if (fft64_len_unsupported(n))
-        return fail(c, DS_ERR_UNSUP, w + ": transform lengths above 2^22 (powers of two) or 2^21 (any other) are not built");
-    if (n_ch > 65535) return fail(c, DS_ERR_UNSUP, w + ": more than 65535 channels in one call is not built");
+        return fail(c, DS_ERR_UNSUP, who, "transform lengths above 2^22 (powers of two) or 2^21 (any other) are not built");
+    if (n_ch > 65535) return fail(c, DS_ERR_UNSUP, who, "more than 65535 channels in one call is not built");
     pl->n = n;
     pl->blue = !is_pow2(n);
     int64_t M = 1;
@@ -4126,16 +4082,8 @@ static int fft64_plan(ds_ctx* c, const char* who, int64_t n, int64_t n_ch, size_
     while (M < (pl->blue ? 2 * n - 1 : n)) M <<= 1, ++lg;
     pl->ld = M;
     pl->lg = lg;
-    HIPCHK(c, hipSetDevice(c->device));
     const bool have_tab = pl->blue && c->blue64.count(n);
-    const size_t tables = pl->blue && !have_tab ? (size_t)(n + 2 * M) * 16 : 0;
-    // as reserve() will allocate them: each buffer grows by an eighth and 4 KB; 1 MB for the carves' 256-byte alignment
-    auto reserved = [](size_t bytes) { return bytes + bytes / 8 + 4096; };
-    const size_t need = reserved(2 * (size_t)M * (size_t)n_ch * 16 + extra + (1 << 20)) + reserved(io + (1 << 20)) + tables;
-    size_t free_b = 0, total_b = 0;
-    CHK(ds_mem_info(c, &free_b, &total_b));
-    if (need > free_b + c->ws_bytes + c->io_bytes)
-        return fail(c, DS_ERR_NOMEM, w + ": the call needs more device memory than is free");
+    CHK(mem_check(c, who, 2 * (size_t)M * (size_t)n_ch * 16 + extra, io, pl->blue && !have_tab ? (size_t)(n + 2 * M) * 16 : 0));
     if (!c->fft64_tw) {
         HIPCHK(c, hipMalloc((void**)&c->fft64_tw, (size_t)(fft64::LDS_MAX / 2) * 16));
         hipLaunchKernelGGL(f64c::k_twiddles, dim3(fft64::LDS_MAX / 2 / 256), dim3(256), 0, c->stream, c->fft64_tw, fft64::LDS_MAX / 2);
@@ -4322,31 +4270,17 @@ struct LpcCall {
     size_t pairs() const { return (size_t)n_frames * (size_t)n_ch; }
 };
 
-// The device memory a call will hold, as reserve() allocates it (fft64_plan has the same rule): DS_ERR_NOMEM before
-// anything is uploaded.
-static int lpc_mem_check(ds_ctx* c, const std::string& w, size_t io, size_t ws) {
-    HIPCHK(c, hipSetDevice(c->device));
-    auto reserved = [](size_t bytes) { return bytes + bytes / 8 + 4096; };
-    const size_t need = reserved(ws + (1 << 20)) + reserved(io + (1 << 20));
-    size_t free_b = 0, total_b = 0;
-    CHK(ds_mem_info(c, &free_b, &total_b));
-    if (need > free_b + c->ws_bytes + c->io_bytes)
-        return fail(c, DS_ERR_NOMEM, w + ": the call needs more device memory than is free");
-    return DS_OK;
-}
-
 // shape, bounds and work guard, then the pointers; nothing touches the device
 static int lpc_check(ds_ctx* c, LpcCall& q, const void* x) {
-    const std::string w(q.who);
     if (q.n_samples < 1 || q.n_ch < 1 || q.L < 2 || q.hop < 1 || q.order < 1 || q.order >= q.L)
-        return fail(c, DS_ERR_ARG, w + ": needs samples, channels, hop >= 1 and 1 <= order < window length");
-    if (q.method != DS_LPC_YULE_WALKER && q.method != DS_LPC_BURG) return fail(c, DS_ERR_ARG, w + ": unknown method");
+        return fail(c, DS_ERR_ARG, q.who, "needs samples, channels, hop >= 1 and 1 <= order < window length");
+    if (q.method != DS_LPC_YULE_WALKER && q.method != DS_LPC_BURG) return fail(c, DS_ERR_ARG, q.who, "unknown method");
     q.n_frames = q.n_samples / q.hop + (q.n_samples % q.hop != 0);
     if (q.n_frames > kLpcMaxPairs / q.n_ch || lpc_shape_unsupported(q.L, q.order, q.n_frames * q.n_ch))
-        return fail(c, DS_ERR_UNSUP, w + ": windows above 8192 samples, orders above 255 or 2^31 (frame, channel) pairs are not built");
+        return fail(c, DS_ERR_UNSUP, q.who, "windows above 8192 samples, orders above 255 or 2^31 (frame, channel) pairs are not built");
     if (lpc_work_too_large(q.n_frames * q.n_ch, q.L, q.order))
-        return fail(c, DS_ERR_UNSUP, w + ": frames x channels x window x (order + 1) is beyond the work bound");
-    if (!c || !x || !q.window || !q.a || !q.var || !q.singular) return fail(c, DS_ERR_ARG, w + ": null argument");
+        return fail(c, DS_ERR_UNSUP, q.who, "frames x channels x window x (order + 1) is beyond the work bound");
+    if (!c || !x || !q.window || !q.a || !q.var || !q.singular) return fail(c, DS_ERR_ARG, q.who, "null argument");
     return DS_OK;
 }
 
@@ -4366,7 +4300,7 @@ extern "C" int ds_lpc(ds_ctx* c, const double* x, int64_t n_samples, int n_ch, c
     LpcCall q{"ds_lpc", n_samples, n_ch, window, window_length, hop, order, method, a, var, singular, 0};
     CHK(lpc_check(c, q, x));
     const size_t nx = (size_t)n_samples * n_ch, na = (size_t)(order + 1) * q.pairs();
-    CHK(lpc_mem_check(c, q.who, (nx + (size_t)q.L + na + q.pairs()) * 8 + 4, 0));
+    CHK(mem_check(c, q.who, 0, (nx + (size_t)q.L + na + q.pairs()) * 8 + 4, 0));
     return staged(c, {{8, nx, x, nullptr}, {8, (size_t)q.L, window, nullptr}, {8, na, nullptr, a}, {8, q.pairs(), nullptr, var},
                       {4, 1, nullptr, singular}}, [&](void* const* d) {
         return lpc_launch<double>(c, q, (const double*)d[0], n_ch, 1, (const double*)d[1], (double*)d[2], (double*)d[3], (int*)d[4]);
@@ -4379,20 +4313,12 @@ extern "C" int ds_lpc_dev(ds_ctx* c, const float* x, int n_ch, int64_t ldx, int6
     CHK(lpc_check(c, q, x));
     if (ldx < n_samples) return fail(c, DS_ERR_ARG, "ds_lpc_dev: ldx < n_samples");
     const size_t na = (size_t)(order + 1) * q.pairs();
-    CHK(lpc_mem_check(c, q.who, 0, ((size_t)q.L + na + q.pairs()) * 8 + 4));
-    double *dw, *da, *dvar;
-    int* dflag;
-    CHK(carve(c, &c->ws, &c->ws_bytes, [&](Carver& cv) {
-        dw = cv.take<double>(q.L);
-        da = cv.take<double>(na);
-        dvar = cv.take<double>(q.pairs());
-        dflag = cv.take<int>(1);
-    }));
-    CHK(ds_upload(c, dw, window, (size_t)q.L * 8));
-    CHK(lpc_launch<float>(c, q, x, 1, ldx, dw, da, dvar, dflag));
-    CHK(ds_download(c, a, da, na * 8));
-    CHK(ds_download(c, var, dvar, q.pairs() * 8));
-    return ds_download(c, singular, dflag, 4);
+    CHK(mem_check(c, q.who, (size_t)q.L * 8, (na + q.pairs()) * 8 + 4, 0));
+    void* t[kMaxStaged];
+    CHK(stage(c, &c->ws, &c->ws_bytes, {{8, (size_t)q.L, window}}, t));
+    return staged(c, {{8, na, nullptr, a}, {8, q.pairs(), nullptr, var}, {4, 1, nullptr, singular}}, [&](void* const* d) {
+        return lpc_launch<float>(c, q, x, 1, ldx, (const double*)t[0], (double*)d[0], (double*)d[1], (int*)d[2]);
+    });
 }
 
 // r: host (order + 1, n_cols); a: host (order + 1, n_cols) with a[0] = 1; var: host (n_cols)
@@ -4402,7 +4328,7 @@ extern "C" int ds_levinson(ds_ctx* c, const double* r, int order, int64_t n_cols
         return fail(c, DS_ERR_UNSUP, "ds_levinson: orders above 255 or 2^31 columns are not built");
     if (!c || !r || !a || !var || !singular) return fail(c, DS_ERR_ARG, "ds_levinson: null argument");
     const size_t nr = (size_t)(order + 1) * (size_t)n_cols;
-    CHK(lpc_mem_check(c, "ds_levinson", (2 * nr + (size_t)n_cols) * 8 + 4, 0));
+    CHK(mem_check(c, "ds_levinson", 0, (2 * nr + (size_t)n_cols) * 8 + 4, 0));
     return staged(c, {{8, nr, r, nullptr}, {8, nr, nullptr, a}, {8, (size_t)n_cols, nullptr, var}, {4, 1, nullptr, singular}},
                   [&](void* const* d) {
         CHK(ds_memset(c, d[3], 0, 4));
@@ -4426,7 +4352,7 @@ extern "C" int ds_lpc_synth(ds_ctx* c, const double* a, const double* sources, c
     if (!c || !a || !sources || !window || !y) return fail(c, DS_ERR_ARG, "ds_lpc_synth: null argument");
     const size_t pairs = (size_t)n_frames * n_ch, na = (size_t)(order + 1) * pairs, ns = (size_t)L * pairs;
     const size_t ny = (size_t)n_out * n_ch;
-    CHK(lpc_mem_check(c, "ds_lpc_synth", (na + ns + (size_t)L + ny) * 8, ns * 8));
+    CHK(mem_check(c, "ds_lpc_synth", ns * 8, (na + ns + (size_t)L + ny) * 8, 0));
     double* yf;
     CHK(carve(c, &c->ws, &c->ws_bytes, [&](Carver& cv) { yf = cv.take<double>(ns); }));
     return staged(c, {{8, na, a, nullptr}, {8, ns, sources, nullptr}, {8, (size_t)L, window, nullptr}, {8, ny, nullptr, y}},
