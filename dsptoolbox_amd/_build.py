@@ -32,6 +32,7 @@ NO_SCRATCH = [
     "k_fft_lds", "5fft6411k_transpose", "5fft647k_chirp", "5fft646k_blue", "5fft646k_load", "5fft647k_store",
     "5fft647k_point", "5fft6410k_gradient",
     "5dslpc8k_lpc_yw", "5dslpc10k_lpc_burg", "5dslpc10k_levinson", "5dslpc12k_lpc_filter", "5dslpc9k_lpc_ola",
+    "6dswarp14k_allpass_tile",
 ]
 
 

@@ -1954,3 +1954,88 @@ def lpc_synthesize(a, sources, window, hop: int, n_out: int):
     ctx.check(ctx.lib.ds_lpc_synth(ctx.handle, _ptr(a), _ptr(sources), _ptr(window), L, n_frames, n_ch, hop, order, n_out,
                                    _ptr(y)), "ds_lpc_synth")
     return y
+
+
+# ---- the all-pass table of frequency warping and the Laguerre transform (csrc/kernels_warp.hpp) --------------------
+# bounds of one call (csrc/size_guards.hpp; DS_ERR_UNSUP above)
+WARP_MAX_SIDE = 1 << 17      # input and output samples: the longest responses in practice
+WARP_MAX_CHANNELS = 65536    # channel groups are the grid's second dimension
+WARP_MAX_WORK = 1e12         # input samples x output samples x channel groups: two seconds at the measured rate
+WARP_GROUP = 4               # channels a workgroup accumulates (G of csrc/warp_plan.hpp)
+
+
+def _warp_check(n_in: int, n_out: int, n_ch: int) -> None:
+    """ValueError for an empty table, NotImplementedError beyond the kernel's bounds; before anything reaches the device."""
+    n_in, n_out, n_ch = int(n_in), int(n_out), int(n_ch)
+    if n_in < 1 or n_out < 1 or n_ch < 1:
+        raise ValueError("allpass_table: needs input samples, output samples and channels")
+    if n_in > WARP_MAX_SIDE or n_out > WARP_MAX_SIDE or n_ch > WARP_MAX_CHANNELS:
+        raise NotImplementedError(f"an all-pass table of {n_in} x {n_out} samples and {n_ch} channels is beyond the device "
+                                  f"kernel's bounds ({WARP_MAX_SIDE} samples a side, {WARP_MAX_CHANNELS} channels)")
+    work = float(n_in) * n_out * (-(-n_ch // WARP_GROUP))
+    if work > WARP_MAX_WORK:
+        raise NotImplementedError(f"an all-pass table of {work:.3g} cells is beyond the device kernel's work bound "
+                                  f"({WARP_MAX_WORK:.0e} = input samples x output samples x groups of {WARP_GROUP} channels)")
+
+
+def allpass_table(time_data, p: float, q: float, row0, col0):
+    """out[j, ch] = sum_i c[i, j] x[i, ch] for the table c[i, j] = p c[i-1, j] + c[i-1, j-1] + q c[i, j-1] (i, j >= 1)
+    with the first row `row0` (its length is the number of output samples) and the first column `col0` (one value per
+    input sample; c[0, 0] = col0[0]).  x is (samples, channels) float64 on the host or a `DevicePlanar`; the table and
+    the sums are float64 on the device, in a fixed order."""
+    row0 = np.ascontiguousarray(row0, dtype=np.float64).ravel()
+    col0 = np.ascontiguousarray(col0, dtype=np.float64).ravel()
+    p, q = float(p), float(q)
+    if not (np.isfinite(p) and np.isfinite(q)):
+        raise ValueError("allpass_table: p and q must be finite")
+    resident = isinstance(time_data, DevicePlanar)
+    if resident:
+        n_in, n_ch = time_data.n_samples, time_data.n_ch
+    else:
+        if np.iscomplexobj(time_data):
+            raise ValueError("allpass_table: the samples must be real")
+        assert np.ndim(time_data) == 2, "the samples are (samples, channels)"
+        n_in, n_ch = np.shape(time_data)
+    n_out = len(row0)
+    _warp_check(n_in, n_out, n_ch)
+    assert len(col0) == n_in, "col0 has a value per input sample"
+    out = np.empty((n_out, n_ch), dtype=np.float64)
+    tail = (p, q, _ptr(row0), _ptr(col0), n_out, _ptr(out))
+    if resident:
+        ctx = time_data.ctx
+        ctx.check(ctx.lib.ds_allpass_table_dev(ctx.handle, C.c_void_p(time_data.ptr), n_ch, time_data.ld, n_in, *tail),
+                  "ds_allpass_table_dev")
+    else:
+        x = np.ascontiguousarray(time_data, dtype=np.float64)
+        ctx = get_context()
+        ctx.check(ctx.lib.ds_allpass_table(ctx.handle, _ptr(x), n_in, n_ch, *tail), "ds_allpass_table")
+    return out
+
+
+def _running_powers(first: float, ratio: float, n: int) -> np.ndarray:
+    """first, first ratio, first ratio^2, ...: running float64 products, as a first-order recursion makes them"""
+    v = np.full(n, float(ratio))
+    v[0] = float(first)
+    return np.multiply.accumulate(v)
+
+
+def _table_length(time_data) -> int:
+    return time_data.n_samples if isinstance(time_data, DevicePlanar) else np.shape(time_data)[0]
+
+
+def warp_time_series(time_data, warping_factor: float):
+    """_warp_time_series of the reference (transforms/_transforms.py:386-428): sample i of every channel times the
+    all-pass (z^-1 - lambda) / (1 - lambda z^-1) applied i times to a unit pulse, summed over i.  (samples, channels)
+    float64 on the host or a `DevicePlanar` -> (samples, channels) float64."""
+    lam, n = float(warping_factor), _table_length(time_data)
+    row0 = np.zeros(n)
+    row0[:1] = 1.0
+    return allpass_table(time_data, -lam, lam, row0, _running_powers(1.0, -lam, n))
+
+
+def laguerre_transform(time_data, warping_factor: float):
+    """The discrete Laguerre transform of the reference (transforms/transforms.py:955-1016): output j is the last
+    sample of the time-reversed input after sqrt(1 - f^2) / (1 + f z^-1) and j all-passes (f + z^-1) / (1 + f z^-1)."""
+    f, n = float(warping_factor), _table_length(time_data)
+    s = (1.0 - f ** 2.0) ** 0.5
+    return allpass_table(time_data, -f, f, _running_powers(s, f, n), _running_powers(s, -f, n))

@@ -47,6 +47,7 @@
 #include "kernels_direct.hpp"
 #include "kernels_fft64.hpp"
 #include "kernels_lpc.hpp"
+#include "kernels_warp.hpp"
 #include "size_guards.hpp"
 
 using namespace dsk;
@@ -4361,6 +4362,71 @@ extern "C" int ds_lpc_synth(ds_ctx* c, const double* a, const double* sources, c
                    FilterArgs{(const double*)d[0], (const double*)d[1], L, (int64_t)pairs, order, yf}));
         return launch(c, "lpc_ola", k_lpc_ola, dim3((unsigned)((ny + NT - 1) / NT)), NT, 0,
                       OlaArgs{yf, (const double*)d[2], L, n_frames, n_ch, hop, n_out, (double*)d[3]});
+    });
+}
+
+// ---- the all-pass table of warp and laguerre (kernels_warp.hpp, warp_plan.hpp), float64 ---------------------------
+// Everything ds_allpass_table and ds_allpass_table_dev share.
+struct AllpassCall {
+    const char* who;
+    int64_t n_in;
+    int n_ch;
+    double p, q;
+    const double *row0, *col0;  // host [n_out], [n_in]
+    int64_t n_out;
+    double* out;                // host (n_out, n_ch)
+    int groups() const { return (n_ch + dswarp::G - 1) / dswarp::G; }
+};
+
+// shape, bounds and work guard, then the pointers; nothing touches the device
+static int allpass_check(ds_ctx* c, const AllpassCall& q, const void* x) {
+    if (q.n_in < 1 || q.n_out < 1 || q.n_ch < 1 || !std::isfinite(q.p) || !std::isfinite(q.q))
+        return fail(c, DS_ERR_ARG, q.who, "needs input samples, output samples, channels and finite p and q");
+    if (warp_shape_unsupported(q.n_in, q.n_out, q.n_ch))
+        return fail(c, DS_ERR_UNSUP, q.who, "tables above 131072 samples a side or 65536 channels are not built");
+    if (warp_work_too_large(q.n_in, q.n_out, q.groups()))
+        return fail(c, DS_ERR_UNSUP, q.who, "input samples x output samples x channel groups is beyond the work bound");
+    if (!c || !x || !q.row0 || !q.col0 || !q.out) return fail(c, DS_ERR_ARG, q.who, "null argument");
+    return DS_OK;
+}
+
+// the boundary image goes to c->ws, then one grid per tile anti-diagonal
+template <typename T>
+static int allpass_launch(ds_ctx* c, const AllpassCall& q, const T* x, int64_t ss, int64_t cs, double* out) {
+    using namespace dswarp;
+    const dswarp::Plan pl = make_plan(q.n_in, q.n_out);
+    std::vector<double> init((size_t)workspace_doubles(pl));
+    initial_image(pl, q.row0, q.col0, init.data());
+    void* t[kMaxStaged];
+    CHK(stage(c, &c->ws, &c->ws_bytes, {{8, init.size(), init.data()}}, t));
+    for (int64_t d = 0; d < pl.launches; ++d) {
+        const TileArgs a{x, ss, cs, q.n_ch, q.p, q.q, (double*)t[0], out, pl, d};
+        CHK(launch(c, "allpass_tile", k_allpass_tile<T>, dim3((unsigned)diagonal(pl, d).count, (unsigned)q.groups()), TJ,
+                   tile_lds_bytes(), a));
+    }
+    return DS_OK;
+}
+
+extern "C" int ds_allpass_table(ds_ctx* c, const double* x, int64_t n_in, int n_ch, double p, double q, const double* row0,
+                                const double* col0, int64_t n_out, double* out) {
+    AllpassCall k{"ds_allpass_table", n_in, n_ch, p, q, row0, col0, n_out, out};
+    CHK(allpass_check(c, k, x));
+    const size_t nx = (size_t)n_in * n_ch, no = (size_t)n_out * n_ch;
+    CHK(mem_check(c, k.who, (size_t)dswarp::workspace_doubles(dswarp::make_plan(n_in, n_out)) * 8, (nx + no) * 8, 0));
+    return staged(c, {{8, nx, x, nullptr}, {8, no, nullptr, out}}, [&](void* const* d) {
+        return allpass_launch<double>(c, k, (const double*)d[0], n_ch, 1, (double*)d[1]);
+    });
+}
+
+extern "C" int ds_allpass_table_dev(ds_ctx* c, const float* x, int n_ch, int64_t ldx, int64_t n_in, double p, double q,
+                                    const double* row0, const double* col0, int64_t n_out, double* out) {
+    AllpassCall k{"ds_allpass_table_dev", n_in, n_ch, p, q, row0, col0, n_out, out};
+    CHK(allpass_check(c, k, x));
+    if (ldx < n_in) return fail(c, DS_ERR_ARG, "ds_allpass_table_dev: ldx < n_in");
+    const size_t no = (size_t)n_out * n_ch;
+    CHK(mem_check(c, k.who, (size_t)dswarp::workspace_doubles(dswarp::make_plan(n_in, n_out)) * 8, no * 8, 0));
+    return staged(c, {{8, no, nullptr, out}}, [&](void* const* d) {
+        return allpass_launch<float>(c, k, x, 1, ldx, (double*)d[0]);
     });
 }
 

@@ -72,3 +72,22 @@ DS_HD inline bool lpc_shape_unsupported(int64_t window, int64_t order, int64_t p
 DS_HD inline bool lpc_work_too_large(int64_t pairs, int64_t window, int64_t order) {
     return (double)pairs * (double)window * (double)(order + 1) > kLpcMaxWork;
 }
+
+// The all-pass table of warp and laguerre (kernels_warp.hpp, warp_plan.hpp): n_in x n_out cells, each depending on three
+// neighbours, swept tile anti-diagonal by tile anti-diagonal -- ceil((n_in - 1) / 1024) + ceil((n_out - 1) / 256) - 1 launches
+// one after the other, whatever the channel count.  The side bound is the ceiling the feature was given, 2^17 samples (the
+// longest room responses in practice): a two-channel warp of that length takes 79 ms on the device, far
+// inside the two seconds one call may take, so no smaller power of two is needed.  Channels come in groups of 4, each group
+// a further workgroup per tile that repeats the table; the work of a call is counted as n_in x n_out x groups table cells.
+// With every compute unit busy (64 channels x 32768 samples: 512 workgroups in the widest launch) the kernel sustains
+// 6.6e11 cells per second; the bound is that rate times two seconds, rounded down.  grid.y carries the groups: at most
+// 65536 channels.  Beyond any of these the entries answer DS_ERR_UNSUP.
+constexpr int64_t kWarpMaxSide = (int64_t)1 << 17;
+constexpr int kWarpMaxChannels = 65536;
+constexpr double kWarpMaxWork = 1e12;
+DS_HD inline bool warp_shape_unsupported(int64_t n_in, int64_t n_out, int64_t n_ch) {
+    return n_in > kWarpMaxSide || n_out > kWarpMaxSide || n_ch > kWarpMaxChannels;
+}
+DS_HD inline bool warp_work_too_large(int64_t n_in, int64_t n_out, int64_t groups) {
+    return (double)n_in * (double)n_out * (double)groups > kWarpMaxWork;
+}

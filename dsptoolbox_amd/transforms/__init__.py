@@ -2,7 +2,8 @@
 row 1) and the STFT consumers log_mel_spectrogram / mfcc / chroma_stft (:113-203, :335-441, :589-684,
 row 4) on the device, and hilbert / cepstrum / from_complex_cepstrum (:59-110, :763-809) on the float64 any-length
 transform (ds_hilbert, ds_cepstrum, ds_from_cepstrum), and lpc (:1199-1283) on the linear-prediction kernels (ds_lpc,
-ds_lpc_synth).  Same signature, parameter handling and quirks as the reference;
+ds_lpc_synth), and warp / laguerre / warp_filter (:955-1196, transforms/_transforms.py:386-463) on the all-pass table
+kernel (ds_allpass_table).  Same signature, parameter handling and quirks as the reference;
 the frame-wise inverse FFTs and the windowed overlap-add with the squared-window envelope
 (standard/_framed_signal_representation.py:70-137) run in the HIP library (ds_istft).  The continuous wavelet
 transform cwt with Wavelet / MorletWavelet (:687-760, transforms/_transforms.py:29-301) lives in _wavelets.py.
@@ -14,13 +15,14 @@ import numpy as np
 from scipy.signal import get_window
 
 from .. import backend
+from ..classes.filter import Filter
 from ..classes.multibandsignal import MultiBandSignal
 from ..classes.signal import Signal
-from ..standard.enums import Window
+from ..standard.enums import FilterCoefficientsType, Window
 from ._wavelets import MorletWavelet, Wavelet, cwt  # noqa: F401
 
 __all__ = ["istft", "mel_filterbank", "log_mel_spectrogram", "mfcc", "chroma_stft", "cwt", "Wavelet", "MorletWavelet",
-           "dft", "hilbert", "cepstrum", "from_complex_cepstrum", "lpc"]
+           "dft", "hilbert", "cepstrum", "from_complex_cepstrum", "lpc", "warp", "laguerre", "warp_filter"]
 
 
 def dft(signal: Signal, frequency_vector_hz) -> np.ndarray:
@@ -292,3 +294,90 @@ def lpc(signal: Signal, order: int, window_length_samples: int, synthesize_encod
             sources[:, n_window, channel] = np.random.normal(0.0, var[n_window, channel] ** 0.5, L)
     y = backend.lpc_synthesize(a, sources, window, hop, n)
     return Signal.from_time_data(y, signal.sampling_rate_hz)
+
+
+def _get_warping_factor(warping_factor: float | str, fs_hz: int) -> float:
+    """A float is asserted to lie in ]-1, 1[; "bark" / "erb" give the factor of the bilinear approximation of that scale
+    after Smith & Abel (1999), eq. 26 and 30, and "bark-" / "erb-" its negative, for de-warping.  Any other string is
+    a ValueError, any other type (an int, a numpy float) a TypeError.  As in the reference the formulas receive the
+    sampling rate in Hz although they were fitted to kHz: "bark" is about -0.876 and "erb" about -0.777 at every audio
+    rate."""
+    if type(warping_factor) is float:
+        assert np.abs(warping_factor) < 1.0, "Warping factor has to be in ]-1; 1["
+        return warping_factor
+    if type(warping_factor) is not str:
+        raise TypeError("Invalid type for warping factor")
+    name = warping_factor.lower()
+    sign = -1.0 if name[-1:] in ("k", "b") else 1.0  # a trailing "-" (any other last character) inverts
+    if "bark" in name:
+        return sign * (1.0674 * (2.0 / np.pi * np.arctan(0.06583 * fs_hz)) ** 0.5 - 0.1916)
+    if "erb" in name:
+        return sign * (0.7446 * (2.0 / np.pi * np.arctan(0.1418 * fs_hz)) ** 0.5 + 0.03237)
+    raise ValueError("Warping factor approximation is not supported")
+
+
+def _find_ir_start(ir: np.ndarray, threshold_dbfs: float = -20) -> int:
+    """room_acoustics/_room_acoustics.py:88-115: walking back from the peak of a 1-D response, the first sample whose
+    magnitude is below the peak by the threshold (0 if there is none)."""
+    mag = np.abs(ir)
+    peak = int(np.argmax(mag))
+    below = np.nonzero(mag[:peak + 1] < mag[peak] * 10 ** (-np.abs(threshold_dbfs) / 20.0))[0]
+    return int(below[-1]) if len(below) else 0
+
+
+def warp(ir: Signal, warping_factor: float | str, shift_ir: bool, total_length: int | None = None):
+    """The frequency-warped impulse response (a warped FIR filter, Haermae et al. 2000): sample i of every channel
+    weights the all-pass (z^-1 - lambda) / (1 - lambda z^-1) applied i times to a unit pulse.  A negative factor
+    pre-warps (more resolution at low frequencies), the same positive factor de-warps.  "bark", "erb" take the factor
+    from the sampling rate (see _get_warping_factor; "bark-", "erb-" de-warp) and the factor is returned beside the
+    Signal.  `shift_ir` rolls every channel so that the sample before it first comes within 20 dB of its peak is
+    first (the operation is not shift-invariant).  `total_length` truncates the input, and with it the output.
+
+    The table of all-pass responses and its contraction with the samples run on the device in float64, one launch per
+    anti-diagonal of tiles; nothing is printed.  The samples of a device-resident signal are read where they lie unless
+    `shift_ir` is set: the roll is done on the host and materialises them there.  NotImplementedError beyond
+    backend.WARP_MAX_SIDE samples."""
+    approximation = type(warping_factor) is str
+    factor = _get_warping_factor(warping_factor, ir.sampling_rate_hz)
+    n = len(ir) if total_length is None else len(range(len(ir))[:total_length])
+    backend._warp_check(n, n, ir.number_of_channels)
+    if ir.on_device and not shift_ir and not ir.is_complex_signal:
+        from .._lib import DevicePlanar
+        dev = ir.device_samples
+        samples = dev if n == dev.n_samples else DevicePlanar(dev.owner, dev.n_ch, n, dev.ld, dev.offset_bytes)
+    else:
+        samples = ir.time_data.copy()
+        if shift_ir:
+            for ch in range(ir.number_of_channels):
+                samples[:, ch] = np.roll(samples[:, ch], -_find_ir_start(samples[:, ch], -20))
+        samples = samples[:n]
+    warped = ir.copy_with_new_time_data(backend.warp_time_series(samples, factor))
+    return (warped, factor) if approximation else warped
+
+
+def laguerre(signal: Signal, warping_factor: float) -> Signal:
+    """The discrete Laguerre transform in the time domain (Zoelzer, DAFX, chapter 11): the same frequency mapping as
+    `warp`, with orthonormal basis functions.  Applying it with `warping_factor` and then with `-warping_factor`
+    undoes it up to the truncation to the signal's length.  The table of basis functions and its contraction with the
+    samples run on the device in float64; the samples of a device-resident signal are read where they lie.
+    AssertionError for |warping_factor| >= 1, NotImplementedError beyond backend.WARP_MAX_SIDE samples."""
+    assert np.abs(warping_factor) < 1.0, "Warping factor cannot be larger than 1."
+    backend._warp_check(len(signal), len(signal), signal.number_of_channels)
+    samples = signal.device_samples if signal.on_device and not signal.is_complex_signal else signal.time_data
+    return signal.copy_with_new_time_data(backend.laguerre_transform(samples, float(warping_factor)))
+
+
+def warp_filter(filter: Filter, warping_factor: float) -> Filter:
+    """The filter with z^-1 replaced by (z^-1 - lambda) / (1 - lambda z^-1): every pole and zero r moves to
+    (lambda + r) / (1 + lambda r), and the shorter of the two lists is filled up with `warping_factor`.  The gain is
+    kept.  Host arithmetic on zpk; the result is Filter.from_zpk, so the stable-poles rule of Filter applies."""
+    assert abs(warping_factor) < 1.0, "Warping factor must be less than 1."
+    z, p, k = filter.get_coefficients(FilterCoefficientsType.Zpk)
+    z, p = np.atleast_1d(z), np.atleast_1d(p)
+    z, p = (warping_factor + z) / (1 + warping_factor * z), (warping_factor + p) / (1 + warping_factor * p)
+    fill = [warping_factor] * abs(len(p) - len(z))
+    if len(p) > len(z):
+        z = np.hstack([z, fill])
+    elif len(z) > len(p):
+        p = np.hstack([p, fill])
+    return Filter.from_zpk(z, p, k, filter.sampling_rate_hz)

@@ -538,6 +538,25 @@ int ds_levinson(ds_ctx* ctx, const double* r, int order, int64_t n_cols, double*
 int ds_lpc_synth(ds_ctx* ctx, const double* a, const double* sources, const double* window, int window_length,
                  int64_t n_frames, int n_ch, int64_t hop, int order, int64_t n_out, double* y);
 
+/* ---- the all-pass table of frequency warping and the Laguerre transform (csrc/kernels_warp.hpp, csrc/warp_plan.hpp):
+ * transforms.warp and transforms.laguerre of the reference (transforms/transforms.py:955-1130,
+ * transforms/_transforms.py:386-428), float64 on the device.  With a given first row row0[n_out] and first column
+ * col0[n_in] (host, float64; c[0][0] is taken from col0[0]) the table is
+ *   c[i][j] = p c[i-1][j] + c[i-1][j-1] + q c[i][j-1]   (i, j >= 1),     out[j][ch] = sum_i c[i][j] x[i][ch].
+ *   warp(lambda):    p = -lambda, q = lambda, row0 = the unit pulse, col0[i] = (-lambda)^i; i is the input sample.
+ *   laguerre(f):     p = -f, q = f, col0[i] = sqrt(1 - f^2) (-f)^i, row0[j] = sqrt(1 - f^2) f^j.
+ * x is host (n_in, n_ch) float64, or for the _dev entry planar fp32 on the device, channel ch at x_dev + ch ldx, widened on
+ * load; out is host (n_out, n_ch) float64.  n_in and n_out are independent.  The table is computed tile by tile, one launch
+ * per tile anti-diagonal on the context's stream, and summed in a fixed order: repeats give the same bits, and with
+ * p = q = 0 and identity boundaries out equals x bit for bit.
+ * Bounds: sizes >= 1 and finite p, q (DS_ERR_ARG); n_in, n_out <= 131072, n_ch <= 65536 and n_in x n_out x ceil(n_ch / 4)
+ *   within the work bound of csrc/size_guards.hpp (DS_ERR_UNSUP); DS_ERR_NOMEM, before anything is uploaded, when the
+ *   device has not the memory free.                                                                                    */
+int ds_allpass_table(ds_ctx* ctx, const double* x, int64_t n_in, int n_ch, double p, double q, const double* row0,
+                     const double* col0, int64_t n_out, double* out);
+int ds_allpass_table_dev(ds_ctx* ctx, const float* x_dev, int n_ch, int64_t ldx, int64_t n_in, double p, double q,
+                         const double* row0, const double* col0, int64_t n_out, double* out);
+
 /* ---- block-streaming FIR classes with device-resident state ------------------------------
  * One process_block of the reference's real-time classes (classes/fir_filter_realtime.py:75-335),
  * executed literally on buffers that stay on the device between calls; per call only the block
