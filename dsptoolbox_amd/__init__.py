@@ -2,7 +2,7 @@
 spectral hot path (Welch/H1-H3, STFT, CSM, spectral deconvolution, FIR filter
 banks) behind the reference's Signal / Filter / FilterBank API."""
 
-from . import beamforming, filterbanks, room_acoustics, standard, tools, transfer_functions, transforms
+from . import beamforming, distances, filterbanks, room_acoustics, standard, tools, transfer_functions, transforms
 from .classes import Filter, FilterBank, ImpulseResponse, MultiBandSignal, Signal, Spectrum
 from .standard.enums import (BiquadEqType, FilterBankMode, FilterCoefficientsType, FilterPassType,
                              FrequencySpacing, IirDesignMethod, SpectrumMethod, SpectrumScaling, SpectrumType, Window)
@@ -13,5 +13,5 @@ __version__ = "0.1.0"
 __all__ = ["Signal", "ImpulseResponse", "Spectrum", "Filter", "FilterBank", "MultiBandSignal",
            "SpectrumMethod", "SpectrumScaling", "SpectrumType", "FrequencySpacing", "Window", "FilterBankMode",
            "FilterPassType", "FilterCoefficientsType", "IirDesignMethod", "BiquadEqType", "TransferFunctionType", "SmoothingDomain",
-           "transfer_functions", "transforms", "room_acoustics", "beamforming", "filterbanks", "tools", "standard",
+           "transfer_functions", "transforms", "room_acoustics", "beamforming", "distances", "filterbanks", "tools", "standard",
            "fractional_delay"]

@@ -25,6 +25,7 @@ NO_SCRATCH = [
     "fir16k5k_firILb1E", "fir4k5k_firILi1E", "fir4k5k_firILi2E", "fir4k6k_fir3ILi0E", "deconv8k10k_deconv_p", "k_csm_gemm64",
     "k_bf_eigh", "k_bf_project", "k_bf_cleansc",
     "k_iir_group", "k_iir_carry", "k_iir_apply",
+    "k_ciir_group", "k_ciir_carry", "k_ciir_apply", "k_pair_partial", "k_pair_final", "k_fw_frame", "k_fw_reduce", "k_fw_mean",
     "k_delay_sum",
     "k_cwt_inv", "k_cwt_squeeze",
     "k_to_log", "k_smooth", "k_to_lin", "k_polar", "k_unwrap", "k_recombine",

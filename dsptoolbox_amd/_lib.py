@@ -115,6 +115,16 @@ SIGNATURES = {
                              C.c_void_p, C.c_void_p]),
     "ds_iir_sos_dev": (C.c_int, [ctx_p, C.c_void_p, C.c_int, i64, i64, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
                                  C.c_int, C.c_void_p, i64, C.c_void_p]),
+    "ds_iir_sos_c128": (C.c_int, [ctx_p, C.c_void_p, C.c_int, i64, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                  C.c_void_p, C.c_void_p]),
+    "ds_pair_moments": (C.c_int, [ctx_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, i64, C.c_void_p, C.c_void_p]),
+    "ds_pair_moments_dev": (C.c_int, [ctx_p, C.c_void_p, C.c_int, i64, C.c_void_p, C.c_int, i64, i64, C.c_void_p,
+                                      C.c_void_p]),
+    "ds_fw_snr_seg": (C.c_int, [ctx_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, i64, C.c_void_p, C.c_int, C.c_int,
+                                C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int, C.c_void_p]),
+    "ds_fw_snr_seg_dev": (C.c_int, [ctx_p, C.c_void_p, C.c_int, i64, C.c_void_p, C.c_int, i64, i64, C.c_void_p, C.c_int,
+                                    C.c_int, C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int,
+                                    C.c_void_p]),
     "ds_delay_sum": (C.c_int, [ctx_p, C.c_void_p, C.c_int, i64, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                C.c_void_p, C.c_void_p, C.c_int, C.c_double, i64, C.c_void_p, C.c_void_p]),
     "ds_delay_sum_dev": (C.c_int, [ctx_p, C.c_void_p, C.c_int, i64, C.c_void_p, C.c_int, C.c_int, C.c_void_p,

@@ -1251,6 +1251,123 @@ def iir_sos_filter_device(x_dev: DevicePlanar, sos_list, mode: int):
     return _bank_outputs(d_y, n_ch, n, n_out, mode)
 
 
+# ---- IIR filtering with complex coefficients (ds_iir_sos_c128, csrc/kernels_ciir.hpp) -------------------------------
+CIIR_MAX_SEC = 16  # sections of one complex cascade on the device (CIIR_MAX_SEC of the kernels; DS_ERR_UNSUP above)
+
+
+def iir_sos_filter_complex(x, sos_list, zi=None, real_only: bool = False):
+    """sosfilt of REAL x (N, C) through K cascades of second-order sections with complex coefficients, every filter on
+    every channel (the recursion in complex float64 on the device) -> (K, N, C) complex128, or float64 (the real part;
+    the imaginary plane is then never written) with real_only.  zi (K, n_max, 2, C) complex gives the initial state;
+    then (y, zf) is returned, zf in the same layout."""
+    if np.iscomplexobj(x):
+        raise NotImplementedError("complex input samples are not run through the device recursion (its input is real)")
+    xa = np.ascontiguousarray(np.asarray(x, dtype=np.float64))
+    if xa.ndim == 1:
+        xa = xa[:, None]
+    n_max = max(np.atleast_2d(s).shape[0] for s in sos_list)
+    if n_max > CIIR_MAX_SEC:
+        raise NotImplementedError(f"cascades of more than {CIIR_MAX_SEC} complex second-order sections are not run on "
+                                  f"the device (got {n_max}); split the filter")
+    sos = _complex_sos_stack(sos_list)
+    k = sos.shape[0]
+    n, n_ch = xa.shape
+    y_re = np.empty((k, n, n_ch), dtype=np.float64)
+    y_im = None if real_only else np.empty((k, n, n_ch), dtype=np.float64)
+    zf = None
+    if zi is not None:
+        zi = np.ascontiguousarray(zi, dtype=np.complex128)
+        assert zi.shape == (k, n_max, 2, n_ch), "zi must be (filters, sections, 2, channels)"
+        zf = np.empty_like(zi)
+    ctx = get_context()
+    ctx.check(ctx.lib.ds_iir_sos_c128(ctx.handle, _ptr(xa), n_ch, n, _ptr(sos), k, n_max,
+                                      None if zi is None else _ptr(zi), _ptr(y_re),
+                                      None if y_im is None else _ptr(y_im), None if zf is None else _ptr(zf)),
+              "ds_iir_sos_c128")
+    y = y_re if real_only else y_re + 1j * y_im
+    return y if zi is None else (y, zf)
+
+
+# ---- sums over a pair of signals (ds_pair_moments, csrc/kernels_dist.hpp) -------------------------------------------
+PAIR_SPAN = 4096  # samples one workgroup of the reduction sums (SPAN of the kernels)
+
+
+def pair_moments(a, b, par=None) -> np.ndarray:
+    """Per channel of a (N, Ca) and b (N, Cb) float64 (one side may have a single channel, paired with every channel of
+    the other): sum (a - mu_a)^2, sum (b - mu_b)^2, sum a b, sum a, sum b, sum (alpha a - b)^2 as (C, 6) float64, in
+    float64 and a fixed order on the device.  par (C, 3) holds alpha, mu_a, mu_b per channel (None: zeros)."""
+    a = np.ascontiguousarray(np.asarray(a, dtype=np.float64))
+    b = np.ascontiguousarray(np.asarray(b, dtype=np.float64))
+    a = a[:, None] if a.ndim == 1 else a
+    b = b[:, None] if b.ndim == 1 else b
+    assert a.shape[0] == b.shape[0], "Length of signals do not match"
+    n_ch = max(a.shape[1], b.shape[1])
+    out = np.empty((n_ch, 6), dtype=np.float64)
+    if par is not None:
+        par = np.ascontiguousarray(par, dtype=np.float64)
+        assert par.shape == (n_ch, 3), "par must be (channels, 3)"
+    ctx = get_context()
+    ctx.check(ctx.lib.ds_pair_moments(ctx.handle, _ptr(a), a.shape[1], _ptr(b), b.shape[1], a.shape[0],
+                                      None if par is None else _ptr(par), _ptr(out)), "ds_pair_moments")
+    return out
+
+
+def pair_moments_device(a_dev: DevicePlanar, b_dev: DevicePlanar, par=None) -> np.ndarray:
+    """pair_moments over device-resident fp32 planar signals (ds_pair_moments_dev): only the sums come down."""
+    assert a_dev.n_samples == b_dev.n_samples, "Length of signals do not match"
+    n_ch = max(a_dev.n_ch, b_dev.n_ch)
+    out = np.empty((n_ch, 6), dtype=np.float64)
+    if par is not None:
+        par = np.ascontiguousarray(par, dtype=np.float64)
+        assert par.shape == (n_ch, 3), "par must be (channels, 3)"
+    ctx = a_dev.ctx
+    ctx.check(ctx.lib.ds_pair_moments_dev(ctx.handle, C.c_void_p(a_dev.ptr), a_dev.n_ch, a_dev.ld, C.c_void_p(b_dev.ptr),
+                                          b_dev.n_ch, b_dev.ld, a_dev.n_samples, None if par is None else _ptr(par),
+                                          _ptr(out)), "ds_pair_moments_dev")
+    return out
+
+
+# ---- frequency-weighted segmental SNR (ds_fw_snr_seg, csrc/kernels_dist.hpp) ----------------------------------------
+FW_SNR_CHUNK_FRAMES = 32  # frames transformed and reduced per pass over the workspace (a test lowers it)
+
+
+def _complex_sos_stack(sos_list) -> np.ndarray:
+    n_max = max(np.atleast_2d(s).shape[0] for s in sos_list)
+    sos = np.tile(_IDENTITY_SECTION.astype(np.complex128), (len(sos_list), n_max, 1))
+    for k, s in enumerate(sos_list):
+        s = np.atleast_2d(np.asarray(s, dtype=np.complex128))
+        sos[k, :s.shape[0]] = s
+    return sos
+
+
+def fw_snr_seg(x, xhat, sos_list, window, snr_range_db, gamma: float) -> np.ndarray:
+    """The frequency-weighted segmental SNR of xhat (N, C) against x (N, C) or (N, 1), per channel of xhat, in one
+    device call: both through the bank of complex sos filters (real parts), frames of len(window) samples at half
+    overlap, one float64 transform per (frame, band, channel), the weighted log ratio reduced per frame, clipped
+    and averaged.  x and xhat are float64 arrays or, both, DevicePlanar (fp32, resident)."""
+    sos = _complex_sos_stack(sos_list)
+    window = np.ascontiguousarray(window, dtype=np.float64)
+    lo, hi = float(snr_range_db[0]), float(snr_range_db[1])
+    tail = (_ptr(sos), sos.shape[0], sos.shape[1], _ptr(window), len(window), lo, hi, float(gamma), int(FW_SNR_CHUNK_FRAMES))
+    if isinstance(x, DevicePlanar):
+        assert isinstance(xhat, DevicePlanar) and x.n_samples == xhat.n_samples, "Signal lengths do not match"
+        out = np.empty(xhat.n_ch, dtype=np.float64)
+        ctx = x.ctx
+        ctx.check(ctx.lib.ds_fw_snr_seg_dev(ctx.handle, C.c_void_p(x.ptr), x.n_ch, x.ld, C.c_void_p(xhat.ptr), xhat.n_ch,
+                                            xhat.ld, x.n_samples, *tail, _ptr(out)), "ds_fw_snr_seg_dev")
+        return out
+    x = np.ascontiguousarray(np.asarray(x, dtype=np.float64))
+    xhat = np.ascontiguousarray(np.asarray(xhat, dtype=np.float64))
+    x = x[:, None] if x.ndim == 1 else x
+    xhat = xhat[:, None] if xhat.ndim == 1 else xhat
+    assert x.shape[0] == xhat.shape[0], "Signal lengths do not match"
+    out = np.empty(xhat.shape[1], dtype=np.float64)
+    ctx = get_context()
+    ctx.check(ctx.lib.ds_fw_snr_seg(ctx.handle, _ptr(x), x.shape[1], _ptr(xhat), xhat.shape[1], x.shape[0], *tail,
+                                    _ptr(out)), "ds_fw_snr_seg")
+    return out
+
+
 def _ba_section(b, a) -> np.ndarray:
     """A ba filter of order <= 2 as one second-order section (lfilter normalises by a[0] as the section does)."""
     b = np.asarray(b, dtype=np.float64)

@@ -3,8 +3,9 @@ fir_filter :189-235, from_ba / from_sos / from_zpk :237-300, initialize_zi :331-
 :485-600, filter_signal :648-743, get_ir :818-860, get_transfer_function :862-900, get_coefficients :927-966).
 FIR filtering runs on the device as FFT block convolution (dsptoolbox_amd.backend.fir_filter_bank), IIR
 filtering -- sos, zpk (converted to sos) and ba filters of order <= 2 -- as a time-parallel float64 recursion
-(backend.iir_sos_filter), both with filter state (zi) and zero-phase filtering.  Design and conversion stay
-scipy on the host.  A recursive filter with a pole on or outside the unit circle raises NotImplementedError
+(backend.iir_sos_filter), both with filter state (zi) and zero-phase filtering; sos filters with complex
+coefficients as the same recursion in complex float64 (backend.iir_sos_filter_complex), with filter state.
+Design and conversion stay scipy on the host.  A recursive filter with a pole on or outside the unit circle raises NotImplementedError
 when it is built: the device's carry over time holds only for stable filters."""
 
 from copy import deepcopy
@@ -257,15 +258,19 @@ class Filter:
 
     def _device_sections(self) -> np.ndarray:
         """The filter as second-order sections for the device recursion: its own sos, or a ba filter of order <= 2
-        as one section.  Complex coefficients and higher-order ba filters raise NotImplementedError."""
+        as one section.  Complex sos come back as complex128 (the complex recursion); complex ba coefficients and
+        higher-order ba filters raise NotImplementedError."""
         if self.has_sos:
             if np.iscomplexobj(self.sos):
-                raise NotImplementedError("IIR filters with complex coefficients are not run on the device "
-                                          "(the recursion is real float64)")
+                if self.sos.shape[0] > backend.CIIR_MAX_SEC:
+                    raise NotImplementedError(
+                        f"complex sos filters of more than {backend.CIIR_MAX_SEC} sections are not run on the device "
+                        f"(got {self.sos.shape[0]})")
+                return np.asarray(self.sos, dtype=np.complex128)
             return np.asarray(self.sos, dtype=np.float64)
         if np.iscomplexobj(self.ba[0]) or np.iscomplexobj(self.ba[1]):
-            raise NotImplementedError("IIR filters with complex coefficients are not run on the device "
-                                      "(the recursion is real float64)")
+            raise NotImplementedError("IIR ba filters with complex coefficients are not run on the device "
+                                      "(the complex recursion takes second-order sections: pass them as sos)")
         return backend._ba_section(self.ba[0], self.ba[1])
 
     def filter_signal(self, signal: Signal, channels=None, activate_zi: bool = False,
@@ -327,6 +332,8 @@ class Filter:
     def _filter_signal_iir(self, signal: Signal, channels, activate_zi: bool, zero_phase: bool,
                            sections: np.ndarray) -> Signal:
         """The IIR branch of filter_signal: sosfilt / lfilter (filter_helpers.py:207-280, :288-382) on the device."""
+        if np.iscomplexobj(sections):
+            return self._filter_signal_complex(signal, channels, activate_zi, zero_phase, sections)
         every_channel = np.array_equal(channels, np.arange(signal.number_of_channels))
         if signal.on_device and not activate_zi and not zero_phase and every_channel:
             # device-resident samples, every channel, no state: read and written in HBM
@@ -357,6 +364,31 @@ class Filter:
             # :377-382 return `zi`): (K, 2, C) for sos, (order, C) for ba -- the next call re-initialises unless
             # its first dimension equals the channel count, exactly as there
             self.zi = zi
+        return signal.copy_with_new_time_data(new_time_data)
+
+    def _filter_signal_complex(self, signal: Signal, channels, activate_zi: bool, zero_phase: bool,
+                               sections: np.ndarray) -> Signal:
+        """sos filters with complex coefficients (filter_helpers.py:207-285 with a complex sos array): real samples
+        in, complex samples out -- the imaginary part lands in Signal.time_data_imaginary."""
+        if zero_phase:
+            raise NotImplementedError("zero-phase filtering with complex sections is not run on the device (its "
+                                      "second pass would take complex input samples)")
+        if signal.is_complex_signal:
+            raise NotImplementedError("complex input samples are not run through the device recursion (its input "
+                                      "is real)")
+        x = signal.time_data[:, channels]
+        if activate_zi:
+            zi = np.moveaxis(np.asarray(self.zi, dtype=np.complex128), 0, -1)  # (K, 2, C)
+            y, zf = backend.iir_sos_filter_complex(x, [sections], zi=zi[:, :, channels][None])
+            y, zi[:, :, channels] = y[0], zf[0]
+        else:
+            y = backend.iir_sos_filter_complex(x, [sections])[0]
+        if self.warning_if_complex:
+            warn("Filter output is complex. Imaginary part is saved in Signal as time_data_imaginary")
+        new_time_data = signal.time_data.astype(np.complex128)
+        new_time_data[:, channels] = y
+        if activate_zi:
+            self.zi = zi  # (the unpacked (K, 2, C) array, as in the real branch)
         return signal.copy_with_new_time_data(new_time_data)
 
     def get_ir(self, length_samples: int, zero_phase: bool = False):

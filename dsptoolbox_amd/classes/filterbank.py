@@ -4,7 +4,8 @@ filter_multiband_signal :479-532, get_ir :534-613, get_transfer_function :615-65
 The FIR filters of a bank are applied in ONE device call (every input block is
 transformed once and all band filters are applied on chip), its IIR filters in
 another (one float64 recursion per filter and channel, every filter of a channel
-from one read of the samples); a bank that mixes both composes the two calls."""
+from one read of the samples); a bank that mixes both composes the two calls.  A bank of sos filters with
+complex coefficients (the gammatone bank) runs in Parallel mode, in one call of the complex recursion."""
 
 from copy import deepcopy
 from warnings import warn
@@ -116,6 +117,27 @@ class FilterBank:
                 self.initialize_zi(signal.number_of_channels)
         if mode not in (FilterBankMode.Parallel, FilterBankMode.Sequential, FilterBankMode.Summed):
             raise ValueError("Invalid filter bank apply mode")
+        if any(self._is_complex(f) for f in self.filters):
+            if mode != FilterBankMode.Parallel:
+                raise NotImplementedError(
+                    "Summed and Sequential filtering with a bank that holds a filter with complex coefficients is not "
+                    "run on the device (the complex recursion takes real input and gives every band on its own)")
+            if zero_phase:
+                raise NotImplementedError("zero-phase filtering with complex sections is not run on the device")
+            if not all(self._is_complex(f) for f in self.filters):
+                raise NotImplementedError("banks mixing filters with complex coefficients and other filters (real "
+                                          "recursive or FIR) are not run on the device; split the bank")
+            if signal.is_complex_signal:
+                raise NotImplementedError("complex input samples are not run through the device recursion (its input "
+                                          "is real)")
+            if not activate_zi:
+                # the whole bank in one call, every band from one read of the samples
+                y = backend.iir_sos_filter_complex(signal.time_data, [f._device_sections() for f in self.filters])
+                for f in self.filters:
+                    if f.warning_if_complex:
+                        warn("Filter output is complex. Imaginary part is saved in Signal as time_data_imaginary")
+                return MultiBandSignal([signal.copy_with_new_time_data(np.ascontiguousarray(b)) for b in y],
+                                       same_sampling_rate=self.same_sampling_rate)
         if activate_zi or zero_phase:
             # per-filter state / two-pass filtering: the reference's own loop
             # (filter_helpers.py:385-451), one device call (or two) per filter
@@ -183,6 +205,10 @@ class FilterBank:
             for i, n in enumerate(idx):
                 bands[n] = signal.copy_with_new_time_data(np.ascontiguousarray(y[i]))
         return MultiBandSignal(bands, same_sampling_rate=self.same_sampling_rate)
+
+    @staticmethod
+    def _is_complex(f: Filter) -> bool:
+        return f.has_sos and np.iscomplexobj(f.sos)
 
     def filter_multiband_signal(self, mbsignal: MultiBandSignal, activate_zi: bool = False,
                                 zero_phase: bool = False) -> MultiBandSignal:

@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
+#include <complex>
 #include <cstdio>
 #include <cstring>
 #include <map>
@@ -41,6 +42,8 @@
 #include "kernels_freqz.hpp"
 #include "kernels_beamform.hpp"
 #include "kernels_iir.hpp"
+#include "kernels_ciir.hpp"
+#include "kernels_dist.hpp"
 #include "kernels_delay.hpp"
 #include "kernels_cwt.hpp"
 #include "kernels_smooth.hpp"
@@ -3425,6 +3428,221 @@ extern "C" int ds_iir_sos(ds_ctx* c, const double* x, int n_ch, int64_t n_sample
     });
 }
 
+// ---- IIR filtering with complex coefficients (kernels_ciir.hpp): complex float64 recursion, real samples ------------
+typedef std::complex<double> cplx;
+
+static void cmat_mul(const std::vector<cplx>& a, const std::vector<cplx>& b, int d, std::vector<cplx>& out) {
+    std::vector<cplx> r((size_t)d * d, cplx(0.0, 0.0));
+    for (int i = 0; i < d; ++i)
+        for (int k = 0; k < d; ++k) {
+            const cplx v = a[(size_t)i * d + k];
+            if (v == cplx(0.0, 0.0)) continue;
+            for (int j = 0; j < d; ++j) r[(size_t)i * d + j] += v * b[(size_t)k * d + j];
+        }
+    out.swap(r);
+}
+
+static void cmat_pow2(std::vector<cplx>& m, int d, int log2_exp) {  // m <- m^(2^log2_exp)
+    for (int i = 0; i < log2_exp; ++i) cmat_mul(m, m, d, m);
+}
+
+// a d x d complex matrix as the kernels read it: the real plane, then the imaginary plane
+static void cmat_planes(const std::vector<cplx>& m, int d, double* dst) {
+    for (size_t i = 0; i < (size_t)d * d; ++i) {
+        dst[i] = m[i].real();
+        dst[(size_t)d * d + i] = m[i].imag();
+    }
+}
+
+// sos [n_filt][n_sec][6] complex -> coef [n_filt][n_sec][5] complex (b0 b1 b2 a1 a2 / a0), phi = A^L, phig = A^(L B),
+// each [n_filt][2][D][D]
+static bool ciir_tables(const double* sos, int n_filt, int n_sec, std::vector<double>& coef, std::vector<double>& phi,
+                        std::vector<double>& phig) {
+    const int d = 2 * n_sec;
+    coef.assign((size_t)n_filt * n_sec * 10, 0.0);
+    phi.assign((size_t)n_filt * 2 * d * d, 0.0);
+    phig.assign((size_t)n_filt * 2 * d * d, 0.0);
+    for (int f = 0; f < n_filt; ++f) {
+        std::vector<cplx> cf((size_t)n_sec * 5);
+        for (int k = 0; k < n_sec; ++k) {
+            const double* s = sos + ((size_t)f * n_sec + k) * 12;
+            for (int i = 0; i < 12; ++i)
+                if (!std::isfinite(s[i])) return false;
+            const cplx a0(s[6], s[7]);
+            if (a0 == cplx(0.0, 0.0)) return false;
+            for (int i = 0; i < 5; ++i) {
+                const int col = i < 3 ? i : i + 1;
+                const cplx v = cplx(s[2 * col], s[2 * col + 1]) / a0;
+                cf[5 * k + i] = v;
+                coef[((size_t)f * n_sec + k) * 10 + 2 * i] = v.real();
+                coef[((size_t)f * n_sec + k) * 10 + 2 * i + 1] = v.imag();
+            }
+        }
+        // column j of A: one zero-input step of the cascade from the unit state e_j
+        std::vector<cplx> a((size_t)d * d, cplx(0.0, 0.0));
+        for (int j = 0; j < d; ++j) {
+            cplx in(0.0, 0.0);
+            for (int k = 0; k < n_sec; ++k) {
+                const cplx z1 = (j == 2 * k) ? 1.0 : 0.0, z2 = (j == 2 * k + 1) ? 1.0 : 0.0;
+                const cplx y = cf[5 * k] * in + z1;
+                a[(size_t)(2 * k) * d + j] = cf[5 * k + 1] * in - cf[5 * k + 3] * y + z2;
+                a[(size_t)(2 * k + 1) * d + j] = cf[5 * k + 2] * in - cf[5 * k + 4] * y;
+                in = y;
+            }
+        }
+        static_assert(ciir::L == 32 && ciir::B == 64, "the squarings below assume L = 2^5, B = 2^6");
+        cmat_pow2(a, d, 5);
+        cmat_planes(a, d, phi.data() + (size_t)f * 2 * d * d);
+        cmat_pow2(a, d, 6);
+        cmat_planes(a, d, phig.data() + (size_t)f * 2 * d * d);
+    }
+    return true;
+}
+
+// Everything ds_iir_sos_c128 and a device-pointer caller share.
+struct CiirCall {
+    const char* who;
+    int n_ch;
+    int64_t n_samples;
+    const double* sos;  // host [n_filt][n_sec][6] complex128
+    int n_filt, n_sec;
+};
+
+// shape and bounds; nothing touches the device
+static int ciir_check(ds_ctx* c, const CiirCall& q, const void* x, const void* yr) {
+    if (!c || !x || !yr || !q.sos) return fail(c, DS_ERR_ARG, q.who, "null argument");
+    if (q.n_ch <= 0 || q.n_samples <= 0 || q.n_filt <= 0 || q.n_sec <= 0) return fail(c, DS_ERR_ARG, q.who, "bad shape");
+    if (q.n_sec > ciir::CIIR_MAX_SEC)
+        return fail(c, DS_ERR_UNSUP, q.who, "more than 16 complex second-order sections in one cascade is not built "
+                                            "(the carry matrix and the block states of more do not fit the LDS)");
+    if ((int64_t)q.n_filt * q.n_ch > 65535)
+        return fail(c, DS_ERR_UNSUP, q.who, "more than 65535 (filter, channel) streams is not built yet");
+    if ((q.n_samples + ciir::G - 1) / ciir::G > INT32_MAX) return fail(c, DS_ERR_UNSUP, q.who, "signal too long");
+    return DS_OK;
+}
+
+// the tables of a call on the host, and where they and the group states lie on the device
+struct CiirTables {
+    std::vector<double> coef, phi, phig;
+};
+struct CiirDev {
+    double *coef, *phi, *phig, *gst;
+};
+static size_t ciir_gst_count(const CiirCall& q) {
+    return 2 * (size_t)q.n_filt * q.n_ch * (size_t)((q.n_samples + ciir::G - 1) / ciir::G) * 2 * q.n_sec;
+}
+static void ciir_take(Carver& cv, const CiirCall& q, CiirDev* dv) {
+    const size_t d = 2 * (size_t)q.n_sec;
+    dv->coef = cv.take<double>((size_t)q.n_filt * q.n_sec * 10);
+    dv->phi = cv.take<double>((size_t)q.n_filt * 2 * d * d);
+    dv->phig = cv.take<double>((size_t)q.n_filt * 2 * d * d);
+    dv->gst = cv.take<double>(ciir_gst_count(q));
+}
+static int ciir_upload(ds_ctx* c, const CiirTables& tb, const CiirDev& dv) {
+    CHK(ds_upload(c, dv.coef, tb.coef.data(), tb.coef.size() * 8));
+    CHK(ds_upload(c, dv.phi, tb.phi.data(), tb.phi.size() * 8));
+    return ds_upload(c, dv.phig, tb.phig.data(), tb.phig.size() * 8);
+}
+
+// the three passes over device buffers of either sample type; output element (f, c, n) at y?[f syf + c syc + n syn], yi
+// may be null; zi, zf: device arrays or nullptr
+template <typename T>
+static int ciir_run(ds_ctx* c, const CiirCall& q, const CiirDev& dv, const T* x, int64_t sxc, int64_t sxn, const double* zi,
+                    double* yr, double* yi, int64_t syf, int64_t syc, int64_t syn, double* zf) {
+    const int n_filt = q.n_filt, n_sec = q.n_sec, n_ch = q.n_ch, d = 2 * n_sec;
+    const int64_t n = q.n_samples, n_groups = (n + ciir::G - 1) / ciir::G;
+    const size_t n_streams = (size_t)n_filt * n_ch;
+    ciir::Args<T> a{x, sxc, sxn, yr, yi, syf, syc, syn, n, n_ch, n_filt, n_sec, n_groups, dv.coef, dv.phi, dv.phig, dv.gst, zi, zf};
+    if (n_groups > 1)
+        CHK(launch(c, "ciir_group", ciir::k_ciir_group<T>, dim3((unsigned)(n_groups - 1), (unsigned)n_streams), ciir::B,
+                   ciir::lds_bytes(n_sec, false), a));
+    ciir::CarryArgs ca{dv.phig, dv.gst, zi, n_groups, n_ch, n_sec};
+    CHK(launch(c, "ciir_carry", ciir::k_ciir_carry, dim3((unsigned)n_streams), ciir::B, sizeof(double) * 2 * d * d, ca));
+    return launch(c, "ciir_apply", ciir::k_ciir_apply<T>, dim3((unsigned)n_groups, (unsigned)n_ch), ciir::B,
+                  ciir::lds_bytes(n_sec, true), a);
+}
+
+// host pointers in the reference's layouts: x (n_samples, n_ch) float64, y_re / y_im (n_filt, n_samples, n_ch) float64
+extern "C" int ds_iir_sos_c128(ds_ctx* c, const double* x, int n_ch, int64_t n_samples, const double* sos, int n_filt,
+                               int n_sec, const double* zi, double* y_re, double* y_im, double* zf) {
+    const CiirCall q{"ds_iir_sos_c128", n_ch, n_samples, sos, n_filt, n_sec};
+    CHK(ciir_check(c, q, x, y_re));
+    CiirTables tb;
+    if (!ciir_tables(sos, n_filt, n_sec, tb.coef, tb.phi, tb.phig))
+        return fail(c, DS_ERR_ARG, q.who, "sections must be finite with a0 != 0");
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t nx = (size_t)n_ch * n_samples, ny = nx * n_filt, nz = (size_t)n_filt * n_sec * 2 * n_ch;
+    Carver probe;
+    CiirDev dv;
+    ciir_take(probe, q, &dv);
+    CHK(mem_check(c, q.who, probe.off, 8 * (nx + ny + (y_im ? ny : 0)) + 16 * 2 * nz, 0));
+    CHK(carve(c, &c->ws, &c->ws_bytes, [&](Carver& cv) { ciir_take(cv, q, &dv); }));
+    CHK(ciir_upload(c, tb, dv));
+    return staged(c, {{8, nx, x}, {8, ny, nullptr, y_re}, {8, y_im ? ny : 0, nullptr, y_im}, {16, nz, zi}, {16, zf ? nz : 0, nullptr, zf}},
+                  [&](void* const* d) {
+        return ciir_run<double>(c, q, dv, (const double*)d[0], 1, n_ch, zi ? (const double*)d[3] : nullptr, (double*)d[1],
+                                y_im ? (double*)d[2] : nullptr, (int64_t)nx, 1, n_ch, zf ? (double*)d[4] : nullptr);
+    });
+}
+
+// ---- sums over a pair of signals for distances.snr / si_sdr (kernels_dist.hpp) -----------------------------------
+struct PairCall {
+    const char* who;
+    int n_ch_a, n_ch_b;
+    int64_t n;
+    int n_ch() const { return std::max(n_ch_a, n_ch_b); }
+    int n_wg() const { return (int)((n + dsdist::SPAN - 1) / dsdist::SPAN); }
+};
+
+static int pair_check(ds_ctx* c, const PairCall& q, const void* a, const void* b, const void* out) {
+    if (!c || !a || !b || !out) return fail(c, DS_ERR_ARG, q.who, "null argument");
+    if (q.n <= 0 || q.n_ch_a <= 0 || q.n_ch_b <= 0 || (q.n_ch_a != q.n_ch_b && q.n_ch_a != 1 && q.n_ch_b != 1))
+        return fail(c, DS_ERR_ARG, q.who, "needs samples, and equal channel counts or one channel on one side");
+    if (q.n_ch() > 65535) return fail(c, DS_ERR_UNSUP, q.who, "more than 65535 channels is not built");
+    if ((q.n + dsdist::SPAN - 1) / dsdist::SPAN > INT32_MAX) return fail(c, DS_ERR_UNSUP, q.who, "signal too long");
+    return DS_OK;
+}
+
+// par: host [n_ch][3] or null; out_dev [n_ch][NS]
+template <typename T>
+static int pair_run(ds_ctx* c, const PairCall& q, const T* a, int64_t sac, int64_t san, const T* b, int64_t sbc, int64_t sbn,
+                    const double* par, double* out_dev) {
+    const int n_ch = q.n_ch(), n_wg = q.n_wg();
+    void* t[kMaxStaged];
+    CHK(stage(c, &c->ws, &c->ws_bytes, {{8, par ? (size_t)n_ch * 3 : 0, par}, {8, (size_t)n_ch * n_wg * dsdist::NS}}, t));
+    dsdist::PairArgs<T> pa{a, b, q.n_ch_a == 1 ? 0 : sac, san, q.n_ch_b == 1 ? 0 : sbc, sbn, q.n, n_wg,
+                           par ? (const double*)t[0] : nullptr, (double*)t[1]};
+    CHK(launch(c, "pair_partial", dsdist::k_pair_partial<T>, dim3((unsigned)n_wg, (unsigned)n_ch), dsdist::NT, 0, pa));
+    hipLaunchKernelGGL(dsdist::k_pair_final, dim3((unsigned)n_ch), dim3(dsdist::NT), 0, c->stream, (const double*)t[1], n_wg,
+                       out_dev);
+    HIPCHK(c, hipGetLastError());
+    return DS_OK;
+}
+
+// host pointers: a (n, n_ch_a), b (n, n_ch_b) float64; par (n_ch, 3) or NULL; out (n_ch, 6)
+extern "C" int ds_pair_moments(ds_ctx* c, const double* a, int n_ch_a, const double* b, int n_ch_b, int64_t n,
+                               const double* par, double* out) {
+    const PairCall q{"ds_pair_moments", n_ch_a, n_ch_b, n};
+    CHK(pair_check(c, q, a, b, out));
+    HIPCHK(c, hipSetDevice(c->device));
+    return staged(c, {{8, (size_t)n * n_ch_a, a}, {8, (size_t)n * n_ch_b, b}, {8, (size_t)q.n_ch() * dsdist::NS, nullptr, out}},
+                  [&](void* const* d) {
+        return pair_run<double>(c, q, (const double*)d[0], 1, n_ch_a, (const double*)d[1], 1, n_ch_b, par, (double*)d[2]);
+    });
+}
+
+// device-resident planar float32 signals, channel ch at a_dev + ch lda
+extern "C" int ds_pair_moments_dev(ds_ctx* c, const float* a, int n_ch_a, int64_t lda, const float* b, int n_ch_b, int64_t ldb,
+                                   int64_t n, const double* par, double* out) {
+    const PairCall q{"ds_pair_moments_dev", n_ch_a, n_ch_b, n};
+    CHK(pair_check(c, q, a, b, out));
+    if (lda < n || ldb < n) return fail(c, DS_ERR_ARG, q.who, "row stride below the sample count");
+    HIPCHK(c, hipSetDevice(c->device));
+    return staged(c, {{8, (size_t)q.n_ch() * dsdist::NS, nullptr, out}}, [&](void* const* d) {
+        return pair_run<float>(c, q, a, lda, 1, b, ldb, 1, par, (double*)d[0]);
+    });
+}
+
 // ---- weighted sums of fractionally delayed channels (kernels_delay.hpp) -----------------------------------------
 // Everything ds_delay_sum and ds_delay_sum_dev share; the arrays are the host's.
 struct DelayCall {
@@ -4252,6 +4470,118 @@ extern "C" int ds_group_delay_phase(ds_ctx* c, const double* x, int64_t n, int n
         CHK(r.load(d[0], false, n));
         CHK(r.fft(false));
         return r.group_delay(nb, delta_f, d[1]);
+    });
+}
+
+// ---- frequency-weighted segmental SNR (kernels_dist.hpp on kernels_ciir.hpp and the transform above) ---------------
+// Everything ds_fw_snr_seg and ds_fw_snr_seg_dev share.
+struct FwCall {
+    const char* who;
+    int n_ch_x, n_ch;
+    int64_t n;
+    const double* sos;     // host [n_band][n_sec][6] complex128: the gammatone bank
+    int n_band, n_sec;
+    const double* window;  // host [lw]
+    int lw;
+    double lo, hi, gamma;
+    int chunk_frames;
+    int64_t hop() const { return lw / 2; }
+    int64_t n_frames() const { return (n + hop() - 1) / hop(); }
+    int64_t cols_per_frame() const { return (int64_t)n_band * n_ch; }
+    int64_t chunk() const {
+        return std::max<int64_t>(1, std::min<int64_t>({chunk_frames > 0 ? chunk_frames : 32, 65535 / cols_per_frame(), n_frames()}));
+    }
+};
+
+static int fw_check(ds_ctx* c, const FwCall& q, const void* x, const void* xhat, const void* out) {
+    if (!c || !x || !xhat || !out || !q.sos || !q.window) return fail(c, DS_ERR_ARG, q.who, "null argument");
+    if (q.n < 1 || q.n_ch < 1 || (q.n_ch_x != q.n_ch && q.n_ch_x != 1) || q.n_band < 1 || q.n_sec < 1 || q.lw < 2 || q.lw % 2 ||
+        !(q.lo <= q.hi) || !std::isfinite(q.gamma) || q.chunk_frames < 0)
+        return fail(c, DS_ERR_ARG, q.who, "needs samples, channels (x: as many as xhat, or one), bands, an even window, "
+                                          "an ordered range and a finite gamma");
+    if (q.lw > 16384) return fail(c, DS_ERR_UNSUP, q.who, "windows above 16384 samples are not built (the bins' sums are held in LDS)");
+    if (q.cols_per_frame() > 65535) return fail(c, DS_ERR_UNSUP, q.who, "more than 65535 (band, channel) pairs is not built");
+    const CiirCall f{q.who, q.n_ch, q.n, q.sos, q.n_band, q.n_sec};
+    return ciir_check(c, f, x, out);
+}
+
+// x, xhat: device samples of either type, sample n of channel ch at x[ch sc + n ss]; out_dev [n_ch]
+template <typename T>
+static int fw_run(ds_ctx* c, const FwCall& q, Fft64Run& r, const CiirTables& tb, const T* x, int64_t sxc, int64_t sxn,
+                  const T* xhat, int64_t shc, int64_t shn, double* out_dev) {
+    using namespace dsdist;
+    const CiirCall fx{q.who, q.n_ch_x, q.n, q.sos, q.n_band, q.n_sec}, fh{q.who, q.n_ch, q.n, q.sos, q.n_band, q.n_sec};
+    const int64_t chunk = q.chunk(), n_frames = q.n_frames();
+    CiirDev dv;
+    double *xb, *xhb, *win, *frames;
+    CHK(carve(c, &c->ws, &c->ws_bytes, [&](Carver& cv) {
+        ciir_take(cv, fh, &dv);  // (xhat has no fewer channels than x: its group states hold either run)
+        xb = cv.take<double>((size_t)q.n_band * q.n_ch_x * q.n);
+        xhb = cv.take<double>((size_t)q.n_band * q.n_ch * q.n);
+        win = cv.take<double>((size_t)q.lw);
+        frames = cv.take<double>((size_t)n_frames * q.n_ch);
+        r.x = cv.take<double2>((size_t)r.pl.ld * chunk * q.cols_per_frame());
+        r.tmp = cv.take<double2>((size_t)r.pl.ld * chunk * q.cols_per_frame());
+    }));
+    CHK(ciir_upload(c, tb, dv));
+    CHK(ds_upload(c, win, q.window, (size_t)q.lw * 8));
+    // the real parts of the bank's outputs, float64 planar (band, channel, sample)
+    CHK(ciir_run<T>(c, fx, dv, x, sxc, sxn, nullptr, xb, nullptr, (int64_t)q.n_ch_x * q.n, q.n, 1, nullptr));
+    CHK(ciir_run<T>(c, fh, dv, xhat, shc, shn, nullptr, xhb, nullptr, (int64_t)q.n_ch * q.n, q.n, 1, nullptr));
+    for (int64_t m0 = 0; m0 < n_frames; m0 += chunk) {
+        const int64_t nf = std::min(chunk, n_frames - m0), cols = nf * q.cols_per_frame();
+        r.n_ch = (int)cols;
+        CHK(launch(c, "fw_frame", k_fw_frame, dim3((unsigned)((q.lw + NT - 1) / NT), (unsigned)cols), NT, 0,
+                   FrameArgs{xb, xhb, win, q.n, q.hop(), m0, q.lw, q.n_band, q.n_ch, q.n_ch_x, cols, r.pl.ld, r.x}));
+        CHK(r.fft(false));
+        CHK(launch(c, "fw_reduce", k_fw_reduce, dim3((unsigned)nf, (unsigned)q.n_ch), NT, fw_reduce_lds_bytes(q.lw),
+                   ReduceArgs{r.x, r.pl.ld, q.lw, q.n_band, q.n_ch, q.gamma, q.lo, q.hi, m0, frames}));
+    }
+    hipLaunchKernelGGL(k_fw_mean, dim3((unsigned)q.n_ch), dim3(NT), 0, c->stream, (const double*)frames, n_frames, q.n_ch, out_dev);
+    HIPCHK(c, hipGetLastError());
+    return DS_OK;
+}
+
+// the checks, the memory pre-check (inside fft64_plan) and the host tables: nothing is uploaded before they pass
+static int fw_plan(ds_ctx* c, const FwCall& q, size_t io, Fft64Run* r, CiirTables* tb) {
+    if (!ciir_tables(q.sos, q.n_band, q.n_sec, tb->coef, tb->phi, tb->phig))
+        return fail(c, DS_ERR_ARG, q.who, "sections must be finite with a0 != 0");
+    HIPCHK(c, hipSetDevice(c->device));
+    Carver probe;
+    CiirDev dv;
+    ciir_take(probe, CiirCall{q.who, q.n_ch, q.n, q.sos, q.n_band, q.n_sec}, &dv);
+    const size_t extra = probe.off + 8 * ((size_t)q.n_band * (q.n_ch_x + q.n_ch) * q.n + q.lw + (size_t)q.n_frames() * q.n_ch) + 8 * 256;
+    r->c = c;
+    r->n_ch = (int)(q.chunk() * q.cols_per_frame());
+    return fft64_plan(c, q.who, q.lw, r->n_ch, extra, io, &r->pl);
+}
+
+// host pointers: x (n, n_ch_x), xhat (n, n_ch) float64; out (n_ch)
+extern "C" int ds_fw_snr_seg(ds_ctx* c, const double* x, int n_ch_x, const double* xhat, int n_ch, int64_t n, const double* sos,
+                             int n_band, int n_sec, const double* window, int window_length, double snr_lo_db, double snr_hi_db,
+                             double gamma, int chunk_frames, double* out) {
+    const FwCall q{"ds_fw_snr_seg", n_ch_x, n_ch, n, sos, n_band, n_sec, window, window_length, snr_lo_db, snr_hi_db, gamma, chunk_frames};
+    CHK(fw_check(c, q, x, xhat, out));
+    Fft64Run r{c, {}, 0};
+    CiirTables tb;
+    CHK(fw_plan(c, q, 8 * ((size_t)n * (n_ch_x + n_ch) + n_ch), &r, &tb));
+    return staged(c, {{8, (size_t)n * n_ch_x, x}, {8, (size_t)n * n_ch, xhat}, {8, (size_t)n_ch, nullptr, out}}, [&](void* const* d) {
+        return fw_run<double>(c, q, r, tb, (const double*)d[0], 1, n_ch_x, (const double*)d[1], 1, n_ch, (double*)d[2]);
+    });
+}
+
+// device-resident planar float32 signals, channel ch at x_dev + ch ldx
+extern "C" int ds_fw_snr_seg_dev(ds_ctx* c, const float* x, int n_ch_x, int64_t ldx, const float* xhat, int n_ch, int64_t ldxh,
+                                 int64_t n, const double* sos, int n_band, int n_sec, const double* window, int window_length,
+                                 double snr_lo_db, double snr_hi_db, double gamma, int chunk_frames, double* out) {
+    const FwCall q{"ds_fw_snr_seg_dev", n_ch_x, n_ch, n, sos, n_band, n_sec, window, window_length, snr_lo_db, snr_hi_db, gamma, chunk_frames};
+    CHK(fw_check(c, q, x, xhat, out));
+    if (ldx < n || ldxh < n) return fail(c, DS_ERR_ARG, q.who, "row stride below the sample count");
+    Fft64Run r{c, {}, 0};
+    CiirTables tb;
+    CHK(fw_plan(c, q, 8 * (size_t)n_ch, &r, &tb));
+    return staged(c, {{8, (size_t)n_ch, nullptr, out}}, [&](void* const* d) {
+        return fw_run<float>(c, q, r, tb, x, ldx, 1, xhat, ldxh, 1, (double*)d[0]);
     });
 }
 

@@ -1,6 +1,7 @@
 """tools: the fractional-octave band arithmetic of the reference's tools.fractional_octave_frequencies
-(dsptoolbox/tools.py:186-255), after the band definitions of IEC 61260-1:2014 / ANSI S1.11-2004, and
-fractional_octave_smoothing (dsptoolbox/tools.py:22-23) on the device."""
+(dsptoolbox/tools.py:186-255), after the band definitions of IEC 61260-1:2014 / ANSI S1.11-2004,
+erb_frequencies (dsptoolbox/tools.py:261-336), and fractional_octave_smoothing (dsptoolbox/tools.py:22-23) on the
+device."""
 
 import numpy as np
 
@@ -47,3 +48,31 @@ def fractional_octave_frequencies(num_fractions=1, frequency_range=(20, 20e3), r
     if not return_cutoff:
         return nominal, exact
     return nominal, exact, (exact * _G ** (-1 / 2 / b), exact * _G ** (1 / 2 / b))
+
+
+# the ERB-number scale of Hohmann 2002, Eq. (16): erb(f) = _ERB_L log(1 + f _ERB_Q)
+_ERB_L = 9.2645
+_ERB_Q = 0.00437
+
+
+def _hz_to_erb(f):
+    return _ERB_L * np.sign(f) * np.log(1 + np.abs(f) * _ERB_Q)
+
+
+def erb_frequencies(freq_range_hz=[20, 20000], resolution: float = 1, reference_frequency_hz: float = 1000):
+    """Frequencies in Hz spaced by `resolution` units of the ERB-number scale (V. Hohmann, "Frequency analysis and
+    synthesis using a gammatone filterbank", Acta Acust. united Ac. 88, 2002, Eq. 16).  The grid passes through the
+    reference frequency and holds every point of it inside the range, whose two limits may come in either order."""
+    if not isinstance(freq_range_hz, (list, tuple, np.ndarray)) or len(freq_range_hz) != 2:
+        raise ValueError("freq_range must be an array like of length 2")
+    if freq_range_hz[0] > freq_range_hz[1]:
+        freq_range_hz = [freq_range_hz[1], freq_range_hz[0]]
+    if resolution <= 0:
+        raise ValueError("Resolution must be larger than zero")
+    erb_lo, erb_hi = _hz_to_erb(np.asarray(freq_range_hz))
+    erb_ref = _hz_to_erb(reference_frequency_hz)
+    # whole steps that fit below and above the reference
+    steps_below = int(np.floor((erb_ref - erb_lo) / resolution))
+    steps_above = int(np.floor((erb_hi - erb_ref) / resolution))
+    erb = np.arange(-steps_below, steps_above + 1) * resolution + erb_ref
+    return 1 / _ERB_Q * np.sign(erb) * (np.exp(np.abs(erb) / _ERB_L) - 1)

@@ -381,6 +381,49 @@ int ds_iir_sos_dev(ds_ctx* ctx, const float* x_dev, int n_ch, int64_t ldx, int64
                    int n_filt, int n_sec, const double* zi_dev, int mode, float* y_dev, int64_t ld_y,
                    double* zf_dev);
 
+/* ---- IIR filtering with COMPLEX coefficients (csrc/kernels_ciir.hpp): what scipy.signal.sosfilt computes for a complex
+ * sos array and real samples -- the four cascaded complex one-pole sections of a gammatone band
+ * (filterbanks/filterbanks.py:217-303).  The recursion, the states and the carry over time are complex float64.
+ * sos [n_filt][n_sec][6] complex128 (interleaved doubles), host pointer, rows b0 b1 b2 a0 a1 a2 (a0 != 0), identity-padded
+ * by the caller; zi / zf [n_filt][n_sec][2][n_ch] complex128 or NULL; x (n_samples, n_ch) float64 REAL, host pointer.
+ * The output is two float64 planes in the reference's layout (n_filt, n_samples, n_ch): y_re and y_im; y_im may be NULL
+ * (the real part only).  Every filter runs on every channel (Parallel); there is no summed or sequential mode.
+ * Bounds: one cascade holds at most 16 sections (CIIR_MAX_SEC of the kernels; DS_ERR_UNSUP above); n_filt * n_ch <= 65535;
+ * DS_ERR_NOMEM, before anything is uploaded, when the device has not the memory free.  The filters must be stable.   */
+int ds_iir_sos_c128(ds_ctx* ctx, const double* x, int n_ch, int64_t n_samples, const double* sos, int n_filt, int n_sec,
+                    const double* zi, double* y_re, double* y_im, double* zf);
+
+/* ---- per-channel sums over a pair of signals, float64, fixed summation order (csrc/kernels_dist.hpp): the device part
+ * of distances.snr and distances.si_sdr (distances/_distances.py:64-101).  par (n_ch, 3) float64, host pointer, holds
+ * alpha, mu_a, mu_b per channel (NULL: zeros); out (n_ch, 6) float64, host pointer, receives
+ *   sum (a - mu_a)^2, sum (b - mu_b)^2, sum a b, sum a, sum b, sum (alpha a - b)^2      -- the last one term by term.
+ * a (n, n_ch_a) and b (n, n_ch_b) float64 host arrays, or for the _dev entry planar fp32 on the device (channel ch at
+ * a_dev + ch lda); a side with ONE channel is paired with every channel of the other; n_ch = max(n_ch_a, n_ch_b).  */
+int ds_pair_moments(ds_ctx* ctx, const double* a, int n_ch_a, const double* b, int n_ch_b, int64_t n, const double* par,
+                    double* out);
+int ds_pair_moments_dev(ds_ctx* ctx, const float* a_dev, int n_ch_a, int64_t lda, const float* b_dev, int n_ch_b,
+                        int64_t ldb, int64_t n, const double* par, double* out);
+
+/* ---- frequency-weighted segmental SNR: distances.fw_snr_seg (distances/distances.py:275-387, _fw_snr_seg_per_channel,
+ * distances/_distances.py:104-195) in one call.  Both signals go through the gammatone bank sos [n_band][n_sec][6]
+ * complex128 (ds_iir_sos_c128's recursion, real part only); the band signals stay in HBM as float64.  Frames of
+ * window_length samples (even; the window is window[window_length], host float64), hop window_length / 2, zeros past the
+ * signal's end, n_frames = ceil(n / hop).  Per (frame, band, channel) ONE complex float64 transform of x_band w + i
+ * xhat_band w gives both spectra; per (frame, channel) the bands' log10(X^2 / (X - Xhat + 1e-30)^2) |X|^gamma are summed,
+ * weighted, averaged over the bins 0 .. window_length / 2 and clipped to [snr_lo_db, snr_hi_db]; out[n_ch] is the mean
+ * over the frames.  Fixed summation order: repeats give the same bits.  A frame whose spectrum sums to zero gives NaN, as
+ * in the reference.  x has n_ch channels or ONE (paired with every channel of xhat).  The frames are walked in chunks of
+ * chunk_frames (0: 32), fewer where (chunk x bands x channels) would pass 65535 transform columns.
+ * Bounds: window_length <= 16384, n_band * n_ch <= 65535, n_sec <= 16 (DS_ERR_UNSUP); DS_ERR_NOMEM, before anything is
+ * uploaded, when the device has not the memory free.
+ * ds_fw_snr_seg: host (n, channels) float64; ds_fw_snr_seg_dev: planar fp32 on the device, channel ch at x_dev + ch ldx. */
+int ds_fw_snr_seg(ds_ctx* ctx, const double* x, int n_ch_x, const double* xhat, int n_ch, int64_t n, const double* sos,
+                  int n_band, int n_sec, const double* window, int window_length, double snr_lo_db, double snr_hi_db,
+                  double gamma, int chunk_frames, double* out);
+int ds_fw_snr_seg_dev(ds_ctx* ctx, const float* x_dev, int n_ch_x, int64_t ldx, const float* xhat_dev, int n_ch, int64_t ldxh,
+                      int64_t n, const double* sos, int n_band, int n_sec, const double* window, int window_length,
+                      double snr_lo_db, double snr_hi_db, double gamma, int chunk_frames, double* out);
+
 /* ---- fractional delays and their weighted sums, float64 arithmetic: replaces the reference's fractional_delay
  * (standard/latency_delay.py:159-285, filter from standard/_standard_backend.py:259-321, :430-492) and the loops of
  * MonopoleSource.get_signals_on_array, mix_sources_on_array and BeamformerDASTime (beamforming/beamforming.py:
