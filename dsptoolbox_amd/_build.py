@@ -34,6 +34,7 @@ NO_SCRATCH = [
     "5fft647k_point", "5fft6410k_gradient",
     "5dslpc8k_lpc_yw", "5dslpc10k_lpc_burg", "5dslpc10k_levinson", "5dslpc12k_lpc_filter", "5dslpc9k_lpc_ola",
     "6dswarp14k_allpass_tile",
+    "k_sfilt_group", "k_sfilt_carry", "k_sfilt_apply",
 ]
 
 

@@ -117,6 +117,10 @@ SIGNATURES = {
                                  C.c_int, C.c_void_p, i64, C.c_void_p]),
     "ds_iir_sos_c128": (C.c_int, [ctx_p, C.c_void_p, C.c_int, i64, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.c_void_p]),
+    "ds_sfilt": (C.c_int, [ctx_p, C.c_void_p, C.c_int, i64, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
+                           C.c_void_p, C.c_void_p]),
+    "ds_sfilt_dev": (C.c_int, [ctx_p, C.c_void_p, C.c_int, i64, i64, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
+                               C.c_void_p, i64, C.c_void_p]),
     "ds_pair_moments": (C.c_int, [ctx_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, i64, C.c_void_p, C.c_void_p]),
     "ds_pair_moments_dev": (C.c_int, [ctx_p, C.c_void_p, C.c_int, i64, C.c_void_p, C.c_int, i64, i64, C.c_void_p,
                                       C.c_void_p]),

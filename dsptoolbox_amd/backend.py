@@ -1288,6 +1288,71 @@ def iir_sos_filter_complex(x, sos_list, zi=None, real_only: bool = False):
     return y if zi is None else (y, zf)
 
 
+# ---- structure filters: lattice-ladder, warped and Kautz recursions (ds_sfilt, csrc/kernels_sfilt.hpp) ----------------
+SFILT_MAX_STATES = 64  # state values of one structure on the device (MAX_D of the kernels; DS_ERR_UNSUP above)
+SFILT_FIR_LATTICE, SFILT_IIR_LATTICE, SFILT_SOS_LATTICE, SFILT_WARPED_FIR, SFILT_WARPED_IIR, SFILT_KAUTZ = range(6)
+
+
+def sfilt_coef_count(kind: int, d: int, aux: int) -> int:
+    """Values in the packed coefficient array of a structure (coef_count of the kernels; include/dsptoolbox_amd.h)."""
+    return {SFILT_FIR_LATTICE: d, SFILT_IIR_LATTICE: 2 * d + 1, SFILT_SOS_LATTICE: 5 * (d // 2), SFILT_WARPED_FIR: 1 + d,
+            SFILT_WARPED_IIR: 1 + d + aux + 1, SFILT_KAUTZ: 3 * aux + 6 * ((d - aux) // 2)}[kind]
+
+
+def _sfilt_args(kind: int, coef, d: int, aux: int, n_ch: int, zi, want_zf: bool):
+    """NotImplementedError beyond the kernels' bounds, before anything reaches the device; the packed coefficients
+    (their count held against what kind, d and aux imply: the entry reads that many), zi and the zf to fill as
+    contiguous float64."""
+    if np.iscomplexobj(coef):
+        raise NotImplementedError("structure filters with complex coefficients are not run on the device (its "
+                                  "recursions are real)")
+    if d > SFILT_MAX_STATES:
+        raise NotImplementedError(f"structure filters with more than {SFILT_MAX_STATES} states are not run on the device "
+                                  f"(got {d}): the carry's state vector is one value per lane of a wave")
+    coef = np.ascontiguousarray(coef, dtype=np.float64)
+    assert kind in range(6) and d >= 1 and 0 <= aux <= d, "unknown structure kind or state counts out of range"
+    assert coef.shape == (sfilt_coef_count(kind, d, aux),), \
+        f"the structure needs {sfilt_coef_count(kind, d, aux)} packed coefficients, got an array of shape {coef.shape}"
+    if zi is not None:
+        zi = np.ascontiguousarray(zi, dtype=np.float64)
+        assert zi.shape == (d, n_ch), "zi must be (states, channels)"
+    zf = np.empty((d, n_ch), dtype=np.float64) if want_zf else None
+    return coef, zi, zf
+
+
+def sfilt_filter(x, kind: int, coef, d: int, aux: int = 0, zi=None, want_zf: bool = False):
+    """x (N, C) float64 through one structure filter (the recursion in float64 on the device): kind, the packed
+    coefficients, the state count d and aux as include/dsptoolbox_amd.h lays them out.  zi (d, C) gives the initial state
+    (None: zero).  -> y (N, C), or (y, zf) with want_zf."""
+    if np.iscomplexobj(x):
+        raise NotImplementedError("complex input samples are not run through the device recursion (its input is real)")
+    xa = np.ascontiguousarray(np.asarray(x, dtype=np.float64))
+    if xa.ndim == 1:
+        xa = xa[:, None]
+    n, n_ch = xa.shape
+    coef, zi, zf = _sfilt_args(kind, coef, d, aux, n_ch, zi, want_zf)
+    y = np.empty((n, n_ch), dtype=np.float64)
+    ctx = get_context()
+    ctx.check(ctx.lib.ds_sfilt(ctx.handle, _ptr(xa), n_ch, n, int(kind), _ptr(coef), int(d), int(aux),
+                               None if zi is None else _ptr(zi), _ptr(y), None if zf is None else _ptr(zf)), "ds_sfilt")
+    return (y, zf) if want_zf else y
+
+
+def sfilt_filter_device(x_dev: DevicePlanar, kind: int, coef, d: int, aux: int = 0, zi=None, want_zf: bool = False):
+    """sfilt_filter over device-resident samples (ds_sfilt_dev): -> a DevicePlanar, or (DevicePlanar, zf); only the
+    states (zi up, zf down) cross."""
+    ctx = x_dev.ctx
+    n, n_ch = x_dev.n_samples, x_dev.n_ch
+    coef, zi, zf = _sfilt_args(kind, coef, d, aux, n_ch, zi, want_zf)
+    with device_scope(ctx) as dev:
+        d_y = dev.alloc(n_ch * n * 4, result=True)
+        ctx.check(ctx.lib.ds_sfilt_dev(ctx.handle, C.c_void_p(x_dev.ptr), n_ch, x_dev.ld, n, int(kind), _ptr(coef), int(d),
+                                       int(aux), None if zi is None else _ptr(zi), C.c_void_p(d_y.ptr), n,
+                                       None if zf is None else _ptr(zf)), "ds_sfilt_dev")
+    y = DevicePlanar(d_y, n_ch, n, n, 0)
+    return (y, zf) if want_zf else y
+
+
 # ---- sums over a pair of signals (ds_pair_moments, csrc/kernels_dist.hpp) -------------------------------------------
 PAIR_SPAN = 4096  # samples one workgroup of the reduction sums (SPAN of the kernels)
 

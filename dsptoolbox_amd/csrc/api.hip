@@ -51,6 +51,7 @@
 #include "kernels_fft64.hpp"
 #include "kernels_lpc.hpp"
 #include "kernels_warp.hpp"
+#include "kernels_sfilt.hpp"
 #include "size_guards.hpp"
 
 using namespace dsk;
@@ -4757,6 +4758,131 @@ extern "C" int ds_allpass_table_dev(ds_ctx* c, const float* x, int n_ch, int64_t
     CHK(mem_check(c, k.who, (size_t)dswarp::workspace_doubles(dswarp::make_plan(n_in, n_out)) * 8, no * 8, 0));
     return staged(c, {{8, no, nullptr, out}}, [&](void* const* d) {
         return allpass_launch<float>(c, k, x, 1, ldx, (double*)d[0]);
+    });
+}
+
+// ---- structure filters: lattice-ladder, warped and Kautz recursions (kernels_sfilt.hpp) ---------------------------------
+// Everything ds_sfilt and ds_sfilt_dev share.  ldx, ld_y: the _dev entry's row strides (the host entry's rows are dense).
+struct SfiltCall {
+    const char* who;
+    int n_ch;
+    int64_t n_samples, ldx, ld_y;
+    int kind, d, aux;
+    const double* coef;  // host, packed as kernels_sfilt.hpp lays it out
+    int64_t n_groups() const { return (n_samples + sfilt::G - 1) / sfilt::G; }
+    size_t n_coef() const { return (size_t)sfilt::coef_count(kind, d, aux); }
+    size_t ws_bytes() const {  // coefficients, Phi, Phi^B, group states: four 256-byte aligned pieces
+        return (n_coef() + 2 * (size_t)d * d + (size_t)n_ch * (size_t)n_groups() * d) * 8 + 4 * 256;
+    }
+};
+
+// shape and bounds; nothing touches the device
+static int sfilt_check(ds_ctx* c, const SfiltCall& q, const void* x, const void* y) {
+    if (!c || !x || !y || !q.coef) return fail(c, DS_ERR_ARG, q.who, "null argument");
+    if (q.n_ch <= 0 || q.n_samples <= 0 || q.d <= 0 || q.ldx < q.n_samples || q.ld_y < q.n_samples)
+        return fail(c, DS_ERR_ARG, q.who, "bad shape");
+    if (q.kind < 0 || q.kind >= sfilt::N_KINDS) return fail(c, DS_ERR_ARG, q.who, "unknown structure kind");
+    if (q.d > sfilt::MAX_D)
+        return fail(c, DS_ERR_UNSUP, q.who, "more than 64 states in one structure is not built (the carry's state "
+                                            "vector is one value per lane of a wave)");
+    if ((q.kind == sfilt::SOS_LATTICE && q.d % 2) || (q.kind == sfilt::WARPED_IIR && (q.aux < 1 || q.aux > q.d)) ||
+        (q.kind == sfilt::KAUTZ && (q.aux < 0 || q.aux > q.d || (q.d - q.aux) % 2)))
+        return fail(c, DS_ERR_ARG, q.who, "the state count does not fit the structure");
+    if (q.n_ch > 65535) return fail(c, DS_ERR_UNSUP, q.who, "more than 65535 channels is not built yet");
+    if (q.n_groups() > INT32_MAX) return fail(c, DS_ERR_UNSUP, q.who, "signal too long");
+    for (size_t i = 0; i < q.n_coef(); ++i)
+        if (!std::isfinite(q.coef[i])) return fail(c, DS_ERR_ARG, q.who, "coefficients must be finite");
+    return DS_OK;
+}
+
+// Host side of the carry: column j of the zero-input transition A is one step of the structure's own step function from
+// the unit state e_j with x = 0 (exact: a zero-input step is linear); Phi = A^L and Phi^B by squaring.  The carry gain is
+// the largest magnitude in the two; above sfilt::max_gain(kind) the carried states' rounding is no longer small beside the
+// output, and a recursion that is not stable ends there or at a non-finite power.
+struct SfiltTables {
+    std::vector<double> phi, phig;
+};
+static int sfilt_tables(ds_ctx* c, const SfiltCall& q, SfiltTables& tb) {
+    const int d = q.d;
+    std::vector<double> a((size_t)d * d, 0.0), st((size_t)d);
+    for (int j = 0; j < d; ++j) {
+        std::fill(st.begin(), st.end(), 0.0);
+        st[j] = 1.0;
+        (void)sfilt::step(q.kind, 0.0, st.data(), q.coef, d, q.aux);
+        for (int i = 0; i < d; ++i) a[(size_t)i * d + j] = st[i];
+    }
+    static_assert(sfilt::L == 32 && sfilt::B == 64, "the squarings below assume L = 2^5, B = 2^6");
+    mat_pow2(a, d, 5);
+    tb.phi = a;
+    mat_pow2(a, d, 6);
+    tb.phig = a;
+    double gain = 0.0;
+    for (const std::vector<double>* m : {&tb.phi, &tb.phig})
+        for (double v : *m) gain = std::isfinite(v) ? std::max(gain, std::fabs(v)) : INFINITY;
+    if (!(gain <= sfilt::max_gain(q.kind)))
+        return fail(c, DS_ERR_UNSUP, q.who, "the recursion's carry gain (largest magnitude in Phi = A^32 and Phi^64) is "
+                                            "above the limit: an unstable or too ill-conditioned structure is not run "
+                                            "time-parallel");
+    return DS_OK;
+}
+
+// the three passes over device buffers of either sample type; y element (c, n) at y[c syc + n syn]; zi, zf: device
+// arrays [D][n_ch] or nullptr
+template <typename T>
+static int sfilt_run(ds_ctx* c, const SfiltCall& q, const SfiltTables& tb, const T* x, int64_t sxc, int64_t sxn,
+                     const double* zi, T* y, int64_t syc, int64_t syn, double* zf) {
+    const int d = q.d, n_ch = q.n_ch;
+    const int64_t n_groups = q.n_groups();
+    void* t[kMaxStaged];
+    CHK(stage(c, &c->ws, &c->ws_bytes, {{8, q.n_coef(), q.coef}, {8, tb.phi.size(), tb.phi.data()},
+                                        {8, tb.phig.size(), tb.phig.data()}, {8, (size_t)n_ch * n_groups * d}}, t));
+    const double *dcoef = (const double*)t[0], *dphi = (const double*)t[1], *dphig = (const double*)t[2];
+    double* gst = (double*)t[3];
+    sfilt::Args<T> a{x, sxc, sxn, y, syc, syn, q.n_samples, n_ch, q.kind, d, q.aux, n_groups, dcoef, dphi, dphig, gst, zi, zf};
+    if (n_groups > 1)
+        CHK(launch(c, "sfilt_group", sfilt::k_sfilt_group<T>, dim3((unsigned)(n_groups - 1), (unsigned)n_ch), sfilt::B,
+                   sfilt::lds_bytes(d, false), a));
+    if (d % 2 == 0) {  // the sos carry counts states in pairs; one filter, zi [D][n_ch] is its [1][D / 2][2][n_ch]
+        iir::CarryArgs ca{dphig, gst, zi, n_groups, n_ch, d / 2};
+        CHK(launch(c, "sfilt_carry@iir", iir::k_iir_carry, dim3((unsigned)n_ch), iir::B, sizeof(double) * d * d, ca));
+    } else {
+        sfilt::CarryArgs ca{dphig, gst, zi, n_groups, n_ch, d};
+        CHK(launch(c, "sfilt_carry@odd", sfilt::k_sfilt_carry, dim3((unsigned)n_ch), sfilt::B, sizeof(double) * d * d, ca));
+    }
+    return launch(c, "sfilt_apply", sfilt::k_sfilt_apply<T>, dim3((unsigned)n_groups, (unsigned)n_ch), sfilt::B,
+                  sfilt::lds_bytes(d, true), a);
+}
+
+// device-resident planar float32 samples; coef, zi and zf stay host pointers (zi / zf [D][n_ch] cross through c->io)
+extern "C" int ds_sfilt_dev(ds_ctx* c, const float* x, int n_ch, int64_t ldx, int64_t n_samples, int kind,
+                            const double* coef, int d, int aux, const double* zi, float* y, int64_t ld_y, double* zf) {
+    const SfiltCall q{"ds_sfilt_dev", n_ch, n_samples, ldx, ld_y, kind, d, aux, coef};
+    CHK(sfilt_check(c, q, x, y));
+    SfiltTables tb;
+    CHK(sfilt_tables(c, q, tb));
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t nz = (size_t)d * n_ch;
+    CHK(mem_check(c, q.who, q.ws_bytes(), 2 * nz * 8, 0));
+    return staged(c, {{8, nz, zi}, {8, zf ? nz : 0, nullptr, zf}}, [&](void* const* dv) {
+        return sfilt_run<float>(c, q, tb, x, ldx, 1, zi ? (const double*)dv[0] : nullptr, y, ld_y, 1,
+                                zf ? (double*)dv[1] : nullptr);
+    });
+}
+
+// host pointers in the reference's layouts: x and y (n_samples, n_ch) float64; the samples cross the link as they are
+// and the kernels read them with the channel stride
+extern "C" int ds_sfilt(ds_ctx* c, const double* x, int n_ch, int64_t n_samples, int kind, const double* coef, int d,
+                        int aux, const double* zi, double* y, double* zf) {
+    const SfiltCall q{"ds_sfilt", n_ch, n_samples, n_samples, n_samples, kind, d, aux, coef};
+    CHK(sfilt_check(c, q, x, y));
+    SfiltTables tb;
+    CHK(sfilt_tables(c, q, tb));
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t nx = (size_t)n_ch * n_samples, nz = (size_t)d * n_ch;
+    CHK(mem_check(c, q.who, q.ws_bytes(), (2 * nx + 2 * nz) * 8, 0));
+    return staged(c, {{8, nx, x}, {8, nx, nullptr, y}, {8, nz, zi}, {8, zf ? nz : 0, nullptr, zf}}, [&](void* const* dv) {
+        return sfilt_run<double>(c, q, tb, (const double*)dv[0], 1, n_ch, zi ? (const double*)dv[2] : nullptr,
+                                 (double*)dv[1], 1, n_ch, zf ? (double*)dv[3] : nullptr);
     });
 }
 

@@ -1,7 +1,9 @@
 """filterbanks: the block-streaming FIR classes of the reference's filterbanks module
 (dsptoolbox/filterbanks/__init__.py:78-83) on the device FIR kernels, the fractional-octave
 Butterworth bank (filterbanks/filterbanks.py:336-413) on the device IIR kernels, and the auditory gammatone bank
-(filterbanks/filterbanks.py:217-303, filterbanks/_filterbank.py:664-701) on the complex-coefficient IIR kernels."""
+(filterbanks/filterbanks.py:217-303, filterbanks/_filterbank.py:664-701) on the complex-coefficient IIR kernels, and the
+structure filters the reference exports here (filterbanks/__init__.py:75-86) -- LatticeLadderFilter, WarpedFIR, WarpedIIR,
+KautzFilter -- on the structure-filter kernels."""
 
 import numpy as np
 
@@ -9,6 +11,7 @@ from ..classes.filter import Filter
 from ..classes.filterbank import FilterBank
 from ..classes.fir_filter_realtime import (FIRFilterOverlapSave, FIRUniformPartitioned,
                                            FIRUniformPartitionedMultichannel)
+from ..classes.structure_filters import KautzFilter, LatticeLadderFilter, WarpedFIR, WarpedIIR
 from ..standard.enums import FilterCoefficientsType, FilterPassType, IirDesignMethod
 from ..tools import erb_frequencies, fractional_octave_frequencies
 
@@ -89,4 +92,5 @@ def auditory_filters_gammatone(frequency_range_hz=[20, 20000], resolution: float
 
 
 __all__ = ["FIRFilterOverlapSave", "FIRUniformPartitioned", "FIRUniformPartitionedMultichannel",
-           "fractional_octave_bands", "auditory_filters_gammatone", "GammaToneFilterBank"]
+           "fractional_octave_bands", "auditory_filters_gammatone", "GammaToneFilterBank", "LatticeLadderFilter", "WarpedFIR",
+           "WarpedIIR", "KautzFilter"]

@@ -393,6 +393,38 @@ int ds_iir_sos_dev(ds_ctx* ctx, const float* x_dev, int n_ch, int64_t ldx, int64
 int ds_iir_sos_c128(ds_ctx* ctx, const double* x, int n_ch, int64_t n_samples, const double* sos, int n_filt, int n_sec,
                     const double* zi, double* y_re, double* y_im, double* zf);
 
+/* ---- structure filters (csrc/kernels_sfilt.hpp): the sample loops of the reference's LatticeLadderFilter
+ * (classes/lattice_ladder_filter.py), WarpedFIR / WarpedIIR (classes/warped_filters.py) and KautzFilter
+ * (classes/kautz_filter.py) as float64 recursions over d <= 64 real state values, time-parallel with the carry of
+ * ds_iir_sos.  kind and the packed float64 coefficient array coef (host pointer), `aux` a count beside d:
+ *   DS_SFILT_FIR_LATTICE  k[d]                                         state: the reference's (len(k), channels)
+ *   DS_SFILT_IIR_LATTICE  k[d], c[d + 1]                               state: (len(k), channels)
+ *   DS_SFILT_SOS_LATTICE  per section k0 k1 c0 c1 c2, d = 2 sections   state: (sections, 2, channels)
+ *   DS_SFILT_WARPED_FIR   lambda, b[d]                                 state: WarpedFIR.buffer (len(b), channels)
+ *   DS_SFILT_WARPED_IIR   lambda, b[d] zero-padded to d = max(len(a), len(b)), sigma[0 .. aux], aux = len(a)
+ *                                                                      state: WarpedIIR.buffer (d, channels)
+ *   DS_SFILT_KAUTZ        aux real poles: pole, normalisation, weight each; then (d - aux) / 2 pole pairs: q, r, the two
+ *                         normalisations, the two weights each.  State: one direct-form-II value w[n-1] per real pole,
+ *                         (w[n-1], w[n-2]) per pair, shared by the tap filters and the all-pass of that pole.
+ * zi / zf [d][n_ch] float64, HOST pointers on both entries: the initial state (NULL: zero) and the state after the last
+ * sample (NULL: not wanted).  Bounds: d <= 64 and n_ch <= 65535 (DS_ERR_UNSUP above); the largest magnitude in
+ * Phi = A^32 and Phi^64 (A the zero-input state transition) at most 30 for the warped IIR filter and 1e6 for the others
+ * (MAX_GAIN_WARPED_IIR, MAX_GAIN of the kernels), DS_ERR_UNSUP above -- that refuses unstable and too ill-conditioned
+ * recursions; DS_ERR_NOMEM, before anything is uploaded, when the device has not the memory free.
+ * ds_sfilt: x and y (n_samples, n_ch) float64 host arrays.
+ * ds_sfilt_dev: device-resident planar float32 samples x_dev[c*ldx + n] -> y_dev[c*ld_y + n]; the recursion itself is
+ * float64 on both entries.                                                                                        */
+#define DS_SFILT_FIR_LATTICE 0
+#define DS_SFILT_IIR_LATTICE 1
+#define DS_SFILT_SOS_LATTICE 2
+#define DS_SFILT_WARPED_FIR 3
+#define DS_SFILT_WARPED_IIR 4
+#define DS_SFILT_KAUTZ 5
+int ds_sfilt(ds_ctx* ctx, const double* x, int n_ch, int64_t n_samples, int kind, const double* coef, int d, int aux,
+             const double* zi, double* y, double* zf);
+int ds_sfilt_dev(ds_ctx* ctx, const float* x_dev, int n_ch, int64_t ldx, int64_t n_samples, int kind, const double* coef,
+                 int d, int aux, const double* zi, float* y_dev, int64_t ld_y, double* zf);
+
 /* ---- per-channel sums over a pair of signals, float64, fixed summation order (csrc/kernels_dist.hpp): the device part
  * of distances.snr and distances.si_sdr (distances/_distances.py:64-101).  par (n_ch, 3) float64, host pointer, holds
  * alpha, mu_a, mu_b per channel (NULL: zeros); out (n_ch, 6) float64, host pointer, receives
