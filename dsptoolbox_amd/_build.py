@@ -24,7 +24,8 @@ NO_SCRATCH = [
     "stft1k11k_stft_wave", "stft4k6k_stft", "stft4k7k_istft", "stft4k10k_stft_dif", "welch1k3k_y", "welch1k3k_x", "welch8k3k_y", "welch8k3k_x", "welch16k3k_y", "welch16k3k_x", "welchl4k_yc", "welchl4k_xc", "stftl10k_stft_cls",
     "fir16k5k_firILb1E", "fir4k5k_firILi1E", "fir4k5k_firILi2E", "fir4k6k_fir3ILi0E", "deconv8k10k_deconv_p", "k_csm_gemm64",
     "k_bf_eigh", "k_bf_project", "k_bf_cleansc",
-    "k_iir_group", "k_iir_carry", "k_iir_apply",
+    "k_block_carry",
+    "k_iir_group", "k_iir_apply",
     "k_ciir_group", "k_ciir_carry", "k_ciir_apply", "k_pair_partial", "k_pair_final", "k_fw_frame", "k_fw_reduce", "k_fw_mean",
     "k_delay_sum",
     "k_cwt_inv", "k_cwt_squeeze",
@@ -34,7 +35,7 @@ NO_SCRATCH = [
     "5fft647k_point", "5fft6410k_gradient",
     "5dslpc8k_lpc_yw", "5dslpc10k_lpc_burg", "5dslpc10k_levinson", "5dslpc12k_lpc_filter", "5dslpc9k_lpc_ola",
     "6dswarp14k_allpass_tile",
-    "k_sfilt_group", "k_sfilt_carry", "k_sfilt_apply",
+    "k_sfilt_group", "k_sfilt_apply",
 ]
 
 

@@ -17,6 +17,7 @@
 #include "../../include/dsptoolbox_amd.h"
 #include "config.hpp"
 #include "host_marshal.hpp"
+#include "carry_tables.hpp"
 #include "kernels_bigfft.hpp"
 #include "kernels_bluestein.hpp"
 #include "kernels_finish.hpp"
@@ -3294,20 +3295,14 @@ extern "C" int ds_fir_freqz(ds_ctx* c, const double* taps, int n_filt, int n_tap
 
 // ---- IIR filtering: cascades of second-order sections (kernels_iir.hpp) --------------------------------
 // Host side of the carry: the normalised sections, the zero-input state transition A of each cascade and its
-// powers Phi = A^L and Phi^B, in float64.
-static void mat_mul(const std::vector<double>& a, const std::vector<double>& b, int d, std::vector<double>& out) {
-    std::vector<double> r((size_t)d * d, 0.0);
-    for (int i = 0; i < d; ++i)
-        for (int k = 0; k < d; ++k) {
-            const double v = a[(size_t)i * d + k];
-            if (v == 0.0) continue;
-            for (int j = 0; j < d; ++j) r[(size_t)i * d + j] += v * b[(size_t)k * d + j];
-        }
-    out.swap(r);
-}
+// powers Phi = A^L and Phi^B, in float64 (carry_tables.hpp).
 
-static void mat_pow2(std::vector<double>& m, int d, int log2_exp) {  // m <- m^(2^log2_exp)
-    for (int i = 0; i < log2_exp; ++i) mat_mul(m, m, d, m);
+// what the grids of the three passes hold, for every family on block_carry.hpp: a stream per block of grid y or x, a
+// group of carry::G samples per block of grid x
+static int carry_limits(ds_ctx* c, const char* who, int64_t n_streams, int64_t n_samples, const char* too_many_streams) {
+    if (n_streams > 65535) return fail(c, DS_ERR_UNSUP, who, too_many_streams);
+    if ((n_samples + carry::G - 1) / carry::G > INT32_MAX) return fail(c, DS_ERR_UNSUP, who, "signal too long");
+    return DS_OK;
 }
 
 // sos [n_filt][n_sec][6] -> coef [n_filt][n_sec][5] (b0 b1 b2 a1 a2 / a0), phi = A^L, phig = A^(L B), each [n_filt][D][D]
@@ -3331,23 +3326,11 @@ static bool iir_tables(const double* sos, int n_filt, int n_sec, std::vector<dou
             cf[5 * k + 3] = s[4] / a0;
             cf[5 * k + 4] = s[5] / a0;
         }
-        // column j of A: one zero-input step of the cascade from the unit state e_j
-        std::vector<double> a((size_t)d * d, 0.0);
-        for (int j = 0; j < d; ++j) {
-            double in = 0.0;
-            for (int k = 0; k < n_sec; ++k) {
-                const double z1 = (j == 2 * k) ? 1.0 : 0.0, z2 = (j == 2 * k + 1) ? 1.0 : 0.0;
-                const double y = cf[5 * k] * in + z1;
-                a[(size_t)(2 * k) * d + j] = cf[5 * k + 1] * in - cf[5 * k + 3] * y + z2;
-                a[(size_t)(2 * k + 1) * d + j] = cf[5 * k + 2] * in - cf[5 * k + 4] * y;
-                in = y;
-            }
-        }
-        static_assert(iir::L == 32 && iir::B == 64, "the squarings below assume L = 2^5, B = 2^6");
-        mat_pow2(a, d, 5);
-        std::copy(a.begin(), a.end(), phi.begin() + (size_t)f * d * d);
-        mat_pow2(a, d, 6);
-        std::copy(a.begin(), a.end(), phig.begin() + (size_t)f * d * d);
+        std::vector<double> a, p, pg;
+        carry::sos_transition(cf, n_sec, a);
+        carry::carry_powers(a, d, p, pg);
+        std::copy(p.begin(), p.end(), phi.begin() + (size_t)f * d * d);
+        std::copy(pg.begin(), pg.end(), phig.begin() + (size_t)f * d * d);
     }
     return true;
 }
@@ -3380,10 +3363,9 @@ static int iir_run(ds_ctx* c, const IirCall& q, const T* x, int64_t sxc, int64_t
     if (n_sec > iir::MAX_SEC)
         return fail(c, DS_ERR_UNSUP, q.who, "more than 32 second-order sections in one cascade is not "
                                             "built (the carry's state vector is one value per lane of a wave)");
-    if ((int64_t)n_filt * n_ch > 65535)
-        return fail(c, DS_ERR_UNSUP, q.who, "more than 65535 (filter, channel) streams is not built yet");
-    const int64_t n = q.n_samples, n_groups = (n + iir::G - 1) / iir::G;
-    if (n_groups > INT32_MAX) return fail(c, DS_ERR_UNSUP, q.who, "signal too long");
+    CHK(carry_limits(c, q.who, (int64_t)n_filt * n_ch, q.n_samples,
+                     "more than 65535 (filter, channel) streams is not built yet"));
+    const int64_t n = q.n_samples, n_groups = (n + carry::G - 1) / carry::G;
     std::vector<double> coef, phi, phig;
     if (!iir_tables(q.sos, n_filt, n_sec, coef, phi, phig))
         return fail(c, DS_ERR_ARG, q.who, "sections must be finite with a0 != 0");
@@ -3399,8 +3381,8 @@ static int iir_run(ds_ctx* c, const IirCall& q, const T* x, int64_t sxc, int64_t
     if (n_groups > 1)
         CHK(launch(c, "iir_group", iir::k_iir_group<T>, dim3((unsigned)(n_groups - 1), (unsigned)n_streams), iir::B,
                    iir::lds_bytes(n_sec, false), a));
-    iir::CarryArgs ca{dphig, gst, zi, n_groups, n_ch, n_sec};
-    CHK(launch(c, "iir_carry", iir::k_iir_carry, dim3((unsigned)n_streams), iir::B, sizeof(double) * d * d, ca));
+    carry::CarryArgs ca{dphig, gst, zi, n_groups, n_ch, d};
+    CHK(launch(c, "iir_carry", carry::k_block_carry, dim3((unsigned)n_streams), iir::B, sizeof(double) * d * d, ca));
     return launch(c, "iir_apply", iir::k_iir_apply<T>, dim3((unsigned)n_groups, (unsigned)n_ch), iir::B,
                   iir::lds_bytes(n_sec, true), a);
 }
@@ -3431,21 +3413,6 @@ extern "C" int ds_iir_sos(ds_ctx* c, const double* x, int n_ch, int64_t n_sample
 
 // ---- IIR filtering with complex coefficients (kernels_ciir.hpp): complex float64 recursion, real samples ------------
 typedef std::complex<double> cplx;
-
-static void cmat_mul(const std::vector<cplx>& a, const std::vector<cplx>& b, int d, std::vector<cplx>& out) {
-    std::vector<cplx> r((size_t)d * d, cplx(0.0, 0.0));
-    for (int i = 0; i < d; ++i)
-        for (int k = 0; k < d; ++k) {
-            const cplx v = a[(size_t)i * d + k];
-            if (v == cplx(0.0, 0.0)) continue;
-            for (int j = 0; j < d; ++j) r[(size_t)i * d + j] += v * b[(size_t)k * d + j];
-        }
-    out.swap(r);
-}
-
-static void cmat_pow2(std::vector<cplx>& m, int d, int log2_exp) {  // m <- m^(2^log2_exp)
-    for (int i = 0; i < log2_exp; ++i) cmat_mul(m, m, d, m);
-}
 
 // a d x d complex matrix as the kernels read it: the real plane, then the imaginary plane
 static void cmat_planes(const std::vector<cplx>& m, int d, double* dst) {
@@ -3479,23 +3446,11 @@ static bool ciir_tables(const double* sos, int n_filt, int n_sec, std::vector<do
                 coef[((size_t)f * n_sec + k) * 10 + 2 * i + 1] = v.imag();
             }
         }
-        // column j of A: one zero-input step of the cascade from the unit state e_j
-        std::vector<cplx> a((size_t)d * d, cplx(0.0, 0.0));
-        for (int j = 0; j < d; ++j) {
-            cplx in(0.0, 0.0);
-            for (int k = 0; k < n_sec; ++k) {
-                const cplx z1 = (j == 2 * k) ? 1.0 : 0.0, z2 = (j == 2 * k + 1) ? 1.0 : 0.0;
-                const cplx y = cf[5 * k] * in + z1;
-                a[(size_t)(2 * k) * d + j] = cf[5 * k + 1] * in - cf[5 * k + 3] * y + z2;
-                a[(size_t)(2 * k + 1) * d + j] = cf[5 * k + 2] * in - cf[5 * k + 4] * y;
-                in = y;
-            }
-        }
-        static_assert(ciir::L == 32 && ciir::B == 64, "the squarings below assume L = 2^5, B = 2^6");
-        cmat_pow2(a, d, 5);
-        cmat_planes(a, d, phi.data() + (size_t)f * 2 * d * d);
-        cmat_pow2(a, d, 6);
-        cmat_planes(a, d, phig.data() + (size_t)f * 2 * d * d);
+        std::vector<cplx> a, p, pg;
+        carry::sos_transition(cf.data(), n_sec, a);
+        carry::carry_powers(a, d, p, pg);
+        cmat_planes(p, d, phi.data() + (size_t)f * 2 * d * d);
+        cmat_planes(pg, d, phig.data() + (size_t)f * 2 * d * d);
     }
     return true;
 }
@@ -3516,10 +3471,8 @@ static int ciir_check(ds_ctx* c, const CiirCall& q, const void* x, const void* y
     if (q.n_sec > ciir::CIIR_MAX_SEC)
         return fail(c, DS_ERR_UNSUP, q.who, "more than 16 complex second-order sections in one cascade is not built "
                                             "(the carry matrix and the block states of more do not fit the LDS)");
-    if ((int64_t)q.n_filt * q.n_ch > 65535)
-        return fail(c, DS_ERR_UNSUP, q.who, "more than 65535 (filter, channel) streams is not built yet");
-    if ((q.n_samples + ciir::G - 1) / ciir::G > INT32_MAX) return fail(c, DS_ERR_UNSUP, q.who, "signal too long");
-    return DS_OK;
+    return carry_limits(c, q.who, (int64_t)q.n_filt * q.n_ch, q.n_samples,
+                        "more than 65535 (filter, channel) streams is not built yet");
 }
 
 // the tables of a call on the host, and where they and the group states lie on the device
@@ -4788,8 +4741,7 @@ static int sfilt_check(ds_ctx* c, const SfiltCall& q, const void* x, const void*
     if ((q.kind == sfilt::SOS_LATTICE && q.d % 2) || (q.kind == sfilt::WARPED_IIR && (q.aux < 1 || q.aux > q.d)) ||
         (q.kind == sfilt::KAUTZ && (q.aux < 0 || q.aux > q.d || (q.d - q.aux) % 2)))
         return fail(c, DS_ERR_ARG, q.who, "the state count does not fit the structure");
-    if (q.n_ch > 65535) return fail(c, DS_ERR_UNSUP, q.who, "more than 65535 channels is not built yet");
-    if (q.n_groups() > INT32_MAX) return fail(c, DS_ERR_UNSUP, q.who, "signal too long");
+    CHK(carry_limits(c, q.who, q.n_ch, q.n_samples, "more than 65535 channels is not built yet"));
     for (size_t i = 0; i < q.n_coef(); ++i)
         if (!std::isfinite(q.coef[i])) return fail(c, DS_ERR_ARG, q.who, "coefficients must be finite");
     return DS_OK;
@@ -4811,11 +4763,7 @@ static int sfilt_tables(ds_ctx* c, const SfiltCall& q, SfiltTables& tb) {
         (void)sfilt::step(q.kind, 0.0, st.data(), q.coef, d, q.aux);
         for (int i = 0; i < d; ++i) a[(size_t)i * d + j] = st[i];
     }
-    static_assert(sfilt::L == 32 && sfilt::B == 64, "the squarings below assume L = 2^5, B = 2^6");
-    mat_pow2(a, d, 5);
-    tb.phi = a;
-    mat_pow2(a, d, 6);
-    tb.phig = a;
+    carry::carry_powers(a, d, tb.phi, tb.phig);
     double gain = 0.0;
     for (const std::vector<double>* m : {&tb.phi, &tb.phig})
         for (double v : *m) gain = std::isfinite(v) ? std::max(gain, std::fabs(v)) : INFINITY;
@@ -4842,13 +4790,8 @@ static int sfilt_run(ds_ctx* c, const SfiltCall& q, const SfiltTables& tb, const
     if (n_groups > 1)
         CHK(launch(c, "sfilt_group", sfilt::k_sfilt_group<T>, dim3((unsigned)(n_groups - 1), (unsigned)n_ch), sfilt::B,
                    sfilt::lds_bytes(d, false), a));
-    if (d % 2 == 0) {  // the sos carry counts states in pairs; one filter, zi [D][n_ch] is its [1][D / 2][2][n_ch]
-        iir::CarryArgs ca{dphig, gst, zi, n_groups, n_ch, d / 2};
-        CHK(launch(c, "sfilt_carry@iir", iir::k_iir_carry, dim3((unsigned)n_ch), iir::B, sizeof(double) * d * d, ca));
-    } else {
-        sfilt::CarryArgs ca{dphig, gst, zi, n_groups, n_ch, d};
-        CHK(launch(c, "sfilt_carry@odd", sfilt::k_sfilt_carry, dim3((unsigned)n_ch), sfilt::B, sizeof(double) * d * d, ca));
-    }
+    carry::CarryArgs ca{dphig, gst, zi, n_groups, n_ch, d};  // one filter: zi [D][n_ch]
+    CHK(launch(c, "sfilt_carry", carry::k_block_carry, dim3((unsigned)n_ch), sfilt::B, sizeof(double) * d * d, ca));
     return launch(c, "sfilt_apply", sfilt::k_sfilt_apply<T>, dim3((unsigned)n_groups, (unsigned)n_ch), sfilt::B,
                   sfilt::lds_bytes(d, true), a);
 }

@@ -10,18 +10,18 @@
 //   k_ciir_carry  one wave per stream: T_{g+1} = Phi^(LB) T_g + t_g from T_0 = zi.
 //   k_ciir_apply  one wave per (group, channel), every filter in turn: each lane reruns its block from its true
 //                 entry state and writes the output's real plane and, where asked for, its imaginary plane.
-// The input samples are real; the block (L, B), the padded tile and load_tile / valid_in_block are kernels_iir.hpp's.
-// Complex values are kept as separate real and imaginary doubles in registers and LDS (two planes), and as
-// interleaved (re, im) pairs in global memory.
+// The input samples are real; the block (L, B), the padded tile with its load and store and valid_in_block are
+// block_carry.hpp's.  Complex values are kept as separate real and imaginary doubles in registers and LDS (two planes),
+// and as interleaved (re, im) pairs in global memory.
 #pragma once
-#include "kernels_iir.hpp"
+#include "block_carry.hpp"
 
 namespace ciir {
 
-using iir::B;
-using iir::G;
-using iir::L;
-using iir::TP;
+using carry::B;
+using carry::G;
+using carry::L;
+using carry::TP;
 // sections per complex cascade: D = 32 complex state values.  With 32 sections Phi (64 KB), the block states
 // (66 KB) and the tiles would not fit the 160 KB of LDS; with 16 the apply kernel takes 82 KB.
 constexpr int CIIR_MAX_SEC = 16;
@@ -111,21 +111,6 @@ __device__ inline void scan(double* sbr, double* sbi, const double* pmr, const d
     }
 }
 
-template <typename T>
-__device__ inline void load_x(const Args<T>& p, int c, int64_t g, double* xt) {
-    iir::Args<T> r{};
-    r.x = p.x;
-    r.sxc = p.sxc;
-    r.sxn = p.sxn;
-    r.n = p.n;
-    iir::load_tile(r, c, g, xt);
-}
-
-// both planes of one d x d matrix
-__device__ inline void load_matrix(const double* src, int d, double* dst) {
-    for (int t = threadIdx.x; t < 2 * d * d; t += B) dst[t] = src[t];
-}
-
 // grid = (n_groups - 1, n_filt n_ch), block = B: the zero-entry state t_g of every group but the last
 template <typename T>
 __global__ __launch_bounds__(B) void k_ciir_group(Args<T> p) {
@@ -138,8 +123,8 @@ __global__ __launch_bounds__(B) void k_ciir_group(Args<T> p) {
     double* sbi = sbr + B * (d + 1);
     double* pmr = sbi + B * (d + 1);
     double* pmi = pmr + d * d;
-    load_matrix(p.phi + (size_t)f * 2 * d * d, d, pmr);
-    load_x(p, c, g, xt);
+    carry::load_matrix(p.phi + (size_t)f * 2 * d * d, 2 * d * d, pmr);  // (both planes)
+    carry::load_tile(p.x + (int64_t)c * p.sxc, p.sxn, p.n, g, xt);
     __syncthreads();
     double wr[L], wi[L];
 #pragma unroll
@@ -147,8 +132,8 @@ __global__ __launch_bounds__(B) void k_ciir_group(Args<T> p) {
         wr[i] = xt[lane * TP + i];
         wi[i] = 0.0;
     }
-    cascade(wr, wi, iir::valid_in_block(p.n, g, lane), p.sos + (size_t)f * p.n_sec * 10, p.n_sec, sbr + lane * (d + 1),
-            sbi + lane * (d + 1), true);
+    cascade(wr, wi, carry::valid_in_block(p.n, g, lane), p.sos + (size_t)f * p.n_sec * 10, p.n_sec,
+            sbr + lane * (d + 1), sbi + lane * (d + 1), true);
     __syncthreads();
     double sr = 0.0, si = 0.0;
     scan(sbr, sbi, pmr, pmi, d, sr, si, false);
@@ -174,7 +159,7 @@ __global__ __launch_bounds__(B) void k_ciir_carry(CarryArgs p) {
     const int stream = blockIdx.x, f = stream / p.n_ch, c = stream % p.n_ch;
     double* pmr = clds;
     double* pmi = pmr + d * d;
-    load_matrix(p.phig + (size_t)f * 2 * d * d, d, pmr);
+    carry::load_matrix(p.phig + (size_t)f * 2 * d * d, 2 * d * d, pmr);
     __syncthreads();
     const double* rowr = pmr + (lane < d ? lane : 0) * d;
     const double* rowi = pmi + (lane < d ? lane : 0) * d;
@@ -199,19 +184,6 @@ __global__ __launch_bounds__(B) void k_ciir_carry(CarryArgs p) {
     }
 }
 
-// the tile of one output plane, from the lanes' registers to y in coalesced rows
-__device__ inline void store_plane(const double (&w)[L], double* ot, double* y, int64_t syn, int64_t n, int64_t g) {
-    const int lane = threadIdx.x;
-    __syncthreads();  // (the tile's previous plane is written out)
-#pragma unroll
-    for (int i = 0; i < L; ++i) ot[lane * TP + i] = w[i];
-    __syncthreads();
-    for (int t = lane; t < G; t += B) {
-        const int64_t nn = g * G + t;
-        if (nn < n) y[nn * syn] = ot[(t / L) * TP + t % L];
-    }
-}
-
 // grid = (n_groups, n_ch), block = B: every filter over one group of one channel -- the x tile is read once
 template <typename T>
 __global__ __launch_bounds__(B) void k_ciir_apply(Args<T> p) {
@@ -226,14 +198,21 @@ __global__ __launch_bounds__(B) void k_ciir_apply(Args<T> p) {
     double* pmi = pmr + d * d;
     double* sr = sbr + lane * (d + 1);
     double* si = sbi + lane * (d + 1);
-    const int nv = iir::valid_in_block(p.n, g, lane);
-    // the lane whose block holds the last sample writes the final state
-    const bool last = p.zf && nv > 0 && g * G + (int64_t)lane * L + nv == p.n;
-    load_x(p, c, g, xt);
+    const int nv = carry::valid_in_block(p.n, g, lane);
+    const bool last = carry::holds_last(p, g, lane, nv);
+    // one output plane, from the lanes' registers through the tile to y in coalesced rows
+    auto store_plane = [&](const double (&w)[L], double* y) {
+        __syncthreads();  // (the tile's previous plane is written out)
+#pragma unroll
+        for (int i = 0; i < L; ++i) ot[lane * TP + i] = w[i];
+        __syncthreads();
+        carry::store_tile(ot, y, p.syn, p.n, g);
+    };
+    carry::load_tile(p.x + (int64_t)c * p.sxc, p.sxn, p.n, g, xt);
     for (int f = 0; f < p.n_filt; ++f) {
         const double* sos = p.sos + (size_t)f * p.n_sec * 10;
         __syncthreads();  // (pm, sb and the tile of the previous filter are done with)
-        load_matrix(p.phi + (size_t)f * 2 * d * d, d, pmr);
+        carry::load_matrix(p.phi + (size_t)f * 2 * d * d, 2 * d * d, pmr);
         double wr[L], wi[L];
 #pragma unroll
         for (int i = 0; i < L; ++i) {
@@ -264,8 +243,8 @@ __global__ __launch_bounds__(B) void k_ciir_apply(Args<T> p) {
                 z[1] = si[i];
             }
         const int64_t off = (int64_t)f * p.syf + (int64_t)c * p.syc;
-        store_plane(wr, ot, p.yr + off, p.syn, p.n, g);
-        if (p.yi) store_plane(wi, ot, p.yi + off, p.syn, p.n, g);
+        store_plane(wr, p.yr + off);
+        if (p.yi) store_plane(wi, p.yi + off);
     }
 }
 

@@ -7,24 +7,23 @@
 // and the cascade of K sections has the state vector S = (z1_0, z2_0, z1_1, z2_1, ...), D = 2K values -- sosfilt's
 // zi[k][j] is S[2k + j].  With zero input the state moves as S' = A S; over a block of L samples
 //     S_{b+1} = Phi S_b + s_b,     Phi = A^L,
-// s_b the final state of block b run from zero state.  The recursion is parallelised over time with that carry:
-//   k_iir_group  one lane per block of L samples, one wave per group of B blocks: s_b for every block, then a serial
-//                in-wave scan over the B blocks (lane i holds S[i]) gives the group's state from zero entry, t_g.
-//   k_iir_carry  one wave per stream: T_{g+1} = Phi^(LB) T_g + t_g from T_0 = zi, serially over the groups.
-//   k_iir_apply  one wave per (group, channel), every filter in turn: s_b again, the in-wave scan from T_g gives each
-//                block's true entry state, and each lane reruns its block from it and writes the output.
+// s_b the final state of block b run from zero state.  The recursion is parallelised over time with that carry, in
+// the three passes of block_carry.hpp:
+//   k_iir_group    one wave per (group, stream): s_b of every block, then the in-wave scan gives t_g.
+//   k_block_carry  one wave per stream: T_{g+1} = Phi^B T_g + t_g from T_0 = zi.
+//   k_iir_apply    one wave per (group, channel), every filter in turn: s_b again, the in-wave scan from T_g gives each
+//                  block's true entry state, and each lane reruns its block from it and writes the output.
 // The output thus differs from the serial recursion only by the rounding of the carried states.
 #pragma once
-#include <hip/hip_runtime.h>
-#include <stdint.h>
+#include "block_carry.hpp"
 
 namespace iir {
 
-constexpr int L = 32;          // samples per block (one lane's recursion, held in registers)
-constexpr int B = 64;          // blocks per group (one wave)
-constexpr int G = L * B;       // samples per group
-constexpr int TP = L + 1;      // LDS tile row: one block, padded against bank conflicts
-constexpr int MAX_SEC = 32;    // sections per cascade (D = 64 state values: one per lane in the scans)
+using carry::B;
+using carry::G;
+using carry::L;
+using carry::TP;
+constexpr int MAX_SEC = 32;  // sections per cascade (D = 64 state values: one per lane in the scans)
 
 template <typename T>
 struct Args {
@@ -38,7 +37,7 @@ struct Args {
     const double* sos;      // [n_filt][n_sec][5]: b0 b1 b2 a1 a2, normalised by a0
     const double* phi;      // [n_filt][D][D]  A^L
     const double* phig;     // [n_filt][D][D]  A^(L B)
-    double* gst;            // [n_filt n_ch][n_groups][D]: t_g (k_iir_group), then T_g (k_iir_carry)
+    double* gst;            // [n_filt n_ch][n_groups][D]: t_g (k_iir_group), then T_g (k_block_carry)
     const double* zi;       // [n_filt][n_sec][2][n_ch] or null (zero initial state)
     double* zf;             // [n_filt][n_sec][2][n_ch] or null
 };
@@ -73,39 +72,6 @@ __device__ inline void cascade(double (&w)[L], int nv, const double* __restrict_
     }
 }
 
-// serial scan over the B blocks of a group, lane i < D holding S[i]: S <- P S + s_b.  With keep_entry the entry
-// state of block b replaces s_b in sb (what k_iir_apply reruns from).  Returns the state after the last block.
-__device__ inline double scan(double* sb, const double* pm, int d, double s, bool keep_entry) {
-    const int lane = threadIdx.x;
-    const double* row = pm + (lane < d ? lane : 0) * d;
-    for (int b = 0; b < B; ++b) {
-        double* sbb = sb + b * (d + 1);
-        double acc = lane < d ? sbb[lane] : 0.0;
-        for (int j = 0; j < d; ++j) acc = fma(row[j], __shfl(s, j), acc);
-        if (keep_entry && lane < d) sbb[lane] = s;
-        s = acc;
-    }
-    return s;
-}
-
-template <typename T>
-__device__ inline void load_tile(const Args<T>& p, int c, int64_t g, double* xt) {
-    const T* x = p.x + (int64_t)c * p.sxc;
-    for (int t = threadIdx.x; t < G; t += B) {
-        const int64_t nn = g * G + t;
-        xt[(t / L) * TP + t % L] = nn < p.n ? (double)x[nn * p.sxn] : 0.0;
-    }
-}
-
-__device__ inline void load_matrix(const double* src, int d, double* dst) {
-    for (int t = threadIdx.x; t < d * d; t += B) dst[t] = src[t];
-}
-
-__device__ inline int valid_in_block(int64_t n, int64_t g, int lane) {
-    const int64_t v = n - (g * G + (int64_t)lane * L);
-    return v <= 0 ? 0 : (v >= L ? L : (int)v);
-}
-
 // grid = (n_groups - 1, n_filt n_ch), block = B: the zero-entry state t_g of every group but the last
 template <typename T>
 __global__ __launch_bounds__(B) void k_iir_group(Args<T> p) {
@@ -116,43 +82,16 @@ __global__ __launch_bounds__(B) void k_iir_group(Args<T> p) {
     double* xt = lds;
     double* sb = xt + B * TP;
     double* pm = sb + B * (d + 1);
-    load_matrix(p.phi + (size_t)f * d * d, d, pm);
-    load_tile(p, c, g, xt);
+    carry::load_matrix(p.phi + (size_t)f * d * d, d * d, pm);
+    carry::load_tile(p.x + (int64_t)c * p.sxc, p.sxn, p.n, g, xt);
     __syncthreads();
     double w[L];
 #pragma unroll
     for (int i = 0; i < L; ++i) w[i] = xt[lane * TP + i];
-    cascade(w, valid_in_block(p.n, g, lane), p.sos + (size_t)f * p.n_sec * 5, p.n_sec, sb + lane * (d + 1), true);
+    cascade(w, carry::valid_in_block(p.n, g, lane), p.sos + (size_t)f * p.n_sec * 5, p.n_sec, sb + lane * (d + 1), true);
     __syncthreads();
-    const double t = scan(sb, pm, d, 0.0, false);
+    const double t = carry::scan(sb, pm, d, 0.0, false);
     if (lane < d) p.gst[((size_t)stream * p.n_groups + g) * d + lane] = t;
-}
-
-struct CarryArgs {
-    const double* phig;  // [n_filt][D][D]
-    double* gst;         // [n_filt n_ch][n_groups][D]
-    const double* zi;    // [n_filt][n_sec][2][n_ch] or null
-    int64_t n_groups;
-    int n_ch, n_sec;
-};
-
-// grid = n_filt n_ch, block = B: the entry state T_g of every group, in place of t_g
-__global__ __launch_bounds__(B) void k_iir_carry(CarryArgs p) {
-    extern __shared__ double lds[];
-    const int d = 2 * p.n_sec, lane = threadIdx.x;
-    const int stream = blockIdx.x, f = stream / p.n_ch, c = stream % p.n_ch;
-    double* pm = lds;
-    load_matrix(p.phig + (size_t)f * d * d, d, pm);
-    __syncthreads();
-    const double* row = pm + (lane < d ? lane : 0) * d;
-    double s = (p.zi && lane < d) ? p.zi[((size_t)f * d + lane) * p.n_ch + c] : 0.0;
-    double* gs = p.gst + (size_t)stream * p.n_groups * d;
-    for (int64_t g = 0; g < p.n_groups; ++g) {
-        double acc = (lane < d && g + 1 < p.n_groups) ? gs[g * d + lane] : 0.0;
-        for (int j = 0; j < d; ++j) acc = fma(row[j], __shfl(s, j), acc);
-        if (lane < d) gs[g * d + lane] = s;
-        s = acc;
-    }
 }
 
 // grid = (n_groups, n_ch), block = B: every filter over one group of one channel -- the x tile is read once
@@ -166,17 +105,16 @@ __global__ __launch_bounds__(B) void k_iir_apply(Args<T> p) {
     double* sb = ot + B * TP;
     double* pm = sb + B * (d + 1);
     double* st = sb + lane * (d + 1);
-    const int nv = valid_in_block(p.n, g, lane);
-    // the lane whose block holds the last sample writes the final state
-    const bool last = p.zf && nv > 0 && g * G + (int64_t)lane * L + nv == p.n;
-    load_tile(p, c, g, xt);
+    const int nv = carry::valid_in_block(p.n, g, lane);
+    const bool last = carry::holds_last(p, g, lane, nv);
+    carry::load_tile(p.x + (int64_t)c * p.sxc, p.sxn, p.n, g, xt);
     double acc[L];
 #pragma unroll
     for (int i = 0; i < L; ++i) acc[i] = 0.0;
     for (int f = 0; f < p.n_filt; ++f) {
         const double* sos = p.sos + (size_t)f * p.n_sec * 5;
         __syncthreads();  // (pm and sb of the previous filter are done with)
-        load_matrix(p.phi + (size_t)f * d * d, d, pm);
+        carry::load_matrix(p.phi + (size_t)f * d * d, d * d, pm);
         double w[L];
 #pragma unroll
         for (int i = 0; i < L; ++i) w[i] = xt[lane * TP + i];
@@ -184,7 +122,7 @@ __global__ __launch_bounds__(B) void k_iir_apply(Args<T> p) {
         __syncthreads();
         const size_t stream = (size_t)f * p.n_ch + c;
         const double t0 = lane < d ? p.gst[(stream * p.n_groups + g) * d + lane] : 0.0;
-        scan(sb, pm, d, t0, true);
+        carry::scan(sb, pm, d, t0, true);
         __syncthreads();
 #pragma unroll
         for (int i = 0; i < L; ++i) w[i] = xt[lane * TP + i];
@@ -199,22 +137,14 @@ __global__ __launch_bounds__(B) void k_iir_apply(Args<T> p) {
 #pragma unroll
         for (int i = 0; i < L; ++i) ot[lane * TP + i] = w[i];
         __syncthreads();
-        T* y = p.y + (int64_t)f * p.syf + (int64_t)c * p.syc;
-        for (int t = lane; t < G; t += B) {
-            const int64_t nn = g * G + t;
-            if (nn < p.n) y[nn * p.syn] = (T)ot[(t / L) * TP + t % L];
-        }
+        carry::store_tile(ot, p.y + (int64_t)f * p.syf + (int64_t)c * p.syc, p.syn, p.n, g);
     }
     if (!p.summed) return;
     __syncthreads();
 #pragma unroll
     for (int i = 0; i < L; ++i) ot[lane * TP + i] = acc[i];
     __syncthreads();
-    T* y = p.y + (int64_t)c * p.syc;
-    for (int t = lane; t < G; t += B) {
-        const int64_t nn = g * G + t;
-        if (nn < p.n) y[nn * p.syn] = (T)ot[(t / L) * TP + t % L];
-    }
+    carry::store_tile(ot, p.y + (int64_t)c * p.syc, p.syn, p.n, g);
 }
 
 }  // namespace iir

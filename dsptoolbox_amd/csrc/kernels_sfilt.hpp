@@ -5,11 +5,10 @@
 // A stream is one channel through one structure.  Every structure is a recursion (y, S') = step(x, S) over D <= 64
 // real state values, linear and time-invariant, so with zero input S' = A S and over a block of L samples
 //     S_{b+1} = Phi S_b + s_b,     Phi = A^L,
-// s_b the final state of block b run from zero state: the carry of kernels_iir.hpp (DESIGN sections 9 and 18), in the
-// same three passes with the same L, B, padded tile and in-wave scan:
+// s_b the final state of block b run from zero state: the block carry of block_carry.hpp (DESIGN sections 9 and 18),
+// in its three passes with its L, B, padded tile and in-wave scan:
 //   k_sfilt_group  one lane per block, one wave per group: s_b of every block, then the scan gives t_g.
-//   carry          one wave per stream: T_{g+1} = Phi^B T_g + t_g from T_0 = zi.  iir::k_iir_carry where D is even
-//                  (it counts states in pairs), k_sfilt_carry otherwise.
+//   k_block_carry  one wave per stream: T_{g+1} = Phi^B T_g + t_g from T_0 = zi, for any D, odd or even.
 //   k_sfilt_apply  one wave per (group, channel): s_b again, the scan from T_g gives each block's true entry state,
 //                  and each lane reruns its block from it, writes the output and, at the last sample, zf.
 // A lane's state lives in its row of the LDS block-state array (stride D + 1 doubles), so one step function per
@@ -26,14 +25,14 @@
 //                and the all-pass of the same denominator share one direct-form-II state: w[n-1] for a real pole,
 //                (w[n-1], w[n-2]) for a pair.
 #pragma once
-#include "kernels_iir.hpp"
+#include "block_carry.hpp"
 
 namespace sfilt {
 
-using iir::B;
-using iir::G;
-using iir::L;
-using iir::TP;
+using carry::B;
+using carry::G;
+using carry::L;
+using carry::TP;
 constexpr int MAX_D = 64;  // state values of one structure: one per lane in the scans
 // The carry gain, the largest magnitude in Phi = A^L and Phi^B, that the host entries accept: set from the conditioning
 // sweep of DESIGN section 18 (tools/sweep_sfilt_gain.py).  The warped IIR realisation is far from normal and its carried
@@ -202,16 +201,6 @@ __device__ inline void block(int kind, const double* xr, double* out, int nv, co
     }
 }
 
-template <typename T>
-__device__ inline void load_x(const Args<T>& p, int c, int64_t g, double* xt) {
-    iir::Args<T> r{};
-    r.x = p.x;
-    r.sxc = p.sxc;
-    r.sxn = p.sxn;
-    r.n = p.n;
-    iir::load_tile(r, c, g, xt);
-}
-
 // grid = (n_groups - 1, n_ch), block = B: the zero-entry state t_g of every group but the last
 template <typename T>
 __global__ __launch_bounds__(B) void k_sfilt_group(Args<T> p) {
@@ -222,40 +211,14 @@ __global__ __launch_bounds__(B) void k_sfilt_group(Args<T> p) {
     double* sb = xt + B * TP;
     double* pm = sb + B * (d + 1);
     double* st = sb + lane * (d + 1);
-    iir::load_matrix(p.phi, d, pm);
-    load_x(p, c, g, xt);
+    carry::load_matrix(p.phi, d * d, pm);
+    carry::load_tile(p.x + (int64_t)c * p.sxc, p.sxn, p.n, g, xt);
     for (int i = 0; i < d; ++i) st[i] = 0.0;
     __syncthreads();
-    block(p.kind, xt + lane * TP, nullptr, iir::valid_in_block(p.n, g, lane), p.coef, d, p.aux, st);
+    block(p.kind, xt + lane * TP, nullptr, carry::valid_in_block(p.n, g, lane), p.coef, d, p.aux, st);
     __syncthreads();
-    const double t = iir::scan(sb, pm, d, 0.0, false);
+    const double t = carry::scan(sb, pm, d, 0.0, false);
     if (lane < d) p.gst[((size_t)c * p.n_groups + g) * d + lane] = t;
-}
-
-struct CarryArgs {
-    const double* phig;  // [D][D]
-    double* gst;         // [n_ch][n_groups][D]
-    const double* zi;    // [D][n_ch] or null
-    int64_t n_groups;
-    int n_ch, d;
-};
-
-// grid = n_ch, block = B: the entry state T_g of every group, in place of t_g: what iir::k_iir_carry does, for an odd D
-__global__ __launch_bounds__(B) void k_sfilt_carry(CarryArgs p) {
-    extern __shared__ double slds[];
-    const int d = p.d, lane = threadIdx.x, c = blockIdx.x;
-    double* pm = slds;
-    iir::load_matrix(p.phig, d, pm);
-    __syncthreads();
-    const double* row = pm + (lane < d ? lane : 0) * d;
-    double s = (p.zi && lane < d) ? p.zi[(size_t)lane * p.n_ch + c] : 0.0;
-    double* gs = p.gst + (size_t)c * p.n_groups * d;
-    for (int64_t g = 0; g < p.n_groups; ++g) {
-        double acc = (lane < d && g + 1 < p.n_groups) ? gs[g * d + lane] : 0.0;
-        for (int j = 0; j < d; ++j) acc = fma(row[j], __shfl(s, j), acc);
-        if (lane < d) gs[g * d + lane] = s;
-        s = acc;
-    }
 }
 
 // grid = (n_groups, n_ch), block = B
@@ -269,27 +232,22 @@ __global__ __launch_bounds__(B) void k_sfilt_apply(Args<T> p) {
     double* sb = ot + B * TP;
     double* pm = sb + B * (d + 1);
     double* st = sb + lane * (d + 1);
-    const int nv = iir::valid_in_block(p.n, g, lane);
-    // the lane whose block holds the last sample writes the final state
-    const bool last = p.zf && nv > 0 && g * G + (int64_t)lane * L + nv == p.n;
-    iir::load_matrix(p.phi, d, pm);
-    load_x(p, c, g, xt);
+    const int nv = carry::valid_in_block(p.n, g, lane);
+    const bool last = carry::holds_last(p, g, lane, nv);
+    carry::load_matrix(p.phi, d * d, pm);
+    carry::load_tile(p.x + (int64_t)c * p.sxc, p.sxn, p.n, g, xt);
     for (int i = 0; i < d; ++i) st[i] = 0.0;
     __syncthreads();
     block(p.kind, xt + lane * TP, nullptr, nv, p.coef, d, p.aux, st);
     __syncthreads();
     const double t0 = lane < d ? p.gst[((size_t)c * p.n_groups + g) * d + lane] : 0.0;
-    iir::scan(sb, pm, d, t0, true);
+    carry::scan(sb, pm, d, t0, true);
     __syncthreads();
     block(p.kind, xt + lane * TP, ot + lane * TP, nv, p.coef, d, p.aux, st);
     if (last)
         for (int i = 0; i < d; ++i) p.zf[(size_t)i * p.n_ch + c] = st[i];
     __syncthreads();
-    T* y = p.y + (int64_t)c * p.syc;
-    for (int t = lane; t < G; t += B) {
-        const int64_t nn = g * G + t;
-        if (nn < p.n) y[nn * p.syn] = (T)ot[(t / L) * TP + t % L];
-    }
+    carry::store_tile(ot, p.y + (int64_t)c * p.syc, p.syn, p.n, g);
 }
 
 }  // namespace sfilt

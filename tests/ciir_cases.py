@@ -23,7 +23,7 @@ import numpy as np
 import ciir_oracle as co
 import dsptoolbox_amd as dsp
 
-# ---- the constants the case list depends on (csrc/kernels_iir.hpp, kernels_ciir.hpp, kernels_dist.hpp) ----------------
+# ---- the constants the case list depends on (csrc/carry_tables.hpp, kernels_ciir.hpp, kernels_dist.hpp) --------------
 L = 32
 B = 64
 CIIR_MAX_SEC = 16

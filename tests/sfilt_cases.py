@@ -19,7 +19,7 @@ import numpy as np
 import sfilt_oracle as so
 from dsptoolbox_amd import backend
 
-# ---- the constants the case list depends on (csrc/kernels_iir.hpp, kernels_sfilt.hpp) --------------------------------
+# ---- the constants the case list depends on (csrc/carry_tables.hpp, kernels_sfilt.hpp) ------------------------------
 L = 32
 B = 64
 MAX_D = 64

@@ -111,7 +111,7 @@ def _header_constant(header, name):
 
 
 def test_case_constants_match_the_sources():
-    assert _header_constant("kernels_iir.hpp", "L") == cc.L and _header_constant("kernels_iir.hpp", "B") == cc.B
+    assert _header_constant("carry_tables.hpp", "L") == cc.L and _header_constant("carry_tables.hpp", "B") == cc.B
     assert _header_constant("kernels_ciir.hpp", "CIIR_MAX_SEC") == cc.CIIR_MAX_SEC == backend.CIIR_MAX_SEC
     assert _header_constant("kernels_dist.hpp", "NT") == cc.PAIR_NT
     assert _header_constant("kernels_dist.hpp", "SPAN") == cc.PAIR_SPAN == backend.PAIR_SPAN

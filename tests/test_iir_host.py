@@ -120,7 +120,7 @@ def test_biquads_match_reference(golden):
 
 
 # ---- the device algorithm restated in numpy ----------------------------------------------------------------------
-L, B = 32, 64  # samples per block, blocks per group (kernels_iir.hpp)
+L, B = 32, 64  # samples per block, blocks per group (carry_tables.hpp)
 
 
 def _cascade(sos, x, state):
@@ -201,3 +201,26 @@ def test_block_carry_algebra_matches_sosfilt(n_sec, n, radius, tol):
     got, zf = _block_parallel(sos, x, zi.reshape(-1))
     assert np.max(np.abs(got - ref)) <= tol * np.max(np.abs(ref))
     assert np.max(np.abs(zf - ref_zf.reshape(-1))) <= tol * np.max(np.abs(ref_zf))
+
+
+def test_carry_tables_under_sanitizers(tmp_path):
+    """tests/host_san/carry_tables_san.cpp: csrc/carry_tables.hpp -- A of a cascade, Phi = A^32 and Phi^64 by squaring --
+    under AddressSanitizer and UBSan, for real cascades of 1, 3 and 32 sections, complex cascades of 1 and 16 sections and
+    a plain matrix with D = 63, against the same powers formed in long double by 31, then 2047, plain multiplications;
+    the bound, four times the largest error measured, is in the program's header.  A table squared one time too few and
+    the powers of the transposed A must miss it."""
+    import shutil
+    import subprocess
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    gxx = shutil.which("g++")
+    assert gxx, "g++ is part of the image"
+    exe = str(tmp_path / "carry_tables_san")
+    subprocess.run([gxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-o", exe,
+                    os.path.join(root, "tests", "host_san", "carry_tables_san.cpp")], check=True, timeout=300)
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=300, env=env)
+    print(r.stdout)
+    assert r.returncode == 0 and "carry_tables_san: ok" in r.stdout, (r.stdout[-2000:], r.stderr[-4000:])
+    for case in ("real, 1 sections", "real, 3 sections", "real, 32 sections", "complex, 1 sections",
+                 "complex, 16 sections", "plain matrix, D = 63"):
+        assert case in r.stdout

@@ -64,7 +64,7 @@ def _constant(header, name, kind="int"):
 
 
 def test_case_constants_match_the_sources():
-    assert _constant("kernels_iir.hpp", "L") == sc.L and _constant("kernels_iir.hpp", "B") == sc.B
+    assert _constant("carry_tables.hpp", "L") == sc.L and _constant("carry_tables.hpp", "B") == sc.B
     assert _constant("kernels_sfilt.hpp", "MAX_D") == sc.MAX_D == backend.SFILT_MAX_STATES
     assert _constant("kernels_sfilt.hpp", "MAX_GAIN", "double") == sc.MAX_GAIN
     assert _constant("kernels_sfilt.hpp", "MAX_GAIN_WARPED_IIR", "double") == sc.MAX_GAIN_WARPED_IIR
@@ -307,7 +307,7 @@ def test_api_surface():
     assert {"ds_sfilt", "ds_sfilt_dev"} <= set(SIGNATURES)
     header = open(os.path.join(ROOT, "include", "dsptoolbox_amd.h")).read()
     assert re.search(r"\bint ds_sfilt\(", header) and re.search(r"\bint ds_sfilt_dev\(", header)
-    assert {"k_sfilt_group", "k_sfilt_carry", "k_sfilt_apply"} <= set(_build.NO_SCRATCH)
+    assert {"k_sfilt_group", "k_block_carry", "k_sfilt_apply"} <= set(_build.NO_SCRATCH)
     assert callable(backend.sfilt_filter) and callable(backend.sfilt_filter_device)
     from dsptoolbox_amd.classes.fir_filter_realtime import RealtimeFilter
     for cls in (LatticeLadderFilter, WarpedFIR, WarpedIIR, KautzFilter):
