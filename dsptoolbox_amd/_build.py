@@ -36,6 +36,7 @@ NO_SCRATCH = [
     "5dslpc8k_lpc_yw", "5dslpc10k_lpc_burg", "5dslpc10k_levinson", "5dslpc12k_lpc_filter", "5dslpc9k_lpc_ola",
     "6dswarp14k_allpass_tile",
     "k_sfilt_group", "k_sfilt_apply",
+    "k_ism_count", "k_ism_scan", "k_ism_fill", "k_ism_sum", "k_modal_tf",
 ]
 
 

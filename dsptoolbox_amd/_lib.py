@@ -165,6 +165,9 @@ SIGNATURES = {
                                    C.c_void_p]),
     "ds_allpass_table_dev": (C.c_int, [ctx_p, C.c_void_p, C.c_int, i64, i64, C.c_double, C.c_double, C.c_void_p, C.c_void_p,
                                        i64, C.c_void_p]),
+    "ds_room_ism": (C.c_int, [ctx_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_int, C.c_void_p, C.c_int,
+                              i64, i64, C.c_void_p]),
+    "ds_room_modal_tf": (C.c_int, [ctx_p, C.c_void_p, C.c_void_p, C.c_void_p, i64, C.c_void_p, i64, C.c_void_p]),
     "ds_welch_tf_x64": (C.c_int, [ctx_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, i64, C.c_int, C.c_int, C.c_int,
                                   C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int,
                                   C.c_void_p, C.c_void_p]),

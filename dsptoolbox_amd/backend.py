@@ -2221,3 +2221,110 @@ def laguerre_transform(time_data, warping_factor: float):
     f, n = float(warping_factor), _table_length(time_data)
     s = (1.0 - f ** 2.0) ** 0.5
     return allpass_table(time_data, -f, f, _running_powers(s, f, n), _running_powers(s, -f, n))
+
+
+# ---- shoebox room simulation: image sources and modes (ds_room_ism, ds_room_modal_tf; csrc/kernels_room.hpp) --------
+# bounds of one call (csrc/size_guards.hpp; DS_ERR_UNSUP above)
+ISM_MAX_CELLS = 1 << 27       # (2 LIMIT + 1)^3 lattice cells of eight image sources each
+ISM_MAX_LIST_BYTES = 1 << 30  # the 4-byte ids of one slab of l planes; a larger call is walked slab by slab
+ISM_MAX_OUT = 1 << 24         # output samples per band
+ISM_MAX_BANDS = 8             # the reference's octave bands
+MODAL_MAX_WORK = 1e11         # modes x frequencies
+# the reference's u_vectors: the eight sources of a cell, (ux, uy, uz)
+_ISM_U = np.array([[0, 0, 0], [0, 0, 1], [0, 1, 0], [1, 0, 0], [0, 1, 1], [1, 0, 1], [1, 1, 0], [1, 1, 1]])
+
+
+def ism_limit(room_dim, t60_s: float, max_order, c: float = 343) -> int:
+    """LIMIT of _generate_rir (room_acoustics/_room_acoustics.py:208-213): the lattice runs from -LIMIT to LIMIT."""
+    l_max = c * (t60_s * 1.1) / 2 / np.asarray(room_dim, dtype=np.float64)
+    limit = int(np.ceil(np.sqrt(l_max @ l_max)))
+    if max_order is not None:
+        limit = limit if max_order > limit else int(max_order)
+    return limit
+
+
+def _ism_cell_indices(lvec, room_dim, s_pos, r_pos, sr, c):
+    """The eight sample indices of cell lvec in the reference's statements (:247-251, :218-219)."""
+    pos = ((1 - 2 * _ISM_U) * s_pos) + (2 * np.asarray(lvec) * room_dim) - r_pos
+    sq = pos ** 2
+    d = ((sq[:, 0] + sq[:, 1]) + sq[:, 2]) ** 0.5
+    return np.asarray(d / c * sr + 0.5).astype(np.int64)
+
+
+def _ism_wall_powers(alpha, limit: int) -> np.ndarray:
+    """beta^k, k = 0 .. limit + 1, of the walls south, west, floor, north, east, ceiling: (6, limit + 2).  alpha: one
+    mean coefficient or six in the reference's order north, south, east, west, floor, ceiling (:196-204)."""
+    beta = np.atleast_1d(np.sqrt(1 - np.asarray(alpha, dtype=np.float64)))
+    if len(beta) == 1:
+        walls = np.ones(6) * beta
+    elif len(beta) == 6:
+        walls = np.array([beta[1], beta[3], beta[4], beta[0], beta[2], beta[5]])
+    else:
+        raise ValueError("Wrong length for absorption coefficients")
+    return walls[:, None] ** np.arange(limit + 2)[None, :]
+
+
+def _ism_guard(limit: int, n_out: int, n_band: int) -> None:
+    cells = (2 * limit + 1) ** 3
+    if cells > ISM_MAX_CELLS:
+        raise NotImplementedError(f"an image-source sum over {cells:.3g} lattice cells (LIMIT = {limit}) is beyond the "
+                                  f"device kernels' work bound ({ISM_MAX_CELLS} cells per call); pass max_order")
+    if n_out > ISM_MAX_OUT or n_band > ISM_MAX_BANDS:
+        raise NotImplementedError(f"an image-source response of {n_out} samples in {n_band} bands is beyond the device "
+                                  f"kernels' bounds ({ISM_MAX_OUT} samples, {ISM_MAX_BANDS} bands)")
+
+
+def image_source_rir(room_dim, alphas, s_pos, r_pos, t60_s: float, max_order, sr: int, n_out: int, c: float = 343,
+                     max_list_bytes: int | None = None) -> np.ndarray:
+    """_generate_rir of the reference (room_acoustics/_room_acoustics.py:162-269) for every row of `alphas` at once,
+    padded or trimmed to n_out samples: (bands, n_out) float64 from the device.  alphas: (bands, 1) or (bands, 6)
+    absorption coefficients (a scalar or a vector is one band); the bands share the lattice, as they share the room's
+    T60 in the reference.  Raises the reference's IndexError when a source falls beyond its int(1.1 T60 5 sr) buffer,
+    ValueError when source and receiver coincide (the reference divides by zero there) and NotImplementedError beyond
+    the bounds above.  max_list_bytes lowers the memory of the source list (a test does); the result does not depend
+    on it."""
+    room_dim, s_pos, r_pos = (np.ascontiguousarray(np.squeeze(v), dtype=np.float64) for v in (room_dim, s_pos, r_pos))
+    assert room_dim.shape == s_pos.shape == r_pos.shape == (3,), "dimensions and positions are (x, y, z)"
+    alphas = np.asarray(alphas, dtype=np.float64)
+    alphas = alphas.reshape(1, -1) if alphas.ndim < 2 else alphas
+    n_band, n_out, sr = alphas.shape[0], int(n_out), int(sr)
+    if n_out < 1 or n_band < 1:
+        raise ValueError("image_source_rir: needs output samples and a band")
+    if np.array_equal(s_pos, r_pos):
+        raise ValueError("Source and receiver positions coincide: the direct sound would be infinite")
+    limit = ism_limit(room_dim, t60_s, max_order, c)
+    _ism_guard(limit, n_out, n_band)
+    if max_list_bytes is not None and int(max_list_bytes) < (2 * limit + 1) ** 2 * 32:
+        raise NotImplementedError(f"a source list of {int(max_list_bytes)} bytes does not hold one plane of the lattice "
+                                  f"({(2 * limit + 1) ** 2 * 32} bytes)")
+    # the largest index belongs to a corner cell: every axis' |pos| peaks at l = -LIMIT or LIMIT
+    buffer_length = int(t60_s * 1.1 * 5 * sr)
+    corners = [(a, b, d) for a in (-limit, limit) for b in (-limit, limit) for d in (-limit, limit)]
+    largest = max(int(_ism_cell_indices(lv, room_dim, s_pos, r_pos, sr, c).max()) for lv in corners)
+    if largest >= buffer_length:
+        raise IndexError(f"index {largest} is out of bounds for axis 0 with size {buffer_length}")
+    pw = np.ascontiguousarray(np.stack([_ism_wall_powers(a, limit) for a in alphas]))
+    out = np.empty((n_band, n_out), dtype=np.float64)
+    ctx = get_context()
+    ctx.check(ctx.lib.ds_room_ism(ctx.handle, _ptr(room_dim), _ptr(s_pos), _ptr(r_pos), float(sr), float(c), limit,
+                                  _ptr(pw), n_band, n_out, int(max_list_bytes or 0), _ptr(out)), "ds_room_ism")
+    return out
+
+
+def room_modal_response(omega_n, eta, weight, omega2) -> np.ndarray:
+    """p[f] = sum_n weight[n] / (omega_n[n]^2 + 2j eta[n] omega_n[n] - omega2[f]), the modes added in the table's order
+    (the loop of get_analytical_transfer_function, room_acoustics/_room_acoustics.py:633-670): complex128 (frequencies,)
+    from the device."""
+    omega_n, eta, weight, omega2 = (np.ascontiguousarray(v, dtype=np.float64).ravel() for v in (omega_n, eta, weight, omega2))
+    assert len(omega_n) == len(eta) == len(weight), "omega_n, eta and weight are per mode"
+    if len(omega_n) < 1 or len(omega2) < 1:
+        raise ValueError("room_modal_response: needs a mode and a frequency")
+    work = float(len(omega_n)) * len(omega2)
+    if work > MODAL_MAX_WORK:
+        raise NotImplementedError(f"a modal sum of {work:.3g} terms is beyond the device kernel's work bound "
+                                  f"({MODAL_MAX_WORK:.0e} = modes x frequencies per call)")
+    p = np.empty(len(omega2), dtype=np.complex128)
+    ctx = get_context()
+    ctx.check(ctx.lib.ds_room_modal_tf(ctx.handle, _ptr(omega_n), _ptr(eta), _ptr(weight), len(omega_n), _ptr(omega2),
+                                       len(omega2), _ptr(p)), "ds_room_modal_tf")
+    return p

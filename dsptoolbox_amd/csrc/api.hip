@@ -53,6 +53,7 @@
 #include "kernels_lpc.hpp"
 #include "kernels_warp.hpp"
 #include "kernels_sfilt.hpp"
+#include "kernels_room.hpp"
 #include "size_guards.hpp"
 
 using namespace dsk;
@@ -4826,6 +4827,74 @@ extern "C" int ds_sfilt(ds_ctx* c, const double* x, int n_ch, int64_t n_samples,
     return staged(c, {{8, nx, x}, {8, nx, nullptr, y}, {8, nz, zi}, {8, zf ? nz : 0, nullptr, zf}}, [&](void* const* dv) {
         return sfilt_run<double>(c, q, tb, (const double*)dv[0], 1, n_ch, zi ? (const double*)dv[2] : nullptr,
                                  (double*)dv[1], 1, n_ch, zf ? (double*)dv[3] : nullptr);
+    });
+}
+
+// ---- shoebox room simulation (kernels_room.hpp), float64 ----------------------------------------------------------
+// pw: host (n_band, 6, limit + 2); out: host (n_band, n_out)
+extern "C" int ds_room_ism(ds_ctx* c, const double dim[3], const double src[3], const double rec[3], double sr, double cs,
+                           int limit, const double* pw, int n_band, int64_t n_out, int64_t max_list_bytes, double* out) {
+    using namespace dsroom;
+    const char* who = "ds_room_ism";
+    if (!c || !dim || !src || !rec || !pw || !out) return fail(c, DS_ERR_ARG, who, "null argument");
+    if (limit < 0 || n_band < 1 || n_out < 1 || !(sr > 0) || !(cs > 0) || !std::isfinite(sr) || !std::isfinite(cs))
+        return fail(c, DS_ERR_ARG, who, "needs limit >= 0, bands, output samples and positive finite sr and c");
+    for (int a = 0; a < 3; ++a)
+        if (!(dim[a] > 0) || !std::isfinite(dim[a]) || !std::isfinite(src[a]) || !std::isfinite(rec[a]))
+            return fail(c, DS_ERR_ARG, who, "needs positive finite dimensions and finite positions");
+    if (ism_shape_unsupported(limit, n_out, n_band))
+        return fail(c, DS_ERR_UNSUP, who, "more than 2^27 cells, 2^24 output samples or 8 bands are not built");
+    if (max_list_bytes <= 0 || max_list_bytes > kIsmMaxListBytes) max_list_bytes = kIsmMaxListBytes;
+    const int64_t side = 2 * (int64_t)limit + 1, planes = ism_slab_planes(limit, max_list_bytes);
+    if (planes < 1) return fail(c, DS_ERR_UNSUP, who, "the id list does not hold one l plane of sources");
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t n_pw = (size_t)n_band * 6 * (limit + 2), n_y = (size_t)n_band * n_out, n_cnt = (size_t)n_out + 1;
+    const size_t n_list = (size_t)planes * side * side * 8;
+    CHK(mem_check(c, who, 2 * n_cnt * 4 + n_list * 4, (n_pw + n_y) * 8, 0));
+    uint32_t *count, *cursor, *list;
+    CHK(carve(c, &c->ws, &c->ws_bytes, [&](Carver& cv) {
+        count = cv.take<uint32_t>(n_cnt);
+        cursor = cv.take<uint32_t>(n_cnt);
+        list = cv.take<uint32_t>(n_list);
+    }));
+    return staged(c, {{8, n_pw, pw, nullptr}, {8, n_y, nullptr, out}}, [&](void* const* d) {
+        IsmArgs a{};
+        for (int k = 0; k < 3; ++k) a.dim[k] = dim[k], a.s[k] = src[k], a.r[k] = rec[k];
+        a.c = cs, a.sr = sr, a.limit = limit, a.n_out = n_out, a.n_band = n_band;
+        a.pw = (const double*)d[0], a.count = count, a.cursor = cursor, a.list = list, a.out = (double*)d[1];
+        CHK(ds_memset(c, a.out, 0, n_y * 8));
+        // slabs in ascending l: k_ism_sum continues the sums the earlier slabs left, so the additions keep their order
+        for (int64_t l0 = 0; l0 < side; l0 += planes) {
+            a.l0 = (int)l0, a.l1 = (int)std::min(l0 + planes, side);
+            const int64_t cells = (int64_t)(a.l1 - a.l0) * side * side;
+            const dim3 grid((unsigned)((cells + NT - 1) / NT));
+            CHK(ds_memset(c, count, 0, n_cnt * 4));
+            CHK(launch(c, "room_ism_count", k_ism_count, grid, NT, 0, a));
+            CHK(launch(c, "room_ism_scan", k_ism_scan, dim3(1), SCAN_NT, 0, a));
+            CHK(launch(c, "room_ism_fill", k_ism_fill, grid, NT, 0, a));
+            CHK(launch(c, "room_ism_sum", k_ism_sum, dim3((unsigned)n_out), NT, 0, a));
+        }
+        return DS_OK;
+    });
+}
+
+// omega_n, eta, weight: host (n_modes); omega2: host (n_freq); p: host (n_freq) complex128
+extern "C" int ds_room_modal_tf(ds_ctx* c, const double* omega_n, const double* eta, const double* weight, int64_t n_modes,
+                                const double* omega2, int64_t n_freq, double* p) {
+    using namespace dsroom;
+    const char* who = "ds_room_modal_tf";
+    if (n_modes < 1 || n_freq < 1) return fail(c, DS_ERR_ARG, who, "needs a mode and a frequency");
+    if (n_freq > ((int64_t)1 << 31) - 1 || modal_work_too_large(n_modes, n_freq))
+        return fail(c, DS_ERR_UNSUP, who, "modes x frequencies is beyond the work bound");
+    if (!c || !omega_n || !eta || !weight || !omega2 || !p) return fail(c, DS_ERR_ARG, who, "null argument");
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t nm = (size_t)n_modes, nf = (size_t)n_freq;
+    CHK(mem_check(c, who, 0, (3 * nm + 3 * nf) * 8, 0));
+    return staged(c, {{8, nm, omega_n, nullptr}, {8, nm, eta, nullptr}, {8, nm, weight, nullptr}, {8, nf, omega2, nullptr},
+                      {16, nf, nullptr, p}}, [&](void* const* d) {
+        return launch(c, "room_modal_tf", k_modal_tf, dim3((unsigned)((nf + MODAL_NT - 1) / MODAL_NT)), MODAL_NT, 0,
+                      ModalArgs{(const double*)d[0], (const double*)d[1], (const double*)d[2], n_modes,
+                                (const double*)d[3], n_freq, (double2*)d[4]});
     });
 }
 

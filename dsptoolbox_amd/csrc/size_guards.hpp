@@ -91,3 +91,33 @@ DS_HD inline bool warp_shape_unsupported(int64_t n_in, int64_t n_out, int64_t n_
 DS_HD inline bool warp_work_too_large(int64_t n_in, int64_t n_out, int64_t groups) {
     return (double)n_in * (double)n_out * (double)groups > kWarpMaxWork;
 }
+
+// Shoebox room simulation (kernels_room.hpp).  The image-source entry enumerates (2 LIMIT + 1)^3 cells of eight sources
+// twice (count, fill) and keeps a list of 4-byte ids of the kept sources of one slab of l planes, which the sum pass
+// sorts and adds per output sample.  Cells per call: at most 2^27 (LIMIT <= 255: T60 = 2 s in a room of 2.6 m a side),
+// 1.07e9 sources -- eleven times the largest shape measured (1.17e7 cells, 9.4e7 sources, 1.2 ms of kernels: DESIGN
+// section 19), so a call stays far below a second.  List bytes per slab: at most 1 GiB unless the caller asks for less;
+// a slab is at least one plane and its ids stay below 2^31 (the sort's padding key is 2^32 - 1; the segment starts are
+// 32-bit).  Output samples: at most 2^24 per band (the scan is one workgroup), bands at most 8.  The modal sum costs one
+// division per (mode, frequency); it sustains 2.0e11 terms per second (68920 modes x 24000 frequencies in 8.4 ms), and
+// the bound is half a second of that.  Beyond any of these the entries answer DS_ERR_UNSUP.
+constexpr int64_t kIsmMaxCells = (int64_t)1 << 27;
+constexpr int64_t kIsmMaxListBytes = (int64_t)1 << 30;
+constexpr int64_t kIsmMaxOut = (int64_t)1 << 24;
+constexpr int kIsmMaxBands = 8;
+constexpr double kModalMaxWork = 1e11;
+DS_HD inline int64_t ism_cells(int64_t limit) { return (2 * limit + 1) * (2 * limit + 1) * (2 * limit + 1); }
+DS_HD inline bool ism_shape_unsupported(int64_t limit, int64_t n_out, int64_t n_band) {
+    return limit > 1024 || ism_cells(limit) > kIsmMaxCells || n_out > kIsmMaxOut || n_band > kIsmMaxBands;  // (1024: no overflow in ism_cells)
+}
+// l planes per slab whose ids fit list_bytes (0: not even one plane does)
+DS_HD inline int64_t ism_slab_planes(int64_t limit, int64_t list_bytes) {
+    const int64_t side = 2 * limit + 1, plane_ids = side * side * 8;
+    int64_t ids = list_bytes / 4;
+    if (ids > (((int64_t)1 << 31) - 1)) ids = ((int64_t)1 << 31) - 1;
+    const int64_t planes = ids / plane_ids;
+    return planes > side ? side : planes;
+}
+DS_HD inline bool modal_work_too_large(int64_t n_modes, int64_t n_freq) {
+    return (double)n_modes * (double)n_freq > kModalMaxWork;
+}

@@ -3,7 +3,8 @@
 Butterworth bank (filterbanks/filterbanks.py:336-413) on the device IIR kernels, and the auditory gammatone bank
 (filterbanks/filterbanks.py:217-303, filterbanks/_filterbank.py:664-701) on the complex-coefficient IIR kernels, and the
 structure filters the reference exports here (filterbanks/__init__.py:75-86) -- LatticeLadderFilter, WarpedFIR, WarpedIIR,
-KautzFilter -- on the structure-filter kernels."""
+KautzFilter -- on the structure-filter kernels, and the Linkwitz-Riley crossover bank (filterbanks/filterbanks.py:37-78,
+filterbanks/_filterbank.py:45-405) on the device IIR kernels."""
 
 import numpy as np
 
@@ -14,6 +15,7 @@ from ..classes.fir_filter_realtime import (FIRFilterOverlapSave, FIRUniformParti
 from ..classes.structure_filters import KautzFilter, LatticeLadderFilter, WarpedFIR, WarpedIIR
 from ..standard.enums import FilterCoefficientsType, FilterPassType, IirDesignMethod
 from ..tools import erb_frequencies, fractional_octave_frequencies
+from ._linkwitz_riley import LRFilterBank
 
 
 def fractional_octave_bands(frequency_range_hz=[31.5, 16e3], octave_fraction: int = 1, filter_order: int = 6,
@@ -39,6 +41,15 @@ def fractional_octave_bands(frequency_range_hz=[31.5, 16e3], octave_fraction: in
                                           filter_design_method=IirDesignMethod.Butterworth,
                                           sampling_rate_hz=sampling_rate_hz))
     return bank, center_freqs_hz, (lower_hz, upper_hz)
+
+
+def linkwitz_riley_crossovers(crossover_frequencies_hz, order, sampling_rate_hz: int) -> LRFilterBank:
+    """A Linkwitz-Riley crossover bank: len(crossover_frequencies_hz) + 1 bands whose sum is an all-pass.  order: one
+    value or one per crossover -- 2 (Sallen-Key sections with Q = 0.5, the high band phase-inverted), a multiple of 4
+    (Butterworth filters of half the order twice; bands cross at -6 dB, slope 6 dB / octave per order) or odd (one
+    Butterworth filter per side, bands cross at -3 dB; not a Linkwitz-Riley crossover, but the magnitudes still
+    reconstruct)."""
+    return LRFilterBank(crossover_frequencies_hz, order, sampling_rate_hz)
 
 
 class GammaToneFilterBank(FilterBank):
@@ -93,4 +104,4 @@ def auditory_filters_gammatone(frequency_range_hz=[20, 20000], resolution: float
 
 __all__ = ["FIRFilterOverlapSave", "FIRUniformPartitioned", "FIRUniformPartitionedMultichannel",
            "fractional_octave_bands", "auditory_filters_gammatone", "GammaToneFilterBank", "LatticeLadderFilter", "WarpedFIR",
-           "WarpedIIR", "KautzFilter"]
+           "WarpedIIR", "KautzFilter", "linkwitz_riley_crossovers", "LRFilterBank"]

@@ -632,6 +632,32 @@ int ds_allpass_table(ds_ctx* ctx, const double* x, int64_t n_in, int n_ch, doubl
 int ds_allpass_table_dev(ds_ctx* ctx, const float* x_dev, int n_ch, int64_t ldx, int64_t n_in, double p, double q,
                          const double* row0, const double* col0, int64_t n_out, double* out);
 
+/* ---- shoebox room simulation (csrc/kernels_room.hpp): the image-source sum of room_acoustics.generate_synthetic_rir
+ * (room_acoustics/_room_acoustics.py:162-269) and the modal sum of ShoeboxRoom.get_analytical_transfer_function
+ * (:554-685) of the reference, float64 on the device.
+ * ds_room_ism: the cells (l, m, n), each index -limit .. limit, in row-major order, eight sources per cell in the
+ *   reference's order u = 000 001 010 100 011 101 110 111 (ux uy uz).  Source (cell, u) lies at
+ *   pos = (1 - 2u) src + 2 l dim - rec per axis, d = sqrt((x^2 + y^2) + z^2), falls into sample int(d / c sr + 0.5) and adds
+ *   ((pw[0][|l - ux|] pw[1][|m - uy|]) pw[2][|n - uz|]) ((pw[3][|l|] pw[4][|m|]) pw[5][|n|]) / (4 pi d) there, every
+ *   operation rounded on its own.  Inside one cell a source whose sample equals that of a later source of the cell
+ *   is dropped, as the reference's fancy-index += drops it; sources at or beyond n_out are dropped.  pw is host
+ *   (n_band, 6, limit + 2): the powers beta^k, k = 0 .. limit + 1, of the walls south, west, floor, north, east,
+ *   ceiling per band; all bands share the enumeration.  out: host (n_band, n_out).  Per sample the kept sources are
+ *   added in the reference's loop order, so repeats give the same bits.  The kept sources' ids are listed l slab by
+ *   l slab, a slab's list within max_list_bytes (<= 0: the bound of csrc/size_guards.hpp).
+ *   The caller guarantees what the reference's buffer guarantees: every sample index is below 2^31 (backend.py raises
+ *   the reference's IndexError first) and src != rec.
+ * ds_room_modal_tf: p[f] = sum_n weight[n] / (omega_n[n]^2 + 2j eta[n] omega_n[n] - omega2[f]) over the table's n_modes
+ *   entries in table order, one writer per frequency; p: host (n_freq) complex128.
+ * Bounds: limit >= 0, n_out, n_band, n_modes, n_freq >= 1, positive finite dim, c, sr (DS_ERR_ARG); (2 limit + 1)^3
+ *   <= 2^27 cells, n_out <= 2^24, n_band <= 8, a list that holds one l plane, n_modes x n_freq within the work bound
+ *   of csrc/size_guards.hpp (DS_ERR_UNSUP); DS_ERR_NOMEM, before anything is uploaded, when the device has not the
+ *   memory free.                                                                                                   */
+int ds_room_ism(ds_ctx* ctx, const double dim[3], const double src[3], const double rec[3], double sr, double c, int limit,
+                const double* pw, int n_band, int64_t n_out, int64_t max_list_bytes, double* out);
+int ds_room_modal_tf(ds_ctx* ctx, const double* omega_n, const double* eta, const double* weight, int64_t n_modes,
+                     const double* omega2, int64_t n_freq, double* p);
+
 /* ---- block-streaming FIR classes with device-resident state ------------------------------
  * One process_block of the reference's real-time classes (classes/fir_filter_realtime.py:75-335),
  * executed literally on buffers that stay on the device between calls; per call only the block
