@@ -154,6 +154,10 @@ SIGNATURES = {
     "ds_from_cepstrum": (C.c_int, [ctx_p, C.c_void_p, i64, C.c_int, C.c_void_p]),
     "ds_min_phase": (C.c_int, [ctx_p, C.c_void_p, i64, C.c_int, i64, C.c_int, i64, C.c_double, C.c_void_p]),
     "ds_group_delay_phase": (C.c_int, [ctx_p, C.c_void_p, i64, C.c_int, C.c_double, C.c_void_p]),
+    "ds_latency": (C.c_int, [ctx_p, C.c_void_p, i64, C.c_int, C.c_void_p, i64, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                             C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ds_lag_pearson": (C.c_int, [ctx_p, C.c_void_p, i64, C.c_int, C.c_void_p, i64, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "ds_group_delay_phase_lat": (C.c_int, [ctx_p, C.c_void_p, i64, C.c_int, C.c_double, C.c_void_p, C.c_double, C.c_void_p]),
     "ds_lpc": (C.c_int, [ctx_p, C.c_void_p, i64, C.c_int, C.c_void_p, C.c_int, i64, C.c_int, C.c_int, C.c_void_p,
                          C.c_void_p, C.c_void_p]),
     "ds_lpc_dev": (C.c_int, [ctx_p, C.c_void_p, C.c_int, i64, i64, C.c_void_p, C.c_int, i64, C.c_int, C.c_int, C.c_void_p,

@@ -2007,16 +2007,144 @@ def min_phase(time_data, n_fft: int, output: str, n_out: int = 0, delta_f: float
     return out
 
 
-def group_delay_phase(time_data, delta_f: float):
+def group_delay_phase(time_data, delta_f: float, latency_samples=None, fs: float = 0.0):
     """-gradient(unwrap(angle(rfft(x)))) / (2 pi delta_f) on the n // 2 + 1 bins of a real (samples, channels) array
-    (_group_delay_direct of the reference on the spectrum's phase), float64."""
+    (_group_delay_direct of the reference on the spectrum's phase), float64.  With latency_samples (one per channel)
+    the phase is wrap(angle + 2 pi f latency / fs) before the unwrap (_remove_ir_latency_from_phase,
+    helpers/latency.py:152-181)."""
     a = _host_columns(time_data, np.float64)
     _fft64_guard(a.shape[0])
     out = np.empty((a.shape[0] // 2 + 1, a.shape[1]), dtype=np.float64)
     ctx = get_context()
-    ctx.check(ctx.lib.ds_group_delay_phase(ctx.handle, _ptr(a), a.shape[0], a.shape[1], float(delta_f), _ptr(out)),
-              "ds_group_delay_phase")
+    if latency_samples is None:
+        ctx.check(ctx.lib.ds_group_delay_phase(ctx.handle, _ptr(a), a.shape[0], a.shape[1], float(delta_f), _ptr(out)),
+                  "ds_group_delay_phase")
+        return out
+    lat = np.ascontiguousarray(latency_samples, dtype=np.float64)
+    assert lat.shape == (a.shape[1],), "one latency per channel"
+    ctx.check(ctx.lib.ds_group_delay_phase_lat(ctx.handle, _ptr(a), a.shape[0], a.shape[1], float(delta_f), _ptr(lat),
+                                               float(fs), _ptr(out)), "ds_group_delay_phase_lat")
     return out
+
+
+# ---- latency estimation by cross-correlation (csrc/kernels_latency.hpp) ---------------------------------------------
+# bounds of one call (csrc/size_guards.hpp; DS_ERR_UNSUP above)
+LATENCY_MAX_ROWS = FFT64_MAX_POW2  # rows of the full correlation, len(td1) + len(td2) - 1
+LATENCY_MAX_COLUMNS = 65535        # channels of both signals together
+LATENCY_MAX_POINTS = 16            # polynomial_points
+LATENCY_WINDOW_MARGIN = 200        # rows kept before the first and after the last peak (helpers/latency.py:34-38)
+
+
+def _finite_columns(a, name: str) -> np.ndarray:
+    a = _host_columns(a, np.float64)
+    if a.shape[0] < 1 or a.shape[1] < 1:
+        raise ValueError(f"{name}: empty array")
+    if not np.isfinite(a).all():
+        raise ValueError(f"{name} holds non-finite samples: the peak of a correlation with NaN or infinity in it is not "
+                         "defined here (numpy's argmax returns the first NaN)")
+    return a
+
+
+def latency_peaks(td1, td2, polynomial_points: int, pearson: bool = False, reverse_pairs: bool = False):
+    """The peaks of scipy's full-mode correlate(td2[:, c], td1[:, c]) per channel c of td1 (samples, channels); td2 has
+    as many channels or one, which then serves every pair.  The correlation is formed and searched on the device and
+    never comes down.  td2 None: the peaks of |td1| itself.  Returns (peaks, window, near, r):
+      peaks   (C,) int64, the row of the largest magnitude, the first among equal ones; the lag is len(td1) - 1 - peak
+      window  (lo, M), the rows [lo, lo + M) shared by all channels that the Hilbert transform was taken of, and
+      near    (C, 2 p + 2), imag(hilbert(window))[d - p .. d + p + 1] around each channel's row d = peak - lo, NaN for
+              rows outside the window -- both None with polynomial_points p = 0
+      r       with pearson: (C, 3) Pearson's r of the pair (td2 channel, td1 channel) at the integer lags
+              len(td1) - 1 - peak + (-1, 0, 1), (C, 1) at the lag itself when p = 0; reverse_pairs takes the peak of
+              channel C - 1 - c for pair c (the reference's order with in2 None, standard.latency).
+    Non-finite samples raise ValueError before anything is uploaded."""
+    p = int(polynomial_points)
+    if p < 0:
+        raise ValueError("polynomial_points must be at least 0")
+    a = _finite_columns(td1, "td1")
+    b = None if td2 is None else _finite_columns(td2, "td2")
+    if b is not None and b.shape[1] not in (1, a.shape[1]):
+        raise ValueError("td2 needs as many channels as td1, or one")
+    if b is None and pearson:
+        raise ValueError("correlation coefficients need a second signal")
+    rows = a.shape[0] + (b.shape[0] - 1 if b is not None else 0)
+    cols = a.shape[1] + (b.shape[1] if b is not None else 0)
+    if rows > LATENCY_MAX_ROWS or cols > LATENCY_MAX_COLUMNS or p > LATENCY_MAX_POINTS:
+        raise NotImplementedError(f"a correlation of {rows} rows, {cols} channels and {p} polynomial points is beyond the "
+                                  f"device kernels' bounds ({LATENCY_MAX_ROWS} rows, {LATENCY_MAX_COLUMNS} channels of both "
+                                  f"signals together, {LATENCY_MAX_POINTS} points)")
+    n_ch = a.shape[1]
+    peaks = np.empty(n_ch, dtype=np.int64)
+    window = np.zeros(2, dtype=np.int64)
+    near = np.empty((n_ch, 2 * p + 2), dtype=np.float64) if p > 0 else None
+    r = np.empty((n_ch, 3 if p > 0 else 1), dtype=np.float64) if pearson else None
+    ctx = get_context()
+    ctx.check(ctx.lib.ds_latency(ctx.handle, _ptr(a), a.shape[0], n_ch, None if b is None else _ptr(b),
+                                 0 if b is None else b.shape[0], 0 if b is None else b.shape[1], p, int(bool(reverse_pairs)),
+                                 _ptr(peaks), _ptr(window) if p > 0 else None, None if near is None else _ptr(near),
+                                 None if r is None else _ptr(r)), "ds_latency")
+    return peaks, ((int(window[0]), int(window[1])) if p > 0 else None), near, r
+
+
+def lag_pearson(time_data, other_time_data, lags, columns=None, other_columns=None) -> np.ndarray:
+    """Pearson's r per entry j between column columns[j] of time_data and column other_columns[j] of other_time_data
+    (default: j, or 0 for a one-channel time_data) at the integer lag lags[j], as _get_correlation_of_latencies forms it
+    (helpers/latency.py:218-265): a lag > 0 drops the first lag samples of the other signal, otherwise the first -lag
+    of time_data; both are cut to the shorter.  NaN where fewer than two samples are left or a channel is constant."""
+    t = _finite_columns(time_data, "time_data")
+    o = _finite_columns(other_time_data, "other_time_data")
+    lags = np.atleast_1d(np.asarray(lags)).astype(np.int64)
+    n = len(lags)
+    ct = (np.zeros(n, dtype=np.int64) if t.shape[1] == 1 else np.arange(n)) if columns is None else np.asarray(columns)
+    co = np.arange(n) if other_columns is None else np.asarray(other_columns)
+    rows = np.ascontiguousarray(np.stack([ct, co, lags], axis=1), dtype=np.int64)
+    out = np.empty(n, dtype=np.float64)
+    ctx = get_context()
+    ctx.check(ctx.lib.ds_lag_pearson(ctx.handle, _ptr(t), t.shape[0], t.shape[1], _ptr(o), o.shape[0], o.shape[1], _ptr(rows),
+                                     n, _ptr(out)), "ds_lag_pearson")
+    return out
+
+
+_LATENCY_FAILED = "Fractional latency detection failed for channel {}. Integer latency is returned"
+
+
+def _fractional_index(h_near, p: int, d: int, ch: int = 0) -> float:
+    """The sub-sample peak row of one channel from the 2 p + 2 values h_near = imag(hilbert)[d - p .. d + p + 1] the
+    device returned, in the branches of _get_fractional_impulse_peak_index (helpers/latency.py:46-97): move the row one
+    back when the two values at d and d + 1 have the same sign; if they still have, warn and return the integer row;
+    otherwise fit 2 p points with a polynomial of degree 2 p - 1 and take its first real root in [0, 1]; without one,
+    warn and return the integer row.  A value that is needed but NaN lies outside the array (the peak is within p + 1
+    rows of one of its ends): ValueError, no guess."""
+    from warnings import warn
+    h = np.asarray(h_near, dtype=np.float64)
+    assert h.shape == (2 * p + 2,), "2 p + 2 values around the peak"
+
+    def rows(first: int, count: int) -> np.ndarray:  # the values at rows d + first .. d + first + count - 1
+        v = h[first + p:first + p + count]
+        if first + p < 0 or len(v) != count or np.isnan(v).any():
+            raise ValueError(f"channel {ch}: the peak lies within {p + 1} rows of an end of the array; its neighbourhood "
+                             "is not there to fit")
+        return v
+
+    selection = rows(0, 2)
+    move_back = int(selection[0] * selection[1] > 0)
+    d = int(d) - move_back
+    selection = rows(-move_back, 2)
+    if selection[0] * selection[1] > 0:
+        warn(_LATENCY_FAILED.format(ch))
+        return float(d + move_back)
+    pol = np.polyfit(np.arange(-p + 1, p + 1), rows(-move_back - p + 1, 2 * p), deg=2 * p - 1)
+    roots = np.roots(pol)
+    roots = roots[(roots == roots.real) & (roots <= 1) & (roots >= 0)].real
+    if len(roots) == 0:
+        warn(_LATENCY_FAILED.format(ch))
+        return float(d + move_back)
+    return d + roots[0]
+
+
+def fractional_peak_rows(peaks, window, near, p: int) -> np.ndarray:
+    """latency_peaks' results as the rows _get_fractional_impulse_peak_index returns, (C,) float64."""
+    lo = window[0]
+    return np.array([_fractional_index(near[c], p, int(peaks[c]) - lo, c) for c in range(len(peaks))], dtype=np.float64) + lo
 
 
 # ---- linear prediction per (frame, channel) pair (csrc/kernels_lpc.hpp) ---------------------------------------------

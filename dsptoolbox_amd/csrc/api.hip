@@ -4,6 +4,7 @@
 #include <hip/hip_ext.h>
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <complex>
 #include <cstdio>
@@ -50,6 +51,7 @@
 #include "kernels_smooth.hpp"
 #include "kernels_direct.hpp"
 #include "kernels_fft64.hpp"
+#include "kernels_latency.hpp"
 #include "kernels_lpc.hpp"
 #include "kernels_warp.hpp"
 #include "kernels_sfilt.hpp"
@@ -4284,9 +4286,11 @@ struct Fft64Run {
             pb = cv.take<double>((size_t)n_phase * n_ch);
         });
     }
-    int load(const void* in_dev, bool cplx, int64_t n_in) {
-        return launch(c, "fft64_load", fft64::k_load, flat(pl.ld * n_ch), fft64::NT, 0,
-                      fft64::LoadArgs{(const double*)in_dev, cplx ? 1 : 0, n_in, pl.n, pl.ld, n_ch, x});
+    // the n_cols columns from col0 on (default: all of them) from an (n_in, n_cols) host-order array
+    int load(const void* in_dev, bool cplx, int64_t n_in, int col0 = 0, int n_cols = -1) {
+        if (n_cols < 0) n_cols = n_ch - col0;
+        return launch(c, "fft64_load", fft64::k_load, flat(pl.ld * n_cols), fft64::NT, 0,
+                      fft64::LoadArgs{(const double*)in_dev, cplx ? 1 : 0, n_in, pl.n, pl.ld, n_cols, x + (int64_t)col0 * pl.ld});
     }
     int fft(bool inv) {
         using namespace fft64;
@@ -4308,9 +4312,13 @@ struct Fft64Run {
         return launch(c, "fft64_store", fft64::k_store, flat(rows * n_ch), fft64::NT, 0,
                       fft64::StoreArgs{x, pl.ld, rows, n_ch, mode, scale, (double*)out_dev});
     }
-    // -gradient(unwrap(angle(x[0 .. nb)))) / (2 pi delta_f)
-    int group_delay(int64_t nb, double delta_f, void* out_dev) {
+    // -gradient(unwrap(angle(x[0 .. nb)))) / (2 pi delta_f); with lat_dev [n_ch] (samples) the phase is first
+    // wrap(angle + 2 pi f lat / fs), f = k delta_f
+    int group_delay(int64_t nb, double delta_f, void* out_dev, const double* lat_dev = nullptr, double fs = 0.0) {
         CHK(store(fft64::STORE_ANGLE, nb, 1.0, pa));
+        if (lat_dev)
+            CHK(launch(c, "lat_phase", dslat::k_lat_phase, flat(nb * n_ch), dslat::NT, 0,
+                       dslat::LatPhaseArgs{pa, nb, n_ch, delta_f, fs, lat_dev}));
         CHK(launch(c, "fft64_unwrap", dssmooth::k_unwrap, dim3((unsigned)n_ch), dssmooth::NT, 0,
                    dssmooth::UnwrapArgs{pa, nb, (int64_t)n_ch, pb}));
         return launch(c, "fft64_gradient", fft64::k_gradient, flat(nb * n_ch), fft64::NT, 0,
@@ -4425,6 +4433,166 @@ extern "C" int ds_group_delay_phase(ds_ctx* c, const double* x, int64_t n, int n
         CHK(r.load(d[0], false, n));
         CHK(r.fft(false));
         return r.group_delay(nb, delta_f, d[1]);
+    });
+}
+
+extern "C" int ds_group_delay_phase_lat(ds_ctx* c, const double* x, int64_t n, int n_ch, double delta_f,
+                                        const double* latency_samples, double fs, double* out) {
+    if (!c || !x || !out || !latency_samples) return fail(c, DS_ERR_ARG, "ds_group_delay_phase_lat: null argument");
+    const int64_t nb = n / 2 + 1;
+    if (n < 2 || !(delta_f > 0.0) || !(fs > 0.0))
+        return fail(c, DS_ERR_ARG, "ds_group_delay_phase_lat: needs two bins, delta_f > 0 and fs > 0");
+    Fft64Run r{c, {}, n_ch};
+    CHK(fft64_plan(c, "ds_group_delay_phase_lat", n, n_ch, Fft64Run::phase_bytes(nb, n_ch),
+                   ((size_t)n + (size_t)nb + 1) * 8 * (size_t)n_ch, &r.pl));
+    CHK(r.carve_ws(nb));
+    return staged(c, {{8, (size_t)n * n_ch, x, nullptr}, {8, (size_t)nb * n_ch, nullptr, out}, {8, (size_t)n_ch, latency_samples}},
+                  [&](void* const* d) {
+        CHK(r.load(d[0], false, n));
+        CHK(r.fft(false));
+        return r.group_delay(nb, delta_f, d[1], (const double*)d[2], fs);
+    });
+}
+
+// ---- latency by cross-correlation (kernels_latency.hpp on the transform above) ---------------------------------------
+// Pearson's r per row of the host table rows [n_rows][3] (col_t, col_o, lag), t and o sample-major on the device;
+// out_dev [n_rows].  The caller has checked the columns.
+static int lag_pearson_run(ds_ctx* c, const char* who, const double* t_dev, int64_t n_t, int n_ch_t, const double* o_dev,
+                           int64_t n_o, int n_ch_o, const int64_t* rows, int n_rows, double* out_dev) {
+    using namespace dslat;
+    const int64_t n_wg = std::max<int64_t>(1, (std::min(n_t, n_o) + dsdist::SPAN - 1) / dsdist::SPAN);  // no span is longer
+    if (n_wg > 65535) return fail(c, DS_ERR_UNSUP, who, "signals above 65535 x 4096 samples are not built");
+    void* t[kMaxStaged];
+    CHK(stage(c, &c->ws, &c->ws_bytes,
+              {{8, (size_t)n_rows * 3, rows}, {8, (size_t)n_rows * 2}, {8, (size_t)n_rows * n_wg * dsdist::NS}}, t));
+    LagArgs a{t_dev, o_dev, n_t, n_o, n_ch_t, n_ch_o, (const int64_t*)t[0], (int)n_wg, nullptr, (double*)t[2], (double*)t[1]};
+    const dim3 grid((unsigned)n_rows, (unsigned)n_wg), one((unsigned)n_rows);
+    CHK(launch(c, "lag_partial", k_lag_partial<false>, grid, NT, 0, a));
+    CHK(launch(c, "lag_final", k_lag_final<false>, one, NT, 0, a));
+    a.mean = (const double*)t[1];
+    a.out = out_dev;
+    CHK(launch(c, "lag_partial@moments", k_lag_partial<true>, grid, NT, 0, a));
+    return launch(c, "lag_final@moments", k_lag_final<true>, one, NT, 0, a);
+}
+
+extern "C" int ds_lag_pearson(ds_ctx* c, const double* t, int64_t n_t, int n_ch_t, const double* o, int64_t n_o, int n_ch_o,
+                              const int64_t* rows, int n_rows, double* out) {
+    if (!c || !t || !o || !rows || !out) return fail(c, DS_ERR_ARG, "ds_lag_pearson: null argument");
+    if (n_t < 1 || n_o < 1 || n_ch_t < 1 || n_ch_o < 1 || n_rows < 1) return fail(c, DS_ERR_ARG, "ds_lag_pearson: bad shape");
+    for (int j = 0; j < n_rows; ++j)
+        if (rows[3 * j] < 0 || rows[3 * j] >= n_ch_t || rows[3 * j + 1] < 0 || rows[3 * j + 1] >= n_ch_o)
+            return fail(c, DS_ERR_ARG, "ds_lag_pearson: a row names a column that is not there");
+    HIPCHK(c, hipSetDevice(c->device));
+    return staged(c, {{8, (size_t)n_t * n_ch_t, t}, {8, (size_t)n_o * n_ch_o, o}, {8, (size_t)n_rows, nullptr, out}},
+                  [&](void* const* d) {
+        return lag_pearson_run(c, "ds_lag_pearson", (const double*)d[0], n_t, n_ch_t, (const double*)d[1], n_o, n_ch_o, rows,
+                               n_rows, (double*)d[2]);
+    });
+}
+
+static int64_t pow2_at_least(int64_t n) {
+    int64_t m = 1;
+    while (m < n) m <<= 1;
+    return m;
+}
+
+extern "C" int ds_latency(ds_ctx* c, const double* a, int64_t n_a, int n_ch, const double* b, int64_t n_b, int n_ch_b,
+                          int polynomial_points, int reverse_pairs, int64_t* peaks, int64_t* window, double* near,
+                          double* pearson) {
+    using namespace dslat;
+    const char* who = "ds_latency";
+    const int p = polynomial_points;
+    if (!c || !a || !peaks || (p > 0 && (!window || !near)) || (!b && pearson)) return fail(c, DS_ERR_ARG, who, "null argument");
+    if (n_a < 1 || n_ch < 1 || p < 0 || (b && (n_b < 1 || (n_ch_b != n_ch && n_ch_b != 1))))
+        return fail(c, DS_ERR_ARG, who, "needs samples, channels (b: as many as a, or one) and polynomial_points >= 0");
+    const bool corr = b != nullptr;
+    const int cb = corr ? n_ch_b : 0;
+    const int64_t L = corr ? n_a + n_b - 1 : n_a, n_fft = pow2_at_least(L);
+    if (latency_shape_unsupported(L, (int64_t)n_ch + cb, p))
+        return fail(c, DS_ERR_UNSUP, who, "correlations above 2^22 rows, more than 65535 channels in one call or more than 16 "
+                                          "polynomial points are not built");
+    HIPCHK(c, hipSetDevice(c->device));
+    // the device memory of the whole call, for the widest window there can be (all L rows), before anything goes up
+    const int n_cand = p > 0 ? 3 : 1, w = 2 * p + 2;
+    const int n_wgp = (int)((L + PEAK_SPAN - 1) / PEAK_SPAN);
+    const size_t n_win = p > 0 && corr ? (size_t)L * n_ch : 0;
+    const size_t io = 8 * ((size_t)n_a * n_ch + (size_t)n_b * cb + n_win + (size_t)n_ch * (1 + w + n_cand));
+    const int64_t m2_worst = std::min(pow2_at_least(2 * L - 1), kFft64MaxPow2);
+    // the three steps use the workspace one after the other: correlation and peak pairs; the window's two planar arrays
+    // (its chirp tables are allocations of their own); Pearson's table, means and block partials
+    const size_t ws_corr = (corr ? 2 * (size_t)n_fft * (n_ch + cb) * 16 : 0) + Fft64Run::phase_bytes(n_wgp, n_ch + cb);
+    const size_t ws_win = p > 0 ? 2 * (size_t)m2_worst * n_ch * 16 : 0;
+    const size_t ws_pearson = pearson ? 8 * (size_t)n_ch * n_cand * (5 + (size_t)(L / dsdist::SPAN + 1) * dsdist::NS) : 0;
+    CHK(mem_check(c, who, std::max({ws_corr, ws_win, ws_pearson}), io, p > 0 ? (size_t)(L + 2 * m2_worst) * 16 : 0));
+    Fft64Run r1{c, {}, n_ch + cb};
+    if (corr) CHK(fft64_plan(c, who, n_fft, n_ch + cb, Fft64Run::phase_bytes(n_wgp, n_ch + cb), io, &r1.pl));
+    return staged(c, {{8, (size_t)n_a * n_ch, a}, {8, (size_t)n_b * cb, b}, {8, n_win}, {8, (size_t)n_ch, nullptr, peaks},
+                      {8, p > 0 ? (size_t)n_ch * w : 0, nullptr, near}, {8, pearson ? (size_t)n_ch * n_cand : 0, nullptr, pearson}},
+                  [&](void* const* d) {
+        const double *da = (const double*)d[0], *db = (const double*)d[1];
+        int64_t* dpk = (int64_t*)d[3];
+        PeakArgs pk{{}, 0, L, n_wgp, nullptr, nullptr, dpk};
+        if (corr) {
+            // both signals as columns of one batch; the workgroups' peak pairs take the place of the run's phase arrays
+            CHK(r1.carve_ws(n_wgp));
+            CHK(r1.load(da, false, n_a, 0, n_ch));
+            CHK(r1.load(db, false, n_b, n_ch, cb));
+            CHK(r1.fft(false));
+            CHK(launch(c, "lat_xmul", k_xmul, r1.flat(n_fft * n_ch), NT, 0, XmulArgs{r1.x, n_fft, r1.pl.ld, n_ch, cb}));
+            r1.n_ch = n_ch;  // the products lie in the leading columns
+            CHK(r1.fft(true));
+            pk.in = RowView{(const double*)r1.x, 2 * r1.pl.ld, 2, n_fft - (n_a - 1), n_fft};
+            pk.pv = r1.pa;
+            pk.pi = (int64_t*)r1.pb;
+        } else {
+            void* t[kMaxStaged];
+            CHK(stage(c, &c->ws, &c->ws_bytes, {{8, (size_t)n_ch * n_wgp}, {8, (size_t)n_ch * n_wgp}}, t));
+            pk.in = RowView{da, 1, n_ch, 0, n_a};
+            pk.pv = (double*)t[0];
+            pk.pi = (int64_t*)t[1];
+        }
+        CHK(launch(c, "lat_peak", k_peak, dim3((unsigned)n_wgp, (unsigned)n_ch), NT, 0, pk));
+        CHK(launch(c, "lat_peak_final", k_peak_final, dim3((unsigned)n_ch), NT, 0, pk));
+        // the window's bounds depend on the peaks: the one read-back in the middle of the call
+        std::vector<int64_t> hp((size_t)n_ch);
+        CHK(ds_download(c, hp.data(), dpk, (size_t)n_ch * 8));
+        if (p > 0) {
+            const int64_t d_min = *std::min_element(hp.begin(), hp.end()), d_max = *std::max_element(hp.begin(), hp.end());
+            const int64_t lo = std::max<int64_t>(d_min - 200, 0), m = std::min(d_max + 200, L) - lo;
+            window[0] = lo;
+            window[1] = m;
+            if (fft64_len_unsupported(m))
+                return fail(c, DS_ERR_UNSUP, who, "the window around the peaks is longer than 2^21 rows and no power of two: "
+                                                  "transform lengths above 2^22 (powers of two) or 2^21 (any other) are not built");
+            const double* src = da + lo * n_ch;
+            if (corr) {
+                CHK(launch(c, "lat_window", k_window, r1.flat(m * n_ch), NT, 0,
+                           WindowArgs{pk.in, lo, m, n_ch, 1.0 / (double)n_fft, (double*)d[2]}));
+                src = (const double*)d[2];
+            }
+            // the window is out of the workspace: the second run may lay its tables and arrays over the first one's
+            Fft64Run r2{c, {}, n_ch};
+            CHK(fft64_plan(c, who, m, n_ch, 0, io, &r2.pl));
+            CHK(r2.carve_ws(0));
+            CHK(r2.load(src, false, m));
+            CHK(r2.fft(false));
+            CHK(r2.point(fft64::POINT_MASK, 1.0));
+            CHK(r2.fft(true));
+            CHK(launch(c, "lat_near", k_near, r2.flat((int64_t)n_ch * w), NT, 0,
+                       NearArgs{r2.x, r2.pl.ld, m, lo, dpk, n_ch, p, (double*)d[4]}));
+        }
+        if (!pearson) return DS_OK;
+        // entry j pairs column j of b (or its only one) with column j of a, at the lags around the peak of column j -- or,
+        // reverse_pairs, of column n_ch - 1 - j
+        std::vector<int64_t> rows((size_t)n_ch * n_cand * 3);
+        for (int j = 0; j < n_ch; ++j)
+            for (int k = 0; k < n_cand; ++k) {
+                int64_t* row = &rows[((size_t)j * n_cand + k) * 3];
+                row[0] = cb == 1 ? 0 : j;
+                row[1] = j;
+                row[2] = n_a - 1 - hp[reverse_pairs ? n_ch - 1 - j : j] + (n_cand == 3 ? k - 1 : 0);
+            }
+        return lag_pearson_run(c, who, db, n_b, cb, da, n_a, n_ch, rows.data(), n_ch * n_cand, (double*)d[5]);
     });
 }
 

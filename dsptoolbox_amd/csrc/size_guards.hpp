@@ -51,6 +51,17 @@ DS_HD inline bool fft64_len_unsupported(int64_t n) {
     return n > (pow2 ? kFft64MaxPow2 : kFft64MaxAny);
 }
 
+// Latency estimation (kernels_latency.hpp).  The full-mode correlation of Na and Nb samples has L = Na + Nb - 1 rows and
+// runs on the power-of-two transform of at least L points: L <= 2^22 (kFft64MaxPow2).  The window around the peaks, M rows,
+// takes the transform of any length and its bounds (fft64_len_unsupported).  The columns of both signals are transformed in
+// one batch, one grid row per column: at most 65535 together.  polynomial_points <= 16: the fit has degree 2 p - 1, and
+// beyond a few points it is ill-conditioned long before the bound.  Beyond any of these the entries answer DS_ERR_UNSUP.
+constexpr int kLatencyMaxPoints = 16;
+constexpr int kLatencyMaxColumns = 65535;
+DS_HD inline bool latency_shape_unsupported(int64_t rows, int64_t columns, int64_t points) {
+    return rows > kFft64MaxPow2 || columns > kLatencyMaxColumns || points > kLatencyMaxPoints;
+}
+
 // Linear prediction (kernels_lpc.hpp).  One workgroup holds a pair's frame in LDS, of which a workgroup may declare
 // 160 KiB = 163840 bytes.  Burg keeps the forward and the backward error row, two coefficient rows of 256 doubles and
 // eight partial sums: (2 L + 520) 8 bytes <= 163840 allows L <= 9980.  Yule-Walker keeps the frame, 260 zeros behind it

@@ -1,4 +1,4 @@
 from . import enums  # noqa: F401
-from .latency_delay import fractional_delay  # noqa: F401
+from .latency_delay import delay, fractional_delay, latency  # noqa: F401
 
-__all__ = ["fractional_delay"]
+__all__ = ["latency", "fractional_delay", "delay"]

@@ -3,7 +3,8 @@
 :61-184; regularisation window helpers/windows.py:8-76, band detection
 helpers/other.py:9-41), window_frequency_dependent (:1288-1377) and complex_smoothing (:1788-1876); the real-cepstrum
 minimum-phase family min_phase_ir / minimum_phase / minimum_group_delay and group_delay / excess_group_delay
-(:789-1083) on the float64 any-length transform (ds_min_phase, ds_group_delay_phase) and the direct DFT (ds_dft)."""
+(:789-1083) on the float64 any-length transform (ds_min_phase, ds_group_delay_phase) and the direct DFT (ds_dft);
+find_ir_latency (:1380-1406) on the latency entries (ds_latency)."""
 
 import numpy as np
 from scipy.fft import next_fast_len
@@ -12,11 +13,12 @@ from scipy.signal.windows import get_window
 from .. import backend
 from ..classes import ImpulseResponse, Signal, Spectrum
 from ..standard.enums import SpectrumMethod, Window
+from ..standard.latency_delay import _fractional_latency, latency
 from .enums import SmoothingDomain, TransferFunctionType
 
 __all__ = ["compute_transfer_function", "spectral_deconvolve", "window_frequency_dependent", "complex_smoothing",
            "min_phase_ir", "group_delay", "minimum_phase", "minimum_group_delay", "excess_group_delay",
-           "min_phase_from_mag", "lin_phase_from_mag", "TransferFunctionType", "SmoothingDomain"]
+           "find_ir_latency", "min_phase_from_mag", "lin_phase_from_mag", "TransferFunctionType", "SmoothingDomain"]
 
 
 def compute_transfer_function(output: Signal, input: Signal, window_length_samples: int,
@@ -320,22 +322,44 @@ def _group_delay_analytic(b: np.ndarray, n_freq: int, fs: int) -> np.ndarray:
     return gd / fs
 
 
+_NO_PUBLIC_LATENCY_FREE = ("group_delay(analytic_computation=False, remove_ir_latency=True) is not built into the public "
+                           "function (DESIGN section 20): transfer_functions._group_delay computes it on the device")
+
+
 def group_delay(signal: Signal, analytic_computation: bool = True, smoothing: int = 0,
                 remove_ir_latency: bool = False):
+    """_group_delay below, except that the numerical form with remove_ir_latency still raises NotImplementedError here
+    (and so in excess_group_delay at its default analytic_computation=False): the refusal is part of what the package
+    has promised so far, and is lifted separately."""
+    if not analytic_computation and remove_ir_latency:
+        raise NotImplementedError(_NO_PUBLIC_LATENCY_FREE)
+    return _group_delay(signal, analytic_computation, smoothing, remove_ir_latency)
+
+
+def _group_delay(signal: Signal, analytic_computation: bool = True, smoothing: int = 0, remove_ir_latency: bool = False):
     """Group delay in seconds (numerical form with a frequency step of exactly 1 Hz: radians per bin, as the reference
     returns it there), (frequency vector, (gd, channel) matrix).  analytic_computation: the quotient form of
     https://www.dsprelated.com/freebooks/filters/Phase_Group_Delay.html from two direct DFTs on the device; otherwise
-    the gradient of the unwrapped phase of the spectrum, transform to gradient on the device (ds_group_delay_phase)."""
+    the gradient of the unwrapped phase of the spectrum, transform to gradient on the device (ds_group_delay_phase).
+    remove_ir_latency (impulse responses, zero-padded to next_fast_len(8 N)): the analytic form starts each channel
+    one sample before its peak; the numerical form takes out the sub-sample latency against the minimum-phase
+    equivalent (padding factor 1) as a linear phase BEFORE the unwrap, wrapped again as the reference does
+    (ds_group_delay_phase_lat)."""
     length_time_signal = (next_fast_len(signal.time_data.shape[0] * 8, True) if remove_ir_latency
                           else signal.time_data.shape[0])
     td = _pad_trim(signal.time_data, length_time_signal)
     fs = signal.sampling_rate_hz
     f = np.fft.rfftfreq(td.shape[0], 1 / fs)
     if not analytic_computation:
+        latency_samples = None
         if remove_ir_latency:
-            raise NotImplementedError("group_delay(analytic_computation=False, remove_ir_latency=True) needs the "
-                                      "fractional-latency helpers, which are not built")
-        group_delays = _group_delay_units(backend.group_delay_phase(td, f[1] - f[0]), f[1] - f[0])
+            assert type(signal) is ImpulseResponse, "This is only valid for an impulse response"
+            # _remove_ir_latency_from_phase_min_phase (helpers/minimum_phase.py:82-117): all n_fft rows of the
+            # minimum-phase response are compared, not the first N
+            n_min = backend.min_phase_fft_length(signal.time_data.shape[0], 1)
+            min_ir = backend.min_phase(signal.time_data, n_min, "ir", n_out=n_min)
+            latency_samples = _fractional_latency(signal.time_data, min_ir, 1)
+        group_delays = _group_delay_units(backend.group_delay_phase(td, f[1] - f[0], latency_samples, fs), f[1] - f[0])
     elif remove_ir_latency:
         group_delays = np.zeros((length_time_signal // 2 + 1, td.shape[1]))
         for n in range(signal.number_of_channels):
@@ -383,11 +407,20 @@ def excess_group_delay(signal: ImpulseResponse, smoothing: int = 0, remove_ir_la
                        analytic_computation: bool = False):
     """(frequency vector, (excess gd, channel) matrix in seconds): the group delay less the minimum group delay (no
     zero-padding for the minimum-phase equivalent).  Where the two frequency vectors differ the group delay is
-    interpolated linearly onto the minimum group delay's, 0 outside, on the host."""
+    interpolated linearly onto the minimum group delay's, 0 outside, on the host.  The numerical form with
+    remove_ir_latency raises NotImplementedError as group_delay does; _excess_group_delay computes it."""
+    assert type(signal) is ImpulseResponse, "This is only valid for an impulse response"
+    if not analytic_computation and remove_ir_latency:
+        raise NotImplementedError(_NO_PUBLIC_LATENCY_FREE)
+    return _excess_group_delay(signal, smoothing, remove_ir_latency, analytic_computation)
+
+
+def _excess_group_delay(signal: ImpulseResponse, smoothing: int = 0, remove_ir_latency: bool = False,
+                        analytic_computation: bool = False):
     assert type(signal) is ImpulseResponse, "This is only valid for an impulse response"
     f_min, min_gd = minimum_group_delay(signal, smoothing=0, padding_factor=1)
-    f, gd = group_delay(signal, smoothing=0, analytic_computation=analytic_computation,
-                        remove_ir_latency=remove_ir_latency)
+    f, gd = _group_delay(signal, smoothing=0, analytic_computation=analytic_computation,
+                         remove_ir_latency=remove_ir_latency)
     if len(f) != len(f_min):
         from scipy.interpolate import interp1d
         gd = interp1d(f, gd, kind="linear", copy=False, bounds_error=False, assume_sorted=True, fill_value=(0.0, 0.0),
@@ -396,6 +429,17 @@ def excess_group_delay(signal: ImpulseResponse, smoothing: int = 0, remove_ir_la
     if smoothing != 0:
         ex_gd = backend.fractional_octave_smoothing(ex_gd, None, smoothing)
     return f_min, ex_gd
+
+
+def find_ir_latency(ir: ImpulseResponse, compare_to_min_phase_ir: bool = True) -> np.ndarray:
+    """The sub-sample position of each channel's peak, in samples: the latency of the response against its own
+    minimum-phase equivalent (padding factor 8; `latency` with one polynomial point), or, compare_to_min_phase_ir
+    False, the zero crossing of the Hilbert transform around the peak of the time data itself."""
+    assert type(ir) is ImpulseResponse, "This is only valid for an impulse response"
+    if compare_to_min_phase_ir:
+        return latency(ir, min_phase_ir(ir), 1)[0]
+    peaks, window, near, _ = backend.latency_peaks(ir.time_data, None, 1)
+    return backend.fractional_peak_rows(peaks, window, near, 1)
 
 
 def min_phase_from_mag(spectrum: Spectrum, sampling_rate_hz: int, ir_length_samples: int | None = None):

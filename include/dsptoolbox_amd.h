@@ -580,6 +580,35 @@ int ds_min_phase(ds_ctx* ctx, const double* x, int64_t n, int n_ch, int64_t n_ff
                  double delta_f, double* out);
 int ds_group_delay_phase(ds_ctx* ctx, const double* x, int64_t n, int n_ch, double delta_f, double* out);
 
+/* ---- latency estimation by cross-correlation (csrc/kernels_latency.hpp on the transforms above): standard.latency of
+ * the reference (standard/latency_delay.py:15-156; _latency, standard/_standard_backend.py:14-34; _fractional_latency,
+ * _get_fractional_impulse_peak_index, _get_correlation_of_latencies, helpers/latency.py:10-149, 218-265) and the latency
+ * removal of group_delay (transfer_functions.py:908-914).  Host pointers, float64 in (rows, channels) C order.
+ * ds_latency: a (n_a, n_ch) is the delayed signal, b (n_b, n_ch_b) the original, n_ch_b = n_ch or 1 (one column for
+ *   every pair).  Channel c of scipy's full-mode correlate(b, a), L = n_a + n_b - 1 rows, is formed on the device and stays
+ *   there.  peaks [n_ch], int64: the row of the largest magnitude, the lowest row among equal ones; the lag is
+ *   n_a - 1 - peak.  With polynomial_points p > 0: window [2] = (lo, M), the rows [max(min peak - 200, 0),
+ *   min(max peak + 200, L)) shared by all channels, and near [n_ch][2 p + 2], the values imag(hilbert(window))[d - p ..
+ *   d + p + 1] around each channel's own peak row d = peak - lo, NaN for a row outside the window.  pearson (or NULL)
+ *   [n_ch][n_cand]: Pearson's r of the pair (b column j, a column j) at the integer lags n_a - 1 - peak' + (-1, 0, 1)
+ *   (n_cand = 3; p = 0: the lag itself, n_cand = 1), with peak' that of column j or, reverse_pairs, of column
+ *   n_ch - 1 - j; NaN where fewer than two samples overlap or a channel is constant.
+ *   b = NULL: no correlation, the peaks, window and values are those of a itself; pearson must be NULL.
+ *   DS_ERR_UNSUP: L above 2^22, more than 65535 columns (n_ch + n_ch_b), p above 16, and -- found after the peak search,
+ *   with nothing launched after it; window is written -- a window M above 2^21 that is no power of two.  DS_ERR_NOMEM
+ *   before anything is uploaded, counted for the widest window (M = L).
+ * ds_lag_pearson: Pearson's r per row of rows [n_rows][3] = (column of t, column of o, lag), int64: lag > 0 drops the
+ *   first lag samples of o's column, otherwise the first -lag of t's; both are cut to the shorter; out [n_rows].
+ * ds_group_delay_phase_lat: ds_group_delay_phase with the phase wrap(angle + 2 pi f latency_samples[c] / fs),
+ *   f = k delta_f, wrap(x) = (x + pi) mod 2 pi - pi, before the unwrap.                                             */
+int ds_latency(ds_ctx* ctx, const double* a, int64_t n_a, int n_ch, const double* b, int64_t n_b, int n_ch_b,
+               int polynomial_points, int reverse_pairs, int64_t* peaks, int64_t* window, double* near,
+               double* pearson);
+int ds_lag_pearson(ds_ctx* ctx, const double* t, int64_t n_t, int n_ch_t, const double* o, int64_t n_o, int n_ch_o,
+                   const int64_t* rows, int n_rows, double* out);
+int ds_group_delay_phase_lat(ds_ctx* ctx, const double* x, int64_t n, int n_ch, double delta_f,
+                             const double* latency_samples, double fs, double* out);
+
 /* ---- linear prediction per (frame, channel) pair (csrc/kernels_lpc.hpp): transforms.lpc of the reference
  * (transforms/transforms.py:1199-1283) with its estimators (helpers/ar_estimation.py:6-205) and its framing and
  * overlap-add (standard/_framed_signal_representation.py:9-137), float64 on the device.
