@@ -39,6 +39,7 @@ NO_SCRATCH = [
     "k_ism_count", "k_ism_scan", "k_ism_fill", "k_ism_sum", "k_modal_tf",
     "5dslat6k_xmul", "5dslat6k_peak", "5dslat12k_peak_final", "5dslat8k_window", "5dslat6k_near", "5dslat13k_lag_partial",
     "5dslat11k_lag_final", "5dslat11k_lat_phase",
+    "k_vqt_decimate", "k_vqt_bank", "k_vqt_interp",
 ]
 
 

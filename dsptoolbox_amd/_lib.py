@@ -172,6 +172,9 @@ SIGNATURES = {
     "ds_room_ism": (C.c_int, [ctx_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_int, C.c_void_p, C.c_int,
                               i64, i64, C.c_void_p]),
     "ds_room_modal_tf": (C.c_int, [ctx_p, C.c_void_p, C.c_void_p, C.c_void_p, i64, C.c_void_p, i64, C.c_void_p]),
+    "ds_vqt": (C.c_int, [ctx_p, C.c_void_p, C.c_int, C.c_int, i64, i64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
+    "ds_resample_int": (C.c_int, [ctx_p, C.c_void_p, i64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "ds_welch_tf_x64": (C.c_int, [ctx_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, i64, C.c_int, C.c_int, C.c_int,
                                   C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int,
                                   C.c_void_p, C.c_void_p]),

@@ -2456,3 +2456,152 @@ def room_modal_response(omega_n, eta, weight, omega2) -> np.ndarray:
     ctx.check(ctx.lib.ds_room_modal_tf(ctx.handle, _ptr(omega_n), _ptr(eta), _ptr(weight), len(omega_n), _ptr(omega2),
                                        len(omega2), _ptr(p)), "ds_room_modal_tf")
     return p
+
+
+# ---- variable-Q transform (ds_vqt, ds_resample_int; csrc/kernels_vqt.hpp) ---------------------------------------------
+VQT_MAX_OUTPUT_BYTES = 1 << 34  # the complex128 result (csrc/size_guards.hpp; DS_ERR_UNSUP above)
+VQT_MAX_DECIMATION = 48         # d: the decimator stages 83 d + 1 samples of four channels in LDS
+VQT_MAX_OCTAVES = 7             # the first interpolation stage goes up by 2^octave, at most 64
+VQT_MAX_KERNEL = 2048           # taps of one kernel, staged in LDS beside the samples it meets
+VQT_MAX_ROWS = 65535            # octaves x bins, and the channel groups of four
+VQT_SAMPLE_TILE = {1: 256, 2: 128}  # samples per workgroup of k_vqt_decimate and k_vqt_bank by channel count; else 64
+
+
+def _vqt_interp_tile(up: int, n_ch: int) -> int:
+    """Output samples of one row a workgroup of k_vqt_interp takes (interp_span of the kernels, times `up`)."""
+    cg = 1 if n_ch == 1 else 2 if n_ch == 2 else 4
+    return 4 * min(max(4 * 256 // (up * cg), 1), 128) * up
+
+
+def _resample_taps(up: int, down: int) -> np.ndarray:
+    """The filter scipy.signal.resample_poly designs by default for an integer ratio: up * firwin(20 r + 1, 1 / r,
+    window=("kaiser", 5.0)) with r = max(up, down); the single tap 1.0 for r = 1, where scipy returns a copy."""
+    from scipy.signal import firwin
+    r = max(int(up), int(down))
+    if r == 1:
+        return np.ones(1)
+    h = firwin(20 * r + 1, 1.0 / r, window=("kaiser", 5.0))
+    h *= up
+    return h
+
+
+class _VqtPlan(NamedTuple):
+    d: int              # the first decimation
+    mid_fs: int         # fs // d: an integer, not the true rate (kept from the reference)
+    n_oct: int
+    bins: int
+    kernel_len: np.ndarray   # int64 [bins]
+    kernel_taps: np.ndarray  # complex128, the kernels back to back
+    taps_dec: np.ndarray
+    taps_half: np.ndarray
+    taps_up: np.ndarray      # 2^o firwin(20 2^o + 1) for o = 1 .. n_oct - 1, then d firwin(20 d + 1)
+
+
+def _vqt_kernels(q: float, highest_f: float, bins: int, mid_fs: int, window, gamma: float) -> list:
+    """transforms/_transforms.py:327-383: the complex kernels of one octave, the highest frequency first."""
+    freqs = highest_f * 2 ** (-1 / bins * np.arange(bins))
+    factor = 2 ** (1 / bins) - 1
+    lengths = np.round(q * mid_fs / ((freqs * factor) + gamma)).astype(int)
+    kernels = []
+    for ind in range(len(lengths)):
+        w = get_window(window, lengths[ind], fftbins=False)
+        w /= w.sum()
+        kernels.append(w * np.exp(1j * freqs[ind] * 2 * np.pi / mid_fs * np.arange(-lengths[ind] // 2, lengths[ind] // 2)))
+    return kernels
+
+
+def _vqt_guard(n_samples: int, n_ch: int, d: int, n_oct: int, bins: int, longest_kernel: int) -> None:
+    """NotImplementedError for a transform beyond the kernels' bounds, each named, before anything reaches the device."""
+    rows = n_oct * bins
+    if d > VQT_MAX_DECIMATION:
+        raise NotImplementedError(f"vqt: a decimation of {d} is beyond VQT_MAX_DECIMATION = {VQT_MAX_DECIMATION} "
+                                  "(the sampling rate is too far above the highest octave)")
+    if n_oct > VQT_MAX_OCTAVES:
+        raise NotImplementedError(f"vqt: {n_oct} octaves are beyond VQT_MAX_OCTAVES = {VQT_MAX_OCTAVES}")
+    if longest_kernel > VQT_MAX_KERNEL:
+        raise NotImplementedError(f"vqt: a kernel of {longest_kernel} taps is beyond VQT_MAX_KERNEL = {VQT_MAX_KERNEL}")
+    if rows > VQT_MAX_ROWS or (n_ch + 3) // 4 > VQT_MAX_ROWS:
+        raise NotImplementedError(f"vqt: {rows} rows or {n_ch} channels are beyond VQT_MAX_ROWS = {VQT_MAX_ROWS} "
+                                  "(rows, and channel groups of four)")
+    if 16.0 * rows * n_samples * n_ch > VQT_MAX_OUTPUT_BYTES:
+        raise NotImplementedError(f"vqt: a result of {16.0 * rows * n_samples * n_ch:.3g} bytes is beyond "
+                                  f"VQT_MAX_OUTPUT_BYTES = 2^34")
+
+
+def _vqt_plan(n_samples: int, n_ch: int, fs: int, q: float, gamma: float, octaves, bins_per_octave: int, a4_tuning,
+              window) -> _VqtPlan:
+    """The reference's setup (transforms/transforms.py:876-890) and the tap tables, on the host in float64.
+    ZeroDivisionError when the top octave lies above Nyquist / 1.1 (d = 0), as in the reference."""
+    fs = int(fs)  # (a numpy integer would divide by zero silently)
+    highest_f = a4_tuning * 2 ** (octaves[1] - 4 + 2 / 12)
+    d = int((fs // 2) / (highest_f * 1.1))
+    mid_fs = fs // d
+    n_oct = int(octaves[1] - octaves[0] + 1)
+    bins = int(bins_per_octave)
+    if n_oct < 1 or bins < 1:
+        raise ValueError("vqt: needs at least one octave and one bin per octave")
+    gamma = gamma / fs * mid_fs
+    freqs = highest_f * 2 ** (-1 / bins * np.arange(bins))
+    lengths = np.round(q * mid_fs / ((freqs * (2 ** (1 / bins) - 1)) + gamma)).astype(int)
+    if lengths.min() < 1:
+        raise ValueError("vqt: a kernel has no taps")
+    _vqt_guard(n_samples, n_ch, d, n_oct, bins, int(lengths.max()))
+    kernels = _vqt_kernels(q, highest_f, bins, mid_fs, window, gamma)
+    ups = [_resample_taps(1 << o, 1) for o in range(1, n_oct)] + [_resample_taps(d, 1)]
+    return _VqtPlan(d, mid_fs, n_oct, bins, np.array([len(k) for k in kernels], dtype=np.int64),
+                    np.ascontiguousarray(np.concatenate(kernels), dtype=np.complex128), _resample_taps(1, d),
+                    _resample_taps(1, 2), np.ascontiguousarray(np.concatenate(ups)))
+
+
+def vqt(samples, fs: int, q: float = 1, gamma: float = 50, octaves=(1, 5), bins_per_octave: int = 24, a4_tuning=440,
+        window="hann", on_device: bool = False):
+    """The variable-Q coefficients (octaves x bins, samples, channels) complex128 of `samples`: (N, C) float64 on the
+    host, or a `DevicePlanar` whose float32 samples are read where they lie.  The decimators, the kernel bank and the
+    polyphase interpolators run on the device in float64 (ds_vqt).  Returns the array, or with `on_device` a
+    `DeviceScalogram` left in HBM."""
+    resident = isinstance(samples, DevicePlanar)
+    if resident:
+        n, n_ch = samples.n_samples, samples.n_ch
+    else:
+        samples = np.ascontiguousarray(samples, dtype=np.float64)
+        assert samples.ndim == 2, "the samples are (samples, channels)"
+        n, n_ch = samples.shape
+    if n < 1 or n_ch < 1:
+        raise ValueError("vqt: needs at least one sample and one channel")
+    p = _vqt_plan(n, n_ch, fs, q, gamma, octaves, bins_per_octave, a4_tuning, window)
+    shape = (p.n_oct * p.bins, n, n_ch)
+    ctx = samples.ctx if resident else get_context()
+    head = (C.c_void_p(samples.ptr), 1, n_ch, samples.ld, n) if resident else (_ptr(samples), 0, n_ch, n, n)
+    tables = (p.d, p.n_oct, p.bins, _ptr(p.kernel_len), _ptr(p.kernel_taps), _ptr(p.taps_dec), _ptr(p.taps_half),
+              _ptr(p.taps_up))
+    if not on_device:
+        out = np.empty(shape, dtype=np.complex128)
+        ctx.check(ctx.lib.ds_vqt(ctx.handle, *head, *tables, _ptr(out), 0), "ds_vqt")
+        return out
+    with device_scope(ctx) as dev:
+        buf = dev.alloc(16 * shape[0] * n * n_ch, result=True)
+        ctx.check(ctx.lib.ds_vqt(ctx.handle, *head, *tables, C.c_void_p(buf.ptr), 1), "ds_vqt")
+        ctx.sync()
+    return DeviceScalogram(buf, shape, np.complex128)
+
+
+def resample_int(td, up: int, down: int) -> np.ndarray:
+    """scipy.signal.resample_poly(td, up, down, axis=0) with its default filter for real (n, C) float64 data and an
+    integer ratio (one of `up` and `down` is 1), on the device in float64 (ds_resample_int): the stage the variable-Q
+    transform is built from, here by itself."""
+    up, down = int(up), int(down)
+    if up < 1 or down < 1 or (up != 1 and down != 1):
+        raise ValueError("resample_int: one of up and down must be 1, the other a positive integer")
+    if down > VQT_MAX_DECIMATION or up > 1 << (VQT_MAX_OCTAVES - 1):
+        raise NotImplementedError(f"resample_int: down beyond VQT_MAX_DECIMATION = {VQT_MAX_DECIMATION} or up beyond "
+                                  f"{1 << (VQT_MAX_OCTAVES - 1)}")
+    x = np.ascontiguousarray(td, dtype=np.float64)
+    assert x.ndim == 2, "the samples are (samples, channels)"
+    n, n_ch = x.shape
+    if n < 1 or n_ch < 1:
+        raise ValueError("resample_int: needs at least one sample and one channel")
+    out = np.empty((-(-n * up // down), n_ch))
+    taps = _resample_taps(up, down)
+    ctx = get_context()
+    ctx.check(ctx.lib.ds_resample_int(ctx.handle, _ptr(x), n, n_ch, up, down, _ptr(taps), _ptr(out)), "ds_resample_int")
+    return out

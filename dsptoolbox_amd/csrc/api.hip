@@ -56,6 +56,7 @@
 #include "kernels_warp.hpp"
 #include "kernels_sfilt.hpp"
 #include "kernels_room.hpp"
+#include "kernels_vqt.hpp"
 #include "size_guards.hpp"
 
 using namespace dsk;
@@ -5063,6 +5064,168 @@ extern "C" int ds_room_modal_tf(ds_ctx* c, const double* omega_n, const double* 
         return launch(c, "room_modal_tf", k_modal_tf, dim3((unsigned)((nf + MODAL_NT - 1) / MODAL_NT)), MODAL_NT, 0,
                       ModalArgs{(const double*)d[0], (const double*)d[1], (const double*)d[2], n_modes,
                                 (const double*)d[3], n_freq, (double2*)d[4]});
+    });
+}
+
+// ---- variable-Q transform and its integer-ratio resampler (kernels_vqt.hpp) --------------------------------------------
+// taps of scipy's default resample_poly filter for the rate r; a rate of 1 is the one-tap copy
+static int vqt_rate_taps(int r) { return r == 1 ? 1 : 20 * r + 1; }
+
+// P(x, 1, D): sample n of channel ch at x[n ss + ch cs] -> out (n_out, n_ch) float64; h: device, vqt_rate_taps(D) taps
+template <typename T>
+static int vqt_decimate(ds_ctx* c, const T* x, int64_t ss, int64_t cs, int64_t n_in, int n_ch, const double* h, int D,
+                        double* out, int64_t n_out) {
+    using namespace dsvqt;
+    const int cg = ch_group(n_ch), dt = NT / cg, ntaps = vqt_rate_taps(D);
+    return launch(c, "vqt_decimate", k_vqt_decimate<T>, dim3((unsigned)((n_out + dt - 1) / dt), (unsigned)((n_ch + cg - 1) / cg)),
+                  NT, dec_lds_doubles(ntaps, D, cg) * 8, DecArgs<T>{x, ss, cs, n_in, n_ch, cg, h, ntaps, D, out, n_out});
+}
+
+// One interpolation launch over the octaves oc[0 .. n_e) (a device table; host_oc its host copy), `rows` rows each.
+template <typename V>
+static int vqt_interp(ds_ctx* c, const char* name, const V* in, V* out, const double* taps, const dsvqt::InterpOct* oc,
+                      const dsvqt::InterpOct* host_oc, int n_e, int rows, int n_ch) {
+    using namespace dsvqt;
+    const int cg = ch_group(n_ch);
+    int64_t tiles = 0;
+    size_t lds = 0;
+    for (int e = 0; e < n_e; ++e) {  // (the octaves of one launch share HW: every rate is above 1, or it is d = 1)
+        const int64_t tile = (int64_t)interp_span((int)host_oc[e].U, cg) * host_oc[e].U;
+        tiles = std::max(tiles, (host_oc[e].n_out + tile - 1) / tile);
+        lds = std::max(lds, interp_lds_bytes((int)host_oc[e].U, (int)host_oc[e].HW, cg, sizeof(V)));
+    }
+    if (tiles < 1) return DS_OK;
+    if (tiles > INT32_MAX) return fail(c, DS_ERR_UNSUP, "vqt: more sample tiles than one launch covers");
+    const dim3 grid((unsigned)tiles, (unsigned)((n_ch + cg - 1) / cg), (unsigned)(n_e * rows));
+    const InterpArgs<V> a{in, out, taps, oc, n_ch, cg, rows};
+    if (host_oc[0].HW == 0) return launch(c, name, k_vqt_interp<V, 0>, grid, NT, lds, a);
+    return launch(c, name, k_vqt_interp<V, 10>, grid, NT, lds, a);
+}
+
+struct VqtCall {
+    const char* who;
+    int64_t n_samples;
+    int n_ch, d, n_oct, bins;
+    const int64_t* kernel_len;
+    const double *kernel_taps, *taps_dec, *taps_half, *taps_up;
+};
+
+// x: the samples on the device (T = double: interleaved, staged by the entry; T = float: planar where they lie);
+// out: the device's (n_oct bins, n_samples, n_ch) complex128 result
+template <typename T>
+static int vqt_run(ds_ctx* c, const VqtCall& q, const T* x, int64_t ss, int64_t cs, double2* out) {
+    using namespace dsvqt;
+    const int C = q.n_ch, bins = q.bins, n_oct = q.n_oct, F = n_oct * bins;
+    const int64_t N = q.n_samples;
+    // octave lengths: len(td_0) = ceil(N / d), then halved (rounding up) per octave.  len(td_o) 2^o >= len(td_0) and
+    // len(td_0) d >= N, so every interpolated row reaches N samples: the reference's zero-padding branch is never taken
+    // and is not built.
+    int64_t M[MAX_OCT], td_off[MAX_OCT], z_off[MAX_OCT], y_off[MAX_OCT], n_td = 0, n_z = 0, n_y = 0;
+    for (int o = 0; o < n_oct; ++o) {
+        M[o] = o == 0 ? (N + q.d - 1) / q.d : (M[o - 1] + 1) / 2;
+        td_off[o] = n_td;
+        z_off[o] = n_z;
+        y_off[o] = n_y;
+        n_td += M[o] * C;
+        n_z += (int64_t)bins * M[o] * C;
+        if (o > 0) n_y += (int64_t)bins * (M[o] << o) * C;
+    }
+    // the tables of the launches: the kernels' (first tap, length), the bank's octaves, the two interpolation stages'
+    std::vector<int64_t> kdesc(2 * (size_t)bins);
+    int64_t n_ktaps = 0, lmax = 0;
+    for (int i = 0; i < bins; ++i) {
+        kdesc[2 * i] = n_ktaps;
+        kdesc[2 * i + 1] = q.kernel_len[i];
+        n_ktaps += q.kernel_len[i];
+        lmax = std::max(lmax, q.kernel_len[i]);
+    }
+    std::vector<BankOct> boct(n_oct);
+    std::vector<InterpOct> first, last(n_oct);
+    int64_t up_off = 0;
+    for (int o = 0; o < n_oct; ++o) {
+        boct[o] = BankOct{td_off[o], z_off[o], M[o]};
+        if (o > 0) {
+            first.push_back(InterpOct{z_off[o], M[o], y_off[o], M[o] << o, 0, 1, up_off, (int64_t)1 << o, 10});
+            up_off += vqt_rate_taps(1 << o);
+        }
+    }
+    for (int o = 0; o < n_oct; ++o)  // octave 0 is read from the bank's rows, the others from the first stage's
+        last[o] = InterpOct{o == 0 ? z_off[0] : n_z + y_off[o], M[o] << o, 0, N, F - 1 - (int64_t)o * bins, -1, up_off, q.d,
+                            q.d == 1 ? 0 : 10};
+    const size_t n_up = (size_t)up_off + vqt_rate_taps(q.d), n_first = first.size();
+    void* t[kMaxStaged];
+    CHK(stage(c, &c->ws, &c->ws_bytes, {{8, kdesc.size(), kdesc.data()}, {sizeof(BankOct), (size_t)n_oct, boct.data()},
+                                        {sizeof(InterpOct), n_first, first.data()}, {sizeof(InterpOct), (size_t)n_oct, last.data()},
+                                        {16, (size_t)n_ktaps, q.kernel_taps}, {8, (size_t)vqt_rate_taps(q.d), q.taps_dec},
+                                        {8, (size_t)vqt_rate_taps(2), q.taps_half}, {8, n_up, q.taps_up}, {8, (size_t)n_td},
+                                        {16, (size_t)(n_z + n_y)}}, t));
+    const double *h_dec = (const double*)t[5], *h_half = (const double*)t[6], *h_up = (const double*)t[7];
+    double* td = (double*)t[8];
+    double2* zy = (double2*)t[9];  // the bank's rows of every octave, then the first stage's
+    CHK(vqt_decimate<T>(c, x, ss, cs, N, C, h_dec, q.d, td, M[0]));
+    for (int o = 1; o < n_oct; ++o)
+        CHK(vqt_decimate<double>(c, td + td_off[o - 1], C, 1, M[o - 1], C, h_half, 2, td + td_off[o], M[o]));
+    const int cg = ch_group(C), bt = NT / cg;
+    CHK(launch(c, "vqt_bank", k_vqt_bank, dim3((unsigned)((M[0] + bt - 1) / bt), (unsigned)((C + cg - 1) / cg), (unsigned)F), NT,
+               bank_lds_bytes((int)lmax, cg),
+               BankArgs{td, (const BankOct*)t[1], (const int64_t*)t[0], (const double2*)t[4], zy, C, cg, bins}));
+    if (n_first)
+        CHK(vqt_interp<double2>(c, "vqt_interp_octave", zy, zy + n_z, h_up, (const InterpOct*)t[2], first.data(), (int)n_first,
+                                bins, C));
+    return vqt_interp<double2>(c, "vqt_interp", zy, out, h_up, (const InterpOct*)t[3], last.data(), n_oct, bins, C);
+}
+
+extern "C" int ds_vqt(ds_ctx* c, const void* x, int x_on_device, int n_ch, int64_t ldx, int64_t n_samples, int d, int n_oct,
+                      int bins, const int64_t* kernel_len, const double* kernel_taps, const double* taps_dec,
+                      const double* taps_half, const double* taps_up, void* out, int out_on_device) {
+    const char* who = "ds_vqt";
+    if (!c || !x || !out || !kernel_len || !kernel_taps || !taps_dec || !taps_half || !taps_up)
+        return fail(c, DS_ERR_ARG, who, "null argument");
+    if (n_samples < 1 || n_ch < 1 || d < 1 || n_oct < 1 || bins < 1 || (x_on_device && ldx < n_samples))
+        return fail(c, DS_ERR_ARG, who, "bad shape");
+    int64_t lmax = 0;
+    for (int i = 0; i < bins; ++i) {
+        if (kernel_len[i] < 1) return fail(c, DS_ERR_ARG, who, "a kernel has no taps");
+        lmax = std::max(lmax, kernel_len[i]);
+    }
+    const int64_t rows = (int64_t)n_oct * bins;
+    if (vqt_shape_unsupported(d, n_oct, lmax, rows, n_ch))
+        return fail(c, DS_ERR_UNSUP, who, "beyond d <= 48, octaves <= 7, kernels of 2048 taps or 65535 rows or channel groups");
+    if (vqt_output_too_large(rows, n_samples, n_ch)) return fail(c, DS_ERR_UNSUP, who, "the result is larger than 2^34 bytes");
+    HIPCHK(c, hipSetDevice(c->device));
+    const VqtCall q{who, n_samples, n_ch, d, n_oct, bins, kernel_len, kernel_taps, taps_dec, taps_half, taps_up};
+    const size_t n_x = x_on_device ? 0 : (size_t)n_samples * n_ch, n_out = out_on_device ? 0 : (size_t)rows * n_samples * n_ch;
+    // the workspace: the decimated samples (at most 2 (N / d + 2) C), the bank's rows (twice that per bin) and the first
+    // stage's (N / d + 64 per row)
+    const size_t m0 = (size_t)((n_samples + d - 1) / d) + 2;
+    CHK(mem_check(c, who, 16 * m0 * n_ch + 32 * (size_t)rows * (m0 + 64) * n_ch + ((size_t)1 << 20), (n_x * 8 + n_out * 16), 0));
+    return staged(c, {{8, n_x, x}, {16, n_out, nullptr, out_on_device ? nullptr : out}}, [&](void* const* s) {
+        double2* dout = out_on_device ? (double2*)out : (double2*)s[1];
+        if (x_on_device) return vqt_run<float>(c, q, (const float*)x, 1, ldx, dout);
+        return vqt_run<double>(c, q, (const double*)s[0], n_ch, 1, dout);
+    });
+}
+
+extern "C" int ds_resample_int(ds_ctx* c, const double* x, int64_t n, int n_ch, int up, int down, const double* taps,
+                               double* out) {
+    using namespace dsvqt;
+    const char* who = "ds_resample_int";
+    if (!c || !x || !taps || !out) return fail(c, DS_ERR_ARG, who, "null argument");
+    if (n < 1 || n_ch < 1 || up < 1 || down < 1 || (up != 1 && down != 1))
+        return fail(c, DS_ERR_ARG, who, "needs samples, channels and an integer ratio: one of up and down is 1");
+    if (down > kVqtMaxDecimation || up > (1 << (kVqtMaxOctaves - 1)) || (n_ch + 3) / 4 > kVqtMaxRows)
+        return fail(c, DS_ERR_UNSUP, who, "beyond down <= 48, up <= 64 or 65535 channel groups");
+    const int64_t n_out = down == 1 ? n * up : (n + down - 1) / down;
+    if ((double)n_out * n_ch * 8.0 > (double)kVqtMaxOutputBytes) return fail(c, DS_ERR_UNSUP, who, "the result is larger than 2^34 bytes");
+    HIPCHK(c, hipSetDevice(c->device));
+    const int r = std::max(up, down);
+    const InterpOct oc{0, n, 0, n_out, 0, 1, 0, up, up == 1 ? 0 : 10};
+    return staged(c, {{8, (size_t)n * n_ch, x}, {8, (size_t)n_out * n_ch, nullptr, out}}, [&](void* const* s) {
+        void* t[kMaxStaged];
+        CHK(stage(c, &c->ws, &c->ws_bytes, {{8, (size_t)vqt_rate_taps(r), taps}, {sizeof(InterpOct), 1, &oc}}, t));
+        if (down > 1) return vqt_decimate<double>(c, (const double*)s[0], n_ch, 1, n, n_ch, (const double*)t[0], down, (double*)s[1], n_out);
+        return vqt_interp<double>(c, "vqt_interp@real", (const double*)s[0], (double*)s[1], (const double*)t[0],
+                                  (const InterpOct*)t[1], &oc, 1, 1, n_ch);
     });
 }
 

@@ -132,3 +132,26 @@ DS_HD inline int64_t ism_slab_planes(int64_t limit, int64_t list_bytes) {
 DS_HD inline bool modal_work_too_large(int64_t n_modes, int64_t n_freq) {
     return (double)n_modes * (double)n_freq > kModalMaxWork;
 }
+
+// Variable-Q transform (kernels_vqt.hpp).  The result, octaves x bins rows of samples x channels complex128, is written
+// once by the last interpolation stage: at most 2^34 bytes (the 2 channel x 2^20 sample call at the defaults writes
+// 2^32).  The workspace beside it (the decimated samples, the bank's rows and the first interpolation stage) is
+// (octaves + 1) / d of that.  The other bounds are what the LDS staging of a workgroup holds, 160 KiB:
+//   d <= 48        k_vqt_decimate stages (255 d + 20 d + 1) samples of one channel, or (63 d + 20 d + 1) of four, and
+//                  the 20 d + 1 taps: 135208 bytes at d = 48 with four channels;
+//   octaves <= 7   the first interpolation stage goes up by 2^o, at most 64: 21 x 64 taps, 10752 bytes;
+//   L_i <= 2048    k_vqt_bank stages a kernel's L complex taps and 64 + L - 1 samples of four channels: 100320 bytes.
+// grid.z carries octaves x bins and grid.y the channel groups of four: at most 65535 each.  Beyond any of these the
+// entries answer DS_ERR_UNSUP.
+constexpr int64_t kVqtMaxOutputBytes = (int64_t)1 << 34;
+constexpr int kVqtMaxDecimation = 48;
+constexpr int kVqtMaxOctaves = 7;
+constexpr int kVqtMaxKernel = 2048;
+constexpr int kVqtMaxRows = 65535;
+DS_HD inline bool vqt_output_too_large(int64_t rows, int64_t n_samples, int64_t n_ch) {
+    return (double)rows * (double)n_samples * (double)n_ch * 16.0 > (double)kVqtMaxOutputBytes;
+}
+DS_HD inline bool vqt_shape_unsupported(int64_t d, int64_t n_oct, int64_t longest_kernel, int64_t rows, int64_t n_ch) {
+    return d > kVqtMaxDecimation || n_oct > kVqtMaxOctaves || longest_kernel > kVqtMaxKernel || rows > kVqtMaxRows ||
+           (n_ch + 3) / 4 > kVqtMaxRows;
+}

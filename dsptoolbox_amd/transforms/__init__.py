@@ -7,7 +7,8 @@ kernel (ds_allpass_table).  Same signature, parameter handling and quirks as the
 the frame-wise inverse FFTs and the windowed overlap-add with the squared-window envelope
 (standard/_framed_signal_representation.py:70-137) run in the HIP library (ds_istft).  The continuous wavelet
 transform cwt with Wavelet / MorletWavelet (:687-760, transforms/_transforms.py:29-301) lives in _wavelets.py.
-dft (:1286-1327) is the direct sum at arbitrary frequencies (ds_dft)."""
+dft (:1286-1327) is the direct sum at arbitrary frequencies (ds_dft).  vqt (:812-923, transforms/_transforms.py:327-383)
+runs its decimators, its kernel bank and its polyphase interpolators in float64 on the device (ds_vqt)."""
 
 from __future__ import annotations
 
@@ -22,7 +23,7 @@ from ..standard.enums import FilterCoefficientsType, Window
 from ._wavelets import MorletWavelet, Wavelet, cwt  # noqa: F401
 
 __all__ = ["istft", "mel_filterbank", "log_mel_spectrogram", "mfcc", "chroma_stft", "cwt", "Wavelet", "MorletWavelet",
-           "dft", "hilbert", "cepstrum", "from_complex_cepstrum", "lpc", "warp", "laguerre", "warp_filter"]
+           "dft", "hilbert", "cepstrum", "from_complex_cepstrum", "lpc", "warp", "laguerre", "warp_filter", "vqt"]
 
 
 def dft(signal: Signal, frequency_vector_hz) -> np.ndarray:
@@ -381,3 +382,37 @@ def warp_filter(filter: Filter, warping_factor: float) -> Filter:
     elif len(z) > len(p):
         p = np.hstack([p, fill])
     return Filter.from_zpk(z, p, k, filter.sampling_rate_hz)
+
+
+def vqt(signal: Signal, channel=None, q: float = 1, gamma: float = 50, octaves: list = [1, 5], bins_per_octave: int = 24,
+        a4_tuning: int = 440, window: str | tuple = "hann", *, on_device: bool = False):
+    """Variable-Q transform: (f, vqt) with the coefficients (frequency, time sample, channel) complex128 at the input
+    rate, the lowest frequency first.  `gamma = 0` gives the constant-Q transform.  The signal is decimated by
+    d = int((fs // 2) / (1.1 highest_f)) and then by 2 per octave; every octave is convolved (same mode) with the same
+    `bins_per_octave` windowed complex exponentials (window from scipy.signal.get_window, normalised to a unit sum,
+    length round(q mid_fs / (f_i (2^(1/bins) - 1) + gamma mid_fs / fs))); every row is brought back to the input rate by
+    polyphase interpolation (scipy.signal.resample_poly's default filter) and cut at the signal's length.  All of it runs
+    on the device in float64; the samples of a device-resident real signal are read where they lie.  With `on_device=True`
+    the coefficients stay in HBM as a `backend.DeviceScalogram` (complex128).
+
+    Kept from the reference: `f` has 12 entries per octave whatever `bins_per_octave` is (60 beside 120 rows at the
+    defaults); a `channel` subset raises ValueError (the reference's accumulator is sized by all channels);
+    ZeroDivisionError when the top octave lies above Nyquist / 1.1; mid_fs = fs // d is an integer, not the true rate.
+    NotImplementedError beyond backend.VQT_MAX_DECIMATION, VQT_MAX_OCTAVES, VQT_MAX_KERNEL, VQT_MAX_ROWS and
+    VQT_MAX_OUTPUT_BYTES."""
+    if channel is None:
+        channel = np.arange(signal.number_of_channels)
+    channel = np.atleast_1d(channel)
+    if len(channel) != signal.number_of_channels:
+        raise ValueError("all the input array dimensions except for the concatenation axis must match exactly, but along "
+                         f"dimension 2, the array at index 0 has size {signal.number_of_channels} and the array at index "
+                         f"1 has size {len(channel)}")
+    whole = np.array_equal(channel, np.arange(signal.number_of_channels))
+    if signal.on_device and whole and not signal.is_complex_signal:
+        samples = signal.device_samples
+    else:
+        samples = signal.time_data[:, channel]
+    coefficients = backend.vqt(samples, signal.sampling_rate_hz, q, gamma, octaves, bins_per_octave, a4_tuning, window,
+                               on_device=on_device)
+    f = a4_tuning * 2 ** (np.arange(octaves[0] - 4 - 9 / 12, octaves[1] - 4 + 2 / 12, 1 / 12))
+    return f, coefficients

@@ -724,6 +724,30 @@ int ds_host_widen_f64(const float* src, int64_t n, double* dst, int threads); /*
 int ds_fir_freqz(ds_ctx* ctx, const double* taps, int n_filt, int n_taps, const double* freqs_hz,
                  int n_freq, double fs_hz, double* out);
 
+/* ---- variable-Q transform: transforms.vqt (transforms/transforms.py:812-923) in one call, float64 throughout
+ * (csrc/kernels_vqt.hpp).  With P(x, up, down) scipy.signal.resample_poly's default filter for an integer ratio:
+ * td_0 = P(x, 1, d), td_{o+1} = P(td_o, 1, 2); per octave o the same-mode convolution of td_o with each of the `bins`
+ * complex kernels; every row back to the input rate by P(., 2^o, 1) (o > 0) and P(., d, 1), cut at n_samples.  Octave o's
+ * kernel i is row n_oct * bins - 1 - (o * bins + i) of out (n_oct * bins, n_samples, n_ch) complex128: the reference's
+ * flipped frequency axis.
+ * x: x_on_device == 0: host (n_samples, n_ch) float64, ldx ignored; != 0: planar float32 on the device, channel c at
+ * x + c * ldx, read where it lies and widened.  out: out_on_device == 0: a host array; != 0: a device buffer.
+ * Host tables, built by the caller exactly as the reference builds them: kernel_len [bins], kernel_taps the kernels'
+ * complex128 taps back to back; taps_dec = firwin(20 d + 1, 1 / d, kaiser 5.0) or the single tap 1.0 when d == 1;
+ * taps_half = firwin(41, 1 / 2, ...); taps_up the interpolation filters back to back, 2^o * firwin(20 * 2^o + 1, 2^-o)
+ * for o = 1 .. n_oct - 1, then d * firwin(20 d + 1, 1 / d) (the single tap 1.0 when d == 1).
+ * Bounds (DS_ERR_UNSUP beyond, before anything is allocated): the result at most 2^34 bytes; d <= 48; n_oct <= 7 (the
+ * first interpolation stage goes up to 2^6); kernels of at most 2048 taps; n_oct * bins and the channel groups of 4 at
+ * most 65535.  DS_ERR_NOMEM, before anything is uploaded, when the device has not the memory free.
+ * ds_resample_int: P alone on real host data, x (n, n_ch) float64 -> out (ceil(n * up / down), n_ch); one of up and down
+ * is 1, the other at most 64 (48 for down); taps: up * firwin(20 r + 1, 1 / r, ...) with r = max(up, down), or the
+ * single tap 1.0 when r == 1.                                                                                      */
+int ds_vqt(ds_ctx* ctx, const void* x, int x_on_device, int n_ch, int64_t ldx, int64_t n_samples, int d, int n_oct,
+           int bins, const int64_t* kernel_len, const double* kernel_taps, const double* taps_dec,
+           const double* taps_half, const double* taps_up, void* out, int out_on_device);
+int ds_resample_int(ds_ctx* ctx, const double* x, int64_t n, int n_ch, int up, int down, const double* taps,
+                    double* out);
+
 /* ---- multi-GPU: RCCL over xGMI, one process per GPU -----------------------
  * The hot path has no exchange step: the only collectives are the
  * broadcast of a shared input (sweep / taps / inverse spectrum) and the gather of sharded
