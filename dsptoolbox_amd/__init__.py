@@ -2,11 +2,11 @@
 spectral hot path (Welch/H1-H3, STFT, CSM, spectral deconvolution, FIR filter
 banks) behind the reference's Signal / Filter / FilterBank API."""
 
-from . import beamforming, distances, filterbanks, room_acoustics, standard, tools, transfer_functions, transforms
+from . import beamforming, distances, effects, filterbanks, room_acoustics, standard, tools, transfer_functions, transforms
 from .classes import Filter, FilterBank, ImpulseResponse, MultiBandSignal, Signal, Spectrum
 from .standard.enums import (BiquadEqType, FilterBankMode, FilterCoefficientsType, FilterPassType,
                              FrequencySpacing, IirDesignMethod, SpectrumMethod, SpectrumScaling, SpectrumType, Window)
-from .standard import delay, fractional_delay, latency
+from .standard import activity_detector, delay, fractional_delay, latency
 from .transfer_functions.enums import SmoothingDomain, TransferFunctionType
 
 __version__ = "0.1.0"
@@ -14,4 +14,4 @@ __all__ = ["Signal", "ImpulseResponse", "Spectrum", "Filter", "FilterBank", "Mul
            "SpectrumMethod", "SpectrumScaling", "SpectrumType", "FrequencySpacing", "Window", "FilterBankMode",
            "FilterPassType", "FilterCoefficientsType", "IirDesignMethod", "BiquadEqType", "TransferFunctionType", "SmoothingDomain",
            "transfer_functions", "transforms", "room_acoustics", "beamforming", "distances", "filterbanks", "tools", "standard",
-           "fractional_delay", "latency", "delay"]
+           "fractional_delay", "latency", "delay", "effects", "activity_detector"]

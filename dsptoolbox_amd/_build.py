@@ -40,6 +40,7 @@ NO_SCRATCH = [
     "5dslat6k_xmul", "5dslat6k_peak", "5dslat12k_peak_final", "5dslat8k_window", "5dslat6k_near", "5dslat13k_lag_partial",
     "5dslat11k_lag_final", "5dslat11k_lat_phase",
     "k_vqt_decimate", "k_vqt_bank", "k_vqt_interp",
+    "k_fx_stats", "k_fx_follow", "k_fx_comb", "k_fx_voices", "k_fx_curve_peak", "k_fx_shape", "k_fx_tremolo", "k_fx_scale",
 ]
 
 

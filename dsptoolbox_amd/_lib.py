@@ -175,6 +175,15 @@ SIGNATURES = {
     "ds_vqt": (C.c_int, [ctx_p, C.c_void_p, C.c_int, C.c_int, i64, i64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
     "ds_resample_int": (C.c_int, [ctx_p, C.c_void_p, i64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "ds_fx_compress": (C.c_int, [ctx_p, C.c_void_p, C.c_int, C.c_int, i64, i64, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                 C.c_void_p, i64]),
+    "ds_fx_detect": (C.c_int, [ctx_p, C.c_void_p, C.c_int, C.c_int, i64, i64, C.c_double, C.c_double, C.c_int, C.c_void_p]),
+    "ds_fx_delay": (C.c_int, [ctx_p, C.c_void_p, C.c_int, C.c_int, i64, i64, i64, i64, C.c_double, C.c_int, C.c_void_p, i64]),
+    "ds_fx_chorus": (C.c_int, [ctx_p, C.c_void_p, C.c_int, C.c_int, i64, i64, C.c_void_p, C.c_int, i64, C.c_double,
+                               C.c_void_p, i64]),
+    "ds_fx_distort": (C.c_int, [ctx_p, C.c_void_p, C.c_int, C.c_int, i64, i64, C.c_int, C.c_void_p, C.c_void_p, C.c_double,
+                                C.c_void_p, i64]),
+    "ds_fx_tremolo": (C.c_int, [ctx_p, C.c_void_p, C.c_int, C.c_int, i64, i64, C.c_void_p, C.c_void_p, i64]),
     "ds_welch_tf_x64": (C.c_int, [ctx_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, i64, C.c_int, C.c_int, C.c_int,
                                   C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int,
                                   C.c_void_p, C.c_void_p]),

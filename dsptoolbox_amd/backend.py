@@ -2605,3 +2605,128 @@ def resample_int(td, up: int, down: int) -> np.ndarray:
     ctx = get_context()
     ctx.check(ctx.lib.ds_resample_int(ctx.handle, _ptr(x), n, n_ch, up, down, _ptr(taps), _ptr(out)), "ds_resample_int")
     return out
+
+
+# ---- audio effects (ds_fx_*, csrc/kernels_fx.hpp) ---------------------------------------------------------------------
+FX_MAX_STREAMS = 65535        # bands x channels of one call (csrc/size_guards.hpp; DS_ERR_UNSUP above)
+FX_MAX_SAMPLES = 1 << 28      # padded samples of one stream
+FX_MAX_ELEMENTS = 1 << 30     # streams x padded samples
+FX_MAX_CURVES = 8             # distortion curves of one call
+FX_MAX_VOICES = 64            # chorus voices of one call
+FX_FOLLOW_TILE = 512          # samples of one round of the follower (FOLLOW_TILE of the kernels)
+FX_THREADS = 256              # threads of the sample-parallel kernels and reductions (NT of the kernels)
+FX_CURVES = {"Arctan": 0, "HardClip": 1, "SoftClip": 2, "NoDistortion": 3}  # DS_FX_CURVE_* of the header
+FX_SATURATIONS = {"digital": 0, "arctan": 1}                                # DS_FX_SAT_*
+
+
+def _fx_guard(n_streams: int, n_padded: int, voices: int = 0, curves: int = 0) -> None:
+    """NotImplementedError for an effect beyond the kernels' bounds, each named, before anything reaches the device."""
+    if n_streams > FX_MAX_STREAMS:
+        raise NotImplementedError(f"effects: {n_streams} streams (bands x channels) are beyond FX_MAX_STREAMS = {FX_MAX_STREAMS}")
+    if n_padded > FX_MAX_SAMPLES:
+        raise NotImplementedError(f"effects: {n_padded} padded samples are beyond FX_MAX_SAMPLES = 2^28")
+    if n_streams * n_padded > FX_MAX_ELEMENTS:
+        raise NotImplementedError(f"effects: {n_streams} streams x {n_padded} samples are beyond FX_MAX_ELEMENTS = 2^30")
+    if voices > FX_MAX_VOICES:
+        raise NotImplementedError(f"effects: {voices} chorus voices are beyond FX_MAX_VOICES = {FX_MAX_VOICES}")
+    if curves > FX_MAX_CURVES:
+        raise NotImplementedError(f"effects: {curves} distortion curves are beyond FX_MAX_CURVES = {FX_MAX_CURVES}")
+
+
+def _fx_samples(x):
+    """x as the entries take it: a DevicePlanar as it is, anything else as a C-order (samples, streams) float64 array."""
+    if isinstance(x, DevicePlanar):
+        return x
+    if np.iscomplexobj(x):
+        raise NotImplementedError("effects: complex samples are not run on the device (the recursions are real)")
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    x = x[:, None] if x.ndim == 1 else x
+    assert x.ndim == 2 and x.shape[0] >= 1 and x.shape[1] >= 1, "the samples are (samples, streams)"
+    return x
+
+
+def _fx_run(entry: str, x, n_out: int, *middle, voices: int = 0, curves: int = 0):
+    """One ds_fx_* call whose result is samples: x (N, S) float64 -> (n_out, S) float64, or a DevicePlanar read where it
+    lies -> a DevicePlanar of n_out samples.  `middle`: the entry's arguments between n and y."""
+    x = _fx_samples(x)
+    n, n_str = _samples_shape(x)
+    _fx_guard(n_str, n_out, voices, curves)
+    if isinstance(x, DevicePlanar):
+        ctx = x.ctx
+        with device_scope(ctx) as dev:
+            d_y = dev.alloc(4 * n_str * n_out, result=True)
+            ctx.check(getattr(ctx.lib, entry)(ctx.handle, C.c_void_p(x.ptr), 1, n_str, x.ld, n, *middle,
+                                              C.c_void_p(d_y.ptr), n_out), entry)
+        return DevicePlanar(d_y, n_str, n_out, n_out, 0)
+    y = np.empty((n_out, n_str), dtype=np.float64)
+    ctx = get_context()
+    ctx.check(getattr(ctx.lib, entry)(ctx.handle, _ptr(x), 0, n_str, n, n, *middle, _ptr(y), n_out), entry)
+    return y
+
+
+def fx_follower_coefficient(samples) -> float:
+    """1 - exp(ln 0.05 / samples): the one-pole coefficient that reaches 95 % after `samples` steps; 1 for 0 samples."""
+    with np.errstate(divide="ignore"):
+        return float(1 - np.exp(np.log(1 - 0.95) / np.float64(samples)))
+
+
+def fx_compress(x, threshold_db: float, ratio: float, knee_db: float, attack_samples: int, release_samples: int,
+                pre_gain: float = 1.0, final_gain: float = 1.0, downward: bool = True, relative: bool = True,
+                make_up: bool = True):
+    """The compressor's sample loop and the stages around it (ds_fx_compress): gains are linear factors."""
+    par = np.array([pre_gain, threshold_db, ratio, knee_db, fx_follower_coefficient(attack_samples),
+                    fx_follower_coefficient(release_samples), 10 ** (-300.0 / 10), final_gain], dtype=np.float64)
+    n = _samples_shape(_fx_samples(x))[0]
+    return _fx_run("ds_fx_compress", x, n, _ptr(par), int(bool(downward)), int(bool(relative)), int(bool(make_up)))
+
+
+def fx_detect(x, threshold_db: float, c_release: float, relative: bool = True) -> np.ndarray:
+    """The activity detector's gate (ds_fx_detect): -> (N, S) bool, True where the smoothed power is above the threshold."""
+    x = _fx_samples(x)
+    n, n_str = _samples_shape(x)
+    _fx_guard(n_str, n)
+    mask = np.empty((n_str, n), dtype=np.uint8)
+    if isinstance(x, DevicePlanar):
+        ctx, head = x.ctx, (C.c_void_p(x.ptr), 1, n_str, x.ld, n)
+    else:
+        ctx, head = get_context(), (_ptr(x), 0, n_str, n, n)
+    ctx.check(ctx.lib.ds_fx_detect(ctx.handle, *head, float(c_release), float(threshold_db), int(bool(relative)), _ptr(mask)),
+              "ds_fx_detect")
+    return mask.T.astype(bool)
+
+
+def fx_delay(x, delay_samples: int, padding: int, feedback: float, saturation: str = "digital"):
+    """The feedback delay line over the samples and `padding` zeros behind them, peak restored (ds_fx_delay)."""
+    n = _samples_shape(_fx_samples(x))[0]
+    return _fx_run("ds_fx_delay", x, n + int(padding), int(delay_samples), int(padding), float(feedback),
+                   FX_SATURATIONS[saturation])
+
+
+def fx_chorus(x, delays, mix: float):
+    """The chorus gather (ds_fx_chorus): delays (N, V) integer samples per voice, the reference's index table."""
+    n = _samples_shape(_fx_samples(x))[0]
+    delays = np.asarray(delays)
+    assert delays.ndim == 2 and delays.shape[0] == n and delays.shape[1] >= 1, "the delays are (samples, voices)"
+    max_delay = int(np.abs(delays).max())
+    _fx_guard(1, n + max_delay, voices=delays.shape[1])
+    m = np.ascontiguousarray(delays, dtype=np.int32)
+    return _fx_run("ds_fx_chorus", x, n, _ptr(m), m.shape[1], max_delay, float(mix), voices=m.shape[1])
+
+
+def fx_distort(x, kinds, levels, offsets, mixes, gain: float = 1.0):
+    """The sum of the peak-restored distortion curves (ds_fx_distort): kinds are FX_CURVES values, levels and offsets
+    linear; curves with a mix weight of 0 are left out as the reference skips them."""
+    keep = [i for i, w in enumerate(mixes) if w != 0.0]
+    _fx_guard(1, 1, curves=len(keep))
+    kind = np.array([kinds[i] for i in keep], dtype=np.int32)
+    par = np.ascontiguousarray([[levels[i], offsets[i], mixes[i]] for i in keep], dtype=np.float64)
+    n = _samples_shape(_fx_samples(x))[0]
+    return _fx_run("ds_fx_distort", x, n, len(keep), _ptr(kind), _ptr(par), float(gain), curves=len(keep))
+
+
+def fx_tremolo(x, modulator):
+    """Every stream times the per-sample modulator (ds_fx_tremolo)."""
+    n = _samples_shape(_fx_samples(x))[0]
+    mod = np.ascontiguousarray(modulator, dtype=np.float64)
+    assert mod.shape == (n,), "the modulator has one value per sample"
+    return _fx_run("ds_fx_tremolo", x, n, _ptr(mod))

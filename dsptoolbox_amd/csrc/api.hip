@@ -57,6 +57,7 @@
 #include "kernels_sfilt.hpp"
 #include "kernels_room.hpp"
 #include "kernels_vqt.hpp"
+#include "kernels_fx.hpp"
 #include "size_guards.hpp"
 
 using namespace dsk;
@@ -5226,6 +5227,188 @@ extern "C" int ds_resample_int(ds_ctx* c, const double* x, int64_t n, int n_ch, 
         if (down > 1) return vqt_decimate<double>(c, (const double*)s[0], n_ch, 1, n, n_ch, (const double*)t[0], down, (double*)s[1], n_out);
         return vqt_interp<double>(c, "vqt_interp@real", (const double*)s[0], (double*)s[1], (const double*)t[0],
                                   (const InterpOct*)t[1], &oc, 1, 1, n_ch);
+    });
+}
+
+// ---- audio effects (kernels_fx.hpp), float64 ------------------------------------------------------------------------
+// What every effects entry takes: x (n samples of n_str streams) and y (n_out samples) both on the host as
+// (samples, streams) float64, or both on the device as planar float32 rows of pitch ldx / ld_y.
+struct FxCall {
+    const char* who;
+    const void* x;
+    int on_device, n_str;
+    int64_t ldx, n, n_out;
+    void* y;
+    int64_t ld_y;
+    size_t elements() const { return (size_t)n_str * (size_t)n_out; }
+};
+
+// shape and bounds; nothing touches the device
+static int fx_check(ds_ctx* c, const FxCall& q) {
+    if (!c || !q.x || !q.y) return fail(c, DS_ERR_ARG, q.who, "null argument");
+    if (q.n_str < 1 || q.n < 1 || q.n_out < q.n || (q.on_device && (q.ldx < q.n || q.ld_y < q.n_out)))
+        return fail(c, DS_ERR_ARG, q.who, "bad shape");
+    if (fx_shape_unsupported(q.n_str, q.n_out))
+        return fail(c, DS_ERR_UNSUP, q.who, "more than 65535 streams, 2^28 samples a stream or 2^30 samples in all are not built");
+    return DS_OK;
+}
+
+// run(src, dst) over the samples where they lie: a host call's arrays are pieces of c->io, a resident call's are read
+// and written in place.  ws_doubles: what run() will carve out of c->ws, for the memory pre-check.
+template <class F>
+static int fx_io(ds_ctx* c, const FxCall& q, size_t ws_doubles, F&& run) {
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t nx = q.on_device ? 0 : (size_t)q.n_str * q.n, ny = q.on_device ? 0 : q.elements();
+    CHK(mem_check(c, q.who, ws_doubles * 8 + 16 * 256, (nx + ny) * 8, 0));
+    if (q.on_device)
+        return run(dsfx::Src<float>{(const float*)q.x, 1, q.ldx}, dsfx::Dst<float>{(float*)q.y, 1, q.ld_y});
+    return staged(c, {{8, nx, q.x}, {8, ny, nullptr, q.y}}, [&](void* const* d) {
+        return run(dsfx::Src<double>{(const double*)d[0], q.n_str, 1}, dsfx::Dst<double>{(double*)d[1], q.n_str, 1});
+    });
+}
+
+static dim3 fx_grid(int64_t n, int n_str) { return dim3((unsigned)((n + dsfx::NT - 1) / dsfx::NT), (unsigned)n_str); }
+
+template <typename T>
+static int fx_stats(ds_ctx* c, dsfx::Src<T> x, int64_t n, int n_str, double gain, double* st) {
+    return launch(c, "fx_stats", dsfx::k_fx_stats<T>, dim3((unsigned)n_str), dsfx::STATS_NT, 0, dsfx::StatsArgs<T>{x, n, gain, st});
+}
+
+// the restore stage of compressor, delay and chorus: yd [n_str][n] -> dst
+template <typename T>
+static int fx_scale(ds_ctx* c, const double* yd, dsfx::Dst<T> y, int64_t n, int n_str, int restore, const double* st_in,
+                    double* st_out, double gain) {
+    if (restore != dsfx::RESTORE_NONE) CHK(fx_stats(c, dsfx::Src<double>{yd, 1, n}, n, n_str, 1.0, st_out));
+    return launch(c, "fx_scale", dsfx::k_fx_scale<T>, fx_grid(n, n_str), dsfx::NT, 0,
+                  dsfx::ScaleArgs<T>{yd, y, n, restore, st_in, st_out, gain});
+}
+
+// par: gain_pre, threshold_db, ratio, knee_db, c_attack, c_release, min_power, gain_post
+extern "C" int ds_fx_compress(ds_ctx* c, const void* x, int on_device, int n_str, int64_t ldx, int64_t n, const double* par,
+                              int downward, int relative, int make_up, void* y, int64_t ld_y) {
+    const FxCall q{"ds_fx_compress", x, on_device, n_str, ldx, n, n, y, ld_y};
+    CHK(fx_check(c, q));
+    if (!par) return fail(c, DS_ERR_ARG, q.who, "null argument");
+    const dsfx::FollowPar p{par[0], par[1], par[2], par[3], par[4], par[5], par[6], downward, relative};
+    const size_t n_st = (size_t)n_str * dsfx::STAT;
+    return fx_io(c, q, 2 * n_st + q.elements(), [&](auto src, auto dst) {
+        using T = typename decltype(src)::type;
+        void* t[kMaxStaged];
+        CHK(stage(c, &c->ws, &c->ws_bytes, {{8, n_st}, {8, n_st}, {8, q.elements()}}, t));
+        double *st_in = (double*)t[0], *st_out = (double*)t[1], *yd = (double*)t[2];
+        CHK(fx_stats(c, src, n, n_str, p.gain, st_in));
+        CHK(launch(c, "fx_follow@compress", dsfx::k_fx_follow<T, dsfx::MODE_COMPRESS>, dim3((unsigned)n_str), dsfx::FOLLOW_NT, 0,
+                   dsfx::FollowArgs<T>{src, n, p, st_in, yd, nullptr}));
+        return fx_scale(c, yd, dst, n, n_str, make_up ? dsfx::RESTORE_RMS : dsfx::RESTORE_NONE, st_in, st_out, par[7]);
+    });
+}
+
+// mask: host (n_str, n) bytes, 1 where 10 log10(gain) > threshold_db
+extern "C" int ds_fx_detect(ds_ctx* c, const void* x, int on_device, int n_str, int64_t ldx, int64_t n, double c_release,
+                            double threshold_db, int relative, uint8_t* mask) {
+    const FxCall q{"ds_fx_detect", x, on_device, n_str, ldx, n, n, mask, n};
+    CHK(fx_check(c, q));
+    HIPCHK(c, hipSetDevice(c->device));
+    const dsfx::FollowPar p{1.0, threshold_db, 1.0, 0.0, 0.0, c_release, 0.0, 1, relative};
+    const size_t n_st = (size_t)n_str * dsfx::STAT, nx = on_device ? 0 : q.elements();
+    CHK(mem_check(c, q.who, n_st * 8 + 256, nx * 8 + q.elements(), 0));
+    return staged(c, {{8, nx, x}, {1, q.elements(), nullptr, mask}}, [&](void* const* d) {
+        void* t[kMaxStaged];
+        CHK(stage(c, &c->ws, &c->ws_bytes, {{8, n_st}}, t));
+        double* st = (double*)t[0];
+        auto run = [&](auto src) {
+            using T = typename decltype(src)::type;
+            CHK(fx_stats(c, src, n, n_str, 1.0, st));
+            return launch(c, "fx_follow@detect", dsfx::k_fx_follow<T, dsfx::MODE_DETECT>, dim3((unsigned)n_str), dsfx::FOLLOW_NT, 0,
+                          dsfx::FollowArgs<T>{src, n, p, st, nullptr, (uint8_t*)d[1]});
+        };
+        if (on_device) return run(dsfx::Src<float>{(const float*)x, 1, ldx});
+        return run(dsfx::Src<double>{(const double*)d[0], n_str, 1});
+    });
+}
+
+// y holds n + padding samples a stream
+extern "C" int ds_fx_delay(ds_ctx* c, const void* x, int on_device, int n_str, int64_t ldx, int64_t n, int64_t delay,
+                           int64_t padding, double feedback, int saturation, void* y, int64_t ld_y) {
+    const FxCall q{"ds_fx_delay", x, on_device, n_str, ldx, n, n + std::max<int64_t>(padding, 0), y, ld_y};
+    if (delay < 0 || padding < 0 || (delay == 0 && padding != 0) || (saturation != dsfx::SAT_DIGITAL && saturation != dsfx::SAT_ARCTAN))
+        return fail(c, DS_ERR_ARG, q.who, "needs delay >= 0, padding >= 0 (0 with no delay) and a known saturation");
+    CHK(fx_check(c, q));
+    const size_t n_st = (size_t)n_str * dsfx::STAT;
+    return fx_io(c, q, 2 * n_st + q.elements(), [&](auto src, auto dst) {
+        using T = typename decltype(src)::type;
+        void* t[kMaxStaged];
+        CHK(stage(c, &c->ws, &c->ws_bytes, {{8, n_st}, {8, n_st}, {8, q.elements()}}, t));
+        double *st_in = (double*)t[0], *st_out = (double*)t[1], *yd = (double*)t[2];
+        CHK(fx_stats(c, src, n, n_str, 1.0, st_in));
+        CHK(launch(c, "fx_comb", dsfx::k_fx_comb<T>, fx_grid(delay ? std::min(delay, q.n_out) : q.n_out, n_str), dsfx::NT, 0,
+                   dsfx::CombArgs<T>{src, n, q.n_out, delay, feedback, saturation, yd}));
+        return fx_scale(c, yd, dst, q.n_out, n_str, dsfx::RESTORE_PEAK, st_in, st_out, 1.0);
+    });
+}
+
+// m: host (n, voices) int32, every |m| <= max_delay
+extern "C" int ds_fx_chorus(ds_ctx* c, const void* x, int on_device, int n_str, int64_t ldx, int64_t n, const int32_t* m,
+                            int voices, int64_t max_delay, double mix, void* y, int64_t ld_y) {
+    const FxCall q{"ds_fx_chorus", x, on_device, n_str, ldx, n, n, y, ld_y};
+    CHK(fx_check(c, q));
+    if (!m) return fail(c, DS_ERR_ARG, q.who, "null argument");
+    if (voices < 1 || max_delay < 0) return fail(c, DS_ERR_ARG, q.who, "needs a voice and a largest delay >= 0");
+    if (voices > kFxMaxVoices || n + max_delay > kFxMaxSamples)
+        return fail(c, DS_ERR_UNSUP, q.who, "more than 64 voices or 2^28 padded samples are not built");
+    const size_t n_m = (size_t)n * voices;
+    for (size_t i = 0; i < n_m; ++i)
+        if (m[i] > max_delay || m[i] < -max_delay) return fail(c, DS_ERR_ARG, q.who, "a delay is beyond max_delay");
+    const size_t n_st = (size_t)n_str * dsfx::STAT;
+    return fx_io(c, q, 2 * n_st + q.elements() + n_m / 2 + 1, [&](auto src, auto dst) {
+        using T = typename decltype(src)::type;
+        void* t[kMaxStaged];
+        CHK(stage(c, &c->ws, &c->ws_bytes, {{8, n_st}, {8, n_st}, {8, q.elements()}, {4, n_m, m}}, t));
+        double *st_in = (double*)t[0], *st_out = (double*)t[1], *yd = (double*)t[2];
+        CHK(fx_stats(c, src, n, n_str, 1.0, st_in));
+        CHK(launch(c, "fx_voices", dsfx::k_fx_voices<T>, fx_grid(n, n_str), dsfx::NT, 0,
+                   dsfx::VoicesArgs<T>{src, n, n + max_delay, (const int32_t*)t[3], voices, mix, 1 - mix, yd}));
+        return fx_scale(c, yd, dst, n, n_str, dsfx::RESTORE_PEAK, st_in, st_out, 1.0);
+    });
+}
+
+// kinds [n_curves]: DS_FX_CURVE_*; par [n_curves][3]: linear level, linear offset, mix weight (none of them 0)
+extern "C" int ds_fx_distort(ds_ctx* c, const void* x, int on_device, int n_str, int64_t ldx, int64_t n, int n_curves,
+                             const int* kinds, const double* par, double gain, void* y, int64_t ld_y) {
+    const FxCall q{"ds_fx_distort", x, on_device, n_str, ldx, n, n, y, ld_y};
+    CHK(fx_check(c, q));
+    if (!kinds || !par || n_curves < 1) return fail(c, DS_ERR_ARG, q.who, "needs a curve");
+    if (n_curves > kFxMaxCurves) return fail(c, DS_ERR_UNSUP, q.who, "more than 8 curves are not built");
+    dsfx::CurvePar cv{};
+    cv.count = n_curves;
+    for (int k = 0; k < n_curves; ++k) {
+        if (kinds[k] < 0 || kinds[k] >= dsfx::N_CURVES) return fail(c, DS_ERR_ARG, q.who, "unknown curve");
+        cv.kind[k] = kinds[k], cv.level[k] = par[3 * k], cv.offset[k] = par[3 * k + 1], cv.mix[k] = par[3 * k + 2];
+    }
+    const size_t n_st = (size_t)n_str * dsfx::STAT, n_pk = (size_t)n_str * dsfx::MAX_CURVES;
+    return fx_io(c, q, n_st + n_pk, [&](auto src, auto dst) {
+        using T = typename decltype(src)::type;
+        void* t[kMaxStaged];
+        CHK(stage(c, &c->ws, &c->ws_bytes, {{8, n_st}, {8, n_pk}}, t));
+        const dsfx::ShapeArgs<T> a{src, dst, n, cv, gain, (const double*)t[0], (double*)t[1]};
+        CHK(fx_stats(c, src, n, n_str, 1.0, (double*)t[0]));
+        CHK(launch(c, "fx_curve_peak", dsfx::k_fx_curve_peak<T>, dim3((unsigned)n_str, (unsigned)n_curves), dsfx::NT, 0, a));
+        return launch(c, "fx_shape", dsfx::k_fx_shape<T>, fx_grid(n, n_str), dsfx::NT, 0, a);
+    });
+}
+
+// mod: host [n], the modulator every stream is multiplied by
+extern "C" int ds_fx_tremolo(ds_ctx* c, const void* x, int on_device, int n_str, int64_t ldx, int64_t n, const double* mod,
+                             void* y, int64_t ld_y) {
+    const FxCall q{"ds_fx_tremolo", x, on_device, n_str, ldx, n, n, y, ld_y};
+    CHK(fx_check(c, q));
+    if (!mod) return fail(c, DS_ERR_ARG, q.who, "null argument");
+    return fx_io(c, q, (size_t)n, [&](auto src, auto dst) {
+        using T = typename decltype(src)::type;
+        void* t[kMaxStaged];
+        CHK(stage(c, &c->ws, &c->ws_bytes, {{8, (size_t)n, mod}}, t));
+        return launch(c, "fx_tremolo", dsfx::k_fx_tremolo<T>, fx_grid(n, n_str), dsfx::NT, 0,
+                      dsfx::TremoloArgs<T>{src, dst, n, (const double*)t[0]});
     });
 }
 

@@ -155,3 +155,19 @@ DS_HD inline bool vqt_shape_unsupported(int64_t d, int64_t n_oct, int64_t longes
     return d > kVqtMaxDecimation || n_oct > kVqtMaxOctaves || longest_kernel > kVqtMaxKernel || rows > kVqtMaxRows ||
            (n_ch + 3) / 4 > kVqtMaxRows;
 }
+
+// Audio effects (kernels_fx.hpp).  A stream is one channel of one band; grid.y (or grid.x of the one-workgroup-per-stream
+// kernels) carries the streams: at most 65535.  A stream's padded length -- the delay's repetitions and the chorus's
+// largest delay included -- stays below 2^28 samples (the chorus index table is 32-bit), and streams x padded samples at
+// most 2^30: the float64 intermediate between the recursion and the restore stage is then at most 8 GiB.  The follower is
+// serial in time per stream, 35 ns a sample, so the longest stream takes under ten seconds.
+// Distortion sums at most 8 curves, the chorus at most 64 voices (registers and kernel arguments, not a measured rate).
+// Beyond any of these the entries answer DS_ERR_UNSUP.
+constexpr int kFxMaxStreams = 65535;
+constexpr int64_t kFxMaxSamples = (int64_t)1 << 28;
+constexpr int64_t kFxMaxElements = (int64_t)1 << 30;
+constexpr int kFxMaxCurves = 8;
+constexpr int kFxMaxVoices = 64;
+DS_HD inline bool fx_shape_unsupported(int64_t n_streams, int64_t n_padded) {
+    return n_streams > kFxMaxStreams || n_padded > kFxMaxSamples || (double)n_streams * (double)n_padded > (double)kFxMaxElements;
+}

@@ -748,6 +748,47 @@ int ds_vqt(ds_ctx* ctx, const void* x, int x_on_device, int n_ch, int64_t ldx, i
 int ds_resample_int(ds_ctx* ctx, const double* x, int64_t n, int n_ch, int up, int down, const double* taps,
                     double* out);
 
+/* ---- audio effects: effects.Compressor, DigitalDelay, Chorus, Distortion, Tremolo (effects/effects.py) and the gate of
+ * standard.activity_detector (standard/_standard_backend.py:324-379), float64 throughout (csrc/kernels_fx.hpp).
+ * A stream is one channel of one band.  x_on_device == 0: x is a host (n, n_str) float64 array, y a host (n_out, n_str)
+ * one, ldx and ld_y are ignored; != 0: both are planar float32 on the device, stream s at x + s * ldx and y + s * ld_y, and
+ * the result stays there.  The small tables (coefficients, chorus indices, modulator) are host arrays the caller builds
+ * as the reference does.  Bounds (DS_ERR_UNSUP beyond, before anything is allocated): 65535 streams, 2^28 padded samples
+ * a stream, 2^30 in all, 8 curves, 64 voices.  DS_ERR_NOMEM, before anything is uploaded, when the memory is not free.
+ * Compressor: par = { pre gain (linear), threshold dB, ratio, knee dB, attack coefficient, release coefficient, the
+ *   floor of the squared sample, final gain (linear) }; with t = x pre_gain (divided by its stream's peak when
+ *   `relative`), d = 10 log10(max(t^2, floor)), f = 10^((K(d) - d) / 20) for the knee curve K, the gain follows
+ *   g <- c f + (1 - c) g from g = 1 with c the attack coefficient where f > g, else the release one; y = t g (times the
+ *   peak again), times rms(x pre_gain) / rms(y) with `make_up`, times the final gain.
+ * Detector: p = x^2 (x divided by its peak when `relative`); g[0] = 0, g[i] = c p[i] + (1 - c) g[i-1] with c = c_release
+ *   where p[i-1] > 0, else 0; mask (n_str, n) bytes on the host: 10 log10(g) > threshold_db.
+ * Delay: y[i] = x[i] + feedback sat(y[i - delay]) over n + padding samples (x zero beyond n), sat the identity
+ *   (DS_FX_SAT_DIGITAL) or 0.5 atan(2 v) (DS_FX_SAT_ARCTAN); delay == 0 gives y = x + feedback sat(x) and needs padding 0;
+ *   then the peak of x is restored.
+ * Chorus: with td the samples followed by max_delay zeros, y[i] = (td[i] + sum_v td[i + m[i][v]]) mix + td[i] (1 - mix),
+ *   a negative index counted from the end of td; then the peak of x is restored.  m: (n, voices) int32.
+ * Distortion: y = gain * sum_k r_k, r_k = c_k peak(x) / peak(c_k), c_k = curve_k(x) mix_k; kinds DS_FX_CURVE_*,
+ *   par (n_curves, 3) = linear level, linear offset, mix weight.  Curves whose weight is 0 are left out by the caller.
+ * Tremolo: y[i] = x[i] mod[i].                                                                                        */
+#define DS_FX_CURVE_ARCTAN 0
+#define DS_FX_CURVE_HARD_CLIP 1
+#define DS_FX_CURVE_SOFT_CLIP 2
+#define DS_FX_CURVE_CLEAN 3
+#define DS_FX_SAT_DIGITAL 0
+#define DS_FX_SAT_ARCTAN 1
+int ds_fx_compress(ds_ctx* ctx, const void* x, int x_on_device, int n_str, int64_t ldx, int64_t n, const double* par,
+                   int downward, int relative, int make_up, void* y, int64_t ld_y);
+int ds_fx_detect(ds_ctx* ctx, const void* x, int x_on_device, int n_str, int64_t ldx, int64_t n, double c_release,
+                 double threshold_db, int relative, uint8_t* mask);
+int ds_fx_delay(ds_ctx* ctx, const void* x, int x_on_device, int n_str, int64_t ldx, int64_t n, int64_t delay,
+                int64_t padding, double feedback, int saturation, void* y, int64_t ld_y);
+int ds_fx_chorus(ds_ctx* ctx, const void* x, int x_on_device, int n_str, int64_t ldx, int64_t n, const int32_t* m,
+                 int voices, int64_t max_delay, double mix, void* y, int64_t ld_y);
+int ds_fx_distort(ds_ctx* ctx, const void* x, int x_on_device, int n_str, int64_t ldx, int64_t n, int n_curves,
+                  const int* kinds, const double* par, double gain, void* y, int64_t ld_y);
+int ds_fx_tremolo(ds_ctx* ctx, const void* x, int x_on_device, int n_str, int64_t ldx, int64_t n, const double* mod,
+                  void* y, int64_t ld_y);
+
 /* ---- multi-GPU: RCCL over xGMI, one process per GPU -----------------------
  * The hot path has no exchange step: the only collectives are the
  * broadcast of a shared input (sweep / taps / inverse spectrum) and the gather of sharded
