@@ -41,6 +41,8 @@ NO_SCRATCH = [
     "5dslat11k_lag_final", "5dslat11k_lat_phase",
     "k_vqt_decimate", "k_vqt_bank", "k_vqt_interp",
     "k_fx_stats", "k_fx_follow", "k_fx_comb", "k_fx_voices", "k_fx_curve_peak", "k_fx_shape", "k_fx_tremolo", "k_fx_scale",
+    "k_level_project", "k_level_final", "k_level_common", "k_level_stats", "k_level_gain", "k_level_apply", "k_level_moving",
+    "k_level_blocks", "k_level_mag",
 ]
 
 

@@ -2730,3 +2730,173 @@ def fx_tremolo(x, modulator):
     mod = np.ascontiguousarray(modulator, dtype=np.float64)
     assert mod.shape == (n,), "the modulator has one value per sample"
     return _fx_run("ds_fx_tremolo", x, n, _ptr(mod))
+
+
+# ---- levels and loudness (ds_level_*, ds_moving_rms, ds_loudness_blocks, ds_envelope_analytic; csrc/kernels_level.hpp) ----
+LEVEL_NT = 256                # lanes per workgroup (NT of the kernels)
+LEVEL_PER_LANE = 16           # samples a lane of a reduction adds in turn (PER_LANE)
+LEVEL_SPAN = LEVEL_NT * LEVEL_PER_LANE  # samples per workgroup of a reduction (SPAN)
+LEVEL_TILE = 1024             # outputs per workgroup of the moving window (TILE)
+LEVEL_VEC_BYTES = 16          # bytes a lane of the apply kernels loads and stores at once (VEC_BYTES)
+LEVEL_MAX_ORDER = 8           # polynomial order of a trend (MAX_ORDER)
+LEVEL_MAX_CHANNELS = 65535    # csrc/size_guards.hpp; DS_ERR_UNSUP above
+LEVEL_MAX_SAMPLES = (1 << 31) - 1
+LEVEL_MAX_ELEMENTS = 1 << 33
+LEVEL_MOVING_MAX_WORK = 1e12  # channels x samples x (2 + min(window, samples) / 1024)
+LEVEL_NORMS = {"none": 0, "peak_each": 1, "peak_all": 2, "rms_each": 3, "rms_all": 4}  # DS_LEVEL_NORM_* of the header
+
+
+def level_basis(n: int, order: int) -> np.ndarray:
+    """The recurrence of the discrete Chebyshev (Gram) polynomials orthonormal on 0 .. n - 1, as the entries take it:
+    [(n - 1) / 2, 1 / sqrt(n), a_0 .. a_7, b_0 .. b_7] with P_{k+1} = a_k t P_k - b_k P_{k-1}, a_k = 1 / beta_{k+1},
+    b_k = beta_k / beta_{k+1}, beta_k^2 = k^2 (n^2 - k^2) / (4 (4 k^2 - 1)); formed in long double, filled up to `order`."""
+    n, order = int(n), int(order)
+    assert 0 <= order <= LEVEL_MAX_ORDER and order < n, "the order is at most 8 and below the length"
+    ld = np.longdouble
+    out = np.zeros(2 + 2 * LEVEL_MAX_ORDER, dtype=np.float64)
+    out[0] = float((ld(n) - 1) / 2)
+    out[1] = float(1 / np.sqrt(ld(n)))
+    k = np.arange(0, order + 1, dtype=ld)
+    beta = np.sqrt(k * k * (ld(n) * ld(n) - k * k) / (4 * (4 * k * k - 1)))
+    for i in range(order):
+        out[2 + i] = float(1 / beta[i + 1])
+        out[2 + LEVEL_MAX_ORDER + i] = float(beta[i] / beta[i + 1])
+    return out
+
+
+def _level_guard(n_ch: int, n: int) -> None:
+    """NotImplementedError for a shape beyond the kernels' bounds, before anything reaches the device."""
+    if n_ch > LEVEL_MAX_CHANNELS or n > LEVEL_MAX_SAMPLES or n_ch * n > LEVEL_MAX_ELEMENTS:
+        raise NotImplementedError(f"levels: {n_ch} channels x {n} samples are beyond the device kernels' bounds "
+                                  f"({LEVEL_MAX_CHANNELS} channels, 2^31 - 1 samples a channel, 2^33 samples in all)")
+
+
+def _level_samples(x):
+    """x as the entries take it, and the arguments that describe it: (x, pointer, on_device, n_ch, ld, n).  No context is
+    opened: the callers' guards come first."""
+    if not isinstance(x, DevicePlanar):
+        if np.iscomplexobj(x):
+            raise NotImplementedError("levels: complex samples are not run on the device")
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        x = x[:, None] if x.ndim == 1 else x
+        assert x.ndim == 2 and x.shape[0] >= 1 and x.shape[1] >= 1, "the samples are (samples, channels)"
+    n, n_ch = _samples_shape(x)
+    _level_guard(n_ch, n)
+    if isinstance(x, DevicePlanar):
+        return x, C.c_void_p(x.ptr), 1, n_ch, x.ld, n
+    return x, _ptr(x), 0, n_ch, n, n
+
+
+def _level_ctx(x):
+    return x.ctx if isinstance(x, DevicePlanar) else get_context()
+
+
+def _level_order(n: int, order: int) -> int:
+    """The order that is fitted: a polynomial through every sample (order >= n) leaves the same zero residual as n - 1."""
+    return min(int(order), n - 1)
+
+
+def level_project(x, order: int = 0) -> np.ndarray:
+    """Per channel of x ((N, C) float64, or a DevicePlanar read where it lies): the coefficients c_k = sum_n x[n] P_k(n),
+    k = 0 .. 8 (zero past the order) in the basis of level_basis, and max |x|, as (C, 10) float64 (ds_level_project)."""
+    x, px, on_dev, n_ch, ld, n = _level_samples(x)
+    order = _level_order(n, order)
+    basis = level_basis(n, order)
+    out = np.empty((n_ch, 10), dtype=np.float64)
+    ctx = _level_ctx(x)
+    ctx.check(ctx.lib.ds_level_project(ctx.handle, px, on_dev, n_ch, ld, n, order, _ptr(basis), _ptr(out)), "ds_level_project")
+    return out
+
+
+def level_stats(x, order: int = 0, common: bool = False) -> np.ndarray:
+    """Per channel: sum (x - p)^2 term by term, max |x - p|, max |x| as (C, 3) float64, p the least-squares polynomial
+    of `order` (0: the mean) of the channel; common: the mean of all channels together (ds_level_stats)."""
+    x, px, on_dev, n_ch, ld, n = _level_samples(x)
+    order = _level_order(n, order)
+    basis = level_basis(n, order)
+    out = np.empty((n_ch, 3), dtype=np.float64)
+    ctx = _level_ctx(x)
+    ctx.check(ctx.lib.ds_level_stats(ctx.handle, px, on_dev, n_ch, ld, n, order, _ptr(basis), int(bool(common)), _ptr(out)),
+              "ds_level_stats")
+    return out
+
+
+def level_apply(x, order: int = -1, norm: str = "none", norm_factor: float = 1.0, gain=None, fade=None,
+                at_start: bool = False, at_end: bool = False):
+    """y[n] = (x[n] - p(n)) g fade[n] fade[N - 1 - n] in one pass (ds_level_apply), every factor optional: order >= 0
+    removes the channel's least-squares polynomial; gain (C,) or, with norm one of LEVEL_NORMS, norm_factor over the
+    peak or the centred rms found on the device; fade (L,) on the first L samples (at_start) and mirrored on the last
+    (at_end).  x (N, C) float64 -> (N, C) float64; a DevicePlanar is read where it lies -> a DevicePlanar."""
+    x, px, on_dev, n_ch, ld, n = _level_samples(x)
+    order = _level_order(n, order) if order >= 0 else -1
+    basis = level_basis(n, max(order, 0))
+    if gain is not None:
+        gain = np.ascontiguousarray(np.broadcast_to(np.asarray(gain, dtype=np.float64), (n_ch,)))
+    l_fade = 0
+    if fade is not None:
+        fade = np.ascontiguousarray(fade, dtype=np.float64)
+        assert fade.ndim == 1 and 1 <= fade.shape[0] <= n and (at_start or at_end), "a fade has 1 .. N samples and an end"
+        l_fade = fade.shape[0]
+    middle = (order, _ptr(basis), LEVEL_NORMS[norm], float(norm_factor), None if gain is None else _ptr(gain),
+              None if fade is None else _ptr(fade), l_fade, int(bool(at_start)), int(bool(at_end)))
+    ctx = _level_ctx(x)
+    if on_dev:
+        with device_scope(ctx) as dev:
+            d_y = dev.alloc(4 * n_ch * n, result=True)
+            ctx.check(ctx.lib.ds_level_apply(ctx.handle, px, 1, n_ch, ld, n, *middle, C.c_void_p(d_y.ptr), n), "ds_level_apply")
+        return DevicePlanar(d_y, n_ch, n, n, 0)
+    y = np.empty((n, n_ch), dtype=np.float64)
+    ctx.check(ctx.lib.ds_level_apply(ctx.handle, px, 0, n_ch, n, n, *middle, _ptr(y), n), "ds_level_apply")
+    return y
+
+
+def moving_rms(x, window_length: int) -> np.ndarray:
+    """sqrt(max(0, mean of the last `window_length` squares of x minus its least-squares line)), samples before the first
+    counted as zero, as (N, C) float64 (ds_moving_rms)."""
+    x, px, on_dev, n_ch, ld, n = _level_samples(x)
+    w = int(window_length)
+    assert w >= 1, "the window has at least one sample"
+    if n_ch * n * (2 + min(w, n) / 1024) > LEVEL_MOVING_MAX_WORK:
+        raise NotImplementedError(f"levels: a window of {w} samples over {n_ch} x {n} samples is beyond "
+                                  f"LEVEL_MOVING_MAX_WORK = {LEVEL_MOVING_MAX_WORK:g} squares")
+    basis = level_basis(n, _level_order(n, 1))
+    out = np.empty((n, n_ch), dtype=np.float64)
+    ctx = _level_ctx(x)
+    ctx.check(ctx.lib.ds_moving_rms(ctx.handle, px, on_dev, n_ch, ld, n, _ptr(basis), w, _ptr(out)), "ds_moving_rms")
+    return out
+
+
+def loudness_block_count(n: int, tg: int, step: int) -> int:
+    """ceil((n - tg) / step), never below 0: the frames the reference cuts without padding."""
+    return max(0, -(-(int(n) - int(tg)) // int(step)))
+
+
+def loudness_blocks(x, sos, tg: int, step: int) -> np.ndarray:
+    """The mean squares of the blocks of tg samples every `step` of x filtered by the cascade sos (K, 6) from rest, as
+    (blocks, C) float64 (ds_loudness_blocks); (0, C) when the signal holds no block."""
+    x, px, on_dev, n_ch, ld, n = _level_samples(x)
+    sos = np.ascontiguousarray(np.atleast_2d(sos), dtype=np.float64)
+    assert sos.ndim == 2 and sos.shape[1] == 6 and sos.shape[0] >= 1, "sos is (sections, 6) with at least one section"
+    if sos.shape[0] > IIR_MAX_SECTIONS:
+        raise NotImplementedError(f"levels: a cascade of {sos.shape[0]} sections is beyond the {IIR_MAX_SECTIONS} of the section runner")
+    n_blocks = loudness_block_count(n, tg, step)
+    z = np.empty((n_blocks, n_ch), dtype=np.float64)
+    if n_blocks == 0:
+        return z
+    ctx = _level_ctx(x)
+    ctx.check(ctx.lib.ds_loudness_blocks(ctx.handle, px, on_dev, n_ch, ld, n, _ptr(sos), sos.shape[0], int(tg), int(step),
+                                         n_blocks, _ptr(z)), "ds_loudness_blocks")
+    return z
+
+
+def envelope_analytic(x) -> np.ndarray:
+    """|hilbert(x minus its least-squares line)| as (N, C) float64 (ds_envelope_analytic), within the bounds of the
+    float64 transform."""
+    n = _samples_shape(x if isinstance(x, DevicePlanar) else np.asarray(x))[0]
+    _fft64_guard(n)
+    x, px, on_dev, n_ch, ld, n = _level_samples(x)
+    basis = level_basis(n, _level_order(n, 1))
+    out = np.empty((n, n_ch), dtype=np.float64)
+    ctx = _level_ctx(x)
+    ctx.check(ctx.lib.ds_envelope_analytic(ctx.handle, px, on_dev, n_ch, ld, n, _ptr(basis), _ptr(out)), "ds_envelope_analytic")
+    return out

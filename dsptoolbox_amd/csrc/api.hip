@@ -58,6 +58,7 @@
 #include "kernels_room.hpp"
 #include "kernels_vqt.hpp"
 #include "kernels_fx.hpp"
+#include "kernels_level.hpp"
 #include "size_guards.hpp"
 
 using namespace dsk;
@@ -5409,6 +5410,259 @@ extern "C" int ds_fx_tremolo(ds_ctx* c, const void* x, int on_device, int n_str,
         CHK(stage(c, &c->ws, &c->ws_bytes, {{8, (size_t)n, mod}}, t));
         return launch(c, "fx_tremolo", dsfx::k_fx_tremolo<T>, fx_grid(n, n_str), dsfx::NT, 0,
                       dsfx::TremoloArgs<T>{src, dst, n, (const double*)t[0]});
+    });
+}
+
+// ---- levels and loudness (kernels_level.hpp), float64 ---------------------------------------------------------------
+// What every entry takes: x, n samples of n_ch channels, on the host as (samples, channels) float64 or on the device as
+// planar float32 rows of pitch ldx.  basis: the host's [2 + 2 * 8] doubles (N - 1) / 2, 1 / sqrt(N), a_0 .. a_7,
+// b_0 .. b_7 of the orthonormal recurrence (kernels_level.hpp), read up to `order`.
+struct LevelCall {
+    const char* who;
+    const void* x;
+    int on_device, n_ch;
+    int64_t ldx, n;
+    int n_wg() const { return (int)((n + dslevel::SPAN - 1) / dslevel::SPAN); }
+    size_t elements() const { return (size_t)n_ch * (size_t)n; }
+    size_t x_count() const { return on_device ? 0 : elements(); }  // what a host call stages
+};
+
+static int level_check(ds_ctx* c, const LevelCall& q, const void* out) {
+    if (!c || !q.x || !out) return fail(c, DS_ERR_ARG, q.who, "null argument");
+    if (q.n_ch < 1 || q.n < 1 || (q.on_device && q.ldx < q.n)) return fail(c, DS_ERR_ARG, q.who, "bad shape");
+    if (level_shape_unsupported(q.n_ch, q.n))
+        return fail(c, DS_ERR_UNSUP, q.who, "more than 65535 channels, 2^31 - 1 samples a channel or 2^33 samples in all are not built");
+    return DS_OK;
+}
+
+// order -1: no polynomial (basis may be null)
+static int level_basis(ds_ctx* c, const LevelCall& q, int order, const double* basis, dslevel::Basis* bs) {
+    *bs = dslevel::Basis{};
+    bs->order = order;
+    if (order < 0) return DS_OK;
+    if (!basis) return fail(c, DS_ERR_ARG, q.who, "null argument");
+    if (order > dslevel::MAX_ORDER || order >= q.n)
+        return fail(c, DS_ERR_ARG, q.who, "the polynomial order is at most 8 and below the sample count");
+    bs->half = basis[0], bs->p0 = basis[1];
+    for (int k = 0; k < dslevel::MAX_ORDER; ++k) {
+        bs->a[k] = k < order ? basis[2 + k] : 0.0;
+        bs->b[k] = k < order ? basis[2 + dslevel::MAX_ORDER + k] : 0.0;
+        if (!std::isfinite(bs->a[k]) || !std::isfinite(bs->b[k])) return fail(c, DS_ERR_ARG, q.who, "the basis must be finite");
+    }
+    return DS_OK;
+}
+
+// run(src) over the samples where they lie; d0: the device address of a host call's staged samples
+template <class F>
+static int level_src(const LevelCall& q, const void* d0, F&& run) {
+    if (q.on_device) return run(dslevel::Src<float>{(const float*)q.x, 1, q.ldx});
+    return run(dslevel::Src<double>{(const double*)d0, q.n_ch, 1});
+}
+
+// c_0 .. c_order and max |x| of every channel: partial [n_ch][n_wg][NC] -> out_dev [n_ch][NC]
+template <typename T>
+static int level_project(ds_ctx* c, const LevelCall& q, dslevel::Src<T> x, const dslevel::Basis& bs, double* partial,
+                         double* out_dev) {
+    CHK(launch(c, "level_project", dslevel::k_level_project<T>, dim3((unsigned)q.n_wg(), (unsigned)q.n_ch), dslevel::NT, 0,
+               dslevel::ProjectArgs<T>{x, q.n, q.n_wg(), bs, partial}));
+    return launch(c, "level_final@project", dslevel::k_level_final<dslevel::MAX_ORDER + 1, 1>, dim3((unsigned)q.n_ch), dslevel::NT, 0,
+                  dslevel::FinalArgs{partial, q.n_wg(), out_dev});
+}
+
+// sum r^2, max |r|, max |x| of r = x - p(n): partial [n_ch][n_wg][NST] -> out_dev [n_ch][NST]
+template <typename T>
+static int level_stats(ds_ctx* c, const LevelCall& q, dslevel::Src<T> x, const dslevel::Basis& bs, const double* coef,
+                       double* partial, double* out_dev) {
+    CHK(launch(c, "level_stats", dslevel::k_level_stats<T>, dim3((unsigned)q.n_wg(), (unsigned)q.n_ch), dslevel::NT, 0,
+               dslevel::StatsArgs<T>{x, q.n, q.n_wg(), bs, coef, partial}));
+    return launch(c, "level_final@stats", dslevel::k_level_final<1, 2>, dim3((unsigned)q.n_ch), dslevel::NT, 0,
+                  dslevel::FinalArgs{partial, q.n_wg(), out_dev});
+}
+
+static size_t level_partial_count(const LevelCall& q) { return (size_t)q.n_ch * q.n_wg() * dslevel::NC; }
+
+// out: host (n_ch, 10): c_0 .. c_8 (zero past the order), max |x|
+extern "C" int ds_level_project(ds_ctx* c, const void* x, int on_device, int n_ch, int64_t ldx, int64_t n, int order,
+                                const double* basis, double* out) {
+    const LevelCall q{"ds_level_project", x, on_device, n_ch, ldx, n};
+    CHK(level_check(c, q, out));
+    dslevel::Basis bs;
+    if (order < 0) return fail(c, DS_ERR_ARG, q.who, "needs an order >= 0");
+    CHK(level_basis(c, q, order, basis, &bs));
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t n_rec = (size_t)n_ch * dslevel::NC;
+    CHK(mem_check(c, q.who, level_partial_count(q) * 8, (q.x_count() + n_rec) * 8, 0));
+    return staged(c, {{8, q.x_count(), x}, {8, n_rec, nullptr, out}}, [&](void* const* d) {
+        void* t[kMaxStaged];
+        CHK(stage(c, &c->ws, &c->ws_bytes, {{8, level_partial_count(q)}}, t));
+        return level_src(q, d[0], [&](auto src) { return level_project(c, q, src, bs, (double*)t[0], (double*)d[1]); });
+    });
+}
+
+// out: host (n_ch, 3): sum (x - p)^2, max |x - p|, max |x|, p the least-squares polynomial of `order` of each channel;
+// with `common` (order 0 only) the mean of all channels together
+extern "C" int ds_level_stats(ds_ctx* c, const void* x, int on_device, int n_ch, int64_t ldx, int64_t n, int order,
+                              const double* basis, int common, double* out) {
+    const LevelCall q{"ds_level_stats", x, on_device, n_ch, ldx, n};
+    CHK(level_check(c, q, out));
+    dslevel::Basis bs;
+    if (order < 0 || (common && order != 0)) return fail(c, DS_ERR_ARG, q.who, "needs an order >= 0, and 0 with a common mean");
+    CHK(level_basis(c, q, order, basis, &bs));
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t n_rec = (size_t)n_ch * dslevel::NC, n_st = (size_t)n_ch * dslevel::NST;
+    CHK(mem_check(c, q.who, (level_partial_count(q) + n_rec) * 8 + 256, (q.x_count() + n_st) * 8, 0));
+    return staged(c, {{8, q.x_count(), x}, {8, n_st, nullptr, out}}, [&](void* const* d) {
+        void* t[kMaxStaged];
+        CHK(stage(c, &c->ws, &c->ws_bytes, {{8, level_partial_count(q)}, {8, n_rec}}, t));
+        double *partial = (double*)t[0], *coef = (double*)t[1];
+        return level_src(q, d[0], [&](auto src) {
+            CHK(level_project(c, q, src, bs, partial, coef));
+            if (common) CHK(launch(c, "level_common", dslevel::k_level_common, dim3(1), 64, 0, dslevel::CommonArgs{coef, n_ch}));
+            return level_stats(c, q, src, bs, coef, partial, (double*)d[1]);
+        });
+    });
+}
+
+// y[n] = (x[n] - p_c(n)) g_c fade[n] fade[N - 1 - n]; y as x: host (n, n_ch) float64 or planar float32 rows of pitch ld_y
+extern "C" int ds_level_apply(ds_ctx* c, const void* x, int on_device, int n_ch, int64_t ldx, int64_t n, int order,
+                              const double* basis, int norm_mode, double norm_factor, const double* gain, const double* fade,
+                              int64_t l_fade, int at_start, int at_end, void* y, int64_t ld_y) {
+    const LevelCall q{"ds_level_apply", x, on_device, n_ch, ldx, n};
+    CHK(level_check(c, q, y));
+    if (on_device && ld_y < n) return fail(c, DS_ERR_ARG, q.who, "bad shape");
+    if (norm_mode < dslevel::NORM_NONE || norm_mode > dslevel::NORM_RMS_ALL || (norm_mode != dslevel::NORM_NONE && gain))
+        return fail(c, DS_ERR_ARG, q.who, "needs a known normalisation, and no gains beside one");
+    if (fade && (l_fade < 1 || l_fade > n || !(at_start || at_end)))
+        return fail(c, DS_ERR_ARG, q.who, "a fade has 1 .. n samples and an end to apply to");
+    dslevel::Basis bs, bs0;
+    CHK(level_basis(c, q, order, basis, &bs));
+    const bool norm = norm_mode != dslevel::NORM_NONE, rms = norm_mode >= dslevel::NORM_RMS_EACH;
+    const double mean_basis[2 + 2 * dslevel::MAX_ORDER] = {0.5 * (double)(n - 1), 1.0 / std::sqrt((double)n)};
+    CHK(level_basis(c, q, norm ? 0 : -1, mean_basis, &bs0));
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t n_rec = (size_t)n_ch * dslevel::NC, n_st = (size_t)n_ch * dslevel::NST, n_fade = fade ? (size_t)l_fade : 0;
+    const size_t n_io = on_device ? 0 : q.elements();
+    CHK(mem_check(c, q.who, (level_partial_count(q) + 2 * n_rec + n_st + n_ch + n_fade) * 8 + 6 * 256, 2 * n_io * 8, 0));
+    return staged(c, {{8, n_io, x}, {8, n_io, nullptr, on_device ? nullptr : y}}, [&](void* const* d) {
+        void* t[kMaxStaged];
+        CHK(stage(c, &c->ws, &c->ws_bytes, {{8, level_partial_count(q)}, {8, n_rec}, {8, n_rec}, {8, n_st}, {8, (size_t)n_ch, gain},
+                                            {8, n_fade, fade}}, t));
+        double *partial = (double*)t[0], *coef = (double*)t[1], *proj0 = (double*)t[2], *stats = (double*)t[3], *g = (double*)t[4];
+        const dslevel::ApplyArgs a{n, n_ch, bs, coef, gain || norm ? g : nullptr, fade ? (const double*)t[5] : nullptr, l_fade,
+                                   at_start, at_end};
+        CHK(level_src(q, d[0], [&](auto src) {
+            if (order >= 0) CHK(level_project(c, q, src, bs, partial, coef));
+            if (norm) {
+                CHK(level_project(c, q, src, bs0, partial, proj0));
+                if (norm_mode == dslevel::NORM_RMS_ALL)
+                    CHK(launch(c, "level_common", dslevel::k_level_common, dim3(1), 64, 0, dslevel::CommonArgs{proj0, n_ch}));
+                if (rms) CHK(level_stats(c, q, src, bs0, proj0, partial, stats));
+                CHK(launch(c, "level_gain", dslevel::k_level_gain, dim3(1), 64, 0,
+                           dslevel::GainArgs{norm_mode, n_ch, n, norm_factor, proj0, stats, g}));
+            }
+            return DS_OK;
+        }));
+        if (on_device)
+            return launch(c, "level_apply@f4", dslevel::k_level_apply_f4, dim3((unsigned)((n / 4 + 2 + dslevel::NT - 1) / dslevel::NT), (unsigned)n_ch),
+                          dslevel::NT, 0, dslevel::ApplyF4{(const float*)x, ldx, (float*)y, ld_y, a});
+        const int64_t pairs = ((int64_t)q.elements() + 1) / 2;
+        return launch(c, "level_apply@d2", dslevel::k_level_apply_d2, dim3((unsigned)((pairs + dslevel::NT - 1) / dslevel::NT)), dslevel::NT, 0,
+                      dslevel::ApplyD2{(const double*)d[0], (double*)d[1], a});
+    });
+}
+
+// out: host (n, n_ch) float64: sqrt(max(0, mean of the last w squares of x - line)), zeros before the first sample
+extern "C" int ds_moving_rms(ds_ctx* c, const void* x, int on_device, int n_ch, int64_t ldx, int64_t n, const double* basis,
+                             int64_t w, double* out) {
+    const LevelCall q{"ds_moving_rms", x, on_device, n_ch, ldx, n};
+    CHK(level_check(c, q, out));
+    if (w < 1) return fail(c, DS_ERR_ARG, q.who, "needs a window of at least one sample");
+    if (level_moving_work_too_large(n_ch, n, w)) return fail(c, DS_ERR_UNSUP, q.who, "a window this long on a signal this long is not built");
+    dslevel::Basis bs;
+    CHK(level_basis(c, q, n > 1 ? 1 : 0, basis, &bs));
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t n_rec = (size_t)n_ch * dslevel::NC;
+    CHK(mem_check(c, q.who, (level_partial_count(q) + n_rec) * 8 + 256, (q.x_count() + q.elements()) * 8, 0));
+    return staged(c, {{8, q.x_count(), x}, {8, q.elements(), nullptr, out}}, [&](void* const* d) {
+        void* t[kMaxStaged];
+        CHK(stage(c, &c->ws, &c->ws_bytes, {{8, level_partial_count(q)}, {8, n_rec}}, t));
+        double *partial = (double*)t[0], *coef = (double*)t[1];
+        return level_src(q, d[0], [&](auto src) {
+            using T = typename decltype(src)::type;
+            CHK(level_project(c, q, src, bs, partial, coef));
+            return launch(c, "level_moving", dslevel::k_level_moving<T>, dim3((unsigned)((n + dslevel::TILE - 1) / dslevel::TILE), (unsigned)n_ch),
+                          dslevel::NT, 0, dslevel::MovingArgs<T>{src, n, w, n_ch, bs, coef, (double*)d[1]});
+        });
+    });
+}
+
+// sos: host [n_sec][6], the weighting cascade; z: host (n_blocks, n_ch) float64, block b the mean square of the weighted
+// samples b step .. b step + tg - 1; n_blocks must be ceil((n - tg) / step) >= 1
+extern "C" int ds_loudness_blocks(ds_ctx* c, const void* x, int on_device, int n_ch, int64_t ldx, int64_t n, const double* sos,
+                                  int n_sec, int64_t tg, int64_t step, int64_t n_blocks, double* z) {
+    const LevelCall q{"ds_loudness_blocks", x, on_device, n_ch, ldx, n};
+    CHK(level_check(c, q, z));
+    if (!sos) return fail(c, DS_ERR_ARG, q.who, "null argument");
+    if (n_sec < 1) return fail(c, DS_ERR_ARG, q.who, "needs at least one section");
+    if (n_sec > iir::MAX_SEC) return fail(c, DS_ERR_UNSUP, q.who, "more than 32 second-order sections in one cascade is not built");
+    for (int i = 0; i < 6 * n_sec; ++i)
+        if (!std::isfinite(sos[i]) || (i % 6 == 3 && sos[i] == 0.0))
+            return fail(c, DS_ERR_ARG, q.who, "sections must be finite with a0 != 0");
+    if (tg < 1 || step < 1 || n <= tg || n_blocks != (n - tg + step - 1) / step)
+        return fail(c, DS_ERR_ARG, q.who, "needs more samples than one block, and ceil((n - tg) / step) blocks");
+    if (n_blocks > INT32_MAX) return fail(c, DS_ERR_UNSUP, q.who, "more than 2^31 - 1 blocks are not built");
+    const IirCall iq{q.who, n_ch, n, n, n, sos, 1, n_sec, DS_FB_PARALLEL};
+    HIPCHK(c, hipSetDevice(c->device));
+    // the float64 planar copy of resident samples and the weighted samples are pieces of c->io: the sos runner carves c->ws
+    const size_t n_wide = on_device ? q.elements() : 0, n_z = (size_t)n_blocks * n_ch;
+    const size_t n_groups = (size_t)((n + carry::G - 1) / carry::G);
+    CHK(mem_check(c, q.who, ((size_t)n_ch * n_groups * 2 * n_sec + 64 * (size_t)n_sec * n_sec) * 8 + 4 * 256,
+                  (q.x_count() + n_wide + q.elements() + n_z) * 8, 0));
+    return staged(c, {{8, q.x_count(), x}, {8, n_wide}, {8, q.elements()}, {8, n_z, nullptr, z}}, [&](void* const* d) {
+        double *wide = (double*)d[1], *yd = (double*)d[2];
+        if (on_device) {
+            dslevel::ApplyArgs a{};
+            a.n = n, a.n_ch = n_ch, a.bs.order = -1;
+            CHK(launch(c, "level_apply@widen", dslevel::k_level_apply<float, double>, dim3((unsigned)((n + dslevel::NT - 1) / dslevel::NT), (unsigned)n_ch),
+                       dslevel::NT, 0, dslevel::ApplyAny<float, double>{dslevel::Src<float>{(const float*)x, 1, ldx}, dslevel::Dst<double>{wide, 1, n}, a}));
+            CHK(iir_run<double>(c, iq, wide, n, 1, nullptr, yd, (int64_t)q.elements(), n, 1, nullptr));
+        } else {
+            CHK(iir_run<double>(c, iq, (const double*)d[0], 1, n_ch, nullptr, yd, (int64_t)q.elements(), n, 1, nullptr));
+        }
+        return launch(c, "level_blocks", dslevel::k_level_blocks, dim3((unsigned)n_blocks, (unsigned)n_ch), dslevel::NT, 0,
+                      dslevel::BlockArgs{yd, n, tg, step, n_ch, (double*)d[3]});
+    });
+}
+
+// out: host (n, n_ch) float64: |analytic signal| of x minus its least-squares line
+extern "C" int ds_envelope_analytic(ds_ctx* c, const void* x, int on_device, int n_ch, int64_t ldx, int64_t n, const double* basis,
+                                    double* out) {
+    const LevelCall q{"ds_envelope_analytic", x, on_device, n_ch, ldx, n};
+    CHK(level_check(c, q, out));
+    dslevel::Basis bs;
+    CHK(level_basis(c, q, n > 1 ? 1 : 0, basis, &bs));
+    const size_t n_rec = (size_t)n_ch * dslevel::NC;
+    Fft64Run r{c, {}, n_ch};
+    CHK(fft64_plan(c, q.who, n, n_ch, level_partial_count(q) * 8 + 256, (q.x_count() + 2 * q.elements() + n_rec) * 8 + 4 * 256, &r.pl));
+    // the detrended samples and the coefficients are pieces of c->io: the transform carves c->ws
+    return staged(c, {{8, q.x_count(), x}, {8, q.elements()}, {8, n_rec}, {8, q.elements(), nullptr, out}}, [&](void* const* d) {
+        void* t[kMaxStaged];
+        CHK(stage(c, &c->ws, &c->ws_bytes, {{8, level_partial_count(q)}}, t));
+        double *det = (double*)d[1], *coef = (double*)d[2];
+        const dslevel::ApplyArgs a{n, n_ch, bs, coef, nullptr, nullptr, 0, 0, 0};
+        CHK(level_src(q, d[0], [&](auto src) {
+            using T = typename decltype(src)::type;
+            CHK(level_project(c, q, src, bs, (double*)t[0], coef));
+            return launch(c, "level_apply@detrend", dslevel::k_level_apply<T, double>, dim3((unsigned)((n + dslevel::NT - 1) / dslevel::NT), (unsigned)n_ch),
+                          dslevel::NT, 0, dslevel::ApplyAny<T, double>{src, dslevel::Dst<double>{det, n_ch, 1}, a});
+        }));
+        CHK(r.carve_ws(0));
+        CHK(r.load(det, false, n));
+        CHK(r.fft(false));
+        CHK(r.point(fft64::POINT_MASK, 1.0));
+        CHK(r.fft(true));
+        return launch(c, "level_mag", dslevel::k_level_mag, dim3((unsigned)((q.elements() + dslevel::NT - 1) / dslevel::NT)), dslevel::NT, 0,
+                      dslevel::MagArgs{r.x, r.pl.ld, n, n_ch, 1.0 / (double)n, (double*)d[3]});
     });
 }
 

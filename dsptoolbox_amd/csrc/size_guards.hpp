@@ -171,3 +171,20 @@ constexpr int kFxMaxVoices = 64;
 DS_HD inline bool fx_shape_unsupported(int64_t n_streams, int64_t n_padded) {
     return n_streams > kFxMaxStreams || n_padded > kFxMaxSamples || (double)n_streams * (double)n_padded > (double)kFxMaxElements;
 }
+
+// Levels and loudness (kernels_level.hpp).  grid.y carries the channels: at most 65535.  A channel stays below 2^31
+// samples (grid.x of the sample-parallel kernels, 256 lanes each, and the 32-bit count of the reduction's workgroups) and
+// channels x samples at most 2^33: the host's float64 array is then 64 GiB, beyond what a call could stage anyway.  The
+// moving window rebuilds a sum of W squares once per tile of 1024 outputs, so its work is counted as samples x channels x
+// (2 + W / 1024) squares and kept below 1e12, a provisional bound (no rate of that kernel has been measured) that only
+// windows of many thousand samples on the longest signals reach.  Beyond any of these the entries answer DS_ERR_UNSUP.
+constexpr int kLevelMaxChannels = 65535;
+constexpr int64_t kLevelMaxSamples = ((int64_t)1 << 31) - 1;
+constexpr int64_t kLevelMaxElements = (int64_t)1 << 33;
+constexpr double kLevelMovingMaxWork = 1e12;
+DS_HD inline bool level_shape_unsupported(int64_t n_ch, int64_t n) {
+    return n_ch > kLevelMaxChannels || n > kLevelMaxSamples || (double)n_ch * (double)n > (double)kLevelMaxElements;
+}
+DS_HD inline bool level_moving_work_too_large(int64_t n_ch, int64_t n, int64_t w) {
+    return (double)n_ch * (double)n * (2.0 + (double)(w < n ? w : n) / 1024.0) > kLevelMovingMaxWork;
+}

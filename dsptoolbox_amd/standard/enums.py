@@ -3,7 +3,7 @@
 Only the members and methods the hot path touches are provided:
 SpectrumMethod (:7-18), SpectrumScaling (:21-229), FilterCoefficientsType
 (:232-243), BiquadEqType (:246-276), FilterBankMode (:279-292), FilterPassType
-(:295-305), IirDesignMethod (:308-338), Window (:341-437), SpectrumType, FrequencySpacing (:525-528).
+(:295-305), IirDesignMethod (:308-338), Window (:341-437), SpectrumType, FrequencySpacing (:525-528), FadeType (:532-536).
 """
 
 from enum import Enum, auto
@@ -226,3 +226,12 @@ class Window(Enum):
 
     def __call__(self, n_values: int, symmetric: bool):
         return _get_window(self.to_scipy_format(), n_values, not symmetric)
+
+
+class FadeType(Enum):
+    """The curve of standard.fade: linear in amplitude, linear in dB (from -100 dB), logarithmic in amplitude, or none."""
+
+    Linear = auto()
+    Exponential = auto()
+    Logarithmic = auto()
+    NoFade = auto()

@@ -1,10 +1,11 @@
 """tools: the fractional-octave band arithmetic of the reference's tools.fractional_octave_frequencies
 (dsptoolbox/tools.py:186-255), after the band definitions of IEC 61260-1:2014 / ANSI S1.11-2004,
-erb_frequencies (dsptoolbox/tools.py:261-336), and fractional_octave_smoothing (dsptoolbox/tools.py:22-23) on the
-device."""
+erb_frequencies (dsptoolbox/tools.py:261-336), fractional_octave_smoothing (dsptoolbox/tools.py:22-23) on the
+device, and the decibel conversions to_db and from_db (dsptoolbox/helpers/gain_and_level.py:28-46, 158-200)."""
 
 import numpy as np
 
+from ._db import from_db, to_db  # noqa: F401
 from .backend import fractional_octave_smoothing  # noqa: F401
 
 # base-ten octave ratio and reference frequency of IEC 61260-1 (5.2, 5.4)

@@ -789,6 +789,50 @@ int ds_fx_distort(ds_ctx* ctx, const void* x, int x_on_device, int n_str, int64_
 int ds_fx_tremolo(ds_ctx* ctx, const void* x, int x_on_device, int n_str, int64_t ldx, int64_t n, const double* mod,
                   void* y, int64_t ld_y);
 
+/* ---- levels and loudness: normalize, rms, crest_factor, fade, apply_gain (standard/gain_and_level.py:12-118, 169-200,
+ * 284-401 with helpers/gain_and_level.py:7-155), detrend and envelope (standard/other.py:182-284,
+ * standard/_standard_backend.py:382-405) and the block energies of lufs_integrated (standard/gain_and_level.py:203-281),
+ * float64 throughout, every sum in a fixed order (csrc/kernels_level.hpp).
+ * x_on_device == 0: x is a host (n, n_ch) float64 array and ldx is ignored; != 0: planar float32 on the device, channel c
+ * at x + c * ldx, read where it lies.  A polynomial trend of `order` 0 .. 8 (order < n) is the least-squares one in the
+ * discrete Chebyshev polynomials orthonormal on 0 .. n - 1; basis: host [18] = (n - 1) / 2, 1 / sqrt(n), a_0 .. a_7,
+ * b_0 .. b_7 of P_{k+1} = a_k t P_k - b_k P_{k-1}, t = i - (n - 1) / 2, read up to the order (the caller forms them in
+ * long double).  Bounds (DS_ERR_UNSUP beyond, before anything is allocated): 65535 channels, 2^31 - 1 samples a channel,
+ * 2^33 in all; DS_ERR_NOMEM, before anything is uploaded, when the memory is not free.
+ * ds_level_project: out (n_ch, 10) = sum_i x[i] P_k(i) for k = 0 .. 8 (0 past the order), max |x|.
+ * ds_level_stats: out (n_ch, 3) = sum (x - p)^2 term by term, max |x - p|, max |x|, p the channel's trend; `common`
+ *   (order 0): the mean of all channels together is removed instead (numpy's std of the flattened array).
+ * ds_level_apply: y[i] = (x[i] - p_c(i)) g_c fade[i] fade[n - 1 - i], one rounding per factor in this order, an absent
+ *   factor skipped: order < 0 no trend; g the host's gain[n_ch] or NULL, or with norm_mode DS_LEVEL_NORM_* the device's
+ *   norm_factor / max |x| or norm_factor / sqrt(mean (x - mean)^2) of each channel or of all; fade the host's
+ *   fade[l_fade], 1 <= l_fade <= n, applied to the first l_fade samples (at_start) and mirrored to the last (at_end).
+ *   y as x: host (n, n_ch) float64, or planar float32 rows of pitch ld_y on the device, where the result stays.
+ * ds_moving_rms: out (n, n_ch) = sqrt(max(0, sum of the squares of x - line over the last w samples / w)), samples before
+ *   the first counted as zero, w >= 1 (w may exceed n); basis of order 1.  The mean square is rebuilt every 1024 outputs:
+ *   its error does not grow along the signal.  n_ch * n * (2 + min(w, n) / 1024) at most 1e12.
+ * ds_loudness_blocks: the cascade sos (n_sec, 6), 1 <= n_sec <= 32, on the float64 section runner of ds_iir_sos from rest, then
+ *   z (n_blocks, n_ch) = mean of the tg squares from sample b * step on; n > tg, n_blocks == ceil((n - tg) / step).
+ * ds_envelope_analytic: out (n, n_ch) = |hilbert(x - line)| on the transform of ds_hilbert and within its length bounds;
+ *   basis of order 1.                                                                                                */
+#define DS_LEVEL_NORM_NONE 0
+#define DS_LEVEL_NORM_PEAK_EACH 1
+#define DS_LEVEL_NORM_PEAK_ALL 2
+#define DS_LEVEL_NORM_RMS_EACH 3
+#define DS_LEVEL_NORM_RMS_ALL 4
+int ds_level_project(ds_ctx* ctx, const void* x, int x_on_device, int n_ch, int64_t ldx, int64_t n, int order,
+                     const double* basis, double* out);
+int ds_level_stats(ds_ctx* ctx, const void* x, int x_on_device, int n_ch, int64_t ldx, int64_t n, int order,
+                   const double* basis, int common, double* out);
+int ds_level_apply(ds_ctx* ctx, const void* x, int x_on_device, int n_ch, int64_t ldx, int64_t n, int order,
+                   const double* basis, int norm_mode, double norm_factor, const double* gain, const double* fade,
+                   int64_t l_fade, int at_start, int at_end, void* y, int64_t ld_y);
+int ds_moving_rms(ds_ctx* ctx, const void* x, int x_on_device, int n_ch, int64_t ldx, int64_t n, const double* basis,
+                  int64_t w, double* out);
+int ds_loudness_blocks(ds_ctx* ctx, const void* x, int x_on_device, int n_ch, int64_t ldx, int64_t n, const double* sos,
+                       int n_sec, int64_t tg, int64_t step, int64_t n_blocks, double* z);
+int ds_envelope_analytic(ds_ctx* ctx, const void* x, int x_on_device, int n_ch, int64_t ldx, int64_t n,
+                         const double* basis, double* out);
+
 /* ---- multi-GPU: RCCL over xGMI, one process per GPU -----------------------
  * The hot path has no exchange step: the only collectives are the
  * broadcast of a shared input (sweep / taps / inverse spectrum) and the gather of sharded
