@@ -7,7 +7,7 @@ from .classes import Filter, FilterBank, ImpulseResponse, MultiBandSignal, Signa
 from .standard.enums import (BiquadEqType, FadeType, FilterBankMode, FilterCoefficientsType, FilterPassType,
                              FrequencySpacing, IirDesignMethod, SpectrumMethod, SpectrumScaling, SpectrumType, Window)
 from .standard import (activity_detector, apply_gain, crest_factor, delay, detrend, envelope, fade, fractional_delay, latency,
-                       lufs_integrated, merge_filters, normalize, rms)
+                       lufs_integrated, merge_filters, normalize, resample, rms)
 from .transfer_functions.enums import SmoothingDomain, TransferFunctionType
 
 __version__ = "0.1.0"
@@ -16,4 +16,4 @@ __all__ = ["Signal", "ImpulseResponse", "Spectrum", "Filter", "FilterBank", "Mul
            "FilterPassType", "FilterCoefficientsType", "IirDesignMethod", "BiquadEqType", "TransferFunctionType", "SmoothingDomain",
            "transfer_functions", "transforms", "room_acoustics", "beamforming", "distances", "filterbanks", "tools", "standard",
            "fractional_delay", "latency", "delay", "effects", "activity_detector", "FadeType", "normalize", "rms", "crest_factor",
-           "fade", "apply_gain", "lufs_integrated", "detrend", "envelope", "merge_filters"]
+           "fade", "apply_gain", "lufs_integrated", "detrend", "envelope", "merge_filters", "resample"]

@@ -43,6 +43,7 @@ NO_SCRATCH = [
     "k_fx_stats", "k_fx_follow", "k_fx_comb", "k_fx_voices", "k_fx_curve_peak", "k_fx_shape", "k_fx_tremolo", "k_fx_scale",
     "k_level_project", "k_level_final", "k_level_common", "k_level_stats", "k_level_gain", "k_level_apply", "k_level_moving",
     "k_level_blocks", "k_level_mag",
+    "k_resample_poly",
 ]
 
 

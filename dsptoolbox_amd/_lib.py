@@ -175,6 +175,8 @@ SIGNATURES = {
     "ds_vqt": (C.c_int, [ctx_p, C.c_void_p, C.c_int, C.c_int, i64, i64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
     "ds_resample_int": (C.c_int, [ctx_p, C.c_void_p, i64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "ds_resample_poly": (C.c_int, [ctx_p, C.c_void_p, i64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "ds_resample_poly_dev": (C.c_int, [ctx_p, C.c_void_p, i64, i64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, i64]),
     "ds_fx_compress": (C.c_int, [ctx_p, C.c_void_p, C.c_int, C.c_int, i64, i64, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                  C.c_void_p, i64]),
     "ds_fx_detect": (C.c_int, [ctx_p, C.c_void_p, C.c_int, C.c_int, i64, i64, C.c_double, C.c_double, C.c_int, C.c_void_p]),

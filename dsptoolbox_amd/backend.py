@@ -23,6 +23,7 @@ ONE route (_welch_route for a Welch estimate, _host_route for every other host f
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 from contextlib import contextmanager
 from typing import NamedTuple
@@ -2605,6 +2606,94 @@ def resample_int(td, up: int, down: int) -> np.ndarray:
     ctx = get_context()
     ctx.check(ctx.lib.ds_resample_int(ctx.handle, _ptr(x), n, n_ch, up, down, _ptr(taps), _ptr(out)), "ds_resample_int")
     return out
+
+
+# ---- rational-ratio resampling (ds_resample_poly, ds_resample_poly_dev; csrc/kernels_resample.hpp) ---------------------
+RESAMPLE_MAX_RATE = 640           # max(up, down) of the reduced ratio (csrc/size_guards.hpp; DS_ERR_UNSUP above)
+RESAMPLE_MAX_SAMPLES = 1 << 31    # the longer of input and output, times the channels
+RESAMPLE_MAX_CHANNELS = 65535     # grid.y carries the channel groups
+RESAMPLE_NT, RESAMPLE_PASSES, RESAMPLE_LDS_DOUBLES = 256, 4, 20480  # csrc/resample_plan.hpp
+
+
+def _resample_tile(up: int, down: int, n_ch: int) -> tuple:
+    """(tile, chunks, span, LDS bytes) of make_plan in csrc/resample_plan.hpp for a reduced ratio: the output samples a
+    workgroup takes, the pieces its sums run in, the input samples per channel it stages for each, and what it declares."""
+    cg = 1 if n_ch == 1 else 2 if n_ch == 2 else 4
+    terms = -(-(20 * max(up, down) + 1) // up)
+    table = up * (terms | 1)
+    w = (RESAMPLE_LDS_DOUBLES - table) // cg
+
+    def adv(tile):
+        return -(-(tile - 1) * down // up)
+
+    tile = RESAMPLE_PASSES * RESAMPLE_NT // cg
+    while tile > 1 and adv(tile) + terms > w and adv(tile) > w // 2:
+        tile >>= 1
+    jc = min(terms, w - adv(tile))
+    return tile, -(-terms // jc), adv(tile) + jc, 8 * (table + (adv(tile) + jc) * cg)
+
+
+def _resample_ratio(who: str, up, down, n: int, n_ch: int) -> tuple:
+    """The reduced (up, down) and the output length; ValueError for a bad ratio or no samples, NotImplementedError beyond
+    the kernel's bounds, each named, before anything reaches the device."""
+    if int(up) != up or int(down) != down or up < 1 or down < 1:
+        raise ValueError(f"{who}: up and down are positive integers")
+    if n < 1 or n_ch < 1:
+        raise ValueError(f"{who}: needs at least one sample and one channel")
+    up, down = int(up), int(down)
+    g = math.gcd(up, down)
+    up, down = up // g, down // g
+    n_out = -(-n * up // down)
+    if max(up, down) > RESAMPLE_MAX_RATE:
+        raise NotImplementedError(f"{who}: the ratio {up} / {down} is beyond RESAMPLE_MAX_RATE = {RESAMPLE_MAX_RATE} "
+                                  "(the larger of up and down once reduced: its taps would not fit a workgroup's LDS)")
+    if max(n, n_out) * n_ch > RESAMPLE_MAX_SAMPLES:
+        raise NotImplementedError(f"{who}: {max(n, n_out)} samples of {n_ch} channels are beyond RESAMPLE_MAX_SAMPLES = 2^31")
+    if n_ch > RESAMPLE_MAX_CHANNELS:
+        raise NotImplementedError(f"{who}: {n_ch} channels are beyond RESAMPLE_MAX_CHANNELS = {RESAMPLE_MAX_CHANNELS}")
+    return up, down, n_out
+
+
+def resample_poly(td, up: int, down: int, scale: float = 1.0) -> np.ndarray:
+    """scale * scipy.signal.resample_poly(td, up, down, axis=0) with its default filter for real (n, C) float64 data and
+    any ratio whose reduced form stays within RESAMPLE_MAX_RATE, on the device in float64 (ds_resample_poly).  `scale` is
+    folded into the taps.  A ratio of 1 / 1 returns a copy (times `scale`) without touching the device."""
+    if np.iscomplexobj(td):
+        raise NotImplementedError("resample_poly: complex samples are not run on the device")
+    x = np.ascontiguousarray(td, dtype=np.float64)
+    x = x[:, None] if x.ndim == 1 else x
+    assert x.ndim == 2, "the samples are (samples, channels)"
+    n, n_ch = x.shape
+    up, down, n_out = _resample_ratio("resample_poly", up, down, n, n_ch)
+    if up == down:
+        return x.copy() if scale == 1.0 else x * scale
+    taps = _resample_taps(up, down)
+    if scale != 1.0:
+        taps *= scale
+    out = np.empty((n_out, n_ch))
+    ctx = get_context()
+    ctx.check(ctx.lib.ds_resample_poly(ctx.handle, _ptr(x), n, n_ch, up, down, _ptr(taps), _ptr(out)), "ds_resample_poly")
+    return out
+
+
+def resample_poly_device(x_dev: DevicePlanar, up: int, down: int, scale: float = 1.0) -> DevicePlanar:
+    """resample_poly of planar float32 samples in HBM, read where they lie and summed in float64, into a new planar
+    float32 buffer of ceil(n up / down) samples per channel (ds_resample_poly_dev); nothing comes down to the host.  A
+    ratio of 1 / 1 without a scale returns the (immutable) samples themselves."""
+    assert isinstance(x_dev, DevicePlanar), "the samples are a DevicePlanar"
+    n, n_ch = x_dev.n_samples, x_dev.n_ch
+    up, down, n_out = _resample_ratio("resample_poly_device", up, down, n, n_ch)
+    if up == down:
+        return x_dev if scale == 1.0 else level_apply(x_dev, gain=scale)
+    taps = _resample_taps(up, down)
+    if scale != 1.0:
+        taps *= scale
+    ctx = x_dev.ctx
+    with device_scope(ctx) as dev:
+        d_y = dev.alloc(4 * n_ch * n_out, result=True)
+        ctx.check(ctx.lib.ds_resample_poly_dev(ctx.handle, C.c_void_p(x_dev.ptr), x_dev.ld, n, n_ch, up, down, _ptr(taps),
+                                               C.c_void_p(d_y.ptr), n_out), "ds_resample_poly_dev")
+    return DevicePlanar(d_y, n_ch, n_out, n_out, 0)
 
 
 # ---- audio effects (ds_fx_*, csrc/kernels_fx.hpp) ---------------------------------------------------------------------

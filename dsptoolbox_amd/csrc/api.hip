@@ -10,6 +10,7 @@
 #include <cstdio>
 #include <cstring>
 #include <map>
+#include <numeric>
 #include <set>
 #include <string>
 #include <thread>
@@ -59,6 +60,7 @@
 #include "kernels_vqt.hpp"
 #include "kernels_fx.hpp"
 #include "kernels_level.hpp"
+#include "kernels_resample.hpp"
 #include "size_guards.hpp"
 
 using namespace dsk;
@@ -5229,6 +5231,68 @@ extern "C" int ds_resample_int(ds_ctx* c, const double* x, int64_t n, int n_ch, 
         return vqt_interp<double>(c, "vqt_interp@real", (const double*)s[0], (double*)s[1], (const double*)t[0],
                                   (const InterpOct*)t[1], &oc, 1, 1, n_ch);
     });
+}
+
+// ---- rational-ratio resampling (kernels_resample.hpp, resample_plan.hpp), float64 arithmetic ---------------------------
+static_assert(resample::MAX_RATE == kResampleMaxRate, "the plan and the guard name the same rate");
+
+struct ResampleCall {
+    const char* who;
+    int64_t n;
+    int n_ch, up, down;
+    const double* taps;  // host, up * firwin(20 r + 1, 1 / r, kaiser 5.0) with r = max(up, down)
+    int64_t n_out() const { return resample::out_len(n, up, down); }
+};
+
+// shape and bounds; nothing touches the device
+static int resample_check(ds_ctx* c, const ResampleCall& q, const void* x, const void* y) {
+    if (!x || !y || !q.taps) return fail(c, DS_ERR_ARG, q.who, "null argument");
+    if (q.n < 1 || q.n_ch < 1 || q.up < 1 || q.down < 1 || (q.up == 1 && q.down == 1) || std::gcd(q.up, q.down) != 1)
+        return fail(c, DS_ERR_ARG, q.who, "needs samples, channels and a reduced ratio other than 1 / 1");
+    if (resample_shape_unsupported(q.up, q.down, q.n, q.n_out(), q.n_ch))
+        return fail(c, DS_ERR_UNSUP, q.who, "a rate beyond 640, more than 2^31 samples in all or more than 65535 channels are not built");
+    if (!c) return fail(c, DS_ERR_ARG, q.who, "null argument");
+    return DS_OK;
+}
+
+// sample n of channel ch at x[n xss + ch xcs] -> y[m yss + ch ycs], both on the device
+template <typename TI, typename TO>
+static int resample_run(ds_ctx* c, const ResampleCall& q, const TI* x, int64_t xss, int64_t xcs, TO* y, int64_t yss, int64_t ycs) {
+    namespace rs = resample;
+    const rs::Plan pl = rs::make_plan(q.up, q.down, q.n_ch);
+    std::vector<double> hp((size_t)rs::table_doubles(pl));
+    rs::phase_major(pl, q.taps, hp.data());
+    void* t[kMaxStaged];
+    CHK(stage(c, &c->ws, &c->ws_bytes, {{8, hp.size(), hp.data()}}, t));
+    const int64_t n_out = q.n_out(), tiles = (n_out + pl.tile - 1) / pl.tile;
+    if (tiles > INT32_MAX) return fail(c, DS_ERR_UNSUP, q.who, "more tiles than one launch covers");
+    return launch(c, "resample_poly", rs::k_resample_poly<TI, TO>, dim3((unsigned)tiles, (unsigned)((q.n_ch + pl.cg - 1) / pl.cg)),
+                  rs::NT, (size_t)rs::lds_doubles(pl) * 8,
+                  rs::PolyArgs<TI, TO>{x, xss, xcs, q.n, (const double*)t[0], y, yss, ycs, n_out, q.n_ch, pl});
+}
+
+// x: host (n, n_ch) float64 -> out: host (ceil(n up / down), n_ch) float64
+extern "C" int ds_resample_poly(ds_ctx* c, const double* x, int64_t n, int n_ch, int up, int down, const double* taps,
+                                double* out) {
+    const ResampleCall q{"ds_resample_poly", n, n_ch, up, down, taps};
+    CHK(resample_check(c, q, x, out));
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t nx = (size_t)n * n_ch, ny = (size_t)q.n_out() * n_ch;
+    CHK(mem_check(c, q.who, (size_t)resample::LDS_DOUBLES * 8, (nx + ny) * 8, 0));
+    return staged(c, {{8, nx, x}, {8, ny, nullptr, out}}, [&](void* const* d) {
+        return resample_run<double, double>(c, q, (const double*)d[0], n_ch, 1, (double*)d[1], n_ch, 1);
+    });
+}
+
+// x: planar float32 on the device, channel ch at x + ch ldx -> y: planar float32 on the device, channel ch at y + ch ld_y
+extern "C" int ds_resample_poly_dev(ds_ctx* c, const float* x, int64_t ldx, int64_t n, int n_ch, int up, int down,
+                                    const double* taps, float* y, int64_t ld_y) {
+    const ResampleCall q{"ds_resample_poly_dev", n, n_ch, up, down, taps};
+    CHK(resample_check(c, q, x, y));
+    if (ldx < n || ld_y < q.n_out()) return fail(c, DS_ERR_ARG, q.who, "bad shape");
+    HIPCHK(c, hipSetDevice(c->device));
+    CHK(mem_check(c, q.who, (size_t)resample::LDS_DOUBLES * 8, 0, 0));
+    return resample_run<float, float>(c, q, x, 1, ldx, y, 1, ld_y);
 }
 
 // ---- audio effects (kernels_fx.hpp), float64 ------------------------------------------------------------------------

@@ -188,3 +188,17 @@ DS_HD inline bool level_shape_unsupported(int64_t n_ch, int64_t n) {
 DS_HD inline bool level_moving_work_too_large(int64_t n_ch, int64_t n, int64_t w) {
     return (double)n_ch * (double)n * (2.0 + (double)(w < n ? w : n) / 1024.0) > kLevelMovingMaxWork;
 }
+
+// Rational-ratio resampling (kernels_resample.hpp, resample_plan.hpp).  The rate r = max(up, down) of the reduced ratio is
+// at most 640 (44100 <-> 192000): its tap table, 110 KB at most, shares the 160 KiB of LDS with the tile's input window.
+// The samples of one call -- the longer of input and output, times the channels -- stay at 2^31: a host call stages both
+// arrays in float64, 32 GiB together at the bound.  grid.y carries the channel groups: at most 65535 channels.  Beyond
+// any of these the entries answer DS_ERR_UNSUP.
+constexpr int kResampleMaxRate = 640;
+constexpr int64_t kResampleMaxSamples = (int64_t)1 << 31;
+constexpr int kResampleMaxChannels = 65535;
+DS_HD inline bool resample_shape_unsupported(int64_t up, int64_t down, int64_t n_in, int64_t n_out, int64_t n_ch) {
+    const int64_t longer = n_in > n_out ? n_in : n_out;
+    return up > kResampleMaxRate || down > kResampleMaxRate || n_ch > kResampleMaxChannels ||
+           (double)longer * (double)n_ch > (double)kResampleMaxSamples;
+}

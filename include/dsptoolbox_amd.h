@@ -748,6 +748,20 @@ int ds_vqt(ds_ctx* ctx, const void* x, int x_on_device, int n_ch, int64_t ldx, i
 int ds_resample_int(ds_ctx* ctx, const double* x, int64_t n, int n_ch, int up, int down, const double* taps,
                     double* out);
 
+/* ---- rational-ratio resampling: standard.resample (standard/resampling.py:9-43), which is scipy.signal.resample_poly
+ * with its default filter, in one launch, float64 arithmetic (csrc/kernels_resample.hpp).  up and down are coprime and
+ * not both 1; r = max(up, down); taps: the host's up * firwin(20 r + 1, 1 / r, window=("kaiser", 5.0)), 20 r + 1 values.
+ *     out[m] = sum_n x[n] taps[m down + 10 r - n up],   m < n_out = ceil(n up / down)
+ * ds_resample_poly: x host (n, n_ch) float64 -> out host (n_out, n_ch) float64.
+ * ds_resample_poly_dev: x planar float32 on the device, channel c at x + c * ldx, read where it lies and widened ->
+ * y planar float32 on the device, channel c at y + c * ld_y (ld_y >= n_out), one rounding to float32 per value.
+ * Bounds (DS_ERR_UNSUP beyond, before anything is allocated): r <= 640; max(n, n_out) * n_ch <= 2^31; n_ch <= 65535.
+ * DS_ERR_NOMEM, before anything is uploaded, when the device has not the memory free.                             */
+int ds_resample_poly(ds_ctx* ctx, const double* x, int64_t n, int n_ch, int up, int down, const double* taps,
+                     double* out);
+int ds_resample_poly_dev(ds_ctx* ctx, const float* x, int64_t ldx, int64_t n, int n_ch, int up, int down,
+                         const double* taps, float* y, int64_t ld_y);
+
 /* ---- audio effects: effects.Compressor, DigitalDelay, Chorus, Distortion, Tremolo (effects/effects.py) and the gate of
  * standard.activity_detector (standard/_standard_backend.py:324-379), float64 throughout (csrc/kernels_fx.hpp).
  * A stream is one channel of one band.  x_on_device == 0: x is a host (n, n_str) float64 array, y a host (n_out, n_str)
