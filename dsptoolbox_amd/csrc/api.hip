@@ -3737,7 +3737,6 @@ static int cwt_run(ds_ctx* c, const CwtCall& q, const float* x, int64_t ld, int 
         while (M < 2 * lc) M *= 2;
         classes[(int)M].push_back(Item{i, k0, lc, h - k0});
     }
-    const int npair = (n_ch + 1) / 2;
     for (auto& kv : classes) {
         const int M = kv.first;
         const auto& items = kv.second;
@@ -3752,6 +3751,7 @@ static int cwt_run(ds_ctx* c, const CwtCall& q, const float* x, int64_t ld, int 
         if (nb64 > INT32_MAX || nf > 65535 || n_ch > 65535)
             return fail(c, DS_ERR_UNSUP, "cwt: too many blocks, frequencies or channels in one call");
         const int n_blocks = (int)nb64;
+        const int64_t n_pairs = (int64_t)n_ch * dscwt::n_block_pairs(n_blocks);  // two blocks of one channel per transform
         std::vector<Freq> fr(nf);
         for (int i = 0; i < nf; ++i) {
             fr[i] = Freq{items[i].row, ntaps, items[i].len, items[i].hc + cc};
@@ -3764,12 +3764,12 @@ static int cwt_run(ds_ctx* c, const CwtCall& q, const float* x, int64_t ld, int 
         const int64_t n_items = (int64_t)nf * n_blocks * n_ch;
         // big route: items per launch pair (the columns stage writes M complex values per item)
         const int64_t chunk = big ? std::min<int64_t>({n_items, 65535, std::max<int64_t>(1, ((int64_t)256 << 20) / (8 * (int64_t)M))}) : 0;
-        if (big && ((int64_t)npair * n_blocks > 65535))
-            return fail(c, DS_ERR_UNSUP, "cwt: more than 65535 four-step blocks in one call");
-        const size_t n_zs = big ? (size_t)std::max<int64_t>({(int64_t)npair * n_blocks, nf, chunk}) * M : 0;
+        if (big && n_pairs > 65535)
+            return fail(c, DS_ERR_UNSUP, "cwt: more than 65535 four-step block pairs in one call");
+        const size_t n_zs = big ? (size_t)std::max<int64_t>({n_pairs, nf, chunk}) * M : 0;
         void* t[kMaxStaged];
         CHK(stage(c, &c->ws, &c->ws_bytes, {{4, (size_t)n_ch, q.channels}, {sizeof(Freq), (size_t)nf, fr.data()}, {8, (size_t)ntaps, ht.data()},
-                                            {8, (size_t)npair * n_blocks * M}, {8, (size_t)nf * M}, {8, n_zs}}, t));
+                                            {8, (size_t)n_pairs * M}, {8, (size_t)nf * M}, {8, n_zs}}, t));
         const int* dch = (const int*)t[0];
         const Freq* dfr = (const Freq*)t[1];
         const float2* dtaps = (const float2*)t[2];
@@ -3785,7 +3785,7 @@ static int cwt_run(ds_ctx* c, const CwtCall& q, const float* x, int64_t ld, int 
                 constexpr int NN = decltype(k)::value;
                 const size_t lds = Plan<NN>::LDS_BYTES;
                 CHK(launch(c, "cwt_wspec", dscwt::k_cwt_wspec<NN>, dim3(nf), Plan<NN>::NT, lds, wa));
-                CHK(launch(c, "cwt_fwd", dscwt::k_cwt_fwd<NN>, dim3(n_blocks, npair), Plan<NN>::NT, lds, fa));
+                CHK(launch(c, "cwt_fwd", dscwt::k_cwt_fwd<NN>, dim3(dscwt::n_block_pairs(n_blocks), n_ch), Plan<NN>::NT, lds, fa));
                 return launch(c, "cwt_inv", dscwt::k_cwt_inv<NN>, dim3(n_blocks, n_ch, nf), Plan<NN>::NT, lds, ia);
             });
             if (rc != DS_OK) return rc;
@@ -3796,10 +3796,10 @@ static int cwt_run(ds_ctx* c, const CwtCall& q, const float* x, int64_t ld, int 
         CHK(launch(c, "cwt_pad@big", dscwt::k_cwt_pad, dim3(grid_x, nf), 256, 0, dscwt::PadArgs{dtaps, dfr, M, inv_m, zs}));
         CHK(big_cols(c, zs, nullptr, 0, 0, 0, zs, M, nf));
         CHK(big_rows(c, zs, W, M, nf));
-        CHK(launch(c, "cwt_segments@big", dscwt::k_cwt_segments, dim3(grid_x, npair * n_blocks), 256, 0,
+        CHK(launch(c, "cwt_segments@big", dscwt::k_cwt_segments, dim3(grid_x, (unsigned)n_pairs), 256, 0,
                    dscwt::SegArgs{x, ld, N, dch, n_ch, n_blocks, V, cc, M, zs}));
-        CHK(big_cols(c, zs, nullptr, 0, 0, 0, zs, M, npair * n_blocks));
-        CHK(big_rows(c, zs, Z, M, npair * n_blocks));
+        CHK(big_cols(c, zs, nullptr, 0, 0, 0, zs, M, (int)n_pairs));
+        CHK(big_rows(c, zs, Z, M, (int)n_pairs));
         constexpr int N1 = dscwt::BIG_N1;
         const int n2 = M / N1;
         const float2 *tw1, *tw2;

@@ -10,11 +10,15 @@
 // one segment layout: block b holds x[b V - cc + j], j < M (zeros outside the signal), with cc the class's largest
 // L_f - 1 - h_f.  For every frequency of the class the circular product with the tap spectrum is the linear
 // convolution at j >= L_f - 1, and output sample n = b V + t sits at j = t + h_f + cc.  V = M - max(h_f) - cc.
-//   k_cwt_fwd<M>   one real block pair (channels 2p, 2p + 1 as real / imaginary part) -> its M-point spectrum,
-//                  computed ONCE per class and shared by all the class's wavelets
+//   k_cwt_fwd<M>   one real block pair (blocks 2q, 2q + 1 of ONE channel as real / imaginary part) -> its M-point
+//                  spectrum, computed ONCE per class and shared by all the class's wavelets
 //   k_cwt_wspec<M> the wavelet's full complex spectrum (taps / M, zero padded), once per frequency
-//   k_cwt_inv<M>   per (block, channel, frequency): unpack the channel from the pair spectrum, multiply, inverse
+//   k_cwt_inv<M>   per (block, channel, frequency): unpack the block from the pair spectrum, multiply, inverse
 //                  M-point transform in LDS, store the V valid samples as complex64 straight into (F, N, C)
+// The two halves of a pair are blocks of the same channel, never two channels: the float32 transform's rounding error is
+// proportional to the pair's norm, so a channel paired with one 60 dB hotter would leave 1e-6 of its OWN peak (the
+// contract of every row), while two blocks of one channel are both held to that channel's peak.  The partner of the last
+// block of an odd count is zeros, and a silent channel's rows are exactly zero.
 // Blocks beyond one workgroup's LDS (M >= 2^15) take the four-step route (kernels_bigfft.hpp, N1 = 1024): the
 // forward spectra through k_big_cols / k_big_rows, the inverse through k_cwt_bcols (the spectral product fused
 // into its column load) and k_cwt_brows (the "same" window fused into its transposed store).  The inverse runs
@@ -46,19 +50,21 @@ struct Freq {
     int64_t j0;    // position of output sample b V in block b: h_f + cc
 };
 
-// real segment pair -> complex block: z[j] = x_a[s + j] + i x_b[s + j]
-__device__ __forceinline__ float2 seg_pair(const float* __restrict__ x, int64_t ld, const int* __restrict__ ch,
-                                           int n_ch, int pair, int64_t n_samples, int64_t s) {
-    const int ca = 2 * pair, cb = ca + 1;
+// block pairs of a class: blocks 2q and 2q + 1 of one channel share a transform
+__host__ __device__ __forceinline__ int n_block_pairs(int n_blocks) { return (n_blocks + 1) / 2; }
+
+// two real segments of one channel -> complex block: z = xc[sa] + i xc[sa + V]; zeros outside the signal and, with
+// has_b false (no block 2q + 1), in the imaginary part
+__device__ __forceinline__ float2 seg_pair(const float* __restrict__ xc, int64_t n_samples, int64_t sa, int64_t V,
+                                           bool has_b) {
     float2 z = make_float2(0.f, 0.f);
-    if (s >= 0 && s < n_samples) {
-        z.x = x[(int64_t)ch[ca] * ld + s];
-        if (cb < n_ch) z.y = x[(int64_t)ch[cb] * ld + s];
-    }
+    const int64_t sb = sa + V;
+    if (sa >= 0 && sa < n_samples) z.x = xc[sa];
+    if (has_b && sb >= 0 && sb < n_samples) z.y = xc[sb];
     return z;
 }
 
-// the spectrum of channel 2p (odd = false) or 2p + 1 (odd) from the pair spectrum Z at bins k and (M - k) mod M
+// the spectrum of block 2q (odd = false) or 2q + 1 (odd) from the pair spectrum Z at bins k and (M - k) mod M
 __device__ __forceinline__ float2 unpack(float2 P, float2 Qc, bool odd) {
     return odd ? make_float2(0.5f * (P.y + Qc.y), -0.5f * (P.x - Qc.x))
                : make_float2(0.5f * (P.x + Qc.x), 0.5f * (P.y - Qc.y));
@@ -70,21 +76,23 @@ struct FwdArgs {
     const int* ch;      // [n_ch] device
     int n_ch, n_blocks;
     int64_t V, cc;
-    float2* Z;          // [pair][block][M]
+    float2* Z;          // [channel][block pair][M]
     const float2* tw;
 };
 
 template <int M>
 __global__ __launch_bounds__(Plan<M>::NT) void k_cwt_fwd(FwdArgs p) {
     extern __shared__ __align__(16) float2 lds[];
-    const int tid = threadIdx.x, b = blockIdx.x, pair = blockIdx.y;
-    const int64_t s0 = (int64_t)b * p.V - p.cc;
-    for (int j = tid; j < M; j += Plan<M>::NT) lds[lidx(j)] = seg_pair(p.x, p.ld, p.ch, p.n_ch, pair, p.n_samples, s0 + j);
+    const int tid = threadIdx.x, q = blockIdx.x, c = blockIdx.y;
+    const int64_t s0 = (int64_t)(2 * q) * p.V - p.cc;
+    const float* xc = p.x + (int64_t)p.ch[c] * p.ld;
+    const bool has_b = 2 * q + 1 < p.n_blocks;
+    for (int j = tid; j < M; j += Plan<M>::NT) lds[lidx(j)] = seg_pair(xc, p.n_samples, s0 + j, p.V, has_b);
     __syncthreads();
     float2 v[Plan<M>::VMAX];
     fft<M, false, false, false>(v, lds, p.tw, tid);
     __syncthreads();
-    float2* z = p.Z + ((int64_t)pair * p.n_blocks + b) * M;
+    float2* z = p.Z + ((int64_t)c * n_block_pairs(p.n_blocks) + q) * M;
     for (int k = tid; k < M; k += Plan<M>::NT) z[k] = lds[lidx(k)];
 }
 
@@ -119,7 +127,7 @@ __global__ __launch_bounds__(Plan<M>::NT) void k_cwt_wspec(WspecArgs p) {
 }
 
 struct InvArgs {
-    const float2* Z;   // [pair][block][M]
+    const float2* Z;   // [channel][block pair][M]
     const float2* W;   // [nf][M], scaled by 1 / M
     const Freq* fr;
     int n_ch, n_blocks;
@@ -133,9 +141,9 @@ __global__ __launch_bounds__(Plan<M>::NT) void k_cwt_inv(InvArgs p) {
     extern __shared__ __align__(16) float2 lds[];
     const int tid = threadIdx.x, b = blockIdx.x, c = blockIdx.y, fi = blockIdx.z;
     const Freq f = p.fr[fi];
-    const float2* z = p.Z + ((int64_t)(c >> 1) * p.n_blocks + b) * M;
+    const float2* z = p.Z + ((int64_t)c * n_block_pairs(p.n_blocks) + (b >> 1)) * M;
     const float2* w = p.W + (int64_t)fi * M;
-    const bool odd = c & 1;
+    const bool odd = b & 1;
     for (int k = tid; k < M; k += Plan<M>::NT)
         lds[lidx(k)] = cmul(unpack(z[k], z[(M - k) & (M - 1)], odd), w[k]);
     __syncthreads();
@@ -149,7 +157,7 @@ __global__ __launch_bounds__(Plan<M>::NT) void k_cwt_inv(InvArgs p) {
 }
 
 // ---- four-step route (M = 1024 * n2) ----
-// complex segments of every (pair, block) into zs[pair][block][M], for k_big_cols / k_big_rows
+// complex segments of every (channel, block pair) into zs[channel][block pair][M], for k_big_cols / k_big_rows
 struct SegArgs {
     const float* x;
     int64_t ld, n_samples;
@@ -159,12 +167,15 @@ struct SegArgs {
     float2* zs;
 };
 __global__ void k_cwt_segments(SegArgs p) {
-    const int64_t bt = blockIdx.y;  // pair * n_blocks + block
-    const int pair = (int)(bt / p.n_blocks), b = (int)(bt % p.n_blocks);
-    const int64_t s0 = (int64_t)b * p.V - p.cc;
+    const int64_t bt = blockIdx.y;  // channel * block pairs + block pair
+    const int nbp = n_block_pairs(p.n_blocks);
+    const int c = (int)(bt / nbp), q = (int)(bt % nbp);
+    const int64_t s0 = (int64_t)(2 * q) * p.V - p.cc;
+    const float* xc = p.x + (int64_t)p.ch[c] * p.ld;
+    const bool has_b = 2 * q + 1 < p.n_blocks;
     float2* z = p.zs + bt * p.M;
     for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < p.M; j += (int64_t)gridDim.x * blockDim.x)
-        z[j] = seg_pair(p.x, p.ld, p.ch, p.n_ch, pair, p.n_samples, s0 + j);
+        z[j] = seg_pair(xc, p.n_samples, s0 + j, p.V, has_b);
 }
 
 // zero-padded taps / M of every frequency of the class into zw[fi][M]
@@ -192,7 +203,7 @@ __global__ void k_cwt_pad(PadArgs p) {
 
 // item = (fi * n_blocks + b) * n_ch + c (item0 + blockIdx.y)
 struct BigInvArgs {
-    const float2* Z;   // [pair][block][M] natural order
+    const float2* Z;   // [channel][block pair][M] natural order
     const float2* W;   // [nf][M] natural order, scaled by 1 / M
     const Freq* fr;
     int n_ch, n_blocks;
@@ -221,9 +232,9 @@ __global__ __launch_bounds__(1024) void k_cwt_bcols(BigInvArgs p) {
     int fi, b, c;
     big_item(p, p.item0 + blockIdx.y, fi, b, c);
     const int64_t M = p.M;
-    const float2* z = p.Z + ((int64_t)(c >> 1) * p.n_blocks + b) * M;
+    const float2* z = p.Z + ((int64_t)c * n_block_pairs(p.n_blocks) + (b >> 1)) * M;
     const float2* w = p.W + (int64_t)fi * M;
-    const bool odd = c & 1;
+    const bool odd = b & 1;
     const int total = N1 * p.ct;
     for (int i = threadIdx.x; i < total; i += blockDim.x) {
         const int j = i % p.ct, n1 = i / p.ct;

@@ -1,15 +1,17 @@
 """The continuous wavelet transform on the device against the reference's golden scalograms and against the float64
 restatement of tests/test_cwt_host.py: every row within 1e-6 max_t|x_ch| (the wavelets have unit magnitude sum, so
 |S| <= max|x|), every size class and both routes (LDS-resident and four-step) by exact wavelet lengths, the resident
-route, and the synchrosqueezing kernel."""
+route, and the synchrosqueezing kernel.  The bound is per channel and holds for channels of unequal level too -- the
+transforms pair two blocks of one channel, never two channels; tests/test_cwt_sweep_gpu.py runs those cases."""
 
 import numpy as np
 import pytest
 from scipy.signal import oaconvolve
 
 import dsptoolbox_amd as dsp
+from cwt_cases import Taps
 from dsptoolbox_amd import backend
-from dsptoolbox_amd.transforms import MorletWavelet, Wavelet, cwt
+from dsptoolbox_amd.transforms import MorletWavelet, cwt
 from dsptoolbox_amd.transforms._wavelets import _normalised_wavelets
 from test_cwt_host import golden, ref_scalogram, ref_squeeze
 
@@ -22,15 +24,6 @@ def row_error(S, ref, td):
     peak = np.abs(td).max(axis=0)
     peak[peak == 0] = 1.0
     return float((np.abs(S - ref).max(axis=1) / peak[None, :]).max())
-
-
-class Taps(Wavelet):
-    """A wavelet of exactly int(f) random complex taps (seeded by the length)."""
-
-    def get_wavelet(self, f, fs):
-        n = int(f)
-        rng = np.random.default_rng(n)
-        return rng.standard_normal(n) + 1j * rng.standard_normal(n)
 
 
 def test_golden_scalograms():
