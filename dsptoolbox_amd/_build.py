@@ -44,6 +44,7 @@ NO_SCRATCH = [
     "k_level_project", "k_level_final", "k_level_common", "k_level_stats", "k_level_gain", "k_level_apply", "k_level_moving",
     "k_level_blocks", "k_level_mag",
     "k_resample_poly",
+    "k_ss_analyze", "k_ss_track", "k_ss_synth", "k_ss_ola", "k_ss_peak",
 ]
 
 

@@ -186,6 +186,8 @@ SIGNATURES = {
     "ds_fx_distort": (C.c_int, [ctx_p, C.c_void_p, C.c_int, C.c_int, i64, i64, C.c_int, C.c_void_p, C.c_void_p, C.c_double,
                                 C.c_void_p, i64]),
     "ds_fx_tremolo": (C.c_int, [ctx_p, C.c_void_p, C.c_int, C.c_int, i64, i64, C.c_void_p, C.c_void_p, i64]),
+    "ds_fx_specsub": (C.c_int, [ctx_p, C.c_void_p, C.c_int, C.c_int, i64, i64, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                C.c_double, C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_double, C.c_void_p, i64]),
     "ds_level_project": (C.c_int, [ctx_p, C.c_void_p, C.c_int, C.c_int, i64, i64, C.c_int, C.c_void_p, C.c_void_p]),
     "ds_level_stats": (C.c_int, [ctx_p, C.c_void_p, C.c_int, C.c_int, i64, i64, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "ds_level_apply": (C.c_int, [ctx_p, C.c_void_p, C.c_int, C.c_int, i64, i64, C.c_int, C.c_void_p, C.c_int, C.c_double,

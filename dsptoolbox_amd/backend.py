@@ -2821,6 +2821,69 @@ def fx_tremolo(x, modulator):
     return _fx_run("ds_fx_tremolo", x, n, _ptr(mod))
 
 
+# ---- spectral subtraction (ds_fx_specsub, csrc/kernels_specsub.hpp) --------------------------------------------------------
+SS_MIN_WINDOW = 4                 # the packed transform has at least two points (csrc/size_guards.hpp)
+SS_MAX_WINDOW = 16384             # W / 2 complex points in LDS: 128 KiB (DS_ERR_UNSUP above)
+SS_MAX_WORKSPACE_BYTES = 1 << 32  # 8 (W + 2) bytes x frames x streams
+SS_MAX_OLA_TERMS = 1 << 29        # samples x streams x ceil(W / step)
+SS_TRACK_TILE = 8                 # frames a lane of k_ss_track loads ahead (TRACK_TILE of the kernels)
+SS_OLA_TILE = 256                 # kept output samples of one workgroup of k_ss_ola (OLA_TILE)
+SS_WINDOW_FLOOR = 1e-6            # the reference clips its window from below here
+SS_MODES = {"adaptive": 0, "static": 1}  # DS_FX_SPECSUB_* of the header
+
+
+def specsub_frames(n: int, window: int, step: int) -> int:
+    """ceil((n + 2 W) / step): the frames of a signal padded by W zeros at both ends, the last ones zero-padded."""
+    return -(-(int(n) + 2 * int(window)) // int(step))
+
+
+def specsub_window(window_type, window: int) -> np.ndarray:
+    """The reference's window: scipy's periodic one, clipped from below at 1e-6."""
+    spec = window_type.to_scipy_format() if isinstance(window_type, Window) else window_type
+    return np.clip(get_window(spec, int(window)), a_min=SS_WINDOW_FLOOR, a_max=None).astype(np.float64)
+
+
+def _specsub_guard(n_streams: int, n: int, window: int, step: int) -> None:
+    """ValueError for a window or step the frames cannot take, NotImplementedError beyond the kernels' bounds, each named;
+    before anything reaches the device."""
+    if window < 1 or window & (window - 1):
+        raise ValueError(f"spectral subtraction: the window, {window} samples, is not a power of two")
+    if window < SS_MIN_WINDOW:
+        raise NotImplementedError(f"spectral subtraction: a window of {window} samples is below SS_MIN_WINDOW = {SS_MIN_WINDOW}")
+    if window > SS_MAX_WINDOW:
+        raise NotImplementedError(f"spectral subtraction: a window of {window} samples is beyond SS_MAX_WINDOW = {SS_MAX_WINDOW}")
+    if not 1 <= step <= window:
+        raise ValueError(f"spectral subtraction: a step of {step} samples is not in 1 .. {window} (the overlap is too large)")
+    frames = specsub_frames(n, window, step)
+    if frames >= 1 << 31 or 8 * (window + 2) * frames * n_streams > SS_MAX_WORKSPACE_BYTES:
+        raise NotImplementedError(f"spectral subtraction: a frame workspace of {8 * (window + 2) * frames * n_streams:.3g} bytes "
+                                  f"({frames} frames x {n_streams} streams) is beyond SS_MAX_WORKSPACE_BYTES = 2^32")
+    if n * n_streams * -(-window // step) > SS_MAX_OLA_TERMS:
+        raise NotImplementedError(f"spectral subtraction: {n * n_streams * -(-window // step):.3g} overlap-add terms are beyond "
+                                  f"SS_MAX_OLA_TERMS = 2^29")
+
+
+def fx_specsub(x, window_type, window: int, step: int, mode: str = "adaptive", threshold_db: float = -40.0,
+               forgetting: float = 0.9, factor: float = 2.0, exponent: float = 2.0, noise_table=None, env_floor=None):
+    """Spectral subtraction of every stream (ds_fx_specsub): frames of `window` samples `step` apart of the zero-padded
+    samples, magnitudes max(|X|^e - t, 0)^(1 / e), weighted overlap-add, the peak restored.  mode "adaptive": t follows the
+    gated frames' amplitudes; "static": t = factor noise_table, (bins,) for every stream or (streams, bins), already
+    |PSD|^(e / 2).  env_floor: where the overlap-added squared window is clipped from below; None for no clipping."""
+    x = _fx_samples(x)
+    n, n_str = _samples_shape(x)
+    window, step = int(window), int(step)
+    _fx_guard(n_str, n)
+    _specsub_guard(n_str, n, window, step)
+    win = specsub_window(window_type, window)
+    table = None
+    if SS_MODES[mode] == SS_MODES["static"]:
+        table = np.asarray(noise_table, dtype=np.float64)
+        table = np.ascontiguousarray(np.broadcast_to(table, (n_str, window // 2 + 1)))
+    return _fx_run("ds_fx_specsub", x, n, _ptr(win), _ptr(win), window, step, SS_MODES[mode], float(threshold_db),
+                   float(forgetting), float(factor), float(exponent), _ptr(table) if table is not None else None,
+                   -1.0 if env_floor is None else float(env_floor))
+
+
 # ---- levels and loudness (ds_level_*, ds_moving_rms, ds_loudness_blocks, ds_envelope_analytic; csrc/kernels_level.hpp) ----
 LEVEL_NT = 256                # lanes per workgroup (NT of the kernels)
 LEVEL_PER_LANE = 16           # samples a lane of a reduction adds in turn (PER_LANE)

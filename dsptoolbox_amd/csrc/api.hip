@@ -59,6 +59,7 @@
 #include "kernels_room.hpp"
 #include "kernels_vqt.hpp"
 #include "kernels_fx.hpp"
+#include "kernels_specsub.hpp"
 #include "kernels_level.hpp"
 #include "kernels_resample.hpp"
 #include "size_guards.hpp"
@@ -5474,6 +5475,62 @@ extern "C" int ds_fx_tremolo(ds_ctx* c, const void* x, int on_device, int n_str,
         CHK(stage(c, &c->ws, &c->ws_bytes, {{8, (size_t)n, mod}}, t));
         return launch(c, "fx_tremolo", dsfx::k_fx_tremolo<T>, fx_grid(n, n_str), dsfx::NT, 0,
                       dsfx::TremoloArgs<T>{src, dst, n, (const double*)t[0]});
+    });
+}
+
+// ---- spectral subtraction (kernels_specsub.hpp), float64 --------------------------------------------------------------
+// win_a, win_s: host [W], the analysis and the synthesis window; table: host [n_str][W / 2 + 1], |noise PSD|^(e / 2) of
+// every stream (DS_FX_SPECSUB_STATIC; not read otherwise); env_floor: the envelope's floor, negative for none.
+extern "C" int ds_fx_specsub(ds_ctx* c, const void* x, int on_device, int n_str, int64_t ldx, int64_t n, const double* win_a,
+                             const double* win_s, int W, int step, int mode, double threshold_db, double forgetting,
+                             double factor, double exponent, const double* table, double env_floor, void* y, int64_t ld_y) {
+    const FxCall q{"ds_fx_specsub", x, on_device, n_str, ldx, n, n, y, ld_y};
+    const bool is_static = mode == dsss::MODE_STATIC;
+    // shape and bounds before the context is looked at: nothing here touches the device
+    if (!x || !y || !win_a || !win_s || (is_static && !table)) return fail(c, DS_ERR_ARG, q.who, "null argument");
+    if (n_str < 1 || n < 1 || (on_device && (ldx < n || ld_y < n))) return fail(c, DS_ERR_ARG, q.who, "bad shape");
+    if (W < kSpecsubMinWindow || (W & (W - 1)) || step < 1 || step > W || (mode != dsss::MODE_ADAPTIVE && !is_static) ||
+        !(forgetting > 0.0 && forgetting <= 1.0) || !(factor > 0.0) || !(exponent > 0.0))
+        return fail(c, DS_ERR_ARG, q.who,
+                    "needs a power-of-two window >= 4, 1 <= step <= window, a known mode, 0 < forgetting <= 1, factor > 0, exponent > 0");
+    if (specsub_window_unsupported(W)) return fail(c, DS_ERR_UNSUP, q.who, "windows above 16384 samples are not built");
+    if (specsub_work_too_large(n_str, n, W, step))
+        return fail(c, DS_ERR_UNSUP, q.who, "a frame workspace above 2^32 bytes or more than 2^29 overlap-add terms are not built");
+    CHK(fx_check(c, q));
+    int lg = 0;
+    while ((1 << lg) < W) ++lg;
+    const dsss::Frames fr{W, lg, step, (int)specsub_frames(n, W, step), n};
+    const size_t n_st = (size_t)n_str * dsfx::STAT, n_slot = (size_t)n_str * fr.n_frames * fr.pitch();
+    const size_t n_gate = (size_t)n_str * fr.n_frames, n_tab = is_static ? (size_t)n_str * fr.bins() : 0;
+    const size_t n_block = (size_t)((n + dsss::OLA_TILE - 1) / dsss::OLA_TILE);
+    const int power = exponent == 1.0 ? dsss::POWER_ONE : (exponent == 2.0 ? dsss::POWER_TWO : dsss::POWER_ANY);
+    return fx_io(c, q, 2 * n_st + q.elements() + n_slot + n_gate / 8 + 1 + 3 * (size_t)W + n_tab + n_gate + n_str * n_block + 11 * 32, [&](auto src, auto dst) {
+        using T = typename decltype(src)::type;
+        void* t[kMaxStaged];
+        CHK(stage(c, &c->ws, &c->ws_bytes, {{8, n_st}, {8, n_st}, {8, q.elements()}, {8, n_slot}, {1, n_gate}, {8, (size_t)W, win_a},
+                                            {8, (size_t)W, win_s}, {16, (size_t)W / 2}, {8, n_tab, table}, {8, n_gate},
+                                            {8, (size_t)n_str * n_block}}, t));
+        double *st_in = (double*)t[0], *st_out = (double*)t[1], *yd = (double*)t[2];
+        double2 *spec = (double2*)t[3], *tw = (double2*)t[7];
+        hipLaunchKernelGGL(f64c::k_twiddles, dim3((W / 2 + 255) / 256), dim3(256), 0, c->stream, tw, W / 2);
+        HIPCHK(c, hipGetLastError());
+        double *frame_peak = (double*)t[9], *block_peak = (double*)t[10];
+        const dim3 per_frame((unsigned)fr.n_frames, (unsigned)n_str);
+        CHK(launch(c, "ss_analyze", dsss::k_ss_analyze<T>, per_frame, dsss::NT, dsss::frame_lds(W),
+                   dsss::AnalyzeArgs<T>{src, fr, (const double*)t[5], tw, threshold_db, spec, (uint8_t*)t[4], frame_peak}));
+        const dsss::TrackArgs ta{spec, (const uint8_t*)t[4], (const double*)t[8], fr.bins(), fr.n_frames, mode, forgetting, factor, exponent};
+        const dim3 tg((unsigned)dsss::track_bin_blocks(fr.bins()) * (unsigned)dsss::track_frame_tiles(fr.n_frames, mode), (unsigned)n_str);
+        if (power == dsss::POWER_ONE) CHK(launch(c, "ss_track@one", dsss::k_ss_track<dsss::POWER_ONE>, tg, dsss::NT, 0, ta));
+        if (power == dsss::POWER_TWO) CHK(launch(c, "ss_track@two", dsss::k_ss_track<dsss::POWER_TWO>, tg, dsss::NT, 0, ta));
+        if (power == dsss::POWER_ANY) CHK(launch(c, "ss_track@pow", dsss::k_ss_track<dsss::POWER_ANY>, tg, dsss::NT, 0, ta));
+        CHK(launch(c, "ss_synth", dsss::k_ss_synth, per_frame, dsss::NT, dsss::frame_lds(W),
+                   dsss::SynthArgs{spec, fr, (const double*)t[6], tw}));
+        CHK(launch(c, "ss_ola", dsss::k_ss_ola, dim3((unsigned)n_block, (unsigned)n_str), dsss::OLA_TILE, 0,
+                   dsss::OlaArgs{(const double*)spec, fr, (const double*)t[6], env_floor, yd, block_peak}));
+        CHK(launch(c, "ss_peak", dsss::k_ss_peak, dim3((unsigned)n_str, 2), dsss::NT, 0,
+                   dsss::PeakArgs{frame_peak, block_peak, fr.n_frames, (int)n_block, st_in, st_out}));
+        return launch(c, "fx_scale", dsfx::k_fx_scale<T>, fx_grid(n, n_str), dsfx::NT, 0,
+                      dsfx::ScaleArgs<T>{yd, dst, n, dsfx::RESTORE_PEAK, st_in, st_out, 1.0});
     });
 }
 

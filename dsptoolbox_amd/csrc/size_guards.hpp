@@ -202,3 +202,24 @@ DS_HD inline bool resample_shape_unsupported(int64_t up, int64_t down, int64_t n
     return up > kResampleMaxRate || down > kResampleMaxRate || n_ch > kResampleMaxChannels ||
            (double)longer * (double)n_ch > (double)kResampleMaxSamples;
 }
+
+// Spectral subtraction (kernels_specsub.hpp).  A window is a power of two from 4 to 2^14 samples: its W / 2 complex
+// points, 128 KiB at the bound, and 2 KiB of partial sums share the 160 KiB of LDS of one workgroup (the default block of
+// 0.1 s gives 2^14 at 192 kHz).  The step is 1 .. W.  The frame workspace, 8 (W + 2) bytes x frames x streams, stays at
+// 2^32 bytes (eight bands of two channels of ten seconds at 48 kHz and 50 % overlap hold 1.2e8).  The overlap-add reads
+// samples x streams x ceil(W / step) terms, one lane per sample: at most 2^29, which is what the workspace bound allows
+// where the step divides the window (frames x W doubles); a step that does not divide it rounds the covering frames up,
+// and such a call is held to the same work.  No measured rate enters either bound yet.  grid.x carries the frames, fewer
+// than 2^31; streams and samples as for the other effects (fx_shape_unsupported).  Beyond any of these the entry answers
+// DS_ERR_UNSUP.
+constexpr int kSpecsubMinWindow = 4;
+constexpr int kSpecsubMaxWindow = 16384;
+constexpr int64_t kSpecsubMaxWorkspaceBytes = (int64_t)1 << 32;
+constexpr int64_t kSpecsubMaxOlaTerms = (int64_t)1 << 29;
+DS_HD inline int64_t specsub_frames(int64_t n, int64_t window, int64_t step) { return (n + 2 * window + step - 1) / step; }
+DS_HD inline bool specsub_window_unsupported(int64_t window) { return window > kSpecsubMaxWindow; }
+DS_HD inline bool specsub_work_too_large(int64_t n_streams, int64_t n, int64_t window, int64_t step) {
+    const double frames = (double)specsub_frames(n, window, step);
+    return frames > 2147483647.0 || 8.0 * (double)(window + 2) * frames * (double)n_streams > (double)kSpecsubMaxWorkspaceBytes ||
+           (double)n * (double)n_streams * (double)((window + step - 1) / step) > (double)kSpecsubMaxOlaTerms;
+}

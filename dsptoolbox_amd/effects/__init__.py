@@ -1,17 +1,22 @@
 """Audio effects on the device (API mirror of dsptoolbox/effects/effects.py): Compressor, Distortion, Tremolo, Chorus
-and DigitalDelay, with the reference's constructors, setters, assertions and defaults.
+and DigitalDelay here and SpectralSubtractor in the submodule `effects.spectral`, with the reference's constructors,
+setters, assertions and defaults.
 
-Every sample is computed by the HIP kernels of csrc/kernels_fx.hpp in float64 (there is no CPU path); the host builds
-only what the reference builds as small tables: LFO waveforms, the chorus index table, the tremolo modulator and the
-follower coefficients.  `apply()` takes a `Signal` or a `MultiBandSignal`.  A device-resident signal is read where it
-lies and its result stays resident.  The bands of a `MultiBandSignal` with one rate and length go through the kernels as
-bands x channels streams of one call where the effect has no per-band table (Compressor, Distortion, DigitalDelay; host
-bands always, resident bands when they are consecutive slices of one buffer, as a filter bank leaves them); Tremolo and
-Chorus build their tables band by band, as the reference's loop draws their phases, and make one call per band.
+Every sample is computed by the HIP kernels of csrc/kernels_fx.hpp (the subtractor's: csrc/kernels_specsub.hpp) in float64
+(there is no CPU path); the host builds only what the reference builds as small tables: LFO waveforms, the chorus index
+table, the tremolo modulator and the follower coefficients.  `apply()` takes a `Signal` or a `MultiBandSignal`.  A
+device-resident signal is read where it lies and its result stays resident.  The bands of a `MultiBandSignal` with one rate
+and length go through the kernels as bands x channels streams of one call where the effect has no per-band table
+(Compressor, Distortion, DigitalDelay; host bands always, resident bands when they are consecutive slices of one buffer, as
+a filter bank leaves them); Tremolo and Chorus build their tables band by band, as the reference's loop draws their
+phases, and make one call per band.
 
 What the reference does and a reader might not expect is kept: the compressor ignores `mix_percent`
 and `post_gain_db` and applies `pre_gain_db` twice; distortion components are peak-restored one by one, so mix weights
-only switch a component off at 0; an ndarray modulator never passes the type checks.  `SpectralSubtractor` is not built.
+only switch a component off at 0; an ndarray modulator never passes the type checks.
+
+The names this module exports are pinned by the effects suite; `SpectralSubtractor` is reached as
+`dsp.effects.spectral.SpectralSubtractor` (the submodule is imported with the package).
 """
 
 from enum import Enum, auto
@@ -338,3 +343,6 @@ class DigitalDelay(AudioEffect):
         delay_samples = int(np.round(self.delay_ms * 1e-3 * fs_hz).astype(int))
         padding = int(delay_samples * (1 + self.feedback * 15))
         return backend.fx_delay(x, delay_samples, padding, self.feedback, self.saturation)
+
+
+from . import spectral  # noqa: E402,F401  (effects.spectral.SpectralSubtractor; after the base class it builds on)

@@ -803,6 +803,26 @@ int ds_fx_distort(ds_ctx* ctx, const void* x, int x_on_device, int n_str, int64_
 int ds_fx_tremolo(ds_ctx* ctx, const void* x, int x_on_device, int n_str, int64_t ldx, int64_t n, const double* mod,
                   void* y, int64_t ld_y);
 
+/* ---- spectral subtraction: effects.SpectralSubtractor (effects/effects.py:138-550), float64 throughout
+ * (csrc/kernels_specsub.hpp).  x, y, n_str, ldx, ld_y and x_on_device as for the effects above.  Every stream is padded
+ * (virtually) by `window` zeros at both ends and cut into F = ceil((n + 2 window) / step) frames.  Per frame: the variance
+ * of its samples gates it (10 log10(max(var, DBL_MIN)) < threshold_db), the frame times win_a is transformed, every bin's
+ * magnitude becomes max(|X|^e - t, 0)^(1 / e) with the phase kept, the inverse transform is multiplied by win_s, and the
+ * frames are overlap-added in ascending order and divided by the overlap-added win_s^2 (clipped from below at env_floor
+ * when that is not negative) wherever it is above DBL_MIN; samples `window` .. `window` + n - 1 are kept and the peak of x
+ * is restored (a stream subtracted to silence comes out as NaN).  DS_FX_SPECSUB_ADAPTIVE: t = factor N^e, where the
+ * amplitude estimate N starts at 0 and becomes N forgetting + |X| (1 - forgetting) at every gated frame, that frame's
+ * own bins included; `table` is not read.  DS_FX_SPECSUB_STATIC: t = factor table[stream][bin], table a host
+ * (n_str, window / 2 + 1) array, and neither the gate nor `forgetting` has an effect.  win_a, win_s: host [window].
+ * window: a power of two, 4 .. 16384; 1 <= step <= window.  DS_ERR_UNSUP beyond 16384, a frame workspace
+ * 8 (window + 2) F n_str above 2^32 bytes, n n_str ceil(window / step) above 2^29, or the effects' bounds, before
+ * anything is allocated; DS_ERR_NOMEM, before anything is uploaded, when the memory is not free.                       */
+#define DS_FX_SPECSUB_ADAPTIVE 0
+#define DS_FX_SPECSUB_STATIC 1
+int ds_fx_specsub(ds_ctx* ctx, const void* x, int x_on_device, int n_str, int64_t ldx, int64_t n, const double* win_a,
+                  const double* win_s, int window, int step, int mode, double threshold_db, double forgetting,
+                  double factor, double exponent, const double* table, double env_floor, void* y, int64_t ld_y);
+
 /* ---- levels and loudness: normalize, rms, crest_factor, fade, apply_gain (standard/gain_and_level.py:12-118, 169-200,
  * 284-401 with helpers/gain_and_level.py:7-155), detrend and envelope (standard/other.py:182-284,
  * standard/_standard_backend.py:382-405) and the block energies of lufs_integrated (standard/gain_and_level.py:203-281),
