@@ -36,6 +36,7 @@ NO_SCRATCH = [
     "5dslpc8k_lpc_yw", "5dslpc10k_lpc_burg", "5dslpc10k_levinson", "5dslpc12k_lpc_filter", "5dslpc9k_lpc_ola",
     "6dswarp14k_allpass_tile",
     "k_sfilt_group", "k_sfilt_apply",
+    "k_rtfilt_group", "k_rtfilt_apply", "k_rtfir",
     "k_ism_count", "k_ism_scan", "k_ism_fill", "k_ism_sum", "k_modal_tf",
     "5dslat6k_xmul", "5dslat6k_peak", "5dslat12k_peak_final", "5dslat8k_window", "5dslat6k_near", "5dslat13k_lag_partial",
     "5dslat11k_lag_final", "5dslat11k_lat_phase",

@@ -121,6 +121,12 @@ SIGNATURES = {
                            C.c_void_p, C.c_void_p]),
     "ds_sfilt_dev": (C.c_int, [ctx_p, C.c_void_p, C.c_int, i64, i64, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
                                C.c_void_p, i64, C.c_void_p]),
+    "ds_rtfilt": (C.c_int, [ctx_p, C.c_void_p, C.c_int, i64, C.c_int, C.c_void_p, C.c_int, C.c_int, i64, C.c_void_p,
+                            C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ds_rtfilt_dev": (C.c_int, [ctx_p, C.c_void_p, C.c_int, i64, i64, C.c_int, C.c_void_p, C.c_int, C.c_int, i64,
+                                C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, i64, C.c_void_p]),
+    "ds_rtfir": (C.c_int, [ctx_p, C.c_void_p, C.c_int, i64, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "ds_rtfir_dev": (C.c_int, [ctx_p, C.c_void_p, C.c_int, i64, i64, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, i64]),
     "ds_pair_moments": (C.c_int, [ctx_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, i64, C.c_void_p, C.c_void_p]),
     "ds_pair_moments_dev": (C.c_int, [ctx_p, C.c_void_p, C.c_int, i64, C.c_void_p, C.c_int, i64, i64, C.c_void_p,
                                       C.c_void_p]),

@@ -1354,6 +1354,134 @@ def sfilt_filter_device(x_dev: DevicePlanar, kind: int, coef, d: int, aux: int =
     return (y, zf) if want_zf else y
 
 
+# ---- realtime filters: state-variable, direct form, parallel, state space; the direct FIR sum (ds_rtfilt, ds_rtfir,
+# csrc/kernels_rtfilt.hpp) ---------------------------------------------------------------------------------------------
+RTFILT_MAX_STATES = 64  # state values of one filter on the device (MAX_D of the kernels; DS_ERR_UNSUP above)
+RTFILT_SVF, RTFILT_TDF2, RTFILT_PARALLEL, RTFILT_STATE_SPACE = range(4)
+RTFIR_MAX_TAPS = 4096  # taps of the direct FIR sum (FIR_MAX_TAPS of the kernels)
+RTFIR_MAX_WORK = 2 ** 40  # multiply-adds (samples x channels x taps) of one call of it
+
+
+def rtfilt_coef_count(kind: int, d: int, aux: int) -> int:
+    """Values in the packed coefficient array of a filter (coef_count of the kernels; include/dsptoolbox_amd.h)."""
+    return {RTFILT_SVF: 3, RTFILT_TDF2: 2 * d + 2, RTFILT_PARALLEL: 5 * aux, RTFILT_STATE_SPACE: d * d + 2 * d + 1}[kind]
+
+
+def rtfilt_bands(kind: int) -> int:
+    return 4 if kind == RTFILT_SVF else 1
+
+
+def _rtfir_taps(b, n: int, n_ch: int):
+    """NotImplementedError beyond the FIR sum's bounds; the taps as contiguous float64."""
+    if np.iscomplexobj(b):
+        raise NotImplementedError("structure filters with complex coefficients are not run on the device (its "
+                                  "recursions are real)")
+    b = np.ascontiguousarray(b, dtype=np.float64)
+    assert b.ndim == 1 and len(b) >= 1, "the FIR sum needs a vector of at least one tap"
+    if len(b) > RTFIR_MAX_TAPS:
+        raise NotImplementedError(f"the direct FIR sum holds at most {RTFIR_MAX_TAPS} taps (got {len(b)})")
+    if n * n_ch * len(b) > RTFIR_MAX_WORK:
+        raise NotImplementedError(f"the direct FIR sum runs at most 2^40 multiply-adds (samples x channels x taps) in one "
+                                  f"call (got {n * n_ch * len(b)})")
+    return b
+
+
+def _rtfilt_args(kind: int, coef, d: int, aux: int, delay: int, fir, n: int, n_ch: int, zi, want_zf: bool):
+    """As _sfilt_args: NotImplementedError beyond the kernels' bounds before anything reaches the device; the packed
+    coefficients, the FIR part, zi and the zf to fill as contiguous float64."""
+    if np.iscomplexobj(coef):
+        raise NotImplementedError("structure filters with complex coefficients are not run on the device (its "
+                                  "recursions are real)")
+    if d > RTFILT_MAX_STATES:
+        raise NotImplementedError(f"realtime filters with more than {RTFILT_MAX_STATES} states are not run on the device "
+                                  f"(got {d}): the carry's state vector is one value per lane of a wave")
+    coef = np.ascontiguousarray(coef, dtype=np.float64)
+    assert kind in range(4) and d >= 1 and aux >= 0 and delay >= 0, "unknown filter kind or counts out of range"
+    assert coef.shape == (rtfilt_coef_count(kind, d, aux),), \
+        f"the filter needs {rtfilt_coef_count(kind, d, aux)} packed coefficients, got an array of shape {coef.shape}"
+    if fir is not None:
+        fir = _rtfir_taps(fir, n, n_ch)
+    if zi is not None:
+        zi = np.ascontiguousarray(zi, dtype=np.float64)
+        assert zi.shape == (d, n_ch), "zi must be (states, channels)"
+    zf = np.empty((d, n_ch), dtype=np.float64) if want_zf else None
+    return coef, fir, zi, zf
+
+
+def _host_samples(x):
+    if np.iscomplexobj(x):
+        raise NotImplementedError("complex input samples are not run through the device recursion (its input is real)")
+    xa = np.ascontiguousarray(np.asarray(x, dtype=np.float64))
+    return xa[:, None] if xa.ndim == 1 else xa
+
+
+def rtfilt_filter(x, kind: int, coef, d: int, aux: int = 0, delay: int = 0, fir=None, zi=None, want_zf: bool = False):
+    """x (N, C) float64 through one realtime filter (the recursion in float64 on the device): kind, the packed
+    coefficients, d, aux, the parallel filter's delay and FIR part as include/dsptoolbox_amd.h lays them out.  zi (d, C)
+    gives the initial state (None: zero).  -> y (N, C), for the state-variable filter (4, N, C); or (y, zf) with
+    want_zf."""
+    xa = _host_samples(x)
+    n, n_ch = xa.shape
+    coef, fir, zi, zf = _rtfilt_args(kind, coef, d, aux, delay, fir, n, n_ch, zi, want_zf)
+    nb = rtfilt_bands(kind)
+    y = np.empty((nb, n, n_ch), dtype=np.float64)
+    ctx = get_context()
+    ctx.check(ctx.lib.ds_rtfilt(ctx.handle, _ptr(xa), n_ch, n, int(kind), _ptr(coef), int(d), int(aux), int(delay),
+                                None if fir is None else _ptr(fir), 0 if fir is None else len(fir),
+                                None if zi is None else _ptr(zi), _ptr(y), None if zf is None else _ptr(zf)), "ds_rtfilt")
+    y = y if nb > 1 else y[0]
+    return (y, zf) if want_zf else y
+
+
+def rtfilt_filter_device(x_dev: DevicePlanar, kind: int, coef, d: int, aux: int = 0, delay: int = 0, fir=None, zi=None,
+                         want_zf: bool = False):
+    """rtfilt_filter over device-resident samples (ds_rtfilt_dev): -> a DevicePlanar (a list of four for the
+    state-variable filter), or (that, zf); only the coefficients and the states (zi up, zf down) cross."""
+    ctx = x_dev.ctx
+    n, n_ch = x_dev.n_samples, x_dev.n_ch
+    coef, fir, zi, zf = _rtfilt_args(kind, coef, d, aux, delay, fir, n, n_ch, zi, want_zf)
+    nb = rtfilt_bands(kind)
+    with device_scope(ctx) as dev:
+        d_y = dev.alloc(nb * n_ch * n * 4, result=True)
+        ctx.check(ctx.lib.ds_rtfilt_dev(ctx.handle, C.c_void_p(x_dev.ptr), n_ch, x_dev.ld, n, int(kind), _ptr(coef), int(d),
+                                        int(aux), int(delay), None if fir is None else _ptr(fir),
+                                        0 if fir is None else len(fir), None if zi is None else _ptr(zi),
+                                        C.c_void_p(d_y.ptr), n, None if zf is None else _ptr(zf)), "ds_rtfilt_dev")
+    y = [DevicePlanar(d_y, n_ch, n, n, b * n_ch * n * 4) for b in range(nb)] if nb > 1 else DevicePlanar(d_y, n_ch, n, n, 0)
+    return (y, zf) if want_zf else y
+
+
+def rtfir_filter(x, b, hist=None):
+    """x (N, C) float64 through the direct float64 FIR sum y[n] = b[0] x[n] + sum b[i + 1] x[n - 1 - i] on the device.
+    hist (C, order): the samples before the first one, oldest first (None: zeros).  -> y (N, C)."""
+    xa = _host_samples(x)
+    n, n_ch = xa.shape
+    b = _rtfir_taps(b, n, n_ch)
+    if hist is not None:
+        hist = np.ascontiguousarray(hist, dtype=np.float64)
+        assert hist.shape == (n_ch, len(b) - 1), "hist must be (channels, order)"
+    y = np.empty((n, n_ch), dtype=np.float64)
+    ctx = get_context()
+    ctx.check(ctx.lib.ds_rtfir(ctx.handle, _ptr(xa), n_ch, n, _ptr(b), len(b), None if hist is None else _ptr(hist),
+                               _ptr(y)), "ds_rtfir")
+    return y
+
+
+def rtfir_filter_device(x_dev: DevicePlanar, b, hist=None):
+    """rtfir_filter over device-resident samples (ds_rtfir_dev) -> a DevicePlanar; only the taps and the history cross."""
+    ctx = x_dev.ctx
+    n, n_ch = x_dev.n_samples, x_dev.n_ch
+    b = _rtfir_taps(b, n, n_ch)
+    if hist is not None:
+        hist = np.ascontiguousarray(hist, dtype=np.float64)
+        assert hist.shape == (n_ch, len(b) - 1), "hist must be (channels, order)"
+    with device_scope(ctx) as dev:
+        d_y = dev.alloc(n_ch * n * 4, result=True)
+        ctx.check(ctx.lib.ds_rtfir_dev(ctx.handle, C.c_void_p(x_dev.ptr), n_ch, x_dev.ld, n, _ptr(b), len(b),
+                                       None if hist is None else _ptr(hist), C.c_void_p(d_y.ptr), n), "ds_rtfir_dev")
+    return DevicePlanar(d_y, n_ch, n, n, 0)
+
+
 # ---- sums over a pair of signals (ds_pair_moments, csrc/kernels_dist.hpp) -------------------------------------------
 PAIR_SPAN = 4096  # samples one workgroup of the reduction sums (SPAN of the kernels)
 

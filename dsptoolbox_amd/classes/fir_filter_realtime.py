@@ -181,3 +181,12 @@ class FIRUniformPartitionedMultichannel(FIRUniformPartitioned):
             "block must have shape (block size, channels) with all channels"
         out = self._step(np.ascontiguousarray(block.T, dtype=np.float32), 0)  # every channel in one go
         return out.T.astype(np.float64)
+
+
+def __getattr__(name):
+    """FIRFilter, the reference's time-domain class of this module (fir_filter_realtime.py:11-70), lives in
+    realtime_filters.py with the other sample-by-sample filters (which imports RealtimeFilter from here)."""
+    if name == "FIRFilter":
+        from .realtime_filters import FIRFilter
+        return FIRFilter
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -56,6 +56,7 @@
 #include "kernels_lpc.hpp"
 #include "kernels_warp.hpp"
 #include "kernels_sfilt.hpp"
+#include "kernels_rtfilt.hpp"
 #include "kernels_room.hpp"
 #include "kernels_vqt.hpp"
 #include "kernels_fx.hpp"
@@ -5001,6 +5002,223 @@ extern "C" int ds_sfilt(ds_ctx* c, const double* x, int n_ch, int64_t n_samples,
     return staged(c, {{8, nx, x}, {8, nx, nullptr, y}, {8, nz, zi}, {8, zf ? nz : 0, nullptr, zf}}, [&](void* const* dv) {
         return sfilt_run<double>(c, q, tb, (const double*)dv[0], 1, n_ch, zi ? (const double*)dv[2] : nullptr,
                                  (double*)dv[1], 1, n_ch, zf ? (double*)dv[3] : nullptr);
+    });
+}
+
+// ---- realtime filters: state-variable, transposed direct form II, parallel sections, state space; the direct FIR sum
+// (kernels_rtfilt.hpp) ------------------------------------------------------------------------------------------------
+// The FIR sum's bounds and its padded taps.  Nothing touches the device.
+struct RtFir {
+    const char* who;
+    const double* b;  // host, n_taps values
+    int n_taps;
+    int order() const { return n_taps - 1; }
+    int nt4() const { return rtfilt::fir_nt4(order()); }
+    std::vector<double> padded() const {
+        std::vector<double> t((size_t)nt4(), 0.0);
+        std::copy(b, b + n_taps, t.begin());
+        return t;
+    }
+};
+static int rtfir_check(ds_ctx* c, const RtFir& f, int n_ch, int64_t n_samples) {
+    if (!f.b || f.n_taps < 1) return fail(c, DS_ERR_ARG, f.who, "the FIR part needs at least one tap");
+    if (f.n_taps > rtfilt::FIR_MAX_TAPS)
+        return fail(c, DS_ERR_UNSUP, f.who, "more than 4096 taps is not built in the direct FIR sum");
+    if ((double)n_samples * (double)n_ch * (double)f.n_taps > 1099511627776.0)
+        return fail(c, DS_ERR_UNSUP, f.who, "more than 2^40 multiply-adds (samples x channels x taps) in one call of the "
+                                            "direct FIR sum is not built");
+    if (n_ch > 65535) return fail(c, DS_ERR_UNSUP, f.who, "more than 65535 channels is not built yet");
+    for (int i = 0; i < f.n_taps; ++i)
+        if (!std::isfinite(f.b[i])) return fail(c, DS_ERR_ARG, f.who, "coefficients must be finite");
+    return DS_OK;
+}
+
+// the launch over device buffers; taps [nt4] and hist [n_ch][order] (or nullptr) are device arrays
+template <typename TI, typename TO>
+static int rtfir_launch(ds_ctx* c, const RtFir& f, const TI* x, int64_t sxc, int64_t sxn, int64_t n, int n_ch,
+                        const double* taps, const double* hist, TO* y, int64_t syc, int64_t syn) {
+    const rtfilt::FirArgs<TI, TO> a{x, sxc, sxn, y, syc, syn, n, n_ch, f.order(), f.nt4(), taps, hist};
+    return launch(c, "rtfir", rtfilt::k_rtfir<TI, TO>, dim3((unsigned)((n + rtfilt::FIR_TILE - 1) / rtfilt::FIR_TILE), (unsigned)n_ch),
+                  rtfilt::FIR_NT, rtfilt::fir_lds_bytes(f.nt4()), a);
+}
+
+template <typename T>
+static int rtfir_run(ds_ctx* c, const RtFir& f, const T* x, int64_t sxc, int64_t sxn, int64_t n, int n_ch, const double* hist,
+                     T* y, int64_t syc, int64_t syn) {
+    const std::vector<double> taps = f.padded();
+    void* t[kMaxStaged];
+    CHK(stage(c, &c->ws, &c->ws_bytes, {{8, taps.size(), taps.data()}, {8, hist ? (size_t)n_ch * f.order() : 0, hist}}, t));
+    return rtfir_launch<T, T>(c, f, x, sxc, sxn, n, n_ch, (const double*)t[0], hist && f.order() ? (const double*)t[1] : nullptr,
+                              y, syc, syn);
+}
+
+// device-resident planar float32 samples; b and hist stay host pointers
+extern "C" int ds_rtfir_dev(ds_ctx* c, const float* x, int n_ch, int64_t ldx, int64_t n_samples, const double* b, int n_taps,
+                            const double* hist, float* y, int64_t ld_y) {
+    const RtFir f{"ds_rtfir_dev", b, n_taps};
+    if (!c || !x || !y) return fail(c, DS_ERR_ARG, f.who, "null argument");
+    if (n_ch <= 0 || n_samples <= 0 || ldx < n_samples || ld_y < n_samples) return fail(c, DS_ERR_ARG, f.who, "bad shape");
+    CHK(rtfir_check(c, f, n_ch, n_samples));
+    HIPCHK(c, hipSetDevice(c->device));
+    CHK(mem_check(c, f.who, ((size_t)f.nt4() + (size_t)n_ch * f.order()) * 8 + 2 * 256, 0, 0));
+    return rtfir_run<float>(c, f, x, ldx, 1, n_samples, n_ch, hist, y, ld_y, 1);
+}
+
+// host pointers: x and y (n_samples, n_ch) float64
+extern "C" int ds_rtfir(ds_ctx* c, const double* x, int n_ch, int64_t n_samples, const double* b, int n_taps,
+                        const double* hist, double* y) {
+    const RtFir f{"ds_rtfir", b, n_taps};
+    if (!c || !x || !y) return fail(c, DS_ERR_ARG, f.who, "null argument");
+    if (n_ch <= 0 || n_samples <= 0) return fail(c, DS_ERR_ARG, f.who, "bad shape");
+    CHK(rtfir_check(c, f, n_ch, n_samples));
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t nx = (size_t)n_ch * n_samples;
+    CHK(mem_check(c, f.who, ((size_t)f.nt4() + (size_t)n_ch * f.order()) * 8 + 2 * 256, 2 * nx * 8, 0));
+    return staged(c, {{8, nx, x}, {8, nx, nullptr, y}}, [&](void* const* dv) {
+        return rtfir_run<double>(c, f, (const double*)dv[0], 1, n_ch, n_samples, n_ch, hist, (double*)dv[1], 1, n_ch);
+    });
+}
+
+// Everything ds_rtfilt and ds_rtfilt_dev share.  ldx, ld_y: the _dev entry's row strides (the host entry's rows are dense).
+struct RtfiltCall {
+    const char* who;
+    int n_ch;
+    int64_t n_samples, ldx, ld_y;
+    int kind, d, aux;
+    int64_t delay;
+    const double* coef;  // host, packed as kernels_rtfilt.hpp lays it out
+    const double* fir;   // host, the FIR part of a parallel filter or nullptr
+    int n_fir;
+    int64_t n_groups() const { return (n_samples + rtfilt::G - 1) / rtfilt::G; }
+    size_t n_coef() const { return (size_t)rtfilt::coef_count(kind, d, aux); }
+    RtFir fir_part() const { return RtFir{who, fir, n_fir}; }
+    // coefficients, Phi, Phi^B, group states, the padded taps, the FIR part's float64 samples (held when `base_in_ws`):
+    // six 256-byte aligned pieces
+    size_t ws_bytes(bool base_in_ws) const {
+        return (n_coef() + 2 * (size_t)d * d + (size_t)n_ch * (size_t)n_groups() * d + (fir ? (size_t)fir_part().nt4() : 0) +
+                (fir && base_in_ws ? (size_t)n_ch * (size_t)n_samples : 0)) * 8 + 6 * 256;
+    }
+};
+
+// shape and bounds; nothing touches the device
+static int rtfilt_check(ds_ctx* c, const RtfiltCall& q, const void* x, const void* y) {
+    if (!c || !x || !y || !q.coef) return fail(c, DS_ERR_ARG, q.who, "null argument");
+    if (q.n_ch <= 0 || q.n_samples <= 0 || q.d <= 0 || q.ldx < q.n_samples || q.ld_y < q.n_samples)
+        return fail(c, DS_ERR_ARG, q.who, "bad shape");
+    if (q.kind < 0 || q.kind >= rtfilt::N_KINDS) return fail(c, DS_ERR_ARG, q.who, "unknown filter kind");
+    if (q.d > rtfilt::MAX_D)
+        return fail(c, DS_ERR_UNSUP, q.who, "more than 64 states in one filter is not built (the carry's state vector is "
+                                            "one value per lane of a wave)");
+    if ((q.kind == rtfilt::SVF && q.d != 2) || (q.kind == rtfilt::PARALLEL && (q.aux < 1 || q.d != 2 * q.aux)) ||
+        (q.kind != rtfilt::PARALLEL && (q.aux != 0 || q.delay != 0 || q.fir)) || q.delay < 0)
+        return fail(c, DS_ERR_ARG, q.who, "the state count, delay or FIR part does not fit the filter kind");
+    CHK(carry_limits(c, q.who, q.n_ch, q.n_samples, "more than 65535 channels is not built yet"));
+    for (size_t i = 0; i < q.n_coef(); ++i)
+        if (!std::isfinite(q.coef[i])) return fail(c, DS_ERR_ARG, q.who, "coefficients must be finite");
+    if (q.fir) CHK(rtfir_check(c, q.fir_part(), q.n_ch, q.n_samples));
+    if (rtfilt::lds_bytes(q.kind, q.d, true) > 160 * 1024)
+        return fail(c, DS_ERR_UNSUP, q.who, "the filter's tiles and states do not fit the 160 KB of local memory");
+    return DS_OK;
+}
+
+// Host side of the carry, as sfilt_tables: A's column j is one zero-input step of the filter's own step function from the
+// unit state e_j; Phi = A^L and Phi^B by squaring; the carry gain is the largest magnitude in the two.
+static int rtfilt_tables(ds_ctx* c, const RtfiltCall& q, SfiltTables& tb) {
+    const int d = q.d;
+    std::vector<double> a((size_t)d * d, 0.0), st((size_t)d), nx((size_t)d);
+    for (int j = 0; j < d; ++j) {
+        std::fill(st.begin(), st.end(), 0.0);
+        st[j] = 1.0;
+        rtfilt::step_state_only(q.kind, 0.0, st.data(), nx.data(), q.coef, d, q.aux);
+        for (int i = 0; i < d; ++i) a[(size_t)i * d + j] = st[i];
+    }
+    carry::carry_powers(a, d, tb.phi, tb.phig);
+    double gain = 0.0;
+    for (const std::vector<double>* m : {&tb.phi, &tb.phig})
+        for (double v : *m) gain = std::isfinite(v) ? std::max(gain, std::fabs(v)) : INFINITY;
+    if (!(gain <= rtfilt::max_gain(q.kind)))
+        return fail(c, DS_ERR_UNSUP, q.who, "the recursion's carry gain (largest magnitude in Phi = A^32 and Phi^64) is "
+                                            "above the limit: an unstable or too ill-conditioned filter is not run "
+                                            "time-parallel");
+    return DS_OK;
+}
+
+// the FIR part (if any) and the three passes over device buffers of either sample type; y element (b, c, n) at
+// y[b syb + c syc + n syn]; zi, zf: device arrays [D][n_ch] or nullptr.  The FIR part's samples go to a float64 piece of
+// c->ws, or, when y is float64 itself (y_as_base), straight into y, where the apply pass adds the sections to them.
+template <typename T>
+static int rtfilt_run(ds_ctx* c, const RtfiltCall& q, const SfiltTables& tb, const T* x, int64_t sxc, int64_t sxn,
+                      const double* zi, T* y, int64_t syb, int64_t syc, int64_t syn, double* zf, bool y_as_base) {
+    const int d = q.d, n_ch = q.n_ch;
+    const int64_t n = q.n_samples, n_groups = q.n_groups();
+    const RtFir f = q.fir_part();
+    const std::vector<double> taps = q.fir ? f.padded() : std::vector<double>();
+    void* t[kMaxStaged];
+    CHK(stage(c, &c->ws, &c->ws_bytes, {{8, q.n_coef(), q.coef}, {8, tb.phi.size(), tb.phi.data()},
+                                        {8, tb.phig.size(), tb.phig.data()}, {8, (size_t)n_ch * n_groups * d},
+                                        {8, taps.size(), taps.data()},
+                                        {8, q.fir && !y_as_base ? (size_t)n_ch * (size_t)n : 0}}, t));
+    const double *dcoef = (const double*)t[0], *dphi = (const double*)t[1], *dphig = (const double*)t[2];
+    double* gst = (double*)t[3];
+    const double* base = nullptr;
+    int64_t sbc = 0, sbn = 0;
+    if (q.fir) {
+        if constexpr (std::is_same<T, double>::value) {
+            if (y_as_base) {
+                CHK((rtfir_launch<T, double>(c, f, x, sxc, sxn, n, n_ch, (const double*)t[4], nullptr, y, syc, syn)));
+                base = y, sbc = syc, sbn = syn;
+            }
+        }
+        if (!base) {
+            CHK((rtfir_launch<T, double>(c, f, x, sxc, sxn, n, n_ch, (const double*)t[4], nullptr, (double*)t[5], n, 1)));
+            base = (const double*)t[5], sbc = n, sbn = 1;
+        }
+    }
+    rtfilt::Args<T> a{x, sxc, sxn, y, syb, syc, syn, n, n_ch, q.kind, d, q.aux, n_groups, q.delay, base, sbc, sbn,
+                      dcoef, dphi, dphig, gst, zi, zf};
+    if (n_groups > 1)
+        CHK(launch(c, "rtfilt_group", rtfilt::k_rtfilt_group<T>, dim3((unsigned)(n_groups - 1), (unsigned)n_ch), rtfilt::B,
+                   rtfilt::lds_bytes(q.kind, d, false), a));
+    carry::CarryArgs ca{dphig, gst, zi, n_groups, n_ch, d};  // one filter: zi [D][n_ch]
+    CHK(launch(c, "rtfilt_carry", carry::k_block_carry, dim3((unsigned)n_ch), rtfilt::B, sizeof(double) * d * d, ca));
+    return launch(c, "rtfilt_apply", rtfilt::k_rtfilt_apply<T>, dim3((unsigned)n_groups, (unsigned)n_ch), rtfilt::B,
+                  rtfilt::lds_bytes(q.kind, d, true), a);
+}
+
+// device-resident planar float32 samples; coef, fir, zi and zf stay host pointers (zi / zf [D][n_ch] cross through c->io);
+// band b of channel c at y[(b n_ch + c) ld_y + n]
+extern "C" int ds_rtfilt_dev(ds_ctx* c, const float* x, int n_ch, int64_t ldx, int64_t n_samples, int kind,
+                             const double* coef, int d, int aux, int64_t delay, const double* fir, int n_fir,
+                             const double* zi, float* y, int64_t ld_y, double* zf) {
+    const RtfiltCall q{"ds_rtfilt_dev", n_ch, n_samples, ldx, ld_y, kind, d, aux, delay, coef, n_fir > 0 ? fir : nullptr, n_fir};
+    if (n_fir > 0 && !fir) return fail(c, DS_ERR_ARG, q.who, "null argument");
+    CHK(rtfilt_check(c, q, x, y));
+    SfiltTables tb;
+    CHK(rtfilt_tables(c, q, tb));
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t nz = (size_t)d * n_ch;
+    CHK(mem_check(c, q.who, q.ws_bytes(true), 2 * nz * 8, 0));
+    return staged(c, {{8, nz, zi}, {8, zf ? nz : 0, nullptr, zf}}, [&](void* const* dv) {
+        return rtfilt_run<float>(c, q, tb, x, ldx, 1, zi ? (const double*)dv[0] : nullptr, y, (int64_t)n_ch * ld_y, ld_y, 1,
+                                 zf ? (double*)dv[1] : nullptr, false);
+    });
+}
+
+// host pointers in the reference's layouts: x (n_samples, n_ch) and y (bands, n_samples, n_ch) float64, bands = 4 for the
+// state-variable filter and 1 otherwise
+extern "C" int ds_rtfilt(ds_ctx* c, const double* x, int n_ch, int64_t n_samples, int kind, const double* coef, int d,
+                         int aux, int64_t delay, const double* fir, int n_fir, const double* zi, double* y, double* zf) {
+    const RtfiltCall q{"ds_rtfilt", n_ch, n_samples, n_samples, n_samples, kind, d, aux, delay, coef, n_fir > 0 ? fir : nullptr, n_fir};
+    if (n_fir > 0 && !fir) return fail(c, DS_ERR_ARG, q.who, "null argument");
+    CHK(rtfilt_check(c, q, x, y));
+    SfiltTables tb;
+    CHK(rtfilt_tables(c, q, tb));
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t nx = (size_t)n_ch * n_samples, ny = nx * rtfilt::n_bands(kind), nz = (size_t)d * n_ch;
+    CHK(mem_check(c, q.who, q.ws_bytes(false), (nx + ny + 2 * nz) * 8, 0));
+    return staged(c, {{8, nx, x}, {8, ny, nullptr, y}, {8, nz, zi}, {8, zf ? nz : 0, nullptr, zf}}, [&](void* const* dv) {
+        return rtfilt_run<double>(c, q, tb, (const double*)dv[0], 1, n_ch, zi ? (const double*)dv[2] : nullptr,
+                                  (double*)dv[1], (int64_t)nx, 1, n_ch, zf ? (double*)dv[3] : nullptr, true);
     });
 }
 

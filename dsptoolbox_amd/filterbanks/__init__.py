@@ -4,7 +4,9 @@ Butterworth bank (filterbanks/filterbanks.py:336-413) on the device IIR kernels,
 (filterbanks/filterbanks.py:217-303, filterbanks/_filterbank.py:664-701) on the complex-coefficient IIR kernels, and the
 structure filters the reference exports here (filterbanks/__init__.py:75-86) -- LatticeLadderFilter, WarpedFIR, WarpedIIR,
 KautzFilter -- on the structure-filter kernels, and the Linkwitz-Riley crossover bank (filterbanks/filterbanks.py:37-78,
-filterbanks/_filterbank.py:45-405) on the device IIR kernels."""
+filterbanks/_filterbank.py:45-405) on the device IIR kernels, and the realtime filters -- StateVariableFilter, ParallelFilter,
+IIRFilter, FIRFilter, StateSpaceFilter, FilterChain on the realtime-filter kernels (classes/realtime_filters.py), and the
+host-only ExponentialAverageFilter."""
 
 import numpy as np
 
@@ -12,6 +14,8 @@ from ..classes.filter import Filter
 from ..classes.filterbank import FilterBank
 from ..classes.fir_filter_realtime import (FIRFilterOverlapSave, FIRUniformPartitioned,
                                            FIRUniformPartitionedMultichannel)
+from ..classes.realtime_filters import (ExponentialAverageFilter, FilterChain, FIRFilter, IIRFilter, ParallelFilter,
+                                        StateSpaceFilter, StateVariableFilter)
 from ..classes.structure_filters import KautzFilter, LatticeLadderFilter, WarpedFIR, WarpedIIR
 from ..standard.enums import FilterCoefficientsType, FilterPassType, IirDesignMethod
 from ..tools import erb_frequencies, fractional_octave_frequencies
@@ -104,4 +108,5 @@ def auditory_filters_gammatone(frequency_range_hz=[20, 20000], resolution: float
 
 __all__ = ["FIRFilterOverlapSave", "FIRUniformPartitioned", "FIRUniformPartitionedMultichannel",
            "fractional_octave_bands", "auditory_filters_gammatone", "GammaToneFilterBank", "LatticeLadderFilter", "WarpedFIR",
-           "WarpedIIR", "KautzFilter", "linkwitz_riley_crossovers", "LRFilterBank"]
+           "WarpedIIR", "KautzFilter", "linkwitz_riley_crossovers", "LRFilterBank", "StateSpaceFilter", "IIRFilter",
+           "FIRFilter", "StateVariableFilter", "ParallelFilter", "FilterChain", "ExponentialAverageFilter"]

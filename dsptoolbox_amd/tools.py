@@ -8,6 +8,13 @@ import numpy as np
 from ._db import from_db, to_db  # noqa: F401
 from .backend import fractional_octave_smoothing  # noqa: F401
 
+
+def get_smoothing_factor_ema(relaxation_time_s: float, sampling_rate_hz: int, accuracy: float = 0.95):
+    """alpha of the exponential moving average y[n] = alpha x[n] + (1 - alpha) y[n - 1] whose step response is within
+    `accuracy` (in ]0, 1[) of 1 after the relaxation time (dsptoolbox/helpers/smoothing.py:132-166)."""
+    from .classes.realtime_filters import _get_smoothing_factor_ema
+    return _get_smoothing_factor_ema(relaxation_time_s, sampling_rate_hz, accuracy)
+
 # base-ten octave ratio and reference frequency of IEC 61260-1 (5.2, 5.4)
 _G = 10 ** (3 / 10)
 _F_REF = 1000.0

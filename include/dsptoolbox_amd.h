@@ -425,6 +425,45 @@ int ds_sfilt(ds_ctx* ctx, const double* x, int n_ch, int64_t n_samples, int kind
 int ds_sfilt_dev(ds_ctx* ctx, const float* x_dev, int n_ch, int64_t ldx, int64_t n_samples, int kind, const double* coef,
                  int d, int aux, const double* zi, float* y_dev, int64_t ld_y, double* zf);
 
+/* ---- realtime filters (csrc/kernels_rtfilt.hpp): the sample loops of the reference's StateVariableFilter
+ * (classes/sv_filter.py), IIRFilter (classes/iir_filter_realtime.py), ParallelFilter (classes/parallel_filter.py) and
+ * StateSpaceFilter (classes/state_space_filter.py) as float64 recursions over d <= 64 real state values, time-parallel
+ * with the carry of ds_iir_sos.  kind and the packed float64 coefficient array coef (host pointer), `aux` a count beside d:
+ *   DS_RTFILT_SVF          g, resonance, 1 / (1 + resonance g + g^2); d = 2, aux = 0     state: the reference's (2, channels)
+ *   DS_RTFILT_TDF2         b[d + 1], a[d + 1], zero-padded to the order d, a[0] = 1       state: (order, channels)
+ *   DS_RTFILT_PARALLEL     per section b0 b1 b2 a1 a2 (a0 = 1): aux sections, d = 2 aux   state: sosfilt's (z1, z2) per section
+ *   DS_RTFILT_STATE_SPACE  A[d][d] row-major, B[d], C[d], D                               state: StateSpaceFilter.x (d, channels)
+ * The state-variable filter writes FOUR bands (low, high, band, all-pass), the others one.  A parallel filter's sections
+ * all read the input delayed by `delay` samples (zeros in front) and their outputs are added, in section order, to the
+ * FIR part's sample sum_i fir[i] x[n - i] (fir NULL or n_fir = 0: to zero); delay, fir and aux are 0 / NULL for the other
+ * kinds (DS_ERR_ARG otherwise).  zi / zf [d][n_ch] float64, HOST pointers on both entries: the initial state (NULL:
+ * zero) and the state after the last sample (NULL: not wanted).  Bounds: d <= 64, n_ch <= 65535 (DS_ERR_UNSUP above); the
+ * largest magnitude in Phi = A^32 and Phi^64 (A the zero-input state transition) at most 30 for DS_RTFILT_TDF2 and
+ * DS_RTFILT_STATE_SPACE and 1e6 for the other two (MAX_GAIN_COMPANION, MAX_GAIN of the kernels), DS_ERR_UNSUP above
+ * (DESIGN section 26); the FIR part's bounds are ds_rtfir's; DS_ERR_NOMEM, before anything is uploaded, when the device
+ * has not the memory free.
+ * ds_rtfilt: x (n_samples, n_ch) and y (bands, n_samples, n_ch) float64 host arrays.
+ * ds_rtfilt_dev: device-resident planar float32 samples x_dev[c*ldx + n] -> y_dev[(band*n_ch + c)*ld_y + n]; the
+ * recursion itself is float64 on both entries.
+ *
+ * ds_rtfir / ds_rtfir_dev: the direct float64 FIR sum y[n] = b[0] x[n] + sum_{i < order} b[i + 1] x[n - 1 - i], order =
+ * n_taps - 1, one fused multiply-add per term in that order (two calls give the same bits).  hist [n_ch][order] float64,
+ * host pointer: the samples before the first one, x[-order] first (NULL: zeros).  Bounds (DS_ERR_UNSUP above): n_taps <=
+ * 4096, n_samples * n_ch * n_taps <= 2^40, n_ch <= 65535.  Layouts as ds_rtfilt / ds_rtfilt_dev with one band.         */
+#define DS_RTFILT_SVF 0
+#define DS_RTFILT_TDF2 1
+#define DS_RTFILT_PARALLEL 2
+#define DS_RTFILT_STATE_SPACE 3
+int ds_rtfilt(ds_ctx* ctx, const double* x, int n_ch, int64_t n_samples, int kind, const double* coef, int d, int aux,
+              int64_t delay, const double* fir, int n_fir, const double* zi, double* y, double* zf);
+int ds_rtfilt_dev(ds_ctx* ctx, const float* x_dev, int n_ch, int64_t ldx, int64_t n_samples, int kind, const double* coef,
+                  int d, int aux, int64_t delay, const double* fir, int n_fir, const double* zi, float* y_dev, int64_t ld_y,
+                  double* zf);
+int ds_rtfir(ds_ctx* ctx, const double* x, int n_ch, int64_t n_samples, const double* b, int n_taps, const double* hist,
+             double* y);
+int ds_rtfir_dev(ds_ctx* ctx, const float* x_dev, int n_ch, int64_t ldx, int64_t n_samples, const double* b, int n_taps,
+                 const double* hist, float* y_dev, int64_t ld_y);
+
 /* ---- per-channel sums over a pair of signals, float64, fixed summation order (csrc/kernels_dist.hpp): the device part
  * of distances.snr and distances.si_sdr (distances/_distances.py:64-101).  par (n_ch, 3) float64, host pointer, holds
  * alpha, mu_a, mu_b per channel (NULL: zeros); out (n_ch, 6) float64, host pointer, receives
