@@ -54,7 +54,7 @@ struct RowView {
     int64_t col_stride, row_stride, rot, n_mod;
     __device__ __forceinline__ double at(int c, int64_t k) const {
         int64_t j = k + rot;
-        if (j >= n_mod) j -= n_mod;  // k < n_mod and rot < n_mod
+        if (j >= n_mod) j -= n_mod;  // k < n_mod and rot <= n_mod (Na = 1: rot == n_mod), so j < 2 n_mod: one suffices
         return v[(int64_t)c * col_stride + j * row_stride];
     }
 };
